@@ -4,14 +4,20 @@
 A "step" = one pass of the hot path over one batch of synthetic pairs:
 predict5(training=True) -> every loss term of training_step (loss_mode 1: recovery
 chamfer + comp + EMD(NxN) + CE x2 + boundary chamfer x2, EMD x4 computed as the
-reference does) -> backward -> gradient all-reduce (N>1) -> Adam + StepLR.
+reference does) -> backward -> gradient all-reduce (N>1) -> Adam + StepLR.  The steps train the model from its seeded
+initial state; the last timed step starts from that state again (state_restorer), so that it has the same inputs and
+computes the same outputs in every run.
 Workload = BASELINE.json configs[1]: N=2048 points, 64 pairs per GPU, fp32.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR    # + the last timed step's outputs as DIR/*.npy
+    python bench.py --full                                               # + everything below
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  Everything a reader of the record needs is a SCALAR inside
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the headline (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, the workload in `config`).  With `--full`, rank 0 then runs the
+instrumented passes, the other workloads and the CPU baseline; everything a reader of that record needs is a SCALAR inside
 `roofline`, `config` and `cpu_baseline` (nested tables follow as extra top-level keys):
 
   roofline       the DOMINANT kernel = the kernel with the largest EXCLUSIVE device time per step among those with a byte / flop
@@ -47,6 +53,9 @@ MFMA_BF16_PEAK_TFLOPS = 2500.0  # dense bf16 matrix rate (v_mfma_f32_32x32x16_bf
 # Every hot matrix-core kernel issues SIX bf16 MFMAs per fp32 product (bf16x3 split precision: fp32-GEMM accuracy),
 # so the ceiling of its fp32-equivalent rate is the bf16 pipe / 6:
 MFMA_X3_PEAK_TFLOPS = MFMA_BF16_PEAK_TFLOPS / 6.0
+# --dump-outputs: parameters and gradients are sampled at this many positions each (2 x 16 MB of float32; the model has 8 M
+# parameters at N = 2048), so that the dump stays under 64 MB at every size
+DUMP_SAMPLE = 1 << 22
 
 
 class Cfg:
@@ -402,6 +411,48 @@ def profile_avg_us(rows, kernel):
     return (sum(r["avg_us"] * r["calls"] for r in hit) / calls) if calls else None
 
 
+def state_restorer(runner, model):
+    """-> restore(): puts the training state as it is now back on the device, enqueued on the current stream: the parameters,
+    both Adam moments and the step count (engine.TrainStep's flat buffers) and the BatchNorm running statistics.
+    The last timed step starts with it, so that its inputs are the same in every run.  The state after a chain of optimiser
+    steps is not: the weight gradients end in fp32 atomics, and Adam turns their rounding noise into different trajectories
+    within a few steps.  The steps before it keep training, as the kernels' times depend on how far
+    the model has trained (steps right after the initialisation are slower)."""
+    opt = runner.opt
+    saved = [(t, t.detach().clone()) for t in (opt.flat, opt.exp_avg, opt.exp_avg_sq)]
+    saved += [(b, b.detach().clone()) for b in model.buffers()]
+    t0 = opt.t
+
+    def restore():
+        with torch.no_grad():
+            for dst, src in saved:
+                dst.copy_(src)
+        opt.t = t0
+    return restore
+
+
+def dump_outputs(out_dir, model, loss):
+    """What a caller of the timed step holds after its last step, as float32 .npy files under `out_dir`: `loss`, the
+    parameters after Adam (`params`), their gradients (`grads`) and the BatchNorm running statistics (`bn_running_stats`).
+    Parameters and gradients are concatenated in `model.parameters()` order; above DUMP_SAMPLE elements both keep the same
+    positions, drawn once from a fixed seed, so that two builds compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for p in model.parameters() if p.requires_grad]
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])
+    n = flat_p.numel()
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+        sel = torch.from_numpy(idx).to(flat_p.device)
+        flat_p, flat_g = flat_p[sel], flat_g[sel]
+    stats = [b.detach().reshape(-1) for b in model.buffers() if b.is_floating_point()]
+    arrays = {"loss": loss.detach().reshape(1), "params": flat_p, "grads": flat_g,
+              "bn_running_stats": torch.cat(stats) if stats else torch.zeros(0)}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def kernel_pass(model, batch, lr, two_streams, steps):
     """`steps` training steps with the library's per-kernel timer on -> {kernel: (launches per step, ms per step)}."""
     from puzzlenet_amd import engine, ops
@@ -430,9 +481,15 @@ def main():
     ap.add_argument("--one-stream", action="store_true",
                     help="the two encoders one after the other on ONE stream in the timed loop too: what the committed "
                          "one-stream kernel summary is collected with (a kernel's duration is then its own)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the instrumented passes (roofline, stages, per-kernel tables), BASELINE "
+                         "configs[3] / [4], the from-raw steps and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="skip BASELINE configs[3] / [4] at their per-GPU share (5 + 10 steps each) and the from-raw steps")
+                    help="with --full: skip BASELINE configs[3] / [4] at their per-GPU share (5 + 10 steps each) and the "
+                         "from-raw steps")
     ap.add_argument("--cpu-pairs", type=int, default=8)
     ap.add_argument("--cpu-iters", type=int, default=3)
     args = ap.parse_args()
@@ -460,6 +517,7 @@ def main():
     torch.manual_seed(1000 + rank)                                        # FPS start indices (pointnet_util.py:65)
 
     runner = engine.TrainStep(model, batch, cfg.lr, world=world)
+    restore = state_restorer(runner, model)                               # the last timed step starts from this state
     if rank == 0:
         print("[bench] runner ready", file=sys.stderr, flush=True)
 
@@ -473,7 +531,11 @@ def main():
         runner.step()
     fence()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if i == args.steps - 1:
+            if args.full:
+                trained = state_restorer(runner, model)      # --full's passes below continue from the trained state
+            restore()
         loss = runner.step()
     t_enq = time.perf_counter() - t0      # the host has enqueued the last step (nothing in a step synchronises)
     fence()
@@ -487,11 +549,37 @@ def main():
     if rank == 0:
         print(f"[bench] gpu: {dt / args.steps * 1e3:.2f} ms/step, {world * args.batch * args.steps / dt:.1f} pairs/s",
               file=sys.stderr, flush=True)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, model, loss)
     if rank != 0:
         dist.barrier()
         dist.destroy_process_group()
         return
 
+    cfg_name = 1 if (B, N) == (64, 2048) else ('4' if N == 8192 else '3' if N == 4096 else '-')
+    out = {
+        "metric": f"point-cloud pairs/sec (fwd+bwd) at N={N}, B={B}; FPS/kNN idx bit-exact",
+        "value": world * B * args.steps / dt, "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32" if args.attn == "f32" else "f32 (attention contractions bf16)",
+        "data": "synthetic",
+        "config": {"workload": f"BASELINE configs[{cfg_name}]: N={N}, {B} pairs/GPU, fp32 train step (predict5 + 4x EMD + bwd + Adam)",
+                   "global_batch": world * B, "points": N, "parallelism": f"dp{world}",
+                   "encoder_streams": 1 if args.one_stream else 2,
+                   "matrix_core_path": "bf16x3 split precision (fp32 results; six bf16 MFMAs per product)",
+                   "attention": args.attn, "build_id": build_id(),
+                   # host time to ENQUEUE a step against the step itself: close to 1 = the host is the bottleneck
+                   "host_enqueue_ms_per_step": t_enq / args.steps * 1e3, "host_enqueue_over_step": t_enq / dt},
+        "loss": loss_val,
+    }
+    if not args.full:
+        print(json.dumps(out))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    trained()
     # ------------------------------------------------------------------ instrumented passes (rank 0, after the timed region)
     # (a) entry points, one stream: a HIP event pair around every C-ABI call -> `stages`, flops per entry point, EMD counters
     prof_steps = 3
@@ -677,21 +765,9 @@ def main():
 
     stages = {k: {"launches_per_step": n / prof_steps, "ms_per_step": ms / prof_steps} for k, (n, ms) in sorted(kern.items())}
     stages_api = {k: {"launches": n, "ms": ms} for k, (n, ms) in sorted(kern_api.items())}
-    cfg_name = 1 if (B, N) == (64, 2048) else ('4' if N == 8192 else '3' if N == 4096 else '-')
-    out = {
-        "metric": f"point-cloud pairs/sec (fwd+bwd) at N={N}, B={B}; FPS/kNN idx bit-exact",
-        "value": world * B * args.steps / dt, "unit": "pairs/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32" if args.attn == "f32" else "f32 (attention contractions bf16)",
-        "data": "synthetic",
-        "config": {"workload": f"BASELINE configs[{cfg_name}]: N={N}, {B} pairs/GPU, fp32 train step (predict5 + 4x EMD + bwd + Adam)",
-                   "global_batch": world * B, "points": N, "parallelism": f"dp{world}",
-                   "encoder_streams": 1 if args.one_stream else 2,
-                   "matrix_core_path": "bf16x3 split precision (fp32 results; six bf16 MFMAs per product)",
-                   "attention": args.attn, "build_id": build_id(),
-                   # host time to ENQUEUE a step against the step itself: close to 1 = this box's host is the bottleneck
-                   "host_enqueue_ms_per_step": t_enq / args.steps * 1e3, "host_enqueue_over_step": t_enq / dt,
-                   "library_launches_per_step": sum(n for n, _ in kt1.values())},
+    out["config"]["library_launches_per_step"] = sum(n for n, _ in kt1.values())
+    out.pop("loss")
+    out.update({
         "roofline": roofline,
         "roofline_knn_group": roofline_knn_group,
         "roofline_emd": roofline_emd,
@@ -700,7 +776,7 @@ def main():
         "stages": stages,
         "stages_sample_and_group_dropin": stages_api,
         "loss": loss_val,
-    }
+    })
     if not args.no_other_workloads and world == 1 and (B, N, args.attn) == (64, 2048, "f32") and not args.one_stream:
         # BASELINE configs[3] and [4] (1-GPU shares) and the step fed from raw clouds, measured by whoever runs this line:
         # same process, after the headline

@@ -49,3 +49,28 @@ def test_committed_profiles_carry_their_sidecars():
         assert avg and avg > 0
         with open(base + ".csv", newline="") as f:
             assert {"Name", "Calls", "AverageNs", "Percentage"} <= set(next(csv.DictReader(f)))
+
+
+def test_dump_outputs_sample_is_fixed(tmp_path, monkeypatch):
+    """--dump-outputs: float32 files; above DUMP_SAMPLE elements parameters and gradients keep the same seeded positions
+    in every run."""
+    import numpy as np
+    import torch
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(16, 8), torch.nn.BatchNorm1d(8))
+    for p in model.parameters():
+        p.grad = 2.0 * p.detach().clone()
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 100)
+    dirs = [os.path.join(tmp_path, d) for d in ("a", "b")]
+    for d in dirs:
+        bench.dump_outputs(d, model, torch.tensor(1.5))
+    loaded = [{n: np.load(os.path.join(d, n + ".npy")) for n in ("loss", "params", "grads", "bn_running_stats")}
+              for d in dirs]
+    a = loaded[0]
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["loss"].tolist() == [1.5] and a["params"].shape == (100,) and a["bn_running_stats"].shape == (16,)
+    assert np.array_equal(a["grads"], 2.0 * a["params"])            # same positions in both
+    flat = torch.cat([p.detach().reshape(-1) for p in model.parameters()]).numpy()
+    assert np.isin(a["params"], flat).all()
+    for k in a:
+        assert np.array_equal(a[k], loaded[1][k])

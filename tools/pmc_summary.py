@@ -5,8 +5,8 @@ roofline objects (profiles/<round>_pmc_traffic.json).
     python tools/pmc_summary.py <fetch_dir> <write_dir> <out.json> [--batch 64 --points 2048]
 
 <fetch_dir> / <write_dir> are the -d directories of two SEPARATE passes of the same command:
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d <fetch_dir> -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d <write_dir> -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d <fetch_dir> -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d <write_dir> -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
 Counters are in KB.  gfx950: FETCH_SIZE tallies 64 B per 128-B request of a wide streaming read, so
 bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024 (MI355X_MICROARCH.md, HBM section).  The summary carries the hash of the
 kernel sources it was taken on (bench.build_id): bench.py reports these bytes only for that build.
