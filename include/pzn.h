@@ -333,6 +333,15 @@ int pzn_sa_level_fwd_packed_f32(const float* Pp, const float* Q, const int64_t* 
  * order, so dP is the same bit for bit in every run.  workspace: pzn_sa_level_bwd_pt_workspace_bytes(B, S, C2) bytes,
  * 16-byte aligned.  PZN_EUNSUPPORTED for C1 % 128 != 0 or C2 not in {64, 128, 256}. */
 size_t pzn_sa_level_bwd_pt_workspace_bytes(int B, int S, int C2);
+/* The weight-gradient pass of pzn_sa_level_bwd_pt_f32 on its own (csrc/poolbwd.hip): dW2[C2, C1] += the sparse dy^T h,
+ * db2[C2] += its column sums (both ADDED to), with the workgroups' partial tiles summed in a fixed order.  The rows are
+ * h[G*32, C1] (Pp, Q, idx NULL), or h == NULL and they are regenerated as relu(Pp[(g / S) * N + idx[g*32+k], :] + Q[g, :]).
+ * workspace: pzn_pool_wgrad_workspace_bytes(G, C1, C2) bytes, 16-byte aligned.  PZN_EUNSUPPORTED for C1 % 128 != 0 or C2 not
+ * in {64, 128, 256}. */
+size_t pzn_pool_wgrad_workspace_bytes(int G, int C1, int C2);
+int pzn_pool_wgrad_f32(const float* dout, const int32_t* argmax, const float* out, const float* h, const float* Pp,
+                       const float* Q, const int64_t* idx, int N, int S, int G, int C1, int C2, float* dW2, float* db2,
+                       void* workspace, pzn_stream_t stream);
 int pzn_sa_level_bwd_pt_f32(const float* dout, const int32_t* argmax, const float* out, const float* W2,
                             const float* Pp, const float* Q, const int64_t* idx, const float* xyz, const float* new_xyz,
                             const int32_t* off, const int32_t* rows, const int32_t* pts, int B, int N, int S, int D, int C1,

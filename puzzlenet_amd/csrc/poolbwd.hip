@@ -11,10 +11,12 @@
 //
 // This file: the WEIGHT-gradient pass, walking groups g = blockIdx.x, += gridDim.x over a 128-column slice (blockIdx.y) of
 // the C1 hidden columns, lane l holding columns 2l, 2l+1:
-//  * pool_wgrad_kernel: 16 (or 8) wavefronts, wave w owns CPW = C2/16 channels whose dW accumulators stay in registers
-//    for the whole walk.  Per group the 32 x 128 tile of h is staged in LDS (double-buffered, next tile
-//    prefetched into registers), the wave's CPW (argmax, gradient) pairs are read as one vector and
-//    broadcast with v_readlane, then per channel: one ds_read_b64 of the arg-max row + one packed fma.
+//  * pool_wgrad_kernel (rows h in memory: the grouped-row composition): 16 (or 8) wavefronts, wave w owns CPW = C2/16
+//    channels whose dW accumulators stay in registers for the whole walk.  Per group the 32 x 128 tile of h is staged in
+//    LDS (double-buffered, next tile prefetched into registers), the wave's CPW (argmax, gradient) pairs are read as one
+//    vector and broadcast with v_readlane, then per channel: one ds_read_b64 of the arg-max row + one packed fma.
+//  * pool_wgrad_regen_kernel (rows regenerated as relu(P'[idx] + Q): the per-point levels): the same walk and hit loop,
+//    the raw rows staged by LDS-DMA into a ring of two batches of four tiles, one barrier per batch (below).
 // The input-gradient side of the encoder's levels is the walk by point of csrc/sapool.hip (the rows' gradient is never in
 // memory); the grouped-row composition (pzn_sharedmlp_max_bwd_f32, h in memory) takes its input gradient from the
 // generated-operand GEMM of gemm.hip.  (Rounds 2-4 had a second sparse kernel here, pool_dgrad_kernel, that wrote dh.)
@@ -76,52 +78,29 @@ __global__ __launch_bounds__(NWV * 64) void pool_wgrad_kernel(PoolBwdArgs p) {
   // Two register sets = two groups in flight.  The loads are unconditional (group index clamped) and the
   // loop is unrolled by the two sets so that the compiler's vmcnt bookkeeping stays exact (a branch around
   // a load makes it fall back to vmcnt(0), i.e. to a prefetch distance of nothing).
-  float4 pa0, pa1 = make_float4(0.f, 0.f, 0.f, 0.f), pb0, pb1 = pa1, qa = pa1, qb = pa1;
+  float4 pa0, pa1 = make_float4(0.f, 0.f, 0.f, 0.f), pb0, pb1 = pa1;
   int ava, avb;
   float gva, gvb;
-  // regenerated rows (p.gQ): the point indices of this thread's rows, looked up one round ahead of the row loads
-  // they address (a dependent idx -> row chain inside one round would cost a memory latency per group)
-  int ja0 = 0, ja1 = 0, jb0 = 0, jb1 = 0;
-  const bool regen = p.gQ != nullptr;
-#define PB_IDX(gg, j0_, j1_)                                                         \
+#define PB_ISSUE(gg, x0, x1, av_, gv_)                                              \
   do {                                                                              \
     const int g_ = (gg) < p.G ? (gg) : p.G - 1;                                     \
-    const int64_t* ip = p.gidx + (size_t)g_ * 32 + srow;                            \
-    j0_ = (int)ip[0];                                                               \
-    if (TWO) j1_ = (int)ip[16];                                                     \
-  } while (0)
-#define PB_ISSUE(gg, x0, x1, q_, av_, gv_, j0_, j1_)                                \
-  do {                                                                              \
-    const int g_ = (gg) < p.G ? (gg) : p.G - 1;                                     \
-    if (regen) {                                                                    \
-      const size_t pb_ = (size_t)(g_ / p.gS) * p.gN;                                \
-      x0 = *reinterpret_cast<const float4*>(p.gP + (pb_ + j0_) * p.C1 + col0 + scol); \
-      if (TWO) x1 = *reinterpret_cast<const float4*>(p.gP + (pb_ + j1_) * p.C1 + col0 + scol); \
-      q_ = *reinterpret_cast<const float4*>(p.gQ + (size_t)g_ * p.C1 + col0 + scol); \
-    } else {                                                                        \
-      const float* hp = p.h + ((size_t)g_ * 32 + srow) * p.C1 + col0 + scol;        \
-      x0 = *reinterpret_cast<const float4*>(hp);                                    \
-      if (TWO) x1 = *reinterpret_cast<const float4*>(hp + (size_t)16 * p.C1);       \
-    }                                                                               \
+    const float* hp = p.h + ((size_t)g_ * 32 + srow) * p.C1 + col0 + scol;          \
+    x0 = *reinterpret_cast<const float4*>(hp);                                      \
+    if (TWO) x1 = *reinterpret_cast<const float4*>(hp + (size_t)16 * p.C1);         \
     const size_t o = (size_t)g_ * p.C2 + ch;                                        \
     const int a = p.argmax[o];                                                      \
     const float go = p.out[o], gd = p.dout[o];                                      \
     av_ = a & 31;                                                                   \
     gv_ = (lane < CPW && go > 0.f) ? gd : 0.f;                                      \
   } while (0)
-#define PB_GROUP(buf, x0, x1, q_, av_, gv_, j0_, j1_, gnext)                        \
+#define PB_GROUP(buf, x0, x1, av_, gv_, gnext)                                      \
   do {                                                                              \
-    if (regen) {                                                                    \
-      x0 = pb_add_relu(x0, q_);                                                     \
-      if (TWO) x1 = pb_add_relu(x1, q_);                                            \
-    }                                                                               \
     *reinterpret_cast<float4*>(&hbuf[buf][srow][scol]) = x0;                        \
     if (TWO) *reinterpret_cast<float4*>(&hbuf[buf][(srow + 16) & 31][scol]) = x1;   \
     const int av = av_;                                                             \
     const float gv = gv_;                                                           \
     __syncthreads(); /* one barrier per group: the tile two groups back is free again by construction */ \
-    PB_ISSUE(gnext, x0, x1, q_, av_, gv_, j0_, j1_);  /* rows of gnext: their indices arrived a round ago */ \
-    if (regen) PB_IDX((gnext) + 2 * gs_, j0_, j1_);   /* indices for the round after */ \
+    PB_ISSUE(gnext, x0, x1, av_, gv_);                                              \
     dbacc += gv;                                                                    \
     _Pragma("unroll") for (int c = 0; c < CPW; ++c) {                               \
       const int a = __builtin_amdgcn_readlane(av, c);                               \
@@ -142,24 +121,15 @@ __global__ __launch_bounds__(NWV * 64) void pool_wgrad_kernel(PoolBwdArgs p) {
     g_first = xcd * gx8 + (int)(blockIdx.x >> 3), gs_ = gridDim.x >> 3;
     g_end = (xcd + 1) * gx8 < p.G ? (xcd + 1) * gx8 : p.G;
   }
-  if (regen) {
-    PB_IDX(g_first, ja0, ja1);
-    PB_IDX(g_first + gs_, jb0, jb1);
-  }
-  PB_ISSUE(g_first, pa0, pa1, qa, ava, gva, ja0, ja1);
-  PB_ISSUE(g_first + gs_, pb0, pb1, qb, avb, gvb, jb0, jb1);
-  if (regen) {
-    PB_IDX(g_first + 2 * gs_, ja0, ja1);
-    PB_IDX(g_first + 3 * gs_, jb0, jb1);
-  }
+  PB_ISSUE(g_first, pa0, pa1, ava, gva);
+  PB_ISSUE(g_first + gs_, pb0, pb1, avb, gvb);
   for (int g = g_first; g < g_end; g += 2 * gs_) {
-    PB_GROUP(0, pa0, pa1, qa, ava, gva, ja0, ja1, g + 2 * gs_);
+    PB_GROUP(0, pa0, pa1, ava, gva, g + 2 * gs_);
     if (g + gs_ >= g_end) break;
-    PB_GROUP(1, pb0, pb1, qb, avb, gvb, jb0, jb1, g + 3 * gs_);
+    PB_GROUP(1, pb0, pb1, avb, gvb, g + 3 * gs_);
   }
 #undef PB_GROUP
 #undef PB_ISSUE
-#undef PB_IDX
 
   if (p.partials) {
     float* part = p.partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * p.C2 * PB_COLS;
@@ -177,6 +147,192 @@ __global__ __launch_bounds__(NWV * 64) void pool_wgrad_kernel(PoolBwdArgs p) {
     if (p.db && blockIdx.y == 0 && lane < CPW) atomicAdd(p.db + wave * CPW + lane, dbacc);
   }
   (void)T;
+}
+
+// Regenerated rows (p.gQ, the path of pzn_sa_level_bwd_pt_f32): the raw P' rows of a group's 32 x 128 tile go global -> LDS
+// by LDS-DMA (global_load_lds_dwordx4: 1 KB per wavefront-instruction; wave w copies rows 2w, 2w + 1, the source address a
+// wave-uniform per-cloud base plus a 32-bit per-lane offset), no staging registers, no 64-bit per-lane addresses.  The ring
+// holds two batches of PR_NB groups and there is ONE barrier per batch:
+//     vmcnt(0)      this wavefront's DMA of batch b's rows (issued a batch ago), of the Q slices and indices of batch b + 2
+//                   and its load of batch b's (arg-max, out, dout) have landed
+//     gate          each thread applies relu(. + Q) to the 16 bytes its own DMA lane wrote, in place (the same fp32 add and
+//                   max as pb_add_relu: 6 vector instructions per group instead of 3 per hit at the hit)
+//     barrier       every tile of batch b is gated; nobody reads batch b - 1's tiles any more
+//     DMA b + 1     into batch b - 1's tiles, in flight behind the hit loops of batch b
+//     hit loops     as pool_wgrad_kernel's, the LDS reads inline asm with their own lgkmcnt waits (a read the compiler sees
+//                   would be waited for with vmcnt(0), i.e. behind the DMA of batch b + 1)
+// The walk, and with it every accumulator's order of additions, is the one of pool_wgrad_kernel: dW and db keep their bits.
+
+// Diagnostic build (tools/pool_stamps.py, -DPOOL_STAMPS): per-phase s_memtime sums of wavefronts 0 and 15 of workgroups 0 and
+// 77 (slice 0) over the whole walk, read back with pzn_pool_wgrad_read_stamps.  Phases: 0 = DMA landed + gate, 1 = barrier,
+// 2 = DMA + load issue, 3 = hit loops; [4] = groups walked.
+#ifdef POOL_STAMPS
+__device__ long long g_pool_stamps[2][2][2][8];      // [CPW == 16][workgroup 0 / 77][wavefront 0 / 15][phase]
+#define PR_STAMP(k)                                      \
+  do {                                                   \
+    const long long u_ = __builtin_amdgcn_s_memtime();   \
+    st_[k] += u_ - t_;                                   \
+    t_ = u_;                                             \
+  } while (0)
+#else
+#define PR_STAMP(k) \
+  do {              \
+  } while (0)
+#endif
+
+constexpr int PR_NB = 4;      // groups per batch (per barrier); the ring is 2 PR_NB x 16 KB of LDS
+
+template <int CPW>
+__global__ __launch_bounds__(1024) void pool_wgrad_regen_kernel(PoolBwdArgs p) {
+  static_assert(PR_NB == 4 && PR_NB * CPW <= 64, "one DMA instruction per batch for the indices, one load per batch for the rest");
+  __shared__ __attribute__((aligned(16))) float ring[2 * PR_NB][32][PB_COLS];
+  __shared__ __attribute__((aligned(16))) float qbuf[2][PR_NB][PB_COLS];      // the groups' Q slices, two batches
+  __shared__ __attribute__((aligned(16))) int64_t ibuf[2][PR_NB][32];        // the groups' neighbour indices, two batches
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int col0 = blockIdx.y * PB_COLS;
+
+  v2f acc[CPW];
+#pragma unroll
+  for (int c = 0; c < CPW; ++c) acc[c] = v2f{0.f, 0.f};
+  float dbacc = 0.f;
+
+  int g_first = blockIdx.x, gs_ = gridDim.x, g_end = p.G;      // (the XCD-aware walk of pool_wgrad_kernel)
+  if ((gridDim.x & 7) == 0) {
+    const int xcd = blockIdx.x & 7, gx8 = (p.G + 7) >> 3;
+    g_first = xcd * gx8 + (int)(blockIdx.x >> 3), gs_ = gridDim.x >> 3;
+    g_end = (xcd + 1) * gx8 < p.G ? (xcd + 1) * gx8 : p.G;
+  }
+  const int n = g_first < g_end ? (g_end - g_first + gs_ - 1) / gs_ : 0;      // groups of this workgroup
+  const int nbat = (n + PR_NB - 1) / PR_NB;
+  // the k-th group of the walk (past the end: the last one, loaded and never added)
+  auto group = [&](int k) { return g_first + (k < n ? k : n - 1) * gs_; };
+
+  // this thread's DMA lane: row srow of the tile, columns scol .. scol + 3 of the slice
+  const int srow = tid >> 5, scol = (tid & 31) * 4;
+  const uint32_t scolb = (uint32_t)scol * 4u, rowb = (uint32_t)p.C1 * 4u;
+  const uint32_t ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float*)&ring[0][0][0];
+  // the batch's (arg-max row, pooled output, gradient) of this wavefront's channels: lane l holds channel l % CPW of the
+  // batch's group l / CPW, one load per array and batch
+  const int mi = lane / CPW < PR_NB ? lane / CPW : PR_NB - 1, mc = wave * CPW + lane % CPW;
+  int an;
+  float on, dn;
+  auto load_meta = [&](int b) {
+    const size_t o = (size_t)group(b * PR_NB + mi) * p.C2 + mc;
+    an = p.argmax[o];
+    on = p.out[o];
+    dn = p.dout[o];
+  };
+  // small per-batch copies into LDS by one DMA instruction each, two batches ahead of their use: a group's Q slice (512
+  // bytes: wavefront j < 2 copies those of groups 2j, 2j + 1) and its 32 neighbour indices (256 bytes: wavefront 2, 16
+  // lanes per group), instead of every thread loading the 16 bytes of Q and the index its rows need
+  auto dma_small = [&](int b) {
+    if (wave < 2) {
+      const int i = 2 * wave + (lane >> 5);
+      const float* src = p.gQ + (size_t)group(b * PR_NB + i) * p.C1 + col0 + (lane & 31) * 4;
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                       (__attribute__((address_space(3))) void*)&qbuf[b & 1][2 * wave][0], 16, 0, 0);
+    } else if (wave == 2) {
+      const int64_t* src = p.gidx + (size_t)group(b * PR_NB + (lane >> 4)) * 32 + 2 * (lane & 15);
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                       (__attribute__((address_space(3))) void*)&ibuf[b & 1][0][0], 16, 0, 0);
+    }
+  };
+  // the DMA of a batch's rows walks the groups in order: their clouds follow by a running remainder, not a division per group
+  int dcl = n > 0 ? g_first / p.gS : 0, drem = n > 0 ? g_first - dcl * p.gS : 0, dk = 0;
+  auto dma_rows = [&](int b) {
+    int j[PR_NB];
+#pragma unroll
+    for (int i = 0; i < PR_NB; ++i) j[i] = (int)ibuf[b & 1][i][srow];      // (all read before the first DMA goes out)
+#pragma unroll
+    for (int i = 0; i < PR_NB; ++i) {
+      const unsigned char* base = reinterpret_cast<const unsigned char*>(p.gP + (size_t)dcl * p.gN * p.C1 + col0);
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(base + ((uint32_t)j[i] * rowb + scolb)),
+                                       (__attribute__((address_space(3))) void*)&ring[(b & 1) * PR_NB + i][2 * wave][0], 16, 0, 0);
+      if (++dk < n)       // (past the end the last group is fetched again: group())
+        for (drem += gs_; drem >= p.gS; drem -= p.gS) ++dcl;
+    }
+  };
+
+#ifdef POOL_STAMPS
+  long long st_[4] = {0, 0, 0, 0}, t_ = __builtin_amdgcn_s_memtime();
+#endif
+  if (nbat > 0) {
+    dma_small(0);
+    if (nbat > 1) dma_small(1);
+    load_meta(0);
+    __syncthreads();      // (vmcnt(0): batch 0's and 1's Q slices and indices are in LDS for everybody)
+    dma_rows(0);
+  }
+  for (int b = 0; b < nbat; ++b) {
+    const int set = (b & 1) * PR_NB;
+    // this wavefront's DMA of batch b's rows (and of batch b + 2's Q slices and indices) has landed: the compiler's own wait
+    // before an LDS access is not relied on (it tracks LDS-DMA targets by alias analysis and has left this one out)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int i = 0; i < PR_NB; ++i) {
+      float4* piece = reinterpret_cast<float4*>(&ring[set + i][srow][scol]);
+      *piece = pb_add_relu(*piece, *reinterpret_cast<const float4*>(&qbuf[b & 1][i][scol]));
+    }
+    const int av = (an & 31) * (PB_COLS * 4);
+    const float gv = on > 0.f ? dn : 0.f;
+    PR_STAMP(0);
+    __syncthreads();
+    PR_STAMP(1);
+    if (b + 1 < nbat) {
+      dma_rows(b + 1);
+      load_meta(b + 1);
+      if (b + 2 < nbat) dma_small(b + 2);      // (into batch b's slices and indices: read before the barrier above)
+    }
+    PR_STAMP(2);
+#pragma unroll
+    for (int i = 0; i < PR_NB; ++i) {
+      if (b * PR_NB + i >= n) break;
+      const uint32_t rbase = ring_lds + (uint32_t)((set + i) * 32 * PB_COLS * 4) + (uint32_t)lane * 8u;
+      dbacc += __shfl(gv, i * CPW + lane);      // (lane c < CPW: channel c of group i)
+      // every channel's row is read (no wave-uniform skip of the dead ones: a branch per channel waits for each read on
+      // its own); a dead channel adds 0 * (a gated, finite row) = +0 and leaves its accumulator's bits as they are
+      uint32_t ra[CPW];
+      float gs[CPW];
+#pragma unroll
+      for (int c = 0; c < CPW; ++c) {
+        ra[c] = (uint32_t)__builtin_amdgcn_readlane(av, i * CPW + c);
+        gs[c] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, gv), i * CPW + c));
+      }
+      v2f x[CPW];
+#pragma unroll
+      for (int c = 0; c < CPW; ++c) asm volatile("ds_read_b64 %0, %1" : "=v"(x[c]) : "v"(rbase + ra[c]));
+#pragma unroll
+      for (int c = 0; c < CPW; ++c) {
+        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(x[c]) : "n"(CPW - 1 - c));
+        acc[c] += gs[c] * x[c];
+      }
+    }
+    PR_STAMP(3);
+  }
+#ifdef POOL_STAMPS
+  if (lane == 0 && (wave == 0 || wave == 15) && blockIdx.y == 0 && (blockIdx.x == 0 || blockIdx.x == 77)) {
+    long long* o = g_pool_stamps[CPW == 16][blockIdx.x ? 1 : 0][wave ? 1 : 0];
+    for (int k = 0; k < 4; ++k) o[k] = st_[k];
+    o[4] = n;
+  }
+#endif
+
+  if (p.partials) {
+    float* part = p.partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * p.C2 * PB_COLS;
+#pragma unroll
+    for (int c = 0; c < CPW; ++c) *reinterpret_cast<v2f*>(part + (size_t)(wave * CPW + c) * PB_COLS + 2 * lane) = acc[c];
+    if (blockIdx.y == 0 && lane < CPW)
+      p.partials[(size_t)gridDim.y * gridDim.x * p.C2 * PB_COLS + (size_t)blockIdx.x * p.C2 + wave * CPW + lane] = dbacc;
+  } else {
+#pragma unroll
+    for (int c = 0; c < CPW; ++c) {
+      float* o = p.dW + (size_t)(wave * CPW + c) * p.C1 + col0 + 2 * lane;
+      atomicAdd(o, acc[c].x);
+      atomicAdd(o + 1, acc[c].y);
+    }
+    if (p.db && blockIdx.y == 0 && lane < CPW) atomicAdd(p.db + wave * CPW + lane, dbacc);
+  }
 }
 
 // dW[c, :] += the workgroups' partial tiles, db[c] += their partial sums, in workgroup order (the same bits in every run; the
@@ -242,7 +398,15 @@ int launch_wgrad(PoolBwdArgs p, hipStream_t st, void* ws, size_t ws_bytes) {
                 (reinterpret_cast<uintptr_t>(p.dW) & 15) == 0)
                    ? static_cast<float*>(ws)
                    : nullptr;
-  if (p.C2 % 16 == 0 && p.C2 / 16 >= 4) {      // 16 wavefronts, C2 / 16 channels each
+  if (p.gQ) {      // regenerated rows: LDS-DMA ring, 16 wavefronts, C2 / 16 channels each (C2 is 64, 128 or 256)
+    const int cpw = p.C2 / 16;
+    if (cpw == 4)
+      PZN_LAUNCH((pool_wgrad_regen_kernel<4>), grid, dim3(1024), 0, st, p);
+    else if (cpw == 8)
+      PZN_LAUNCH((pool_wgrad_regen_kernel<8>), grid, dim3(1024), 0, st, p);
+    else
+      PZN_LAUNCH((pool_wgrad_regen_kernel<16>), grid, dim3(1024), 0, st, p);
+  } else if (p.C2 % 16 == 0 && p.C2 / 16 >= 4) {      // 16 wavefronts, C2 / 16 channels each
     const int cpw = p.C2 / 16;
     if (cpw == 4)
       PZN_LAUNCH((pool_wgrad_kernel<4, 16>), grid, dim3(1024), 0, st, p);
@@ -294,3 +458,29 @@ int pzn_pool_wgrad_sparse(const float* dout, const int32_t* argmax, const float*
   if (!dW || (!h && !p.gQ)) return PZN_EINVAL;      // the pass needs the rows or their source
   return launch_wgrad(p, st, ws, ws_bytes);
 }
+
+PZN_EXPORT size_t pzn_pool_wgrad_workspace_bytes(int G, int C1, int C2) { return pzn_pool_wgrad_ws_bytes(G, C1, C2); }
+
+PZN_EXPORT int pzn_pool_wgrad_f32(const float* dout, const int32_t* argmax, const float* out, const float* h, const float* Pp,
+                                  const float* Q, const int64_t* idx, int N, int S, int G, int C1, int C2, float* dW2, float* db2,
+                                  void* workspace, pzn_stream_t stream) {
+  PZN_CHECK_ARG(dout && argmax && out && dW2 && db2 && workspace && G > 0 && C1 > 0 && C2 > 0);
+  PZN_CHECK_ARG(h ? !(Pp || Q || idx) : (Pp && Q && idx && N > 0 && S > 0 && G % S == 0));
+  if (!pzn_pool_wgrad_supported(C1, C2, h) || (reinterpret_cast<uintptr_t>(workspace) & 15) ||
+      (reinterpret_cast<uintptr_t>(dW2) & 15) || (!h && ((reinterpret_cast<uintptr_t>(Pp) & 15) || (reinterpret_cast<uintptr_t>(Q) & 7))))
+    return PZN_EUNSUPPORTED;
+  const PznGateSource gs{Pp, idx, Q, N, S};
+  return pzn_pool_wgrad_sparse(dout, argmax, out, h, dW2, db2, G, C1, C2, pzn_hip_stream(stream), h ? nullptr : &gs, workspace,
+                               pzn_pool_wgrad_ws_bytes(G, C1, C2));
+}
+
+#ifdef POOL_STAMPS
+// diagnostic build only: copy the stamps to host (zero != 0: clear them instead)
+PZN_EXPORT int pzn_pool_wgrad_read_stamps(long long* host, int zero) {
+  if (zero) {
+    static const long long z[sizeof(g_pool_stamps) / sizeof(long long)] = {};
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_pool_stamps), z, sizeof(z)) == hipSuccess ? 0 : -1;
+  }
+  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_pool_stamps), sizeof(g_pool_stamps)) == hipSuccess ? 0 : -1;
+}
+#endif
