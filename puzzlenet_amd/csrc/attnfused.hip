@@ -15,7 +15,7 @@
 //   No score matrix, no LDS transposes; a wavefront owns 16 points end to end and never talks to another one.
 //
 // Split precision: every fp32 operand is x = x1 + x2 + x3 (three bf16 "planes"); a product is the six MFMAs of
-// magnitude >= 2^-16 (fp32-GEMM accuracy, see gemm.hip).  Shared operands are split ONCE by their producer and kept in
+// magnitude >= 2^-16 (fp32-GEMM accuracy, see pzn_x3.h).  Shared operands are split ONCE by their producer and kept in
 // memory as plane images in MFMA-fragment order; the per-wavefront operand is split in registers as it is consumed.
 // NPL = 1 (the opt-in bf16 attention mode): one plane, one MFMA per product.
 //
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void pack_rp_kernel(PackArgs a) {
       v[j] = J.src[(long)(16 * rt + c) * J.rs + (long)k * J.cs];
     }
     bf16x8 b[3];
-    split8(v, b);
+    split8<split_pair_scalar>(v, b);
     const int tg = J.rt0 + rt;
     unsigned char* slab = J.dst + (size_t)((J.ks0 + ks) * J.groups + (tg >> 3)) * SLAB;
 #pragma unroll

@@ -28,11 +28,8 @@
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+#include "pzn_x3.h"
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int AW_T = 512;          // 8 wavefronts: 4 load the A tile, 4 the B tile; each multiplies a 32 x 64 block
@@ -60,30 +57,14 @@ struct AwArgs {
   int M, rows_per_split;
 };
 
-__device__ __forceinline__ void aw_split_pair(v2f x, uint32_t& p1, uint32_t& p2, uint32_t& p3) {
-  bf16x2 a = __builtin_convertvector(x, bf16x2);
-  p1 = __builtin_bit_cast(uint32_t, a);
-  v2f fa = v2f{__uint_as_float(p1 << 16), __uint_as_float(p1 & 0xffff0000u)};
-  v2f r = x - fa;
-  bf16x2 b = __builtin_convertvector(r, bf16x2);
-  p2 = __builtin_bit_cast(uint32_t, b);
-  v2f fb = v2f{__uint_as_float(p2 << 16), __uint_as_float(p2 & 0xffff0000u)};
-  v2f r2 = r - fb;
-  bf16x2 c = __builtin_convertvector(r2, bf16x2);
-  p3 = __builtin_bit_cast(uint32_t, c);
-}
-
 // the three planes of 8 consecutive reduction indices of one column -> LDS, as the operand of lane (col & 31, half)
 __device__ __forceinline__ void aw_store(const float (&v)[8], unsigned char* oper, int col, int half) {
-  uint32_t a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3;
-  aw_split_pair(v2f{v[0], v[1]}, a0, b0, c0);
-  aw_split_pair(v2f{v[2], v[3]}, a1, b1, c1);
-  aw_split_pair(v2f{v[4], v[5]}, a2, b2, c2);
-  aw_split_pair(v2f{v[6], v[7]}, a3, b3, c3);
+  uint32_t w[3][4];
+  split8<split_pair_packed>(v, w);
   unsigned char* dst = oper + (col >> 5) * AW_FRAG + ((half << 5) | (col & 31)) * 16;
-  *reinterpret_cast<u32x4*>(dst) = u32x4{a0, a1, a2, a3};
-  *reinterpret_cast<u32x4*>(dst + 4 * AW_FRAG) = u32x4{b0, b1, b2, b3};
-  *reinterpret_cast<u32x4*>(dst + 8 * AW_FRAG) = u32x4{c0, c1, c2, c3};
+  *reinterpret_cast<u32x4*>(dst) = u32x4{w[0][0], w[0][1], w[0][2], w[0][3]};
+  *reinterpret_cast<u32x4*>(dst + 4 * AW_FRAG) = u32x4{w[1][0], w[1][1], w[1][2], w[1][3]};
+  *reinterpret_cast<u32x4*>(dst + 8 * AW_FRAG) = u32x4{w[2][0], w[2][1], w[2][2], w[2][3]};
 }
 
 __global__ __launch_bounds__(AW_T) void attn_wgrad_kernel(AwArgs p) {
@@ -155,25 +136,13 @@ __global__ __launch_bounds__(AW_T) void attn_wgrad_kernel(AwArgs p) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) dbsum += rn[e];
     }
-    uint32_t a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3;
-    aw_split_pair(v2f{rn[0], rn[1]}, a0, b0, c0);
-    aw_split_pair(v2f{rn[2], rn[3]}, a1, b1, c1);
-    aw_split_pair(v2f{rn[4], rn[5]}, a2, b2, c2);
-    aw_split_pair(v2f{rn[6], rn[7]}, a3, b3, c3);
+    uint32_t w[3][4];
+    split8<split_pair_packed>(rn, w);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      floatx16 c = acc[j];
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[j][0], c, 0, 0, 0);  // small terms first
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[j][1], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[j][2], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[j][0], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[j][1], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[j][0], c, 0, 0, 0);
-      acc[j] = c;
-    }
-    *reinterpret_cast<u32x4*>(dst) = u32x4{a0, a1, a2, a3};
-    *reinterpret_cast<u32x4*>(dst + 4 * AW_FRAG) = u32x4{b0, b1, b2, b3};
-    *reinterpret_cast<u32x4*>(dst + 8 * AW_FRAG) = u32x4{c0, c1, c2, c3};
+    for (int j = 0; j < 2; ++j) acc[j] = mma_x3(fa, fb[j], acc[j]);
+    *reinterpret_cast<u32x4*>(dst) = u32x4{w[0][0], w[0][1], w[0][2], w[0][3]};
+    *reinterpret_cast<u32x4*>(dst + 4 * AW_FRAG) = u32x4{w[1][0], w[1][1], w[1][2], w[1][3]};
+    *reinterpret_cast<u32x4*>(dst + 8 * AW_FRAG) = u32x4{w[2][0], w[2][1], w[2][2], w[2][3]};
     issue(s + 3, rn);
     __syncthreads();      // step s + 1 is in LDS, every wavefront is done with the buffer of step s
   };

@@ -28,11 +28,7 @@
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+#include "pzn_x3.h"
 
 struct DfArgs {
   const float* dy;    // [M, N]
@@ -57,33 +53,6 @@ struct DfArgs {
   float* sdw[3];
   float* sdb[3];
 };
-
-__device__ __forceinline__ void split_pair(v2f x, uint32_t& p1, uint32_t& p2, uint32_t& p3) {
-  bf16x2 a = __builtin_convertvector(x, bf16x2);
-  p1 = __builtin_bit_cast(uint32_t, a);
-  v2f fa = v2f{__uint_as_float(p1 << 16), __uint_as_float(p1 & 0xffff0000u)};
-  v2f r = x - fa;
-  bf16x2 b = __builtin_convertvector(r, bf16x2);
-  p2 = __builtin_bit_cast(uint32_t, b);
-  v2f fb = v2f{__uint_as_float(p2 << 16), __uint_as_float(p2 & 0xffff0000u)};
-  v2f r2 = r - fb;
-  bf16x2 c = __builtin_convertvector(r2, bf16x2);
-  p3 = __builtin_bit_cast(uint32_t, c);
-}
-
-struct Planes {
-  bf16x8 p1, p2, p3;
-};
-
-__device__ __forceinline__ Planes split8(const float (&v)[8]) {
-  uint32_t a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3;
-  split_pair(v2f{v[0], v[1]}, a0, b0, c0);
-  split_pair(v2f{v[2], v[3]}, a1, b1, c1);
-  split_pair(v2f{v[4], v[5]}, a2, b2, c2);
-  split_pair(v2f{v[6], v[7]}, a3, b3, c3);
-  const u32x4 a = {a0, a1, a2, a3}, b = {b0, b1, b2, b3}, c = {c0, c1, c2, c3};
-  return Planes{__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), __builtin_bit_cast(bf16x8, c)};
-}
 
 template <int TI, int TJ, bool GENY, bool WITH_DB>
 __global__ __launch_bounds__(768) void df_wgrad_kernel(DfArgs p) {
@@ -166,7 +135,7 @@ __global__ __launch_bounds__(768) void df_wgrad_kernel(DfArgs p) {
   int s = s_begin + rep;
   if (s < s_end) issue(s);
   for (; s < s_end; s += p.reps) {
-    Planes pa[TI], pb[TJ];
+    bf16x8 pa[TI][3], pb[TJ][3];
 #pragma unroll
     for (int i = 0; i < TI; ++i) {
       float v[8];
@@ -175,10 +144,10 @@ __global__ __launch_bounds__(768) void df_wgrad_kernel(DfArgs p) {
         v[e] = (GENY && !(ry[i][e] > 0.f)) ? 0.f : ra[i][e];
         if (WITH_DB) dbacc[i] += v[e];
       }
-      pa[i] = split8(v);
+      split8<split_pair_packed>(v, pa[i]);
     }
 #pragma unroll
-    for (int j = 0; j < TJ; ++j) pb[j] = split8(rb[j]);
+    for (int j = 0; j < TJ; ++j) split8<split_pair_packed>(rb[j], pb[j]);
     {
       const int sn = s + p.reps;
       issue(sn < s_end ? sn : s);  // the last one re-reads its own rows: harmless, keeps the loop branch-free
@@ -186,16 +155,7 @@ __global__ __launch_bounds__(768) void df_wgrad_kernel(DfArgs p) {
 #pragma unroll
     for (int i = 0; i < TI; ++i)
 #pragma unroll
-      for (int j = 0; j < TJ; ++j) {
-        floatx16 c = acc[i][j];
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[i].p3, pb[j].p1, c, 0, 0, 0);  // small terms first
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[i].p2, pb[j].p2, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[i].p1, pb[j].p3, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[i].p2, pb[j].p1, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[i].p1, pb[j].p2, c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[i].p1, pb[j].p1, c, 0, 0, 0);
-        acc[i][j] = c;
-      }
+      for (int j = 0; j < TJ; ++j) acc[i][j] = mma_x3(pa[i], pb[j], acc[i][j]);
   }
 
   // 2 / 4 / 8 replicas per tile block meet in LDS (lane-major images, halving rounds), so a tile block issues ONE

@@ -34,29 +34,7 @@
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-// ---- split precision ("bf16x3") -------------------------------------------------------------
-// x = x1 + x2 + x3 exactly, each xi a bf16 (8 significant bits, fp32's exponent range): x1 = bf16(x),
-// x2 = bf16(x - x1), x3 = bf16(x - x1 - x2).  a*b is then summed from the six products whose magnitude is
-// >= 2^-16 of the leading one: (1,1) (1,2) (2,1) (1,3) (2,2) (3,1); the three dropped ones are <= 2^-24
-// relative, i.e. below fp32 rounding.  Each product of two bf16 is exact in fp32 and the MFMA accumulates
-// in fp32, so the result has fp32-GEMM accuracy — at 6 v_mfma_f32_32x32x16_bf16 (32 cycles for 16 k) against
-// 8 v_mfma_f32_32x32x2_f32 (64 cycles for 2 k): 2.67x the matrix-pipe throughput.
-__device__ __forceinline__ uint32_t f2bf(float x) {
-  __bf16 b = (__bf16)x;  // v_cvt_pk_bf16_f32, round to nearest even
-  return (uint32_t)__builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ float bf2f(uint32_t b) { return __uint_as_float(b << 16); }
-__device__ __forceinline__ void split3(float x, uint32_t& a, uint32_t& b, uint32_t& c) {
-  a = f2bf(x);
-  float r = x - bf2f(a);
-  b = f2bf(r);
-  float r2 = r - bf2f(b);
-  c = f2bf(r2);
-}
+#include "pzn_x3.h"  // split precision: bf16 planes, six products
 
 constexpr int BK = 16;
 constexpr int GT = 256;  // threads per block
@@ -418,20 +396,7 @@ __global__ __launch_bounds__(GT) void gemm_kernel(GemmArgs p) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          floatx16 c = acc[i][j];
-          if constexpr (ONE) {  // plain bf16 operands, fp32 accumulation: one product
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][0], c, 0, 0, 0);
-          } else {
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][2], bf[j][0], c, 0, 0, 0);  // small terms first
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], bf[j][1], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][2], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][1], bf[j][0], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][1], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bf[j][0], c, 0, 0, 0);
-          }
-          acc[i][j] = c;
-        }
+        for (int j = 0; j < TN; ++j) acc[i][j] = mma_x3<NPL>(af[i], bf[j], acc[i][j]);  // ONE: plain bf16, one product
       if (convert_next && !ONE) {
 #pragma unroll
         for (int g = 0; g < TM * TN * 6; ++g) {

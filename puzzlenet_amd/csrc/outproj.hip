@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void op_pack_w_kernel(const float* __restrict_
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = src[j];
     bf16x8 b[3];
-    split8(v, b);
+    split8<split_pair_scalar>(v, b);
 #pragma unroll
     for (int p = 0; p < 3; ++p)
       *reinterpret_cast<bf16x8*>(dst + (((((size_t)cg * OP_STEPS + ks) * 3 + p) * OP_CT + ct) * 64 + lane) * 16) = b[p];
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(OP_WAVES * 64, 2) void outproj_maxpts_kernel(OpArgs
     constexpr int st = decltype(setc)::value;
     const f32x4 pv = pa[st][j >> 1];
     uint32_t w0, w1, w2;
-    split_pair(pv[2 * (j & 1)], pv[2 * (j & 1) + 1], w0, w1, w2);
+    split_pair_scalar(pv[2 * (j & 1)], pv[2 * (j & 1) + 1], w0, w1, w2);
     asm volatile("" : "+v"(w0), "+v"(w1), "+v"(w2));   // (pins the work to its fill slot)
     bn.w[0][j] = w0, bn.w[1][j] = w1, bn.w[2][j] = w2;
   };

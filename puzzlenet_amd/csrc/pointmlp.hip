@@ -113,7 +113,7 @@ __device__ __forceinline__ void pm_build_image(unsigned char* img, const float* 
       v[j] = (row < rows && k < K) ? (TRANS ? W[(long)k * ldw + row] : W[(long)row * ldw + k]) : 0.f;
     }
     bf16x8 b[3];
-    split8(v, b);
+    split8<split_pair_scalar>(v, b);
 #pragma unroll
     for (int p = 0; p < 3; ++p) *reinterpret_cast<bf16x8*>(img + ((ks * 3 + p) * RT + rt) * 1024 + l * 16) = b[p];
   }
@@ -131,7 +131,7 @@ __device__ __forceinline__ void pm_layer(floatx16 (&acc)[RT], const floatx16* in
       bf16x8 a[3];
 #pragma unroll
       for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8*>(img + ((ks * 3 + p) * RT + rt) * 1024 + lane * 16);
-      acc[rt] = mma6(a, b, acc[rt]);
+      acc[rt] = mma_x3(a, b, acc[rt]);
     }
   }
 }
@@ -315,7 +315,7 @@ __device__ __forceinline__ void pm_point_frag(const float* stg, int ot, int s, c
   float v[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) v[j] = stg[o.fo[j] + 16 * s * F + 32 * ot];
-  split8(v, b);
+  split8<split_pair_scalar>(v, b);
 }
 // column sums of a tile: lane = feature (< F); four chains
 template <int F>
@@ -430,7 +430,7 @@ __global__ __launch_bounds__(256, 1) void point_mlp3_bwd_kernel(PmBwdArgs a) {
           float v[8];
 #pragma unroll
           for (int j = 0; j < 8; ++j) v[j] = r < 2 ? P[2 * (16 * s + 8 * h + j) + r] : 0.f;
-          split8(v, fa[ot]);
+          split8<split_pair_scalar>(v, fa[ot]);
         }
       }
 #pragma unroll
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(256, 1) void point_mlp3_bwd_kernel(PmBwdArgs a) {
 #pragma unroll
       for (int ot = 0; ot < T3; ++ot)
 #pragma unroll
-        for (int it = 0; it < T2; ++it) dW3[ot][it] = mma6(fa[ot], fb[it], dW3[ot][it]);
+        for (int it = 0; it < T2; ++it) dW3[ot][it] = mma_x3(fa[ot], fb[it], dW3[ot][it]);
     }
     pzn::wave_lds_sync();                     // both tiles are dead: h1 may land in Q
     pm_dma_tile<64>(a.h1 + row0 * 64, Q, lane);
@@ -468,7 +468,7 @@ __global__ __launch_bounds__(256, 1) void point_mlp3_bwd_kernel(PmBwdArgs a) {
 #pragma unroll
       for (int ot = 0; ot < T2; ++ot)
 #pragma unroll
-        for (int it = 0; it < 2; ++it) dW2[ot][it] = mma6(fa[ot], fb[it], dW2[ot][it]);
+        for (int it = 0; it < 2; ++it) dW2[ot][it] = mma_x3(fa[ot], fb[it], dW2[ot][it]);
     }
     pzn::wave_lds_sync();
     pm_dma_tile<64>(a.x + row0 * 64, Q, lane);
@@ -495,7 +495,7 @@ __global__ __launch_bounds__(256, 1) void point_mlp3_bwd_kernel(PmBwdArgs a) {
 #pragma unroll
       for (int ot = 0; ot < 2; ++ot)
 #pragma unroll
-        for (int it = 0; it < 2; ++it) dW1[ot][it] = mma6(fa[ot], fb[it], dW1[ot][it]);
+        for (int it = 0; it < 2; ++it) dW1[ot][it] = mma_x3(fa[ot], fb[it], dW1[ot][it]);
     }
     pzn::wave_lds_sync();
     if (tile + 1 < t1) pm_dma_tile<C2>(a.h2 + (row0 + 32) * C2, Q, lane);     // the next tile's first operands

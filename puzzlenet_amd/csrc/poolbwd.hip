@@ -27,7 +27,7 @@
 
 namespace {
 
-typedef float v2f __attribute__((ext_vector_type(2)));
+#include "pzn_x3.h"  // v2f; add_relu, the gate of a regenerated row
 
 constexpr int PB_T = 512;     // threads per workgroup
 constexpr int PB_W = 8;       // wavefronts
@@ -50,10 +50,6 @@ struct PoolBwdArgs {
   // order by pool_wgrad_reduce_kernel; NULL: the workgroups add into dW / db with atomics
   float* partials;
 };
-
-__device__ __forceinline__ float4 pb_add_relu(float4 a, float4 q) {
-  return make_float4(fmaxf(a.x + q.x, 0.f), fmaxf(a.y + q.y, 0.f), fmaxf(a.z + q.z, 0.f), fmaxf(a.w + q.w, 0.f));
-}
 
 // NWV wavefronts per workgroup (8 or 16), wave w owns CPW = C2 / NWV channels.  16 wavefronts: the whole 32 x 128 tile is
 // staged in one pass (one 16-byte piece per thread) and four wavefronts per SIMD hide the LDS latency of the hit loop
@@ -156,7 +152,7 @@ __global__ __launch_bounds__(NWV * 64) void pool_wgrad_kernel(PoolBwdArgs p) {
 //     vmcnt(0)      this wavefront's DMA of batch b's rows (issued a batch ago), of the Q slices and indices of batch b + 2
 //                   and its load of batch b's (arg-max, out, dout) have landed
 //     gate          each thread applies relu(. + Q) to the 16 bytes its own DMA lane wrote, in place (the same fp32 add and
-//                   max as pb_add_relu: 6 vector instructions per group instead of 3 per hit at the hit)
+//                   max as add_relu: 6 vector instructions per group instead of 3 per hit at the hit)
 //     barrier       every tile of batch b is gated; nobody reads batch b - 1's tiles any more
 //     DMA b + 1     into batch b - 1's tiles, in flight behind the hit loops of batch b
 //     hit loops     as pool_wgrad_kernel's, the LDS reads inline asm with their own lgkmcnt waits (a read the compiler sees
@@ -272,7 +268,7 @@ __global__ __launch_bounds__(1024) void pool_wgrad_regen_kernel(PoolBwdArgs p) {
 #pragma unroll
     for (int i = 0; i < PR_NB; ++i) {
       float4* piece = reinterpret_cast<float4*>(&ring[set + i][srow][scol]);
-      *piece = pb_add_relu(*piece, *reinterpret_cast<const float4*>(&qbuf[b & 1][i][scol]));
+      *piece = add_relu(*piece, *reinterpret_cast<const float4*>(&qbuf[b & 1][i][scol]));
     }
     const int av = (an & 31) * (PB_COLS * 4);
     const float gv = on > 0.f ? dn : 0.f;

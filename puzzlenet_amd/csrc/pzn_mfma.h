@@ -1,47 +1,17 @@
 // pzn_mfma.h — building blocks of the chained matrix-core kernels (attnfused.hip via pzn_mfma16.h, salevel.hip, outproj.hip), gfx950 only:
-// bf16x3 split precision, fragment reads from LDS as inline asm with counted waits (two tiles ahead), the LDS-DMA slab
-// ring (three slots, two slabs in flight, one barrier per slab), compile-time loops.  Included inside an anonymous
-// namespace by each translation unit (which includes <type_traits> and pzn_common.h first).
+// the next B fragment split behind the MFMAs, fragment reads from LDS as inline asm with counted waits (two tiles ahead),
+// the LDS-DMA slab ring (three slots, two slabs in flight, one barrier per slab), compile-time loops; the split precision
+// itself is pzn_x3.h.  Included inside an anonymous namespace by each translation unit (which includes <type_traits> and
+// pzn_common.h first).
 #pragma once
 
+#include "pzn_x3.h"
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef bf16x4 __attribute__((address_space(3))) * lds4_t;
 
 constexpr int SLAB = 24576;               // 3 planes x 8 KB
 constexpr int NT = 256;                   // threads per workgroup
 constexpr float LOG2E = 1.4426950408889634f;
-
-__device__ __forceinline__ uint32_t f2bf(float x) {
-  __bf16 b = (__bf16)x;
-  return (uint32_t)__builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ float bf2f(uint32_t b) { return __uint_as_float(b << 16); }
-
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-// two fp32 values -> three dwords of two bf16 each (x = x1 + x2 + x3, every xi a round-to-nearest bf16 of the remainder):
-// 3 v_cvt_pk_bf16_f32 + 4 unpack + 4 subtract
-__device__ __forceinline__ void split_pair(float x0, float x1, uint32_t& a, uint32_t& bq, uint32_t& c) {
-  const floatx2 x = {x0, x1};
-  a = __builtin_bit_cast(uint32_t, __builtin_convertvector(x, bf16x2));
-  const floatx2 r = {x0 - __uint_as_float(a << 16), x1 - __uint_as_float(a & 0xffff0000u)};
-  bq = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, bf16x2));
-  const floatx2 t = {r[0] - __uint_as_float(bq << 16), r[1] - __uint_as_float(bq & 0xffff0000u)};
-  c = __builtin_bit_cast(uint32_t, __builtin_convertvector(t, bf16x2));
-}
-
-// eight fp32 values -> three bf16x8 fragments (x = b0 + b1 + b2 exactly up to 2^-24)
-__device__ __forceinline__ void split8(const float (&v)[8], bf16x8 (&b)[3]) {
-  uint32_t w[3][4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) split_pair(v[2 * j], v[2 * j + 1], w[0][j], w[1][j], w[2][j]);
-#pragma unroll
-  for (int p = 0; p < 3; ++p) b[p] = __builtin_bit_cast(bf16x8, make_uint4(w[p][0], w[p][1], w[p][2], w[p][3]));
-}
 
 // The B fragment of the NEXT k-step, built a pair of values at a time behind the MFMAs of the current one
 // (BNext::pair(j), j = 0..3, from the step's fill callback), so that its ~44 vector instructions sit in the shadow of
@@ -51,13 +21,13 @@ struct BNext {
   template <bool NEG = false>
   __device__ __forceinline__ void pair(const floatx16& x, int s, int j) {
     const float x0 = x[8 * s + 2 * j], x1 = x[8 * s + 2 * j + 1];
-    split_pair(NEG ? -x0 : x0, NEG ? -x1 : x1, w[0][j], w[1][j], w[2][j]);
+    split_pair_scalar(NEG ? -x0 : x0, NEG ? -x1 : x1, w[0][j], w[1][j], w[2][j]);
   }
   // the same with the values gated by bits (16 s' + 8 s + 2 j) and the next one of `word` (a ReLU mask)
   __device__ __forceinline__ void pair_gated(const floatx16& x, int s, int j, uint32_t word, int bit0) {
     const int i = 8 * s + 2 * j;
     const float x0 = (word >> (bit0 + i)) & 1u ? x[i] : 0.f, x1 = (word >> (bit0 + i + 1)) & 1u ? x[i + 1] : 0.f;
-    split_pair(x0, x1, w[0][j], w[1][j], w[2][j]);
+    split_pair_scalar(x0, x1, w[0][j], w[1][j], w[2][j]);
   }
   __device__ __forceinline__ void get(bf16x8 (&b)[3]) const {
 #pragma unroll
@@ -71,18 +41,7 @@ __device__ __forceinline__ void make_b(const floatx16& x, int s, bf16x8 (&b)[3])
   float v[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) v[j] = NEG ? -x[8 * s + j] : x[8 * s + j];
-  split8(v, b);
-}
-
-// acc += A B with A, B in three planes each: the six products >= 2^-16, small terms first
-__device__ __forceinline__ floatx16 mma6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], floatx16 c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
-  return c;
+  split8<split_pair_scalar>(v, b);
 }
 
 struct NoGate {};
@@ -108,16 +67,6 @@ __device__ __forceinline__ void static_for(F&& f) {
     f(std::integral_constant<int, I>{});
     static_for<I + 1, N>(f);
   }
-}
-
-__device__ __forceinline__ floatx16 mma6v(bf16x8 a0, bf16x8 a1, bf16x8 a2, const bf16x8 (&b)[3], floatx16 c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b[1], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b[2], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b[1], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b[0], c, 0, 0, 0);
-  return c;
 }
 
 // one k-step of acc[rt] += A_rt B, A from an Rp slab in LDS: [plane][RT][lane][16 B].  lane_addr = LDS byte address of
@@ -153,9 +102,9 @@ __device__ __forceinline__ void kstep_rp(floatx16 (&acc)[RT], uint32_t lane_addr
       RP_WAITN(0, f[cur][0], f[cur][1], f[cur][2]);
     }
     if constexpr (LDS_IS_B)
-      acc[rt] = mma6v(b[0], b[1], b[2], f[cur], acc[rt]);
+      acc[rt] = mma_x3(b, f[cur], acc[rt]);
     else
-      acc[rt] = mma6v(f[cur][0], f[cur][1], f[cur][2], b, acc[rt]);
+      acc[rt] = mma_x3(f[cur], b, acc[rt]);
     fill(rt);
   });
 }

@@ -1,5 +1,5 @@
 // pzn_mfma16.h — the chained attention kernels' building blocks on 16-row tiles (v_mfma_f32_16x16x32_bf16), gfx950 only.
-// Included after pzn_mfma.h inside the same anonymous namespace (split_pair, static_for, Ring, step_sync, rp_issue ...).
+// Included after pzn_mfma.h inside the same anonymous namespace (pzn_x3.h, static_for, Ring, step_sync, rp_issue ...).
 //
 // Why a second tile shape: with 32-row tiles a wavefront's accumulator sets are 128 registers each, a kernel needs two or
 // three of them, and one wavefront fills a SIMD's register file — nobody hides its LDS latencies, its DMA issue, its
@@ -22,26 +22,9 @@
 // tile: a transposed read uses half the banks, 2 LDS cycles per instruction more than the 32-row form.)
 #pragma once
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
 constexpr int NT16 = 512;                          // threads per workgroup: eight wavefronts, two per SIMD
 constexpr int STG16_LD = 136;                      // dwords per staged row (16-byte units: 34 per row -> conflict-free both ways)
 constexpr int STG16_BYTES = 16 * STG16_LD * 4;     // 8,704 per wavefront: 16 rows x 128 features per pass
-
-template <int NPL>
-__device__ __forceinline__ floatx4 mma16(bf16x8 a0, bf16x8 a1, bf16x8 a2, const bf16x8 (&b)[3], floatx4 c) {
-  if constexpr (NPL == 3) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b[0], c, 0, 0, 0);
-    return c;
-  } else {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b[0], c, 0, 0, 0);
-  }
-}
 
 // B fragment of a k-step from the two accumulator tiles t0 (features 0..15 of the step) and t1 (16..31), a pair of
 // values at a time: pair jj = 0, 1 -> t0 registers 2jj, 2jj+1; jj = 2, 3 -> t1 registers 2(jj-2), 2(jj-2)+1
@@ -50,9 +33,9 @@ struct BNext16 {
   uint32_t w[3][4];
   __device__ __forceinline__ void put(float x0, float x1, int jj) {
     if constexpr (NPL == 3) {
-      split_pair(x0, x1, w[0][jj], w[1][jj], w[2][jj]);
+      split_pair_scalar(x0, x1, w[0][jj], w[1][jj], w[2][jj]);
     } else {
-      const floatx2 x = {x0, x1};
+      const v2f x = {x0, x1};
       w[0][jj] = __builtin_bit_cast(uint32_t, __builtin_convertvector(x, bf16x2));
     }
   }
@@ -98,7 +81,7 @@ __device__ __forceinline__ void kstep16(floatx4* acc, uint32_t lane_addr, const 
     } else {
       rp_wait<NPL, 0>(f[cur]);
     }
-    acc[rt] = mma16<NPL>(f[cur][0], f[cur][1], f[cur][2], b, acc[rt]);
+    acc[rt] = mma_x3<NPL>(f[cur], b, acc[rt]);
     fill(rt);
   });
 }
@@ -134,7 +117,7 @@ __device__ __forceinline__ void kstep16_tr(floatx4* acc, uint32_t la, const bf16
     }
     bf16x8 a[3];
     tr_join<NPL>(t[cur], a);
-    acc[ft] = mma16<NPL>(a[0], a[1], a[2], b, acc[ft]);
+    acc[ft] = mma_x3<NPL>(a, b, acc[ft]);
     fill(ft);
   });
 }

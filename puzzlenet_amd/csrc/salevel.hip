@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void sa_pack_w_kernel(const float* __restrict_
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = src[j];
     bf16x8 b[3];
-    split8(v, b);
+    split8<split_pair_scalar>(v, b);
 #pragma unroll
     for (int p = 0; p < 3; ++p) *reinterpret_cast<bf16x8*>(dst + ((((size_t)ks * 3 + p) * CT + ct) * 64 + lane) * 16) = b[p];
   }
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(SA_WAVES * 64, 2) void sa_level_stream_kernel(SaArg
     const f32x4 pv = pa[st][j >> 1], qv = (j >> 1) ? q1 : q0;
     const float x0 = fmaxf(pv[2 * (j & 1)] + qv[2 * (j & 1)], 0.f), x1 = fmaxf(pv[2 * (j & 1) + 1] + qv[2 * (j & 1) + 1], 0.f);
     uint32_t w0, w1, w2;
-    split_pair(x0, x1, w0, w1, w2);
+    split_pair_scalar(x0, x1, w0, w1, w2);
     asm volatile("" : "+v"(w0), "+v"(w1), "+v"(w2));   // (pins the work to its fill slot: the compiler sinks it to its use, the next step's head)
     bn.w[0][j] = w0, bn.w[1][j] = w1, bn.w[2][j] = w2;
   };

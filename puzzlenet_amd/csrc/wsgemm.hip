@@ -17,7 +17,7 @@
 //   * so a wavefront owns a 32-row tile end to end: no barrier after the prologue, every wave runs its
 //     own software pipeline (next loads in flight while the current 16 floats are split and multiplied),
 //     and the 32 rows of a tile are one (centroid, K = 32 neighbours) group for the max-pool epilogue.
-// Split precision as in gemm.hip: x = x1 + x2 + x3 (bf16 each, exact), six products per tile and 16 k.
+// Split precision (pzn_x3.h): x = x1 + x2 + x3 (bf16 each, exact), six products per tile and 16 k.
 #include <stdlib.h>
 
 #include "pzn_common.h"
@@ -25,11 +25,7 @@
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+#include "pzn_x3.h"
 
 constexpr int WS_NW = 12;        // wavefronts per workgroup, each on its own row tiles
 constexpr int WS_STAGE_LD = 36;  // floats per row of a wave's 32 x 32 output patch in LDS (16-B aligned, conflict-free)
@@ -77,36 +73,6 @@ struct WsArgs {
   const float* r3_w;
 };
 
-// two floats -> their three bf16 planes, packed (lo = first element)
-__device__ __forceinline__ void split_pair(v2f x, uint32_t& p1, uint32_t& p2, uint32_t& p3) {
-  bf16x2 a = __builtin_convertvector(x, bf16x2);
-  p1 = __builtin_bit_cast(uint32_t, a);
-  v2f fa = v2f{__uint_as_float(p1 << 16), __uint_as_float(p1 & 0xffff0000u)};
-  v2f r = x - fa;
-  bf16x2 b = __builtin_convertvector(r, bf16x2);
-  p2 = __builtin_bit_cast(uint32_t, b);
-  v2f fb = v2f{__uint_as_float(p2 << 16), __uint_as_float(p2 & 0xffff0000u)};
-  v2f r2 = r - fb;
-  bf16x2 c = __builtin_convertvector(r2, bf16x2);
-  p3 = __builtin_bit_cast(uint32_t, c);
-}
-
-__device__ __forceinline__ void split8(float4 lo, float4 hi, bf16x8& p1, bf16x8& p2, bf16x8& p3) {
-  uint32_t a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3;
-  split_pair(v2f{lo.x, lo.y}, a0, b0, c0);
-  split_pair(v2f{lo.z, lo.w}, a1, b1, c1);
-  split_pair(v2f{hi.x, hi.y}, a2, b2, c2);
-  split_pair(v2f{hi.z, hi.w}, a3, b3, c3);
-  const u32x4 a = {a0, a1, a2, a3}, b = {b0, b1, b2, b3}, c = {c0, c1, c2, c3};
-  p1 = __builtin_bit_cast(bf16x8, a);
-  p2 = __builtin_bit_cast(bf16x8, b);
-  p3 = __builtin_bit_cast(bf16x8, c);
-}
-
-__device__ __forceinline__ float4 add_relu(float4 x, float4 q) {  // relu(x + q): the first layer's row from P' and Q
-  return make_float4(fmaxf(x.x + q.x, 0.f), fmaxf(x.y + q.y, 0.f), fmaxf(x.z + q.z, 0.f), fmaxf(x.w + q.w, 0.f));
-}
-
 __device__ __forceinline__ float4 relu_mask(float4 x, float4 y) {
   return make_float4(y.x > 0.f ? x.x : 0.f, y.y > 0.f ? x.y : 0.f, y.z > 0.f ? x.z : 0.f, y.w > 0.f ? x.w : 0.f);
 }
@@ -149,12 +115,12 @@ __global__ __launch_bounds__(NW * 64) void ws_gemm_kernel(WsArgs p) {
       const size_t off = p.w_kmajor ? (size_t)(k + i) * p.ldw + n : (size_t)n * p.ldw + k + i;
       v[i] = ok ? p.W[off] : 0.f;
     }
-    bf16x8 w1, w2, w3;
-    split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), w1, w2, w3);
+    bf16x8 w[3];
+    split8<split_pair_packed>(v, w);
     unsigned char* dst = wlds + ((size_t)(ks * NT + j) * 3) * 1024 + l * 16;
-    *reinterpret_cast<bf16x8*>(dst) = w1;
-    *reinterpret_cast<bf16x8*>(dst + 1024) = w2;
-    *reinterpret_cast<bf16x8*>(dst + 2048) = w3;
+    *reinterpret_cast<bf16x8*>(dst) = w[0];
+    *reinterpret_cast<bf16x8*>(dst + 1024) = w[1];
+    *reinterpret_cast<bf16x8*>(dst + 2048) = w[2];
   }
   __syncthreads();  // the only barrier
 
@@ -247,31 +213,18 @@ __global__ __launch_bounds__(NW * 64) void ws_gemm_kernel(WsArgs p) {
     const unsigned char* wb = wlds + (size_t)(d * 2) * (NT * 3 * 1024) + lane * 16;
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      bf16x8 a1, a2, a3;
-      split8(s ? c2 : c0, s ? c3 : c1, a1, a2, a3);
+      const float4 lo = s ? c2 : c0, hi = s ? c3 : c1;
+      const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+      bf16x8 a[3];
+      split8<split_pair_packed>(v, a);
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
         const unsigned char* wj = wb + (s * NT + j) * (3 * 1024);
-        const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(wj);
-        const bf16x8 b2 = *reinterpret_cast<const bf16x8*>(wj + 1024);
-        const bf16x8 b3 = *reinterpret_cast<const bf16x8*>(wj + 2048);
-        floatx16 c = acc[j];
-        if (MAXPOOL) {  // C[row][col]: the 32 rows of the group sit in one lane's registers (+ the other half)
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, c, 0, 0, 0);  // small terms first
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, c, 0, 0, 0);
-        } else {  // transposed product C^T[col][row]: a lane ends up with 4 consecutive columns of one row
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a3, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b2, a2, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b3, a1, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a2, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b2, a1, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, a1, c, 0, 0, 0);
-        }
-        acc[j] = c;
+        const bf16x8 b[3] = {*reinterpret_cast<const bf16x8*>(wj), *reinterpret_cast<const bf16x8*>(wj + 1024),
+                             *reinterpret_cast<const bf16x8*>(wj + 2048)};
+        // MAXPOOL: C[row][col], the 32 rows of the group sit in one lane's registers (+ the other half);
+        // else the transposed product C^T[col][row]: a lane ends up with 4 consecutive columns of one row
+        acc[j] = mma_x3<3, !MAXPOOL>(a, b, acc[j]);
       }
     }
   };
