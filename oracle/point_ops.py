@@ -3,6 +3,7 @@
 Every function mirrors one reference function and cites it; the arithmetic
 lives in the C file.  Arrays in, arrays out (fp32 / int64, C-contiguous).
 """
+import contextlib
 import ctypes
 import os
 import subprocess
@@ -158,6 +159,53 @@ def _emd_t(dtype):
     return np.float32, _f, "f32"
 
 
+# The C entry points walk the batch pair after pair on one thread.  Pairs are independent and ctypes releases the GIL
+# around a call, so with set_emd_threads(n > 1) the batch is cut into single pairs (b = 1: every call has its own scratch)
+# that a thread pool hands to the same C functions: each pair's arithmetic is untouched and the results are the
+# one-thread bits.  The default is ONE thread: bench.py's cpu_baseline reports this code as "EMD = 1-thread C".
+_EMD_THREADS = 1
+_EMD_POOL = None
+
+
+def set_emd_threads(n):
+    """Threads the EMD entry points spread a batch over (1 = the plain loop inside the C code) -> the previous value."""
+    global _EMD_THREADS, _EMD_POOL
+    n = int(n)
+    if n < 1:
+        raise ValueError("set_emd_threads: need n >= 1")
+    prev, _EMD_THREADS = _EMD_THREADS, n
+    if _EMD_POOL is not None and n != prev:
+        _EMD_POOL.shutdown(wait=True)
+        _EMD_POOL = None
+    return prev
+
+
+def get_emd_threads():
+    return _EMD_THREADS
+
+
+@contextlib.contextmanager
+def emd_threads(n):
+    prev = set_emd_threads(n)
+    try:
+        yield
+    finally:
+        set_emd_threads(prev)
+
+
+def _emd_over_batch(B, one):
+    """one(lo, hi) runs the C function on pairs lo..hi-1 (views of the batch arrays, outputs written in place)."""
+    global _EMD_POOL
+    if _EMD_THREADS == 1 or B <= 1:
+        one(0, B)
+        return
+    if _EMD_POOL is None:
+        from concurrent.futures import ThreadPoolExecutor
+        _EMD_POOL = ThreadPoolExecutor(max_workers=_EMD_THREADS, thread_name_prefix="orc_emd")
+    for f in [_EMD_POOL.submit(one, i, i + 1) for i in range(B)]:
+        f.result()
+
+
 def emd_approxmatch(xyz1, xyz2):
     """emd_kernel.cu:25-158 / :171-193 -> match[B,m,n]"""
     dt, pt, suf = _emd_t(xyz1.dtype)
@@ -166,7 +214,8 @@ def emd_approxmatch(xyz1, xyz2):
     B, n, _ = xyz1.shape
     m = xyz2.shape[1]
     match = np.empty((B, m, n), dt)
-    getattr(lib(), "orc_emd_approxmatch_" + suf)(_p(xyz1, pt), _p(xyz2, pt), B, n, m, _p(match, pt))
+    fn = getattr(lib(), "orc_emd_approxmatch_" + suf)
+    _emd_over_batch(B, lambda lo, hi: fn(_p(xyz1[lo:hi], pt), _p(xyz2[lo:hi], pt), hi - lo, n, m, _p(match[lo:hi], pt)))
     return match
 
 
@@ -177,7 +226,9 @@ def emd_matchcost(xyz1, xyz2, match):
     B, n, _ = xyz1.shape
     m = xyz2.shape[1]
     cost = np.empty((B,), dt)
-    getattr(lib(), "orc_emd_matchcost_" + suf)(_p(xyz1, pt), _p(xyz2, pt), _p(match, pt), B, n, m, _p(cost, pt))
+    fn = getattr(lib(), "orc_emd_matchcost_" + suf)
+    _emd_over_batch(B, lambda lo, hi: fn(_p(xyz1[lo:hi], pt), _p(xyz2[lo:hi], pt), _p(match[lo:hi], pt), hi - lo, n, m,
+                                         _p(cost[lo:hi], pt)))
     return cost
 
 
@@ -189,8 +240,9 @@ def emd_matchcost_grad(grad_cost, xyz1, xyz2, match):
     m = xyz2.shape[1]
     g1 = np.empty((B, n, 3), dt)
     g2 = np.empty((B, m, 3), dt)
-    getattr(lib(), "orc_emd_matchcost_grad_" + suf)(_p(grad_cost, pt), _p(xyz1, pt), _p(xyz2, pt), _p(match, pt),
-                                                     B, n, m, _p(g1, pt), _p(g2, pt))
+    fn = getattr(lib(), "orc_emd_matchcost_grad_" + suf)
+    _emd_over_batch(B, lambda lo, hi: fn(_p(grad_cost[lo:hi], pt), _p(xyz1[lo:hi], pt), _p(xyz2[lo:hi], pt), _p(match[lo:hi], pt),
+                                         hi - lo, n, m, _p(g1[lo:hi], pt), _p(g2[lo:hi], pt)))
     return g1, g2
 
 

@@ -190,8 +190,10 @@ __global__ __launch_bounds__(NW * 64) void pool_point_kernel(PointArgs p) {
             const int m_ = min(64, n_ - h0);
             // the row's (channel, gradient) pairs go through a wavefront-private 512 bytes of LDS and come back as BROADCAST
             // reads (every lane the same address): the two v_readlane per hit and their wait states were half the hit's issue
-            // slots (same wavefront writes and reads: in order, no barrier)
+            // slots (same wavefront writes and reads: in order in hardware; the wave barriers emit no instruction, they keep the
+            // compiler from moving the cross-lane reads over the stores - as wsgemm.hip does for its stage patch)
             hslot[wave][lane] = cur_h;
+            __builtin_amdgcn_wave_barrier();
             int h = 0;
             for (; h + 1 < m_; h += 2) {      // two hits per trip: two LDS reads in flight
               const uint4 two = *reinterpret_cast<const uint4*>(&hslot[wave][h]);
@@ -210,6 +212,7 @@ __global__ __launch_bounds__(NW * 64) void pool_point_kernel(PointArgs p) {
               asm volatile("" : "+v"(g0));
               s0 += g0 * *reinterpret_cast<const v2f*>(wl + (int)one.x * PP_COLS);
             }
+            __builtin_amdgcn_wave_barrier();      // before the next 64 hits / the next row overwrite the slots
           }
           v2f row = s0 + s1;
           const v2f gate = pv[u] + qv[u];      // the forward's own expression: relu(P'[j] + Q[g]) is on where this is > 0

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from oracle import model_ref as mr
+from tests._oracle_compare import _check_flips, _device_winners
 
 pytestmark = pytest.mark.gpu
 
@@ -151,40 +152,6 @@ def test_training_step_vs_reference(golden_loss, dev, loss_mode):
         rms = float(norm) / max(1.0, flat.numel() ** 0.5)
         np.testing.assert_allclose(flat[idx].cpu().numpy(), samp, rtol=rt_s, atol=1e-6 * total + 0.05 * rms,
                                    err_msg=str(name))
-
-
-def _device_winners(m, capture):
-    """ops.WINNER_CAPTURE of one forward of the product model -> the keys oracle.model_ref.RefModel.pin_winners takes."""
-    from puzzlenet_amd import _lib
-    if _lib.load().pzn_gemm_get_precision() == 0:
-        # (PZN_GEMM_PRECISION=f32: the encoders' global max then goes through the plain max over points, whose captures carry no
-        # owner - three of them could not be told apart below; the fingerprint test covers that mode)
-        pytest.skip("the winner pinning needs the split-precision paths' captures (default mode)")
-    owner = {}
-    for tag, enc in (("Encoder.", m.Encoder), ("Encoder2.", m.Encoder2)):
-        owner[enc.mlp4.weight.data_ptr()] = tag + "sa1"
-        owner[enc.mlp6.weight.data_ptr()] = tag + "sa2"
-        owner[enc.out.weight.data_ptr()] = tag + "gmax"
-    win = {}
-    for kind, ptr, arg in capture:
-        key = "heads.gmax" if kind == "maxpts" else owner[ptr]
-        assert key not in win, key
-        win[key] = arg.detach().cpu().to(torch.long)
-    assert len(win) == 7, sorted(win)
-    return win
-
-
-def _check_flips(pins, max_flips=16, max_gap=1e-5):
-    """The oracle's own arg-max differs from the pinned (device) winner only on near-ties: a handful of entries, each with
-    the two candidates closer than fp32 rounding of the sums in front of them."""
-    total = 0
-    for key, (n, gap, of) in sorted(pins["flips"].items()):
-        total += n
-        assert gap <= max_gap, (key, n, gap)
-    print("max-pool winners that differ from the oracle's own:", {k: v[0] for k, v in pins["flips"].items() if v[0]}, "of",
-          sum(v[2] for v in pins["flips"].values()))
-    assert total <= max_flips, pins["flips"]
-    return total
 
 
 @pytest.mark.parametrize("loss_mode", [0, 1])

@@ -49,3 +49,29 @@ def test_hand_derived_capacity_vectors():
         w1, w2 = ev.gradients(x1, x2, match, 1.5)
         np.testing.assert_allclose(g1, w1, rtol=1e-4, atol=1e-4, err_msg=case.__name__)
         np.testing.assert_allclose(g2, w2, rtol=1e-4, atol=1e-4, err_msg=case.__name__)
+
+
+def test_threaded_batch_equals_one_thread():
+    """point_ops.set_emd_threads(n): the batch's pairs go to a thread pool one by one, each through the same C function with
+    its own scratch, so match, cost and both gradients are the one-thread run's bits (float and double); the default,
+    which bench.py's cpu_baseline reports as "EMD = 1-thread C", stays one thread."""
+    assert orc.get_emd_threads() == 1
+    rng = np.random.default_rng(7)
+    for n, m in [(128, 128), (100, 300)]:
+        for dt in (np.float32, np.float64):
+            x1 = rng.random((5, n, 3)).astype(dt)
+            x2 = rng.random((5, m, 3)).astype(dt)
+            gc = rng.random(5).astype(dt)
+
+            def run():
+                match = orc.emd_approxmatch(x1, x2)
+                return (match, orc.emd_matchcost(x1, x2, match)) + orc.emd_matchcost_grad(gc, x1, x2, match)
+            one = run()
+            with orc.emd_threads(4):
+                assert orc.get_emd_threads() == 4
+                four = run()
+            assert orc.get_emd_threads() == 1
+            for name, a, b in zip(("match", "cost", "grad1", "grad2"), one, four):
+                assert a.dtype == dt and np.abs(a).max() > 0
+                assert np.array_equal(a, b), (name, n, m, dt)
+    assert orc.set_emd_threads(3) == 1 and orc.set_emd_threads(1) == 3
