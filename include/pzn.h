@@ -651,6 +651,18 @@ int pzn_adam_step_f32(float* param, const float* grad, float* exp_avg, float* ex
 int pzn_cut_compact_f32(const float* raw, const double* normals, const double* zs, const double* u, int B, int M,
                         int K, int n_min, int cap, float* pieces, int64_t* counts, int64_t* start, double* plane,
                         uint8_t* ok, pzn_stream_t stream);
+/* dataset.py:715-759 (sphere_split / cylinder_split / cone_split) + 1175-1179 (the re-draw loop) for a batch, one launch; the
+ * contract of pzn_cut_compact_f32 with a solid in place of the plane.  kind 0 sphere, 1 cylinder, 2 cone (uniform per launch);
+ * params float64 [B,K,6] = (rot[3] = np.random.rand(3,1), shift[3] = np.random.rand(3,1)/3) per candidate: the sphere ignores
+ * rot, the cone ignores shift.  `up` (rows 0..B-1 of pieces) = strictly INSIDE the polyhedron open3d 0.15.2 builds at
+ * resolution 50 (create_sphere(0.5, 50) translated by shift; create_cylinder(0.6, 1, 50) rotated by the axis-angle vector rot
+ * about the origin, then translated by shift; create_cone(1, 2, 50) translated by (0,0,-1), then rotated by rot), `down` (rows
+ * B..2B-1) = the rest; float64, no fma.  The FIRST candidate with n_min <= n_up and n_min <= M - n_up is taken (none: the most
+ * balanced one, the first among equals, ok = 0; ok = 0 also when a piece exceeds cap).  pieces, counts, start as in
+ * pzn_cut_compact_f32; chosen float64 [B,6] = the parameters taken, chosen_k int32 [B] their candidate index; ok uint8 [B]. */
+int pzn_cut_compact_solid_f32(const float* raw, int kind, const double* params, const double* u, int B, int M, int K,
+                              int n_min, int cap, float* pieces, int64_t* counts, int64_t* start, double* chosen,
+                              int32_t* chosen_k, uint8_t* ok, pzn_stream_t stream);
 /* dataset.py:1363-1366: 0/1 masks [R,N] with ones at the k picked rows idx int64 [R,k] of each cloud. */
 int pzn_pick_mask_f32(const int64_t* idx, int R, int k, int N, float* mask, pzn_stream_t stream);
 

@@ -23,6 +23,14 @@ in this image, so its published mesh construction is restated (oracle/solids.py:
 create_cylinder / create_cone at resolution 50) and `solid_cut_mask` evaluates membership of exactly those convex
 polyhedra in closed form; tests/test_datapipe_cpu.py holds it to the oracle's brute-force face-plane test point for
 point.  Parity is pinned to that restatement, not to the library itself (no fixture can be produced here).
+
+For a loader that runs BESIDE the training step there is `PairFeeder`: a fresh batch per step on a background stream, cut by
+a plane (`cut_pairs`: csrc/datapipe.hip) or by one of the three solids (`PairFeeder(..., cut="sphere" | "cylinder" | "cone")`
+-> `cut_pairs_solid`: csrc/solidcut.hip).  Either cut is ONE launch per batch: K candidate draws per sample (`solid_draws`
+for the solids), the first that leaves >= n points in both pieces taken on the device (the reference's re-draw loop,
+dataset.py:1175-1180), both pieces compacted in point order and padded, the FPS start indices.  The solid kernel tests the
+same polyhedra as `solid_cut_mask`, face plane by face plane with the rotation families folded (no atan2 / acos per point);
+tests/test_gpu_solid_feeder.py holds its pieces to the oracle's masks bit for bit.
 """
 import numpy as np
 import torch
@@ -283,12 +291,47 @@ def cut_pairs(raw, normals, zs, u, twist, n=1024, k=128, cap=None):
     return (down, moved, g, up, bnd[B:], bnd[:B], masks[B:], masks[:B]), ok & (counts[:B] >= n) & (counts[B:] >= n), plane
 
 
+def solid_draws(rng, B, K):
+    """K candidate solids per sample from ONE rng.rand(B, K, 6): columns 0-2 the axis-angle vector np.random.rand(3,1)
+    (dataset.py:732, :749), columns 3-5 the translation np.random.rand(3,1)/3 (:718, :733).  -> [B,K,6] float64"""
+    p = rng.rand(B, K, 6)
+    p[:, :, 3:] /= 3
+    return p
+
+
+def cut_pairs_solid(raw, kind, params, u, twist, n=1024, k=128, cap=None):
+    """cut_pairs with a sphere / cylinder / cone cut (dataset.py:715-759; the mesh's inside is `up`) in front: K candidate
+    solids per sample, the first valid one taken on the device, both pieces compacted and padded, the FPS start indices -
+    one launch (csrc/solidcut.hip, ops.cut_compact_solid); the rest is cut_pairs' tail.  raw [B,M,3]; kind "sphere" |
+    "cylinder" | "cone"; params [B,K,6] (rot, shift: solid_draws), u [B,2] float64 draws; twist [B,6].
+    -> ((down, moved_up, igt, up, down_boundary, up_boundary, down_mask, up_mask), ok [B], chosen [B,6])"""
+    if not raw.is_cuda:
+        raise _lib.PznError("datapipe.cut_pairs_solid runs on the GPU (puzzlenet_amd has no CPU fallback)")
+    B, M, _ = raw.shape
+    cap = M if cap is None else int(cap)
+    if cap > 32768:
+        raise _lib.PznUnsupported(f"cut_pairs_solid: pieces of up to {cap} points (the FPS kernel holds <= 32768)")
+    pieces, counts, start, chosen, _, ok = ops.cut_compact_solid(raw, kind, params, u, n, cap)
+    # (a valid cut leaves >= n points on either side, so a piece holds <= M - n; rows of samples without a valid cut are re-drawn)
+    idx = ops.farthest_point_sample(pieces, n, start, background=True, counts=counts, max_count=max(M - n, n))      # dataset.py:1147-1163
+    both = ops.index_points(pieces, idx)
+    up, down = both[:B], both[B:]
+    cd_over_up, cd_over_down = ops.chamfer(down, up)                                             # dataset.py:1357-1367
+    top = ops.topk_rows(torch.cat([cd_over_up, cd_over_down], 0).neg_(), k)                      # [2B,k]: up picks, down picks
+    bnd = ops.index_points(both, top)
+    masks = ops.pick_mask(top, n)
+    g = se3.exp(twist.to(torch.float32))                                                         # transforms.py:176-186
+    moved = se3.transform_points(g, up)
+    return (down, moved, g, up, bnd[B:], bnd[:B], masks[B:], masks[:B]), ok & (counts[:B] >= n) & (counts[B:] >= n), chosen
+
+
 class PairBatch(list):
     """The 8-tuple of a training batch + `ready`: the event behind which its tensors exist (they were produced on the
-    feeder's stream), + `ok` [B] (a valid plane was among the candidates)."""
+    feeder's stream), + `ok` [B] (a valid cut was among the candidates)."""
     ready = None
     ok = None
-    plane = None      # (normal [B,3], z [B]) float64: the plane each sample was cut with
+    plane = None      # (normal [B,3], z [B]) float64: the plane each sample was cut with (cut="plane")
+    cut = None        # (kind, rot [B,3], shift [B,3]) float64: the solid each sample was cut with (cut=a solid)
 
 
 class PairFeeder:
@@ -300,7 +343,10 @@ class PairFeeder:
     in next_batch() waits for the device.  engine.TrainStep.step(next_batch=feeder.next_batch()) orders its streams behind
     `ready` and keeps the tensors alive across the streams that read them."""
 
-    def __init__(self, raw, device, n=1024, k=128, mag=0.8, candidates=16, seed=0):
+    def __init__(self, raw, device, n=1024, k=128, mag=0.8, candidates=16, seed=0, cut="plane"):
+        if cut != "plane" and cut not in ops.SOLID_KINDS:
+            raise _lib.PznError(f"PairFeeder: cut={cut!r} (one of 'plane', 'sphere', 'cylinder', 'cone')")
+        self.cut = cut
         raw = torch.as_tensor(raw, dtype=torch.float32)
         if raw.dim() != 3 or raw.shape[2] != 3:
             raise _lib.PznError("PairFeeder: raw clouds as [B, M, 3]")
@@ -314,12 +360,14 @@ class PairFeeder:
         self.stream = torch.cuda.Stream(device=self.device)
         B = self.raw.shape[0]
         # one pinned staging block per batch in flight (two: the upload of batch k + 1 may still be queued when k + 2 is drawn)
-        self._width = self.K * 3 + self.K + 2 + 6
+        self._width = self.K * 3 + self.K + 2 + 6 if cut == "plane" else self.K * 6 + 2 + 6
         self._stage = [torch.empty((B, self._width), dtype=torch.float64, pin_memory=True) for _ in range(3)]
         self._turn = 0
         self._busy = [None] * 3
 
     def next_batch(self):
+        if self.cut != "plane":
+            return self._next_batch_solid()
         B, K, n = self.raw.shape[0], self.K, self.n
         st = self._stage[self._turn]
         if self._busy[self._turn] is not None:
@@ -342,6 +390,31 @@ class PairFeeder:
         self._turn = (self._turn + 1) % 3
         out = PairBatch(tensors)
         out.ready, out.ok, out.plane = ready, ok, (plane[:, :3], plane[:, 3])
+        return out
+
+    def _next_batch_solid(self):
+        """next_batch() for cut = a solid: the same protocol, K (rot, shift) candidates in place of the K planes."""
+        B, K, n = self.raw.shape[0], self.K, self.n
+        st = self._stage[self._turn]
+        if self._busy[self._turn] is not None:
+            self._busy[self._turn].synchronize()          # (three batches back: long done)
+        h = st.numpy()
+        h[:, :6 * K] = solid_draws(self.rng, B, K).reshape(B, 6 * K)            # dataset.py:718, 732-733, 749
+        h[:, 6 * K:6 * K + 2] = self.rng.rand(B, 2)                             # FPS start points as fractions of the piece sizes, :1153
+        x = torch.randn(B, 6, generator=self.gen, dtype=torch.float64)          # transforms.py:163-168
+        h[:, 6 * K + 2:] = (x / x.norm(p=2, dim=1, keepdim=True) * self.mag).numpy()
+        with torch.cuda.stream(self.stream):
+            d = st.to(self.device, non_blocking=True)
+            up_ev = torch.cuda.Event()
+            up_ev.record(self.stream)
+            self._busy[self._turn] = up_ev
+            tensors, ok, chosen = cut_pairs_solid(self.raw, self.cut, d[:, :6 * K].reshape(B, K, 6), d[:, 6 * K:6 * K + 2],
+                                                  d[:, 6 * K + 2:], n=n, k=self.k)
+            ready = torch.cuda.Event()
+            ready.record(self.stream)
+        self._turn = (self._turn + 1) % 3
+        out = PairBatch(tensors)
+        out.ready, out.ok, out.cut = ready, ok, (self.cut, chosen[:, :3], chosen[:, 3:])
         return out
 
     def close(self):

@@ -427,6 +427,35 @@ def cut_compact(raw, normals, zs, u, n_min, cap):
     return pieces, counts, start, plane, ok.to(torch.bool)
 
 
+SOLID_KINDS = ("sphere", "cylinder", "cone")      # the `kind` codes of pzn_cut_compact_solid_f32
+
+
+def cut_compact_solid(raw, kind, params, u, n_min, cap):
+    """dataset.py:715-759 + 1175-1179 for a batch in one launch (pzn_cut_compact_solid_f32): raw [B,M,3] f32, kind "sphere" |
+    "cylinder" | "cone", K candidate solids per sample (params [B,K,6] float64: rot, shift), start fractions u [B,2] float64
+    -> (pieces [2B,cap,3]: up (inside) pieces then down pieces, counts [2B] int64, start [2B] int64, chosen [B,6] float64,
+        chosen_k [B] int32, ok [B] bool)"""
+    if kind not in SOLID_KINDS:
+        raise _lib.PznError(f"cut_compact_solid: unknown solid {kind!r} (one of {SOLID_KINDS})")
+    raw = _f32(raw, "raw")
+    params, u = _req(params, torch.float64, "params"), _req(u, torch.float64, "u")
+    B, M, _ = raw.shape
+    if params.dim() != 3 or params.shape[0] != B or params.shape[2] != 6 or tuple(u.shape) != (B, 2):
+        raise _lib.PznError("cut_compact_solid: params as [B, K, 6] and u as [B, 2]")
+    K = params.shape[1]
+    dev = raw.device
+    pieces = torch.empty((2 * B, int(cap), 3), dtype=torch.float32, device=dev)
+    counts = torch.empty((2 * B,), dtype=torch.int64, device=dev)
+    start = torch.empty((2 * B,), dtype=torch.int64, device=dev)
+    chosen = torch.empty((B, 6), dtype=torch.float64, device=dev)
+    chosen_k = torch.empty((B,), dtype=torch.int32, device=dev)
+    ok = torch.empty((B,), dtype=torch.uint8, device=dev)
+    with _on(dev):
+        _call("pzn_cut_compact_solid_f32", _p(raw), SOLID_KINDS.index(kind), _p(params), _p(u), B, M, K, int(n_min), int(cap),
+              _p(pieces), _p(counts), _p(start), _p(chosen), _p(chosen_k), _p(ok), _stream())
+    return pieces, counts, start, chosen, chosen_k, ok.to(torch.bool)
+
+
 def pick_mask(idx, N):
     """0/1 float masks [R,N] with ones at idx [R,k] (dataset.py:1363-1366), one launch."""
     idx = _i64(idx, "idx")

@@ -1,0 +1,79 @@
+"""CPU: the plumbing of the solid-cut loader (sphere / cylinder / cone cuts in one launch per batch): the entry point is
+declared and bound with one arity, the candidate draws have the reference's ranges and order, and the feeder refuses what it
+cannot run before it touches a device.  The kernel itself is held to the oracle in tests/test_gpu_solid_feeder.py."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _declaration(name):
+    src = open(os.path.join(ROOT, "include", "pzn.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    m = re.search(r"\b" + name + r"\s*\(([^)]*)\)\s*;", src)
+    assert m, f"include/pzn.h does not declare {name}"
+    return [a.strip() for a in m.group(1).split(",")]
+
+
+def test_header_and_binding_table_agree_on_the_solid_cut():
+    from puzzlenet_amd import _lib
+    args = _declaration("pzn_cut_compact_solid_f32")
+    assert "pzn_cut_compact_solid_f32" in _lib.SIGNATURES
+    res, bound = _lib.SIGNATURES["pzn_cut_compact_solid_f32"]
+    assert res is _lib._c_i and len(bound) == len(args) == 16
+    # pointers travel as addresses, the scalars (kind, B, M, K, n_min, cap) as ints: position by position
+    for decl, ctype in zip(args, bound):
+        assert (ctype is _lib._c_i) == decl.startswith("int "), (decl, ctype)
+    assert args[1] == "int kind" and args[-1] == "pzn_stream_t stream"
+
+
+def test_solid_cut_is_listed_for_integrators():
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    row = [l for l in doc.splitlines() if l.startswith("| `pzn_cut_compact_solid_f32`")]
+    assert len(row) == 1 and "ops.cut_compact_solid" in row[0] and "dataset.py" in row[0]
+
+
+def test_solid_draws_shape_ranges_and_order():
+    from puzzlenet_amd import datapipe
+    B, K = 7, 5
+    p = datapipe.solid_draws(np.random.RandomState(42), B, K)
+    assert p.shape == (B, K, 6) and p.dtype == np.float64
+    assert p[:, :, :3].min() >= 0 and p[:, :, :3].max() < 1                 # np.random.rand(3,1)
+    assert p[:, :, 3:].min() >= 0 and p[:, :, 3:].max() < 1 / 3            # np.random.rand(3,1)/3
+    want = np.random.RandomState(42).rand(B, K, 6)                          # ONE draw, sample-major, rot before shift
+    assert np.array_equal(p[:, :, :3], want[:, :, :3]) and np.array_equal(p[:, :, 3:], want[:, :, 3:] / 3)
+    big = datapipe.solid_draws(np.random.RandomState(1), 64, 16)
+    assert big[:, :, :3].max() > 0.99 and big[:, :, 3:].max() > 0.33       # (the ranges are filled, not merely respected)
+    # the generator has advanced by exactly B*K*6 uniforms
+    r1, r2 = np.random.RandomState(9), np.random.RandomState(9)
+    datapipe.solid_draws(r1, B, K)
+    r2.rand(B * K * 6)
+    assert r1.rand() == r2.rand()
+
+
+@pytest.mark.parametrize("cut", ["sphere", "torus"])
+def test_feeder_refuses_in_the_constructor(cut):
+    """A solid kind on the CPU: there is no CPU fallback.  An unknown kind: refused before any device work."""
+    from puzzlenet_amd import _lib, datapipe
+    raw = np.zeros((2, 64, 3), dtype=np.float32)
+    with pytest.raises(_lib.PznError):
+        datapipe.PairFeeder(raw, "cpu", cut=cut)
+
+
+def test_unknown_cut_is_refused_before_the_device_is_looked_at():
+    from puzzlenet_amd import _lib, datapipe
+    with pytest.raises(_lib.PznError, match="torus"):
+        datapipe.PairFeeder(np.zeros((2, 64, 3), dtype=np.float32), "cuda:0", cut="torus")
+
+
+def test_ops_cut_compact_solid_rejects_cpu_tensors_and_unknown_kinds():
+    import torch
+    from puzzlenet_amd import _lib, ops
+    raw, params, u = torch.zeros(1, 8, 3), torch.zeros(1, 2, 6, dtype=torch.float64), torch.zeros(1, 2, dtype=torch.float64)
+    with pytest.raises(_lib.PznError):
+        ops.cut_compact_solid(raw, "sphere", params, u, 1, 8)
+    with pytest.raises(_lib.PznError, match="torus"):
+        ops.cut_compact_solid(raw, "torus", params, u, 1, 8)

@@ -1,10 +1,20 @@
 """GPU training-pair construction (puzzlenet_amd/datapipe.py): pairs per second for raw clouds of M points cut, sampled
 to N, labelled and moved — next to the training step's consumption rate, and to the reference-style numpy FPS of ONE
-piece on one host core (the dominant cost of the reference's per-sample CPU pipeline)."""
-import os, sys, time
+piece on one host core (the dominant cost of the reference's per-sample CPU pipeline).
+
+    python tools/bench_datapipe.py [--cut {plane,sphere,cylinder,cone}] [--reps 30]
+
+Then the loader's batch as PairFeeder builds it, B = 64, M = 10000, N = 2048, 16 candidates: datapipe.cut_pairs (plane) and, with
+--cut a solid, datapipe.cut_pairs_solid of that kind next to the tensor form datapipe.make_pairs_solid on the same clouds with the
+one candidate the kernel took - one process, the forms alternating inside every repetition, a device synchronise around each."""
+import argparse, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from puzzlenet_amd import datapipe
+ap = argparse.ArgumentParser()
+ap.add_argument("--cut", choices=["plane", "sphere", "cylinder", "cone"], default="plane")
+ap.add_argument("--reps", type=int, default=30)
+a = ap.parse_args()
 dev = torch.device('cuda:0')
 g = torch.Generator().manual_seed(0)
 for (B, M, N) in [(64, 6000, 1024), (64, 10000, 2048), (64, 12000, 2048)]:
@@ -31,3 +41,31 @@ for i in range(2048):
     d = np.sum((pts - pts[far]) ** 2, -1)
     m = d < distance; distance[m] = d[m]; far = np.argmax(distance, -1)
 print('numpy FPS 5000 -> 2048 on one host core: %.1f ms per piece' % ((time.perf_counter() - t0) * 1e3))
+
+# the feeder's batch (PairFeeder.next_batch without the host draws and the upload), forms alternating
+B, M, N, K = 64, 10000, 2048, 16
+rng = np.random.RandomState(0)
+raw = (torch.rand(B, M, 3, generator=g) - 0.5).to(dev)
+u = torch.from_numpy(rng.rand(B, 2)).to(dev)
+tw = torch.randn(B, 6, generator=g, dtype=torch.float64); tw = (tw / tw.norm(dim=1, keepdim=True) * 0.8).to(dev)
+normals = torch.from_numpy(rng.rand(B, K, 3)).to(dev)
+zs = torch.from_numpy(rng.rand(B, K) / 3 - 0.4).to(dev)
+forms = {"plane: cut_pairs": lambda: datapipe.cut_pairs(raw, normals, zs, u, tw, n=N)[1]}
+if a.cut != "plane":
+    params = torch.from_numpy(datapipe.solid_draws(rng, B, K)).to(dev)
+    _, ok, chosen = datapipe.cut_pairs_solid(raw, a.cut, params, u, tw, n=N)
+    print('%s: valid cuts among %d candidates %d/%d' % (a.cut, K, int(ok.sum()), B), flush=True)
+    rot, shift, s0 = chosen[:, :3].contiguous(), chosen[:, 3:].contiguous(), torch.zeros(B, dtype=torch.int64, device=dev)
+    forms[a.cut + ": cut_pairs_solid"] = lambda: datapipe.cut_pairs_solid(raw, a.cut, params, u, tw, n=N)[1]
+    forms[a.cut + ": make_pairs_solid (tensor form, one candidate)"] = lambda: datapipe.make_pairs_solid(raw, a.cut, rot, shift, s0, s0, tw, n=N)[1]
+times = {name: [] for name in forms}
+for rep in range(a.reps + 3):
+    for name, fn in forms.items():
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        if rep >= 3:                                     # (three warm-up rounds of every form)
+            times[name].append(time.perf_counter() - t0)
+for name, t in times.items():
+    t = np.sort(np.array(t)) * 1e3
+    print('B=%d M=%d -> N=%d  %-55s %.2f ms per batch (median of %d; min %.2f, max %.2f)' % (B, M, N, name, np.median(t), len(t), t[0], t[-1]), flush=True)
