@@ -74,7 +74,10 @@ int pzn_fps_f32(const float* xyz, int B, int N, int npoint,
  * LDS-tiled kernels keep their CUs.  N <= 32768.  counts (NULL or int64 [B]): rows >= counts[b] of cloud b are padding
  * (copies of row 0, which never win) and are left out of the rounds.  max_count (0: unknown): the caller's promise that
  * counts[b] <= max_count for every cloud - a cut piece holds at most M - n of the raw cloud's M points - which lets the
- * launch hold only that many rows in registers (fewer, faster wavefronts); rows beyond it are never read. */
+ * launch hold only that many rows in registers (fewer, faster wavefronts); rows beyond it are never read.  counts[b] < 0 =
+ * a piece that does not exist (pzn_cut_compact_double_f32): a workgroup all of whose pieces are such writes index 0 to every
+ * output slot of them and returns without a round; beside a real piece in the same workgroup (B even: pieces b and b + B / 2
+ * share one) it counts as 1 row, as counts[b] = 0 does. */
 int pzn_fps_background_f32(const float* xyz, int B, int N, int npoint,
                            const int64_t* start_idx, int64_t* out_idx,
                            const int64_t* counts, int max_count, pzn_stream_t stream);
@@ -663,6 +666,23 @@ int pzn_cut_compact_f32(const float* raw, const double* normals, const double* z
 int pzn_cut_compact_solid_f32(const float* raw, int kind, const double* params, const double* u, int B, int M, int K,
                               int n_min, int cap, float* pieces, int64_t* counts, int64_t* start, double* chosen,
                               int32_t* chosen_k, uint8_t* ok, pzn_stream_t stream);
+/* dataset.py:1203-1355 (CADDataset.__getitem__ with split_twice=True, `train.py --random_slice`) up to the sampling, for a
+ * batch, one launch: steps 1-7 of datapipe.double_cut_rule, which is the statement of this entry point.  Draws per sample:
+ * normals1 float64 [B,K,3], zs1 float64 [B,K] = K candidates for plane 1; normals2 float64 [B,7,3], zs2 float64 [B,7] = the
+ * first draw of plane 2 and the six re-draws of `while time <= 5`; u float64 [B,7] = u_seed, u_se, u_choice, u_sU, u_sD, u_sFU,
+ * u_sFD.  side = (points . normal + z >= 0), float64, no fma, as in pzn_cut_compact_f32.  n_min: the points a piece must hold
+ * (the reference's 1024); n_rich: the points a piece must hold to be cut again (the reference's 3000, dataset.py:1214-1217).
+ * pieces [4B,cap,3]: rows 0..B-1 U, B..2B-1 D, 2B..3B-1 / 3B..4B-1 the pair of plane 1 alone that replaces a HALF_VS_OTHER
+ * pair whose boundaries do not touch; each piece = rows of its first region table, then of its second, in the cloud's point
+ * order, padded with copies of its first row.  counts int64 [4B] (-1 in the fallback rows of samples that are not
+ * HALF_VS_OTHER: their rows are copies of the cloud's first point); start int64 [4B] = clamp(floor(u * count), 0, count - 1);
+ * kind int32 [B] (0 SINGLE, 1 HALF_VS_REST, 2 HALF_VS_OTHER, 3 HALVES); planes float64 [B,2,4] = (normal, z) of the two planes
+ * taken (plane 2 zero for SINGLE); tabs int32 [B,4] = the region tables u_tab[2], d_tab[2] (bit 2 s1 + s2); ok uint8 [B]: 0 when
+ * SINGLE found no valid candidate among the K (the most balanced one is taken, the first among equals) or a piece exceeds cap. */
+int pzn_cut_compact_double_f32(const float* raw, const double* normals1, const double* zs1, const double* normals2,
+                               const double* zs2, const double* u, int B, int M, int K, int n_min, int n_rich, int cap,
+                               float* pieces, int64_t* counts, int64_t* start, int32_t* kind, double* planes, int32_t* tabs,
+                               uint8_t* ok, pzn_stream_t stream);
 /* dataset.py:1363-1366: 0/1 masks [R,N] with ones at the k picked rows idx int64 [R,k] of each cloud. */
 int pzn_pick_mask_f32(const int64_t* idx, int R, int k, int N, float* mask, pzn_stream_t stream);
 

@@ -135,6 +135,7 @@ SIGNATURES = {
     "pzn_attn_bwd_f32": (_c_i, [_c_f] * 6 + [_c_i] * 4 + [_c_f] * 5),
     "pzn_cut_compact_f32": (_c_i, [_c_f] * 4 + [_c_i] * 5 + [_c_f] * 6),
     "pzn_cut_compact_solid_f32": (_c_i, [_c_f, _c_i, _c_f, _c_f] + [_c_i] * 5 + [_c_f] * 7),
+    "pzn_cut_compact_double_f32": (_c_i, [_c_f] * 6 + [_c_i] * 6 + [_c_f] * 8),
     "pzn_pick_mask_f32": (_c_i, [_c_f, _c_i, _c_i, _c_i, _c_f, _c_f]),
     "pzn_chamfer_bwd_f32": (_c_i, [_c_f, _c_f, _c_i, _c_i, _c_i, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
 }

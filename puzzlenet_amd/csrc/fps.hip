@@ -81,6 +81,18 @@ __global__ __launch_bounds__(T * G) void fps_kernel(const float* __restrict__ xy
   const int wave = tid / PZN_WAVE;
   const float* g = xyz + (size_t)b * N * 3;
 
+  // counts < 0 = a piece that does not exist (the fallback rows of pzn_cut_compact_double_f32): when that holds for every piece
+  // of the workgroup it writes index 0 everywhere and leaves before the first barrier, so it holds no CU for npoint rounds
+  if (counts) {
+    bool skip = true;
+#pragma unroll
+    for (int q = 0; q < G; ++q) skip = skip && counts[blockIdx.x + q * gridDim.x] < 0;
+    if (skip) {      // (workgroup-uniform)
+      for (int t = tid; t < npoint; t += T) out[(size_t)b * npoint + t] = 0;
+      return;
+    }
+  }
+
   float px[PPT], py[PPT], pz[PPT], dist[PPT];
   // the no-image form keeps its points as PAIRS of register slots (2q, 2q + 1): the distance update is packed fp32 - two points
   // per instruction, every operation individually rounded as in sqdist3 (this file is built with -ffp-contract=off) -: with

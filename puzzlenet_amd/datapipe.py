@@ -31,7 +31,12 @@ for the solids), the first that leaves >= n points in both pieces taken on the d
 dataset.py:1175-1180), both pieces compacted in point order and padded, the FPS start indices.  The solid kernel tests the
 same polyhedra as `solid_cut_mask`, face plane by face plane with the rotation families folded (no atan2 / acos per point);
 tests/test_gpu_solid_feeder.py holds its pieces to the oracle's masks bit for bit.
+`PairFeeder(..., split_twice=True)` is the reference's second sampling mode (`train.py --random_slice`, dataset.py:1203-1355):
+the double cuts, decided and compacted on the device in one launch (`double_cut_rule` states the rule, csrc/doublecut.hip runs
+it, `cut_pairs_double` samples the pair and its fallback and applies the reference's acceptance test without a host round trip).
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -325,6 +330,56 @@ def cut_pairs_solid(raw, kind, params, u, twist, n=1024, k=128, cap=None):
     return (down, moved, g, up, bnd[B:], bnd[:B], masks[B:], masks[:B]), ok & (counts[:B] >= n) & (counts[B:] >= n), chosen
 
 
+DoubleCut = collections.namedtuple("DoubleCut", "kind planes tabs rejected cd U D Ub Db")
+DoubleCut.__doc__ = """What cut_pairs_double decided per sample: kind [B] int32 (SINGLE .. HALVES), planes [B,2,4] float64 (normal, z of
+plane 1 and plane 2; plane 2 zero for SINGLE), tabs [B,4] int32 (u_tab, d_tab), rejected [B] bool (the HALF_VS_OTHER pair was
+replaced by its fallback), cd [B] float32 (chamfer distance of the primary pair's boundaries) and the PRIMARY pair itself
+(U, D [B,n,3]; Ub, Db [B,k,3]), from which cd can be recomputed."""
+
+
+def cut_pairs_double(raw, normals1, zs1, normals2, zs2, u, twist, n=1024, n_rich=None, k=128, cap=None):
+    """cut_pairs for the reference's double cuts (dataset.py:1203-1355, split_twice=True; the rule: double_cut_rule): steps 1-7
+    - branch decisions, region tables, the two-segment compaction of U, D and the HALF_VS_OTHER fallback pair, start indices -
+    are one launch (csrc/doublecut.hip, ops.cut_compact_double); then the sampling of the primary and of the fallback rows (the
+    second launch runs rounds for the HALF_VS_OTHER samples only: the other rows carry counts = -1), the primary pair's
+    boundary, step 8 (`cd` of the two boundaries against 0.015, :1253-1256) as a device-side select, and cut_pairs' tail on the
+    final pair.  Nothing here reads a value back to the host.  raw [B,M,3]; normals1 [B,K,3], zs1 [B,K], normals2 [B,7,3],
+    zs2 [B,7], u [B,7] float64 draws; twist [B,6]; n_rich: None = 3000 n / 1024.
+    -> ((D, moved U, igt, U, D boundary, U boundary, D mask, U mask), ok [B], DoubleCut)"""
+    if not raw.is_cuda:
+        raise _lib.PznError("datapipe.cut_pairs_double runs on the GPU (puzzlenet_amd has no CPU fallback)")
+    B, M, _ = raw.shape
+    cap = M if cap is None else int(cap)
+    if cap > 32768:
+        raise _lib.PznUnsupported(f"cut_pairs_double: pieces of up to {cap} points (the FPS kernel holds <= 32768)")
+    n_rich = 3000 * n // 1024 if n_rich is None else int(n_rich)
+    pieces, counts, start, kind, planes, tabs, ok = ops.cut_compact_double(raw, normals1, zs1, normals2, zs2, u, n, n_rich, cap)
+    # (U holds >= n points, so D holds <= M - n; the fallback is a valid single cut; rows of samples without a valid cut are re-drawn)
+    def sample(part):                                                                            # dataset.py:1147-1163
+        idx = ops.farthest_point_sample(pieces[part], n, start[part], background=True, counts=counts[part], max_count=max(M - n, n))
+        return ops.index_points(pieces[part], idx)
+
+    primary, fallback = sample(slice(0, 2 * B)), sample(slice(2 * B, 4 * B))                     # [2B,n,3] each: U rows, D rows
+
+    def picks(both):                                                                             # dataset.py:1357-1367
+        cd_over_u, cd_over_d = ops.chamfer(both[B:], both[:B])
+        top = ops.topk_rows(torch.cat([cd_over_u, cd_over_d], 0).neg_(), k)                      # [2B,k]: U picks, D picks
+        return top, ops.index_points(both, top)
+
+    _, bnd = picks(primary)
+    cd1, cd2 = ops.chamfer(bnd[B:], bnd[:B])                                                     # :1253-1254
+    cd = cd1.mean(1) + cd2.mean(1)
+    rejected = double_cut_rejects(kind, cd)
+    both = torch.where(rejected.repeat(2).view(2 * B, 1, 1), fallback, primary)
+    top, fbnd = picks(both)
+    masks = ops.pick_mask(top, n)
+    g = se3.exp(twist.to(torch.float32))                                                         # transforms.py:176-186
+    U, D = both[:B], both[B:]
+    moved = se3.transform_points(g, U)
+    record = DoubleCut(kind, planes, tabs, rejected, cd, primary[:B], primary[B:], bnd[:B], bnd[B:])
+    return (D, moved, g, U, fbnd[B:], fbnd[:B], masks[B:], masks[:B]), ok & (counts[:B] >= n) & (counts[B:2 * B] >= n), record
+
+
 class PairBatch(list):
     """The 8-tuple of a training batch + `ready`: the event behind which its tensors exist (they were produced on the
     feeder's stream), + `ok` [B] (a valid cut was among the candidates)."""
@@ -332,6 +387,7 @@ class PairBatch(list):
     ok = None
     plane = None      # (normal [B,3], z [B]) float64: the plane each sample was cut with (cut="plane")
     cut = None        # (kind, rot [B,3], shift [B,3]) float64: the solid each sample was cut with (cut=a solid)
+    double = None     # DoubleCut: kind, planes, region tables, the acceptance test's outcome (split_twice=True)
 
 
 class PairFeeder:
@@ -341,12 +397,16 @@ class PairFeeder:
     k + 1 is cut and sampled while step k trains.  The host part of a batch is a handful of draws (K candidate planes, two
     uniform numbers for the FPS start points, a twist) from PRIVATE generators and one pinned, asynchronous upload: nothing
     in next_batch() waits for the device.  engine.TrainStep.step(next_batch=feeder.next_batch()) orders its streams behind
-    `ready` and keeps the tensors alive across the streams that read them."""
+    `ready` and keeps the tensors alive across the streams that read them.
+    split_twice=True (cut="plane" only): the reference's `train.py --random_slice`, i.e. CADDataset(split_twice=True) - the
+    double cuts of dataset.py:1203-1355 by cut_pairs_double, with n_rich = 3000 n / 1024; batch.double says what was cut."""
 
-    def __init__(self, raw, device, n=1024, k=128, mag=0.8, candidates=16, seed=0, cut="plane"):
+    def __init__(self, raw, device, n=1024, k=128, mag=0.8, candidates=16, seed=0, cut="plane", split_twice=False):
         if cut != "plane" and cut not in ops.SOLID_KINDS:
             raise _lib.PznError(f"PairFeeder: cut={cut!r} (one of 'plane', 'sphere', 'cylinder', 'cone')")
-        self.cut = cut
+        if split_twice and cut != "plane":
+            raise _lib.PznUnsupported(f"PairFeeder: split_twice=True cuts with planes (cut={cut!r})")
+        self.cut, self.split_twice = cut, bool(split_twice)
         raw = torch.as_tensor(raw, dtype=torch.float32)
         if raw.dim() != 3 or raw.shape[2] != 3:
             raise _lib.PznError("PairFeeder: raw clouds as [B, M, 3]")
@@ -361,6 +421,8 @@ class PairFeeder:
         B = self.raw.shape[0]
         # one pinned staging block per batch in flight (two: the upload of batch k + 1 may still be queued when k + 2 is drawn)
         self._width = self.K * 3 + self.K + 2 + 6 if cut == "plane" else self.K * 6 + 2 + 6
+        if self.split_twice:      # K + 7 planes, 7 uniforms, the twist
+            self._width = (self.K + ops.DOUBLE_CUT_TRIES) * 4 + ops.DOUBLE_CUT_UNIFORMS + 6
         self._stage = [torch.empty((B, self._width), dtype=torch.float64, pin_memory=True) for _ in range(3)]
         self._turn = 0
         self._busy = [None] * 3
@@ -368,6 +430,8 @@ class PairFeeder:
     def next_batch(self):
         if self.cut != "plane":
             return self._next_batch_solid()
+        if self.split_twice:
+            return self._next_batch_double()
         B, K, n = self.raw.shape[0], self.K, self.n
         st = self._stage[self._turn]
         if self._busy[self._turn] is not None:
@@ -415,6 +479,37 @@ class PairFeeder:
         self._turn = (self._turn + 1) % 3
         out = PairBatch(tensors)
         out.ready, out.ok, out.cut = ready, ok, (self.cut, chosen[:, :3], chosen[:, 3:])
+        return out
+
+    def _next_batch_double(self):
+        """next_batch() for split_twice=True: the same protocol, the draws of double_cut_rule in place of the K planes."""
+        B, K, n, T, Q = self.raw.shape[0], self.K, self.n, ops.DOUBLE_CUT_TRIES, ops.DOUBLE_CUT_UNIFORMS
+        st = self._stage[self._turn]
+        if self._busy[self._turn] is not None:
+            self._busy[self._turn].synchronize()          # (three batches back: long done)
+        h = st.numpy()
+        c = np.cumsum([0, 3 * K, K, 3 * T, T, Q, 6])
+        h[:, c[0]:c[1]] = self.rng.rand(B, 3 * K)                               # plane 1: normals, dataset.py:767
+        h[:, c[1]:c[2]] = self.rng.rand(B, K) / 3                               # plane 1: offsets, :769
+        h[:, c[2]:c[3]] = self.rng.rand(B, 3 * T)                               # plane 2: the draw of :1226 / :1296 and its six re-draws
+        h[:, c[3]:c[4]] = self.rng.rand(B, T) / 3
+        h[:, c[4]:c[5]] = self.rng.rand(B, Q)                                   # u_seed, u_se, u_choice, u_sU, u_sD, u_sFU, u_sFD
+        x = torch.randn(B, 6, generator=self.gen, dtype=torch.float64)          # transforms.py:163-168
+        h[:, c[5]:] = (x / x.norm(p=2, dim=1, keepdim=True) * self.mag).numpy()
+        with torch.cuda.stream(self.stream):
+            d = st.to(self.device, non_blocking=True)
+            up_ev = torch.cuda.Event()
+            up_ev.record(self.stream)
+            self._busy[self._turn] = up_ev
+            tensors, ok, record = cut_pairs_double(self.raw, d[:, c[0]:c[1]].reshape(B, K, 3), d[:, c[1]:c[2]],
+                                                   d[:, c[2]:c[3]].reshape(B, T, 3), d[:, c[3]:c[4]], d[:, c[4]:c[5]], d[:, c[5]:],
+                                                   n=n, k=self.k)
+            ready = torch.cuda.Event()
+            ready.record(self.stream)
+        self._turn = (self._turn + 1) % 3
+        out = PairBatch(tensors)
+        out.ready, out.ok, out.double = ready, ok, record
+        out.plane = (record.planes[:, 0, :3], record.planes[:, 0, 3])
         return out
 
     def close(self):
@@ -488,6 +583,112 @@ def building_pairs(fpcs, rpcs, twist, k=128):
     if not (fpcs.is_cuda and rpcs.is_cuda):
         raise _lib.PznError("datapipe.building_pairs runs on the GPU (puzzlenet_amd has no CPU fallback)")
     return pairs_from_pieces(rpcs.to(torch.float32).contiguous(), fpcs.to(torch.float32).contiguous(), twist, k)
+
+
+# The double cut as the FEEDER samples it (PairFeeder(split_twice=True)): the same decision tree from draws made up front.
+SINGLE, HALF_VS_REST, HALF_VS_OTHER, HALVES = range(4)       # `kind` codes (ops.DOUBLE_CUT_KINDS names them as the plan does)
+CD_ACCEPT = 0.015                                            # dataset.py:1255, :1322
+
+
+def double_cut_rejects(kind, cd):
+    """Step 8 of double_cut_rule (numpy arrays or tensors): the pair is replaced by its fallback."""
+    return (kind == HALF_VS_OTHER) & (cd > CD_ACCEPT)
+
+
+def _side64(pts, plane):
+    """side(p, plane) = (p . normal + z >= 0) as plane_cut_mask and the kernels evaluate it: float64, every operation
+    individually rounded, ((x n0 + y n1) + z n2) + offset.  pts [M,3] float32, plane [4] float64 -> bool [M]"""
+    p = np.asarray(pts, dtype=np.float32).astype(np.float64)
+    plane = np.asarray(plane, dtype=np.float64)
+    return ((p[:, 0] * plane[0] + p[:, 1] * plane[1]) + p[:, 2] * plane[2]) + plane[3] >= 0
+
+
+def region_rows(raw, code, tab):
+    """Rows of the piece tab = (first region table, second): the points whose cell `code` is in the first, then the others whose
+    cell is in the second, each in the cloud's order (_segments + _compact_segments without the padding).  numpy."""
+    in0 = ((int(tab[0]) >> code) & 1) == 1
+    in1 = (((int(tab[1]) >> code) & 1) == 1) & ~in0
+    return np.concatenate([raw[in0], raw[in1]], axis=0)
+
+
+def double_cut_rule(raw, planes1, planes2, u, n=1024, n_rich=3000, cap=None):
+    """The sampling rule of PairFeeder(split_twice=True) for ONE sample, in numpy on the host, float64: the statement that
+    pzn_cut_compact_double_f32 (steps 1-7) and cut_pairs_double (step 8) implement and the tests hold them to.  It reproduces
+    the DISTRIBUTION of CADDataset.__getitem__ with split_twice=True (dataset.py:1203-1355) from draws made up front; it does not
+    replay the reference's generator order (plan_double_cut_like_reference does).
+      raw      [M,3] float32
+      planes1  [K,4] float64: K candidates (normal = rand(3), z = rand() / 3) for plane 1, as the plane feeder draws them
+      planes2  [7,4] float64: the first draw of plane 2 and the six re-draws of `while time <= 5` (:1227, :1300)
+      u        [7] uniforms: u_seed, u_se, u_choice, u_sU, u_sD, u_sFU, u_sFD
+      n        points per piece, where the reference hard-wires 1024
+      n_rich   points a piece must hold to be cut again: the reference's 3000 (:1214-1217).  The reference only exists at
+               n = 1024; the feeder scales the threshold with n and passes 3000 n // 1024
+      cap      rows a piece may hold (None: M)
+    The rule:
+      1. a = |up|, b = M - a by plane-1 candidate 0.
+      2. seed = min(2, floor(3 u_seed)); seed 1 with a < n_rich becomes 2; THEN seed 2 with b < n_rich becomes 1 (:1214-1217).
+      3. seed 0: SINGLE.
+      4. inner = up (seed 1) or down (seed 2), the other piece holds c points; the first of the 7 plane-2 candidates that leaves
+         >= n points on both sides within inner gives uppc (side 1) / downpc (side 0); none: SINGLE.
+      5. se = min(2, floor(3 u_se)), choice = min(1, floor(2 u_choice)):
+         se 0 or c < n: HALF_VS_REST, U = the chosen half, D = the other half's rows, then the other piece's (np.vstack, :1239);
+         se 1: HALF_VS_OTHER, U = the chosen half, D = the other piece; fallback pair = (up, down) of plane-1 candidate 0 (valid:
+               inner holds >= 2 n points and c >= n);
+         se 2: HALVES, U = uppc, D = downpc (the `re_now` branch only makes draws whose results it overwrites, :1283-1285).
+      6. SINGLE: U = up, D = down of the first plane-1 candidate, counted from 0, with >= n points on both sides (`self.slice`
+         starting from the split already made); none: the most balanced one, the first among equals, ok = False.
+      7. start = clamp(floor(u count), 0, count - 1) with u_sU, u_sD for U, D and u_sFU, u_sFD for the fallback pieces.
+      8. (on the sampled pieces, so not here: double_cut_rejects) HALF_VS_OTHER only: cd = mean(cd1) + mean(cd2) of the chamfer
+         distances between the two 128-point boundaries of get_boundary(D, U); cd > 0.015: the fallback pair, sampled from its
+         own start indices, replaces the pair (:1253-1256, :1320-1323).
+    -> dict(kind, planes [2,4] (plane 2 zero for SINGLE), u_tab [2], d_tab [2], pieces: [U, D, fallback U, fallback D] row
+       arrays (None where there is no fallback), counts [4] (-1 there), start [4], ok)"""
+    raw = np.asarray(raw, dtype=np.float32)
+    planes1, planes2, u = (np.asarray(t, dtype=np.float64) for t in (planes1, planes2, u))
+    M, K = raw.shape[0], planes1.shape[0]
+    cap = M if cap is None else int(cap)
+    s1 = _side64(raw, planes1[0])
+    a = int(s1.sum())
+    b = M - a
+    seed = min(2, int(np.floor(3 * u[0])))
+    if seed == 1 and a < n_rich:
+        seed = 2
+    if seed == 2 and b < n_rich:
+        seed = 1
+    kind, p1, p2 = SINGLE, planes1[0], np.zeros(4)
+    u_tab, d_tab = (UP, 0), (DOWN, 0)
+    if seed != 0:
+        inner = s1 if seed == 1 else ~s1
+        c = M - int(inner.sum())
+        for t in range(planes2.shape[0]):
+            s2 = _side64(raw, planes2[t])
+            if int((inner & s2).sum()) >= n and int((inner & ~s2).sum()) >= n:
+                A, Bt, other = (UP_UPPC, UP_DOWNPC, DOWN) if seed == 1 else (DOWN_UPPC, DOWN_DOWNPC, UP)
+                se, choice = min(2, int(np.floor(3 * u[1]))), min(1, int(np.floor(2 * u[2])))
+                first, second = (A, Bt) if choice == 0 else (Bt, A)
+                if se == 0 or c < n:
+                    kind, u_tab, d_tab = HALF_VS_REST, (first, 0), (second, other)
+                elif se == 1:
+                    kind, u_tab, d_tab = HALF_VS_OTHER, (first, 0), (other, 0)
+                else:
+                    kind, u_tab, d_tab = HALVES, (A, 0), (Bt, 0)
+                p2 = planes2[t]
+                break
+    ok = True
+    if kind == SINGLE:
+        ups = [a] + [int(_side64(raw, planes1[k]).sum()) for k in range(1, K)]
+        valid = [k for k in range(K) if ups[k] >= n and M - ups[k] >= n]
+        ok = bool(valid)
+        pick = valid[0] if valid else int(np.argmax([min(x, M - x) for x in ups]))      # (argmax: the first among equals)
+        p1 = planes1[pick]
+    code = 2 * _side64(raw, p1).astype(np.int64) + _side64(raw, p2).astype(np.int64)
+    tabs = [u_tab, d_tab] + ([(UP, 0), (DOWN, 0)] if kind == HALF_VS_OTHER else [])
+    pieces = [region_rows(raw, code, t) for t in tabs] + [None] * (4 - len(tabs))
+    counts = np.array([-1 if r is None else len(r) for r in pieces], dtype=np.int64)
+    start = np.array([0 if cnt < 0 else max(0, min(cnt - 1, int(np.floor(u[3 + i] * cnt)))) for i, cnt in enumerate(counts)],
+                     dtype=np.int64)
+    return dict(kind=kind, planes=np.stack([p1, p2]), u_tab=np.array(u_tab, np.int64), d_tab=np.array(d_tab, np.int64),
+                pieces=pieces, counts=counts, start=start, ok=bool(ok and counts.max() <= cap))
 
 
 def _plane_draw():

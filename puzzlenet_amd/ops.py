@@ -456,6 +456,42 @@ def cut_compact_solid(raw, kind, params, u, n_min, cap):
     return pieces, counts, start, chosen, chosen_k, ok.to(torch.bool)
 
 
+DOUBLE_CUT_KINDS = ("single", "half_vs_rest", "half_vs_other", "halves")      # the `kind` codes of pzn_cut_compact_double_f32
+DOUBLE_CUT_TRIES = 7      # plane-2 candidates per sample: the first draw + the re-draws of `while time <= 5` (dataset.py:1227)
+DOUBLE_CUT_UNIFORMS = 7   # u_seed, u_se, u_choice, u_sU, u_sD, u_sFU, u_sFD
+
+
+def cut_compact_double(raw, normals1, zs1, normals2, zs2, u, n_min, n_rich, cap):
+    """dataset.py:1203-1355 (split_twice=True) up to the sampling for a batch in one launch (pzn_cut_compact_double_f32; the
+    rule: datapipe.double_cut_rule): raw [B,M,3] f32; K candidates for plane 1 (normals1 [B,K,3], zs1 [B,K]), 7 for plane 2
+    (normals2 [B,7,3], zs2 [B,7]), uniforms u [B,7], all float64
+    -> (pieces [4B,cap,3]: U, D, fallback U, fallback D; counts [4B] int64, -1 where there is no fallback; start [4B] int64;
+        kind [B] int32; planes [B,2,4] float64; tabs [B,4] int32; ok [B] bool)"""
+    raw = _f32(raw, "raw")
+    normals1, zs1, normals2, zs2, u = (_req(t, torch.float64, n_) for t, n_ in (
+        (normals1, "normals1"), (zs1, "zs1"), (normals2, "normals2"), (zs2, "zs2"), (u, "u")))
+    B, M, _ = raw.shape
+    if normals1.dim() != 3 or normals1.shape[0] != B or normals1.shape[2] != 3 or tuple(zs1.shape) != (B, normals1.shape[1]):
+        raise _lib.PznError("cut_compact_double: normals1 as [B, K, 3] and zs1 as [B, K]")
+    if tuple(normals2.shape) != (B, DOUBLE_CUT_TRIES, 3) or tuple(zs2.shape) != (B, DOUBLE_CUT_TRIES) \
+            or tuple(u.shape) != (B, DOUBLE_CUT_UNIFORMS):
+        raise _lib.PznError(f"cut_compact_double: normals2 as [B, {DOUBLE_CUT_TRIES}, 3], zs2 as [B, {DOUBLE_CUT_TRIES}] and "
+                            f"u as [B, {DOUBLE_CUT_UNIFORMS}]")
+    K = normals1.shape[1]
+    dev = raw.device
+    pieces = torch.empty((4 * B, int(cap), 3), dtype=torch.float32, device=dev)
+    counts = torch.empty((4 * B,), dtype=torch.int64, device=dev)
+    start = torch.empty((4 * B,), dtype=torch.int64, device=dev)
+    kind = torch.empty((B,), dtype=torch.int32, device=dev)
+    planes = torch.empty((B, 2, 4), dtype=torch.float64, device=dev)
+    tabs = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    ok = torch.empty((B,), dtype=torch.uint8, device=dev)
+    with _on(dev):
+        _call("pzn_cut_compact_double_f32", _p(raw), _p(normals1), _p(zs1), _p(normals2), _p(zs2), _p(u), B, M, K, int(n_min),
+              int(n_rich), int(cap), _p(pieces), _p(counts), _p(start), _p(kind), _p(planes), _p(tabs), _p(ok), _stream())
+    return pieces, counts, start, kind, planes, tabs, ok.to(torch.bool)
+
+
 def pick_mask(idx, N):
     """0/1 float masks [R,N] with ones at idx [R,k] (dataset.py:1363-1366), one launch."""
     idx = _i64(idx, "idx")

@@ -2,17 +2,20 @@
 to N, labelled and moved — next to the training step's consumption rate, and to the reference-style numpy FPS of ONE
 piece on one host core (the dominant cost of the reference's per-sample CPU pipeline).
 
-    python tools/bench_datapipe.py [--cut {plane,sphere,cylinder,cone}] [--reps 30]
+    python tools/bench_datapipe.py [--cut {plane,sphere,cylinder,cone}] [--random_slice] [--reps 30]
 
 Then the loader's batch as PairFeeder builds it, B = 64, M = 10000, N = 2048, 16 candidates: datapipe.cut_pairs (plane) and, with
 --cut a solid, datapipe.cut_pairs_solid of that kind next to the tensor form datapipe.make_pairs_solid on the same clouds with the
-one candidate the kernel took - one process, the forms alternating inside every repetition, a device synchronise around each."""
+one candidate the kernel took - one process, the forms alternating inside every repetition, a device synchronise around each.
+--random_slice: datapipe.cut_pairs_double (the double cuts, PairFeeder(split_twice=True)) beside the plane batch on the same clouds,
+and its cut launch and its two sampling launches beside the plane batch's, each alone between two device events."""
 import argparse, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from puzzlenet_amd import datapipe
 ap = argparse.ArgumentParser()
 ap.add_argument("--cut", choices=["plane", "sphere", "cylinder", "cone"], default="plane")
+ap.add_argument("--random_slice", action="store_true")
 ap.add_argument("--reps", type=int, default=30)
 a = ap.parse_args()
 dev = torch.device('cuda:0')
@@ -58,6 +61,26 @@ if a.cut != "plane":
     rot, shift, s0 = chosen[:, :3].contiguous(), chosen[:, 3:].contiguous(), torch.zeros(B, dtype=torch.int64, device=dev)
     forms[a.cut + ": cut_pairs_solid"] = lambda: datapipe.cut_pairs_solid(raw, a.cut, params, u, tw, n=N)[1]
     forms[a.cut + ": make_pairs_solid (tensor form, one candidate)"] = lambda: datapipe.make_pairs_solid(raw, a.cut, rot, shift, s0, s0, tw, n=N)[1]
+launches = {}
+if a.random_slice:
+    from puzzlenet_amd import ops
+    T, Q = ops.DOUBLE_CUT_TRIES, ops.DOUBLE_CUT_UNIFORMS
+    normals2, zs2 = torch.from_numpy(rng.rand(B, T, 3)).to(dev), torch.from_numpy(rng.rand(B, T) / 3 - 0.4).to(dev)
+    u7 = torch.from_numpy(rng.rand(B, Q)).to(dev)
+    _, ok, rec = datapipe.cut_pairs_double(raw, normals, zs, normals2, zs2, u7, tw, n=N)
+    print('double cut: valid %d/%d, kinds (single, half vs rest, half vs other, halves) %s, replaced by the fallback %d' % (
+        int(ok.sum()), B, torch.bincount(rec.kind.long(), minlength=4).tolist(), int(rec.rejected.sum())), flush=True)
+    forms["plane: cut_pairs_double"] = lambda: datapipe.cut_pairs_double(raw, normals, zs, normals2, zs2, u7, tw, n=N)[1]
+    # the launches the double cut adds or changes, each alone between two events
+    n_rich, mc = 3000 * N // 1024, max(M - N, N)
+    p2, c2, s2, _, _ = ops.cut_compact(raw, normals, zs, u, N, M)
+    p4, c4, s4 = ops.cut_compact_double(raw, normals, zs, normals2, zs2, u7, N, n_rich, M)[:3]
+    launches["cut_compact (plane)"] = lambda: ops.cut_compact(raw, normals, zs, u, N, M)
+    launches["cut_compact_double"] = lambda: ops.cut_compact_double(raw, normals, zs, normals2, zs2, u7, N, n_rich, M)
+    launches["FPS of the plane pair"] = lambda: ops.farthest_point_sample(p2, N, s2, background=True, counts=c2, max_count=mc)
+    launches["FPS of the primary pair"] = lambda: ops.farthest_point_sample(p4[:2 * B], N, s4[:2 * B], background=True, counts=c4[:2 * B], max_count=mc)
+    launches["FPS of the fallback pair (%d of %d samples)" % (int((c4[2 * B:3 * B] >= 0).sum()), B)] = \
+        lambda: ops.farthest_point_sample(p4[2 * B:], N, s4[2 * B:], background=True, counts=c4[2 * B:], max_count=mc)
 times = {name: [] for name in forms}
 for rep in range(a.reps + 3):
     for name, fn in forms.items():
@@ -69,3 +92,15 @@ for rep in range(a.reps + 3):
 for name, t in times.items():
     t = np.sort(np.array(t)) * 1e3
     print('B=%d M=%d -> N=%d  %-55s %.2f ms per batch (median of %d; min %.2f, max %.2f)' % (B, M, N, name, np.median(t), len(t), t[0], t[-1]), flush=True)
+ltimes = {name: [] for name in launches}
+for rep in range(a.reps + 3):
+    for name, fn in launches.items():
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(); e0.record()
+        fn()
+        e1.record(); e1.synchronize()
+        if rep >= 3:
+            ltimes[name].append(e0.elapsed_time(e1))
+for name, t in ltimes.items():
+    t = np.sort(np.array(t)) * 1e3
+    print('B=%d M=%d -> N=%d  launch: %-47s %.0f us between events (median of %d; min %.0f, max %.0f)' % (B, M, N, name, np.median(t), len(t), t[0], t[-1]), flush=True)

@@ -3,10 +3,13 @@ labels, random motion on a background stream: the reference's loader processes, 
 :98-105) -> engine.TrainStep, a fresh batch every step, nothing synchronises.
 
     python tools/train_from_raw.py [--batch 64] [--points 2048] [--raw 10000] [--steps 20] [--cut {plane,sphere,cylinder,cone}]
+                                     [--random_slice]
 
 --cut sphere | cylinder | cone: the reference's mesh cuts (dataset.py:715-759; "bed_sphere" is its documented training
 command) in place of the plane.  The cone (apex and base one unit from the origin) holds every point within 0.447 of the
 origin, so for it the shells are twice as large.
+--random_slice: the reference's flag of the same name (CADDataset(split_twice=True), dataset.py:1203-1355): the double cuts, with
+the plane only.
 """
 import argparse, os, sys, time
 import numpy as np, torch
@@ -20,6 +23,7 @@ ap.add_argument("--points", type=int, default=2048)
 ap.add_argument("--raw", type=int, default=10000)
 ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--cut", choices=["plane", "sphere", "cylinder", "cone"], default="plane")
+ap.add_argument("--random_slice", action="store_true")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 B, N, M = a.batch, a.points, a.raw
@@ -32,16 +36,17 @@ if a.cut == "cone":
 cfg = Cfg(); cfg.num_points = N
 torch.manual_seed(0)
 model = model5_b.TouchedRegraster(cfg).to(dev)
-feeder = datapipe.PairFeeder(raw, dev, n=N, seed=0, cut=a.cut)
+feeder = datapipe.PairFeeder(raw, dev, n=N, seed=0, cut=a.cut, split_twice=a.random_slice)
 runner = engine.TrainStep(model, feeder.next_batch(), cfg.lr, world=1)
 nxt = feeder.next_batch()
-losses, mem, oks = [], [], [nxt.ok]
+losses, mem, oks, doubles = [], [], [nxt.ok], [nxt.double]
 for it in range(a.steps + 3):
     if it == 3:
         torch.cuda.synchronize(); t0 = time.perf_counter()
     losses.append(runner.step(next_batch=nxt))
     nxt = feeder.next_batch()
     oks.append(nxt.ok)
+    doubles.append(nxt.double)
     if it % 50 == 0:
         mem.append(torch.cuda.memory_allocated() >> 20)      # (no synchronisation: the allocator's own count)
 torch.cuda.synchronize()
@@ -50,5 +55,9 @@ print("loss first / last: %.4f / %.4f" % (float(losses[0]), float(losses[-1])))
 ls = torch.stack([l.detach().float().reshape(()) for l in losses])
 print("every loss finite:", bool(torch.isfinite(ls).all()), " MiB allocated every 50 steps:", mem)
 print("cut %s: every batch cut validly:" % a.cut, all(bool(o.all()) for o in oks))
+if a.random_slice:
+    kinds = torch.bincount(torch.cat([d.kind for d in doubles]).long(), minlength=4).tolist()
+    print("double cuts: single / half vs rest / half vs other / halves:", kinds, " pairs replaced by their fallback:",
+          int(torch.cat([d.rejected for d in doubles]).sum()))
 print("%.2f ms per step of %d fresh pairs from %d-point raw clouds = %.0f pairs/s" % (1e3 * dt / a.steps, B, M, B * a.steps / dt))
 runner.close(); feeder.close()
