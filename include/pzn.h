@@ -552,6 +552,18 @@ int pzn_point_mlp3_bwd_f32(const float* dy, const float* x, const float* h1, con
                            int rows_per_cloud, const float* W1, int ldw1, int b1_per_cloud, const float* W2,
                            const float* W3, int C2, int C3, float* dx, float* dW1, float* db1, float* dW2,
                            float* db2, float* dW3, float* db3, int accumulate, void* workspace, pzn_stream_t stream);
+/* The fixed-side boundary head of an all-pairs table (assembly.py), forward only, one launch (csrc/pointmlp.hip):
+ *   y[i, j, p, :] = (relu(relu(x[i, p, :] W1^T + c[j, :]) W2^T + b2)) W3^T + b3     for i < Kf, j < Km, p < N,
+ * x[Kf, N, 64] the local features of the fixed-role pieces, c[Km, 64] the first-layer bias of every moved piece (the
+ * folded global half g_j W1[:, :64]^T + b1), W1[64, ldw1] the LOCAL half of the first layer (a column slice, ldw1 >= 64).
+ * The first-layer product is computed once per 32-row tile and reused for every j; no hidden activation is written, no
+ * workspace, no atomics (the same bits on every run).  The bias is added behind the products, so the result equals
+ * pzn_point_mlp3_fwd_f32 on the materialised pair batch to rounding, not bitwise.  N % 32 == 0 and (C2, C3) = (32, 2)
+ * (pzn_pair_head_supported); PZN_EUNSUPPORTED otherwise, before anything is launched.  16-byte aligned x, c, b2, y. */
+int pzn_pair_head_supported(int N, int C2, int C3);
+int pzn_pair_head_fwd_f32(const float* x, int Kf, int N, const float* c, int Km, const float* W1, int ldw1,
+                          const float* W2, const float* b2, const float* W3, const float* b3, int C2, int C3,
+                          float* y, pzn_stream_t stream);
 
 /* The encoder's out projection and the max over the points in ONE launch (model5_b.py:466-475):
  *   out[b,l,:] = cat(x[0] .. x[nslice-1])[b,l,:] W^T + bias   (W[Nout, nslice*E]; the concatenation is never built),

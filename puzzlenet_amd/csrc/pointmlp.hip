@@ -232,6 +232,87 @@ __global__ __launch_bounds__(PM_FWD_WAVES * 64) void point_mlp3_fwd_kernel(PmFwd
 }
 
 // ================================================================================================================
+// pair head, forward only (assembly.py: every fixed piece against every moved piece).  de_fpcb[i, j] =
+// MLPFpcb(cat([g_j, local_i])): the first-layer product on local_i does not depend on j, only the bias c_j = g_j
+// W1[:, :64]^T + b1 does.  A wavefront's work item is one 32-row tile of one fixed piece and a chunk [j0, j1) of moved
+// pieces: the tile is read once, A = W1_loc x computed once and kept in registers (zero-seeded: the bias is added behind
+// the products), and for every j the rest of the chain runs on relu(A + c_j) and only the 32 x 2 logits are written.
+// Nothing is kept for a backward pass; every output element has one owner and one summation order.
+struct PmPairArgs {
+  const float* x;          // [Kf, N, 64]
+  const float* c;          // [Km, 64]
+  const float* w1;         // [64, ldw1]: the local half of the first layer
+  const float *w2, *b2;    // [32, 64], [32]
+  const float *w3, *b3;    // [2, 32], [2]
+  float* y;                // [Kf, Km, N, 2]
+  int ldw1, Km, N, tiles_per_piece, ntiles, chunk, nchunks, nitems;
+};
+
+// x = relu(a + bias[feature]) (the feature is the row of a transposed tile)
+__device__ __forceinline__ void pm_bias_relu(floatx16 (&x)[2], const floatx16 (&a)[2], const float* __restrict__ bias, int h) {
+#pragma unroll
+  for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const pm_f4 v = *reinterpret_cast<const pm_f4*>(bias + 32 * rt + 8 * g + 4 * h);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) x[rt][4 * g + e] = fmaxf(a[rt][4 * g + e] + v[e], 0.f);
+    }
+}
+
+__global__ __launch_bounds__(PM_FWD_WAVES * 64) void pair_head_fwd_kernel(PmPairArgs a) {
+  constexpr int C2 = 32;
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  unsigned char* img1 = lds;
+  unsigned char* img2 = img1 + 4 * 3 * 2 * 1024;
+  unsigned char* img3 = img2 + 4 * 3 * 1024;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), h = lane >> 5;
+  float* stg = reinterpret_cast<float*>(img3 + 2 * 3 * 1024 + wave * PM_STG);
+  const int stride = gridDim.x * PM_FWD_WAVES;
+  int item = blockIdx.x * PM_FWD_WAVES + wave;      // item = tile * nchunks + chunk: neighbours share the tile's rows
+  pm_f4 pre[8];
+  pm_rows_load<64>(a.x + (long)min(item / a.nchunks, a.ntiles - 1) * 32 * PM_C, pre, lane);
+  pm_build_image<2, 4, false>(img1, a.w1, a.ldw1, PM_C, PM_C, tid, PM_FWD_WAVES * 64);
+  pm_build_image<1, 4, false>(img2, a.w2, PM_C, C2, PM_C, tid, PM_FWD_WAVES * 64);
+  pm_build_image<1, 2, false>(img3, a.w3, C2, 2, C2, tid, PM_FWD_WAVES * 64);
+  floatx16 B2[1];
+  pm_bias<1>(B2, a.b2, C2, h);
+  const float b30 = a.b3[0], b31 = a.b3[1];
+  __syncthreads();
+  while (item < a.nitems) {
+    const int tile = item / a.nchunks, ch = item - tile * a.nchunks;
+    const int piece = tile / a.tiles_per_piece, prow = (tile - piece * a.tiles_per_piece) * 32;
+    const int j0 = ch * a.chunk, j1 = min(a.Km, j0 + a.chunk);
+    floatx16 X[2];
+    pm_rows_to_stage<64>(stg, pre, lane);
+    pzn::wave_lds_sync();
+    pm_get<2>(stg, X, lane);
+    pzn::wave_lds_sync();
+    const int next = item + stride;
+    pm_rows_load<64>(a.x + (long)min(next / a.nchunks, a.ntiles - 1) * 32 * PM_C, pre, lane);   // (the last tile again past the end)
+    floatx16 A[2];
+    ZERO16(A[0]);
+    ZERO16(A[1]);
+    pm_layer<2, 4>(A, X, img1, lane);
+    float* yrow = a.y + (((long)piece * a.Km + j0) * a.N + prow + lane) * 2;
+    for (int j = j0; j < j1; ++j, yrow += (long)a.N * 2) {
+      floatx16 H1[2];
+      pm_bias_relu(H1, A, a.c + (long)j * PM_C, h);
+      floatx16 H2[1];
+      H2[0] = B2[0];
+      pm_layer<1, 4>(H2, H1, img2, lane);
+      pm_relu<1>(H2);
+      floatx16 Y[1];
+      ZERO16(Y[0]);
+      Y[0][0] = b30, Y[0][1] = b31;      // features 0, 1 are registers 0, 1 of the lanes with h = 0
+      pm_layer<1, 2>(Y, H2, img3, lane);
+      if (h == 0) *reinterpret_cast<float2*>(yrow) = make_float2(Y[0][0], Y[0][1]);
+    }
+    item = next;
+  }
+}
+
+// ================================================================================================================
 // backward
 // Row-major staging tiles WITHOUT padding, filled by LDS-DMA (no register staging, the load of the next operand flies
 // while the current one is multiplied): a tile is 32 rows of F floats, the 16-byte chunk c of row p at chunk position
@@ -669,6 +750,37 @@ PZN_EXPORT int pzn_point_mlp3_fwd_f32(const float* x, long long M, int rows_per_
     if (pm_set_lds(point_mlp3_fwd_kernel<32, 2>, lds) != PZN_OK) return PZN_ELAUNCH;
     PZN_LAUNCH((point_mlp3_fwd_kernel<32, 2>), grid, block, lds, st, a);
   }
+  PZN_RETURN_LAUNCH_STATUS();
+}
+
+// 1 when the pair head takes pieces of N points behind a 64 -> 64 -> C2 -> C3 chain: the MLPFpcb chain on whole tiles
+PZN_EXPORT int pzn_pair_head_supported(int N, int C2, int C3) {
+  return pm_enabled() && N > 0 && N % 32 == 0 && C2 == 32 && C3 == 2;
+}
+
+// y[i, j, p, :] = (relu(relu(x[i, p] W1^T + c[j]) W2^T + b2)) W3^T + b3 for every fixed piece i < Kf and moved piece j < Km;
+// forward only, one launch, no workspace.  W1[64, ldw1] is the local half of the first layer (a column slice, ldw1 >= 64),
+// c[j] the folded global half (g_j W1[:, :64]^T + b1).
+PZN_EXPORT int pzn_pair_head_fwd_f32(const float* x, int Kf, int N, const float* c, int Km, const float* W1, int ldw1,
+                                     const float* W2, const float* b2, const float* W3, const float* b3, int C2, int C3,
+                                     float* y, pzn_stream_t stream) {
+  PZN_CHECK_ARG(x && c && W1 && W2 && b2 && W3 && b3 && y && Kf > 0 && Km > 0 && N > 0 && ldw1 >= 64);
+  if (!pzn_pair_head_supported(N, C2, C3)) return PZN_EUNSUPPORTED;
+  const long long ntiles = (long long)Kf * (N / 32);
+  // moved pieces per work item: as long as the tiles alone do not give every SIMD two wavefronts, split the j range
+  constexpr int SLOTS = 256 * PM_FWD_WAVES;
+  int nchunks = ntiles >= SLOTS ? 1 : (int)((SLOTS + ntiles - 1) / ntiles);
+  if (nchunks > Km) nchunks = Km;
+  const int chunk = (Km + nchunks - 1) / nchunks;
+  nchunks = (Km + chunk - 1) / chunk;
+  if (ntiles * nchunks > 0x3fffffffLL) return PZN_EUNSUPPORTED;      // (the walk adds one grid stride to an item index)
+  PZN_CHECK_ARG(pm_aligned16(x) && pm_aligned16(c) && pm_aligned16(b2) && pm_aligned16(y));
+  PmPairArgs a{x, c, W1, W2, b2, W3, b3, y, ldw1, Km, N, N / 32, (int)ntiles, chunk, nchunks, (int)(ntiles * nchunks)};
+  const int nwg = (a.nitems + PM_FWD_WAVES - 1) / PM_FWD_WAVES;
+  const dim3 grid(nwg < 256 ? nwg : 256), block(PM_FWD_WAVES * 64);
+  constexpr int lds = pm_fwd_lds<32, 2>();
+  if (pm_set_lds(pair_head_fwd_kernel, lds) != PZN_OK) return PZN_ELAUNCH;
+  PZN_LAUNCH(pair_head_fwd_kernel, grid, block, lds, pzn_hip_stream(stream), a);
   PZN_RETURN_LAUNCH_STATUS();
 }
 

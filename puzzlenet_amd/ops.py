@@ -1053,6 +1053,41 @@ def point_mlp3(x, w1, b1, w2, b2, w3, b3, g=None):
     return _PointMlp3.apply(x, g, w1, b1, w2, b2, w3, b3)
 
 
+def pair_head_supported(N, C2, C3):
+    return bool(_lib.load().pzn_pair_head_supported(int(N), int(C2), int(C3)))
+
+
+def pair_head(x, g, w1, b1, w2, b2, w3, b3):
+    """MLPFpcb over every (fixed, moved) pair without the pair batch (csrc/pointmlp.hip, pair_head_fwd_kernel):
+    y[i, j] = the 128 -> 64 -> 32 -> 2 chain on cat([g[j].repeat(N, 1), x[i]], -1).  x[Kf,N,64] local features of the
+    fixed-role pieces, g[Km,64] (or [Km,1,64]) the moved pieces' global vectors, w1[64,128] -> [Kf,Km,N,2].  The global
+    half of the first layer becomes the per-moved-piece bias c = g W1[:, :64]^T + b1 (as _PointMlp3.forward forms it), then
+    one launch.  Forward only: no autograd, nothing saved."""
+    x = _f32(x.detach(), "x")
+    g = _f32(g.detach(), "g")
+    w1, b1, w2, b2, w3, b3 = (_f32(t.detach(), n) for t, n in ((w1, "w1"), (b1, "b1"), (w2, "w2"), (b2, "b2"), (w3, "w3"), (b3, "b3")))
+    if x.dim() != 3 or x.shape[2] != 64:
+        raise _lib.PznError(f"pair_head expects x[Kf,N,64]; got {tuple(x.shape)}")
+    Kf, N, C = x.shape
+    g2 = g.reshape(-1, g.shape[-1])
+    Km, Cg = g2.shape
+    C2, C3 = w2.shape[0], w3.shape[0]
+    if w1.shape != (64, Cg + C) or w2.shape[1] != 64 or w3.shape[1] != C2:
+        raise _lib.PznError(f"pair_head: w1{tuple(w1.shape)}, w2{tuple(w2.shape)}, w3{tuple(w3.shape)} vs {Cg} + {C} input columns")
+    if not pair_head_supported(N, C2, C3):
+        raise _lib.PznUnsupported(f"pair_head: N = {N} (a multiple of 32) and a 64 -> {C2} -> {C3} tail (32 -> 2) are not "
+                                  "a shape the kernel takes")
+    dev = x.device
+    c = torch.empty((Km, 64), dtype=torch.float32, device=dev)
+    y = torch.empty((Kf, Km, N, C3), dtype=torch.float32, device=dev)
+    with _on(dev):
+        st = _stream()
+        _call("pzn_linear_slice_fwd_f32", _p(g2), _p(w1), Cg + C, _p(b1), Km, Cg, 64, 0, _p(c), st, flops=2 * Km * Cg * 64)
+        _call("pzn_pair_head_fwd_f32", _p(x), Kf, N, _p(c), Km, _p(w1) + 4 * Cg, Cg + C, _p(w2), _p(b2), _p(w3), _p(b3),
+              C2, C3, _p(y), st, flops=2 * Kf * N * (64 * 64 + Km * (64 * C2 + C2 * C3)))
+    return y
+
+
 class _SharedMlpMax(torch.autograd.Function):
     """relu(x W1^T + b1) -> relu(. W2^T + b2) -> max over the K=32 axis (model5_b.py:452-454, 459-461)."""
 

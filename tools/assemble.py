@@ -1,0 +1,68 @@
+"""Put K pieces together: the all-pairs table of puzzlenet_amd.assembly.match_pairs, the greedy walk of assemble(), the
+assembled cloud.
+
+    python tools/assemble.py --pieces pieces.npy [--ckpt model.ckpt] [--k 128] [--max-score S] [--out PREFIX]
+
+pieces.npy holds [K, N, 3] float32 (N = the model's points per piece).  Prints the score table and the edges in
+placement order, writes PREFIX_G.npy ([K,4,4], each piece into the root's frame) and PREFIX_cloud.npy ([K,N,3]).
+Needs a GPU; there is no CPU path."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np
+import torch
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--pieces", required=True, help=".npy file with [K, N, 3] float32 pieces")
+    ap.add_argument("--ckpt", default=None, help="reference checkpoint (puzzlenet_amd.checkpoint); closed-form weights if absent")
+    ap.add_argument("--k", type=int, default=128, help="boundary points picked per piece and pair")
+    ap.add_argument("--max-score", type=float, default=None, help="stop placing pieces above this boundary distance")
+    ap.add_argument("--out", default="assembly", help="prefix of the two .npy files written")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the FPS start indices")
+    args = ap.parse_args()
+
+    if not torch.cuda.is_available():
+        sys.exit("tools/assemble.py needs a GPU: puzzlenet_amd has no CPU path")
+    from puzzlenet_amd import assembly, checkpoint, model5_b
+    dev = torch.device("cuda:0")
+    pieces = np.load(args.pieces)
+    if pieces.ndim != 3 or pieces.shape[2] != 3:
+        sys.exit(f"{args.pieces}: expected [K, N, 3], got {pieces.shape}")
+    K, N, _ = pieces.shape
+    if args.ckpt:
+        model = checkpoint.build_from_reference_checkpoint(args.ckpt, num_points=N, device=dev)
+        print(f"weights: {args.ckpt}")
+    else:
+        from oracle import model_ref
+        model = model5_b.TouchedRegraster(model_ref.Cfg(num_points=N))
+        model_ref.fill_params(model)
+        model.to(dev)
+        print("weights: no --ckpt given, closed-form pseudo-random weights (oracle.model_ref.fill_params): the poses mean nothing")
+    model.fps_generator = torch.Generator().manual_seed(args.seed)
+
+    x = torch.from_numpy(np.ascontiguousarray(pieces, dtype=np.float32)).to(dev)
+    table = assembly.match_pairs(model, x, k=args.k)
+    result = assembly.assemble(table.score, table.T, max_score=args.max_score)
+
+    score = table.score.cpu().numpy()
+    print(f"score[fixed i, moved j] ({K} pieces of {N} points, k = {args.k}):")
+    with np.printoptions(precision=5, suppress=True, linewidth=200):
+        print(score)
+    print(f"root: piece {result.root}")
+    for i, j, s, new in result.edges:
+        print(f"  place piece {new}: pair (fixed {i}, moved {j}), score {s:.6f}")
+    left = [k for k in range(K) if not result.placed[k]]
+    if left:
+        print(f"not placed: {left}")
+    np.save(args.out + "_G.npy", result.G)
+    np.save(args.out + "_cloud.npy", assembly.apply(x, result.G).cpu().numpy())
+    print(f"wrote {args.out}_G.npy, {args.out}_cloud.npy")
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,161 @@
+"""All-pairs matching of K = 16 pieces of N = 1024 points (fp32, closed-form weights, seeded pieces): the factored table of
+puzzlenet_amd.assembly.match_pairs (a) against what a user had before it (b) - predict5(training=False) over the 240
+ordered pairs in batches of 64, followed by the same top-k / chamfer scoring - alternated in one process; then the
+pair-head kernel alone against the 16 point_mlp3 launches of match_pairs' fallback on the same inputs (the library's own
+event pair around every kernel launch, ops.ktimer_start / ktimer_stop), beside the bytes each must move.
+
+    python tools/bench_assembly.py [--reps 20] [--out profiles/assembly_k16.json]
+
+Needs a GPU (there is no CPU path)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch
+
+K, N, TOP, BATCH = 16, 1024, 128, 64
+
+
+def _timed(fn, reps):
+    ms = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return ms
+
+
+def _spread(ms):
+    s = sorted(ms)
+    return {"median_ms": statistics.median(s), "min_ms": s[0], "max_ms": s[-1], "p10_ms": s[len(s) // 10], "p90_ms": s[(9 * len(s)) // 10],
+            "reps": len(s)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "assembly_k16.json"))
+    args = ap.parse_args()
+    if args.reps < 20:
+        sys.exit("--reps: at least 20 timed repetitions each")
+    if not torch.cuda.is_available():
+        sys.exit("tools/bench_assembly.py needs a GPU: puzzlenet_amd has no CPU path")
+
+    from oracle import model_ref as mr
+    from puzzlenet_amd import assembly, model5_b, ops, se3
+    dev = torch.device("cuda:0")
+    model = model5_b.TouchedRegraster(mr.Cfg(num_points=N))
+    mr.fill_params(model)
+    model.to(dev)
+    model.fps_generator = torch.Generator().manual_seed(7)
+    g = torch.Generator().manual_seed(16)
+    pieces = torch.rand(K, N, 3, generator=g).to(dev)
+    off = [(i, j) for i in range(K) for j in range(K) if i != j]
+    I = torch.tensor([p[0] for p in off], device=dev)
+    J = torch.tensor([p[1] for p in off], device=dev)
+
+    def factored():
+        return assembly.match_pairs(model, pieces, k=TOP).score
+
+    def pair_batches():
+        """predict5 on the materialised pairs, 64 at a time, and the scoring of match_pairs on each batch."""
+        scores = []
+        with torch.no_grad():
+            for a in range(0, len(off), BATCH):
+                fpc, mrpc = pieces[I[a:a + BATCH]], pieces[J[a:a + BATCH]]
+                out, _, de_fpcb, de_mrpcb = model.predict5([fpc, mrpc], fpc.shape[0], training=False)
+                T = se3.exp(out)
+                top_f = ops.topk_rows(torch.softmax(de_fpcb, dim=1)[:, 1, :], TOP)
+                top_m = ops.topk_rows(torch.softmax(de_mrpcb, dim=1)[:, 1, :], TOP)
+                Bf = ops.index_points(fpc, top_f)
+                Bm = se3.transform_points(T, ops.index_points(mrpc, top_m))
+                d1, d2 = ops.chamfer(Bf, Bm)
+                scores.append(d1.mean(dim=1) + d2.mean(dim=1))
+        return torch.cat(scores)
+
+    for _ in range(args.warmup):
+        factored()
+        pair_batches()
+    ms_a, ms_b = [], []
+    for _ in range(args.reps):              # alternated: both see the same clocks and the same neighbours on the box
+        ms_a += _timed(factored, 1)
+        ms_b += _timed(pair_batches, 1)
+    a, b = _spread(ms_a), _spread(ms_b)
+
+    # ---- the fixed-side boundary head alone: one pair_head launch against the fallback's 16 point_mlp3 launches
+    with torch.no_grad():
+        gen = torch.Generator().manual_seed(3)
+        local = torch.randn(K, N, 64, generator=gen).to(dev)
+        gvec = torch.randn(K, 64, generator=gen).to(dev)
+        seq = model.MLPFpcb
+        l1, l2, l3 = seq[0], seq[2], seq[4]
+        par = (l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias)
+
+        def fast():
+            return ops.pair_head(local, gvec, *par)
+
+        def fallback():
+            return [ops.point_mlp3(local, *par, g=gvec[j:j + 1].expand(K, -1).reshape(K, 1, 64).contiguous()) for j in range(K)]
+
+        for _ in range(args.warmup):
+            fast()
+            fallback()
+
+        def kernel_time(fn, name):
+            ops.ktimer_start()
+            for _ in range(args.reps):
+                fn()
+            torch.cuda.synchronize()
+            rows = ops.ktimer_stop()
+            hit = [v for k_, v in rows.items() if name in k_]
+            if len(hit) != 1:
+                sys.exit(f"kernel timer: expected one row for {name}, got {sorted(rows)}")
+            others = {k_: v for k_, v in rows.items() if name not in k_}
+            return hit[0], others
+
+        (n_f, ms_f), rest_f = kernel_time(fast, "pair_head_fwd_kernel")
+        (n_s, ms_s), rest_s = kernel_time(fallback, "point_mlp3_fwd_kernel")
+    us_fast = 1e3 * ms_f / n_f                              # per launch = per table
+    us_slow = 1e3 * ms_s / n_s * K                          # 16 launches per table
+    weights = 4 * (64 * 64 + 32 * 64 + 32 + 2 * 32 + 2)
+    bytes_fast = 4 * K * N * 64 + 4 * K * 64 + weights + 4 * K * K * N * 2
+    bytes_slow = K * (4 * K * N * (64 + 64 + 32 + 2) + 4 * K * 64 + weights)
+    flop = 2 * K * N * (64 * 64 + K * (64 * 32 + 32 * 2))
+    mfma_us = 1e6 * flop / (2500e12 / 6)                    # six bf16 MFMAs per fp32 product
+    hbm_us = 1e6 * bytes_fast / 8e12
+    bound = "MFMA" if mfma_us >= hbm_us else "HBM"
+    result = {
+        "tool": "tools/bench_assembly.py", "device": torch.cuda.get_device_name(0), "K": K, "N": N, "k": TOP, "dtype": "float32",
+        "pairs": len(off), "pair_batch": BATCH,
+        "match_pairs": a, "predict5_pair_batches": b, "speedup_median": b["median_ms"] / a["median_ms"],
+        "pair_head_fwd_kernel": {
+            "kernel_us_per_table": us_fast, "launches_timed": n_f, "bytes": bytes_fast, "flop": flop,
+            "mfma_bound_us": mfma_us, "hbm_bound_us": hbm_us, "bound": bound,
+            "fraction_of_bound": max(mfma_us, hbm_us) / us_fast,
+            "other_kernels_us_per_table": {k_: 1e3 * v[1] / args.reps for k_, v in rest_f.items()}},
+        "point_mlp3_fallback": {
+            "kernel_us_per_table": us_slow, "launches_per_table": K, "launches_timed": n_s, "bytes": bytes_slow,
+            "hbm_bound_us": 1e6 * bytes_slow / 8e12,
+            "other_kernels_us_per_table": {k_: 1e3 * v[1] / args.reps for k_, v in rest_s.items()}},
+        "pair_head_over_fallback": us_slow / us_fast,
+    }
+    line = json.dumps(result)
+    print(line)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(json.dumps(result, indent=1) + "\n")
+    if not a["median_ms"] < b["median_ms"]:
+        sys.exit(f"match_pairs ({a['median_ms']:.3f} ms) is not faster than predict5 over the pair batches ({b['median_ms']:.3f} ms)")
+
+
+if __name__ == "__main__":
+    main()
