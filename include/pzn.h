@@ -82,6 +82,22 @@ int pzn_fps_background_f32(const float* xyz, int B, int N, int npoint,
                            const int64_t* start_idx, int64_t* out_idx,
                            const int64_t* counts, int max_count, pzn_stream_t stream);
 
+/* Merge two placed pieces and resample the union (no counterpart in the reference, which ships no assembly code; the rounds
+ * are pointnet_util.py:53-73): M merges in one launch, one workgroup each.  The union of merge m has Na + Nb rows: rows
+ * 0..Na-1 are a[m] [Na,3] as read, rows Na.. are b[m] [Nb,3] moved by T[m] ([4,4] row-major, as pzn_se3_exp_fwd_f32 writes
+ * it): x' = ((R00 x + R01 y) + R02 z) + t0 and likewise y', z', every product and sum rounded to fp32 on its own.
+ * Farthest point sampling of the union for n_out rounds, the arithmetic and the tie rule of pzn_fps_f32 (lowest union index),
+ * gives out[M,n_out,3] (the picked coordinates in pick order) and src[M,n_out] (int64 union index of every pick).
+ * drop_a[M,ka], drop_b[M,kb] (int64 rows of a / b; NULL or a count of 0: none; repeats allowed; an index outside its cloud
+ * is ignored): listed rows start with running distance 0 instead of 1e10 and are otherwise rows like any other, so one
+ * is picked only when every kept row is at distance 0 too.  start[M]: the union index sampling begins at (clamped to the
+ * union); if that row is dropped, the first kept row at or after it, wrapping round to 0.
+ * Na + Nb <= 4096 and 1 <= n_out <= Na + Nb (pzn_merge_resample_supported: 1 / 0); PZN_EUNSUPPORTED otherwise. */
+int pzn_merge_resample_supported(int Na, int Nb, int n_out);
+int pzn_merge_resample_f32(const float* a, const float* b, const float* T, const int64_t* start,
+                           const int64_t* drop_a, int ka, const int64_t* drop_b, int kb, int M, int Na, int Nb,
+                           int n_out, float* out, int64_t* src, pzn_stream_t stream);
+
 /* pointnet_util.py:118-119  dists.argsort()[:, :, :K] fused with the distance:
  * idx[B,S,K] = the K nearest points of xyz[B,N,3] to each new_xyz[B,S,3],
  * ascending by (distance, index) == a stable ascending sort.  K <= N. */

@@ -15,8 +15,15 @@ is per row), so the all-pairs table factors exactly:
     pair: one launch of ops.pair_head (csrc/pointmlp.hip, pair_head_fwd_kernel), which computes the first-layer product
     of a tile once and loops over the moved pieces in registers.
 
-Inference only: eval mode, torch.no_grad(), fp32, one GPU.  Out of scope: re-encoding merged pieces after each placement
-(resampling the union to N points and matching again), any training on more than two pieces, and more than one GPU.
+match_pairs is encode_pieces (everything that depends on one piece) and pair_block (the rectangular [Kf, Km] block) plus the
+diagonal fill.  ProgressiveAssembler uses the same two for what the greedy walk leaves out - it never looks at a merged
+shape -: every round it takes the smallest score, merges the two parts on the device (ops.merge_resample: the moved part
+under its pose, the union resampled to N points by farthest point sampling with the matched boundary points left out, the
+origin of every point kept), encodes the merged part alone - its sampling plan is read off its pick order, no FPS - and
+computes only its row and its column of the table again.
+
+Inference only: eval mode, torch.no_grad(), fp32, one GPU.  Out of scope: any training on merged parts or on more than two
+pieces, beam search or several merges per round, undoing a merge, and more than one GPU.
 """
 import collections
 
@@ -28,6 +35,9 @@ from .model5_b import _run_seq, _run_seq_cat_global
 
 PairTable = collections.namedtuple("PairTable", "twist T de_fpcb de_mrpcb top_f top_m score x2")
 Assembly = collections.namedtuple("Assembly", "root edges G placed")
+PieceCodes = collections.namedtuple("PieceCodes", "U V local_f g_max de_mrpcb top_m x2")
+PairBlock = collections.namedtuple("PairBlock", "twist T de_fpcb top_f score")
+Progressive = collections.namedtuple("Progressive", "G edges placed cloud piece_id row_id parts")
 
 ENCODER_ROWS = 64      # pieces per encoder call (the fused per-point stem takes up to 64 clouds)
 
@@ -67,39 +77,43 @@ def _pair_fixed_head(seq, local, g):
     return torch.stack(cols, dim=1)
 
 
-def match_pairs(model, pieces, k=128, start=None):
-    """All K (K - 1) ordered pairs of `pieces` [K,N,3] (float32, on the GPU, N = model.num_points, K >= 2) through
-    predict5's eval path with every piece encoded once -> PairTable, index order [fixed i, moved j]:
-
-      twist [K,K,6]       predict5's `out` for fpc = pieces[i], mrpc = pieces[j]
-      T [K,K,4,4]         se3.exp(twist): maps piece j into piece i's frame
-      de_fpcb [K,K,2,N]   fixed-side boundary logits (a permuted view of the kernel's [K,K,N,2])
-      de_mrpcb [K,2,N]    moved-side boundary logits (they depend on j only)
-      top_f [K,K,k], top_m [K,k]   the k points of largest class-1 probability
-      score [K,K]         mean + mean of the chamfer distances between pieces[i][top_f[i,j]] and T[i,j] applied to
-                          pieces[j][top_m[j]]; +inf on the diagonal
-      x2 [K,256,3]        the second-level sample points of every piece (one plan, shared by both encoders)
-
-    start = (s1[K], s2[K]): int64 FPS start indices of the two set-abstraction levels; None draws them with
-    torch.randint(0, N, (K,)) then torch.randint(0, 512, (K,)) from model.fps_generator (the global generator when that
-    is None).  Any K is taken: the encoders run on 64 pieces at a time.  Nothing here waits for the device."""
+def _check_pieces(model, pieces, k, who, least=1):
     if not isinstance(pieces, torch.Tensor) or not pieces.is_cuda:
-        raise _lib.PznError("match_pairs: pieces must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
+        raise _lib.PznError(f"{who}: pieces must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
     if pieces.dim() != 3 or pieces.shape[2] != 3 or pieces.dtype != torch.float32:
-        raise _lib.PznError(f"match_pairs expects float32 pieces[K,N,3]; got {pieces.dtype} {tuple(pieces.shape)}")
+        raise _lib.PznError(f"{who} expects float32 pieces[K,N,3]; got {pieces.dtype} {tuple(pieces.shape)}")
     K, N, _ = pieces.shape
-    if K < 2 or N != model.num_points:
-        raise _lib.PznError(f"match_pairs: K = {K} pieces (>= 2) of N = {N} points (the model takes {model.num_points})")
+    if K < least or N != model.num_points:
+        raise _lib.PznError(f"{who}: K = {K} pieces (>= {least}) of N = {N} points (the model takes {model.num_points})")
     k = int(k)
     if not 0 < k <= N:
-        raise _lib.PznError(f"match_pairs: k = {k} of {N} points")
+        raise _lib.PznError(f"{who}: k = {k} of {N} points")
+    return K, N, k
+
+
+def encode_pieces(model, pieces, k=128, start=None, plan=None, _who="encode_pieces", _least=1):
+    """Everything of the pair table that depends on ONE piece, for pieces [K,N,3] (float32, on the GPU) -> PieceCodes:
+
+      U [K,H], V [K,H]    the fixed and the moved half of the pose head's first layer (V carries the bias)
+      local_f [K,N,64]    MLPLocalPreFpc over Encoder's per-point features (the fixed-side boundary head's input)
+      g_max [K,64]        the max over MLPLocalPreRpc of Encoder2's per-point features (model5_b.py:440)
+      de_mrpcb [K,2,N]    moved-side boundary logits
+      top_m [K,k]         their k points of largest class-1 probability
+      x2 [K,256,3]        the second-level sample points
+
+    start = (s1[K], s2[K]) as match_pairs takes it; plan = ((x1, idx1), (x2, idx2)) replaces both FPS levels and both
+    neighbour searches by a plan the caller already has (start is ignored then).  Encoder2 runs on the model's side stream
+    beside Encoder.  Nothing here waits for the device."""
+    K, N, k = _check_pieces(model, pieces, k, _who, _least)
     pieces = pieces.contiguous()
     dev = pieces.device
     for m in (model.Encoder, model.Encoder2, model.tfMLP, model.fpc_decoder, model.rpc_decoder):
         if any(sm.training for sm in m.modules()):
             m.train(False)
     with torch.no_grad():
-        if start is None:
+        if plan is not None:
+            pass
+        elif start is None:
             gen = getattr(model, "fps_generator", None)
             s1 = torch.randint(0, N, (K,), dtype=torch.long, generator=gen)
             s2 = torch.randint(0, 512, (K,), dtype=torch.long, generator=gen)
@@ -109,8 +123,9 @@ def match_pairs(model, pieces, k=128, start=None):
         else:
             s1, s2 = (torch.as_tensor(s, dtype=torch.long).to(dev, non_blocking=True) for s in start)
             if s1.shape != (K,) or s2.shape != (K,):
-                raise _lib.PznError(f"match_pairs: start = (s1[{K}], s2[{K}]); got {tuple(s1.shape)}, {tuple(s2.shape)}")
-        plan = _plan(model, pieces, s1, s2)
+                raise _lib.PznError(f"{_who}: start = (s1[{K}], s2[{K}]); got {tuple(s1.shape)}, {tuple(s2.shape)}")
+        if plan is None:
+            plan = _plan(model, pieces, s1, s2)
 
         cur = torch.cuda.current_stream(dev)
         side = model.side_stream()
@@ -134,9 +149,8 @@ def match_pairs(model, pieces, k=128, start=None):
         for t in (pieces,) + tuple(t for lvl in plan for t in lvl):      # made on this stream, read on the side stream
             t.record_stream(side)
 
-        # pose head: the first layer splits into a fixed and a moved half, the other four run on the K^2 rows
-        mods = list(model.tfMLP)
-        w1, b1 = mods[0].weight, mods[0].bias
+        # pose head: the first layer splits into a fixed and a moved half
+        w1, b1 = model.tfMLP[0].weight, model.tfMLP[0].bias
         D = ffpc.shape[1]
         U = torch.empty((K, w1.shape[0]), dtype=torch.float32, device=dev)
         V = torch.empty_like(U)
@@ -147,25 +161,62 @@ def match_pairs(model, pieces, k=128, start=None):
                       U.data_ptr(), st, flops=2 * K * D * w1.shape[0])
             ops._call("pzn_linear_slice_fwd_f32", fmrpc.data_ptr(), w1.data_ptr() + 4 * D, w1.shape[1], b1.data_ptr(), K,
                       w1.shape[1] - D, w1.shape[0], 0, V.data_ptr(), st, flops=2 * K * (w1.shape[1] - D) * w1.shape[0])
-        hidden = torch.relu(U[:, None] + V[None]).reshape(K * K, -1)
-        twist = _run_seq(mods[2:], hidden).view(K, K, 6)
+        p_m = torch.softmax(de_mrpcb, dim=-1)[..., 1]
+        top_m = ops.topk_rows(p_m, k)
+    return PieceCodes(U, V, local_f, g_max, de_mrpcb.permute(0, 2, 1), top_m, plan[1][0])
+
+
+def pair_block(model, pieces_f, codes_f, pieces_m, codes_m, k=128):
+    """The rectangular block of the pair table with pieces_f [Kf,N,3] in the fixed role and pieces_m [Km,N,3] in the moved
+    role, from their PieceCodes -> PairBlock(twist [Kf,Km,6], T [Kf,Km,4,4], de_fpcb [Kf,Km,2,N], top_f [Kf,Km,k],
+    score [Kf,Km]); entries as match_pairs documents them (no diagonal is masked here)."""
+    Kf, N = pieces_f.shape[0], pieces_f.shape[1]
+    Km = pieces_m.shape[0]
+    k = int(k)
+    with torch.no_grad():
+        # pose head: the four layers after the split first one run on the Kf Km rows relu(U_i + V_j)
+        hidden = torch.relu(codes_f.U[:, None] + codes_m.V[None]).reshape(Kf * Km, -1)
+        twist = _run_seq(list(model.tfMLP)[2:], hidden).view(Kf, Km, 6)
         T = se3.exp(twist)
 
-        y_f = _pair_fixed_head(model.MLPFpcb, local_f, g_max)                                # [K,K,N,2]
+        y_f = _pair_fixed_head(model.MLPFpcb, codes_f.local_f, codes_m.g_max)                # [Kf,Km,N,2]
         de_fpcb = y_f.permute(0, 1, 3, 2)
 
         # the k points of largest class-1 probability (softmax over two logits) and the boundary-to-boundary distance
-        p_f = torch.softmax(y_f, dim=-1)[..., 1].reshape(K * K, N)
-        p_m = torch.softmax(de_mrpcb, dim=-1)[..., 1]
-        top_f = ops.topk_rows(p_f, k).view(K, K, k)
-        top_m = ops.topk_rows(p_m, k)
-        Bf = ops.index_points(pieces, top_f.reshape(K, K * k)).view(K * K, k, 3)             # pieces[i][top_f[i, j]]
-        Bm = ops.index_points(pieces, top_m)                                                 # pieces[j][top_m[j]]
-        Bm = se3.transform_points(T.reshape(K * K, 4, 4), Bm.unsqueeze(0).expand(K, -1, -1, -1).reshape(K * K, k, 3))
+        p_f = torch.softmax(y_f, dim=-1)[..., 1].reshape(Kf * Km, N)
+        top_f = ops.topk_rows(p_f, k).view(Kf, Km, k)
+        Bf = ops.index_points(pieces_f, top_f.reshape(Kf, Km * k)).view(Kf * Km, k, 3)       # pieces_f[i][top_f[i, j]]
+        Bm = ops.index_points(pieces_m, codes_m.top_m)                                       # pieces_m[j][top_m[j]]
+        Bm = se3.transform_points(T.reshape(Kf * Km, 4, 4), Bm.unsqueeze(0).expand(Kf, -1, -1, -1).reshape(Kf * Km, k, 3))
         d1, d2 = ops.chamfer(Bf, Bm)
-        score = (d1.mean(dim=1) + d2.mean(dim=1)).view(K, K)
-        score = score.masked_fill(torch.eye(K, dtype=torch.bool, device=dev), float("inf"))
-    return PairTable(twist, T, de_fpcb, de_mrpcb.permute(0, 2, 1), top_f, top_m, score, plan[1][0])
+        score = (d1.mean(dim=1) + d2.mean(dim=1)).view(Kf, Km)
+    return PairBlock(twist, T, de_fpcb, top_f, score)
+
+
+def match_pairs(model, pieces, k=128, start=None):
+    """All K (K - 1) ordered pairs of `pieces` [K,N,3] (float32, on the GPU, N = model.num_points, K >= 2) through
+    predict5's eval path with every piece encoded once -> PairTable, index order [fixed i, moved j]:
+
+      twist [K,K,6]       predict5's `out` for fpc = pieces[i], mrpc = pieces[j]
+      T [K,K,4,4]         se3.exp(twist): maps piece j into piece i's frame
+      de_fpcb [K,K,2,N]   fixed-side boundary logits (a permuted view of the kernel's [K,K,N,2])
+      de_mrpcb [K,2,N]    moved-side boundary logits (they depend on j only)
+      top_f [K,K,k], top_m [K,k]   the k points of largest class-1 probability
+      score [K,K]         mean + mean of the chamfer distances between pieces[i][top_f[i,j]] and T[i,j] applied to
+                          pieces[j][top_m[j]]; +inf on the diagonal
+      x2 [K,256,3]        the second-level sample points of every piece (one plan, shared by both encoders)
+
+    start = (s1[K], s2[K]): int64 FPS start indices of the two set-abstraction levels; None draws them with
+    torch.randint(0, N, (K,)) then torch.randint(0, 512, (K,)) from model.fps_generator (the global generator when that
+    is None).  Any K is taken: the encoders run on 64 pieces at a time.  Nothing here waits for the device.
+    It is encode_pieces, the square pair_block and the diagonal fill."""
+    codes = encode_pieces(model, pieces, k, start, _who="match_pairs", _least=2)
+    pieces = pieces.contiguous()
+    blk = pair_block(model, pieces, codes, pieces, codes, k)
+    K = pieces.shape[0]
+    with torch.no_grad():
+        score = blk.score.masked_fill(torch.eye(K, dtype=torch.bool, device=pieces.device), float("inf"))
+    return PairTable(blk.twist, blk.T, blk.de_fpcb, codes.de_mrpcb, blk.top_f, codes.top_m, score, codes.x2)
 
 
 def _host(a):
@@ -232,3 +283,202 @@ def apply(pieces, G):
         raise _lib.PznError("apply: pieces must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
     g = torch.as_tensor(np.asarray(G) if not isinstance(G, torch.Tensor) else G).to(pieces.device, torch.float32)
     return se3.transform_points(g.contiguous(), pieces.contiguous())
+
+
+# --------------------------------------------------------------------------- progressive assembly
+
+def _choose(score, max_score=None):
+    """The first row-major minimum off the diagonal of score[K,K] (host) -> (i, j, s), or None when it is not finite or
+    above max_score."""
+    S = np.array(score, dtype=np.float64)
+    K = S.shape[0]
+    S[np.arange(K), np.arange(K)] = np.inf
+    S[np.isnan(S)] = np.inf
+    i, j = divmod(int(np.argmin(S)), K)
+    s = float(S[i, j])
+    if not np.isfinite(s) or (max_score is not None and s > max_score):
+        return None
+    return i, j, s
+
+
+class MergeLedger:
+    """The host side of progressive assembly, float64: which original pieces every current part holds and where they sit.
+
+      members   one list of original piece indices per current part (a part's label is the lowest of them)
+      frame     per current part, the original piece whose frame the part lives in
+      G [K,4,4] maps original piece p into the frame of the part that holds it
+      edges     (label_i, label_j, score, dropped_a, dropped_b) in merge order"""
+
+    def __init__(self, K):
+        self.members = [[p] for p in range(K)]
+        self.frame = list(range(K))
+        self.G = np.tile(np.eye(4), (K, 1, 1))
+        self.edges = []
+
+    def label(self, part):
+        return min(self.members[part])
+
+    def merge(self, i, j, T_ij, score, dropped_a=None, dropped_b=None):
+        """Part j, moved by T_ij (which maps it into part i's frame), joins part i and is removed from the list: parts
+        after j move down one place -> the new index of the merged part."""
+        if i == j:
+            raise ValueError("a part cannot be merged with itself")
+        T_ij = np.asarray(T_ij, dtype=np.float64)
+        edge = (self.label(i), self.label(j), float(score), dropped_a, dropped_b)
+        for p in self.members[j]:
+            self.G[p] = T_ij @ self.G[p]
+        self.members[i].extend(self.members[j])
+        del self.members[j], self.frame[j]
+        self.edges.append(edge)
+        return i if i < j else i - 1
+
+
+def _del1(x, j):
+    return torch.cat((x[:j], x[j + 1:]), dim=0)
+
+
+def _del2(x, j):
+    x = _del1(x, j)
+    return torch.cat((x[:, :j], x[:, j + 1:]), dim=1)
+
+
+class ProgressiveAssembler:
+    """Progressive assembly: after every placement the two joined parts are merged into ONE N-point part (ops.merge_resample:
+    the union resampled by farthest point sampling, the matched boundary points left out with drop_matched), the merged part
+    is encoded alone and only its row and its column of the pair table are computed again.
+
+    State: parts [K',N,3] (device), codes (their PieceCodes), table (their PairTable), piece_id / row_id [K',N] int64
+    (which original piece and row every point is), starts (the FPS starts (s1, s2) of every current part, host lists),
+    and the MergeLedger fields members, G, edges.  pieces, k, start as match_pairs takes them; max_score stops the walk
+    at the first minimum above it; generator draws the merges' start rows (torch.randint(0, N) on the host, K - 1 draws
+    at construction).  Inference only: eval mode, no_grad, fp32, one GPU."""
+
+    def __init__(self, model, pieces, k=128, start=None, max_score=None, drop_matched=True, generator=None):
+        K, N, k = _check_pieces(model, pieces, k, "ProgressiveAssembler", 2)
+        if drop_matched and 2 * k > N:
+            raise _lib.PznError(f"ProgressiveAssembler: drop_matched needs k <= N / 2 (k = {k}, N = {N}): the rows kept "
+                                "of a union must fill the merged part")
+        if not ops.merge_resample_supported(N, N, N):
+            raise _lib.PznUnsupported(f"ProgressiveAssembler: two parts of N = {N} points are not a union merge_resample takes")
+        self.model, self.k, self.max_score, self.drop_matched = model, k, max_score, bool(drop_matched)
+        dev = pieces.device
+        if start is None:
+            gen = getattr(model, "fps_generator", None)
+            s1 = torch.randint(0, N, (K,), dtype=torch.long, generator=gen)
+            s2 = torch.randint(0, 512, (K,), dtype=torch.long, generator=gen)
+        else:
+            s1, s2 = (torch.as_tensor(s, dtype=torch.long).cpu() for s in start)
+        self._s1, self._s2 = s1.tolist(), s2.tolist()
+        self.parts = pieces.contiguous().clone()
+        self.codes = encode_pieces(model, self.parts, k, (s1, s2), _who="ProgressiveAssembler", _least=2)
+        blk = pair_block(model, self.parts, self.codes, self.parts, self.codes, k)
+        eye = torch.eye(K, dtype=torch.bool, device=dev)
+        self.table = PairTable(blk.twist, blk.T, blk.de_fpcb, self.codes.de_mrpcb, blk.top_f, self.codes.top_m,
+                               blk.score.masked_fill(eye, float("inf")), self.codes.x2)
+        self.piece_id = torch.arange(K, dtype=torch.long, device=dev)[:, None].expand(K, N).contiguous()
+        self.row_id = torch.arange(N, dtype=torch.long, device=dev)[None].expand(K, N).contiguous()
+        self.ledger = MergeLedger(K)
+        stage = torch.empty((K - 1,), dtype=torch.long, pin_memory=True)
+        torch.randint(0, N, (K - 1,), dtype=torch.long, generator=generator, out=stage)
+        self.merge_starts = stage.tolist()
+        self._merge_starts = stage.to(dev, non_blocking=True)
+        self._stage = stage      # (alive until the copy has run)
+        self.rounds = 0
+
+    members = property(lambda self: self.ledger.members)
+    G = property(lambda self: self.ledger.G)
+    edges = property(lambda self: self.ledger.edges)
+
+    @property
+    def starts(self):
+        return torch.tensor(self._s1, dtype=torch.long), torch.tensor(self._s2, dtype=torch.long)
+
+    def step(self):
+        """One round -> the edge made, or None when one part is left, the smallest score is not finite or it is above
+        max_score.  One wait for the device: the download of the scores and poses the choice is made from."""
+        t = self.table
+        Kp, N, k = self.parts.shape[0], self.parts.shape[1], self.k
+        if Kp < 2:
+            return None
+        with torch.no_grad():
+            # 1. choose the pair (scores and poses in one download)
+            host = torch.cat((t.score.reshape(-1), t.T.reshape(-1))).cpu().double().numpy()
+            pick = _choose(host[:Kp * Kp].reshape(Kp, Kp), self.max_score)
+            if pick is None:
+                return None
+            i, j, s = pick
+            T_ij = host[Kp * Kp:].reshape(Kp, Kp, 4, 4)[i, j]
+
+            # 2. merge: part j moved into part i's frame, the union resampled to N points
+            da = t.top_f[i, j].reshape(1, k) if self.drop_matched else None
+            db = t.top_m[j].reshape(1, k) if self.drop_matched else None
+            u = self._merge_starts[self.rounds:self.rounds + 1]
+            merged, src = ops.merge_resample(self.parts[i:i + 1], self.parts[j:j + 1], t.T[i, j].reshape(1, 4, 4), u, N, da, db)
+            pid = torch.cat((self.piece_id[i], self.piece_id[j]))
+            rid = torch.cat((self.row_id[i], self.row_id[j]))
+            dropped = (None, None)
+            if self.drop_matched:
+                dropped = (torch.stack((self.piece_id[i][da[0]], self.row_id[i][da[0]]), dim=1),
+                           torch.stack((self.piece_id[j][db[0]], self.row_id[j][db[0]]), dim=1))
+            pid, rid = pid[src[0]], rid[src[0]]
+
+            # 3. host bookkeeping
+            n = self.ledger.merge(i, j, T_ij, s, *dropped)
+            del self._s1[j], self._s2[j]
+            self._s1[n] = self._s2[n] = 0
+            self.rounds += 1
+
+            # 4. the merged part comes out in pick order: its first 512 points are its FPS-512 sample started at point 0,
+            # the first 256 of those the FPS-256 sample of that: the sampling plan costs no FPS
+            x1 = merged[:, :512].contiguous()
+            x2 = merged[:, :256].contiguous()
+            plan = ((x1, ops.knn(merged, x1, 32)), (x2, ops.knn(x1, x2, 32)))
+
+            # 5. encode the merged part alone; its row and its column of the table; row and column j leave
+            code = encode_pieces(self.model, merged, k, plan=plan, _who="ProgressiveAssembler")
+            self.parts = _del1(self.parts, j)
+            self.parts[n] = merged[0]
+            self.piece_id, self.row_id = _del1(self.piece_id, j), _del1(self.row_id, j)
+            self.piece_id[n], self.row_id[n] = pid, rid
+            fields = []
+            for old, new in zip(self.codes, code):
+                old = _del1(old, j)
+                old[n] = new[0]
+                fields.append(old)
+            self.codes = PieceCodes(*fields)
+            row = pair_block(self.model, merged, code, self.parts, self.codes, k)      # [1, K' - 1]
+            col = pair_block(self.model, self.parts, self.codes, merged, code, k)      # [K' - 1, 1]
+            upd = {}
+            for name in PairBlock._fields:
+                x = _del2(getattr(t, name), j)
+                x[:, n] = getattr(col, name)[:, 0]
+                x[n] = getattr(row, name)[0]
+                upd[name] = x
+            upd["score"][n, n] = float("inf")
+            self.table = PairTable(upd["twist"], upd["T"], upd["de_fpcb"], self.codes.de_mrpcb, upd["top_f"], self.codes.top_m,
+                                   upd["score"], self.codes.x2)
+        return self.ledger.edges[-1]
+
+    def run(self):
+        while self.step() is not None:
+            pass
+        return self.result()
+
+    def result(self):
+        """-> Progressive(G, edges, placed [K] bool, cloud [N,3], piece_id [N], row_id [N], parts [K',N,3]): cloud and its two
+        provenance rows are those of the part that holds the first edge's fixed piece (part 0 when no edge was made);
+        placed marks the pieces in that part, and none without an edge."""
+        K = self.ledger.G.shape[0]
+        placed = np.zeros(K, dtype=bool)
+        root = 0
+        if self.ledger.edges:
+            first = self.ledger.edges[0][0]
+            root = next(q for q, mem in enumerate(self.ledger.members) if first in mem)
+            placed[self.ledger.members[root]] = True
+        return Progressive(self.ledger.G.copy(), list(self.ledger.edges), placed, self.parts[root], self.piece_id[root],
+                           self.row_id[root], self.parts)
+
+
+def assemble_progressive(model, pieces, k=128, start=None, max_score=None, drop_matched=True, generator=None):
+    """ProgressiveAssembler(...).step() until one part is left or the walk stops -> Progressive."""
+    return ProgressiveAssembler(model, pieces, k, start, max_score, drop_matched, generator).run()

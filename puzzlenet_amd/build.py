@@ -27,6 +27,7 @@ NOSLP = ["-fno-slp-vectorize"]
 SOURCES = [
     ("core.hip", NOSLP),
     ("fps.hip", ["-ffp-contract=off"] + NOSLP),
+    ("mergefps.hip", ["-ffp-contract=off"] + NOSLP),
     ("knn.hip", ["-ffp-contract=off"]),
     ("group.hip", ["-ffp-contract=off"] + NOSLP),
     ("emd.hip", NOSLP),

@@ -185,6 +185,48 @@ def farthest_point_sample(xyz, npoint, start_idx, background=False, counts=None,
     return out
 
 
+def merge_resample_supported(Na, Nb, n_out):
+    return bool(_lib.load().pzn_merge_resample_supported(int(Na), int(Nb), int(n_out)))
+
+
+def merge_resample(a, b, T, start, n_out=None, drop_a=None, drop_b=None):
+    """M merges in one launch (pzn_merge_resample_f32): the union of a[M,Na,3] and T[M,4,4] applied to b[M,Nb,3], resampled
+    to n_out (default Na) points by farthest point sampling from the union index start[M] -> (points [M,n_out,3] in pick
+    order, src [M,n_out] int64 union index of every pick: u < Na is row u of a, otherwise row u - Na of b).  drop_a[M,ka],
+    drop_b[M,kb] (int64, optional): rows that start at running distance 0, i.e. are picked only when every kept row is at 0
+    too; a start on a dropped row moves to the first kept row at or after it, wrapping round.  Na + Nb <= 4096
+    (PznUnsupported beyond).  No autograd, nothing waits for the device."""
+    a, b, T = _f32(a, "a"), _f32(b, "b"), _f32(T, "T")
+    if a.dim() != 3 or b.dim() != 3 or a.shape[2] != 3 or b.shape[2] != 3 or b.shape[0] != a.shape[0]:
+        raise _lib.PznError(f"merge_resample: expected a[M,Na,3], b[M,Nb,3]; got {tuple(a.shape)}, {tuple(b.shape)}")
+    M, Na, Nb = a.shape[0], a.shape[1], b.shape[1]
+    if T.shape != (M, 4, 4):
+        raise _lib.PznError(f"merge_resample: expected T[{M},4,4]; got {tuple(T.shape)}")
+    start = _i64(start, "start")
+    if start.shape != (M,):
+        raise _lib.PznError(f"merge_resample: expected start[{M}]; got {tuple(start.shape)}")
+    n_out = Na if n_out is None else int(n_out)
+    drops = []
+    for name, d in (("drop_a", drop_a), ("drop_b", drop_b)):
+        if d is not None:
+            d = _i64(d, name)
+            if d.dim() != 2 or d.shape[0] != M:
+                raise _lib.PznError(f"merge_resample: expected {name}[{M},k]; got {tuple(d.shape)}")
+            if d.shape[1] == 0:
+                d = None
+        drops.append(d)
+    da, db = drops
+    if M == 0 or not merge_resample_supported(Na, Nb, n_out):
+        raise _lib.PznUnsupported(f"merge_resample: M = {M} merges of Na = {Na} and Nb = {Nb} rows to n_out = {n_out} "
+                                  "(Na + Nb <= 4096, 1 <= n_out <= Na + Nb)")
+    out = torch.empty((M, n_out, 3), dtype=torch.float32, device=a.device)
+    src = torch.empty((M, n_out), dtype=torch.int64, device=a.device)
+    with _on(a.device):
+        _call("pzn_merge_resample_f32", _p(a), _p(b), _p(T), _p(start), _p(da), 0 if da is None else da.shape[1], _p(db),
+              0 if db is None else db.shape[1], M, Na, Nb, n_out, _p(out), _p(src), _stream())
+    return out, src
+
+
 def knn(xyz, new_xyz, K):
     xyz, new_xyz = _f32(xyz, "xyz"), _f32(new_xyz, "new_xyz")
     B, N, _ = xyz.shape

@@ -1,10 +1,13 @@
 """Put K pieces together: the all-pairs table of puzzlenet_amd.assembly.match_pairs, the greedy walk of assemble(), the
 assembled cloud.
 
-    python tools/assemble.py --pieces pieces.npy [--ckpt model.ckpt] [--k 128] [--max-score S] [--out PREFIX]
+    python tools/assemble.py --pieces pieces.npy [--ckpt model.ckpt] [--k 128] [--max-score S] [--out PREFIX] [--progressive]
 
 pieces.npy holds [K, N, 3] float32 (N = the model's points per piece).  Prints the score table and the edges in
 placement order, writes PREFIX_G.npy ([K,4,4], each piece into the root's frame) and PREFIX_cloud.npy ([K,N,3]).
+--progressive: assembly.assemble_progressive instead - after every placement the two parts are merged and resampled to N
+points and matched again -; PREFIX_G.npy then maps each piece into the frame of the part that holds it, PREFIX_cloud.npy
+is the [N,3] part around the first pair, PREFIX_piece_id.npy / PREFIX_row_id.npy say where each of its points came from.
 Needs a GPU; there is no CPU path."""
 import argparse
 import os
@@ -24,6 +27,8 @@ def main():
     ap.add_argument("--max-score", type=float, default=None, help="stop placing pieces above this boundary distance")
     ap.add_argument("--out", default="assembly", help="prefix of the two .npy files written")
     ap.add_argument("--seed", type=int, default=0, help="seed of the FPS start indices")
+    ap.add_argument("--progressive", action="store_true", help="merge placed parts, resample and match again after every placement")
+    ap.add_argument("--keep-matched", action="store_true", help="--progressive: keep the matched boundary points in the merged part")
     args = ap.parse_args()
 
     if not torch.cuda.is_available():
@@ -46,6 +51,19 @@ def main():
     model.fps_generator = torch.Generator().manual_seed(args.seed)
 
     x = torch.from_numpy(np.ascontiguousarray(pieces, dtype=np.float32)).to(dev)
+    if args.progressive:
+        res = assembly.assemble_progressive(model, x, k=args.k, max_score=args.max_score, drop_matched=not args.keep_matched,
+                                            generator=torch.Generator().manual_seed(args.seed))
+        for a, b, s, _da, _db in res.edges:
+            print(f"  merge: part of piece {b} into part of piece {a}, score {s:.6f}")
+        left = [k for k in range(K) if not res.placed[k]]
+        if left:
+            print(f"not in the part around the first pair: {left} ({res.parts.shape[0]} parts left)")
+        np.save(args.out + "_G.npy", res.G)
+        for name, t in (("cloud", res.cloud), ("piece_id", res.piece_id), ("row_id", res.row_id)):
+            np.save(f"{args.out}_{name}.npy", t.cpu().numpy())
+        print(f"wrote {args.out}_G.npy, {args.out}_cloud.npy, {args.out}_piece_id.npy, {args.out}_row_id.npy")
+        return
     table = assembly.match_pairs(model, x, k=args.k)
     result = assembly.assemble(table.score, table.T, max_score=args.max_score)
 

@@ -5,6 +5,12 @@ pair-head kernel alone against the 16 point_mlp3 launches of match_pairs' fallba
 event pair around every kernel launch, ops.ktimer_start / ktimer_stop), beside the bytes each must move.
 
     python tools/bench_assembly.py [--reps 20] [--out profiles/assembly_k16.json]
+    python tools/bench_assembly.py --progressive [--reps 20] [--out profiles/assembly_progressive_k16.json]
+
+--progressive measures instead (a) ops.merge_resample against the unfused chain se3.transform_points -> cat ->
+farthest_point_sample -> index_points on the same inputs (Na = Nb = 1024 and 2048, M = 1 and 16; device time between two
+events around 20 back-to-back calls, five repeats, alternated) and (b) one ProgressiveAssembler.step() at K = 16 against
+match_pairs on the same 15 parts, what a round cost before it (host wall time around a synchronised call, alternated).
 
 Needs a GPU (there is no CPU path)."""
 import argparse
@@ -39,16 +45,96 @@ def _spread(ms):
             "reps": len(s)}
 
 
+def _device_ms(fn, calls):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(calls):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / calls
+
+
+def progressive(args):
+    from oracle import model_ref as mr
+    from puzzlenet_amd import assembly, model5_b, ops, se3
+    dev = torch.device("cuda:0")
+    result = {"tool": "tools/bench_assembly.py --progressive", "device": torch.cuda.get_device_name(0), "dtype": "float32",
+              "merge": [], "k": TOP}
+    g = torch.Generator().manual_seed(16)
+    for n in (1024, 2048):
+        for M in (1, 16):
+            a, b = torch.rand(M, n, 3, generator=g).to(dev), torch.rand(M, n, 3, generator=g).to(dev)
+            T = se3.exp(((torch.rand(M, 6, generator=g) - 0.5)).to(dev))
+            start = torch.randint(0, 2 * n, (M,), generator=g).to(dev)
+
+            def fused():
+                return ops.merge_resample(a, b, T, start, n)
+
+            def chain():
+                u = torch.cat((a, se3.transform_points(T, b)), dim=1)
+                return ops.index_points(u, ops.farthest_point_sample(u, n, start))
+
+            with torch.no_grad():
+                if not torch.equal(fused()[0], chain()):
+                    # (the chain's transform rounds in its own order: equal picks are not promised, only the same work)
+                    result.setdefault("note", "fused and chained outputs differ in some bits (transform rounding order)")
+                for _ in range(args.warmup):
+                    fused(), chain()
+                f_ms, c_ms = [], []
+                for _ in range(5):
+                    f_ms.append(_device_ms(fused, 20))
+                    c_ms.append(_device_ms(chain, 20))
+            row = {"Na": n, "Nb": n, "n_out": n, "M": M, "fused_ms": sorted(f_ms), "chain_ms": sorted(c_ms),
+                   "fused_median_ms": statistics.median(f_ms), "chain_median_ms": statistics.median(c_ms)}
+            row["chain_over_fused"] = row["chain_median_ms"] / row["fused_median_ms"]
+            print(json.dumps(row))
+            result["merge"].append(row)
+
+    model = model5_b.TouchedRegraster(mr.Cfg(num_points=N))
+    mr.fill_params(model)
+    model.to(dev)
+    pieces = torch.rand(K, N, 3, generator=g).to(dev)
+    s1, s2 = torch.randint(0, N, (K,), generator=g), torch.randint(0, 512, (K,), generator=g)
+    step_ms, full_ms = [], []
+    for rep in range(args.warmup + args.reps):
+        asm = assembly.ProgressiveAssembler(model, pieces, k=TOP, start=(s1, s2), generator=torch.Generator().manual_seed(rep))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        edge = asm.step()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        if edge is None or asm.parts.shape[0] != K - 1:
+            sys.exit("the first round made no edge")
+        parts, starts = asm.parts, asm.starts
+        ms = _timed(lambda: assembly.match_pairs(model, parts, k=TOP, start=starts), 1)
+        if rep >= args.warmup:
+            step_ms.append((t1 - t0) * 1e3)
+            full_ms += ms
+    result["round_K16"] = {"K": K, "N": N, "step": _spread(step_ms), "match_pairs_15_parts": _spread(full_ms),
+                           "full_over_step_median": statistics.median(full_ms) / statistics.median(step_ms)}
+    print(json.dumps(result["round_K16"]))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(json.dumps(result, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "assembly_k16.json"))
+    ap.add_argument("--progressive", action="store_true")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "assembly_progressive_k16.json" if args.progressive else "assembly_k16.json")
     if args.reps < 20:
         sys.exit("--reps: at least 20 timed repetitions each")
     if not torch.cuda.is_available():
         sys.exit("tools/bench_assembly.py needs a GPU: puzzlenet_amd has no CPU path")
+    if args.progressive:
+        return progressive(args)
 
     from oracle import model_ref as mr
     from puzzlenet_amd import assembly, model5_b, ops, se3
