@@ -12,25 +12,23 @@
 // A point's cell is code = 2 s1 + s2 (s = side of the plane taken, 1: distance >= 0); a piece is an ordered pair of region
 // tables (bit `code` set = the cell belongs to it: datapipe.UP, UP_UPPC, ...): rows of the first table, then rows of the second,
 // each in the cloud's point order (np.vstack, dataset.py:1239) - a two-segment stable partition written from ONE scan of the
-// packed per-thread counts.  The signed distance is the plane cut's: float64, every operation individually rounded (no fma).
+// packed per-thread counts.  The signed distance is the plane cut's: float64, every operation individually rounded (no fma);
+// it, the block sum, the padding and the start index come from pzn_cut.h.  The decision tree and the two-segment partition are
+// this file's own (the single cuts' two-way body is a different algorithm).
 //
 // Replaces, per batch: a device-to-host round trip per decision, two float64 einsums, two stable sorts of [B, M] keys per piece.
 #include "pzn_common.h"
 
 namespace {
 
-constexpr int DC_T = 1024;
-constexpr int DC_W = DC_T / PZN_WAVE;
+#include "pzn_cut.h"
+
 constexpr int DC_TRIES = 7;          // plane-2 candidates: the first draw + the re-draws of `while time <= 5` (dataset.py:1227)
 constexpr int DC_UNIFORMS = 7;       // u_seed, u_se, u_choice, u_sU, u_sD, u_sFU, u_sFD
 
 enum Kind { SINGLE = 0, HALF_VS_REST = 1, HALF_VS_OTHER = 2, HALVES = 3 };
 // region tables (datapipe.py): bit 2 s1 + s2
 constexpr int R_UP = 0xC, R_DOWN = 0x3, R_UP_UPPC = 0x8, R_UP_DOWNPC = 0x4, R_DOWN_UPPC = 0x2, R_DOWN_DOWNPC = 0x1;
-
-struct Plane {
-  double n0, n1, n2, off;
-};
 
 struct DoubleCutArgs {
   const float* raw;         // [B, M, 3]
@@ -49,41 +47,18 @@ struct DoubleCutArgs {
   uint8_t* ok;              // [B]
 };
 
-__device__ __forceinline__ bool is_up(float x, float y, float z, const Plane& p) {
-  const double d = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn((double)x, p.n0), __dmul_rn((double)y, p.n1)), __dmul_rn((double)z, p.n2)), p.off);
-  return d >= 0.0;
-}
-
-// sum of one int per thread over the workgroup, the same value returned to every thread (two barriers)
-__device__ __forceinline__ int block_sum(int v, int* slots) {
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, PZN_WAVE);
-  __syncthreads();          // (slots may still be read from the previous call)
-  if ((threadIdx.x & (PZN_WAVE - 1)) == 0) slots[threadIdx.x / PZN_WAVE] = v;
-  __syncthreads();
-  int t = 0;
-#pragma unroll
-  for (int w = 0; w < DC_W; ++w) t += slots[w];
-  return t;
-}
-
 // 0 / 1: the segment of the piece (t0, t1) a cell belongs to; 2: left out (datapipe._segments)
 __device__ __forceinline__ int segment(int code, int t0, int t1) { return ((t0 >> code) & 1) ? 0 : (((t1 >> code) & 1) ? 1 : 2); }
 
-__device__ __forceinline__ long start_index(double u, int cnt) {      // np.random.randint(0, n_piece) from a uniform draw
-  long s = (long)floor(u * (double)cnt);
-  s = s > cnt - 1 ? cnt - 1 : s;
-  return s < 0 ? 0 : s;
-}
-
-__global__ __launch_bounds__(DC_T) void cut_compact_double_kernel(DoubleCutArgs a) {
-  __shared__ int slots[DC_W];
-  __shared__ int seg_tot[2][DC_W];
-  __shared__ int seg_base[2][DC_W + 1];
+__global__ __launch_bounds__(CUT_T) void cut_compact_double_kernel(DoubleCutArgs a) {
+  __shared__ int slots[CUT_W];
+  __shared__ int seg_tot[2][CUT_W];
+  __shared__ int seg_base[2][CUT_W + 1];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (PZN_WAVE - 1), wave = tid / PZN_WAVE;
   const int M = a.M, n = a.n_min;
   const float* g = a.raw + (size_t)b * M * 3;
   // a thread owns a CONTIGUOUS run of points, so that a partition keeps the original order with one scan over threads
-  const int chunk = (M + DC_T - 1) / DC_T;
+  const int chunk = (M + CUT_T - 1) / CUT_T;
   const int lo = tid * chunk < M ? tid * chunk : M, hi = lo + chunk < M ? lo + chunk : M;
 
   auto plane1 = [&](int k) {
@@ -165,8 +140,7 @@ __global__ __launch_bounds__(DC_T) void cut_compact_double_kernel(DoubleCutArgs 
   for (int p = 0; p < 4; ++p) {
     float* dst = a.pieces + ((size_t)p * a.B + b) * a.cap * 3;
     if (p >= n_pieces) {      // no such piece: rows of the cloud's first point, count -1 (the sampling skips it)
-      const float fx = g[0], fy = g[1], fz = g[2];
-      for (int r = tid; r < a.cap; r += DC_T) dst[3 * r] = fx, dst[3 * r + 1] = fy, dst[3 * r + 2] = fz;
+      pad_piece(dst, 0, a.cap, g);
       if (tid == 0) a.counts[(size_t)p * a.B + b] = -1, a.start[(size_t)p * a.B + b] = 0;
       continue;
     }
@@ -189,11 +163,11 @@ __global__ __launch_bounds__(DC_T) void cut_compact_double_kernel(DoubleCutArgs 
     __syncthreads();
     if (tid < 2) {
       int run = 0;
-      for (int w = 0; w < DC_W; ++w) seg_base[tid][w] = run, run += seg_tot[tid][w];
-      seg_base[tid][DC_W] = run;      // total
+      for (int w = 0; w < CUT_W; ++w) seg_base[tid][w] = run, run += seg_tot[tid][w];
+      seg_base[tid][CUT_W] = run;      // total
     }
     __syncthreads();
-    const int n0 = seg_base[0][DC_W], cnt = n0 + seg_base[1][DC_W];
+    const int n0 = seg_base[0][CUT_W], cnt = n0 + seg_base[1][CUT_W];
     const long long excl = incl - packed;
     int at0 = seg_base[0][wave] + (int)(excl & 0xffffffffll);            // rows of the first region in front of this run
     int at1 = n0 + seg_base[1][wave] + (int)(excl >> 32);                // the second region follows the whole first one
@@ -205,10 +179,7 @@ __global__ __launch_bounds__(DC_T) void cut_compact_double_kernel(DoubleCutArgs 
       at0 += s == 0, at1 += s == 1;
     }
     __syncthreads();      // the piece's first row is in memory for this workgroup
-    // padding: copies of the piece's first row (of the cloud's first row when the piece is empty)
-    const float* first = cnt > 0 ? dst : g;
-    const float fx = first[0], fy = first[1], fz = first[2];
-    for (int r = (cnt < a.cap ? cnt : a.cap) + tid; r < a.cap; r += DC_T) dst[3 * r] = fx, dst[3 * r + 1] = fy, dst[3 * r + 2] = fz;
+    pad_piece(dst, cnt, a.cap, g);
     fits = fits && cnt <= a.cap;
     if (tid == 0) {
       a.counts[(size_t)p * a.B + b] = cnt;
@@ -235,6 +206,6 @@ PZN_EXPORT int pzn_cut_compact_double_f32(const float* raw, const double* normal
   PZN_CHECK_ARG(raw && normals1 && zs1 && normals2 && zs2 && u && pieces && counts && start && kind && planes && tabs && ok);
   PZN_CHECK_ARG(B > 0 && M > 0 && K > 0 && cap > 0 && n_min >= 0 && n_rich >= 0);
   DoubleCutArgs a{raw, normals1, zs1, normals2, zs2, u, B, M, K, n_min, n_rich, cap, pieces, counts, start, kind, planes, tabs, ok};
-  PZN_LAUNCH(cut_compact_double_kernel, dim3(B), dim3(DC_T), 0, pzn_hip_stream(stream), a);
+  PZN_LAUNCH(cut_compact_double_kernel, dim3(B), dim3(CUT_T), 0, pzn_hip_stream(stream), a);
   PZN_RETURN_LAUNCH_STATUS();
 }

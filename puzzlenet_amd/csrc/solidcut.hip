@@ -1,5 +1,6 @@
 // solidcut.hip — the sphere / cylinder / cone cuts of the reference's loader (dataset.py:715-759, re-draw :1175-1179) as one
-// launch per batch: the contract of cut_compact_kernel (datapipe.hip) with a solid in place of the plane.
+// launch per batch: the single-cut body of pzn_cut.h (the plane cut's, datapipe.hip) with a solid in place of the plane.  This
+// file holds the predicate, its tables and the solids' cut object.
 //
 // The reference keeps the points whose signed distance to a tessellated open3d mesh is negative, i.e. the points strictly
 // inside a CONVEX polyhedron (oracle/solids.py: a UV sphere of 50 bands x 100 sectors, a 50-gon prism, a 50-gon pyramid):
@@ -15,15 +16,14 @@
 //     bands of one hemisphere are tested against |z|.
 // That is the brute-force test over ALL faces with the equal and the implied ones left out.  Per workgroup the tables
 // (sector cosines / sines, band normals and offsets) are computed once into LDS; per candidate one thread computes the
-// rotation matrix.  A thread evaluates the predicate ONCE per point and candidate and keeps the bits of its run (<= 64 points,
-// i.e. M <= 65536; beyond that the chosen candidate is evaluated again for the scan and the write).
+// rotation matrix.  The body evaluates the predicate ONCE per point and candidate (it keeps the bits of a thread's run).
 // float64 throughout, every operation individually rounded (-ffp-contract=off), like the plane cut.
 #include "pzn_common.h"
 
 namespace {
 
-constexpr int SC_T = 1024;
-constexpr int SC_W = SC_T / PZN_WAVE;
+#include "pzn_cut.h"
+
 constexpr int SC_RES = 50;                    // resolution of the three meshes (dataset.py:717, :733, :750)
 constexpr int SC_SEC_MAX = SC_RES / 2;        // sphere: 25 of the 100 sector mid-angles lie in [0, pi/2]
 constexpr int SC_BANDS = SC_RES / 2;          // sphere: 25 latitude bands per hemisphere
@@ -32,16 +32,10 @@ constexpr double SC_PI = 3.14159265358979323846;
 enum { SOLID_SPHERE = 0, SOLID_CYLINDER = 1, SOLID_CONE = 2 };
 
 struct SolidArgs {
-  const float* raw;        // [B, M, 3]
+  CutIO io;                // pieces: the up side is the solid's inside
   const double* params;    // [B, K, 6]: rot, shift
-  const double* u;         // [B, 2]: start fractions (up, down)
-  int B, M, K, n_min, cap;
-  float* pieces;           // [2B, cap, 3]: rows 0..B-1 the up pieces (inside), rows B..2B-1 the down pieces
-  int64_t* counts;         // [2B]
-  int64_t* start;          // [2B]
   double* chosen;          // [B, 6]: rot, shift of the candidate that was taken
   int32_t* chosen_k;       // [B]: its index
-  uint8_t* ok;             // [B]: a candidate was valid (else: the most balanced candidate was taken)
 };
 
 struct Tables {
@@ -140,117 +134,27 @@ __device__ __forceinline__ bool inside(const Tables& t, const Cand& c, float fx,
   return h > 0.0 && 2.0 * m + t.half_c * h < 2.0 * t.half_c;      // of a sector has the normal (2 cos phi, 2 sin phi, cos(step/2))
 }
 
-// sum of one int per thread over the workgroup, the same value returned to every thread (two barriers)
-__device__ __forceinline__ int block_sum(int v, int* slots) {
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, PZN_WAVE);
-  __syncthreads();          // (slots may still be read from the previous call)
-  if ((threadIdx.x & (PZN_WAVE - 1)) == 0) slots[threadIdx.x / PZN_WAVE] = v;
-  __syncthreads();
-  int t = 0;
-#pragma unroll
-  for (int w = 0; w < SC_W; ++w) t += slots[w];
-  return t;
-}
+template <int KIND>
+struct SolidCut {
+  const SolidArgs& a;
+  Tables& t;
+  __device__ const double* candidate(int k) const { return a.params + ((size_t)blockIdx.x * a.io.K + k) * 6; }
+  __device__ Cand load(int k) const { return load_candidate<KIND>(t, candidate(k)); }
+  __device__ bool test(const Cand& c, float x, float y, float z) const { return inside<KIND>(t, c, x, y, z); }
+  __device__ void record(int k) const {
+    const double* pk = candidate(k);
+    for (int i = 0; i < 6; ++i) a.chosen[6 * blockIdx.x + i] = pk[i];
+    a.chosen_k[blockIdx.x] = k;
+  }
+};
 
 template <int KIND>
-__global__ __launch_bounds__(SC_T) void cut_compact_solid_kernel(SolidArgs a) {
+__global__ __launch_bounds__(CUT_T) void cut_compact_solid_kernel(SolidArgs a) {
   __shared__ Tables tab;
-  __shared__ int slots[SC_W];
-  __shared__ int wave_base[SC_W];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (PZN_WAVE - 1), wave = tid / PZN_WAVE;
-  const int M = a.M;
-  const float* g = a.raw + (size_t)b * M * 3;
-  // a thread owns a CONTIGUOUS run of points, so that the partition keeps the original order with one scan over threads
-  const int chunk = (M + SC_T - 1) / SC_T;
-  const int lo = tid * chunk < M ? tid * chunk : M, hi = lo + chunk < M ? lo + chunk : M;
-  const bool keep = chunk <= 64;      // the run's membership bits fit one register pair (uniform)
-  fill_tables<KIND>(tab);
-
-  int chosen = -1, best_k = 0, best_bal = -1;
-  uint64_t sel = 0;                   // membership of this thread's run under the candidate that is taken
-  for (int k = 0; k < a.K; ++k) {
-    const Cand cd = load_candidate<KIND>(tab, a.params + ((size_t)b * a.K + k) * 6);
-    int c = 0;
-    uint64_t bits = 0;
-    for (int j = lo; j < hi; ++j) {
-      const bool in = inside<KIND>(tab, cd, g[3 * j], g[3 * j + 1], g[3 * j + 2]);
-      c += in ? 1 : 0;
-      bits |= (uint64_t)(in ? 1 : 0) << ((j - lo) & 63);
-    }
-    const int up = block_sum(c, slots);
-    const int bal = up < M - up ? up : M - up;
-    const bool valid = up >= a.n_min && M - up >= a.n_min;      // (uniform: every thread holds the same sum)
-    if (bal > best_bal || valid) sel = bits;
-    if (bal > best_bal) best_bal = bal, best_k = k;
-    if (valid) {
-      chosen = k;
-      break;
-    }
-  }
-  const bool valid = chosen >= 0;
-  if (!valid) chosen = best_k;
-  const double* pk = a.params + ((size_t)b * a.K + chosen) * 6;
-  Cand cd = {};
-  if (!keep) cd = load_candidate<KIND>(tab, pk);
-  auto member = [&](int j) -> bool {
-    return keep ? ((sel >> (j - lo)) & 1) != 0 : inside<KIND>(tab, cd, g[3 * j], g[3 * j + 1], g[3 * j + 2]);
-  };
-
-  // stable partition: exclusive scan of the per-thread up counts over the workgroup
-  int c = 0;
-  if (keep) c = __popcll(sel);
-  else
-    for (int j = lo; j < hi; ++j) c += member(j) ? 1 : 0;
-  int incl = c;
-  for (int d = 1; d < PZN_WAVE; d <<= 1) {
-    const int o = __shfl_up(incl, d, PZN_WAVE);
-    if (lane >= d) incl += o;
-  }
-  __syncthreads();
-  if (lane == PZN_WAVE - 1) slots[wave] = incl;
-  __syncthreads();
-  if (tid == 0) {
-    int run = 0;
-    for (int w = 0; w < SC_W; ++w) wave_base[w] = run, run += slots[w];
-    slots[0] = run;      // total
-  }
-  __syncthreads();
-  const int n_up = slots[0], n_down = M - n_up;
-  int up_at = wave_base[wave] + incl - c;      // ups in front of this thread's run
-  int down_at = lo - up_at;                    // downs in front of it
-  float* pu = a.pieces + (size_t)b * a.cap * 3;
-  float* pd = a.pieces + (size_t)(a.B + b) * a.cap * 3;
-  for (int j = lo; j < hi; ++j) {
-    const float x = g[3 * j], y = g[3 * j + 1], z = g[3 * j + 2];
-    const bool up = member(j);
-    const int at = up ? up_at : down_at;
-    float* dst = (up ? pu : pd) + (size_t)at * 3;
-    if (at < a.cap) dst[0] = x, dst[1] = y, dst[2] = z;
-    up_at += up ? 1 : 0;
-    down_at += up ? 0 : 1;
-  }
-  __syncthreads();      // the pieces' first rows are in memory for this workgroup
-  // padding: copies of the piece's first row (of the cloud's first row when the piece is empty)
-  for (int half = 0; half < 2; ++half) {
-    float* p = half ? pd : pu;
-    const int cnt = half ? n_down : n_up;
-    const float* first = cnt > 0 ? p : g;
-    const float fx = first[0], fy = first[1], fz = first[2];
-    for (int r = (cnt < a.cap ? cnt : a.cap) + tid; r < a.cap; r += SC_T) p[3 * r] = fx, p[3 * r + 1] = fy, p[3 * r + 2] = fz;
-  }
-  if (tid == 0) {
-    a.counts[b] = n_up;
-    a.counts[a.B + b] = n_down;
-    for (int half = 0; half < 2; ++half) {
-      const int cnt = half ? n_down : n_up;
-      long s = (long)floor(a.u[2 * b + half] * (double)cnt);      // np.random.randint(0, n_piece) from a uniform draw
-      s = s < 0 ? 0 : (s > cnt - 1 ? cnt - 1 : s);
-      a.start[half * a.B + b] = s < 0 ? 0 : s;
-    }
-    for (int i = 0; i < 6; ++i) a.chosen[6 * b + i] = pk[i];
-    a.chosen_k[b] = chosen;
-    a.ok[b] = (valid && n_up <= a.cap && n_down <= a.cap) ? 1 : 0;
-  }
+  __shared__ int slots[CUT_W];
+  __shared__ int wave_base[CUT_W];
+  fill_tables<KIND>(tab);      // (published by the barriers of the first load)
+  cut_compact_body(a.io, SolidCut<KIND>{a, tab}, slots, wave_base);
 }
 
 }  // namespace
@@ -261,10 +165,10 @@ PZN_EXPORT int pzn_cut_compact_solid_f32(const float* raw, int kind, const doubl
   PZN_CHECK_ARG(raw && params && u && pieces && counts && start && chosen && chosen_k && ok);
   PZN_CHECK_ARG(B > 0 && M > 0 && K > 0 && cap > 0 && n_min >= 0);
   PZN_CHECK_ARG(kind == SOLID_SPHERE || kind == SOLID_CYLINDER || kind == SOLID_CONE);
-  SolidArgs a{raw, params, u, B, M, K, n_min, cap, pieces, counts, start, chosen, chosen_k, ok};
+  SolidArgs a{{raw, u, B, M, K, n_min, cap, pieces, counts, start, ok}, params, chosen, chosen_k};
   hipStream_t st = pzn_hip_stream(stream);
-  if (kind == SOLID_SPHERE) PZN_LAUNCH(cut_compact_solid_kernel<SOLID_SPHERE>, dim3(B), dim3(SC_T), 0, st, a);
-  else if (kind == SOLID_CYLINDER) PZN_LAUNCH(cut_compact_solid_kernel<SOLID_CYLINDER>, dim3(B), dim3(SC_T), 0, st, a);
-  else PZN_LAUNCH(cut_compact_solid_kernel<SOLID_CONE>, dim3(B), dim3(SC_T), 0, st, a);
+  if (kind == SOLID_SPHERE) PZN_LAUNCH(cut_compact_solid_kernel<SOLID_SPHERE>, dim3(B), dim3(CUT_T), 0, st, a);
+  else if (kind == SOLID_CYLINDER) PZN_LAUNCH(cut_compact_solid_kernel<SOLID_CYLINDER>, dim3(B), dim3(CUT_T), 0, st, a);
+  else PZN_LAUNCH(cut_compact_solid_kernel<SOLID_CONE>, dim3(B), dim3(CUT_T), 0, st, a);
   PZN_RETURN_LAUNCH_STATUS();
 }

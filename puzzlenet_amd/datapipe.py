@@ -26,7 +26,7 @@ point.  Parity is pinned to that restatement, not to the library itself (no fixt
 
 For a loader that runs BESIDE the training step there is `PairFeeder`: a fresh batch per step on a background stream, cut by
 a plane (`cut_pairs`: csrc/datapipe.hip) or by one of the three solids (`PairFeeder(..., cut="sphere" | "cylinder" | "cone")`
--> `cut_pairs_solid`: csrc/solidcut.hip).  Either cut is ONE launch per batch: K candidate draws per sample (`solid_draws`
+-> `cut_pairs_solid`: csrc/solidcut.hip; both kernels are the one body of csrc/pzn_cut.h).  Either cut is ONE launch per batch: K candidate draws per sample (`solid_draws`
 for the solids), the first that leaves >= n points in both pieces taken on the device (the reference's re-draw loop,
 dataset.py:1175-1180), both pieces compacted in point order and padded, the FPS start indices.  The solid kernel tests the
 same polyhedra as `solid_cut_mask`, face plane by face plane with the rotation families folded (no atan2 / acos per point);
@@ -34,6 +34,8 @@ tests/test_gpu_solid_feeder.py holds its pieces to the oracle's masks bit for bi
 `PairFeeder(..., split_twice=True)` is the reference's second sampling mode (`train.py --random_slice`, dataset.py:1203-1355):
 the double cuts, decided and compacted on the device in one launch (`double_cut_rule` states the rule, csrc/doublecut.hip runs
 it, `cut_pairs_double` samples the pair and its fallback and applies the reference's acceptance test without a host round trip).
+The three modes share one `next_batch` (staging turn, pinned upload, events) and one tail from the compacted pieces to the
+8-tuple (`_sample`, `_picks`, `_finish`); a mode is a staging layout, a host draw function and a builder.
 """
 import collections
 
@@ -181,8 +183,12 @@ def solid_cut_mask(raw, kind, rot=None, shift=None, exact_solid=False):
     raise _lib.PznError(f"solid_cut_mask: unknown solid {kind!r}")
 
 
-def make_pairs_mask(raw, mask, start_up, start_down, twist, n=1024, k=128, cap=None):
-    """The pair construction of make_pairs from a given up-mask [B,M] (whatever cut produced it)."""
+def make_pairs_mask(raw, mask, start_up, start_down, twist, n=1024, k=128, cap=None, background=False):
+    """The pair construction from a given up-mask [B,M] (whatever cut produced it): raw [B,M,3] fp32 on the GPU + the draws ->
+    the 8-tuple (down, moved_up, igt, up, down_boundary, up_boundary, down_mask, up_mask) and `ok` [B] (both pieces of the cut
+    hold >= n points: the reference re-draws the cut otherwise, dataset.py:1176-1180 - the caller re-draws for the rows where
+    ok is False).  background=True: the sampling as the small-footprint launch that skips the padding (for a side stream
+    beside a training step: PairFeeder)."""
     if not raw.is_cuda:
         raise _lib.PznError("datapipe.make_pairs_mask runs on the GPU (puzzlenet_amd has no CPU fallback)")
     raw = raw.to(torch.float32).contiguous()
@@ -190,9 +196,10 @@ def make_pairs_mask(raw, mask, start_up, start_down, twist, n=1024, k=128, cap=N
     cap = M if cap is None else int(cap)
     up_piece, n_up = _compact(raw, mask, cap)
     down_piece, n_down = _compact(raw, ~mask, cap)
-    ok = (n_up >= n) & (n_down >= n) & (n_up <= cap) & (n_down <= cap)
+    ok = (n_up >= n) & (n_down >= n) & (n_up <= cap) & (n_down <= cap)      # (a piece larger than `cap` would be truncated)
+    # one FPS launch for both pieces of every sample (a workgroup per piece: 2B workgroups instead of 2 x B)
     both = fps_to_n(torch.cat([up_piece, down_piece], 0), torch.cat([n_up, n_down], 0),
-                    torch.cat([start_up.reshape(-1), start_down.reshape(-1)], 0), n)
+                    torch.cat([start_up.reshape(-1), start_down.reshape(-1)], 0), n, background=background)
     up, down = both[:B].contiguous(), both[B:].contiguous()
     downb, upb, down_mask, up_mask = boundary(down, up, k)
     moved, igt = move(up, twist)
@@ -248,26 +255,53 @@ def move(up, twist):
 
 
 def make_pairs(raw, normal, z, start_up, start_down, twist, n=1024, k=128, cap=None, background=False):
-    """raw [B,M,3] fp32 on the GPU + the draws -> the 8-tuple (down, moved_up, igt, up, down_boundary, up_boundary,
-    down_mask, up_mask) and `ok` [B] (both pieces of the cut hold >= n points: the reference re-draws the cut
-    otherwise, dataset.py:1176-1180 — the caller re-draws for the rows where ok is False).  background=True: the sampling as
-    the small-footprint launch that skips the padding (for a side stream beside a training step: PairFeeder)."""
+    """make_pairs_mask for the plane cut of dataset.py:761-775: normal [B,3], z [B] float64 draws."""
     if not raw.is_cuda:
         raise _lib.PznError("datapipe.make_pairs runs on the GPU (puzzlenet_amd has no CPU fallback)")
     raw = raw.to(torch.float32).contiguous()
-    B, M, _ = raw.shape
-    cap = M if cap is None else int(cap)
-    mask = plane_cut_mask(raw, normal, z)
-    up_piece, n_up = _compact(raw, mask, cap)
-    down_piece, n_down = _compact(raw, ~mask, cap)
-    ok = (n_up >= n) & (n_down >= n) & (n_up <= cap) & (n_down <= cap)      # (a piece larger than `cap` would be truncated)
-    # one FPS launch for both pieces of every sample (a workgroup per piece: 2B workgroups instead of 2 x B)
-    both = fps_to_n(torch.cat([up_piece, down_piece], 0), torch.cat([n_up, n_down], 0),
-                    torch.cat([start_up.reshape(-1), start_down.reshape(-1)], 0), n, background=background)
-    up, down = both[:B].contiguous(), both[B:].contiguous()
-    downb, upb, down_mask, up_mask = boundary(down, up, k)
-    moved, igt = move(up, twist)
-    return (down, moved, igt, up, downb, upb, down_mask, up_mask), ok
+    return make_pairs_mask(raw, plane_cut_mask(raw, normal, z), start_up, start_down, twist, n, k, cap, background)
+
+
+def _feeder_cap(who, raw, cap):
+    """The guard of the cut_pairs* forms: -> rows a piece may hold."""
+    if not raw.is_cuda:
+        raise _lib.PznError(f"datapipe.{who} runs on the GPU (puzzlenet_amd has no CPU fallback)")
+    cap = raw.shape[1] if cap is None else int(cap)
+    if cap > 32768:
+        raise _lib.PznUnsupported(f"{who}: pieces of up to {cap} points (the FPS kernel holds <= 32768)")
+    return cap
+
+
+# The tail of a feeder batch, from the compacted pieces of a cut to the 8-tuple, in three stages on [2B, ...] stacks (up rows,
+# then down rows).  A valid cut leaves >= n points on either side, so a piece holds <= M - n (the promise made to the
+# small-footprint FPS); rows of samples without a valid cut are re-drawn by the caller.
+def _sample(pieces, counts, start, n, M):                                                        # dataset.py:1147-1163
+    idx = ops.farthest_point_sample(pieces, n, start, background=True, counts=counts, max_count=max(M - n, n))
+    return ops.index_points(pieces, idx)
+
+
+def _picks(both, k):                                                                             # dataset.py:1357-1367
+    B = both.shape[0] // 2
+    cd_over_up, cd_over_down = ops.chamfer(both[B:], both[:B])
+    top = ops.topk_rows(torch.cat([cd_over_up, cd_over_down], 0).neg_(), k)                      # [2B,k]: up picks, down picks
+    return top, ops.index_points(both, top)
+
+
+def _finish(both, top, bnd, twist):
+    B, n = both.shape[0] // 2, both.shape[1]
+    masks = ops.pick_mask(top, n)
+    g = se3.exp(twist.to(torch.float32))                                                         # transforms.py:176-186
+    up, down = both[:B], both[B:]
+    moved = se3.transform_points(g, up)
+    return down, moved, g, up, bnd[B:], bnd[:B], masks[B:], masks[:B]
+
+
+def _pair_tail(pieces, counts, start, ok, twist, n, k, M):
+    """pieces [2B,cap,3], counts / start [2B], ok [B] of a single cut -> (the 8-tuple, ok [B] with the piece sizes held to n)"""
+    B = ok.shape[0]
+    both = _sample(pieces, counts, start, n, M)
+    top, bnd = _picks(both, k)
+    return _finish(both, top, bnd, twist), ok & (counts[:B] >= n) & (counts[B:] >= n)
 
 
 def cut_pairs(raw, normals, zs, u, twist, n=1024, k=128, cap=None):
@@ -276,24 +310,9 @@ def cut_pairs(raw, normals, zs, u, twist, n=1024, k=128, cap=None):
     (csrc/datapipe.hip, ops.cut_compact); sampling by the small-footprint FPS that skips the padding; boundary picks by
     ops.topk_rows; masks by one launch.  raw [B,M,3]; normals [B,K,3], zs [B,K], u [B,2] float64 draws; twist [B,6].
     -> ((down, moved_up, igt, up, down_boundary, up_boundary, down_mask, up_mask), ok [B], plane [B,4])"""
-    if not raw.is_cuda:
-        raise _lib.PznError("datapipe.cut_pairs runs on the GPU (puzzlenet_amd has no CPU fallback)")
-    B, M, _ = raw.shape
-    cap = M if cap is None else int(cap)
-    if cap > 32768:
-        raise _lib.PznUnsupported(f"cut_pairs: pieces of up to {cap} points (the FPS kernel holds <= 32768)")
+    cap = _feeder_cap("cut_pairs", raw, cap)
     pieces, counts, start, plane, ok = ops.cut_compact(raw, normals, zs, u, n, cap)
-    # (a valid cut leaves >= n points on either side, so a piece holds <= M - n; rows of samples without a valid cut are re-drawn)
-    idx = ops.farthest_point_sample(pieces, n, start, background=True, counts=counts, max_count=max(M - n, n))      # dataset.py:1147-1163
-    both = ops.index_points(pieces, idx)
-    up, down = both[:B], both[B:]
-    cd_over_up, cd_over_down = ops.chamfer(down, up)                                             # dataset.py:1357-1367
-    top = ops.topk_rows(torch.cat([cd_over_up, cd_over_down], 0).neg_(), k)                      # [2B,k]: up picks, down picks
-    bnd = ops.index_points(both, top)
-    masks = ops.pick_mask(top, n)
-    g = se3.exp(twist.to(torch.float32))                                                         # transforms.py:176-186
-    moved = se3.transform_points(g, up)
-    return (down, moved, g, up, bnd[B:], bnd[:B], masks[B:], masks[:B]), ok & (counts[:B] >= n) & (counts[B:] >= n), plane
+    return _pair_tail(pieces, counts, start, ok, twist, n, k, raw.shape[1]) + (plane,)
 
 
 def solid_draws(rng, B, K):
@@ -310,24 +329,9 @@ def cut_pairs_solid(raw, kind, params, u, twist, n=1024, k=128, cap=None):
     one launch (csrc/solidcut.hip, ops.cut_compact_solid); the rest is cut_pairs' tail.  raw [B,M,3]; kind "sphere" |
     "cylinder" | "cone"; params [B,K,6] (rot, shift: solid_draws), u [B,2] float64 draws; twist [B,6].
     -> ((down, moved_up, igt, up, down_boundary, up_boundary, down_mask, up_mask), ok [B], chosen [B,6])"""
-    if not raw.is_cuda:
-        raise _lib.PznError("datapipe.cut_pairs_solid runs on the GPU (puzzlenet_amd has no CPU fallback)")
-    B, M, _ = raw.shape
-    cap = M if cap is None else int(cap)
-    if cap > 32768:
-        raise _lib.PznUnsupported(f"cut_pairs_solid: pieces of up to {cap} points (the FPS kernel holds <= 32768)")
+    cap = _feeder_cap("cut_pairs_solid", raw, cap)
     pieces, counts, start, chosen, _, ok = ops.cut_compact_solid(raw, kind, params, u, n, cap)
-    # (a valid cut leaves >= n points on either side, so a piece holds <= M - n; rows of samples without a valid cut are re-drawn)
-    idx = ops.farthest_point_sample(pieces, n, start, background=True, counts=counts, max_count=max(M - n, n))      # dataset.py:1147-1163
-    both = ops.index_points(pieces, idx)
-    up, down = both[:B], both[B:]
-    cd_over_up, cd_over_down = ops.chamfer(down, up)                                             # dataset.py:1357-1367
-    top = ops.topk_rows(torch.cat([cd_over_up, cd_over_down], 0).neg_(), k)                      # [2B,k]: up picks, down picks
-    bnd = ops.index_points(both, top)
-    masks = ops.pick_mask(top, n)
-    g = se3.exp(twist.to(torch.float32))                                                         # transforms.py:176-186
-    moved = se3.transform_points(g, up)
-    return (down, moved, g, up, bnd[B:], bnd[:B], masks[B:], masks[:B]), ok & (counts[:B] >= n) & (counts[B:] >= n), chosen
+    return _pair_tail(pieces, counts, start, ok, twist, n, k, raw.shape[1]) + (chosen,)
 
 
 DoubleCut = collections.namedtuple("DoubleCut", "kind planes tabs rejected cd U D Ub Db")
@@ -346,38 +350,102 @@ def cut_pairs_double(raw, normals1, zs1, normals2, zs2, u, twist, n=1024, n_rich
     final pair.  Nothing here reads a value back to the host.  raw [B,M,3]; normals1 [B,K,3], zs1 [B,K], normals2 [B,7,3],
     zs2 [B,7], u [B,7] float64 draws; twist [B,6]; n_rich: None = 3000 n / 1024.
     -> ((D, moved U, igt, U, D boundary, U boundary, D mask, U mask), ok [B], DoubleCut)"""
-    if not raw.is_cuda:
-        raise _lib.PznError("datapipe.cut_pairs_double runs on the GPU (puzzlenet_amd has no CPU fallback)")
+    cap = _feeder_cap("cut_pairs_double", raw, cap)
     B, M, _ = raw.shape
-    cap = M if cap is None else int(cap)
-    if cap > 32768:
-        raise _lib.PznUnsupported(f"cut_pairs_double: pieces of up to {cap} points (the FPS kernel holds <= 32768)")
     n_rich = 3000 * n // 1024 if n_rich is None else int(n_rich)
     pieces, counts, start, kind, planes, tabs, ok = ops.cut_compact_double(raw, normals1, zs1, normals2, zs2, u, n, n_rich, cap)
-    # (U holds >= n points, so D holds <= M - n; the fallback is a valid single cut; rows of samples without a valid cut are re-drawn)
-    def sample(part):                                                                            # dataset.py:1147-1163
-        idx = ops.farthest_point_sample(pieces[part], n, start[part], background=True, counts=counts[part], max_count=max(M - n, n))
-        return ops.index_points(pieces[part], idx)
-
-    primary, fallback = sample(slice(0, 2 * B)), sample(slice(2 * B, 4 * B))                     # [2B,n,3] each: U rows, D rows
-
-    def picks(both):                                                                             # dataset.py:1357-1367
-        cd_over_u, cd_over_d = ops.chamfer(both[B:], both[:B])
-        top = ops.topk_rows(torch.cat([cd_over_u, cd_over_d], 0).neg_(), k)                      # [2B,k]: U picks, D picks
-        return top, ops.index_points(both, top)
-
-    _, bnd = picks(primary)
+    # [2B,n,3] each: U rows, D rows (U holds >= n points, so D holds <= M - n; the fallback is a valid single cut)
+    primary = _sample(pieces[:2 * B], counts[:2 * B], start[:2 * B], n, M)
+    fallback = _sample(pieces[2 * B:], counts[2 * B:], start[2 * B:], n, M)
+    _, bnd = _picks(primary, k)
     cd1, cd2 = ops.chamfer(bnd[B:], bnd[:B])                                                     # :1253-1254
     cd = cd1.mean(1) + cd2.mean(1)
     rejected = double_cut_rejects(kind, cd)
     both = torch.where(rejected.repeat(2).view(2 * B, 1, 1), fallback, primary)
-    top, fbnd = picks(both)
-    masks = ops.pick_mask(top, n)
-    g = se3.exp(twist.to(torch.float32))                                                         # transforms.py:176-186
-    U, D = both[:B], both[B:]
-    moved = se3.transform_points(g, U)
+    top, fbnd = _picks(both, k)
     record = DoubleCut(kind, planes, tabs, rejected, cd, primary[:B], primary[B:], bnd[:B], bnd[B:])
-    return (D, moved, g, U, fbnd[B:], fbnd[:B], masks[B:], masks[:B]), ok & (counts[:B] >= n) & (counts[B:2 * B] >= n), record
+    return _finish(both, top, fbnd, twist), ok & (counts[:B] >= n) & (counts[B:2 * B] >= n), record
+
+
+def _cols(*widths):
+    """Column slices of a staging row that holds blocks of these widths side by side."""
+    c = np.cumsum((0,) + widths)
+    return [slice(int(lo), int(hi)) for lo, hi in zip(c[:-1], c[1:])]
+
+
+def _plane_cols(K):             # normals, offsets, start fractions, twist
+    return _cols(3 * K, K, 2, 6)
+
+
+def _solid_cols(K):             # (rot, shift) candidates, start fractions, twist
+    return _cols(6 * K, 2, 6)
+
+
+def _double_cols(K):            # plane 1: normals, offsets; plane 2: normals, offsets; uniforms; twist
+    return _cols(3 * K, K, 3 * ops.DOUBLE_CUT_TRIES, ops.DOUBLE_CUT_TRIES, ops.DOUBLE_CUT_UNIFORMS, 6)
+
+
+def _draw_twist(gen, mag, out):                                                 # transforms.py:163-168
+    x = torch.randn(out.shape[0], 6, generator=gen, dtype=torch.float64)
+    out[:] = (x / x.norm(p=2, dim=1, keepdim=True) * mag).numpy()
+
+
+# The host draws of one feeder batch, per mode: (rng: np.random.RandomState, gen: torch.Generator, B, K candidates, mag, out:
+# the [B, width] float64 staging row as a numpy array).  No GPU is needed.  The calls made on rng and gen, their shapes and
+# their order are what a seed MEANS (tests/test_datapipe_cpu.py restates them).
+def draw_plane_batch(rng, gen, B, K, mag, out):
+    normals, zs, u, tw = _plane_cols(K)
+    out[:, normals] = rng.rand(B, 3 * K)                                        # plane normals, dataset.py:767
+    out[:, zs] = rng.rand(B, K) / 3                                             # plane offsets, :769
+    out[:, u] = rng.rand(B, 2)                                                  # FPS start points as fractions of the piece sizes, :1153
+    _draw_twist(gen, mag, out[:, tw])
+
+
+def draw_solid_batch(rng, gen, B, K, mag, out):
+    params, u, tw = _solid_cols(K)
+    out[:, params] = solid_draws(rng, B, K).reshape(B, 6 * K)                   # dataset.py:718, 732-733, 749
+    out[:, u] = rng.rand(B, 2)                                                  # FPS start points as fractions of the piece sizes, :1153
+    _draw_twist(gen, mag, out[:, tw])
+
+
+def draw_double_batch(rng, gen, B, K, mag, out):
+    normals1, zs1, normals2, zs2, u, tw = _double_cols(K)
+    T = ops.DOUBLE_CUT_TRIES
+    out[:, normals1] = rng.rand(B, 3 * K)                                       # plane 1: normals, dataset.py:767
+    out[:, zs1] = rng.rand(B, K) / 3                                            # plane 1: offsets, :769
+    out[:, normals2] = rng.rand(B, 3 * T)                                       # plane 2: the draw of :1226 / :1296 and its six re-draws
+    out[:, zs2] = rng.rand(B, T) / 3
+    out[:, u] = rng.rand(B, ops.DOUBLE_CUT_UNIFORMS)                            # u_seed, u_se, u_choice, u_sU, u_sD, u_sFU, u_sFD
+    _draw_twist(gen, mag, out[:, tw])
+
+
+# The builders: the uploaded staging row d [B, width] -> (the 8-tuple, ok, the PairBatch fields that say what was cut)
+def _build_plane(f, d):
+    B, K = d.shape[0], f.K
+    normals, zs, u, tw = _plane_cols(K)
+    tensors, ok, plane = cut_pairs(f.raw, d[:, normals].reshape(B, K, 3), d[:, zs], d[:, u], d[:, tw], n=f.n, k=f.k)
+    return tensors, ok, dict(plane=(plane[:, :3], plane[:, 3]))
+
+
+def _build_solid(f, d):
+    B, K = d.shape[0], f.K
+    params, u, tw = _solid_cols(K)
+    tensors, ok, chosen = cut_pairs_solid(f.raw, f.cut, d[:, params].reshape(B, K, 6), d[:, u], d[:, tw], n=f.n, k=f.k)
+    return tensors, ok, dict(cut=(f.cut, chosen[:, :3], chosen[:, 3:]))
+
+
+def _build_double(f, d):
+    B, K, T = d.shape[0], f.K, ops.DOUBLE_CUT_TRIES
+    normals1, zs1, normals2, zs2, u, tw = _double_cols(K)
+    tensors, ok, record = cut_pairs_double(f.raw, d[:, normals1].reshape(B, K, 3), d[:, zs1], d[:, normals2].reshape(B, T, 3),
+                                           d[:, zs2], d[:, u], d[:, tw], n=f.n, k=f.k)
+    return tensors, ok, dict(double=record, plane=(record.planes[:, 0, :3], record.planes[:, 0, 3]))
+
+
+_FeederMode = collections.namedtuple("_FeederMode", "cols draw build")
+_PLANE_MODE = _FeederMode(_plane_cols, draw_plane_batch, _build_plane)
+_SOLID_MODE = _FeederMode(_solid_cols, draw_solid_batch, _build_solid)
+_DOUBLE_MODE = _FeederMode(_double_cols, draw_double_batch, _build_double)
 
 
 class PairBatch(list):
@@ -419,97 +487,31 @@ class PairFeeder:
         self.gen = torch.Generator().manual_seed(seed)
         self.stream = torch.cuda.Stream(device=self.device)
         B = self.raw.shape[0]
+        self._mode = _DOUBLE_MODE if self.split_twice else (_PLANE_MODE if cut == "plane" else _SOLID_MODE)
         # one pinned staging block per batch in flight (two: the upload of batch k + 1 may still be queued when k + 2 is drawn)
-        self._width = self.K * 3 + self.K + 2 + 6 if cut == "plane" else self.K * 6 + 2 + 6
-        if self.split_twice:      # K + 7 planes, 7 uniforms, the twist
-            self._width = (self.K + ops.DOUBLE_CUT_TRIES) * 4 + ops.DOUBLE_CUT_UNIFORMS + 6
+        self._width = self._mode.cols(self.K)[-1].stop
         self._stage = [torch.empty((B, self._width), dtype=torch.float64, pin_memory=True) for _ in range(3)]
         self._turn = 0
         self._busy = [None] * 3
 
     def next_batch(self):
-        if self.cut != "plane":
-            return self._next_batch_solid()
-        if self.split_twice:
-            return self._next_batch_double()
-        B, K, n = self.raw.shape[0], self.K, self.n
         st = self._stage[self._turn]
         if self._busy[self._turn] is not None:
             self._busy[self._turn].synchronize()          # (three batches back: long done)
-        h = st.numpy()
-        h[:, :3 * K] = self.rng.rand(B, 3 * K)                                  # plane normals, dataset.py:767
-        h[:, 3 * K:4 * K] = self.rng.rand(B, K) / 3                             # plane offsets, :769
-        h[:, 4 * K:4 * K + 2] = self.rng.rand(B, 2)                             # FPS start points as fractions of the piece sizes, :1153
-        x = torch.randn(B, 6, generator=self.gen, dtype=torch.float64)          # transforms.py:163-168
-        h[:, 4 * K + 2:] = (x / x.norm(p=2, dim=1, keepdim=True) * self.mag).numpy()
+        self._mode.draw(self.rng, self.gen, self.raw.shape[0], self.K, self.mag, st.numpy())
         with torch.cuda.stream(self.stream):
             d = st.to(self.device, non_blocking=True)
             up_ev = torch.cuda.Event()
             up_ev.record(self.stream)
             self._busy[self._turn] = up_ev
-            tensors, ok, plane = cut_pairs(self.raw, d[:, :3 * K].reshape(B, K, 3), d[:, 3 * K:4 * K], d[:, 4 * K:4 * K + 2],
-                                           d[:, 4 * K + 2:], n=n, k=self.k)
+            tensors, ok, what = self._mode.build(self, d)
             ready = torch.cuda.Event()
             ready.record(self.stream)
         self._turn = (self._turn + 1) % 3
         out = PairBatch(tensors)
-        out.ready, out.ok, out.plane = ready, ok, (plane[:, :3], plane[:, 3])
-        return out
-
-    def _next_batch_solid(self):
-        """next_batch() for cut = a solid: the same protocol, K (rot, shift) candidates in place of the K planes."""
-        B, K, n = self.raw.shape[0], self.K, self.n
-        st = self._stage[self._turn]
-        if self._busy[self._turn] is not None:
-            self._busy[self._turn].synchronize()          # (three batches back: long done)
-        h = st.numpy()
-        h[:, :6 * K] = solid_draws(self.rng, B, K).reshape(B, 6 * K)            # dataset.py:718, 732-733, 749
-        h[:, 6 * K:6 * K + 2] = self.rng.rand(B, 2)                             # FPS start points as fractions of the piece sizes, :1153
-        x = torch.randn(B, 6, generator=self.gen, dtype=torch.float64)          # transforms.py:163-168
-        h[:, 6 * K + 2:] = (x / x.norm(p=2, dim=1, keepdim=True) * self.mag).numpy()
-        with torch.cuda.stream(self.stream):
-            d = st.to(self.device, non_blocking=True)
-            up_ev = torch.cuda.Event()
-            up_ev.record(self.stream)
-            self._busy[self._turn] = up_ev
-            tensors, ok, chosen = cut_pairs_solid(self.raw, self.cut, d[:, :6 * K].reshape(B, K, 6), d[:, 6 * K:6 * K + 2],
-                                                  d[:, 6 * K + 2:], n=n, k=self.k)
-            ready = torch.cuda.Event()
-            ready.record(self.stream)
-        self._turn = (self._turn + 1) % 3
-        out = PairBatch(tensors)
-        out.ready, out.ok, out.cut = ready, ok, (self.cut, chosen[:, :3], chosen[:, 3:])
-        return out
-
-    def _next_batch_double(self):
-        """next_batch() for split_twice=True: the same protocol, the draws of double_cut_rule in place of the K planes."""
-        B, K, n, T, Q = self.raw.shape[0], self.K, self.n, ops.DOUBLE_CUT_TRIES, ops.DOUBLE_CUT_UNIFORMS
-        st = self._stage[self._turn]
-        if self._busy[self._turn] is not None:
-            self._busy[self._turn].synchronize()          # (three batches back: long done)
-        h = st.numpy()
-        c = np.cumsum([0, 3 * K, K, 3 * T, T, Q, 6])
-        h[:, c[0]:c[1]] = self.rng.rand(B, 3 * K)                               # plane 1: normals, dataset.py:767
-        h[:, c[1]:c[2]] = self.rng.rand(B, K) / 3                               # plane 1: offsets, :769
-        h[:, c[2]:c[3]] = self.rng.rand(B, 3 * T)                               # plane 2: the draw of :1226 / :1296 and its six re-draws
-        h[:, c[3]:c[4]] = self.rng.rand(B, T) / 3
-        h[:, c[4]:c[5]] = self.rng.rand(B, Q)                                   # u_seed, u_se, u_choice, u_sU, u_sD, u_sFU, u_sFD
-        x = torch.randn(B, 6, generator=self.gen, dtype=torch.float64)          # transforms.py:163-168
-        h[:, c[5]:] = (x / x.norm(p=2, dim=1, keepdim=True) * self.mag).numpy()
-        with torch.cuda.stream(self.stream):
-            d = st.to(self.device, non_blocking=True)
-            up_ev = torch.cuda.Event()
-            up_ev.record(self.stream)
-            self._busy[self._turn] = up_ev
-            tensors, ok, record = cut_pairs_double(self.raw, d[:, c[0]:c[1]].reshape(B, K, 3), d[:, c[1]:c[2]],
-                                                   d[:, c[2]:c[3]].reshape(B, T, 3), d[:, c[3]:c[4]], d[:, c[4]:c[5]], d[:, c[5]:],
-                                                   n=n, k=self.k)
-            ready = torch.cuda.Event()
-            ready.record(self.stream)
-        self._turn = (self._turn + 1) % 3
-        out = PairBatch(tensors)
-        out.ready, out.ok, out.double = ready, ok, record
-        out.plane = (record.planes[:, 0, :3], record.planes[:, 0, 3])
+        out.ready, out.ok = ready, ok
+        for field, value in what.items():
+            setattr(out, field, value)
         return out
 
     def close(self):

@@ -449,6 +449,13 @@ def topk_rows(x, k):
     return idx
 
 
+def _cut_outputs(raw, P, cap):
+    """What every cut launch writes for P pieces per sample: pieces [P B,cap,3] f32, counts [P B] and start [P B] int64, ok [B] uint8."""
+    B, dev = raw.shape[0], raw.device
+    return (torch.empty((P * B, int(cap), 3), dtype=torch.float32, device=dev), torch.empty((P * B,), dtype=torch.int64, device=dev),
+            torch.empty((P * B,), dtype=torch.int64, device=dev), torch.empty((B,), dtype=torch.uint8, device=dev))
+
+
 def cut_compact(raw, normals, zs, u, n_min, cap):
     """dataset.py:761-775 + 1176-1180 for a batch in one launch (pzn_cut_compact_f32): raw [B,M,3] f32, K candidate planes per
     sample (normals [B,K,3], zs [B,K], float64), start fractions u [B,2] float64
@@ -458,11 +465,8 @@ def cut_compact(raw, normals, zs, u, n_min, cap):
     B, M, _ = raw.shape
     K = normals.shape[1]
     dev = raw.device
-    pieces = torch.empty((2 * B, int(cap), 3), dtype=torch.float32, device=dev)
-    counts = torch.empty((2 * B,), dtype=torch.int64, device=dev)
-    start = torch.empty((2 * B,), dtype=torch.int64, device=dev)
+    pieces, counts, start, ok = _cut_outputs(raw, 2, cap)
     plane = torch.empty((B, 4), dtype=torch.float64, device=dev)
-    ok = torch.empty((B,), dtype=torch.uint8, device=dev)
     with _on(dev):
         _call("pzn_cut_compact_f32", _p(raw), _p(normals), _p(zs), _p(u), B, M, K, int(n_min), int(cap), _p(pieces), _p(counts),
               _p(start), _p(plane), _p(ok), _stream())
@@ -486,12 +490,9 @@ def cut_compact_solid(raw, kind, params, u, n_min, cap):
         raise _lib.PznError("cut_compact_solid: params as [B, K, 6] and u as [B, 2]")
     K = params.shape[1]
     dev = raw.device
-    pieces = torch.empty((2 * B, int(cap), 3), dtype=torch.float32, device=dev)
-    counts = torch.empty((2 * B,), dtype=torch.int64, device=dev)
-    start = torch.empty((2 * B,), dtype=torch.int64, device=dev)
+    pieces, counts, start, ok = _cut_outputs(raw, 2, cap)
     chosen = torch.empty((B, 6), dtype=torch.float64, device=dev)
     chosen_k = torch.empty((B,), dtype=torch.int32, device=dev)
-    ok = torch.empty((B,), dtype=torch.uint8, device=dev)
     with _on(dev):
         _call("pzn_cut_compact_solid_f32", _p(raw), SOLID_KINDS.index(kind), _p(params), _p(u), B, M, K, int(n_min), int(cap),
               _p(pieces), _p(counts), _p(start), _p(chosen), _p(chosen_k), _p(ok), _stream())
@@ -521,13 +522,10 @@ def cut_compact_double(raw, normals1, zs1, normals2, zs2, u, n_min, n_rich, cap)
                             f"u as [B, {DOUBLE_CUT_UNIFORMS}]")
     K = normals1.shape[1]
     dev = raw.device
-    pieces = torch.empty((4 * B, int(cap), 3), dtype=torch.float32, device=dev)
-    counts = torch.empty((4 * B,), dtype=torch.int64, device=dev)
-    start = torch.empty((4 * B,), dtype=torch.int64, device=dev)
+    pieces, counts, start, ok = _cut_outputs(raw, 4, cap)
     kind = torch.empty((B,), dtype=torch.int32, device=dev)
     planes = torch.empty((B, 2, 4), dtype=torch.float64, device=dev)
     tabs = torch.empty((B, 4), dtype=torch.int32, device=dev)
-    ok = torch.empty((B,), dtype=torch.uint8, device=dev)
     with _on(dev):
         _call("pzn_cut_compact_double_f32", _p(raw), _p(normals1), _p(zs1), _p(normals2), _p(zs2), _p(u), B, M, K, int(n_min),
               int(n_rich), int(cap), _p(pieces), _p(counts), _p(start), _p(kind), _p(planes), _p(tabs), _p(ok), _stream())

@@ -2,6 +2,7 @@
 float64 `distance` array holding float32 values, first maximum) must be what the fp32 oracle FPS computes on the cut
 pieces, draw for draw — that is what lets the GPU pipeline run `pzn_fps_f32` on them."""
 import numpy as np
+import pytest
 
 from oracle import point_ops as orc
 
@@ -157,3 +158,31 @@ def test_solid_cut_masks_against_the_restated_meshes():
     zero = torch.zeros(1, 3, dtype=torch.float64)
     probe = torch.tensor([[[0.0, 0.0, 0.9], [0.0, 0.0, 1.1], [0.9, 0.0, -0.95], [1.05, 0.0, -0.95], [0.0, 0.0, -1.05]]])
     assert dp.solid_cut_mask(probe, "cone", zero + 1e-12, None).tolist() == [[True, False, True, False, False]]
+
+
+@pytest.mark.parametrize("mode", ["plane", "solid", "double"])
+def test_feeder_draws_keep_the_meaning_of_a_seed(mode):
+    """The host draws of a PairFeeder batch, per mode, against the generator calls written out: the same calls on the
+    RandomState and on the torch Generator, with the same shapes, in the same order, land in the same staging columns - for
+    two consecutive batches.  (The GPU tests pin "same seed, same batches"; this pins what the seed means.)"""
+    import torch
+    from puzzlenet_amd import datapipe
+    B, K, seed, mag = 3, 4, 7, 0.8
+    draw = {"plane": datapipe.draw_plane_batch, "solid": datapipe.draw_solid_batch, "double": datapipe.draw_double_batch}[mode]
+    width = {"plane": 3 * K + K + 2 + 6, "solid": 6 * K + 2 + 6, "double": (K + 7) * 4 + 7 + 6}[mode]
+    rng, gen = np.random.RandomState(seed), torch.Generator().manual_seed(seed)
+    want_rng, want_gen = np.random.RandomState(seed), torch.Generator().manual_seed(seed)
+    for _ in range(2):
+        got = np.full((B, width), np.nan)
+        draw(rng, gen, B, K, mag, got)
+        r = want_rng
+        if mode == "plane":
+            blocks = [r.rand(B, 3 * K), r.rand(B, K) / 3, r.rand(B, 2)]
+        elif mode == "solid":
+            blocks = [datapipe.solid_draws(r, B, K).reshape(B, 6 * K), r.rand(B, 2)]
+        else:
+            blocks = [r.rand(B, 3 * K), r.rand(B, K) / 3, r.rand(B, 21), r.rand(B, 7) / 3, r.rand(B, 7)]
+        x = torch.randn(B, 6, generator=want_gen, dtype=torch.float64)
+        blocks.append((x / x.norm(p=2, dim=1, keepdim=True) * mag).numpy())
+        want = np.concatenate(blocks, axis=1)
+        assert want.shape == got.shape and np.array_equal(got, want)

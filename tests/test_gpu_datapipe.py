@@ -220,7 +220,11 @@ def test_pair_feeder_builds_fresh_batches_beside_the_training_step():
     feeder.close()
 
 
-@pytest.mark.parametrize("B,M,K,n_min,cap", [(5, 5000, 8, 1024, 5000), (3, 777, 4, 100, 777), (2, 3000, 3, 1400, 2000), (1, 64, 2, 1, 64)])
+@pytest.mark.parametrize("B,M,K,n_min,cap", [
+    (5, 5000, 8, 1024, 5000), (3, 777, 4, 100, 777), (2, 3000, 3, 1400, 2000), (1, 64, 2, 1, 64),
+    (2, 65537 + 1024, 3, 20000, 66561),      # runs of more than 64 points per thread: the kept membership bits no longer fit, the plane is evaluated again
+    (3, 777, 4, 400, 777),                   # n_min > M / 2: no candidate can be valid, the most balanced one is written from kept bits
+    (1, 1024, 2, 1, 1024), (1, 1025, 2, 1, 1025)])      # a run of one point | of two, with empty trailing threads
 def test_cut_compact_equals_the_tensor_form(B, M, K, n_min, cap):
     """ops.cut_compact (one launch: first valid of K candidate planes, stable partition, padding, start indices) against the
     tensor statement of the same thing: plane_cut_mask (float64, numpy's summation order) per candidate, the first valid one,
@@ -234,6 +238,7 @@ def test_cut_compact_equals_the_tensor_form(B, M, K, n_min, cap):
     u = torch.from_numpy(rng.rand(B, 2)).to(dev)
     pieces, counts, start, plane, ok = ops.cut_compact(raw, normals, zs, u, n_min, cap)
     torch.cuda.synchronize()
+    most_balanced = []
     for b in range(B):
         pick, valid, best = None, False, (-1, 0)
         for k in range(K):
@@ -244,6 +249,7 @@ def test_cut_compact_equals_the_tensor_form(B, M, K, n_min, cap):
             if up >= n_min and M - up >= n_min:
                 pick, valid = k, True
                 break
+        most_balanced.append(best[1])
         pick = best[1] if pick is None else pick
         assert plane[b].tolist() == normals[b, pick].tolist() + [float(zs[b, pick])]
         m = datapipe.plane_cut_mask(raw[b:b + 1], normals[b:b + 1, pick], zs[b:b + 1, pick])
@@ -257,3 +263,5 @@ def test_cut_compact_equals_the_tensor_form(B, M, K, n_min, cap):
         for half, cnt in ((0, n_up), (1, M - n_up)):
             s = start[half * B + b].item()
             assert s == max(0, min(cnt - 1, int(np.floor(float(u[b, half]) * cnt))))
+    if 2 * n_min > M:      # the bits that are written were kept while later candidates were tried, and replaced earlier ones
+        assert not ok.any() and any(0 < k < K - 1 for k in most_balanced)
