@@ -98,6 +98,26 @@ int pzn_merge_resample_f32(const float* a, const float* b, const float* T, const
                            const int64_t* drop_a, int ka, const int64_t* drop_b, int kb, int M, int Na, int Nb,
                            int n_out, float* out, int64_t* src, pzn_stream_t stream);
 
+/* Refine P poses on their matched point sets by symmetric point-to-point ICP (no counterpart in the reference): one launch,
+ * one workgroup per problem, no workspace, no atomics, nothing waits for the device.  Problem p has the fixed set
+ * a[a_of ? a_of[p] : p] [ka,3], the moved set b[b_of ? b_of[p] : p] [kb,3] (a_of / b_of: NULL or int64 [P] rows of a / b,
+ * so one set can serve many problems) and the start pose T0[p] ([4,4] row-major, as pzn_se3_exp_fwd_f32 writes it).
+ * A pose moves a point as pzn_merge_resample_f32 does: x' = ((R00 x + R01 y) + R02 z) + t0, each operation rounded to fp32.
+ * Objective E(T) = mean_i min_j |a_i - T b_j|^2 + mean_j min_i |a_i - T b_j|^2 (fp32 differences, lowest index on ties,
+ * sums in a fixed order).  One iteration: the arg-mins c1(i), c2(j) under T give ka + kb pairs; the candidate T' is their
+ * least-squares rigid motion (centred float64 sums, Horn's quaternion in float64 = Kabsch with the reflection fix), rounded to
+ * fp32; E(T') < E(T) takes it, anything else stops.  Pairs whose moved-side points are one point, coincident or collinear
+ * (sum of the principal 2x2 minors of their scatter <= 1e-10 trace^2) keep the rotation and update the translation only.
+ * Out: T[P,4,4] (last row exactly 0 0 0 1), score[P] = E(T) <= score0[P] = E(T0), iters_used[P] (int32, accepted
+ * candidates), and, when non-NULL, corr_a[P,ka] / corr_b[P,kb] (int32): the c1 / c2 the last candidate was built from
+ * (those under T0 when iters = 0).  iters = 0 returns T0.  1 <= ka, kb <= 1024 (pzn_icp_refine_supported: 1 / 0) and
+ * iters >= 0, PZN_EUNSUPPORTED otherwise, before any launch; P = 0 is a success that launches nothing. */
+int pzn_icp_refine_supported(int ka, int kb);
+int pzn_icp_refine_f32(const float* a, const int64_t* a_of, const float* b, const int64_t* b_of,
+                       const float* T0, int P, int ka, int kb, int iters,
+                       float* T, float* score, float* score0, int32_t* iters_used,
+                       int32_t* corr_a, int32_t* corr_b, pzn_stream_t stream);
+
 /* pointnet_util.py:118-119  dists.argsort()[:, :, :K] fused with the distance:
  * idx[B,S,K] = the K nearest points of xyz[B,N,3] to each new_xyz[B,S,3],
  * ascending by (distance, index) == a stable ascending sort.  K <= N. */

@@ -30,6 +30,8 @@ SIGNATURES = {
     "pzn_fps_background_f32": (_c_i, [_c_f, _c_i, _c_i, _c_i, _c_f, _c_f, _c_f, _c_i, _c_f]),
     "pzn_merge_resample_supported": (_c_i, [_c_i] * 3),
     "pzn_merge_resample_f32": (_c_i, [_c_f] * 5 + [_c_i, _c_f] + [_c_i] * 5 + [_c_f] * 3),
+    "pzn_icp_refine_supported": (_c_i, [_c_i] * 2),
+    "pzn_icp_refine_f32": (_c_i, [_c_f] * 5 + [_c_i] * 4 + [_c_f] * 7),
     "pzn_knn_f32": (_c_i, [_c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_f, _c_f]),
     "pzn_ball_query_f32": (_c_i, [_c_fl, _c_i, _c_f, _c_f, _c_i, _c_i, _c_i, _c_f, _c_f]),
     "pzn_gather_fwd_f32": (_c_i, [_c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_f, _c_f]),

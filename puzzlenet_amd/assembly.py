@@ -22,6 +22,13 @@ under its pose, the union resampled to N points by farthest point sampling with 
 origin of every point kept), encodes the merged part alone - its sampling plan is read off its pick order, no FPS - and
 computes only its row and its column of the table again.
 
+refine=N (pair_block, match_pairs, ProgressiveAssembler, assemble_progressive; default 0 = none, and not one launch more)
+lets every pair pose move to where the two picked boundaries meet: refine_pairs runs symmetric point-to-point ICP on the k
+picked points of each side, all pairs in ONE launch (ops.icp_refine, csrc/icprefine.hip), at most N accepted steps from the
+network's pose.  It lowers exactly the quantity the walks rank by, so T and score of the block or table are the refined ones
+(score never above the unrefined chamfer of the same rows); twist stays the network's output (the project has no SE(3)
+logarithm), every other field is untouched.
+
 Inference only: eval mode, torch.no_grad(), fp32, one GPU.  Out of scope: any training on merged parts or on more than two
 pieces, beam search or several merges per round, undoing a merge, and more than one GPU.
 """
@@ -37,6 +44,7 @@ PairTable = collections.namedtuple("PairTable", "twist T de_fpcb de_mrpcb top_f 
 Assembly = collections.namedtuple("Assembly", "root edges G placed")
 PieceCodes = collections.namedtuple("PieceCodes", "U V local_f g_max de_mrpcb top_m x2")
 PairBlock = collections.namedtuple("PairBlock", "twist T de_fpcb top_f score")
+Refined = collections.namedtuple("Refined", "T score score0 iters_used")
 Progressive = collections.namedtuple("Progressive", "G edges placed cloud piece_id row_id parts")
 
 ENCODER_ROWS = 64      # pieces per encoder call (the fused per-point stem takes up to 64 clouds)
@@ -166,10 +174,52 @@ def encode_pieces(model, pieces, k=128, start=None, plan=None, _who="encode_piec
     return PieceCodes(U, V, local_f, g_max, de_mrpcb.permute(0, 2, 1), top_m, plan[1][0])
 
 
-def pair_block(model, pieces_f, codes_f, pieces_m, codes_m, k=128):
+def _refine_gathered(Bf, Bm, T, iters):
+    """refine_pairs on boundaries that are gathered already: Bf [Kf Km,k,3] per pair, Bm [Km,k,3] per moved piece (served to
+    every fixed piece through b_of), T [Kf,Km,4,4] -> Refined.  One launch."""
+    Kf, Km = T.shape[0], T.shape[1]
+    b_of = torch.arange(Km, dtype=torch.long, device=T.device).repeat(Kf)              # problem i Km + j reads Bm[j]
+    Tr, score, score0, used = ops.icp_refine(Bf, Bm, T.reshape(Kf * Km, 4, 4), iters, b_of=b_of)
+    return Refined(Tr.view(Kf, Km, 4, 4), score.view(Kf, Km), score0.view(Kf, Km), used.view(Kf, Km))
+
+
+def refine_pairs(pieces_f, top_f, pieces_m, top_m, T, iters=30):
+    """Refine every pair pose on its matched boundaries: for pieces_f [Kf,N,3] with picked rows top_f [Kf,Km,k], pieces_m
+    [Km,N,3] with top_m [Km,k] and poses T [Kf,Km,4,4] (T[i,j] maps moved piece j into fixed piece i's frame), symmetric
+    point-to-point ICP between pieces_f[i][top_f[i,j]] and pieces_m[j][top_m[j]] from T[i,j], at most `iters` accepted steps
+    -> Refined(T [Kf,Km,4,4], score [Kf,Km], score0 [Kf,Km], iters_used [Kf,Km] int32).  score is the table's quantity (mean
+    + mean of the squared nearest-neighbour distances) under the returned pose and never above score0, the same under T.
+    All Kf Km problems run in one launch (ops.icp_refine); nothing waits for the device."""
+    for name, t in (("pieces_f", pieces_f), ("pieces_m", pieces_m), ("T", T), ("top_f", top_f), ("top_m", top_m)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.PznError(f"refine_pairs: {name} must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
+    if pieces_f.dim() != 3 or pieces_m.dim() != 3 or pieces_f.shape[2] != 3 or pieces_m.shape[2] != 3:
+        raise _lib.PznError(f"refine_pairs expects pieces_f[Kf,N,3], pieces_m[Km,N,3]; got {tuple(pieces_f.shape)}, "
+                            f"{tuple(pieces_m.shape)}")
+    Kf, Km = pieces_f.shape[0], pieces_m.shape[0]
+    if top_f.dim() != 3 or top_f.shape[:2] != (Kf, Km) or top_m.dim() != 2 or top_m.shape[0] != Km or T.shape != (Kf, Km, 4, 4):
+        raise _lib.PznError(f"refine_pairs expects top_f[{Kf},{Km},k], top_m[{Km},k], T[{Kf},{Km},4,4]; got "
+                            f"{tuple(top_f.shape)}, {tuple(top_m.shape)}, {tuple(T.shape)}")
+    with torch.no_grad():
+        Bf = ops.index_points(pieces_f, top_f.reshape(Kf, -1)).view(Kf * Km, top_f.shape[2], 3)
+        Bm = ops.index_points(pieces_m, top_m)
+        return _refine_gathered(Bf, Bm, T.contiguous(), iters)
+
+
+def _check_refine(refine, who):
+    refine = int(refine)
+    if refine < 0:
+        raise _lib.PznError(f"{who}: refine = {refine} (0: none, or the number of ICP steps at most)")
+    return refine
+
+
+def pair_block(model, pieces_f, codes_f, pieces_m, codes_m, k=128, refine=0):
     """The rectangular block of the pair table with pieces_f [Kf,N,3] in the fixed role and pieces_m [Km,N,3] in the moved
     role, from their PieceCodes -> PairBlock(twist [Kf,Km,6], T [Kf,Km,4,4], de_fpcb [Kf,Km,2,N], top_f [Kf,Km,k],
-    score [Kf,Km]); entries as match_pairs documents them (no diagonal is masked here)."""
+    score [Kf,Km]); entries as match_pairs documents them (no diagonal is masked here).  refine > 0: T and score are those
+    of refine_pairs(..., iters=refine) from the network's pose, one launch in place of the transform and the chamfer; twist
+    stays the network's output."""
+    refine = _check_refine(refine, "pair_block")
     Kf, N = pieces_f.shape[0], pieces_f.shape[1]
     Km = pieces_m.shape[0]
     k = int(k)
@@ -187,13 +237,16 @@ def pair_block(model, pieces_f, codes_f, pieces_m, codes_m, k=128):
         top_f = ops.topk_rows(p_f, k).view(Kf, Km, k)
         Bf = ops.index_points(pieces_f, top_f.reshape(Kf, Km * k)).view(Kf * Km, k, 3)       # pieces_f[i][top_f[i, j]]
         Bm = ops.index_points(pieces_m, codes_m.top_m)                                       # pieces_m[j][top_m[j]]
+        if refine > 0:
+            r = _refine_gathered(Bf, Bm, T, refine)
+            return PairBlock(twist, r.T, de_fpcb, top_f, r.score)
         Bm = se3.transform_points(T.reshape(Kf * Km, 4, 4), Bm.unsqueeze(0).expand(Kf, -1, -1, -1).reshape(Kf * Km, k, 3))
         d1, d2 = ops.chamfer(Bf, Bm)
         score = (d1.mean(dim=1) + d2.mean(dim=1)).view(Kf, Km)
     return PairBlock(twist, T, de_fpcb, top_f, score)
 
 
-def match_pairs(model, pieces, k=128, start=None):
+def match_pairs(model, pieces, k=128, start=None, refine=0):
     """All K (K - 1) ordered pairs of `pieces` [K,N,3] (float32, on the GPU, N = model.num_points, K >= 2) through
     predict5's eval path with every piece encoded once -> PairTable, index order [fixed i, moved j]:
 
@@ -209,10 +262,15 @@ def match_pairs(model, pieces, k=128, start=None):
     start = (s1[K], s2[K]): int64 FPS start indices of the two set-abstraction levels; None draws them with
     torch.randint(0, N, (K,)) then torch.randint(0, 512, (K,)) from model.fps_generator (the global generator when that
     is None).  Any K is taken: the encoders run on 64 pieces at a time.  Nothing here waits for the device.
-    It is encode_pieces, the square pair_block and the diagonal fill."""
+    It is encode_pieces, the square pair_block and the diagonal fill.
+
+    refine = N > 0: T and score are refined on the picked rows (refine_pairs, at most N accepted ICP steps from se3.exp(twist),
+    one launch for the table; the diagonal is refined like any pair and then masked); twist stays the network's output, so
+    T is no longer se3.exp(twist); every other field is what refine = 0 gives, bit for bit."""
+    refine = _check_refine(refine, "match_pairs")
     codes = encode_pieces(model, pieces, k, start, _who="match_pairs", _least=2)
     pieces = pieces.contiguous()
-    blk = pair_block(model, pieces, codes, pieces, codes, k)
+    blk = pair_block(model, pieces, codes, pieces, codes, k, refine)
     K = pieces.shape[0]
     with torch.no_grad():
         score = blk.score.masked_fill(torch.eye(K, dtype=torch.bool, device=pieces.device), float("inf"))
@@ -351,9 +409,11 @@ class ProgressiveAssembler:
     (which original piece and row every point is), starts (the FPS starts (s1, s2) of every current part, host lists),
     and the MergeLedger fields members, G, edges.  pieces, k, start as match_pairs takes them; max_score stops the walk
     at the first minimum above it; generator draws the merges' start rows (torch.randint(0, N) on the host, K - 1 draws
-    at construction).  Inference only: eval mode, no_grad, fp32, one GPU."""
+    at construction).  refine = N > 0: every pose of the table is refined on its picked rows (refine_pairs; the whole table
+    once, then only the new row and column of a round - kept entries stay bit for bit), so the merge moves the part by the
+    refined pose and the ledger records it.  Inference only: eval mode, no_grad, fp32, one GPU."""
 
-    def __init__(self, model, pieces, k=128, start=None, max_score=None, drop_matched=True, generator=None):
+    def __init__(self, model, pieces, k=128, start=None, max_score=None, drop_matched=True, generator=None, refine=0):
         K, N, k = _check_pieces(model, pieces, k, "ProgressiveAssembler", 2)
         if drop_matched and 2 * k > N:
             raise _lib.PznError(f"ProgressiveAssembler: drop_matched needs k <= N / 2 (k = {k}, N = {N}): the rows kept "
@@ -361,6 +421,7 @@ class ProgressiveAssembler:
         if not ops.merge_resample_supported(N, N, N):
             raise _lib.PznUnsupported(f"ProgressiveAssembler: two parts of N = {N} points are not a union merge_resample takes")
         self.model, self.k, self.max_score, self.drop_matched = model, k, max_score, bool(drop_matched)
+        self.refine = _check_refine(refine, "ProgressiveAssembler")
         dev = pieces.device
         if start is None:
             gen = getattr(model, "fps_generator", None)
@@ -371,7 +432,7 @@ class ProgressiveAssembler:
         self._s1, self._s2 = s1.tolist(), s2.tolist()
         self.parts = pieces.contiguous().clone()
         self.codes = encode_pieces(model, self.parts, k, (s1, s2), _who="ProgressiveAssembler", _least=2)
-        blk = pair_block(model, self.parts, self.codes, self.parts, self.codes, k)
+        blk = pair_block(model, self.parts, self.codes, self.parts, self.codes, k, self.refine)
         eye = torch.eye(K, dtype=torch.bool, device=dev)
         self.table = PairTable(blk.twist, blk.T, blk.de_fpcb, self.codes.de_mrpcb, blk.top_f, self.codes.top_m,
                                blk.score.masked_fill(eye, float("inf")), self.codes.x2)
@@ -446,8 +507,8 @@ class ProgressiveAssembler:
                 old[n] = new[0]
                 fields.append(old)
             self.codes = PieceCodes(*fields)
-            row = pair_block(self.model, merged, code, self.parts, self.codes, k)      # [1, K' - 1]
-            col = pair_block(self.model, self.parts, self.codes, merged, code, k)      # [K' - 1, 1]
+            row = pair_block(self.model, merged, code, self.parts, self.codes, k, self.refine)      # [1, K' - 1]
+            col = pair_block(self.model, self.parts, self.codes, merged, code, k, self.refine)      # [K' - 1, 1]
             upd = {}
             for name in PairBlock._fields:
                 x = _del2(getattr(t, name), j)
@@ -479,6 +540,6 @@ class ProgressiveAssembler:
                            self.row_id[root], self.parts)
 
 
-def assemble_progressive(model, pieces, k=128, start=None, max_score=None, drop_matched=True, generator=None):
+def assemble_progressive(model, pieces, k=128, start=None, max_score=None, drop_matched=True, generator=None, refine=0):
     """ProgressiveAssembler(...).step() until one part is left or the walk stops -> Progressive."""
-    return ProgressiveAssembler(model, pieces, k, start, max_score, drop_matched, generator).run()
+    return ProgressiveAssembler(model, pieces, k, start, max_score, drop_matched, generator, refine).run()

@@ -28,6 +28,7 @@ SOURCES = [
     ("core.hip", NOSLP),
     ("fps.hip", ["-ffp-contract=off"] + NOSLP),
     ("mergefps.hip", ["-ffp-contract=off"] + NOSLP),
+    ("icprefine.hip", ["-ffp-contract=off"] + NOSLP),
     ("knn.hip", ["-ffp-contract=off"]),
     ("group.hip", ["-ffp-contract=off"] + NOSLP),
     ("emd.hip", NOSLP),

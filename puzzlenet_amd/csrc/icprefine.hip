@@ -1,0 +1,372 @@
+// icprefine.hip — refine every pair pose on its matched boundaries, for gfx950 (assembly.refine_pairs).
+//
+// One workgroup per problem p does symmetric point-to-point ICP between the fixed set a (ka rows) and the moved set b (kb
+// rows), from the pose T0[p], with everything in LDS: what would otherwise be transform -> chamfer -> two gathers -> centring
+// -> bmm -> batched 3x3 SVD -> compose -> chamfer again, about a dozen launches per iteration.
+//   * state: ONE pose (R, t) as fp32 values, in every thread's registers.  A pose is always evaluated on the original moved
+//     points: x' = ((R00 x + R01 y) + R02 z) + t0, every product and sum rounded on its own (__fmul_rn / __fadd_rn: the
+//     arithmetic of mergefps.hip, so a refined pose moves points to the same bits there as here);
+//   * objective: E(T) = mean_i min_j |a_i - T b_j|^2 + mean_j min_i |a_i - T b_j|^2, direct differences
+//     (pzn::sqdist3), arg-min = the lowest index of the minimum.  Row r < ka of the ka + kb rows is a_r scanning T b, row
+//     ka + j is T b_j scanning a; a thread owns rows tid, tid + 256, ... and adds their minima in that order, the wave adds
+//     its 64 lanes by the xor butterfly (both partners form the same sum), the four wave sums are added in wave order:
+//     the same bits on every run;
+//   * one iteration from T: the correspondences c1(i), c2(j) of the evaluation of T give ka + kb pairs (fixed p, moved q):
+//     (a_i, b_c1(i)) and (a_c2(j), b_j), q always the ORIGINAL point.  Centroids, then the centred cross-covariance
+//     S = sum (q - qc)(p - pc)^T and the moved side's scatter C = sum (q - qc)(q - qc)^T, all accumulated in float64 (thread,
+//     butterfly, wave order).  Thread 0 solves in float64: Horn's quaternion - the eigenvector of the largest eigenvalue of
+//     the symmetric 4x4 N(S), cyclic Jacobi sweeps - which is Kabsch with the reflection fix; t' = pc - R' qc; both rounded
+//     to fp32.  E(T') < E(T) takes the candidate, anything else (NaN included) stops and keeps T: the only stop rule besides
+//     iters;
+//   * DEGENERATE correspondences (a single point, all moved-side points q coincident or collinear) keep the current R and
+//     update t only.  The rule, stated once: with C's trace tr and the sum of its three principal 2x2 minors m2
+//     (= l1 l2 + l1 l3 + l2 l3 for eigenvalues l), degenerate iff m2 <= ICP_DEGENERATE * tr * tr, ICP_DEGENERATE = 1e-10
+//     (m2 / tr^2 is about l2 / l1 for a thin set; points exactly on a line, rounded to fp32, sit near 1e-14).
+// Latency-bound: per iteration a serial chain of six barriers, a (ka | kb)-step scan and one lane's float64 solve; the
+// launch is parallel over problems only, and the grid walks when P exceeds ICP_MAX_GRID.
+#include "pzn_common.h"
+
+namespace {
+
+constexpr int ICP_T = 256;                 // four wavefronts
+constexpr int ICP_W = ICP_T / PZN_WAVE;
+constexpr int ICP_MAX_K = 1024;            // 36 KB of point images + 4 KB of arg-mins + 0.5 KB of reduction slots: 40.5 KB of LDS at most
+constexpr int ICP_MAX_GRID = 512;          // two workgroups per CU of a 256-CU part; more problems share a workgroup in turn
+constexpr int ICP_SWEEPS = 12;             // cyclic Jacobi sweeps at most (a 4x4 converges in 5 to 7)
+constexpr double ICP_DEGENERATE = 1e-10;
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+  uint64_t u;
+  u = pzn::xor_lane_u64<1>((uint64_t)__double_as_longlong(v)), v += __longlong_as_double((long long)u);
+  u = pzn::xor_lane_u64<2>((uint64_t)__double_as_longlong(v)), v += __longlong_as_double((long long)u);
+  u = pzn::xor_lane_u64<4>((uint64_t)__double_as_longlong(v)), v += __longlong_as_double((long long)u);
+  u = pzn::xor_lane_u64<8>((uint64_t)__double_as_longlong(v)), v += __longlong_as_double((long long)u);
+  u = pzn::xor_lane_u64<16>((uint64_t)__double_as_longlong(v)), v += __longlong_as_double((long long)u);
+  u = pzn::xor_lane_u64<32>((uint64_t)__double_as_longlong(v)), v += __longlong_as_double((long long)u);
+  return v;
+}
+
+__device__ __forceinline__ float wave_sum_f32_dpp(float v) {
+  v = __fadd_rn(v, __uint_as_float(pzn::xor_lane<1>(__float_as_uint(v))));
+  v = __fadd_rn(v, __uint_as_float(pzn::xor_lane<2>(__float_as_uint(v))));
+  v = __fadd_rn(v, __uint_as_float(pzn::xor_lane<4>(__float_as_uint(v))));
+  v = __fadd_rn(v, __uint_as_float(pzn::xor_lane<8>(__float_as_uint(v))));
+  v = __fadd_rn(v, __uint_as_float(pzn::xor_lane<16>(__float_as_uint(v))));
+  v = __fadd_rn(v, __uint_as_float(pzn::xor_lane<32>(__float_as_uint(v))));
+  return v;
+}
+
+// One Jacobi rotation of the symmetric 4x4 A in the (P, Q) plane, accumulated into V (columns = eigenvectors).
+template <int P, int Q>
+__device__ __forceinline__ void jacobi_rot(double (&A)[4][4], double (&V)[4][4]) {
+  const double apq = A[P][Q];
+  if (apq == 0.0) return;
+  const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
+  const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+  const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double x = A[k][P], y = A[k][Q];
+    A[k][P] = c * x - s * y;
+    A[k][Q] = s * x + c * y;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double x = A[P][k], y = A[Q][k];
+    A[P][k] = c * x - s * y;
+    A[Q][k] = s * x + c * y;
+  }
+  A[P][Q] = A[Q][P] = 0.0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double x = V[k][P], y = V[k][Q];
+    V[k][P] = c * x - s * y;
+    V[k][Q] = s * x + c * y;
+  }
+}
+
+// Horn's closed form: the rotation R (row-major) that maximises sum p . R q for S[u][v] = sum q_u p_v.
+__device__ void horn_rotation(const double (&S)[3][3], double (&R)[9]) {
+  double A[4][4], V[4][4];
+  A[0][0] = S[0][0] + S[1][1] + S[2][2];
+  A[1][1] = S[0][0] - S[1][1] - S[2][2];
+  A[2][2] = -S[0][0] + S[1][1] - S[2][2];
+  A[3][3] = -S[0][0] - S[1][1] + S[2][2];
+  A[0][1] = A[1][0] = S[1][2] - S[2][1];
+  A[0][2] = A[2][0] = S[2][0] - S[0][2];
+  A[0][3] = A[3][0] = S[0][1] - S[1][0];
+  A[1][2] = A[2][1] = S[0][1] + S[1][0];
+  A[1][3] = A[3][1] = S[2][0] + S[0][2];
+  A[2][3] = A[3][2] = S[1][2] + S[2][1];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < ICP_SWEEPS; ++sweep) {
+    const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[0][3] * A[0][3] + A[1][2] * A[1][2] + A[1][3] * A[1][3] +
+                       A[2][3] * A[2][3];
+    const double dia = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2] + A[3][3] * A[3][3];
+    if (off <= 1e-34 * dia) break;
+    jacobi_rot<0, 1>(A, V);
+    jacobi_rot<0, 2>(A, V);
+    jacobi_rot<0, 3>(A, V);
+    jacobi_rot<1, 2>(A, V);
+    jacobi_rot<1, 3>(A, V);
+    jacobi_rot<2, 3>(A, V);
+  }
+  // the column of the largest eigenvalue (first of equals), by selects: no dynamically indexed array
+  double l = A[0][0], w = V[0][0], x = V[1][0], y = V[2][0], z = V[3][0];
+#pragma unroll
+  for (int c = 1; c < 4; ++c) {
+    const bool take = A[c][c] > l;
+    l = take ? A[c][c] : l;
+    w = take ? V[0][c] : w, x = take ? V[1][c] : x, y = take ? V[2][c] : y, z = take ? V[3][c] : z;
+  }
+  const double inv = 1.0 / sqrt(w * w + x * x + y * y + z * z);
+  w *= inv, x *= inv, y *= inv, z *= inv;
+  R[0] = 1.0 - 2.0 * (y * y + z * z), R[1] = 2.0 * (x * y - w * z), R[2] = 2.0 * (x * z + w * y);
+  R[3] = 2.0 * (x * y + w * z), R[4] = 1.0 - 2.0 * (x * x + z * z), R[5] = 2.0 * (y * z - w * x);
+  R[6] = 2.0 * (x * z - w * y), R[7] = 2.0 * (y * z + w * x), R[8] = 1.0 - 2.0 * (x * x + y * y);
+}
+
+struct Pose {
+  float r[9], t[3];
+};
+
+struct Lds {
+  float *ax, *ay, *az;      // fixed set, [ka]
+  float *bx, *by, *bz;      // moved set as given, [kb]
+  float *tx, *ty, *tz;      // moved set under the pose being evaluated, [kb]
+  unsigned short* corr;     // [ka + kb] arg-min of every row under the pose evaluated last (a row's owner alone touches it)
+  double* redd;             // [ICP_W][15] wave partials of the float64 sums
+  float* rede;              // [ICP_W][2] wave partials of the two objective sums
+  float* cand;              // [12] the candidate pose, thread 0 -> everyone
+};
+
+// E(pose): moves b into (tx, ty, tz), scans, leaves every row's arg-min in L.corr -> the objective, the same bits in every
+// thread.  Three barriers; on entry no thread may still be reading tx / rede (every caller comes from a barrier).
+__device__ float evaluate(const Lds& L, const Pose& g, int ka, int kb, int tid) {
+  for (int j = tid; j < kb; j += ICP_T) {
+    const float x = L.bx[j], y = L.by[j], z = L.bz[j];
+    L.tx[j] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(g.r[0], x), __fmul_rn(g.r[1], y)), __fmul_rn(g.r[2], z)), g.t[0]);
+    L.ty[j] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(g.r[3], x), __fmul_rn(g.r[4], y)), __fmul_rn(g.r[5], z)), g.t[1]);
+    L.tz[j] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(g.r[6], x), __fmul_rn(g.r[7], y)), __fmul_rn(g.r[8], z)), g.t[2]);
+  }
+  __syncthreads();
+  float s1 = 0.f, s2 = 0.f;
+  const int rows = ka + kb;
+  for (int r = tid; r < rows; r += ICP_T) {
+    const bool fixed_row = r < ka;
+    const int own = fixed_row ? r : r - ka;
+    const float qx = fixed_row ? L.ax[own] : L.tx[own];
+    const float qy = fixed_row ? L.ay[own] : L.ty[own];
+    const float qz = fixed_row ? L.az[own] : L.tz[own];
+    const float* sx = fixed_row ? L.tx : L.ax;
+    const float* sy = fixed_row ? L.ty : L.ay;
+    const float* sz = fixed_row ? L.tz : L.az;
+    const int n = fixed_row ? kb : ka;
+    float best = __builtin_inff();
+    int arg = 0;
+    for (int c = 0; c < n; ++c) {
+      // (a - T b) in both directions; strict <: the lowest index of equal distances stays
+      const float d = fixed_row ? pzn::sqdist3(qx, qy, qz, sx[c], sy[c], sz[c]) : pzn::sqdist3(sx[c], sy[c], sz[c], qx, qy, qz);
+      const bool take = d < best;
+      best = take ? d : best;
+      arg = take ? c : arg;
+    }
+    L.corr[r] = (unsigned short)arg;
+    if (fixed_row)
+      s1 = __fadd_rn(s1, best);
+    else
+      s2 = __fadd_rn(s2, best);
+  }
+  s1 = wave_sum_f32_dpp(s1);
+  s2 = wave_sum_f32_dpp(s2);
+  if ((tid & (PZN_WAVE - 1)) == 0) L.rede[2 * (tid / PZN_WAVE)] = s1, L.rede[2 * (tid / PZN_WAVE) + 1] = s2;
+  __syncthreads();
+  float e1 = L.rede[0], e2 = L.rede[1];
+#pragma unroll
+  for (int w = 1; w < ICP_W; ++w) e1 = __fadd_rn(e1, L.rede[2 * w]), e2 = __fadd_rn(e2, L.rede[2 * w + 1]);
+  const float e = __fadd_rn(__fdiv_rn(e1, (float)ka), __fdiv_rn(e2, (float)kb));
+  __syncthreads();      // rede and tx are free again
+  return e;
+}
+
+// The candidate from the correspondences in L.corr and the current pose (kept when the pairs are degenerate).  Three barriers.
+__device__ Pose candidate(const Lds& L, const Pose& cur, int ka, int kb, int tid) {
+  const int rows = ka + kb;
+  const int lane = tid & (PZN_WAVE - 1), wave = tid / PZN_WAVE;
+  // pass 1: centroids of the fixed-side points p and the moved-side points q of the ka + kb pairs
+  double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int r = tid; r < rows; r += ICP_T) {
+    const int c = L.corr[r];
+    const int ia = r < ka ? r : c, ib = r < ka ? c : r - ka;
+    s[0] += (double)L.ax[ia], s[1] += (double)L.ay[ia], s[2] += (double)L.az[ia];
+    s[3] += (double)L.bx[ib], s[4] += (double)L.by[ib], s[5] += (double)L.bz[ib];
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) s[k] = wave_sum_f64(s[k]);
+  if (lane == 0)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) L.redd[15 * wave + k] = s[k];
+  __syncthreads();
+  double cen[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    double v = L.redd[k];
+#pragma unroll
+    for (int w = 1; w < ICP_W; ++w) v += L.redd[15 * w + k];
+    cen[k] = v / (double)rows;
+  }
+  __syncthreads();      // redd is written again below
+  // pass 2: S[u][v] = sum qd_u pd_v (9) and the upper triangle of C = sum qd qd^T (6)
+  double m[15];
+#pragma unroll
+  for (int k = 0; k < 15; ++k) m[k] = 0.0;
+  for (int r = tid; r < rows; r += ICP_T) {
+    const int c = L.corr[r];
+    const int ia = r < ka ? r : c, ib = r < ka ? c : r - ka;
+    const double px = (double)L.ax[ia] - cen[0], py = (double)L.ay[ia] - cen[1], pz = (double)L.az[ia] - cen[2];
+    const double qx = (double)L.bx[ib] - cen[3], qy = (double)L.by[ib] - cen[4], qz = (double)L.bz[ib] - cen[5];
+    m[0] += qx * px, m[1] += qx * py, m[2] += qx * pz;
+    m[3] += qy * px, m[4] += qy * py, m[5] += qy * pz;
+    m[6] += qz * px, m[7] += qz * py, m[8] += qz * pz;
+    m[9] += qx * qx, m[10] += qy * qy, m[11] += qz * qz;
+    m[12] += qx * qy, m[13] += qx * qz, m[14] += qy * qz;
+  }
+#pragma unroll
+  for (int k = 0; k < 15; ++k) m[k] = wave_sum_f64(m[k]);
+  if (lane == 0)
+#pragma unroll
+    for (int k = 0; k < 15; ++k) L.redd[15 * wave + k] = m[k];
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int k = 0; k < 15; ++k) {
+      double v = L.redd[k];
+#pragma unroll
+      for (int w = 1; w < ICP_W; ++w) v += L.redd[15 * w + k];
+      m[k] = v;
+    }
+    const double tr = m[9] + m[10] + m[11];
+    const double m2 = (m[9] * m[10] - m[12] * m[12]) + (m[9] * m[11] - m[13] * m[13]) + (m[10] * m[11] - m[14] * m[14]);
+    double R[9];
+    if (m2 <= ICP_DEGENERATE * tr * tr) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) R[k] = (double)cur.r[k];
+    } else {
+      const double S[3][3] = {{m[0], m[1], m[2]}, {m[3], m[4], m[5]}, {m[6], m[7], m[8]}};
+      horn_rotation(S, R);
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) L.cand[k] = (float)R[k];
+#pragma unroll
+    for (int u = 0; u < 3; ++u)
+      L.cand[9 + u] = (float)(cen[u] - ((R[3 * u] * cen[3] + R[3 * u + 1] * cen[4]) + R[3 * u + 2] * cen[5]));
+  }
+  __syncthreads();
+  Pose out;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) out.r[k] = L.cand[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out.t[k] = L.cand[9 + k];
+  return out;      // (cand is written next after the three barriers of an evaluation)
+}
+
+// The arg-mins of the pose evaluated last leave as corr_a[p] / corr_b[p] (either may be NULL); every row by its owner.
+__device__ __forceinline__ void store_corr(const Lds& L, int p, int ka, int kb, int tid, int32_t* __restrict__ corr_a,
+                                           int32_t* __restrict__ corr_b) {
+  for (int r = tid; r < ka + kb; r += ICP_T) {
+    if (r < ka) {
+      if (corr_a) corr_a[(size_t)p * ka + r] = (int32_t)L.corr[r];
+    } else {
+      if (corr_b) corr_b[(size_t)p * kb + (r - ka)] = (int32_t)L.corr[r];
+    }
+  }
+}
+
+__global__ __launch_bounds__(ICP_T) void icp_refine_kernel(const float* __restrict__ a, const int64_t* __restrict__ a_of,
+                                                           const float* __restrict__ b, const int64_t* __restrict__ b_of,
+                                                           const float* __restrict__ T0, int P, int ka, int kb, int iters,
+                                                           float* __restrict__ T, float* __restrict__ score,
+                                                           float* __restrict__ score0, int32_t* __restrict__ iters_used,
+                                                           int32_t* __restrict__ corr_a, int32_t* __restrict__ corr_b) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  Lds L;
+  L.redd = reinterpret_cast<double*>(smem_raw);                       // [ICP_W][15]
+  L.rede = reinterpret_cast<float*>(L.redd + ICP_W * 15);             // [ICP_W][2]
+  L.cand = L.rede + ICP_W * 2;                                        // [12]
+  L.ax = L.cand + 12, L.ay = L.ax + ka, L.az = L.ay + ka;
+  L.bx = L.az + ka, L.by = L.bx + kb, L.bz = L.by + kb;
+  L.tx = L.bz + kb, L.ty = L.tx + kb, L.tz = L.ty + kb;
+  L.corr = reinterpret_cast<unsigned short*>(L.tz + kb);              // [ka + kb]
+  const int tid = (int)threadIdx.x;
+
+  for (int p = (int)blockIdx.x; p < P; p += (int)gridDim.x) {      // (workgroup-uniform)
+    const float* ga = a + (size_t)(a_of ? a_of[p] : (int64_t)p) * ka * 3;
+    const float* gb = b + (size_t)(b_of ? b_of[p] : (int64_t)p) * kb * 3;
+    for (int i = tid; i < 3 * ka; i += ICP_T) {
+      const float v = ga[i];
+      const int q = i / 3, c = i - 3 * q;
+      (c == 0 ? L.ax : (c == 1 ? L.ay : L.az))[q] = v;
+    }
+    for (int i = tid; i < 3 * kb; i += ICP_T) {
+      const float v = gb[i];
+      const int q = i / 3, c = i - 3 * q;
+      (c == 0 ? L.bx : (c == 1 ? L.by : L.bz))[q] = v;
+    }
+    const float* g0 = T0 + (size_t)p * 16;
+    Pose cur;
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      cur.r[3 * u] = g0[4 * u], cur.r[3 * u + 1] = g0[4 * u + 1], cur.r[3 * u + 2] = g0[4 * u + 2];
+      cur.t[u] = g0[4 * u + 3];
+    }
+    __syncthreads();
+
+    float e = evaluate(L, cur, ka, kb, tid);
+    const float e0 = e;
+    int used = 0;
+    for (int it = 0; it < iters; ++it) {      // (e, and with it the exit, is the same in every thread)
+      // the correspondences this candidate is built from (L.corr is overwritten by its evaluation)
+      store_corr(L, p, ka, kb, tid, corr_a, corr_b);
+      const Pose nxt = candidate(L, cur, ka, kb, tid);
+      const float en = evaluate(L, nxt, ka, kb, tid);
+      if (!(en < e)) break;
+      cur = nxt, e = en, ++used;
+    }
+    if (iters == 0) store_corr(L, p, ka, kb, tid, corr_a, corr_b);      // the correspondences under T0
+    if (tid < 16) {
+      const int u = tid >> 2, v = tid & 3;
+      float val = 0.f;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) val = (u < 3 && v < 3 && 3 * u + v == k) ? cur.r[k] : val;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) val = (u == k && v == 3) ? cur.t[k] : val;
+      val = tid == 15 ? 1.f : val;
+      T[(size_t)p * 16 + tid] = val;
+    }
+    if (tid == 0) score[p] = e, score0[p] = e0, iters_used[p] = used;
+    __syncthreads();      // the LDS image is replaced by the next problem's
+  }
+}
+
+}  // namespace
+
+PZN_EXPORT int pzn_icp_refine_supported(int ka, int kb) { return ka >= 1 && kb >= 1 && ka <= ICP_MAX_K && kb <= ICP_MAX_K; }
+
+PZN_EXPORT int pzn_icp_refine_f32(const float* a, const int64_t* a_of, const float* b, const int64_t* b_of, const float* T0,
+                                  int P, int ka, int kb, int iters, float* T, float* score, float* score0,
+                                  int32_t* iters_used, int32_t* corr_a, int32_t* corr_b, pzn_stream_t stream) {
+  if (!pzn_icp_refine_supported(ka, kb) || iters < 0) return PZN_EUNSUPPORTED;
+  PZN_CHECK_ARG(P >= 0);
+  if (P == 0) return PZN_OK;
+  PZN_CHECK_ARG(a && b && T0 && T && score && score0 && iters_used);
+  hipStream_t st = pzn_hip_stream(stream);
+  const size_t lds = ICP_W * 15 * sizeof(double) + (ICP_W * 2 + 12) * sizeof(float) +
+                     3 * ((size_t)ka + 2 * (size_t)kb) * sizeof(float) + ((size_t)ka + kb) * sizeof(unsigned short);
+  const int grid = P < ICP_MAX_GRID ? P : ICP_MAX_GRID;
+  PZN_LAUNCH(icp_refine_kernel, dim3(grid), dim3(ICP_T), lds, st, a, a_of, b, b_of, T0, P, ka, kb, iters, T, score, score0,
+             iters_used, corr_a, corr_b);
+  PZN_RETURN_LAUNCH_STATUS();
+}

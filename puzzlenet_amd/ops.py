@@ -227,6 +227,57 @@ def merge_resample(a, b, T, start, n_out=None, drop_a=None, drop_b=None):
     return out, src
 
 
+def icp_refine_supported(ka, kb):
+    return bool(_lib.load().pzn_icp_refine_supported(int(ka), int(kb)))
+
+
+def icp_refine(a, b, T0, iters, a_of=None, b_of=None, return_corr=False):
+    """P pose refinements in one launch (pzn_icp_refine_f32): symmetric point-to-point ICP of the moved set b[.,kb,3] onto the
+    fixed set a[.,ka,3] from T0[P,4,4], at most `iters` accepted steps per problem -> (T [P,4,4], score [P], score0 [P],
+    iters_used [P] int32), and with return_corr the correspondences the last candidate was built from, corr_a [P,ka] and
+    corr_b [P,kb] (int32).  score = E(T) <= score0 = E(T0), E as include/pzn.h states it; iters = 0 returns T0.
+    Problem p reads a[a_of[p]] and b[b_of[p]] (int64 [P]; the caller keeps them inside a / b - they are not checked, that
+    would wait for the device); without a map, a / b hold P sets.  1 <= ka, kb <= 1024 and iters >= 0 (PznUnsupported
+    beyond).  No autograd, nothing waits for the device."""
+    for name, t, dt in (("a", a, torch.float32), ("b", b, torch.float32), ("T0", T0, torch.float32), ("a_of", a_of, torch.int64),
+                        ("b_of", b_of, torch.int64)):
+        if isinstance(t, torch.Tensor) and t.dtype != dt:      # (no silent conversion: a pose refined in another precision)
+            raise _lib.PznError(f"icp_refine: {name} must be {dt}; got {t.dtype}")
+    a, b, T0 = _f32(a, "a"), _f32(b, "b"), _f32(T0, "T0")
+    if a.dim() != 3 or b.dim() != 3 or a.shape[2] != 3 or b.shape[2] != 3:
+        raise _lib.PznError(f"icp_refine: expected a[.,ka,3], b[.,kb,3]; got {tuple(a.shape)}, {tuple(b.shape)}")
+    if T0.dim() != 3 or T0.shape[1:] != (4, 4):
+        raise _lib.PznError(f"icp_refine: expected T0[P,4,4]; got {tuple(T0.shape)}")
+    P, ka, kb = T0.shape[0], a.shape[1], b.shape[1]
+    maps = []
+    for name, m, x in (("a_of", a_of, a), ("b_of", b_of, b)):
+        if m is None:
+            if x.shape[0] != P:
+                raise _lib.PznError(f"icp_refine: {name[0]} holds {x.shape[0]} sets for P = {P} poses and no {name} is given")
+        else:
+            m = _i64(m, name)
+            if m.shape != (P,):
+                raise _lib.PznError(f"icp_refine: expected {name}[{P}]; got {tuple(m.shape)}")
+            if x.shape[0] == 0 and P > 0:
+                raise _lib.PznError(f"icp_refine: {name} indexes an empty {name[0]}")
+        maps.append(m)
+    iters = int(iters)
+    if iters < 0 or not icp_refine_supported(ka, kb):
+        raise _lib.PznUnsupported(f"icp_refine: ka = {ka}, kb = {kb}, iters = {iters} (1 <= ka, kb <= 1024, iters >= 0)")
+    dev = a.device
+    T = torch.empty((P, 4, 4), dtype=torch.float32, device=dev)
+    score = torch.empty((P,), dtype=torch.float32, device=dev)
+    score0 = torch.empty_like(score)
+    used = torch.empty((P,), dtype=torch.int32, device=dev)
+    ca = torch.empty((P, ka), dtype=torch.int32, device=dev) if return_corr else None
+    cb = torch.empty((P, kb), dtype=torch.int32, device=dev) if return_corr else None
+    if P > 0:
+        with _on(dev):
+            _call("pzn_icp_refine_f32", _p(a), _p(maps[0]), _p(b), _p(maps[1]), _p(T0), P, ka, kb, iters, _p(T), _p(score),
+                  _p(score0), _p(used), _p(ca), _p(cb), _stream())
+    return (T, score, score0, used, ca, cb) if return_corr else (T, score, score0, used)
+
+
 def knn(xyz, new_xyz, K):
     xyz, new_xyz = _f32(xyz, "xyz"), _f32(new_xyz, "new_xyz")
     B, N, _ = xyz.shape

@@ -2,12 +2,15 @@
 assembled cloud.
 
     python tools/assemble.py --pieces pieces.npy [--ckpt model.ckpt] [--k 128] [--max-score S] [--out PREFIX] [--progressive]
+                             [--refine N]
 
 pieces.npy holds [K, N, 3] float32 (N = the model's points per piece).  Prints the score table and the edges in
 placement order, writes PREFIX_G.npy ([K,4,4], each piece into the root's frame) and PREFIX_cloud.npy ([K,N,3]).
 --progressive: assembly.assemble_progressive instead - after every placement the two parts are merged and resampled to N
 points and matched again -; PREFIX_G.npy then maps each piece into the frame of the part that holds it, PREFIX_cloud.npy
 is the [N,3] part around the first pair, PREFIX_piece_id.npy / PREFIX_row_id.npy say where each of its points came from.
+--refine N: every pair pose is refined on its picked boundary points before it is used (assembly.refine_pairs: symmetric
+point-to-point ICP, at most N accepted steps, one launch per table or per round); 0, the default, uses the network's poses.
 Needs a GPU; there is no CPU path."""
 import argparse
 import os
@@ -29,7 +32,10 @@ def main():
     ap.add_argument("--seed", type=int, default=0, help="seed of the FPS start indices")
     ap.add_argument("--progressive", action="store_true", help="merge placed parts, resample and match again after every placement")
     ap.add_argument("--keep-matched", action="store_true", help="--progressive: keep the matched boundary points in the merged part")
+    ap.add_argument("--refine", type=int, default=0, help="ICP steps at most per pair pose on the picked boundary points (0: none)")
     args = ap.parse_args()
+    if args.refine < 0:
+        sys.exit("--refine: 0 or a number of steps")
 
     if not torch.cuda.is_available():
         sys.exit("tools/assemble.py needs a GPU: puzzlenet_amd has no CPU path")
@@ -53,7 +59,7 @@ def main():
     x = torch.from_numpy(np.ascontiguousarray(pieces, dtype=np.float32)).to(dev)
     if args.progressive:
         res = assembly.assemble_progressive(model, x, k=args.k, max_score=args.max_score, drop_matched=not args.keep_matched,
-                                            generator=torch.Generator().manual_seed(args.seed))
+                                            generator=torch.Generator().manual_seed(args.seed), refine=args.refine)
         for a, b, s, _da, _db in res.edges:
             print(f"  merge: part of piece {b} into part of piece {a}, score {s:.6f}")
         left = [k for k in range(K) if not res.placed[k]]
@@ -64,7 +70,7 @@ def main():
             np.save(f"{args.out}_{name}.npy", t.cpu().numpy())
         print(f"wrote {args.out}_G.npy, {args.out}_cloud.npy, {args.out}_piece_id.npy, {args.out}_row_id.npy")
         return
-    table = assembly.match_pairs(model, x, k=args.k)
+    table = assembly.match_pairs(model, x, k=args.k, refine=args.refine)
     result = assembly.assemble(table.score, table.T, max_score=args.max_score)
 
     score = table.score.cpu().numpy()

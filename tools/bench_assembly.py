@@ -6,11 +6,21 @@ event pair around every kernel launch, ops.ktimer_start / ktimer_stop), beside t
 
     python tools/bench_assembly.py [--reps 20] [--out profiles/assembly_k16.json]
     python tools/bench_assembly.py --progressive [--reps 20] [--out profiles/assembly_progressive_k16.json]
+    python tools/bench_assembly.py --refine [--reps 20] [--out profiles/assembly_refine_k16.json]
 
 --progressive measures instead (a) ops.merge_resample against the unfused chain se3.transform_points -> cat ->
 farthest_point_sample -> index_points on the same inputs (Na = Nb = 1024 and 2048, M = 1 and 16; device time between two
 events around 20 back-to-back calls, five repeats, alternated) and (b) one ProgressiveAssembler.step() at K = 16 against
 match_pairs on the same 15 parts, what a round cost before it (host wall time around a synchronised call, alternated).
+
+--refine measures instead (a) assembly.refine_pairs - 30 ICP iterations at most over the 256 pairs of the K = 16 table, one
+launch, every pair stopping by the accept rule - against the torch composition a user would write today with public calls
+(transform, torch.cdist and two arg-mins, two gathers, centring, bmm, torch.linalg.svd with the sign fix, compose; ops.chamfer
+for the final score) on the same boundaries and poses, once with 30 fixed iterations (it has no accept rule) and once with as
+many iterations as the LONGEST pair of the fused launch ran (iters_used max + 1: the matched count, since the launch lasts as
+long as its longest problem); device time between two events around each call, alternated in one process; per-iteration
+figures and the library's launches beside them; and (b) match_pairs with refine = 30 against refine = 0 (host wall time around
+a synchronised call, alternated).
 
 Needs a GPU (there is no CPU path)."""
 import argparse
@@ -120,21 +130,115 @@ def progressive(args):
         f.write(json.dumps(result, indent=1) + "\n")
 
 
+def refine(args):
+    from oracle import model_ref as mr
+    from puzzlenet_amd import assembly, model5_b, ops, se3
+    ITERS = 30
+    dev = torch.device("cuda:0")
+    model = model5_b.TouchedRegraster(mr.Cfg(num_points=N))
+    mr.fill_params(model)
+    model.to(dev)
+    g = torch.Generator().manual_seed(16)
+    pieces = torch.rand(K, N, 3, generator=g).to(dev)
+    start = (torch.randint(0, N, (K,), generator=g), torch.randint(0, 512, (K,), generator=g))
+    with torch.no_grad():
+        table = assembly.match_pairs(model, pieces, k=TOP, start=start)
+        Bf = ops.index_points(pieces, table.top_f.reshape(K, K * TOP)).view(K * K, TOP, 3)
+        Bm = ops.index_points(pieces, table.top_m)
+        Bm_pairs = Bm.unsqueeze(0).expand(K, -1, -1, -1).reshape(K * K, TOP, 3).contiguous()
+        T0 = table.T.reshape(K * K, 4, 4).contiguous()
+
+    def fused():
+        return assembly.refine_pairs(pieces, table.top_f, pieces, table.top_m, table.T, ITERS)
+
+    def composition(iters):
+        """What a user writes today with public calls only: `iters` fixed iterations (no accept rule: that would need the score,
+        i.e. one more pass over the distances per iteration), every step a separate launch or several."""
+        T = T0
+        with torch.no_grad():
+            for _ in range(iters):
+                D = torch.cdist(Bf, se3.transform_points(T, Bm_pairs))               # [P, k, k]
+                i1, i2 = D.argmin(dim=2), D.argmin(dim=1)                            # per fixed point, per moved point
+                p = torch.cat((Bf, torch.gather(Bf, 1, i2.unsqueeze(-1).expand(-1, -1, 3))), dim=1)
+                q = torch.cat((torch.gather(Bm_pairs, 1, i1.unsqueeze(-1).expand(-1, -1, 3)), Bm_pairs), dim=1)
+                pc, qc = p.mean(dim=1, keepdim=True), q.mean(dim=1, keepdim=True)
+                S = torch.bmm((q - qc).transpose(1, 2), p - pc)
+                U, _s, Vh = torch.linalg.svd(S)
+                V = Vh.transpose(1, 2)
+                d = torch.sign(torch.linalg.det(torch.bmm(V, U.transpose(1, 2))))
+                V = torch.cat((V[:, :, :2], V[:, :, 2:] * d.view(-1, 1, 1)), dim=2)
+                R = torch.bmm(V, U.transpose(1, 2))
+                t = pc.transpose(1, 2) - torch.bmm(R, qc.transpose(1, 2))
+                T = torch.cat((torch.cat((R, t), dim=2), T0[:, 3:, :]), dim=1).contiguous()
+            d1, d2 = ops.chamfer(Bf, se3.transform_points(T, Bm_pairs))
+            return T, d1.mean(dim=1) + d2.mean(dim=1)
+
+    with torch.no_grad():
+        r = fused()
+    # the launch lasts as long as its longest problem: iters_used accepted candidates and the one that ended its loop
+    longest = min(ITERS, int(r.iters_used.max()) + 1)
+    Tc, sc = composition(ITERS)
+    for _ in range(args.warmup):
+        fused(), composition(ITERS), composition(longest)
+    f_ms, c_ms, m_ms = [], [], []
+    for _ in range(args.reps):               # alternated in one process
+        f_ms.append(_device_ms(fused, 1))
+        c_ms.append(_device_ms(lambda: composition(ITERS), 1))
+        m_ms.append(_device_ms(lambda: composition(longest), 1))
+    # kernel launches of the library in one call of each (torch's own kernels of the composition are not in this count)
+    ops.ktimer_start()
+    fused()
+    torch.cuda.synchronize()
+    k_f = ops.ktimer_stop()
+    icp = [v for name, v in k_f.items() if "icp_refine_kernel" in name]
+    off = ~torch.eye(K, dtype=torch.bool, device=dev)
+    f_med, c_med, m_med = statistics.median(f_ms), statistics.median(c_ms), statistics.median(m_ms)
+    result = {"tool": "tools/bench_assembly.py --refine", "device": torch.cuda.get_device_name(0), "dtype": "float32", "K": K,
+              "N": N, "k": TOP, "pairs": K * K, "iters": ITERS,
+              "refine_pairs_device": _spread(f_ms),
+              "torch_composition_fixed_iters_device": _spread(c_ms),
+              "torch_composition_matched_device": dict(_spread(m_ms), iterations=longest),
+              "composition_fixed_over_refine_pairs_median": c_med / f_med,
+              "composition_matched_over_refine_pairs_median": m_med / f_med,
+              "per_iteration_ms": {"refine_pairs_per_candidate_of_longest_pair": f_med / longest,
+                                   "composition": c_med / ITERS},
+              "refine_pairs_library_launches": {k_: v[0] for k_, v in k_f.items()},
+              "icp_refine_kernel_ms": icp[0][1] if icp else None,
+              "iters_used_mean": float(r.iters_used.float().mean()), "iters_used_max": int(r.iters_used.max()),
+              "score_over_score0_mean_off_diagonal": float((r.score[off] / r.score0[off]).mean()),
+              "composition_fixed_score_over_score0_mean_off_diagonal": float((sc.view(K, K)[off] / r.score0[off]).mean())}
+    print(json.dumps(result))
+    w0, w1 = [], []
+    for _ in range(args.reps):
+        w0 += _timed(lambda: assembly.match_pairs(model, pieces, k=TOP, start=start), 1)
+        w1 += _timed(lambda: assembly.match_pairs(model, pieces, k=TOP, start=start, refine=ITERS), 1)
+    result["match_pairs_wall"] = {"refine_0": _spread(w0), f"refine_{ITERS}": _spread(w1),
+                                  "added_median_ms": statistics.median(w1) - statistics.median(w0)}
+    print(json.dumps(result["match_pairs_wall"]))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(json.dumps(result, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--progressive", action="store_true")
+    ap.add_argument("--refine", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "assembly_progressive_k16.json" if args.progressive else "assembly_k16.json")
+        name = "assembly_progressive_k16.json" if args.progressive else ("assembly_refine_k16.json" if args.refine else "assembly_k16.json")
+        args.out = os.path.join(ROOT, "profiles", name)
     if args.reps < 20:
         sys.exit("--reps: at least 20 timed repetitions each")
     if not torch.cuda.is_available():
         sys.exit("tools/bench_assembly.py needs a GPU: puzzlenet_amd has no CPU path")
     if args.progressive:
         return progressive(args)
+    if args.refine:
+        return refine(args)
 
     from oracle import model_ref as mr
     from puzzlenet_amd import assembly, model5_b, ops, se3
