@@ -850,6 +850,9 @@ def emd_fused_small_multi(pairs):
 
 # --------------------------------------------------------------------------- chamfer
 
+CHAMFER_MAX_BATCH = 65535      # pzn_chamfer_*_f32 put the problem index on the grid's y axis
+
+
 class _Chamfer(torch.autograd.Function):
     """TouchedRegraster.chamfer_loss (model5_b.py:1495-1505) without P[B,n,m]."""
 
@@ -859,6 +862,9 @@ class _Chamfer(torch.autograd.Function):
         if a.dim() != 3 or b.dim() != 3 or a.shape[2] != 3 or b.shape[2] != 3 or a.shape[0] != b.shape[0]:
             raise _lib.PznError(f"chamfer expects a[B,n,3], b[B,m,3]; got {tuple(a.shape)}, {tuple(b.shape)}")
         B, n, m = a.shape[0], a.shape[1], b.shape[1]
+        if B > CHAMFER_MAX_BATCH:
+            raise _lib.PznError(f"chamfer takes at most {CHAMFER_MAX_BATCH} problems in one call (got {B}); "
+                                "ops.chamfer splits a larger batch")
         dev = a.device
         moa = torch.empty((B, m), dtype=torch.float32, device=dev)
         mob = torch.empty((B, n), dtype=torch.float32, device=dev)
@@ -889,7 +895,14 @@ class _Chamfer(torch.autograd.Function):
 
 
 def chamfer(a, b):
-    """-> (min over a per b-point [B,m], min over b per a-point [B,n])  == torch.min(P,1)[0], torch.min(P,2)[0]."""
+    """-> (min over a per b-point [B,m], min over b per a-point [B,n])  == torch.min(P,1)[0], torch.min(P,2)[0].
+    More than CHAMFER_MAX_BATCH problems (assembly's K^2 pairs from K = 256 pieces on) go in several calls, each chunk with
+    the bits of a call of its own."""
+    if (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and a.dim() == 3 and b.dim() == 3
+            and a.shape[0] == b.shape[0] and a.shape[0] > CHAMFER_MAX_BATCH):
+        parts = [_Chamfer.apply(a[s:s + CHAMFER_MAX_BATCH], b[s:s + CHAMFER_MAX_BATCH])
+                 for s in range(0, a.shape[0], CHAMFER_MAX_BATCH)]
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
     moa, mob, _, _ = _Chamfer.apply(a, b)
     return moa, mob
 
