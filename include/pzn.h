@@ -731,6 +731,24 @@ int pzn_cut_compact_double_f32(const float* raw, const double* normals1, const d
                                const double* zs2, const double* u, int B, int M, int K, int n_min, int n_rich, int cap,
                                float* pieces, int64_t* counts, int64_t* start, int32_t* kind, double* planes, int32_t* tabs,
                                uint8_t* ok, pzn_stream_t stream);
+/* Fracture (no counterpart in the reference, which ships pairs only): every cloud of a batch cut into P pieces by P - 1 planes,
+ * one launch, one workgroup per sample; datapipe.fracture_rule is the statement of this entry point.  All points start with
+ * label 0.  Step s = 1 .. P-1: the target t is the label with the most points among 0 .. s-1 (ties: the lowest); candidate k
+ * (k < K) is the plane with normal normals[b,s-1,k] (float64 [B,P-1,K,3]) through the ANCHOR, the target's r-th point in the
+ * cloud's order, r = clamp(floor(u_anchor[b,s-1,k] count[t]), 0, count[t] - 1) (u_anchor float64 [B,P-1,K]); its offset is
+ * -((x n0 + y n1) + z n2) of the anchor and its side test that of pzn_cut_compact_f32 (float64, no fma), so the anchor is at
+ * exactly 0, on the up side.  The FIRST candidate that leaves >= n_min target points on both sides is taken (none: the most
+ * balanced one, the first among equals, ok = 0); the up side keeps t, the down side becomes s.
+ * pieces [P B,cap,3]: piece p of sample b at row p B + b, the rows of label p in the cloud's order, padded with copies of its
+ * first row (of the cloud's first row when it is empty); rows beyond cap are not written (ok = 0).  counts int64 [P B];
+ * start int64 [P B] = clamp(floor(u_start[b,p] count), 0, count - 1) (u_start float64 [B,P]); label uint8 [B,M]; order int32
+ * [B,M]: the cloud row of every position of the concatenated pieces (the stable argsort of label); planes float64 [B,P-1,4]
+ * (normal, offset); target, cand int32 [B,P-1]: the label cut and the candidate taken at every step; ok uint8 [B].
+ * 2 <= P <= 16, K >= 1, 1 <= M <= 65536 (pzn_fracture_supported: 1 / 0), PZN_EUNSUPPORTED otherwise, before any launch. */
+int pzn_fracture_supported(int M, int P, int K);
+int pzn_fracture_f32(const float* raw, const double* normals, const double* u_anchor, const double* u_start, int B, int M,
+                     int P, int K, int n_min, int cap, float* pieces, int64_t* counts, int64_t* start, uint8_t* label,
+                     int32_t* order, double* planes, int32_t* target, int32_t* cand, uint8_t* ok, pzn_stream_t stream);
 /* dataset.py:1363-1366: 0/1 masks [R,N] with ones at the k picked rows idx int64 [R,k] of each cloud. */
 int pzn_pick_mask_f32(const int64_t* idx, int R, int k, int N, float* mask, pzn_stream_t stream);
 

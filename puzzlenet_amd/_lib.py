@@ -142,6 +142,8 @@ SIGNATURES = {
     "pzn_cut_compact_f32": (_c_i, [_c_f] * 4 + [_c_i] * 5 + [_c_f] * 6),
     "pzn_cut_compact_solid_f32": (_c_i, [_c_f, _c_i, _c_f, _c_f] + [_c_i] * 5 + [_c_f] * 7),
     "pzn_cut_compact_double_f32": (_c_i, [_c_f] * 6 + [_c_i] * 6 + [_c_f] * 8),
+    "pzn_fracture_supported": (_c_i, [_c_i] * 3),
+    "pzn_fracture_f32": (_c_i, [_c_f] * 4 + [_c_i] * 6 + [_c_f] * 10),
     "pzn_pick_mask_f32": (_c_i, [_c_f, _c_i, _c_i, _c_i, _c_f, _c_f]),
     "pzn_chamfer_bwd_f32": (_c_i, [_c_f, _c_f, _c_i, _c_i, _c_i, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
 }

@@ -343,6 +343,74 @@ def apply(pieces, G):
     return se3.transform_points(g.contiguous(), pieces.contiguous())
 
 
+# --------------------------------------------------------------------------- ground truth and the score of an assembly
+
+Evaluation = collections.namedtuple("Evaluation", "rot_deg trans msd part_ok part_accuracy edge_precision")
+
+
+def truth_table(pose, mates=None, cd=None):
+    """The pair table a perfect matcher would return for pieces moved by `pose` [P,4,4] (datapipe.fracture's pose of one sample:
+    moved piece = pose[p] applied to the piece where it belongs), on the host in float64 -> (T_gt [P,P,4,4], score_gt [P,P]):
+    T_gt[i,j] = pose[i] inv(pose[j]) maps moved piece j into moved piece i's frame (PairTable.T's convention); score_gt = cd
+    where mates, +inf elsewhere and on the diagonal (mates None: every pair; cd None: 0), so assemble(score_gt, T_gt) walks
+    the pieces that touch."""
+    X = _host(pose)
+    P = X.shape[0]
+    if X.shape != (P, 4, 4) or P < 2:
+        raise ValueError(f"truth_table expects pose[P,4,4] with P >= 2; got {X.shape}")
+    inv = np.stack([_rigid_inv(X[p]) for p in range(P)])
+    T = np.einsum("iab,jbc->ijac", X, inv)
+    S = np.zeros((P, P)) if cd is None else _host(cd).copy()
+    keep = np.ones((P, P), dtype=bool) if mates is None else np.asarray(_host(mates) != 0)
+    if S.shape != (P, P) or keep.shape != (P, P):
+        raise ValueError(f"truth_table expects cd[P,P] and mates[P,P] with P = {P}; got {S.shape}, {keep.shape}")
+    S[~keep] = np.inf
+    S[np.arange(P), np.arange(P)] = np.inf
+    return T, S
+
+
+def evaluate(G, placed, pose, rest, root, edges=None, mates=None, tol=0.01):
+    """The score of an assembly against the truth, on the host in float64.  G [P,4,4] maps moved piece p into the frame of moved
+    piece `root`; placed [P] bool; pose [P,4,4] and rest [P,n,3] are datapipe.fracture's of one sample.  The truth for piece p
+    is G*[p] = pose[root] inv(pose[p]).  -> Evaluation:
+      rot_deg [P]      the geodesic angle between the rotations of G[p] and G*[p], degrees
+      trans [P]        |t - t*|
+      msd [P]          the mean over the piece's points x = pose[p] rest[p] of |G[p] x - G*[p] x|^2
+      part_ok [P]      placed & (msd < tol); tol is a definition (a squared distance in the cloud's units), not a measurement
+      part_accuracy    the share of the pieces other than root with part_ok
+      edge_precision   the share of `edges` (tuples that begin with the two pieces joined) whose pair is in mates [P,P]; None
+                       without both or without an edge
+    It takes assemble's Assembly as evaluate(a.G, a.placed, pose, rest, a.root, a.edges, mates).  For a Progressive it takes
+    one part: G and placed limited to that part's members, root the piece whose frame the part lives in (MergeLedger.frame)."""
+    G, X, R = _host(G), _host(pose), _host(rest)
+    P = X.shape[0]
+    placed = np.asarray(placed.detach().cpu().numpy() if isinstance(placed, torch.Tensor) else placed).astype(bool)
+    root = int(root)
+    if G.shape != (P, 4, 4) or X.shape != (P, 4, 4) or R.ndim != 3 or R.shape[0] != P or R.shape[2] != 3 or placed.shape != (P,) \
+            or not 0 <= root < P:
+        raise ValueError(f"evaluate expects G[P,4,4], placed[P], pose[P,4,4], rest[P,n,3], 0 <= root < P; got {G.shape}, "
+                         f"{placed.shape}, {X.shape}, {R.shape}, root = {root}")
+    rot_deg, trans, msd = np.zeros(P), np.zeros(P), np.zeros(P)
+    for p in range(P):
+        Gt = X[root] @ _rigid_inv(X[p])
+        D = G[p, :3, :3] @ Gt[:3, :3].T
+        # the angle from both the trace and the skew part: atan2 keeps its precision at 0 and at 180 degrees
+        skew = np.array([D[2, 1] - D[1, 2], D[0, 2] - D[2, 0], D[1, 0] - D[0, 1]])
+        rot_deg[p] = np.degrees(np.arctan2(np.linalg.norm(skew), np.trace(D) - 1.0))
+        trans[p] = np.linalg.norm(G[p, :3, 3] - Gt[:3, 3])
+        x = R[p] @ X[p, :3, :3].T + X[p, :3, 3]
+        d = x @ (G[p, :3, :3] - Gt[:3, :3]).T + (G[p, :3, 3] - Gt[:3, 3])
+        msd[p] = (d * d).sum(1).mean()
+    part_ok = placed & (msd < tol)
+    others = np.arange(P) != root
+    part_accuracy = float(part_ok[others].mean()) if others.any() else 1.0
+    edge_precision = None
+    if edges is not None and mates is not None and len(edges) > 0:
+        m = np.asarray(_host(mates) != 0)
+        edge_precision = float(np.mean([bool(m[int(e[0]), int(e[1])]) for e in edges]))
+    return Evaluation(rot_deg, trans, msd, part_ok, part_accuracy, edge_precision)
+
+
 # --------------------------------------------------------------------------- progressive assembly
 
 def _choose(score, max_score=None):

@@ -56,6 +56,7 @@ SOURCES = [
     ("datapipe.hip", ["-ffp-contract=off"] + NOSLP),
     ("solidcut.hip", ["-ffp-contract=off"] + NOSLP),
     ("doublecut.hip", ["-ffp-contract=off"] + NOSLP),
+    ("fracture.hip", ["-ffp-contract=off"] + NOSLP),
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-fvisibility=hidden",
           "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function"]

@@ -1,0 +1,227 @@
+// fracture.hip — a cloud cut into P pieces with ground truth, one launch per batch (no counterpart in the reference, which
+// ships pairs only; the multi-piece assembly of assembly.py is what consumes it).
+//
+// One workgroup per sample runs datapipe.fracture_rule (the numpy statement of this kernel): all points start with label 0;
+// step s = 1 .. P-1 cuts the TARGET, the label with the most points so far (ties: the lowest), by the first of K candidate
+// planes that leaves >= n_min target points on both sides (none: the most balanced one, the first among equals, ok = 0); the
+// up side keeps the target's label, the down side becomes s.  A candidate plane goes through an ANCHOR, the target's r-th
+// point in the cloud's order (r from a uniform draw): a plane drawn around the origin need not meet a sub-piece, one through
+// a point of it always does, and the offset -((x n0 + y n1) + z n2) of one point is reproducible to the bit where a centroid
+// would depend on the order of a sum.  The side test is the plane cut's (float64, every operation individually rounded, no
+// fma), so the anchor evaluates to exactly 0 and is on the up side.
+//
+// A thread owns a contiguous run of <= 64 points (M <= 65536) as the other cut kernels do and is the only one that reads or
+// writes its run's labels, which live in LDS, one byte per point (a register array indexed by a run-time j would go to
+// scratch); the per-label counts are registers that every thread holds alike (the sums come from block_sum), so every branch
+// on them is uniform.  Per step: the run's target members as one bit mask, ONE exclusive scan of their counts for all K anchor
+// ranks (the thread whose run holds rank r_k writes that point to a small LDS table, FR_KC candidates at a time), then one
+// pass over the members and a block_sum per candidate.  The P-way stable partition at the end is doublecut.hip's wave scan
+// and seg_base pattern, once per label; the same pass writes `order`, the first one `label`.  Side test, workgroup sum, start
+// index and padding come from pzn_cut.h.
+#include "pzn_common.h"
+
+namespace {
+
+#include "pzn_cut.h"
+
+constexpr int FR_MAX_P = 16;         // pieces per sample
+constexpr int FR_MAX_M = 65536;      // points per sample: runs of <= 64 points, one membership mask per thread
+constexpr int FR_KC = 16;            // anchors held in LDS at a time
+// the dynamic LDS region: every table at a multiple of 16 bytes, the labels last
+constexpr int FR_SLOTS = 0, FR_WBASE = FR_SLOTS + CUT_W * 4, FR_SBASE = FR_WBASE + CUT_W * 4;
+constexpr int FR_ANCHOR = FR_SBASE + ((CUT_W + 1) * 4 + 15) / 16 * 16, FR_LABELS = FR_ANCHOR + FR_KC * 4 * 4;
+
+struct FractureArgs {
+  const float* raw;          // [B, M, 3]
+  const double* normals;     // [B, P-1, K, 3]
+  const double* u_anchor;    // [B, P-1, K]
+  const double* u_start;     // [B, P]
+  int B, M, P, K, n_min, cap;
+  float* pieces;             // [P B, cap, 3]: piece p of sample b at row p B + b
+  int64_t* counts;           // [P B]
+  int64_t* start;            // [P B]
+  uint8_t* label;            // [B, M]
+  int32_t* order;            // [B, M]
+  double* planes;            // [B, P-1, 4]
+  int32_t* target;           // [B, P-1]
+  int32_t* cand;             // [B, P-1]
+  uint8_t* ok;               // [B]
+};
+
+// exclusive scan of one int per thread over the workgroup in thread order (three barriers); the total in slots[0]
+__device__ __forceinline__ int block_excl_scan(int c, int* slots, int* wave_base) {
+  const int lane = threadIdx.x & (PZN_WAVE - 1), wave = threadIdx.x / PZN_WAVE;
+  int incl = c;
+  for (int d = 1; d < PZN_WAVE; d <<= 1) {
+    const int o = __shfl_up(incl, d, PZN_WAVE);
+    if (lane >= d) incl += o;
+  }
+  __syncthreads();          // (the tables may still be read from the call before)
+  if (lane == PZN_WAVE - 1) slots[wave] = incl;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int run = 0;
+    for (int w = 0; w < CUT_W; ++w) wave_base[w] = run, run += slots[w];
+    slots[0] = run;
+  }
+  __syncthreads();
+  return wave_base[wave] + incl - c;
+}
+
+__global__ __launch_bounds__(CUT_T) void fracture_kernel(FractureArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  int* slots = reinterpret_cast<int*>(smem + FR_SLOTS);
+  int* wave_base = reinterpret_cast<int*>(smem + FR_WBASE);
+  int* seg_base = reinterpret_cast<int*>(smem + FR_SBASE);      // [CUT_W + 1]
+  float* anchor = reinterpret_cast<float*>(smem + FR_ANCHOR);   // [FR_KC][4]
+  uint8_t* lab = smem + FR_LABELS;                              // [M]
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (PZN_WAVE - 1), wave = tid / PZN_WAVE;
+  const int M = a.M, P = a.P, K = a.K;
+  const float* g = a.raw + (size_t)b * M * 3;
+  // a thread owns a CONTIGUOUS run of points, so that a partition keeps the original order with one scan over threads
+  const int chunk = (M + CUT_T - 1) / CUT_T;      // <= 64
+  const int lo = tid * chunk < M ? tid * chunk : M, hi = lo + chunk < M ? lo + chunk : M;
+  for (int j = lo; j < hi; ++j) lab[j] = 0;
+
+  int cnt[FR_MAX_P];          // points per label: the same in every thread; only ever indexed by unrolled loops (registers)
+#pragma unroll
+  for (int p = 0; p < FR_MAX_P; ++p) cnt[p] = p == 0 ? M : 0;
+  bool all_valid = true;
+
+  for (int s = 1; s < P; ++s) {
+    // 1. the target: the first largest label among 0 .. s-1
+    int t = 0, n_t = cnt[0];
+#pragma unroll
+    for (int p = 1; p < FR_MAX_P; ++p)
+      if (p < s && cnt[p] > n_t) t = p, n_t = cnt[p];
+    uint64_t tbits = 0;      // the run's members of the target
+    for (int j = lo; j < hi; ++j) tbits |= (uint64_t)(lab[j] == t ? 1 : 0) << (j - lo);
+    const int c_t = __popcll(tbits);
+    const int before = block_excl_scan(c_t, slots, wave_base);      // target members in front of this run
+
+    const double* nrm = a.normals + ((size_t)b * (P - 1) + (s - 1)) * K * 3;
+    const double* ua = a.u_anchor + ((size_t)b * (P - 1) + (s - 1)) * K;
+    int chosen = -1, best_k = 0, best_bal = -1, best_up = 0;
+    uint64_t sel = 0;        // the run's target members on the DOWN side of the candidate that is taken
+    Plane taken{0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < K && chosen < 0; k0 += FR_KC) {
+      // 2. the anchors of candidates k0 .. k0 + FR_KC - 1 (the table's readers of the chunk before are behind block_sum's barriers)
+      const int kn = K - k0 < FR_KC ? K - k0 : FR_KC;
+      for (int kk = 0; kk < kn; ++kk) {
+        const int r = (int)start_index(ua[k0 + kk], n_t) - before;      // (n_t >= 1: the target is a largest label)
+        if (r >= 0 && r < c_t) {
+          uint64_t m = tbits;
+          for (int i = 0; i < r; ++i) m &= m - 1;
+          const int j = lo + __ffsll((unsigned long long)m) - 1;
+          anchor[4 * kk] = g[3 * j], anchor[4 * kk + 1] = g[3 * j + 1], anchor[4 * kk + 2] = g[3 * j + 2];
+        }
+      }
+      __syncthreads();
+      for (int kk = 0; kk < kn; ++kk) {
+        const int k = k0 + kk;
+        // 3. the plane through the anchor: the anchor itself evaluates to d + (-d) = 0
+        const double n0 = nrm[3 * k], n1 = nrm[3 * k + 1], n2 = nrm[3 * k + 2];
+        const double ax = (double)anchor[4 * kk], ay = (double)anchor[4 * kk + 1], az = (double)anchor[4 * kk + 2];
+        const Plane q{n0, n1, n2, -__dadd_rn(__dadd_rn(__dmul_rn(ax, n0), __dmul_rn(ay, n1)), __dmul_rn(az, n2))};
+        int c = 0;
+        uint64_t down = 0;
+        for (uint64_t m = tbits; m != 0; m &= m - 1) {
+          const int i = __ffsll((unsigned long long)m) - 1, j = lo + i;
+          const bool up = is_up(g[3 * j], g[3 * j + 1], g[3 * j + 2], q);
+          c += up ? 1 : 0;
+          down |= (uint64_t)(up ? 0 : 1) << i;
+        }
+        // 4. the first valid candidate, else the most balanced one (uniform: every thread holds the same sum)
+        const int up = block_sum(c, slots);
+        const int bal = up < n_t - up ? up : n_t - up;
+        const bool valid = up >= a.n_min && n_t - up >= a.n_min;
+        if (bal > best_bal || valid) sel = down, taken = q, best_up = up;
+        if (bal > best_bal) best_bal = bal, best_k = k;
+        if (valid) {
+          chosen = k;
+          break;
+        }
+      }
+    }
+    all_valid = all_valid && chosen >= 0;
+    if (chosen < 0) chosen = best_k;
+    // 5. the down side becomes label s
+    for (uint64_t m = sel; m != 0; m &= m - 1) lab[lo + __ffsll((unsigned long long)m) - 1] = (uint8_t)s;
+#pragma unroll
+    for (int p = 0; p < FR_MAX_P; ++p) {
+      if (p == t) cnt[p] = best_up;
+      if (p == s) cnt[p] = n_t - best_up;
+    }
+    if (tid == 0) {
+      double* pl = a.planes + ((size_t)b * (P - 1) + (s - 1)) * 4;
+      pl[0] = taken.n0, pl[1] = taken.n1, pl[2] = taken.n2, pl[3] = taken.off;
+      a.target[(size_t)b * (P - 1) + (s - 1)] = t;
+      a.cand[(size_t)b * (P - 1) + (s - 1)] = chosen;
+    }
+  }
+
+  // the pieces: a stable P-way partition, one scan per label; `order` is the same partition without the cap
+  for (int j = lo; j < hi; ++j) a.label[(size_t)b * M + j] = lab[j];
+  int32_t* ord = a.order + (size_t)b * M;
+  const double* us = a.u_start + (size_t)b * P;
+  bool fits = true;
+  int off = 0;               // rows of the labels in front
+  for (int p = 0; p < P; ++p) {
+    float* dst = a.pieces + ((size_t)p * a.B + b) * a.cap * 3;
+    int c = 0;
+    for (int j = lo; j < hi; ++j) c += lab[j] == p ? 1 : 0;
+    int incl = c;
+    for (int d = 1; d < PZN_WAVE; d <<= 1) {
+      const int o = __shfl_up(incl, d, PZN_WAVE);
+      if (lane >= d) incl += o;
+    }
+    __syncthreads();         // (the tables may still be read for the piece before)
+    if (lane == PZN_WAVE - 1) slots[wave] = incl;
+    __syncthreads();
+    if (tid == 0) {
+      int run = 0;
+      for (int w = 0; w < CUT_W; ++w) seg_base[w] = run, run += slots[w];
+      seg_base[CUT_W] = run;      // total
+    }
+    __syncthreads();
+    const int n_p = seg_base[CUT_W];      // == cnt[p]
+    int at = seg_base[wave] + incl - c;   // rows of label p in front of this run
+    for (int j = lo; j < hi; ++j) {
+      if (lab[j] != p) continue;
+      if (at < a.cap) dst[(size_t)at * 3] = g[3 * j], dst[(size_t)at * 3 + 1] = g[3 * j + 1], dst[(size_t)at * 3 + 2] = g[3 * j + 2];
+      ord[off + at] = j;
+      ++at;
+    }
+    __syncthreads();         // the piece's first row is in memory for this workgroup
+    pad_piece(dst, n_p, a.cap, g);
+    fits = fits && n_p <= a.cap;
+    if (tid == 0) {
+      a.counts[(size_t)p * a.B + b] = n_p;
+      a.start[(size_t)p * a.B + b] = start_index(us[p], n_p);
+    }
+    off += n_p;
+  }
+  if (tid == 0) a.ok[b] = (all_valid && fits) ? 1 : 0;
+}
+
+}  // namespace
+
+PZN_EXPORT int pzn_fracture_supported(int M, int P, int K) {
+  return (M >= 1 && M <= FR_MAX_M && P >= 2 && P <= FR_MAX_P && K >= 1) ? 1 : 0;
+}
+
+PZN_EXPORT int pzn_fracture_f32(const float* raw, const double* normals, const double* u_anchor, const double* u_start, int B,
+                                int M, int P, int K, int n_min, int cap, float* pieces, int64_t* counts, int64_t* start,
+                                uint8_t* label, int32_t* order, double* planes, int32_t* target, int32_t* cand, uint8_t* ok,
+                                pzn_stream_t stream) {
+  PZN_CHECK_ARG(raw && normals && u_anchor && u_start && pieces && counts && start && label && order && planes && target && cand && ok);
+  PZN_CHECK_ARG(B > 0 && cap > 0 && n_min >= 0);
+  if (!pzn_fracture_supported(M, P, K)) return PZN_EUNSUPPORTED;
+  FractureArgs a{raw, normals, u_anchor, u_start, B, M, P, K, n_min, cap, pieces, counts, start, label, order, planes, target, cand, ok};
+  const size_t lds = (size_t)FR_LABELS + ((size_t)M + 15) / 16 * 16;      // <= 64.5 KiB
+  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(fracture_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return PZN_ELAUNCH;
+  PZN_LAUNCH(fracture_kernel, dim3(B), dim3(CUT_T), lds, pzn_hip_stream(stream), a);
+  PZN_RETURN_LAUNCH_STATUS();
+}

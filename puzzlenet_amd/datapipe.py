@@ -693,6 +693,162 @@ def double_cut_rule(raw, planes1, planes2, u, n=1024, n_rich=3000, cap=None):
                 pieces=pieces, counts=counts, start=start, ok=bool(ok and counts.max() <= cap))
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Fracture: a cloud cut into P pieces with known answers (no counterpart in the reference, which ships pairs only) - the input
+# of assembly.py's multi-piece walks and, with assembly.evaluate, their score.
+
+def _start_index(u, cnt):
+    """start_index of csrc/pzn_cut.h: floor(u cnt) held to [0, cnt - 1] (0 for an empty piece)."""
+    return max(0, min(int(cnt) - 1, int(np.floor(np.float64(u) * np.float64(cnt)))))
+
+
+def _pad_rows(rows, cap, first_of_cloud):
+    """pad_piece of csrc/pzn_cut.h: the first `cap` rows of a piece, rows beyond its count copies of its first row (of the
+    cloud's first row when it is empty).  -> [cap,3] float32"""
+    keep = rows[:cap]
+    fill = rows[0] if len(rows) else first_of_cloud
+    return np.concatenate([keep, np.broadcast_to(fill, (cap - len(keep), 3))], axis=0).astype(np.float32)
+
+
+def fracture_rule(raw, normals, u_anchor, u_start, P, n_min, cap=None):
+    """The fracture of ONE sample, in numpy on the host: the statement that pzn_fracture_f32 (csrc/fracture.hip) implements and
+    the tests hold it to, bit for bit.
+      raw       [M,3] float32
+      normals   [P-1,K,3] float64: unit vectors, K candidates per cut
+      u_anchor  [P-1,K] float64 uniforms in [0,1): which point of the target a candidate plane goes through
+      u_start   [P] float64 uniforms in [0,1): the FPS start of every piece
+      n_min     points both sides of a cut must hold;  cap: rows a piece may hold (None: M)
+    All points start with label 0.  Step s = 1 .. P-1:
+      1. the target t is the label with the most points among 0 .. s-1 (ties: the lowest label);
+      2. candidate k is the plane with normal normals[s-1,k] through the ANCHOR, the r-th point of the target in the cloud's
+         order, r = start_index(u_anchor[s-1,k], count[t]) (a plane through one of the target's own points always meets it);
+      3. its offset is -((x n0 + y n1) + z n2) of the anchor, float64, every operation rounded on its own, and the side test
+         is _side64's expression: the anchor itself evaluates to exactly 0 and is on the up side;
+      4. the FIRST candidate that leaves >= n_min target points on both sides is taken; none: the most balanced one, the first
+         among equals (the single cut's rule);
+      5. the up side keeps label t, the down side becomes label s.
+    -> dict(label [M] uint8, counts [P] int64, pieces: P arrays [cap,3] (the rows of a label in the cloud's order, padded as
+       pad_piece does; an empty piece is the cloud's first row throughout), order [M] int32 (the cloud row of every position of
+       the concatenated pieces = the stable argsort of label), start [P] int64 = start_index(u_start[p], counts[p]),
+       planes [P-1,4] float64, target [P-1] int32, cand [P-1] int32, ok: every step had a valid candidate and every count <= cap)"""
+    raw = np.asarray(raw, dtype=np.float32)
+    normals, u_anchor, u_start = (np.asarray(t, dtype=np.float64) for t in (normals, u_anchor, u_start))
+    M, P = raw.shape[0], int(P)
+    K = normals.shape[1]
+    cap = M if cap is None else int(cap)
+    p64 = raw.astype(np.float64)
+    label = np.zeros(M, dtype=np.uint8)
+    planes = np.zeros((P - 1, 4), dtype=np.float64)
+    target, cand = np.zeros(P - 1, dtype=np.int32), np.zeros(P - 1, dtype=np.int32)
+    ok = True
+    for s in range(1, P):
+        count = np.bincount(label, minlength=P)
+        t = int(np.argmax(count[:s]))                                 # (argmax: the first among equals)
+        members = np.flatnonzero(label == t)
+        n_t = len(members)
+        best = None
+        for k in range(K):
+            n = normals[s - 1, k]
+            a = p64[members[_start_index(u_anchor[s - 1, k], n_t)]]
+            plane = np.array([n[0], n[1], n[2], -((a[0] * n[0] + a[1] * n[1]) + a[2] * n[2])])
+            up = _side64(raw[members], plane)
+            n_up = int(up.sum())
+            valid = n_up >= n_min and n_t - n_up >= n_min
+            if valid or best is None or min(n_up, n_t - n_up) > best[0]:
+                best = (min(n_up, n_t - n_up), k, plane, up)
+            if valid:
+                break
+        else:
+            ok = False
+        _, cand[s - 1], planes[s - 1], up = best
+        target[s - 1] = t
+        label[members[~up]] = s
+    counts = np.bincount(label, minlength=P).astype(np.int64)
+    order = np.argsort(label, kind="stable").astype(np.int32)
+    pieces = [_pad_rows(raw[label == p], cap, raw[0]) for p in range(P)]
+    start = np.array([_start_index(u_start[p], counts[p]) for p in range(P)], dtype=np.int64)
+    return dict(label=label, counts=counts, pieces=pieces, order=order, start=start, planes=planes, target=target, cand=cand,
+                ok=bool(ok and counts.max() <= cap))
+
+
+Fracture = collections.namedtuple("Fracture", "pieces pose rest src top cd mates ok label planes target cand counts")
+Fracture.__doc__ = """A K-piece sample with its answers (datapipe.fracture): pieces [B,P,n,3] the moved pieces (the model's input, [P,n,3]
+per sample as assembly.match_pairs takes them), pose [B,P,4,4] the motion of every piece (pieces = pose rest), rest [B,P,n,3]
+the pieces where they belong, src [B,P,n] int64 the cloud row of every sampled point, top [B,P,P,k] int64 the k rows of piece a
+nearest to piece b, cd [B,P,P] float32 the chamfer distance of the two picked boundaries, mates [B,P,P] bool the pieces that
+touch, ok [B] bool, and the kernel's label [B,M] uint8, planes [B,P-1,4] float64, target / cand [B,P-1] int32 and counts [B,P]
+int64."""
+
+
+def fracture(raw, normals, u_anchor, u_start, twist, n=1024, n_min=None, k=128, cap=None):
+    """A batch of P-piece samples with ground truth: every cloud cut into P pieces in one launch (ops.fracture, csrc/fracture.hip;
+    the rule: fracture_rule), every piece sampled to n points and moved, and which pieces touch.  raw [B,M,3] f32 on the GPU;
+    normals [B,P-1,K,3], u_anchor [B,P-1,K], u_start [B,P] float64 draws (draw_fracture_batch); twist [B,P,6]; n_min: points both
+    sides of a cut must hold (None: n).  Nothing here reads a value back to the host.  -> Fracture:
+      rest    the cut's P B compacted pieces sampled by the feeder's FPS from the kernel's start indices (no promise about the
+              piece sizes is made to it: without a valid cut a piece may hold the whole cloud)
+      src     order[offset of piece p + FPS index]: raw[b, src[b,p,i]] == rest[b,p,i] bit for bit (ok samples)
+      pose    se3.exp(twist);  pieces = se3.transform_points(pose, rest)
+      top     top[b,a,c] = ops.topk_rows of minus the second output of ops.chamfer(rest[b,a], rest[b,c]): the k rows of piece a
+              nearest to piece c (the diagonal: a piece against itself)
+      cd      mean + mean of ops.chamfer(rest[b,a][top[b,a,c]], rest[b,c][top[b,c,a]]) - what cut_pairs_double calls cd
+      mates   cd <= CD_ACCEPT (the reference's 0.015, dataset.py:1255), False on the diagonal
+      ok      the kernel's ok (a valid candidate at every step, every piece within cap) and every piece holds >= n points"""
+    cap = _feeder_cap("fracture", raw, cap)
+    n, k = int(n), int(k)
+    n_min = n if n_min is None else int(n_min)
+    B, M, P = raw.shape[0], raw.shape[1], u_start.shape[-1]
+    if not isinstance(twist, torch.Tensor) or not twist.is_cuda or tuple(twist.shape) != (B, P, 6):
+        raise _lib.PznError(f"fracture: twist as [B, P, 6] = [{B}, {P}, 6] on the GPU; got {tuple(twist.shape)}")
+    packed, counts, start, label, order, planes, target, cand, ok = ops.fracture(raw, normals, u_anchor, u_start, n_min, cap)
+    idx = ops.farthest_point_sample(packed, n, start, background=True, counts=counts, max_count=0)      # [P B,n]
+    rest = ops.index_points(packed, idx).view(P, B, n, 3).transpose(0, 1).contiguous()               # dataset.py:1147-1163
+    cnt = counts.view(P, B)
+    at = (cnt.cumsum(0) - cnt).view(P * B, 1) + idx                    # position in the concatenated pieces
+    src = torch.gather(order.to(torch.int64).repeat(P, 1), 1, at.clamp_(max=M - 1)).view(P, B, n).transpose(0, 1).contiguous()
+    pose = se3.exp(twist.to(torch.float32).contiguous())                                                # [B,P,4,4]
+    moved = se3.transform_points(pose.view(B * P, 4, 4), rest.view(B * P, n, 3)).view(B, P, n, 3)
+    # boundaries: every ordered pair (a, c) of a sample is one chamfer problem (ops.chamfer splits more than it takes at once)
+    A = rest.view(B, P, 1, n, 3).expand(B, P, P, n, 3).reshape(B * P * P, n, 3)
+    C = rest.view(B, 1, P, n, 3).expand(B, P, P, n, 3).reshape(B * P * P, n, 3)
+    _, d_a = ops.chamfer(A, C)
+    top = ops.topk_rows(d_a.neg_(), k)                                                               # [B P P,k]
+    bnd = ops.index_points(A, top).view(B, P, P, k, 3)
+    cd1, cd2 = ops.chamfer(bnd.reshape(B * P * P, k, 3), bnd.transpose(1, 2).reshape(B * P * P, k, 3))
+    cd = (cd1.mean(1) + cd2.mean(1)).view(B, P, P)
+    mates = (cd <= CD_ACCEPT) & ~torch.eye(P, dtype=torch.bool, device=raw.device)
+    return Fracture(moved, pose, rest, src, top.view(B, P, P, k), cd, mates, ok & (cnt >= n).all(0), label, planes, target, cand,
+                    cnt.t().contiguous())
+
+
+def _fracture_cols(P, K):       # normals, anchor draws, start fractions, twists
+    return _cols(3 * (P - 1) * K, (P - 1) * K, P, 6 * P)
+
+
+def draw_fracture_batch(rng, gen, B, P, K, mag, out):
+    """The host draws of one fracture batch into out [B, width] float64 (columns: _fracture_cols(P, K)): candidate normals
+    randn(3) normalised, the anchor and start uniforms from rng, one twist per piece from gen."""
+    normals, u_anchor, u_start, tw = _fracture_cols(P, K)
+    v = rng.randn(B, (P - 1) * K, 3)
+    out[:, normals] = (v / np.linalg.norm(v, axis=2, keepdims=True)).reshape(B, -1)
+    out[:, u_anchor] = rng.rand(B, (P - 1) * K)
+    out[:, u_start] = rng.rand(B, P)
+    twist = np.empty((B * P, 6), dtype=np.float64)
+    _draw_twist(gen, mag, twist)
+    out[:, tw] = twist.reshape(B, 6 * P)
+
+
+def fracture_draws(rng, gen, B, P, K, mag):
+    """draw_fracture_batch into a fresh row, split: -> (normals [B,P-1,K,3], u_anchor [B,P-1,K], u_start [B,P], twist [B,P,6]),
+    float64 numpy arrays."""
+    cols = _fracture_cols(P, K)
+    out = np.empty((B, cols[-1].stop), dtype=np.float64)
+    draw_fracture_batch(rng, gen, B, P, K, mag, out)
+    normals, u_anchor, u_start, tw = cols
+    return (out[:, normals].reshape(B, P - 1, K, 3), out[:, u_anchor].reshape(B, P - 1, K), out[:, u_start].copy(),
+            out[:, tw].reshape(B, P, 6))
+
+
 def _plane_draw():
     return np.random.rand(3, 1), np.random.rand(1) / 3          # dataset.py:767-769 (z=None)
 

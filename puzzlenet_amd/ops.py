@@ -583,6 +583,52 @@ def cut_compact_double(raw, normals1, zs1, normals2, zs2, u, n_min, n_rich, cap)
     return pieces, counts, start, kind, planes, tabs, ok.to(torch.bool)
 
 
+def fracture_supported(M, P, K):
+    return bool(_lib.load().pzn_fracture_supported(int(M), int(P), int(K)))
+
+
+def fracture(raw, normals, u_anchor, u_start, n_min, cap):
+    """Every cloud of a batch cut into P pieces in one launch (pzn_fracture_f32; the rule: datapipe.fracture_rule): raw [B,M,3]
+    f32; K candidate normals per cut (normals [B,P-1,K,3]), their anchor draws (u_anchor [B,P-1,K]) and the start fractions
+    (u_start [B,P]), all float64 (no silent conversion: PznError)
+    -> (pieces [P B,cap,3]: piece p of sample b at row p B + b; counts [P B] int64; start [P B] int64; label [B,M] uint8;
+        order [B,M] int32; planes [B,P-1,4] float64; target [B,P-1] int32; cand [B,P-1] int32; ok [B] bool)
+    2 <= P <= 16, K >= 1, M <= 65536 (PznUnsupported beyond).  Nothing waits for the device."""
+    for name, t, dt in (("raw", raw, torch.float32), ("normals", normals, torch.float64), ("u_anchor", u_anchor, torch.float64),
+                        ("u_start", u_start, torch.float64)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.PznError(f"fracture: {name} must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
+        if t.dtype != dt:
+            raise _lib.PznError(f"fracture: {name} must be {dt}; got {t.dtype}")
+    if raw.dim() != 3 or raw.shape[2] != 3 or raw.shape[0] == 0 or raw.shape[1] == 0:
+        raise _lib.PznError(f"fracture: raw as [B, M, 3]; got {tuple(raw.shape)}")
+    B, M, _ = raw.shape
+    if u_start.dim() != 2 or u_start.shape[0] != B:
+        raise _lib.PznError(f"fracture: u_start as [B, P]; got {tuple(u_start.shape)}")
+    P = u_start.shape[1]
+    K = normals.shape[2] if normals.dim() == 4 else 0
+    if not fracture_supported(M, P, max(K, 1)):
+        raise _lib.PznUnsupported(f"fracture: M = {M} points into P = {P} pieces (2 <= P <= 16, M <= 65536)")
+    if normals.dim() != 4 or tuple(normals.shape) != (B, P - 1, K, 3) or K < 1 or tuple(u_anchor.shape) != (B, P - 1, K):
+        raise _lib.PznError(f"fracture: normals as [B, P - 1, K, 3] and u_anchor as [B, P - 1, K] with P = {P}, K >= 1; got "
+                            f"{tuple(normals.shape)}, {tuple(u_anchor.shape)}")
+    cap, n_min = int(cap), int(n_min)
+    if cap < 1 or n_min < 0:
+        raise _lib.PznError(f"fracture: cap = {cap}, n_min = {n_min}")
+    raw, normals, u_anchor, u_start = raw.contiguous(), normals.contiguous(), u_anchor.contiguous(), u_start.contiguous()
+    dev = raw.device
+    pieces, counts, start, ok = _cut_outputs(raw, P, cap)
+    label = torch.empty((B, M), dtype=torch.uint8, device=dev)
+    order = torch.empty((B, M), dtype=torch.int32, device=dev)
+    planes = torch.empty((B, P - 1, 4), dtype=torch.float64, device=dev)
+    target = torch.empty((B, P - 1), dtype=torch.int32, device=dev)
+    cand = torch.empty((B, P - 1), dtype=torch.int32, device=dev)
+    with _on(dev):
+        _call("pzn_fracture_f32", _p(raw), _p(normals), _p(u_anchor), _p(u_start), B, M, P, K, n_min, cap, _p(pieces),
+              _p(counts), _p(start), _p(label), _p(order), _p(planes), _p(target), _p(cand), _p(ok), _stream())
+    return pieces, counts, start, label, order, planes, target, cand, ok.to(torch.bool)
+
+
 def pick_mask(idx, N):
     """0/1 float masks [R,N] with ones at idx [R,k] (dataset.py:1363-1366), one launch."""
     idx = _i64(idx, "idx")

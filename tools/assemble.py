@@ -2,7 +2,7 @@
 assembled cloud.
 
     python tools/assemble.py --pieces pieces.npy [--ckpt model.ckpt] [--k 128] [--max-score S] [--out PREFIX] [--progressive]
-                             [--refine N]
+                             [--refine N] [--gt PREFIX_gt.npz]
 
 pieces.npy holds [K, N, 3] float32 (N = the model's points per piece).  Prints the score table and the edges in
 placement order, writes PREFIX_G.npy ([K,4,4], each piece into the root's frame) and PREFIX_cloud.npy ([K,N,3]).
@@ -11,6 +11,9 @@ points and matched again -; PREFIX_G.npy then maps each piece into the frame of 
 is the [N,3] part around the first pair, PREFIX_piece_id.npy / PREFIX_row_id.npy say where each of its points came from.
 --refine N: every pair pose is refined on its picked boundary points before it is used (assembly.refine_pairs: symmetric
 point-to-point ICP, at most N accepted steps, one launch per table or per round); 0, the default, uses the network's poses.
+--gt PREFIX_gt.npz (written by tools/fracture.py beside the pieces): the assembly is scored against the truth - per piece the
+rotation error in degrees, the translation error and the mean squared distance of its points from where they belong, the share
+of pieces placed right (assembly.evaluate) and, for the greedy walk, the share of its edges between pieces that touch.
 Needs a GPU; there is no CPU path."""
 import argparse
 import os
@@ -20,6 +23,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import numpy as np
 import torch
+
+
+def report(ev):
+    """assembly.evaluate's fields, one line per piece."""
+    for p in range(len(ev.msd)):
+        print(f"  piece {p}: rot {ev.rot_deg[p]:9.4f} deg, trans {ev.trans[p]:.6f}, msd {ev.msd[p]:.3e}, "
+              f"{'ok' if ev.part_ok[p] else 'NOT ok'}")
+    print(f"part accuracy {ev.part_accuracy:.3f}" + ("" if ev.edge_precision is None else f", edge precision {ev.edge_precision:.3f}"))
 
 
 def main():
@@ -33,6 +44,7 @@ def main():
     ap.add_argument("--progressive", action="store_true", help="merge placed parts, resample and match again after every placement")
     ap.add_argument("--keep-matched", action="store_true", help="--progressive: keep the matched boundary points in the merged part")
     ap.add_argument("--refine", type=int, default=0, help="ICP steps at most per pair pose on the picked boundary points (0: none)")
+    ap.add_argument("--gt", default=None, help="PREFIX_gt.npz of tools/fracture.py: score the assembly against the truth")
     args = ap.parse_args()
     if args.refine < 0:
         sys.exit("--refine: 0 or a number of steps")
@@ -57,9 +69,13 @@ def main():
     model.fps_generator = torch.Generator().manual_seed(args.seed)
 
     x = torch.from_numpy(np.ascontiguousarray(pieces, dtype=np.float32)).to(dev)
+    gt = np.load(args.gt) if args.gt else None
+    if gt is not None and gt["pose"].shape != (K, 4, 4):
+        sys.exit(f"{args.gt}: the truth of {gt['pose'].shape[0]} pieces, {args.pieces} holds {K}")
     if args.progressive:
-        res = assembly.assemble_progressive(model, x, k=args.k, max_score=args.max_score, drop_matched=not args.keep_matched,
-                                            generator=torch.Generator().manual_seed(args.seed), refine=args.refine)
+        pa = assembly.ProgressiveAssembler(model, x, k=args.k, max_score=args.max_score, drop_matched=not args.keep_matched,
+                                           generator=torch.Generator().manual_seed(args.seed), refine=args.refine)
+        res = pa.run()
         for a, b, s, _da, _db in res.edges:
             print(f"  merge: part of piece {b} into part of piece {a}, score {s:.6f}")
         left = [k for k in range(K) if not res.placed[k]]
@@ -69,6 +85,11 @@ def main():
         for name, t in (("cloud", res.cloud), ("piece_id", res.piece_id), ("row_id", res.row_id)):
             np.save(f"{args.out}_{name}.npy", t.cpu().numpy())
         print(f"wrote {args.out}_G.npy, {args.out}_cloud.npy, {args.out}_piece_id.npy, {args.out}_row_id.npy")
+        if gt is not None and res.placed.any():
+            part = next(q for q, mem in enumerate(pa.members) if int(np.flatnonzero(res.placed)[0]) in mem)
+            root = pa.ledger.frame[part]
+            print(f"against {args.gt} (the part around the first pair, in piece {root}'s frame):")
+            report(assembly.evaluate(res.G, res.placed, gt["pose"], gt["rest"], root))
         return
     table = assembly.match_pairs(model, x, k=args.k, refine=args.refine)
     result = assembly.assemble(table.score, table.T, max_score=args.max_score)
@@ -86,6 +107,9 @@ def main():
     np.save(args.out + "_G.npy", result.G)
     np.save(args.out + "_cloud.npy", assembly.apply(x, result.G).cpu().numpy())
     print(f"wrote {args.out}_G.npy, {args.out}_cloud.npy")
+    if gt is not None:
+        print(f"against {args.gt} (in the root's frame):")
+        report(assembly.evaluate(result.G, result.placed, gt["pose"], gt["rest"], result.root, result.edges, gt["mates"]))
 
 
 if __name__ == "__main__":

@@ -2,13 +2,17 @@
 to N, labelled and moved — next to the training step's consumption rate, and to the reference-style numpy FPS of ONE
 piece on one host core (the dominant cost of the reference's per-sample CPU pipeline).
 
-    python tools/bench_datapipe.py [--cut {plane,sphere,cylinder,cone}] [--random_slice] [--reps 30]
+    python tools/bench_datapipe.py [--cut {plane,sphere,cylinder,cone}] [--random_slice] [--reps 30] [--fracture]
 
 Then the loader's batch as PairFeeder builds it, B = 64, M = 10000, N = 2048, 16 candidates: datapipe.cut_pairs (plane) and, with
 --cut a solid, datapipe.cut_pairs_solid of that kind next to the tensor form datapipe.make_pairs_solid on the same clouds with the
 one candidate the kernel took - one process, the forms alternating inside every repetition, a device synchronise around each.
 --random_slice: datapipe.cut_pairs_double (the double cuts, PairFeeder(split_twice=True)) beside the plane batch on the same clouds,
-and its cut launch and its two sampling launches beside the plane batch's, each alone between two device events."""
+and its cut launch and its two sampling launches beside the plane batch's, each alone between two device events.
+--fracture: only the fracture (datapipe.fracture), B = 64, M = 10000, P = 8 pieces, 16 candidates, pieces of >= 256 points: the
+ops.fracture launch and the single cut's ops.cut_compact launch on the same clouds, alternating, each alone between two device
+events, and the whole datapipe.fracture call (n = 256, k = 64) on a host clock around a device synchronise; the three medians
+and the ratio of the two launches are written to profiles/fracture_batch.txt."""
 import argparse, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -17,9 +21,56 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--cut", choices=["plane", "sphere", "cylinder", "cone"], default="plane")
 ap.add_argument("--random_slice", action="store_true")
 ap.add_argument("--reps", type=int, default=30)
+ap.add_argument("--fracture", action="store_true")
 a = ap.parse_args()
 dev = torch.device('cuda:0')
 g = torch.Generator().manual_seed(0)
+
+
+def bench_fracture(reps):
+    from puzzlenet_amd import ops
+    B, M, P, K, n, k = 64, 10000, 8, 16, 256, 64
+    rng = np.random.RandomState(0)
+    raw = torch.from_numpy((rng.rand(B, M, 3) - 0.5).astype(np.float32)).to(dev)
+    normals, u_anchor, u_start, twist = (torch.from_numpy(np.ascontiguousarray(t)).to(dev)
+                                         for t in datapipe.fracture_draws(rng, torch.Generator().manual_seed(0), B, P, K, 0.8))
+    pn, pz, pu = torch.from_numpy(rng.rand(B, K, 3)).to(dev), torch.from_numpy(rng.rand(B, K) / 3 - 0.4).to(dev), torch.from_numpy(rng.rand(B, 2)).to(dev)
+    f = datapipe.fracture(raw, normals, u_anchor, u_start, twist, n=n, k=k)
+    print('fracture: valid %d/%d, smallest piece %d, mates per sample %.1f' % (int(f.ok.sum()), B, int(f.counts.min()), float(f.mates.sum()) / 2 / B), flush=True)
+    launches = {"ops.fracture (P = 8)": lambda: ops.fracture(raw, normals, u_anchor, u_start, n, M),
+                "ops.cut_compact (the single cut)": lambda: ops.cut_compact(raw, pn, pz, pu, n, M)}
+    lt = {name: [] for name in launches}
+    whole = []
+    for rep in range(reps + 3):                          # (three warm-up rounds of everything)
+        for name, fn in launches.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(); e0.record()
+            fn()
+            e1.record(); e1.synchronize()
+            if rep >= 3:
+                lt[name].append(e0.elapsed_time(e1) * 1e3)
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        datapipe.fracture(raw, normals, u_anchor, u_start, twist, n=n, k=k)
+        torch.cuda.synchronize()
+        if rep >= 3:
+            whole.append((time.perf_counter() - t0) * 1e3)
+    fr_us, cut_us = (float(np.median(lt[name])) for name in launches)
+    lines = ['tools/bench_datapipe.py --fracture --reps %d: B = %d, M = %d, P = %d, K = %d, n_min = n = %d, k = %d (medians of %d)' % (reps, B, M, P, K, n, k, reps)]
+    for name in launches:
+        t = np.sort(np.array(lt[name]))
+        lines.append('launch: %-34s %.0f us between events (min %.0f, max %.0f)' % (name, np.median(t), t[0], t[-1]))
+    lines.append('ratio fracture / cut_compact: %.2f (%d cuts and a %d-way partition against 1 cut and a 2-way one)' % (fr_us / cut_us, P - 1, P))
+    t = np.sort(np.array(whole))
+    lines.append('datapipe.fracture, the whole call: %.2f ms per batch on the host clock (min %.2f, max %.2f), valid %d/%d' % (np.median(t), t[0], t[-1], int(f.ok.sum()), B))
+    print('\n'.join(lines), flush=True)
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'fracture_batch.txt')
+    with open(out, 'w') as fh:
+        fh.write('\n'.join(lines) + '\n')
+
+
+if a.fracture:
+    bench_fracture(a.reps)
+    sys.exit(0)
 for (B, M, N) in [(64, 6000, 1024), (64, 10000, 2048), (64, 12000, 2048)]:
     raw = (torch.rand(B, M, 3, generator=g) - 0.5).to(dev)
     normal = torch.rand(B, 3, generator=g, dtype=torch.float64).to(dev)

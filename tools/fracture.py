@@ -1,0 +1,71 @@
+"""Cut a cloud into P pieces that belong together, with the answers: the input tools/assemble.py takes and the truth its
+--gt scores against (puzzlenet_amd.datapipe.fracture, one launch of csrc/fracture.hip for the cut).
+
+    python tools/fracture.py [--cloud cloud.npy] [--pieces 8] [--n 1024] [--k 128] [--candidates 16] [--mag 0.8] [--seed 0]
+                             [--out PREFIX]
+
+cloud.npy holds [M, 3] float32 (M <= 65536; a piece may hold at most 32768 points); without it a seeded uniform cloud of --m
+points in [-0.5, 0.5)^3 is cut.  Writes PREFIX_pieces.npy ([P, n, 3] float32: every piece sampled to n points and moved by a
+random rigid motion of magnitude --mag) and PREFIX_gt.npz with pose [P,4,4] (moved piece = pose applied to the piece where it
+belongs), rest [P,n,3], label [M] (the piece of every cloud point), src [P,n] (the cloud row of every sampled point), mates
+[P,P] and cd [P,P] (which pieces touch: the chamfer distance of the k-point boundaries against 0.015), planes [P-1,4].
+Needs a GPU; there is no CPU path."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np
+import torch
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--cloud", default=None, help=".npy file with [M, 3] float32 points")
+    ap.add_argument("--m", type=int, default=10000, help="points of the synthetic cloud (no --cloud)")
+    ap.add_argument("--pieces", type=int, default=8, help="P: pieces to cut (2 .. 16)")
+    ap.add_argument("--n", type=int, default=1024, help="points every piece is sampled to (the model's points per piece)")
+    ap.add_argument("--n-min", type=int, default=None, help="points both sides of a cut must hold (default: --n)")
+    ap.add_argument("--k", type=int, default=128, help="boundary points per piece and pair")
+    ap.add_argument("--candidates", type=int, default=16, help="candidate planes per cut")
+    ap.add_argument("--mag", type=float, default=0.8, help="magnitude of every piece's twist")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", default="fracture", help="prefix of the two files written")
+    args = ap.parse_args()
+
+    if not torch.cuda.is_available():
+        sys.exit("tools/fracture.py needs a GPU: puzzlenet_amd has no CPU path")
+    from puzzlenet_amd import datapipe
+    dev = torch.device("cuda:0")
+    rng = np.random.RandomState(args.seed)
+    if args.cloud:
+        cloud = np.ascontiguousarray(np.load(args.cloud), dtype=np.float32)
+        if cloud.ndim != 2 or cloud.shape[1] != 3:
+            sys.exit(f"{args.cloud}: expected [M, 3], got {cloud.shape}")
+    else:
+        cloud = (rng.rand(args.m, 3) - 0.5).astype(np.float32)
+    M, P = cloud.shape[0], args.pieces
+    normals, u_anchor, u_start, twist = datapipe.fracture_draws(rng, torch.Generator().manual_seed(args.seed), 1, P,
+                                                                args.candidates, args.mag)
+    to = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    f = datapipe.fracture(to(cloud[None]), to(normals), to(u_anchor), to(u_start), to(twist), n=args.n, n_min=args.n_min,
+                          k=args.k, cap=min(M, 32768))
+    counts = f.counts[0].tolist()
+    print(f"{M} points into {P} pieces: {counts}")
+    if not bool(f.ok[0]):
+        print(f"NOT a valid fracture: a cut had no valid candidate among {args.candidates}, or a piece holds fewer than "
+              f"{args.n} or more than {min(M, 32768)} points; the files are written all the same")
+    cd, mates = f.cd[0].cpu().numpy(), f.mates[0].cpu().numpy()
+    with np.printoptions(precision=5, suppress=True, linewidth=200):
+        print("cd[a, b] of the boundaries:")
+        print(cd)
+    print("mates:", [(a, b) for a in range(P) for b in range(a + 1, P) if mates[a, b]])
+    np.save(args.out + "_pieces.npy", f.pieces[0].cpu().numpy())
+    np.savez(args.out + "_gt.npz", pose=f.pose[0].cpu().numpy(), rest=f.rest[0].cpu().numpy(), label=f.label[0].cpu().numpy(),
+             src=f.src[0].cpu().numpy(), mates=mates, cd=cd, planes=f.planes[0].cpu().numpy())
+    print(f"wrote {args.out}_pieces.npy, {args.out}_gt.npz")
+
+
+if __name__ == "__main__":
+    main()
