@@ -3,7 +3,9 @@
 // the only definition.  Included inside the translation unit's anonymous namespace, after pzn_common.h (pzn_mfma.h
 // includes it for the chained kernels).
 //
-// x = x1 + x2 + x3 exactly, each xi a bf16 (8 significant bits, fp32's exponent range): x1 = bf16(x),
+// x = x1 + x2 + x3 exactly, each xi a bf16 (8 significant bits, fp32's exponent range - as long as x3, up to 2^-16 of x,
+// is still a normal number; tests/test_gpu_x3_exact.py probes operands scaled by 2^-40 .. 2^40 with every plane at or
+// above 2^-40 and every product within 2^-80 .. 2^104, and says nothing about where a plane would underflow): x1 = bf16(x),
 // x2 = bf16(x - x1), x3 = bf16(x - x1 - x2).  a*b is then summed from the six products whose magnitude is
 // >= 2^-16 of the leading one: (1,1) (1,2) (2,1) (1,3) (2,2) (3,1); the three dropped ones are <= 2^-24
 // relative, i.e. below fp32 rounding.  Each product of two bf16 is exact in fp32 and the MFMA accumulates
