@@ -13,7 +13,7 @@
 // tables (bit `code` set = the cell belongs to it: datapipe.UP, UP_UPPC, ...): rows of the first table, then rows of the second,
 // each in the cloud's point order (np.vstack, dataset.py:1239) - a two-segment stable partition written from ONE scan of the
 // packed per-thread counts.  The signed distance is the plane cut's: float64, every operation individually rounded (no fma);
-// it, the block sum, the padding and the start index come from pzn_cut.h.  The decision tree and the two-segment partition are
+// it, the block sum, the exclusive scan, the padding and the start index come from pzn_cut.h.  The decision tree and the two-segment partition are
 // this file's own (the single cuts' two-way body is a different algorithm).
 //
 // Replaces, per batch: a device-to-host round trip per decision, two float64 einsums, two stable sorts of [B, M] keys per piece.
@@ -52,9 +52,8 @@ __device__ __forceinline__ int segment(int code, int t0, int t1) { return ((t0 >
 
 __global__ __launch_bounds__(CUT_T) void cut_compact_double_kernel(DoubleCutArgs a) {
   __shared__ int slots[CUT_W];
-  __shared__ int seg_tot[2][CUT_W];
-  __shared__ int seg_base[2][CUT_W + 1];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (PZN_WAVE - 1), wave = tid / PZN_WAVE;
+  __shared__ long long seg_slots[CUT_W], seg_base[CUT_W];      // the scan's tables: two counts per word
+  const int b = blockIdx.x, tid = threadIdx.x;
   const int M = a.M, n = a.n_min;
   const float* g = a.raw + (size_t)b * M * 3;
   // a thread owns a CONTIGUOUS run of points, so that a partition keeps the original order with one scan over threads
@@ -153,24 +152,12 @@ __global__ __launch_bounds__(CUT_T) void cut_compact_double_kernel(DoubleCutArgs
       const int s = segment(2 * (int)is_up(x, y, z, p1) + (int)is_up(x, y, z, p2), t0, t1);
       c0 += s == 0, c1 += s == 1;
     }
-    long long packed = (long long)c0 | ((long long)c1 << 32), incl = packed;
-    for (int d = 1; d < PZN_WAVE; d <<= 1) {
-      const long long o = __shfl_up(incl, d, PZN_WAVE);
-      if (lane >= d) incl += o;
-    }
-    __syncthreads();      // (the tables may still be read for the piece before)
-    if (lane == PZN_WAVE - 1) seg_tot[0][wave] = (int)(incl & 0xffffffffll), seg_tot[1][wave] = (int)(incl >> 32);
-    __syncthreads();
-    if (tid < 2) {
-      int run = 0;
-      for (int w = 0; w < CUT_W; ++w) seg_base[tid][w] = run, run += seg_tot[tid][w];
-      seg_base[tid][CUT_W] = run;      // total
-    }
-    __syncthreads();
-    const int n0 = seg_base[0][CUT_W], cnt = n0 + seg_base[1][CUT_W];
-    const long long excl = incl - packed;
-    int at0 = seg_base[0][wave] + (int)(excl & 0xffffffffll);            // rows of the first region in front of this run
-    int at1 = n0 + seg_base[1][wave] + (int)(excl >> 32);                // the second region follows the whole first one
+    // (each half counts at most M < 2^31 points, so no carry crosses from the low count into the high one)
+    const long long excl = block_excl_scan((long long)c0 | ((long long)c1 << 32), seg_slots, seg_base);
+    const long long tot = seg_slots[0];
+    const int n0 = (int)(tot & 0xffffffffll), cnt = n0 + (int)(tot >> 32);
+    int at0 = (int)(excl & 0xffffffffll);            // rows of the first region in front of this run
+    int at1 = n0 + (int)(excl >> 32);                // the second region follows the whole first one
     for (int j = lo; j < hi; ++j) {
       const float x = g[3 * j], y = g[3 * j + 1], z = g[3 * j + 2];
       const int s = segment(2 * (int)is_up(x, y, z, p1) + (int)is_up(x, y, z, p2), t0, t1);

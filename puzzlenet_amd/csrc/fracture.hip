@@ -15,9 +15,9 @@
 // scratch); the per-label counts are registers that every thread holds alike (the sums come from block_sum), so every branch
 // on them is uniform.  Per step: the run's target members as one bit mask, ONE exclusive scan of their counts for all K anchor
 // ranks (the thread whose run holds rank r_k writes that point to a small LDS table, FR_KC candidates at a time), then one
-// pass over the members and a block_sum per candidate.  The P-way stable partition at the end is doublecut.hip's wave scan
-// and seg_base pattern, once per label; the same pass writes `order`, the first one `label`.  Side test, workgroup sum, start
-// index and padding come from pzn_cut.h.
+// pass over the members and a block_sum per candidate.  The P-way stable partition at the end is the same exclusive scan, once
+// per label; the same pass writes `order`, the first one `label`.  Side test, workgroup sum, exclusive scan, start index and
+// padding come from pzn_cut.h.
 #include "pzn_common.h"
 
 namespace {
@@ -28,8 +28,7 @@ constexpr int FR_MAX_P = 16;         // pieces per sample
 constexpr int FR_MAX_M = 65536;      // points per sample: runs of <= 64 points, one membership mask per thread
 constexpr int FR_KC = 16;            // anchors held in LDS at a time
 // the dynamic LDS region: every table at a multiple of 16 bytes, the labels last
-constexpr int FR_SLOTS = 0, FR_WBASE = FR_SLOTS + CUT_W * 4, FR_SBASE = FR_WBASE + CUT_W * 4;
-constexpr int FR_ANCHOR = FR_SBASE + ((CUT_W + 1) * 4 + 15) / 16 * 16, FR_LABELS = FR_ANCHOR + FR_KC * 4 * 4;
+constexpr int FR_SLOTS = 0, FR_WBASE = FR_SLOTS + CUT_W * 4, FR_ANCHOR = FR_WBASE + CUT_W * 4, FR_LABELS = FR_ANCHOR + FR_KC * 4 * 4;
 
 struct FractureArgs {
   const float* raw;          // [B, M, 3]
@@ -48,34 +47,13 @@ struct FractureArgs {
   uint8_t* ok;               // [B]
 };
 
-// exclusive scan of one int per thread over the workgroup in thread order (three barriers); the total in slots[0]
-__device__ __forceinline__ int block_excl_scan(int c, int* slots, int* wave_base) {
-  const int lane = threadIdx.x & (PZN_WAVE - 1), wave = threadIdx.x / PZN_WAVE;
-  int incl = c;
-  for (int d = 1; d < PZN_WAVE; d <<= 1) {
-    const int o = __shfl_up(incl, d, PZN_WAVE);
-    if (lane >= d) incl += o;
-  }
-  __syncthreads();          // (the tables may still be read from the call before)
-  if (lane == PZN_WAVE - 1) slots[wave] = incl;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int run = 0;
-    for (int w = 0; w < CUT_W; ++w) wave_base[w] = run, run += slots[w];
-    slots[0] = run;
-  }
-  __syncthreads();
-  return wave_base[wave] + incl - c;
-}
-
 __global__ __launch_bounds__(CUT_T) void fracture_kernel(FractureArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   int* slots = reinterpret_cast<int*>(smem + FR_SLOTS);
   int* wave_base = reinterpret_cast<int*>(smem + FR_WBASE);
-  int* seg_base = reinterpret_cast<int*>(smem + FR_SBASE);      // [CUT_W + 1]
   float* anchor = reinterpret_cast<float*>(smem + FR_ANCHOR);   // [FR_KC][4]
   uint8_t* lab = smem + FR_LABELS;                              // [M]
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (PZN_WAVE - 1), wave = tid / PZN_WAVE;
+  const int b = blockIdx.x, tid = threadIdx.x;
   const int M = a.M, P = a.P, K = a.K;
   const float* g = a.raw + (size_t)b * M * 3;
   // a thread owns a CONTIGUOUS run of points, so that a partition keeps the original order with one scan over threads
@@ -170,22 +148,8 @@ __global__ __launch_bounds__(CUT_T) void fracture_kernel(FractureArgs a) {
     float* dst = a.pieces + ((size_t)p * a.B + b) * a.cap * 3;
     int c = 0;
     for (int j = lo; j < hi; ++j) c += lab[j] == p ? 1 : 0;
-    int incl = c;
-    for (int d = 1; d < PZN_WAVE; d <<= 1) {
-      const int o = __shfl_up(incl, d, PZN_WAVE);
-      if (lane >= d) incl += o;
-    }
-    __syncthreads();         // (the tables may still be read for the piece before)
-    if (lane == PZN_WAVE - 1) slots[wave] = incl;
-    __syncthreads();
-    if (tid == 0) {
-      int run = 0;
-      for (int w = 0; w < CUT_W; ++w) seg_base[w] = run, run += slots[w];
-      seg_base[CUT_W] = run;      // total
-    }
-    __syncthreads();
-    const int n_p = seg_base[CUT_W];      // == cnt[p]
-    int at = seg_base[wave] + incl - c;   // rows of label p in front of this run
+    int at = block_excl_scan(c, slots, wave_base);      // rows of label p in front of this run
+    const int n_p = slots[0];                           // == cnt[p]
     for (int j = lo; j < hi; ++j) {
       if (lab[j] != p) continue;
       if (at < a.cap) dst[(size_t)at * 3] = g[3 * j], dst[(size_t)at * 3 + 1] = g[3 * j + 1], dst[(size_t)at * 3 + 2] = g[3 * j + 2];
@@ -218,7 +182,7 @@ PZN_EXPORT int pzn_fracture_f32(const float* raw, const double* normals, const d
   PZN_CHECK_ARG(B > 0 && cap > 0 && n_min >= 0);
   if (!pzn_fracture_supported(M, P, K)) return PZN_EUNSUPPORTED;
   FractureArgs a{raw, normals, u_anchor, u_start, B, M, P, K, n_min, cap, pieces, counts, start, label, order, planes, target, cand, ok};
-  const size_t lds = (size_t)FR_LABELS + ((size_t)M + 15) / 16 * 16;      // <= 64.5 KiB
+  const size_t lds = (size_t)FR_LABELS + ((size_t)M + 15) / 16 * 16;      // <= 64.4 KiB
   if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(fracture_kernel),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return PZN_ELAUNCH;

@@ -10,18 +10,18 @@
 //   * drops: one flag byte per union row in LDS (indices may repeat: every writer stores the same byte);
 //   * start: start[m] if that row is kept, otherwise the first kept row at or after it, wrapping round to 0: one
 //     wavefront-uniform scan of the flag bytes, 64 rows per step, done by every wavefront alike before the rounds;
-//   * rounds: the loop of fps.hip's fps_kernel with the LDS image (the arithmetic is the same code, so with an identity
-//     pose and no drops the picks are pzn_fps_f32's on cat(a, b) bit for bit): running distance min(dist, sqdist3), arg-max
-//     as one u64 maximum of (dist_bits << 32) | ~index (lowest union index wins ties), one barrier per round on
-//     parity-double-buffered slots;
-//   * epilogue: picks are buffered in LDS and leave in chunks, as src (int64 union index) and out (the coordinates from the
-//     image: a rows as read, b rows as transformed).
+//   * rounds: pzn_fps_round.h, the round of fps.hip's image form - the arithmetic is the same code, so with an identity
+//     pose and no drops the picks are pzn_fps_f32's on cat(a, b) bit for bit, and the lowest union index wins ties;
+//   * epilogue: the round's pick buffer flushes src (int64 union index) and out (the coordinates from the image: a rows as
+//     read, b rows as transformed).
+// This file's own: the pose transform into the image, the drop flags, the start scan and the coordinate write-out.
 // The round is a latency chain (n_out dependent rounds); the launch is parallel over merges only.
 #include "pzn_common.h"
 
 namespace {
 
-constexpr int MRG_OUT_CHUNK = 256;      // picks buffered in LDS between write-outs (power of two)
+#include "pzn_fps_round.h"
+
 constexpr int MRG_T = 256;              // four wavefronts: the round's cross-wave part grows with the wave count (fps.hip)
 constexpr int MRG_MAX_UNION = 4096;     // 48 KB image + 4 KB flags + slots and pick buffer: below the 64 KB default
 
@@ -35,8 +35,8 @@ __global__ __launch_bounds__(T) void merge_resample_kernel(const float* __restri
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int U = Na + Nb;
   uint64_t* slots = reinterpret_cast<uint64_t*>(smem_raw);                              // [2][W]
-  int* sout = reinterpret_cast<int*>(smem_raw + 2 * W * sizeof(uint64_t));              // [MRG_OUT_CHUNK] picks not yet written out
-  float* sx = reinterpret_cast<float*>(smem_raw + 2 * W * sizeof(uint64_t) + MRG_OUT_CHUNK * sizeof(int));
+  int* sout = reinterpret_cast<int*>(smem_raw + 2 * W * sizeof(uint64_t));              // [FPS_OUT_CHUNK] picks not yet written out
+  float* sx = reinterpret_cast<float*>(smem_raw + fps_lds_head(W));
   float* sy = sx + U;
   float* sz = sy + U;
   unsigned char* sdrop = reinterpret_cast<unsigned char*>(sz + U);                      // [U] 1 = dropped row
@@ -50,16 +50,8 @@ __global__ __launch_bounds__(T) void merge_resample_kernel(const float* __restri
   const float* g = pose + (size_t)m * 16;
 
   // load: both clouds once, flat and coalesced, into the union's SoA image; the flags start clear
-  for (int i = tid; i < 3 * Na; i += T) {
-    const float v = ga[i];
-    const int p = i / 3, c = i - 3 * p;
-    (c == 0 ? sx : (c == 1 ? sy : sz))[p] = v;
-  }
-  for (int i = tid; i < 3 * Nb; i += T) {
-    const float v = gb[i];
-    const int p = i / 3, c = i - 3 * p;
-    (c == 0 ? sx : (c == 1 ? sy : sz))[Na + p] = v;
-  }
+  fps_load_soa<T>(ga, Na, sx, sy, sz, 0, tid);
+  fps_load_soa<T>(gb, Nb, sx, sy, sz, Na, tid);
   for (int i = tid; i < U; i += T) sdrop[i] = 0;
   __syncthreads();
   // drop lists (an index outside its cloud is ignored)
@@ -124,75 +116,20 @@ __global__ __launch_bounds__(T) void merge_resample_kernel(const float* __restri
   int64_t* o = src + (size_t)m * n_out;
   float* oc = out + (size_t)m * n_out * 3;
 
+  auto flush = [&](int base, int cnt) {
+    for (int t = tid; t < cnt; t += T) o[base + t] = (int64_t)sout[t];
+    for (int e = tid; e < 3 * cnt; e += T) {
+      const int t = e / 3, c = e - 3 * t;
+      const int r = sout[t];
+      oc[(size_t)base * 3 + e] = (c == 0 ? sx : (c == 1 ? sy : sz))[r];
+    }
+  };
+
   for (int i = 0; i < n_out; ++i) {
-    // the pick goes to LDS and leaves in chunks (a global store inside the loop keeps a vector-memory operation outstanding
-    // at every barrier)
-    if (tid == 0) sout[i & (MRG_OUT_CHUNK - 1)] = far;
-    if ((i & (MRG_OUT_CHUNK - 1)) == MRG_OUT_CHUNK - 1 || i == n_out - 1) {
-      __syncthreads();
-      const int base = i & ~(MRG_OUT_CHUNK - 1);
-      const int cnt = i - base + 1;
-      for (int t = tid; t < cnt; t += T) o[base + t] = (int64_t)sout[t];
-      for (int e = tid; e < 3 * cnt; e += T) {
-        const int t = e / 3, c = e - 3 * t;
-        const int r = sout[t];
-        oc[(size_t)base * 3 + e] = (c == 0 ? sx : (c == 1 ? sy : sz))[r];
-      }
-      __syncthreads();      // (sout is rewritten next round)
-    }
+    fps_buffer_pick(sout, i, n_out, far, tid, flush);
     const float cx = sx[far], cy = sy[far], cz = sz[far];
-    uint64_t best;
-    if constexpr (PPT <= 4) {
-      // arg-max in two parts, as fps_kernel: the 32-bit distance pattern through the wave reduction alone, the index
-      // resolved afterwards (one lane holds the maximum almost always; on a tie the lowest index wins)
-      uint32_t bd = 0, bj = 0x7fffffffu;      // (a thread without a row keeps the sentinel and never ties)
-#pragma unroll
-      for (int p = 0; p < PPT; ++p) {
-        const int j = tid + p * T;
-        const float d = pzn::sqdist3(px[p], py[p], pz[p], cx, cy, cz);
-        const float nd = d < dist[p] ? d : dist[p];
-        dist[p] = nd;
-        const uint32_t nb = __float_as_uint(nd);
-        // strict >: the lower index of equal distances stays (j ascends with p); the thread's first row is always taken
-        const bool take = p == 0 ? (full || j < U) : ((full || j < U) && nb > bd);
-        bd = take ? nb : bd;
-        bj = take ? (uint32_t)j : bj;
-      }
-      const uint32_t wm = pzn::wave_max_u32_dpp(bd);
-      const bool tied = bd == wm && (full || bj != 0x7fffffffu);
-      const unsigned long long tmask = __ballot(tied);
-      uint32_t wj;
-      if (__popcll(tmask) == 1)
-        wj = (uint32_t)__builtin_amdgcn_readlane((int)bj, __builtin_ctzll(tmask));
-      else
-        wj = pzn::wave_min_u32_dpp(tied ? bj : 0xffffffffu);
-      best = ((uint64_t)wm << 32) | (uint32_t)(~wj);
-    } else {      // many rows per thread: the 64-bit key (distance, ~index) per row, as fps_kernel
-      best = 0;   // below every real key: real keys have ~j >= 1
-#pragma unroll
-      for (int p = 0; p < PPT; ++p) {
-        if (p < pmax) {      // (workgroup-uniform: slots at and beyond pmax hold no row)
-          const int j = tid + p * T;
-          const float d = pzn::sqdist3(px[p], py[p], pz[p], cx, cy, cz);
-          const float nd = d < dist[p] ? d : dist[p];
-          dist[p] = nd;
-          uint64_t key = ((uint64_t)__float_as_uint(nd) << 32) | (uint32_t)(~(uint32_t)j);
-          key = j < U ? key : 0ull;
-          best = key > best ? key : best;
-        }
-      }
-      best = pzn::wave_max_u64_dpp(best);
-    }
-    uint64_t* sl = slots + (i & 1) * W;
-    if (lane == 0) sl[wave] = best;
-    __syncthreads();
-    uint64_t mx = sl[0];
-#pragma unroll
-    for (int w = 1; w < W; ++w) {
-      const uint64_t v = sl[w];
-      mx = v > mx ? v : mx;
-    }
-    far = (int)(~(uint32_t)mx);      // first (lowest-index) maximum
+    const uint64_t best = fps_wave_argmax<T, PPT>(px, py, pz, dist, cx, cy, cz, tid, U, pmax, full);
+    far = (int)(~(uint32_t)fps_cross_wave<W>(slots, i, lane, wave, best));
   }
 }
 
@@ -201,7 +138,7 @@ int launch(const float* a, const float* b, const float* pose, const int64_t* sta
            const int64_t* drop_b, int kb, int M, int Na, int Nb, int n_out, float* out, int64_t* src, hipStream_t st) {
   constexpr int W = MRG_T / PZN_WAVE;
   const size_t U = (size_t)Na + Nb;
-  const size_t lds = 2 * W * sizeof(uint64_t) + MRG_OUT_CHUNK * sizeof(int) + 3 * U * sizeof(float) + U;
+  const size_t lds = fps_lds_head(W) + 3 * U * sizeof(float) + U;
   PZN_LAUNCH((merge_resample_kernel<MRG_T, PPT>), dim3(M), dim3(MRG_T), lds, st, a, b, pose, start, drop_a, ka, drop_b, kb,
              Na, Nb, n_out, out, src);
   PZN_RETURN_LAUNCH_STATUS();

@@ -1,6 +1,7 @@
 // pzn_cut.h — what the loader's three cut kernels share (datapipe.hip: plane, solidcut.hip: sphere / cylinder / cone,
-// doublecut.hip: two planes): the workgroup shape, the float64 plane side test, the workgroup sum, the FPS start index, the
-// padding of a piece, and the whole single-cut body - the first valid of K candidates, else the most balanced one, written as
+// doublecut.hip: two planes) and fracture.hip (P pieces): the workgroup shape, the float64 plane side test, the workgroup sum,
+// the workgroup exclusive scan behind every stable partition, the FPS start index, the padding of a piece, and the whole
+// single-cut body - the first valid of K candidates, else the most balanced one, written as
 // a stable two-way partition.  Tests pin pieces, counts and start indices bit for bit, so each of these has this one
 // definition.  Included inside the translation unit's anonymous namespace, after pzn_common.h; the translation units are
 // built with -ffp-contract=off (float64, every operation individually rounded, like numpy).
@@ -29,6 +30,29 @@ __device__ __forceinline__ int block_sum(int v, int* slots) {
 #pragma unroll
   for (int w = 0; w < CUT_W; ++w) t += slots[w];
   return t;
+}
+
+// exclusive scan of one count per thread over the workgroup in thread order (three barriers, the first for tables that may
+// still be read from the call before); the total in slots[0].  slots, wave_base: CUT_W counts of LDS each.  Count: int, or
+// long long holding two counts, one per 32-bit half, each of which stays below 2^31 (no carry crosses).
+template <class Count>
+__device__ __forceinline__ Count block_excl_scan(Count c, Count* slots, Count* wave_base) {
+  const int lane = threadIdx.x & (PZN_WAVE - 1), wave = threadIdx.x / PZN_WAVE;
+  Count incl = c;
+  for (int d = 1; d < PZN_WAVE; d <<= 1) {
+    const Count o = __shfl_up(incl, d, PZN_WAVE);
+    if (lane >= d) incl += o;
+  }
+  __syncthreads();
+  if (lane == PZN_WAVE - 1) slots[wave] = incl;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    Count run = 0;
+    for (int w = 0; w < CUT_W; ++w) wave_base[w] = run, run += slots[w];
+    slots[0] = run;
+  }
+  __syncthreads();
+  return wave_base[wave] + incl - c;
 }
 
 // np.random.randint(0, n_piece) from a uniform draw: floor(u n_piece) held to [0, n_piece - 1] (0 for an empty piece)
@@ -67,7 +91,7 @@ struct CutIO {
 // beyond that the candidate taken is evaluated again for the scan and the write).  slots, wave_base: CUT_W ints of LDS each.
 template <class Cut>
 __device__ __forceinline__ void cut_compact_body(const CutIO& a, const Cut& cut, int* slots, int* wave_base) {
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (PZN_WAVE - 1), wave = tid / PZN_WAVE;
+  const int b = blockIdx.x, tid = threadIdx.x;
   const int M = a.M;
   const float* g = a.raw + (size_t)b * M * 3;
   // a thread owns a CONTIGUOUS run of points, so that the partition keeps the original order with one scan over threads
@@ -109,22 +133,8 @@ __device__ __forceinline__ void cut_compact_body(const CutIO& a, const Cut& cut,
   if (keep) c = __popcll(sel);
   else
     for (int j = lo; j < hi; ++j) c += member(j) ? 1 : 0;
-  int incl = c;
-  for (int d = 1; d < PZN_WAVE; d <<= 1) {
-    const int o = __shfl_up(incl, d, PZN_WAVE);
-    if (lane >= d) incl += o;
-  }
-  __syncthreads();
-  if (lane == PZN_WAVE - 1) slots[wave] = incl;
-  __syncthreads();
-  if (tid == 0) {
-    int run = 0;
-    for (int w = 0; w < CUT_W; ++w) wave_base[w] = run, run += slots[w];
-    slots[0] = run;      // total
-  }
-  __syncthreads();
+  int up_at = block_excl_scan(c, slots, wave_base);      // ups in front of this thread's run
   const int n_up = slots[0], n_down = M - n_up;
-  int up_at = wave_base[wave] + incl - c;      // ups in front of this thread's run
   int down_at = lo - up_at;                    // downs in front of it
   float* pu = a.pieces + (size_t)b * a.cap * 3;
   float* pd = a.pieces + (size_t)(a.B + b) * a.cap * 3;

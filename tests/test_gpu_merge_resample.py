@@ -68,7 +68,7 @@ def test_bit_exact_with_drops(dev, big):
 
 
 def test_bit_exact_odd_sizes(dev):
-    """Sizes that are no multiple of 64, a union that leaves register slots empty, n_out below Na."""
+    """Sizes that are no multiple of 64, a union of exactly one row per thread (96 + 160 = 256), n_out below Na."""
     a, b, T, start = _inputs(dev, 33, 2, 96, 160, [200, 3])
     g = torch.Generator().manual_seed(34)
     drop_a = torch.stack([torch.randperm(96, generator=g)[:10] for _ in range(2)])
@@ -76,6 +76,20 @@ def test_bit_exact_odd_sizes(dev):
         got = _run(dev, a, b, T, start, 64, da, None)
         want = _merge_ref.merge_resample(a, b, T, start, 64, da, None)
         assert torch.equal(got[1], want[1]) and torch.equal(got[0], want[0])
+
+
+@pytest.mark.parametrize("Na,Nb,n_out", [(100, 100, 64),        # 1 row per thread, register slots left empty
+                                         (200, 130, 300),       # 2 rows per thread, not full; one pick-buffer flush at 256
+                                         (300, 400, 128)])      # 4 rows per thread, not full
+@pytest.mark.parametrize("with_drops", [False, True])
+def test_bit_exact_partly_filled_workgroup(dev, Na, Nb, n_out, with_drops):
+    """Unions of up to 1024 rows that do not fill the workgroup's register slots: the arg-max with bounds tests."""
+    a, b, T, start = _inputs(dev, 36 + Na, 2, Na, Nb, [Na + Nb - 1, 3])
+    g = torch.Generator().manual_seed(37)
+    drop_a = torch.stack([torch.randperm(Na, generator=g)[:10] for _ in range(2)]) if with_drops else None
+    got = _run(dev, a, b, T, start, n_out, drop_a, None)
+    want = _merge_ref.merge_resample(a, b, T, start, n_out, drop_a, None)
+    assert torch.equal(got[1], want[1]) and torch.equal(got[0], want[0])
 
 
 def test_bit_exact_largest_union(dev):

@@ -123,7 +123,9 @@ def test_index_points_golden_and_grad(golden_point_ops, dev):
 
 @pytest.mark.parametrize("B,N,S", [(4, 1024, 512), (3, 2048, 512), (2, 4096, 512), (1, 8192, 512),
                                    (5, 512, 256), (2, 100, 100), (1, 1, 1), (2, 65, 7), (1, 12000, 16),
-                                   (1, 20000, 8)])
+                                   (1, 20000, 8),
+                                   (2, 200, 9),        # 256 threads, one point each, not every thread has one
+                                   (1, 13000, 8)])     # the main entry without the LDS image (it no longer fits), 16 slots
 def test_fps_vs_oracle(dev, B, N, S):
     from puzzlenet_amd import ops
     rng = np.random.default_rng(N * 7 + S)
