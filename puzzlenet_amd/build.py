@@ -9,6 +9,8 @@ import os
 import subprocess
 import sys
 
+from ._lib import HEADER_PATH
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
@@ -79,7 +81,7 @@ def _stale(target, deps):
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    headers.append(os.path.join(os.path.dirname(HERE), "include", "pzn.h"))
+    headers.append(HEADER_PATH)
     objs = []
     procs = []
     for src, extra in SOURCES:

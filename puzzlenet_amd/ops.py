@@ -462,7 +462,8 @@ class _BoundaryCE(torch.autograd.Function):
         if C != 2 or tuple(labels.shape) != (B, N):
             raise _lib.PznError(f"boundary_ce expects logits[B,2,N], labels[B,N]; got {tuple(logits.shape)}, {tuple(labels.shape)}")
         prob1 = torch.empty((B, N), dtype=torch.float32, device=logits.device)
-        loss = torch.empty((513,), dtype=torch.float32, device=logits.device)   # PZN_BOUNDARY_CE_LOSS_FLOATS: value + partials
+        loss = torch.empty((_lib.CONSTANTS["PZN_BOUNDARY_CE_LOSS_FLOATS"],), dtype=torch.float32,      # value + partials
+                           device=logits.device)
         with _on(logits.device):
             _call("pzn_boundary_ce_fwd_f32", _p(logits), _p(labels), B, N, int(pm), _p(prob1), _p(loss), _stream())
         ctx.save_for_backward(logits, labels)

