@@ -8,6 +8,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests._attn_launch import fused_block as _fused_block
+from tests._attn_ref import attn_block_ref as _attn_block_ref64, attn_chain_ref as _attn_chain_ref64
+
 pytestmark = pytest.mark.gpu
 
 
@@ -468,35 +471,11 @@ def test_linear_maxpts_sparse_backward(dev, B, L, seg_cols, nseg, Nout):
 
 # ---------------------------------------------------------------- chained attention kernels (csrc/attnfused.hip)
 
-def _attn_block_ref64(x, wq, bq, wk, bk, wv, bv, wo, bo, dr, gate=None):
-    """model5_b.py:67-101 and its backward, every intermediate the chained kernels leave in memory, in float64.
-    gate: the ReLU gates the backward uses (default: the float64 pre-activation's own)."""
-    D = torch.float64
-    X = x.to(D)
-    q, k, v = X @ wq.to(D).T + bq.to(D), X @ wk.to(D).T + bk.to(D), X @ wv.to(D).T + bv.to(D)
-    s = q @ k.transpose(1, 2) / 8
-    P = torch.softmax(s, dim=-1)
-    t = X - P @ v
-    z = t @ wo.to(D).T + bo.to(D)
-    r = X + torch.relu(z)
-    DR = dr.to(D)
-    dz = DR * ((z > 0) if gate is None else gate.reshape(z.shape))
-    dt = dz @ wo.to(D)
-    dP = (-dt) @ v.transpose(1, 2)
-    delta = (P * dP).sum(-1)
-    dS = P * (dP - delta[..., None]) / 8
-    dq, dk, dv = dS @ k, dS.transpose(1, 2) @ q, P.transpose(1, 2) @ (-dt)
-    u = DR + dt                                   # (what the query-side pass leaves for the key-side pass)
-    dx = u + dq @ wq.to(D) + dk @ wk.to(D) + dv @ wv.to(D)
-    return dict(r=r, t=t, map=P, lse=torch.logsumexp(s, dim=-1), dz=dz, delta=delta, dq=dq, u=u, dk=dk, dv=dv, dx=dx, z=z)
-
-
 @pytest.mark.parametrize("B", [2, 64])
 def test_attention_fused_block_intermediates(dev, B):
     """One layerAttention block through pzn_attn_fused_{prep_weights,proj,fwd,bwd_q,bwd_k}: the block output, x - attn v,
     the attention map, ln-sum-exp, and every backward intermediate (dz, delta, dq, u, dk, dv, dx) against float64 at
     1e-5 relative (measured 1e-7 .. 8e-7); B = 64 is the production launch (128 workgroups)."""
-    from puzzlenet_amd import _lib, ops
     L, E, dk = 256, 256, 64
     M = B * L
     g = torch.Generator().manual_seed(3)
@@ -506,37 +485,13 @@ def test_attention_fused_block_intermediates(dev, B):
     bq, bk = [(torch.randn(dk, generator=g) / 4).to(dev) for _ in range(2)]
     bv, bo = [(torch.randn(E, generator=g) / 4).to(dev) for _ in range(2)]
     dr = torch.randn(M, E, generator=g).to(dev)
-    lib = _lib.load()
-    assert lib.pzn_attn_fused_supported(L, E, dk)
-    P = ops._ptrs
-    st = torch.cuda.current_stream().cuda_stream
-    raw = lambda n: torch.zeros(n, dtype=torch.uint8, device=dev)
-    mk = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
-    W = raw(lib.pzn_attn_fused_weight_bytes())
-    _lib.call("pzn_attn_fused_prep_weights", wq.data_ptr(), wk.data_ptr(), wv.data_ptr(), wo.data_ptr(), W.data_ptr(), st)
-    qkb, vb = lib.pzn_attn_fused_qk_image_bytes(B), lib.pzn_attn_fused_v_image_bytes(B)
-    qrp, krp, vrp = raw(qkb), raw(qkb), raw(vb)
-    _lib.call("pzn_attn_fused_proj", 1, P([x]), P([W]), P([bq]), P([bk]), P([bv]), B, P([qrp]), P([krp]), P([vrp]), st)
-    r, t, lse, amap = mk(M, E), mk(M, E), mk(M), mk(B, L, L)
-    mask = torch.zeros((M, 8), dtype=torch.int32, device=dev)
-    _lib.call("pzn_attn_fused_fwd", 1, P([x]), P([qrp]), P([krp]), P([vrp]), P([W]), P([bo]), B, P([r]), P([t]), P([mask]),
-              P([amap]), P([lse]), 0, 1.0, st)
-    dz, u, dq, delta = mk(M, E), mk(M, E), mk(M, dk), mk(M)
-    dqt = mk(M, dk)
-    darp = raw(vb)
-    _lib.call("pzn_attn_fused_bwd_q", 1, P([dr]), E, None, E, P([mask]), P([qrp]), P([krp]), P([vrp]), P([W]), B, P([dz]), P([u]),
-              P([dq]), P([dqt]), P([darp]), P([delta]), st)
-    dkk, dvv, dx = mk(M, dk), mk(M, E), mk(M, E)
-    _lib.call("pzn_attn_fused_bwd_k", 1, P([qrp]), P([krp]), P([vrp]), P([darp]), P([W]), P([lse]),
-              P([delta]), P([u]), P([dqt]), B, P([dkk]), P([dvv]), P([dx]), st)
     args = (x.view(B, L, E), wq, bq, wk, bk, wv, bv, wo, bo, dr.view(B, L, E))
     ref = _attn_block_ref64(*args)
     # the ReLU gate is discrete: an element whose pre-activation is within rounding of zero may be gated differently,
     # which is no kernel error; none may flip away from zero, and where one flips near zero the backward is compared with
     # the float64 backward THROUGH THE DEVICE'S GATES (a flipped element moves dz by a whole dr element)
-    untile = ops.attention_tile_image_rows
-    assert torch.equal(untile(dqt, dk), dq)                    # the same values in the two layouts
-    got = dict(r=r, t=t, map=amap, lse=lse, dz=dz, delta=delta, dq=dq, u=untile(u, E), dk=dkk, dv=dvv, dx=dx)
+    got = _fused_block(dev, *args)     # (also: dq holds the same values in its two layouts)
+    dz = got["dz"]
     flipped = (dz != 0) != (ref["dz"].reshape(M, E) != 0)
     assert int((flipped & (ref["z"].abs() > 1e-5).reshape(M, E)).sum()) == 0
     assert int(flipped.sum()) <= 4
@@ -776,17 +731,6 @@ def test_attention_chain_fused_vs_float64(dev, nprob, use):
                         w0.to(dtype).clone().requires_grad_(True), b0.to(dtype).clone().requires_grad_(True), wg.to(dtype)))
         return out
 
-    def ref64(x, blocks, w, b):
-        cur, maps, outs = x, [], []
-        for wq, bq, wk, bk, wv, bv, wo, bo in blocks:
-            q, k, v = cur @ wq.T + bq, cur @ wk.T + bk, cur @ wv.T + bv
-            a = torch.softmax(q @ k.transpose(-2, -1) / math.sqrt(q.shape[-1]), dim=-1)
-            cur = cur + torch.relu((cur - a @ v) @ wo.T + bo)
-            maps.append(a)
-            outs.append(cur)
-        y = torch.cat(outs + [x], dim=-1) @ w.T + b
-        return y, sum(maps) / 4, y.max(dim=1)[0]
-
     res, grads = {}, {}
     for kind, dtype in (("fused", torch.float32), ("ref", torch.float64)):
         lf = leafs(dtype)
@@ -794,7 +738,7 @@ def test_attention_chain_fused_vs_float64(dev, nprob, use):
             assert ops.attention_chain_fused_supported(lf[0][0], dk, lf[0][2])
             out = ops.attention_chain_fused([l[0] for l in lf], [l[1] for l in lf], [l[2] for l in lf], [l[3] for l in lf])
         else:
-            out = [ref64(x, blocks, w, b) for x, blocks, w, b, _ in lf]
+            out = [_attn_chain_ref64(x, blocks, w, b) for x, blocks, w, b, _ in lf]
         loss = sum((r[2 if use == "max" else 0] * l[4]).sum() for r, l in zip(out, lf))
         loss.backward()
         res[kind] = [(r[0].detach(), r[1].detach(), r[2].detach()) for r in out]
