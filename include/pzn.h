@@ -749,6 +749,25 @@ int pzn_fracture_supported(int M, int P, int K);
 int pzn_fracture_f32(const float* raw, const double* normals, const double* u_anchor, const double* u_start, int B, int M,
                      int P, int K, int n_min, int cap, float* pieces, int64_t* counts, int64_t* start, uint8_t* label,
                      int32_t* order, double* planes, int32_t* target, int32_t* cand, uint8_t* ok, pzn_stream_t stream);
+/* A training pair cut out of a fracture, one launch, one workgroup per sample; datapipe.fracture_pair_rule is the statement of
+ * this entry point.  raw, normals, u_anchor, n_min, cap and the steps as in pzn_fracture_f32, made for s = 1 .. P_b - 1 with
+ * P_b = n_pieces[b] (int32 [B], 2 <= P_b <= P; the draws of later steps are not read; planes, target and cand rows from
+ * P_b - 1 on are zero).  u float64 [B,7] = u_kind, u_a, u_c, u_sU, u_sD, u_sFU, u_sFD.  The SIBLING pair is U = target[P_b-2]
+ * (the up side of the last cut), D = P_b - 1 (its down side).  kind int32 [B]: 1 NEIGHBOUR iff P_b >= 3, u_kind < neighbours
+ * (0 <= neighbours <= 1) and the drawn pair a = min(P_b - 1, floor(u_a P_b)), c = c' + (c' >= a) with c' = min(P_b - 2,
+ * floor(u_c (P_b - 1))) is not the sibling pair in either order: then (U, D) = (a, c) and the sibling pair is the fallback;
+ * else 0 SIBLING, without a fallback.  pieces [4B,cap,3]: rows 0..B-1 U, B..2B-1 D, 2B..3B-1 / 3B..4B-1 the fallback pair, each
+ * the rows of its label in the cloud's order, padded as in pzn_fracture_f32; counts int64 [4B] (-1 where there is no fallback:
+ * those rows are copies of the cloud's first point, start 0); start int64 [4B] = clamp(floor(u_s* count), 0, count - 1);
+ * pair int32 [B,4]: the four labels (-1: none); label uint8 [B,M]; planes float64 [B,P-1,4]; target, cand int32 [B,P-1];
+ * ok uint8 [B]: every step made had a valid candidate and every written piece fits in cap.  n_pieces lives on the device, so a
+ * value outside 2 .. P is refused by the launch itself: that sample gets kind -1, no piece (counts -1), label 0 and ok = 0.
+ * Limits: those of pzn_fracture_f32 (pzn_fracture_pair_supported: 1 / 0), PZN_EUNSUPPORTED otherwise, before any launch. */
+int pzn_fracture_pair_supported(int M, int P, int K);
+int pzn_fracture_pair_f32(const float* raw, const double* normals, const double* u_anchor, const int32_t* n_pieces,
+                          const double* u, double neighbours, int B, int M, int P, int K, int n_min, int cap, float* pieces,
+                          int64_t* counts, int64_t* start, int32_t* kind, int32_t* pair, uint8_t* label, double* planes,
+                          int32_t* target, int32_t* cand, uint8_t* ok, pzn_stream_t stream);
 /* dataset.py:1363-1366: 0/1 masks [R,N] with ones at the k picked rows idx int64 [R,k] of each cloud. */
 int pzn_pick_mask_f32(const int64_t* idx, int R, int k, int N, float* mask, pzn_stream_t stream);
 

@@ -18,6 +18,11 @@
 // pass over the members and a block_sum per candidate.  The P-way stable partition at the end is the same exclusive scan, once
 // per label; the same pass writes `order`, the first one `label`.  Side test, workgroup sum, exclusive scan, start index and
 // padding come from pzn_cut.h.
+//
+// fracture_pair_kernel (datapipe.fracture_pair_rule; the loader's PairFeeder(pieces=...)) runs the same steps, one
+// __device__ function for both kernels, for a per-sample number of pieces, chooses a training pair on the device - the two
+// sides of the last cut, or a drawn pair of final pieces with those two as its fallback - and partitions the <= 4 chosen
+// labels only: no `order`, no other piece.
 #include "pzn_common.h"
 
 namespace {
@@ -47,26 +52,47 @@ struct FractureArgs {
   uint8_t* ok;               // [B]
 };
 
-__global__ __launch_bounds__(CUT_T) void fracture_kernel(FractureArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  int* slots = reinterpret_cast<int*>(smem + FR_SLOTS);
-  int* wave_base = reinterpret_cast<int*>(smem + FR_WBASE);
-  float* anchor = reinterpret_cast<float*>(smem + FR_ANCHOR);   // [FR_KC][4]
-  uint8_t* lab = smem + FR_LABELS;                              // [M]
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int M = a.M, P = a.P, K = a.K;
-  const float* g = a.raw + (size_t)b * M * 3;
-  // a thread owns a CONTIGUOUS run of points, so that a partition keeps the original order with one scan over threads
-  const int chunk = (M + CUT_T - 1) / CUT_T;      // <= 64
-  const int lo = tid * chunk < M ? tid * chunk : M, hi = lo + chunk < M ? lo + chunk : M;
-  for (int j = lo; j < hi; ++j) lab[j] = 0;
+// What a workgroup of either kernel holds about its sample: the dynamic LDS region cut into its tables, and the run of points
+// this thread owns.
+struct FractureBlock {
+  int* slots;
+  int* wave_base;
+  float* anchor;             // [FR_KC][4]
+  uint8_t* lab;              // [M]
+  const float* g;            // the sample's cloud
+  int lo, hi;                // this thread's run of points
+};
 
-  int cnt[FR_MAX_P];          // points per label: the same in every thread; only ever indexed by unrolled loops (registers)
-#pragma unroll
-  for (int p = 0; p < FR_MAX_P; ++p) cnt[p] = p == 0 ? M : 0;
+__device__ __forceinline__ FractureBlock fracture_block(unsigned char* smem, const float* raw, int M) {
+  FractureBlock w;
+  w.slots = reinterpret_cast<int*>(smem + FR_SLOTS);
+  w.wave_base = reinterpret_cast<int*>(smem + FR_WBASE);
+  w.anchor = reinterpret_cast<float*>(smem + FR_ANCHOR);
+  w.lab = smem + FR_LABELS;
+  w.g = raw + (size_t)blockIdx.x * M * 3;
+  // a thread owns a CONTIGUOUS run of points, so that a partition keeps the original order with one scan over threads
+  const int tid = threadIdx.x, chunk = (M + CUT_T - 1) / CUT_T;      // <= 64
+  w.lo = tid * chunk < M ? tid * chunk : M;
+  w.hi = w.lo + chunk < M ? w.lo + chunk : M;
+  return w;
+}
+
+// Steps s = 1 .. steps of the rule on sample blockIdx.x (both kernels; steps <= P - 1, uniform over the workgroup): the labels in
+// w.lab, the counts per label in cnt (the same in every thread), planes / target / cand rows 0 .. steps - 1 written by thread 0.
+// nrm0, ua0: the sample's normals [P-1,K,3] and anchor draws [P-1,K]; planes, target, cand: the sample's rows.  last_t: the
+// target of the last step.  -> every step had a valid candidate
+__device__ __forceinline__ bool fracture_cuts(const FractureBlock& w, const double* nrm0, const double* ua0, int K, int n_min,
+                                              int steps, int (&cnt)[FR_MAX_P], double* planes, int32_t* target, int32_t* cand,
+                                              int& last_t) {
+  int* slots = w.slots;
+  int* wave_base = w.wave_base;
+  float* anchor = w.anchor;
+  uint8_t* lab = w.lab;
+  const float* g = w.g;
+  const int lo = w.lo, hi = w.hi, tid = threadIdx.x;
   bool all_valid = true;
 
-  for (int s = 1; s < P; ++s) {
+  for (int s = 1; s <= steps; ++s) {
     // 1. the target: the first largest label among 0 .. s-1
     int t = 0, n_t = cnt[0];
 #pragma unroll
@@ -77,8 +103,8 @@ __global__ __launch_bounds__(CUT_T) void fracture_kernel(FractureArgs a) {
     const int c_t = __popcll(tbits);
     const int before = block_excl_scan(c_t, slots, wave_base);      // target members in front of this run
 
-    const double* nrm = a.normals + ((size_t)b * (P - 1) + (s - 1)) * K * 3;
-    const double* ua = a.u_anchor + ((size_t)b * (P - 1) + (s - 1)) * K;
+    const double* nrm = nrm0 + (size_t)(s - 1) * K * 3;
+    const double* ua = ua0 + (size_t)(s - 1) * K;
     int chosen = -1, best_k = 0, best_bal = -1, best_up = 0;
     uint64_t sel = 0;        // the run's target members on the DOWN side of the candidate that is taken
     Plane taken{0.0, 0.0, 0.0, 0.0};
@@ -112,7 +138,7 @@ __global__ __launch_bounds__(CUT_T) void fracture_kernel(FractureArgs a) {
         // 4. the first valid candidate, else the most balanced one (uniform: every thread holds the same sum)
         const int up = block_sum(c, slots);
         const int bal = up < n_t - up ? up : n_t - up;
-        const bool valid = up >= a.n_min && n_t - up >= a.n_min;
+        const bool valid = up >= n_min && n_t - up >= n_min;
         if (bal > best_bal || valid) sel = down, taken = q, best_up = up;
         if (bal > best_bal) best_bal = bal, best_k = k;
         if (valid) {
@@ -131,12 +157,35 @@ __global__ __launch_bounds__(CUT_T) void fracture_kernel(FractureArgs a) {
       if (p == s) cnt[p] = n_t - best_up;
     }
     if (tid == 0) {
-      double* pl = a.planes + ((size_t)b * (P - 1) + (s - 1)) * 4;
+      double* pl = planes + (size_t)(s - 1) * 4;
       pl[0] = taken.n0, pl[1] = taken.n1, pl[2] = taken.n2, pl[3] = taken.off;
-      a.target[(size_t)b * (P - 1) + (s - 1)] = t;
-      a.cand[(size_t)b * (P - 1) + (s - 1)] = chosen;
+      target[s - 1] = t;
+      cand[s - 1] = chosen;
     }
+    last_t = t;
   }
+  return all_valid;
+}
+
+__global__ __launch_bounds__(CUT_T) void fracture_kernel(FractureArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int M = a.M, P = a.P, K = a.K;
+  const FractureBlock w = fracture_block(smem, a.raw, M);
+  int* slots = w.slots;
+  int* wave_base = w.wave_base;
+  uint8_t* lab = w.lab;
+  const float* g = w.g;
+  const int lo = w.lo, hi = w.hi;
+  for (int j = lo; j < hi; ++j) lab[j] = 0;
+
+  int cnt[FR_MAX_P];          // points per label: the same in every thread; only ever indexed by unrolled loops (registers)
+#pragma unroll
+  for (int p = 0; p < FR_MAX_P; ++p) cnt[p] = p == 0 ? M : 0;
+  int last_t = 0;
+  const bool all_valid = fracture_cuts(w, a.normals + (size_t)b * (P - 1) * K * 3, a.u_anchor + (size_t)b * (P - 1) * K, K, a.n_min,
+                                       P - 1, cnt, a.planes + (size_t)b * (P - 1) * 4, a.target + (size_t)b * (P - 1),
+                                       a.cand + (size_t)b * (P - 1), last_t);
 
   // the pieces: a stable P-way partition, one scan per label; `order` is the same partition without the cap
   for (int j = lo; j < hi; ++j) a.label[(size_t)b * M + j] = lab[j];
@@ -168,6 +217,120 @@ __global__ __launch_bounds__(CUT_T) void fracture_kernel(FractureArgs a) {
   if (tid == 0) a.ok[b] = (all_valid && fits) ? 1 : 0;
 }
 
+// The training pair of a fractured sample (datapipe.fracture_pair_rule): the cuts of a P_b-piece fracture, the pair chosen on
+// the device, and only the chosen pieces written - what a loader beside the training step needs of a fracture.
+constexpr int FP_UNIFORMS = 7;       // u_kind, u_a, u_c, u_sU, u_sD, u_sFU, u_sFD
+enum PairKind { SIBLING = 0, NEIGHBOUR = 1 };
+
+struct FracturePairArgs {
+  const float* raw;          // [B, M, 3]
+  const double* normals;     // [B, P-1, K, 3]
+  const double* u_anchor;    // [B, P-1, K]
+  const int32_t* n_pieces;   // [B]: P_b, 2 .. P
+  const double* u;           // [B, 7]
+  double neighbours;
+  int B, M, P, K, n_min, cap;
+  float* pieces;             // [4B, cap, 3]: U, D, fallback U, fallback D
+  int64_t* counts;           // [4B]: -1 = no such piece
+  int64_t* start;            // [4B]
+  int32_t* kind;             // [B]
+  int32_t* pair;             // [B, 4]: the labels of the four pieces, -1 = none
+  uint8_t* label;            // [B, M]
+  double* planes;            // [B, P-1, 4]
+  int32_t* target;           // [B, P-1]
+  int32_t* cand;             // [B, P-1]
+  uint8_t* ok;               // [B]
+};
+
+__global__ __launch_bounds__(CUT_T) void fracture_pair_kernel(FracturePairArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int M = a.M, P = a.P, K = a.K;
+  const FractureBlock w = fracture_block(smem, a.raw, M);
+  int* slots = w.slots;
+  int* wave_base = w.wave_base;
+  uint8_t* lab = w.lab;
+  const float* g = w.g;
+  const int lo = w.lo, hi = w.hi;
+  for (int j = lo; j < hi; ++j) lab[j] = 0;
+
+  // a count outside 2 .. P (the host refuses the ones it can see): no cut, no piece, ok = 0
+  const int asked = a.n_pieces[b];
+  const bool in_range = asked >= 2 && asked <= P;
+  const int Pb = in_range ? asked : 1;
+  int cnt[FR_MAX_P];          // points per label: the same in every thread; only ever indexed by unrolled loops (registers)
+#pragma unroll
+  for (int p = 0; p < FR_MAX_P; ++p) cnt[p] = p == 0 ? M : 0;
+  double* planes = a.planes + (size_t)b * (P - 1) * 4;
+  int32_t* target = a.target + (size_t)b * (P - 1);
+  int32_t* cand = a.cand + (size_t)b * (P - 1);
+  int last_t = 0;
+  const bool all_valid = fracture_cuts(w, a.normals + (size_t)b * (P - 1) * K * 3, a.u_anchor + (size_t)b * (P - 1) * K, K, a.n_min,
+                                       Pb - 1, cnt, planes, target, cand, last_t);
+  // the steps that were not made: zero rows
+  for (int i = (Pb - 1) * 4 + tid; i < (P - 1) * 4; i += CUT_T) planes[i] = 0.0;
+  for (int i = Pb - 1 + tid; i < P - 1; i += CUT_T) target[i] = 0, cand[i] = 0;
+  for (int j = lo; j < hi; ++j) a.label[(size_t)b * M + j] = lab[j];
+
+  // the pair (uniform: every thread reads the same draws and holds the same last target)
+  const double* u = a.u + (size_t)b * FP_UNIFORMS;
+  int kind = SIBLING;
+  int lab4[4] = {last_t, Pb - 1, -1, -1};      // U, D, fallback U, fallback D; the sibling pair: the two sides of the last cut
+  if (Pb >= 3 && u[0] < a.neighbours) {
+    int pa = (int)floor(u[1] * (double)Pb);
+    pa = pa > Pb - 1 ? Pb - 1 : pa;
+    int pc = (int)floor(u[2] * (double)(Pb - 1));
+    pc = pc > Pb - 2 ? Pb - 2 : pc;
+    pc += pc >= pa ? 1 : 0;
+    const bool sibling = (pa == lab4[0] && pc == lab4[1]) || (pa == lab4[1] && pc == lab4[0]);
+    if (!sibling) kind = NEIGHBOUR, lab4[2] = lab4[0], lab4[3] = lab4[1], lab4[0] = pa, lab4[1] = pc;
+  }
+  if (!in_range) lab4[0] = lab4[1] = -1;
+
+  // the pieces: a stable partition of the chosen labels only, one scan each
+  bool fits = true;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    float* dst = a.pieces + ((size_t)q * a.B + b) * a.cap * 3;
+    const int lq = lab4[q];
+    if (lq < 0) {            // no such piece: rows of the cloud's first point, count -1 (the sampling skips it)
+      pad_piece(dst, 0, a.cap, g);
+      if (tid == 0) a.counts[(size_t)q * a.B + b] = -1, a.start[(size_t)q * a.B + b] = 0;
+      continue;
+    }
+    int c = 0;
+    for (int j = lo; j < hi; ++j) c += lab[j] == lq ? 1 : 0;
+    int at = block_excl_scan(c, slots, wave_base);      // rows of the label in front of this run
+    const int n_p = slots[0];
+    for (int j = lo; j < hi; ++j) {
+      if (lab[j] != lq) continue;
+      if (at < a.cap) dst[(size_t)at * 3] = g[3 * j], dst[(size_t)at * 3 + 1] = g[3 * j + 1], dst[(size_t)at * 3 + 2] = g[3 * j + 2];
+      ++at;
+    }
+    __syncthreads();         // the piece's first row is in memory for this workgroup
+    pad_piece(dst, n_p, a.cap, g);
+    fits = fits && n_p <= a.cap;
+    if (tid == 0) {
+      a.counts[(size_t)q * a.B + b] = n_p;
+      a.start[(size_t)q * a.B + b] = start_index(u[3 + q], n_p);
+    }
+  }
+  if (tid == 0) {
+    a.kind[b] = in_range ? kind : -1;
+    int32_t* pr = a.pair + (size_t)b * 4;
+    pr[0] = lab4[0], pr[1] = lab4[1], pr[2] = lab4[2], pr[3] = lab4[3];
+    a.ok[b] = (in_range && all_valid && fits) ? 1 : 0;
+  }
+}
+
+// the dynamic LDS of either kernel: <= 64.4 KiB
+int fracture_lds(const void* kernel, int M, size_t* lds) {
+  *lds = (size_t)FR_LABELS + ((size_t)M + 15) / 16 * 16;
+  if (*lds > 64 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds) != hipSuccess)
+    return PZN_ELAUNCH;
+  return PZN_OK;
+}
+
 }  // namespace
 
 PZN_EXPORT int pzn_fracture_supported(int M, int P, int K) {
@@ -182,10 +345,26 @@ PZN_EXPORT int pzn_fracture_f32(const float* raw, const double* normals, const d
   PZN_CHECK_ARG(B > 0 && cap > 0 && n_min >= 0);
   if (!pzn_fracture_supported(M, P, K)) return PZN_EUNSUPPORTED;
   FractureArgs a{raw, normals, u_anchor, u_start, B, M, P, K, n_min, cap, pieces, counts, start, label, order, planes, target, cand, ok};
-  const size_t lds = (size_t)FR_LABELS + ((size_t)M + 15) / 16 * 16;      // <= 64.4 KiB
-  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(fracture_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return PZN_ELAUNCH;
+  size_t lds;
+  if (fracture_lds(reinterpret_cast<const void*>(fracture_kernel), M, &lds) != PZN_OK) return PZN_ELAUNCH;
   PZN_LAUNCH(fracture_kernel, dim3(B), dim3(CUT_T), lds, pzn_hip_stream(stream), a);
+  PZN_RETURN_LAUNCH_STATUS();
+}
+
+PZN_EXPORT int pzn_fracture_pair_supported(int M, int P, int K) { return pzn_fracture_supported(M, P, K); }
+
+PZN_EXPORT int pzn_fracture_pair_f32(const float* raw, const double* normals, const double* u_anchor, const int32_t* n_pieces,
+                                     const double* u, double neighbours, int B, int M, int P, int K, int n_min, int cap,
+                                     float* pieces, int64_t* counts, int64_t* start, int32_t* kind, int32_t* pair, uint8_t* label,
+                                     double* planes, int32_t* target, int32_t* cand, uint8_t* ok, pzn_stream_t stream) {
+  PZN_CHECK_ARG(raw && normals && u_anchor && n_pieces && u && pieces && counts && start && kind && pair && label && planes &&
+                target && cand && ok);
+  PZN_CHECK_ARG(B > 0 && cap > 0 && n_min >= 0 && neighbours >= 0.0 && neighbours <= 1.0);
+  if (!pzn_fracture_pair_supported(M, P, K)) return PZN_EUNSUPPORTED;
+  FracturePairArgs a{raw, normals, u_anchor, n_pieces, u, neighbours, B, M, P, K, n_min, cap, pieces, counts, start, kind, pair,
+                     label, planes, target, cand, ok};
+  size_t lds;
+  if (fracture_lds(reinterpret_cast<const void*>(fracture_pair_kernel), M, &lds) != PZN_OK) return PZN_ELAUNCH;
+  PZN_LAUNCH(fracture_pair_kernel, dim3(B), dim3(CUT_T), lds, pzn_hip_stream(stream), a);
   PZN_RETURN_LAUNCH_STATUS();
 }

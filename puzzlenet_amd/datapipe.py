@@ -34,7 +34,10 @@ tests/test_gpu_solid_feeder.py holds its pieces to the oracle's masks bit for bi
 `PairFeeder(..., split_twice=True)` is the reference's second sampling mode (`train.py --random_slice`, dataset.py:1203-1355):
 the double cuts, decided and compacted on the device in one launch (`double_cut_rule` states the rule, csrc/doublecut.hip runs
 it, `cut_pairs_double` samples the pair and its fallback and applies the reference's acceptance test without a host round trip).
-The three modes share one `next_batch` (staging turn, pinned upload, events) and one tail from the compacted pieces to the
+`PairFeeder(..., pieces=P | (lo, hi))` cuts pairs out of P-piece fractures (no counterpart in the reference): the fracture's
+cuts, the choice of the pair and the compaction of its pieces alone are one launch (`fracture_pair_rule` states the rule,
+csrc/fracture.hip runs it, `cut_pairs_fracture` samples the pair and its fallback as `cut_pairs_double` does).
+The four modes share one `next_batch` (staging turn, pinned upload, events) and one tail from the compacted pieces to the
 8-tuple (`_sample`, `_picks`, `_finish`); a mode is a staging layout, a host draw function and a builder.
 """
 import collections
@@ -367,6 +370,43 @@ def cut_pairs_double(raw, normals1, zs1, normals2, zs2, u, twist, n=1024, n_rich
     return _finish(both, top, fbnd, twist), ok & (counts[:B] >= n) & (counts[B:2 * B] >= n), record
 
 
+FracturePair = collections.namedtuple("FracturePair", "kind pair rejected cd label planes target cand U D Ub Db")
+FracturePair.__doc__ = """What cut_pairs_fracture decided per sample: kind [B] int32 (SIBLING, NEIGHBOUR), pair [B,4] int32 (the labels of U, D and
+of the fallback pair, -1: none), rejected [B] bool (the NEIGHBOUR pair was replaced by the sibling pair), cd [B] float32 (chamfer
+distance of the primary pair's boundaries), the fracture itself (label [B,M] uint8, planes [B,P-1,4] float64, target / cand
+[B,P-1] int32; rows of the cuts a sample did not make are zero) and the PRIMARY pair (U, D [B,n,3]; Ub, Db [B,k,3]), from which cd
+can be recomputed."""
+
+
+def cut_pairs_fracture(raw, normals, u_anchor, pieces, u, twist, n=1024, k=128, neighbours=0.5, cap=None):
+    """cut_pairs for pairs cut out of a fracture (the rule: fracture_pair_rule): every cloud cut into pieces[b] pieces, the pair
+    chosen and only its pieces - and the fallback's - compacted in one launch (csrc/fracture.hip, ops.fracture_pair; the cuts
+    leave >= n points on both sides, n_min = n); then, as cut_pairs_double does, the sampling of the primary and of the fallback
+    rows (one launch for both; rounds run for the fallback rows of the NEIGHBOUR samples only: the other rows carry
+    counts = -1), the primary pair's boundary, step 8 (`cd` of the two boundaries against CD_ACCEPT) as a device-side select,
+    and cut_pairs' tail on the final pair.  Nothing here reads a value back to the host.  raw [B,M,3]; normals [B,P-1,K,3],
+    u_anchor [B,P-1,K], u [B,7] float64 draws; pieces: ops.fracture_pair's; twist [B,6].
+    -> ((D, moved U, igt, U, D boundary, U boundary, D mask, U mask), ok [B], FracturePair)"""
+    cap = _feeder_cap("cut_pairs_fracture", raw, cap)
+    B, M, _ = raw.shape
+    packed, counts, start, kind, pair, label, planes, target, cand, ok = ops.fracture_pair(raw, normals, u_anchor, pieces, u, n,
+                                                                                          neighbours, cap)
+    # [2B,n,3] each: U rows, D rows (every cut left >= n points on its other side, so a piece holds <= M - n).  The primary and
+    # the fallback rows are sampled in ONE launch: a sampling launch lasts its n dependent rounds however few workgroups run them
+    # (measured: the fallback rows of half the samples alone cost what the primary rows cost), and the picks of a row do not
+    # depend on the rows beside it
+    sampled = _sample(packed, counts, start, n, M)
+    primary, fallback = sampled[:2 * B], sampled[2 * B:]
+    _, bnd = _picks(primary, k)
+    cd1, cd2 = ops.chamfer(bnd[B:], bnd[:B])
+    cd = cd1.mean(1) + cd2.mean(1)
+    rejected = fracture_pair_rejects(kind, cd)
+    both = torch.where(rejected.repeat(2).view(2 * B, 1, 1), fallback, primary)
+    top, fbnd = _picks(both, k)
+    record = FracturePair(kind, pair, rejected, cd, label, planes, target, cand, primary[:B], primary[B:], bnd[:B], bnd[B:])
+    return _finish(both, top, fbnd, twist), ok & (counts[:B] >= n) & (counts[B:2 * B] >= n), record
+
+
 def _cols(*widths):
     """Column slices of a staging row that holds blocks of these widths side by side."""
     c = np.cumsum((0,) + widths)
@@ -456,6 +496,7 @@ class PairBatch(list):
     plane = None      # (normal [B,3], z [B]) float64: the plane each sample was cut with (cut="plane")
     cut = None        # (kind, rot [B,3], shift [B,3]) float64: the solid each sample was cut with (cut=a solid)
     double = None     # DoubleCut: kind, planes, region tables, the acceptance test's outcome (split_twice=True)
+    fracture = None   # FracturePair: kind, labels of the pair, the acceptance test's outcome, the fracture itself (pieces=...)
 
 
 class PairFeeder:
@@ -467,13 +508,30 @@ class PairFeeder:
     in next_batch() waits for the device.  engine.TrainStep.step(next_batch=feeder.next_batch()) orders its streams behind
     `ready` and keeps the tensors alive across the streams that read them.
     split_twice=True (cut="plane" only): the reference's `train.py --random_slice`, i.e. CADDataset(split_twice=True) - the
-    double cuts of dataset.py:1203-1355 by cut_pairs_double, with n_rich = 3000 n / 1024; batch.double says what was cut."""
+    double cuts of dataset.py:1203-1355 by cut_pairs_double, with n_rich = 3000 n / 1024; batch.double says what was cut.
+    pieces=P or (lo, hi) (cut="plane", split_twice=False only; 2 <= lo <= hi <= 16): pairs cut out of a fracture - every sample
+    is cut into lo + floor(u (hi - lo + 1)) pieces (u drawn per sample on the host) and one pair of final pieces is taken, the
+    two sides of the last cut or, for a share `neighbours` of the samples, a drawn pair with those two as its fallback
+    (fracture_pair_rule, cut_pairs_fracture); batch.fracture says what was cut and batch.plane stays None."""
 
-    def __init__(self, raw, device, n=1024, k=128, mag=0.8, candidates=16, seed=0, cut="plane", split_twice=False):
+    def __init__(self, raw, device, n=1024, k=128, mag=0.8, candidates=16, seed=0, cut="plane", split_twice=False, pieces=None,
+                 neighbours=0.5):
         if cut != "plane" and cut not in ops.SOLID_KINDS:
             raise _lib.PznError(f"PairFeeder: cut={cut!r} (one of 'plane', 'sphere', 'cylinder', 'cone')")
         if split_twice and cut != "plane":
             raise _lib.PznUnsupported(f"PairFeeder: split_twice=True cuts with planes (cut={cut!r})")
+        if pieces is not None:
+            if cut != "plane" or split_twice:
+                raise _lib.PznUnsupported(f"PairFeeder: pieces={pieces!r} fractures with planes, one pair per sample "
+                                          f"(cut={cut!r}, split_twice={bool(split_twice)})")
+            lo, hi = (pieces, pieces) if isinstance(pieces, (int, np.integer)) else pieces
+            lo, hi = int(lo), int(hi)
+            if not 2 <= lo <= hi <= 16:
+                raise _lib.PznUnsupported(f"PairFeeder: pieces={pieces!r} (an int P or a pair (lo, hi), 2 <= lo <= hi <= 16)")
+            pieces = (lo, hi)
+        if not 0.0 <= float(neighbours) <= 1.0:
+            raise _lib.PznError(f"PairFeeder: neighbours={neighbours!r} (a share of the samples, in [0, 1])")
+        self.pieces, self.neighbours = pieces, float(neighbours)
         self.cut, self.split_twice = cut, bool(split_twice)
         raw = torch.as_tensor(raw, dtype=torch.float32)
         if raw.dim() != 3 or raw.shape[2] != 3:
@@ -488,6 +546,8 @@ class PairFeeder:
         self.stream = torch.cuda.Stream(device=self.device)
         B = self.raw.shape[0]
         self._mode = _DOUBLE_MODE if self.split_twice else (_PLANE_MODE if cut == "plane" else _SOLID_MODE)
+        if self.pieces is not None:
+            self._mode = _fracture_pair_mode(*self.pieces)
         # one pinned staging block per batch in flight (two: the upload of batch k + 1 may still be queued when k + 2 is drawn)
         self._width = self._mode.cols(self.K)[-1].stop
         self._stage = [torch.empty((B, self._width), dtype=torch.float64, pin_memory=True) for _ in range(3)]
@@ -734,14 +794,27 @@ def fracture_rule(raw, normals, u_anchor, u_start, P, n_min, cap=None):
     raw = np.asarray(raw, dtype=np.float32)
     normals, u_anchor, u_start = (np.asarray(t, dtype=np.float64) for t in (normals, u_anchor, u_start))
     M, P = raw.shape[0], int(P)
-    K = normals.shape[1]
     cap = M if cap is None else int(cap)
+    label, planes, target, cand, ok = _fracture_steps(raw, normals, u_anchor, P, P - 1, n_min)
+    counts = np.bincount(label, minlength=P).astype(np.int64)
+    order = np.argsort(label, kind="stable").astype(np.int32)
+    pieces = [_pad_rows(raw[label == p], cap, raw[0]) for p in range(P)]
+    start = np.array([_start_index(u_start[p], counts[p]) for p in range(P)], dtype=np.int64)
+    return dict(label=label, counts=counts, pieces=pieces, order=order, start=start, planes=planes, target=target, cand=cand,
+                ok=bool(ok and counts.max() <= cap))
+
+
+def _fracture_steps(raw, normals, u_anchor, P, steps, n_min):
+    """Steps s = 1 .. steps (<= P - 1) of fracture_rule on raw [M,3] float32; normals [P-1,K,3], u_anchor [P-1,K] float64.
+    -> (label [M] uint8, planes [P-1,4], target [P-1], cand [P-1] with the rows of the steps not made zero, every step made had
+    a valid candidate)"""
+    M, K = raw.shape[0], normals.shape[1]
     p64 = raw.astype(np.float64)
     label = np.zeros(M, dtype=np.uint8)
     planes = np.zeros((P - 1, 4), dtype=np.float64)
     target, cand = np.zeros(P - 1, dtype=np.int32), np.zeros(P - 1, dtype=np.int32)
     ok = True
-    for s in range(1, P):
+    for s in range(1, steps + 1):
         count = np.bincount(label, minlength=P)
         t = int(np.argmax(count[:s]))                                 # (argmax: the first among equals)
         members = np.flatnonzero(label == t)
@@ -763,11 +836,68 @@ def fracture_rule(raw, normals, u_anchor, u_start, P, n_min, cap=None):
         _, cand[s - 1], planes[s - 1], up = best
         target[s - 1] = t
         label[members[~up]] = s
-    counts = np.bincount(label, minlength=P).astype(np.int64)
-    order = np.argsort(label, kind="stable").astype(np.int32)
-    pieces = [_pad_rows(raw[label == p], cap, raw[0]) for p in range(P)]
-    start = np.array([_start_index(u_start[p], counts[p]) for p in range(P)], dtype=np.int64)
-    return dict(label=label, counts=counts, pieces=pieces, order=order, start=start, planes=planes, target=target, cand=cand,
+    return label, planes, target, cand, ok
+
+
+# A training pair cut out of a fracture, as the FEEDER samples it (PairFeeder(pieces=...)).
+SIBLING, NEIGHBOUR = 0, 1                                    # `kind` codes (ops.FRACTURE_PAIR_KINDS names them)
+
+
+def fracture_pair_rejects(kind, cd):
+    """Step 8 of fracture_pair_rule (numpy arrays or tensors): the drawn pair is replaced by the sibling pair."""
+    return (kind == NEIGHBOUR) & (cd > CD_ACCEPT)
+
+
+def fracture_pair_rule(raw, normals, u_anchor, u, pieces, P, n_min, neighbours, cap=None):
+    """The training pair of ONE sample cut out of a fracture, in numpy on the host: the statement that pzn_fracture_pair_f32
+    (csrc/fracture.hip, steps 1-7) and cut_pairs_fracture (step 8) implement and the tests hold them to, bit for bit.
+      raw        [M,3] float32
+      normals    [P-1,K,3], u_anchor [P-1,K] float64: as fracture_rule takes them
+      u          [7] float64 uniforms: u_kind, u_a, u_c, u_sU, u_sD, u_sFU, u_sFD
+      pieces     P_b, this sample's number of pieces, 2 <= P_b <= P
+      n_min      points both sides of a cut must hold;  cap: rows a piece may hold (None: M)
+      neighbours the share of samples whose pair is drawn among all final pieces, in [0, 1]
+    The rule:
+      1. steps 1-5 of fracture_rule for s = 1 .. P_b - 1 (the draw rows of later steps are not read; planes, target and cand
+         rows from P_b - 1 on are zero).
+      2. the SIBLING pair is U = target[P_b-2], the up side of the last cut, which keeps its label, and D = P_b - 1, its down
+         side: both are final pieces, and they touch along the whole of that cut.
+      3. the kind is NEIGHBOUR iff P_b >= 3 and u_kind < neighbours, with a = min(P_b - 1, floor(u_a P_b)),
+         c' = min(P_b - 2, floor(u_c (P_b - 1))), c = c' + (c' >= a) - an ordered pair of distinct final pieces - unless {a, c}
+         is the sibling pair in either order: then, and otherwise, the kind is SIBLING.
+      4. SIBLING: the primary pair is the sibling pair and there is no fallback (counts -1, pieces None, start 0, as
+         double_cut_rule lays out a missing fallback).
+      5. NEIGHBOUR: the primary pair is (U, D) = (a, c) and the fallback is the sibling pair.
+      6. the four pieces [U, D, fallback U, fallback D] are the rows of their labels in the cloud's order, padded as pad_piece
+         does; start = start_index(u_sU / u_sD / u_sFU / u_sFD, count).
+      7. ok: every step made had a valid candidate and every written piece fits in cap.  With n_min = n every cut of an ok
+         sample left >= n points on both sides, and a later cut of either side leaves >= n on both of its sides again, so every
+         final piece - whichever pair is drawn - holds >= n points.
+      8. (on the sampled pieces, so not here: fracture_pair_rejects) NEIGHBOUR only: cd = mean(cd1) + mean(cd2) of the chamfer
+         distances between the two k-point boundaries; cd > CD_ACCEPT: the fallback pair, sampled from its own start indices,
+         replaces the pair.
+    -> dict(kind, pair [4] int32 labels (-1: none), pieces: four [cap,3] arrays (None where there is no fallback), counts [4]
+       (-1 there), start [4], label [M] uint8, planes [P-1,4], target [P-1], cand [P-1], ok)"""
+    raw = np.asarray(raw, dtype=np.float32)
+    normals, u_anchor, u = (np.asarray(t, dtype=np.float64) for t in (normals, u_anchor, u))
+    M, P, Pb = raw.shape[0], int(P), int(pieces)
+    if not 2 <= Pb <= P or not 0.0 <= neighbours <= 1.0 or u.shape != (7,):
+        raise _lib.PznError(f"fracture_pair_rule: pieces = {Pb} of P = {P}, neighbours = {neighbours}, u {u.shape}")
+    cap = M if cap is None else int(cap)
+    label, planes, target, cand, ok = _fracture_steps(raw, normals, u_anchor, P, Pb - 1, n_min)
+    sibling = (int(target[Pb - 2]), Pb - 1)
+    kind, pair = SIBLING, sibling + (-1, -1)
+    if Pb >= 3 and u[0] < neighbours:
+        a = min(Pb - 1, int(np.floor(u[1] * np.float64(Pb))))
+        c = min(Pb - 2, int(np.floor(u[2] * np.float64(Pb - 1))))
+        c += c >= a
+        if (a, c) != sibling and (c, a) != sibling:
+            kind, pair = NEIGHBOUR, (a, c) + sibling
+    rows = [None if p < 0 else raw[label == p] for p in pair]
+    counts = np.array([-1 if r is None else len(r) for r in rows], dtype=np.int64)
+    start = np.array([0 if cnt < 0 else _start_index(u[3 + i], cnt) for i, cnt in enumerate(counts)], dtype=np.int64)
+    return dict(kind=kind, pair=np.array(pair, dtype=np.int32), pieces=[None if r is None else _pad_rows(r, cap, raw[0]) for r in rows],
+                counts=counts, start=start, label=label, planes=planes, target=target, cand=cand,
                 ok=bool(ok and counts.max() <= cap))
 
 
@@ -829,13 +959,50 @@ def draw_fracture_batch(rng, gen, B, P, K, mag, out):
     """The host draws of one fracture batch into out [B, width] float64 (columns: _fracture_cols(P, K)): candidate normals
     randn(3) normalised, the anchor and start uniforms from rng, one twist per piece from gen."""
     normals, u_anchor, u_start, tw = _fracture_cols(P, K)
-    v = rng.randn(B, (P - 1) * K, 3)
-    out[:, normals] = (v / np.linalg.norm(v, axis=2, keepdims=True)).reshape(B, -1)
-    out[:, u_anchor] = rng.rand(B, (P - 1) * K)
+    _draw_fracture_cuts(rng, B, P, K, out, normals, u_anchor)
     out[:, u_start] = rng.rand(B, P)
     twist = np.empty((B * P, 6), dtype=np.float64)
     _draw_twist(gen, mag, twist)
     out[:, tw] = twist.reshape(B, 6 * P)
+
+
+def _draw_fracture_cuts(rng, B, P, K, out, normals, u_anchor):
+    """The cut draws of a fracture (both fracture forms): candidate normals randn(3) normalised, then the anchor uniforms."""
+    v = rng.randn(B, (P - 1) * K, 3)
+    out[:, normals] = (v / np.linalg.norm(v, axis=2, keepdims=True)).reshape(B, -1)
+    out[:, u_anchor] = rng.rand(B, (P - 1) * K)
+
+
+def _fracture_pair_cols(P, K):  # normals, anchor draws, the number of pieces, uniforms, twist
+    return _cols(3 * (P - 1) * K, (P - 1) * K, 1, ops.FRACTURE_PAIR_UNIFORMS, 6)
+
+
+def draw_fracture_pair_batch(rng, gen, B, lo, hi, K, mag, out):
+    """The host draws of one PairFeeder(pieces=(lo, hi)) batch into out [B, width] float64 (columns: _fracture_pair_cols(hi, K)):
+    the cut draws of draw_fracture_batch for P = hi (a sample with fewer pieces leaves the later rows unread), the number of
+    pieces lo + floor(u (hi - lo + 1)) from one rng.rand(B), the seven uniforms of fracture_pair_rule, one twist per sample."""
+    normals, u_anchor, pc, u, tw = _fracture_pair_cols(hi, K)
+    _draw_fracture_cuts(rng, B, hi, K, out, normals, u_anchor)
+    out[:, pc] = np.minimum(hi, lo + np.floor(rng.rand(B, 1) * (hi - lo + 1)))
+    out[:, u] = rng.rand(B, ops.FRACTURE_PAIR_UNIFORMS)                         # u_kind, u_a, u_c, u_sU, u_sD, u_sFU, u_sFD
+    _draw_twist(gen, mag, out[:, tw])
+
+
+def _build_fracture_pair(f, d):
+    B, K, P = d.shape[0], f.K, f.pieces[1]
+    normals, u_anchor, pc, u, tw = _fracture_pair_cols(P, K)
+    tensors, ok, record = cut_pairs_fracture(f.raw, d[:, normals].reshape(B, P - 1, K, 3), d[:, u_anchor].reshape(B, P - 1, K),
+                                             d[:, pc].reshape(B).to(torch.int32), d[:, u], d[:, tw], n=f.n, k=f.k,
+                                             neighbours=f.neighbours)
+    return tensors, ok, dict(fracture=record)
+
+
+def _fracture_pair_mode(lo, hi):
+    """The feeder mode of PairFeeder(pieces=(lo, hi)): the protocol's cols(K) and draw(rng, gen, B, K, mag, out) with the range
+    bound."""
+    return _FeederMode(lambda K: _fracture_pair_cols(hi, K),
+                       lambda rng, gen, B, K, mag, out: draw_fracture_pair_batch(rng, gen, B, lo, hi, K, mag, out),
+                       _build_fracture_pair)
 
 
 def fracture_draws(rng, gen, B, P, K, mag):

@@ -630,6 +630,68 @@ def fracture(raw, normals, u_anchor, u_start, n_min, cap):
     return pieces, counts, start, label, order, planes, target, cand, ok.to(torch.bool)
 
 
+FRACTURE_PAIR_KINDS = ("sibling", "neighbour")      # the `kind` codes of pzn_fracture_pair_f32
+FRACTURE_PAIR_UNIFORMS = 7                          # u_kind, u_a, u_c, u_sU, u_sD, u_sFU, u_sFD
+
+
+def fracture_pair_supported(M, P, K):
+    return bool(_lib.load().pzn_fracture_pair_supported(int(M), int(P), int(K)))
+
+
+def fracture_pair(raw, normals, u_anchor, pieces, u, n_min, neighbours, cap):
+    """A training pair cut out of a fracture of every cloud of a batch in one launch (pzn_fracture_pair_f32; the rule:
+    datapipe.fracture_pair_rule): raw [B,M,3] f32; normals [B,P-1,K,3], u_anchor [B,P-1,K], u [B,7], all float64 on the GPU (no
+    silent conversion: PznError); pieces: the number of pieces P_b of every sample, 2 <= P_b <= P - an int, a sequence or a CPU
+    tensor (checked here, PznError, before any launch) or an int32 tensor [B] on the GPU (nothing waits for the device: the
+    launch itself refuses a sample out of range with kind -1, no pieces and ok = 0); neighbours in [0, 1]
+    -> (pieces [4B,cap,3]: U, D, fallback U, fallback D; counts [4B] int64, -1 where there is no fallback; start [4B] int64;
+        kind [B] int32; pair [B,4] int32; label [B,M] uint8; planes [B,P-1,4] float64; target, cand [B,P-1] int32; ok [B] bool)
+    2 <= P <= 16, K >= 1, M <= 65536 (PznUnsupported beyond)."""
+    for name, t, dt in (("raw", raw, torch.float32), ("normals", normals, torch.float64), ("u_anchor", u_anchor, torch.float64),
+                        ("u", u, torch.float64)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.PznError(f"fracture_pair: {name} must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
+        if t.dtype != dt:
+            raise _lib.PznError(f"fracture_pair: {name} must be {dt}; got {t.dtype}")
+    if raw.dim() != 3 or raw.shape[2] != 3 or raw.shape[0] == 0 or raw.shape[1] == 0:
+        raise _lib.PznError(f"fracture_pair: raw as [B, M, 3]; got {tuple(raw.shape)}")
+    B, M, _ = raw.shape
+    if normals.dim() != 4 or normals.shape[0] != B or normals.shape[3] != 3:
+        raise _lib.PznError(f"fracture_pair: normals as [B, P - 1, K, 3]; got {tuple(normals.shape)}")
+    P, K = normals.shape[1] + 1, normals.shape[2]
+    if not fracture_pair_supported(M, P, max(K, 1)):
+        raise _lib.PznUnsupported(f"fracture_pair: M = {M} points into P = {P} pieces (2 <= P <= 16, M <= 65536)")
+    if K < 1 or tuple(u_anchor.shape) != (B, P - 1, K) or tuple(u.shape) != (B, FRACTURE_PAIR_UNIFORMS):
+        raise _lib.PznError(f"fracture_pair: u_anchor as [B, P - 1, K] with K >= 1 and u as [B, {FRACTURE_PAIR_UNIFORMS}]; got "
+                            f"{tuple(u_anchor.shape)}, {tuple(u.shape)}")
+    cap, n_min, neighbours = int(cap), int(n_min), float(neighbours)
+    if cap < 1 or n_min < 0 or not 0.0 <= neighbours <= 1.0:
+        raise _lib.PznError(f"fracture_pair: cap = {cap}, n_min = {n_min}, neighbours = {neighbours}")
+    dev = raw.device
+    if isinstance(pieces, torch.Tensor) and pieces.is_cuda:
+        if pieces.dtype != torch.int32 or tuple(pieces.shape) != (B,):
+            raise _lib.PznError(f"fracture_pair: pieces on the GPU as int32 [B]; got {pieces.dtype} {tuple(pieces.shape)}")
+    else:
+        host = torch.as_tensor(pieces).reshape(-1)
+        if host.numel() == 1:
+            host = host.expand(B)
+        if host.is_floating_point() or host.numel() != B or int(host.min()) < 2 or int(host.max()) > P:
+            raise _lib.PznError(f"fracture_pair: pieces as an integer or B = {B} integers in 2 .. P = {P}; got {pieces!r}")
+        pieces = host.to(torch.int32).to(dev)
+    raw, normals, u_anchor, pieces, u = (t.contiguous() for t in (raw, normals, u_anchor, pieces, u))
+    out, counts, start, ok = _cut_outputs(raw, 4, cap)
+    kind = torch.empty((B,), dtype=torch.int32, device=dev)
+    pair = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    label = torch.empty((B, M), dtype=torch.uint8, device=dev)
+    planes = torch.empty((B, P - 1, 4), dtype=torch.float64, device=dev)
+    target = torch.empty((B, P - 1), dtype=torch.int32, device=dev)
+    cand = torch.empty((B, P - 1), dtype=torch.int32, device=dev)
+    with _on(dev):
+        _call("pzn_fracture_pair_f32", _p(raw), _p(normals), _p(u_anchor), _p(pieces), _p(u), neighbours, B, M, P, K, n_min, cap,
+              _p(out), _p(counts), _p(start), _p(kind), _p(pair), _p(label), _p(planes), _p(target), _p(cand), _p(ok), _stream())
+    return out, counts, start, kind, pair, label, planes, target, cand, ok.to(torch.bool)
+
+
 def pick_mask(idx, N):
     """0/1 float masks [R,N] with ones at idx [R,k] (dataset.py:1363-1366), one launch."""
     idx = _i64(idx, "idx")

@@ -12,7 +12,10 @@ and its cut launch and its two sampling launches beside the plane batch's, each 
 --fracture: only the fracture (datapipe.fracture), B = 64, M = 10000, P = 8 pieces, 16 candidates, pieces of >= 256 points: the
 ops.fracture launch and the single cut's ops.cut_compact launch on the same clouds, alternating, each alone between two device
 events, and the whole datapipe.fracture call (n = 256, k = 64) on a host clock around a device synchronise; the three medians
-and the ratio of the two launches are written to profiles/fracture_batch.txt."""
+and the ratio of the two launches are written to profiles/fracture_batch.txt.
+--pieces P: only the fracture feeder's batch (datapipe.cut_pairs_fracture, PairFeeder(pieces=P)) beside the plane batch on the same
+clouds, B = 64, M = 10000, N = 2048, 16 candidates, alternating inside every repetition; and its cut launch and its two sampling
+launches beside the plane batch's, each alone between two device events (profiles/fracture_feeder_batch.txt holds a run)."""
 import argparse, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,6 +25,7 @@ ap.add_argument("--cut", choices=["plane", "sphere", "cylinder", "cone"], defaul
 ap.add_argument("--random_slice", action="store_true")
 ap.add_argument("--reps", type=int, default=30)
 ap.add_argument("--fracture", action="store_true")
+ap.add_argument("--pieces", type=int, default=0)
 a = ap.parse_args()
 dev = torch.device('cuda:0')
 g = torch.Generator().manual_seed(0)
@@ -68,8 +72,64 @@ def bench_fracture(reps):
         fh.write('\n'.join(lines) + '\n')
 
 
+def bench_pieces(P, reps):
+    from puzzlenet_amd import ops
+    B, M, N, K = 64, 10000, 2048, 16
+    rng = np.random.RandomState(0)
+    raw = torch.from_numpy((rng.rand(B, M, 3) - 0.5).astype(np.float32)).to(dev)
+    cols = datapipe._fracture_pair_cols(P, K)
+    row = np.empty((B, cols[-1].stop))
+    datapipe.draw_fracture_pair_batch(rng, torch.Generator().manual_seed(0), B, P, P, K, 0.8, row)
+    d = torch.from_numpy(row).to(dev)
+    normals, u_anchor = d[:, cols[0]].reshape(B, P - 1, K, 3).contiguous(), d[:, cols[1]].reshape(B, P - 1, K).contiguous()
+    pieces, u7, tw = d[:, cols[2]].reshape(B).to(torch.int32), d[:, cols[3]].contiguous(), d[:, cols[4]].contiguous()
+    pn, pz, pu = torch.from_numpy(rng.rand(B, K, 3)).to(dev), torch.from_numpy(rng.rand(B, K) / 3 - 0.4).to(dev), torch.from_numpy(rng.rand(B, 2)).to(dev)
+    _, ok, rec = datapipe.cut_pairs_fracture(raw, normals, u_anchor, pieces, u7, tw, n=N)
+    _, pok, _ = datapipe.cut_pairs(raw, pn, pz, pu, tw, n=N)
+    n_nb = int((rec.kind == datapipe.NEIGHBOUR).sum())
+    print('fracture pairs, P = %d: valid %d/%d (plane: %d/%d), NEIGHBOUR %d, replaced by the sibling pair %d' % (
+        P, int(ok.sum()), B, int(pok.sum()), B, n_nb, int(rec.rejected.sum())), flush=True)
+    forms = {"plane: cut_pairs": lambda: datapipe.cut_pairs(raw, pn, pz, pu, tw, n=N),
+             "fracture: cut_pairs_fracture (P = %d)" % P: lambda: datapipe.cut_pairs_fracture(raw, normals, u_anchor, pieces, u7, tw, n=N)}
+    mc = max(M - N, N)
+    p2, c2, s2, _, _ = ops.cut_compact(raw, pn, pz, pu, N, M)
+    p4, c4, s4 = ops.fracture_pair(raw, normals, u_anchor, pieces, u7, N, 0.5, M)[:3]
+    launches = {"cut_compact (plane)": lambda: ops.cut_compact(raw, pn, pz, pu, N, M),
+                "fracture_pair (P = %d)" % P: lambda: ops.fracture_pair(raw, normals, u_anchor, pieces, u7, N, 0.5, M),
+                "FPS of the plane pair": lambda: ops.farthest_point_sample(p2, N, s2, background=True, counts=c2, max_count=mc),
+                "FPS of the primary pair": lambda: ops.farthest_point_sample(p4[:2 * B], N, s4[:2 * B], background=True, counts=c4[:2 * B], max_count=mc),
+                "FPS of the fallback pair (%d of %d samples)" % (n_nb, B):
+                    lambda: ops.farthest_point_sample(p4[2 * B:], N, s4[2 * B:], background=True, counts=c4[2 * B:], max_count=mc),
+                "FPS of all four rows, one launch (what runs)": lambda: ops.farthest_point_sample(p4, N, s4, background=True, counts=c4, max_count=mc)}
+    times, ltimes = {name: [] for name in forms}, {name: [] for name in launches}
+    for rep in range(reps + 3):                          # (three warm-up rounds of everything; the forms alternate)
+        for name, fn in forms.items():
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if rep >= 3:
+                times[name].append((time.perf_counter() - t0) * 1e3)
+        for name, fn in launches.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(); e0.record()
+            fn()
+            e1.record(); e1.synchronize()
+            if rep >= 3:
+                ltimes[name].append(e0.elapsed_time(e1) * 1e3)
+    print('tools/bench_datapipe.py --pieces %d --reps %d: B = %d, M = %d, N = %d, K = %d, neighbours = 0.5 (medians of %d)' % (P, reps, B, M, N, K, reps))
+    for name, t in times.items():
+        t = np.sort(np.array(t))
+        print('%-45s %.2f ms per batch on the host clock (min %.2f, max %.2f)' % (name, np.median(t), t[0], t[-1]), flush=True)
+    for name, t in ltimes.items():
+        t = np.sort(np.array(t))
+        print('launch: %-45s %.0f us between events (min %.0f, max %.0f)' % (name, np.median(t), t[0], t[-1]), flush=True)
+
+
 if a.fracture:
     bench_fracture(a.reps)
+    sys.exit(0)
+if a.pieces:
+    bench_pieces(a.pieces, a.reps)
     sys.exit(0)
 for (B, M, N) in [(64, 6000, 1024), (64, 10000, 2048), (64, 12000, 2048)]:
     raw = (torch.rand(B, M, 3, generator=g) - 0.5).to(dev)

@@ -1,9 +1,10 @@
 """The step fed from raw clouds (datapipe.PairFeeder) against the step on a resident batch, and where the difference goes:
 host time of next_batch(), device time of a batch built alone, step time with the feeder beside it.
 
-    [M=10000] python tools/from_raw_probe.py [--random_slice]
+    [M=10000] python tools/from_raw_probe.py [--random_slice] [--pieces P]
 
---random_slice: the double-cut feeder (PairFeeder(split_twice=True)) as a third form, alternating with the other two."""
+--random_slice: the double-cut feeder (PairFeeder(split_twice=True)) as a third form, alternating with the other two.
+--pieces P: the fracture feeder (PairFeeder(pieces=P)) as a further form, in the same alternating blocks."""
 import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -21,6 +22,9 @@ model = model5_b.TouchedRegraster(cfg).to(dev)
 feeders = {"from raw": datapipe.PairFeeder(raw, dev, n=N, seed=0)}
 if "--random_slice" in sys.argv[1:]:
     feeders["from raw, double cuts"] = datapipe.PairFeeder(raw, dev, n=N, seed=0, split_twice=True)
+if "--pieces" in sys.argv[1:]:
+    P = int(sys.argv[sys.argv.index("--pieces") + 1])
+    feeders["from raw, %d-piece fractures" % P] = datapipe.PairFeeder(raw, dev, n=N, seed=0, pieces=P)
 for rep in range(2):      # (alternating)
     for name, feeder in feeders.items():
         for _ in range(3):

@@ -3,13 +3,15 @@ labels, random motion on a background stream: the reference's loader processes, 
 :98-105) -> engine.TrainStep, a fresh batch every step, nothing synchronises.
 
     python tools/train_from_raw.py [--batch 64] [--points 2048] [--raw 10000] [--steps 20] [--cut {plane,sphere,cylinder,cone}]
-                                     [--random_slice]
+                                     [--random_slice] [--pieces P [--pieces_min L] [--neighbours q]]
 
 --cut sphere | cylinder | cone: the reference's mesh cuts (dataset.py:715-759; "bed_sphere" is its documented training
 command) in place of the plane.  The cone (apex and base one unit from the origin) holds every point within 0.447 of the
 origin, so for it the shells are twice as large.
 --random_slice: the reference's flag of the same name (CADDataset(split_twice=True), dataset.py:1203-1355): the double cuts, with
 the plane only.
+--pieces P [--pieces_min L] [--neighbours q]: pairs cut out of fractures of L .. P pieces (L = P without --pieces_min), a share q of
+them drawn among all final pieces (PairFeeder(pieces=(L, P), neighbours=q)); with the plane only, without --random_slice.
 """
 import argparse, os, sys, time
 import numpy as np, torch
@@ -24,7 +26,11 @@ ap.add_argument("--raw", type=int, default=10000)
 ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--cut", choices=["plane", "sphere", "cylinder", "cone"], default="plane")
 ap.add_argument("--random_slice", action="store_true")
+ap.add_argument("--pieces", type=int, default=0)
+ap.add_argument("--pieces_min", type=int, default=0)
+ap.add_argument("--neighbours", type=float, default=0.5)
 a = ap.parse_args()
+pieces = None if not a.pieces else (a.pieces_min or a.pieces, a.pieces)
 dev = torch.device("cuda:0")
 B, N, M = a.batch, a.points, a.raw
 rng = np.random.RandomState(0)
@@ -36,10 +42,10 @@ if a.cut == "cone":
 cfg = Cfg(); cfg.num_points = N
 torch.manual_seed(0)
 model = model5_b.TouchedRegraster(cfg).to(dev)
-feeder = datapipe.PairFeeder(raw, dev, n=N, seed=0, cut=a.cut, split_twice=a.random_slice)
+feeder = datapipe.PairFeeder(raw, dev, n=N, seed=0, cut=a.cut, split_twice=a.random_slice, pieces=pieces, neighbours=a.neighbours)
 runner = engine.TrainStep(model, feeder.next_batch(), cfg.lr, world=1)
 nxt = feeder.next_batch()
-losses, mem, oks, doubles = [], [], [nxt.ok], [nxt.double]
+losses, mem, oks, doubles, fractures = [], [], [nxt.ok], [nxt.double], [nxt.fracture]
 for it in range(a.steps + 3):
     if it == 3:
         torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -47,6 +53,7 @@ for it in range(a.steps + 3):
     nxt = feeder.next_batch()
     oks.append(nxt.ok)
     doubles.append(nxt.double)
+    fractures.append(nxt.fracture)
     if it % 50 == 0:
         mem.append(torch.cuda.memory_allocated() >> 20)      # (no synchronisation: the allocator's own count)
 torch.cuda.synchronize()
@@ -59,5 +66,9 @@ if a.random_slice:
     kinds = torch.bincount(torch.cat([d.kind for d in doubles]).long(), minlength=4).tolist()
     print("double cuts: single / half vs rest / half vs other / halves:", kinds, " pairs replaced by their fallback:",
           int(torch.cat([d.rejected for d in doubles]).sum()))
+if pieces:
+    kinds = torch.bincount(torch.cat([f.kind for f in fractures]).long(), minlength=2).tolist()
+    print("fractures of %d .. %d pieces: sibling / neighbour pairs:" % pieces, kinds, " neighbour pairs replaced by the sibling pair:",
+          int(torch.cat([f.rejected for f in fractures]).sum()))
 print("%.2f ms per step of %d fresh pairs from %d-point raw clouds = %.0f pairs/s" % (1e3 * dt / a.steps, B, M, B * a.steps / dt))
 runner.close(); feeder.close()
