@@ -9,7 +9,7 @@ is per row), so the all-pairs table factors exactly:
     piece: FPS and kNN depend on coordinates only.
   * Pose head: the first tfMLP layer on cat([ffpc_i, fmrpc_j]) is U_i + V_j with U = ffpc W1[:, :1024]^T and
     V = fmrpc W1[:, 1024:]^T + b1; the other four layers run on the K^2 rows relu(U_i + V_j).
-  * Moved-side boundary head: both "global" vectors are the max over the MOVED piece's local features (model5_b.py:440,
+  * Moved-side boundary head: both "global" vectors are the max over the MOVED piece's local features (TouchedRegraster.moved_branch,
     the reference's line 741), so de_mrpcb depends on j only: K rows.
   * Fixed-side boundary head: de_fpcb[i, j] = MLPFpcb(cat([g_j, local_i])), the only per-point work that depends on the
     pair: one launch of ops.pair_head (csrc/pointmlp.hip, pair_head_fwd_kernel), which computes the first-layer product
@@ -38,7 +38,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops, se3
-from .model5_b import _run_seq, _run_seq_cat_global
+from .model5_b import draw_fps_starts, pick_order_plan, run_seq, run_seq_cat_global, sampling_plan, upload_starts
 
 PairTable = collections.namedtuple("PairTable", "twist T de_fpcb de_mrpcb top_f top_m score x2")
 Assembly = collections.namedtuple("Assembly", "root edges G placed")
@@ -50,23 +50,13 @@ Progressive = collections.namedtuple("Progressive", "G edges placed cloud piece_
 ENCODER_ROWS = 64      # pieces per encoder call (the fused per-point stem takes up to 64 clouds)
 
 
-def _plan(model, pieces, s1, s2):
-    """FPS -> gather -> FPS -> gather and the two neighbour searches of every piece: coordinates only, so both encoders of
-    a piece use the same plan (the form TouchedRegraster.prefetch_plans hands to predict5)."""
-    f1 = ops.farthest_point_sample(pieces, 512, s1)
-    x1 = ops.index_points(pieces, f1)
-    f2 = ops.farthest_point_sample(x1, 256, s2)
-    x2 = ops.index_points(x1, f2)
-    return (x1, ops.knn(pieces, x1, 32)), (x2, ops.knn(x1, x2, 32))
-
-
 def _encode(enc, pieces, plan):
     """One encoder over all pieces, ENCODER_ROWS at a time -> (global feature [K,1024], per-point features [K,N,64])."""
     outs = []
     for a in range(0, pieces.shape[0], ENCODER_ROWS):
         b = a + ENCODER_ROWS
         sub = tuple((x[a:b], i[a:b]) for x, i in plan)
-        r = enc(pieces[a:b], sub)
+        r = enc(pieces[a:b], sub, None, False)      # need_out = False: only the maximum of the projection is used
         outs.append((r[0], r[4]))
     if len(outs) == 1:
         return outs[0]
@@ -81,7 +71,7 @@ def _pair_fixed_head(seq, local, g):
     if len(mods) == 5 and ops.pair_head_supported(N, mods[2].out_features, mods[4].out_features):
         l1, l2, l3 = mods[0], mods[2], mods[4]
         return ops.pair_head(local, g, l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias)
-    cols = [_run_seq_cat_global(seq, local, g[j:j + 1].expand(K, -1).reshape(K, 1, -1).contiguous()) for j in range(g.shape[0])]
+    cols = [run_seq_cat_global(seq, local, g[j:j + 1].expand(K, -1).reshape(K, 1, -1).contiguous()) for j in range(g.shape[0])]
     return torch.stack(cols, dim=1)
 
 
@@ -104,7 +94,7 @@ def encode_pieces(model, pieces, k=128, start=None, plan=None, _who="encode_piec
 
       U [K,H], V [K,H]    the fixed and the moved half of the pose head's first layer (V carries the bias)
       local_f [K,N,64]    MLPLocalPreFpc over Encoder's per-point features (the fixed-side boundary head's input)
-      g_max [K,64]        the max over MLPLocalPreRpc of Encoder2's per-point features (model5_b.py:440)
+      g_max [K,64]        the max over MLPLocalPreRpc of Encoder2's per-point features (TouchedRegraster.moved_branch)
       de_mrpcb [K,2,N]    moved-side boundary logits
       top_m [K,k]         their k points of largest class-1 probability
       x2 [K,256,3]        the second-level sample points
@@ -115,63 +105,42 @@ def encode_pieces(model, pieces, k=128, start=None, plan=None, _who="encode_piec
     K, N, k = _check_pieces(model, pieces, k, _who, _least)
     pieces = pieces.contiguous()
     dev = pieces.device
-    for m in (model.Encoder, model.Encoder2, model.tfMLP, model.fpc_decoder, model.rpc_decoder):
-        if any(sm.training for sm in m.modules()):
-            m.train(False)
+    model.set_mode(False)
     with torch.no_grad():
         if plan is not None:
             pass
         elif start is None:
-            gen = getattr(model, "fps_generator", None)
-            s1 = torch.randint(0, N, (K,), dtype=torch.long, generator=gen)
-            s2 = torch.randint(0, 512, (K,), dtype=torch.long, generator=gen)
-            stage = torch.empty((2, K), dtype=torch.long, pin_memory=True)
-            torch.stack((s1, s2), out=stage)
-            s1, s2 = stage.to(dev, non_blocking=True).unbind(0)
+            plan = sampling_plan(pieces, *upload_starts(draw_fps_starts(1, K, N, getattr(model, "fps_generator", None)), dev), True)
         else:
             s1, s2 = (torch.as_tensor(s, dtype=torch.long).to(dev, non_blocking=True) for s in start)
             if s1.shape != (K,) or s2.shape != (K,):
                 raise _lib.PznError(f"{_who}: start = (s1[{K}], s2[{K}]); got {tuple(s1.shape)}, {tuple(s2.shape)}")
-        if plan is None:
-            plan = _plan(model, pieces, s1, s2)
+            plan = sampling_plan(pieces, s1, s2, True)
 
         cur = torch.cuda.current_stream(dev)
         side = model.side_stream()
-        model.Encoder.need_out = model.Encoder2.need_out = False
-        try:
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                # Encoder2 and everything that depends on the moved piece alone: its local chain, the global vector
-                # (model5_b.py:440 - the max over the MOVED piece's local features serves both heads) and de_mrpcb
-                fmrpc, local_m = _encode(model.Encoder2, pieces, plan)
-                local_m = _run_seq(model.MLPLocalPreRpc, local_m)
-                g_max = ops.max_over_points(local_m)                                          # [K,64]
-                de_mrpcb = _run_seq_cat_global(model.MLPRpcb, local_m, g_max.unsqueeze(1))    # [K,N,2]
-            ffpc, local_f = _encode(model.Encoder, pieces, plan)
-            local_f = _run_seq(model.MLPLocalPreFpc, local_f)
-        finally:
-            model.Encoder.need_out = model.Encoder2.need_out = True
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            # Encoder2 and everything that depends on the moved piece alone: its local chain, the global vector and
+            # de_mrpcb (TouchedRegraster.moved_branch)
+            fmrpc, local_m = _encode(model.Encoder2, pieces, plan)
+            _, g_max, de_mrpcb = model.moved_branch(local_m)                              # [K,1,64], [K,N,2]
+        ffpc, local_f = _encode(model.Encoder, pieces, plan)
+        local_f = run_seq(model.MLPLocalPreFpc, local_f)
         cur.wait_stream(side)
         for t in (fmrpc, g_max, de_mrpcb):                     # made on the side stream, used on this one
             t.record_stream(cur)
         for t in (pieces,) + tuple(t for lvl in plan for t in lvl):      # made on this stream, read on the side stream
             t.record_stream(side)
 
-        # pose head: the first layer splits into a fixed and a moved half
+        # pose head: the first layer splits into a fixed and a moved half (V carries the bias)
         w1, b1 = model.tfMLP[0].weight, model.tfMLP[0].bias
-        D = ffpc.shape[1]
-        U = torch.empty((K, w1.shape[0]), dtype=torch.float32, device=dev)
-        V = torch.empty_like(U)
         ffpc, fmrpc = ffpc.contiguous(), fmrpc.contiguous()
-        with ops._on(dev):
-            st = ops._stream()
-            ops._call("pzn_linear_slice_fwd_f32", ffpc.data_ptr(), w1.data_ptr(), w1.shape[1], None, K, D, w1.shape[0], 0,
-                      U.data_ptr(), st, flops=2 * K * D * w1.shape[0])
-            ops._call("pzn_linear_slice_fwd_f32", fmrpc.data_ptr(), w1.data_ptr() + 4 * D, w1.shape[1], b1.data_ptr(), K,
-                      w1.shape[1] - D, w1.shape[0], 0, V.data_ptr(), st, flops=2 * K * (w1.shape[1] - D) * w1.shape[0])
+        U = ops.linear_cols(ffpc, w1, 0)
+        V = ops.linear_cols(fmrpc, w1, ffpc.shape[1], b1)
         p_m = torch.softmax(de_mrpcb, dim=-1)[..., 1]
         top_m = ops.topk_rows(p_m, k)
-    return PieceCodes(U, V, local_f, g_max, de_mrpcb.permute(0, 2, 1), top_m, plan[1][0])
+    return PieceCodes(U, V, local_f, g_max.squeeze(1), de_mrpcb.permute(0, 2, 1), top_m, plan[1][0])
 
 
 def _refine_gathered(Bf, Bm, T, iters):
@@ -226,7 +195,7 @@ def pair_block(model, pieces_f, codes_f, pieces_m, codes_m, k=128, refine=0):
     with torch.no_grad():
         # pose head: the four layers after the split first one run on the Kf Km rows relu(U_i + V_j)
         hidden = torch.relu(codes_f.U[:, None] + codes_m.V[None]).reshape(Kf * Km, -1)
-        twist = _run_seq(list(model.tfMLP)[2:], hidden).view(Kf, Km, 6)
+        twist = run_seq(list(model.tfMLP)[2:], hidden).view(Kf, Km, 6)
         T = se3.exp(twist)
 
         y_f = _pair_fixed_head(model.MLPFpcb, codes_f.local_f, codes_m.g_max)                # [Kf,Km,N,2]
@@ -492,9 +461,7 @@ class ProgressiveAssembler:
         self.refine = _check_refine(refine, "ProgressiveAssembler")
         dev = pieces.device
         if start is None:
-            gen = getattr(model, "fps_generator", None)
-            s1 = torch.randint(0, N, (K,), dtype=torch.long, generator=gen)
-            s2 = torch.randint(0, 512, (K,), dtype=torch.long, generator=gen)
+            s1, s2 = draw_fps_starts(1, K, N, getattr(model, "fps_generator", None))
         else:
             s1, s2 = (torch.as_tensor(s, dtype=torch.long).cpu() for s in start)
         self._s1, self._s2 = s1.tolist(), s2.tolist()
@@ -557,11 +524,8 @@ class ProgressiveAssembler:
             self._s1[n] = self._s2[n] = 0
             self.rounds += 1
 
-            # 4. the merged part comes out in pick order: its first 512 points are its FPS-512 sample started at point 0,
-            # the first 256 of those the FPS-256 sample of that: the sampling plan costs no FPS
-            x1 = merged[:, :512].contiguous()
-            x2 = merged[:, :256].contiguous()
-            plan = ((x1, ops.knn(merged, x1, 32)), (x2, ops.knn(x1, x2, 32)))
+            # 4. the merged part comes out in pick order: its sampling plan costs no FPS
+            plan = pick_order_plan(merged)
 
             # 5. encode the merged part alone; its row and its column of the table; row and column j leave
             code = encode_pieces(self.model, merged, k, plan=plan, _who="ProgressiveAssembler")

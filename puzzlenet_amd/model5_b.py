@@ -128,9 +128,10 @@ class PCTransformer_nonsort(nn.Module):
         self.atten4 = layerAttention(self.C, gs2_feature_size * 2)
         self.out = nn.Linear(gs2_feature_size * 2 * 5, 1024)
 
+    # (centroids, neighbours) of the two set-abstraction levels (:449, :456): the one statement of these sizes, read by the
+    # sampling plan below, by its start-index draws and by assembly.py
+    SA_LEVELS = ((512, 32), (256, 32))
     fused_sa = True     # False: literally sample_and_group -> [B,S,K,3+D] -> shared MLP, as the reference composes it
-    attn_strips = False  # True: slot 2 (attention) is [B,16,256] strip column sums with the same mean over dim 1 (ops.attention_chain_fused)
-    need_out = True     # False: slot 3 of the 5-tuple (the [B,256,1024] projection) is None; predict5 sets it around its calls
     grad_marker = None       # engine.TrainStep (N > 1): marker(tensor) registers "the backward has come this far" on it
 
     def _mark_f2f(self, f2f):
@@ -140,15 +141,10 @@ class PCTransformer_nonsort(nn.Module):
             self.grad_marker(f2f)
         return f2f
 
-    def _set_abstraction(self, npoint, nsample, xyz, feat, lin_a, lin_b, plan=None):
-        """sample_and_group(npoint, 0, nsample, xyz, feat, knn=True) + relu(lin_a) + relu(lin_b) + max over K.
-        `plan` = (new_xyz, idx) when the sampling / neighbour search was already done (sa_plan)."""
-        if plan is None:
-            fps_idx = self.fps(xyz, npoint)                               # pointnet_util.py:113
-            new_xyz = ops.index_points(xyz, fps_idx)                      # :115
-            idx = None                                                    # :118-119 fused into the group launch
-        else:
-            new_xyz, idx = plan
+    def _set_abstraction(self, xyz, feat, lin_a, lin_b, plan):
+        """sample_and_group(npoint, 0, nsample, xyz, feat, knn=True) + relu(lin_a) + relu(lin_b) + max over K on one level
+        of a sampling plan: plan = (new_xyz, idx), idx None = the search (:118-119) fused into the group launch."""
+        new_xyz, idx = plan
         return new_xyz, ops.sa_mlp_max(xyz, feat, new_xyz, idx, lin_a.weight, lin_a.bias, lin_b.weight, lin_b.bias)
 
     def local_features(self, xyz):
@@ -179,46 +175,84 @@ class PCTransformer_nonsort(nn.Module):
         if isinstance(x_feature, tuple):
             x_feature, second = x_feature
         if self.fused_sa and not xyz.requires_grad:
-            p1, p2 = sa_plan if sa_plan is not None else (None, None)
-            x, f1f = self._set_abstraction(512, 32, xyz, x_feature, self.mlp3, self.mlp4, p1)
-            x2, f2f = self._set_abstraction(256, 32, x, f1f, self.mlp5, self.mlp6, p2)
+            if sa_plan is None:      # the encoder on its own: its two draws from the global generator (pointnet_util.py:65)
+                sa_plan = sampling_plan(xyz, *upload_starts(draw_fps_starts(1, xyz.shape[0], xyz.shape[1]), xyz.device), False)
+            x, f1f = self._set_abstraction(xyz, x_feature, self.mlp3, self.mlp4, sa_plan[0])
+            x2, f2f = self._set_abstraction(x, f1f, self.mlp5, self.mlp6, sa_plan[1])
         else:
-            x, f1 = self.sg1(512, 0, 32, xyz, x_feature, False, True)                             # :449
+            (n1, k1), (n2, k2) = self.SA_LEVELS
+            x, f1 = self.sg1(n1, 0, k1, xyz, x_feature, False, True)                              # :449
             f1f = ops.shared_mlp_max(f1, self.mlp3.weight, self.mlp3.bias, self.mlp4.weight, self.mlp4.bias)  # :452-454
-            x2, f2 = self.sg2(256, 0, 32, x, f1f, False, True)                                    # :456
+            x2, f2 = self.sg2(n2, 0, k2, x, f1f, False, True)                                     # :456
             f2f = ops.shared_mlp_max(f2, self.mlp5.weight, self.mlp5.bias, self.mlp6.weight, self.mlp6.bias)  # :459-461
         return x2, self._mark_f2f(f2f), second
 
     def chain_fused_ok(self, f2f):
-        return f2f.is_cuda and ops.attention_chain_fused_supported(
-            f2f, self.atten1.mlpq.weight.shape[0], self.out.weight)
+        return ops.attention_chain_fused_supported(f2f, self.atten1.mlpq.weight.shape[0], self.out.weight)
 
-    def forward(self, xyz, sa_plan=None, x_feature=None):
-        return self.tail(*self.stem(xyz, sa_plan, x_feature))
+    def forward(self, xyz, sa_plan=None, x_feature=None, need_out=True, attn_strips=False):
+        """-> (f_global, x2, attention, out, x_feature).  need_out = False: slot 3 (the [B,256,1024] projection) is None where
+        the fused chain runs.  attn_strips = True: slot 2 is [B,16,256] strip column sums with the same mean over dim 1
+        there (ops.attention_chain_fused)."""
+        return self.tail(*self.stem(xyz, sa_plan, x_feature), need_out, attn_strips)
 
-    def tail(self, x2, f2f, x_feature):
+    def tail(self, x2, f2f, x_feature, need_out=True, attn_strips=False):
         """:462-475 behind stem(): the four attention blocks, the out projection, the max over the points."""
-        blocks = (self.atten1, self.atten2, self.atten3, self.atten4)
         if self.chain_fused_ok(f2f):
             # :462-475 through the chained matrix-core kernels (csrc/attnfused.hip), one encoder per launch here
-            # need_out = False (set by predict5, which uses only the maximum: :723): `out` is None, never written
+            # need_out = False (passed by predict5, which uses only the maximum: :723): `out` is None, never written
             (out, attention, f_global), = ops.attention_chain_fused([f2f], [self._block_params()], [self.out.weight], [self.out.bias],
-                                                                   need_out=self.need_out, map_strips=self.attn_strips)
+                                                                   need_out=need_out, map_strips=attn_strips)
             return f_global, x2, attention, out, x_feature
-        if True:      # any other shape: the four blocks as modules, as the reference composes them
-            att1, attention1 = self.atten1(f2f)
-            att2, attention2 = self.atten2(att1)
-            att3, attention3 = self.atten3(att2)
-            att4, attention4 = self.atten4(att3)
-            if attention1.is_cuda:
-                attention = ops.avg4(attention1, attention2, attention3, attention4)     # :468-469, one launch
-            else:
-                attention = attention1 + attention2 + attention3 + attention4
-                attention = attention / 4
-            att = torch.cat([att1, att2, att3, att4, f2f], dim=-1)       # (:466, :470 as one copy instead of two)
-            out = ops.linear(att, self.out.weight, self.out.bias)                                   # :474
+        # any other shape: the four blocks as modules, as the reference composes them
+        att1, attention1 = self.atten1(f2f)
+        att2, attention2 = self.atten2(att1)
+        att3, attention3 = self.atten3(att2)
+        att4, attention4 = self.atten4(att3)
+        attention = ops.avg4(attention1, attention2, attention3, attention4)     # :468-469, one launch
+        att = torch.cat([att1, att2, att3, att4, f2f], dim=-1)       # (:466, :470 as one copy instead of two)
+        out = ops.linear(att, self.out.weight, self.out.bias)                                   # :474
         f_global = ops.max_over_points(out)                                                       # :475
         return f_global, x2, attention, out, x_feature
+
+
+def draw_fps_starts(clouds, rows, n_points, generator=None):
+    """The host draws of the FPS start indices for `clouds` clouds of `rows` samples with n_points points each -> 2 * clouds
+    int64 CPU tensors [rows]: per cloud, in order, the level-1 starts in [0, n_points) and then the level-2 starts in
+    [0, SA_LEVELS[0][0]) - the reference's order (sg1, sg2 of one encoder, then the next; pointnet_util.py:65).  The order of
+    these calls is what a seed means.  generator None = torch's global one, as the reference."""
+    n1 = PCTransformer_nonsort.SA_LEVELS[0][0]
+    return [torch.randint(0, n_, (rows,), dtype=torch.long, generator=generator) for _ in range(clouds) for n_ in (n_points, n1)]
+
+
+def upload_starts(draws, dev):
+    """Host index vectors of one length -> their device copies, through ONE asynchronous upload from pinned memory: a
+    pageable `.to(dev)` blocks the host until everything queued before it has run (4 of them per step drained the launch
+    queue at every step start)."""
+    stage = torch.empty((len(draws), draws[0].shape[0]), dtype=torch.long, pin_memory=True)
+    torch.stack(tuple(draws), out=stage)
+    return stage.to(dev, non_blocking=True).unbind(0)
+
+
+def sampling_plan(xyz, s1, s2, with_knn):
+    """FPS -> gather of both set-abstraction levels from the start indices s1, s2 (on the device) and, with_knn, the two
+    neighbour searches -> ((x1, idx1 | None), (x2, idx2 | None)).  Coordinates only: no weight is read.  idx None = the
+    search runs inside the encoder, fused with the group write."""
+    (n1, k1), (n2, k2) = PCTransformer_nonsort.SA_LEVELS
+    x1 = ops.index_points(xyz, ops.farthest_point_sample(xyz, n1, s1))
+    x2 = ops.index_points(x1, ops.farthest_point_sample(x1, n2, s2))
+    if with_knn:
+        return (x1, ops.knn(xyz, x1, k1)), (x2, ops.knn(x1, x2, k2))
+    return (x1, None), (x2, None)
+
+
+def pick_order_plan(xyz):
+    """sampling_plan(with_knn=True) of clouds that are in FPS pick order already (ops.merge_resample's output): the first n1
+    points are the level-1 sample started at point 0, the first n2 of those the level-2 sample of that - no FPS."""
+    (n1, k1), (n2, k2) = PCTransformer_nonsort.SA_LEVELS
+    x1 = xyz[:, :n1].contiguous()
+    x2 = xyz[:, :n2].contiguous()
+    return (x1, ops.knn(xyz, x1, k1)), (x2, ops.knn(x1, x2, k2))
 
 
 # training_step takes nothing but the row mean of the two attention maps (model5_b.py:937-942): on the fused attention path it
@@ -244,7 +278,7 @@ def _chain3(mods, x, cin):
     (the boundary heads' chains: 64 -> 64 -> 64 -> 64 and (64 |) 64 -> 64 -> 32 -> 2); None otherwise."""
     if not (len(mods) == 5 and isinstance(mods[1], nn.ReLU) and isinstance(mods[3], nn.ReLU)
             and all(isinstance(mods[i], nn.Linear) and mods[i].bias is not None for i in (0, 2, 4))
-            and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32 and x.shape[1] % 32 == 0):
+            and x.dim() == 3 and x.dtype == torch.float32 and x.shape[1] % 32 == 0):
         return None
     l1, l2, l3 = mods[0], mods[2], mods[4]
     if l1.in_features != cin or l2.in_features != l1.out_features or l3.in_features != l2.out_features:
@@ -252,8 +286,9 @@ def _chain3(mods, x, cin):
     return (l1, l2, l3) if ops.point_mlp3_available(x.shape[2], l1.out_features, l2.out_features, l3.out_features) else None
 
 
-def _run_seq(seq, x):
-    """nn.Sequential(Linear, ReLU, Linear, ...) through the fused linear(+ReLU) kernel."""
+def run_seq(seq, x):
+    """nn.Sequential(Linear, ReLU, Linear, ...) (or a list of its modules) through the fused kernels: one launch for a
+    three-layer chain on [B, N, 64] rows (_chain3), the linear(+ReLU) kernel per layer otherwise."""
     mods = list(seq)
     ch = _chain3(mods, x, x.shape[-1])
     if ch is not None:
@@ -268,17 +303,17 @@ def _run_seq(seq, x):
     return x
 
 
-def _run_seq_cat_global(seq, x, g):
-    """_run_seq on cat([g.repeat(1, N, 1), x], -1) with the first Linear + ReLU split into a per-point and a per-cloud part."""
+def run_seq_cat_global(seq, x, g):
+    """run_seq on cat([g.repeat(1, N, 1), x], -1) with the first Linear + ReLU split into a per-point and a per-cloud part."""
     mods = list(seq)
     if not (len(mods) >= 2 and isinstance(mods[1], nn.ReLU)):
-        return _run_seq(seq, torch.cat([g.expand(-1, x.shape[1], -1), x], dim=-1))
+        return run_seq(seq, torch.cat([g.expand(-1, x.shape[1], -1), x], dim=-1))
     ch = _chain3(mods, x, g.shape[-1] + x.shape[-1])
     if ch is not None:
         l1, l2, l3 = ch
         return ops.point_mlp3(x, l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias, g=g)
     y = ops.cat_global_linear_relu(x, g, mods[0].weight, mods[0].bias)
-    return _run_seq(mods[2:], y)
+    return run_seq(mods[2:], y)
 
 
 class TouchedRegraster(_Base):
@@ -300,7 +335,7 @@ class TouchedRegraster(_Base):
         self.MLPLocalPreFpc = _seq(64, 64, 64, 64)
         self.MLPRpcb = _seq(128, 64, 32, 2)                                        # :586-592
         self.MLPFpcb = _seq(128, 64, 32, 2)
-        self.two_streams = True        # Encoder2 on a side stream (GPU only); False = everything on the current stream
+        self.two_streams = True        # Encoder2 on a side stream; False = everything on the current stream
         self._side_stream = None
         self._plan_stream = None
         self._plan_cache = None        # (fpc, mrpc, plans, event, versions) from prefetch_plans, handed over by use_plans
@@ -315,29 +350,15 @@ class TouchedRegraster(_Base):
         only, which takes nothing but the row mean of the two attention maps): on the fused attention path the maps come back
         as [B,16,256] strip column sums with that same row mean (ops.attention_chain_fused); every other path and every other
         caller gets the reference's [B,256,256] maps."""
-        for m in (self.Encoder, self.Encoder2, self.tfMLP, self.fpc_decoder, self.rpc_decoder):
-            # :677-690.  (Module.train() re-assigns the flag of every submodule through Module.__setattr__: 0.3 ms of host time
-            # per predict5 call when nothing changes; reading the flags is a tenth of that and leaves the behaviour as it is)
-            if any(sm.training != bool(training) for sm in m.modules()):
-                m.train(training)
+        self.set_mode(training)
         fpc, mrpc = batch[0], batch[1]
         if len(fpc.shape) == 2:
             fpc = fpc.unsqueeze(0)
             mrpc = mrpc.unsqueeze(0)
-        N = fpc.shape[1]
-
+        attn_strips = bool(attn_strips)
         # the encoders' [B,256,1024] projection itself (5-tuple slot 3) is not used by predict5, only its max over the
-        # points (:723): not materialised here (the encoder called on its own still returns it)
-        self.Encoder.need_out = self.Encoder2.need_out = False
-        self.Encoder.attn_strips = self.Encoder2.attn_strips = bool(attn_strips)
-        try:
-            return self._predict5_encoders(fpc, mrpc, N, need, pose_hook)
-        finally:
-            self.Encoder.attn_strips = self.Encoder2.attn_strips = False
-            self.Encoder.need_out = self.Encoder2.need_out = True
-
-    def _predict5_encoders(self, fpc, mrpc, N, need, pose_hook):
-        if self.two_streams and fpc.is_cuda:
+        # points (:723): every encoder call below passes need_out = False (the encoder called on its own still returns it)
+        if self.two_streams:
             # FPS is a latency-bound chain on 128 workgroups: it runs on the side stream while this one computes the
             # per-point features of both clouds, which do not depend on it; then Encoder stays here, Encoder2 goes
             # to the side stream (the two are independent and most of their launches do not fill 256 CUs; autograd
@@ -367,19 +388,28 @@ class TouchedRegraster(_Base):
                 # no hoisted sampling (fused_sa off, or clouds that carry gradients): each sample_and_group draws its own FPS
                 # start indices, so the encoders are CALLED in the reference's order (:710 before :716) - the draws of a
                 # seeded run are the reference's; the streams are the same either way
-                ffpcs = self.Encoder(fpc, plan_f, xf_f)                         # :710
+                ffpcs = self.Encoder(fpc, plan_f, xf_f, False, attn_strips)                         # :710
                 with torch.cuda.stream(side):
-                    fmrpcs = self.Encoder2(mrpc, plan_m, xf_m)                  # :716
+                    fmrpcs = self.Encoder2(mrpc, plan_m, xf_m, False, attn_strips)                  # :716
             else:
                 with torch.cuda.stream(side):
-                    fmrpcs = self.Encoder2(mrpc, plan_m, xf_m)                  # :716
-                ffpcs = self.Encoder(fpc, plan_f, xf_f)                         # :710
+                    fmrpcs = self.Encoder2(mrpc, plan_m, xf_m, False, attn_strips)                  # :716
+                ffpcs = self.Encoder(fpc, plan_f, xf_f, False, attn_strips)                         # :710
             # Encoder2's outputs are joined inside _heads: the second cloud's boundary head stays on the side stream
-            return self._heads(ffpcs, fmrpcs, N, need, pose_hook, side=side)
+            return self._heads(ffpcs, fmrpcs, need, pose_hook, side)
         plan_f, plan_m = self._sa_plans(fpc, mrpc)
-        ffpcs = self.Encoder(fpc, plan_f)                                           # :710
-        fmrpcs = self.Encoder2(mrpc, plan_m)                                        # :716
-        return self._heads(ffpcs, fmrpcs, N, need, pose_hook)
+        ffpcs = self.Encoder(fpc, plan_f, None, False, attn_strips)                 # :710
+        fmrpcs = self.Encoder2(mrpc, plan_m, None, False, attn_strips)              # :716
+        return self._heads(ffpcs, fmrpcs, need, pose_hook)
+
+    def set_mode(self, training):
+        """:677-690: the five sub-modules predict5 moves to train or eval mode."""
+        training = bool(training)
+        for m in (self.Encoder, self.Encoder2, self.tfMLP, self.fpc_decoder, self.rpc_decoder):
+            # (Module.train() re-assigns the flag of every submodule through Module.__setattr__: 0.3 ms of host time
+            # per predict5 call when nothing changes; reading the flags is a tenth of that and leaves the behaviour as it is)
+            if any(sm.training != training for sm in m.modules()):
+                m.train(training)
 
     def side_stream(self):
         """The stream Encoder2 (and the N x N EMD) runs on, created on first use."""
@@ -390,12 +420,34 @@ class TouchedRegraster(_Base):
                 _quiet(False)
         return self._side_stream
 
-    def _heads(self, ffpcs, fmrpcs, N, need, pose_hook=None, side=None):
+    def pose_head(self, ffpc, fmrpc):
+        """:723-725: tfMLP on the two global features side by side -> the twist [B,6]."""
+        return run_seq(self.tfMLP, torch.cat([ffpc, fmrpc], dim=-1))
+
+    def moved_branch(self, feat, ready=None, stream=None):
+        """:739, :741, :749, :753-754: the moved cloud's per-point features [B,N,64] -> (local [B,N,64], g_max [B,1,64], logits
+        [B,N,2]).  :741 - the reference takes the max over the MOVED cloud's local features for BOTH globals (its bug, kept):
+        one reduction serves this branch and fixed_branch.  ready: an event recorded on `stream` (the one this runs on) once
+        g_max is enqueued, for a consumer on another stream that needs no logits.
+        :745-754 run without the repeat and the concatenation: the first layer of a head = a per-point product on the local
+        features + a per-cloud bias from the global one (run_seq_cat_global)."""
+        local = run_seq(self.MLPLocalPreRpc, feat)                                  # :739
+        g_max = ops.max_over_points(local).unsqueeze(1)                             # :741
+        if ready is not None:
+            ready.record(stream)
+        return local, g_max, run_seq_cat_global(self.MLPRpcb, local, g_max)         # :749, :753-754
+
+    def fixed_branch(self, feat, g_max):
+        """:738, :748, :751-752: the fixed cloud's per-point features [B,N,64] and moved_branch's g_max -> logits [B,N,2]."""
+        return run_seq_cat_global(self.MLPFpcb, run_seq(self.MLPLocalPreFpc, feat), g_max)
+
+    def _heads(self, ffpcs, fmrpcs, need, pose_hook=None, side=None):
         """:723-759: pose head on the two global features, boundary heads on the per-point features.
         side: the stream Encoder2 ran on (fmrpcs not yet joined).  The boundary head of the second cloud then stays on
         that stream - its inputs were produced there - beside the pose head and the first cloud's boundary head on this
         one: two chains of 131 072-row layers (25 us launches at a third of the HBM rate each) instead of one, forward and,
-        since autograd replays a node on its forward stream, backward."""
+        since autograd replays a node on its forward stream, backward.  side None: the same launches in the same order on
+        the current stream, no events."""
         ffpc, non_sg_ffpc = ffpcs[0], ffpcs[4]
         fmrpc, non_sg_fmrpc = fmrpcs[0], fmrpcs[4]
         if self.grad_marker is not None:
@@ -406,51 +458,25 @@ class TouchedRegraster(_Base):
                 non_sg_ffpc = self.grad_marker(non_sg_ffpc.view_as(non_sg_ffpc))
             if non_sg_fmrpc.requires_grad:
                 non_sg_fmrpc = self.grad_marker(non_sg_fmrpc.view_as(non_sg_fmrpc))
-        if side is not None:
+        if side is None:
+            _, g_max, de_mrpcb = self.moved_branch(non_sg_fmrpc)
+        else:
             cur = torch.cuda.current_stream()
+            ready = torch.cuda.Event()
             with torch.cuda.stream(side):
-                non_sg_fmrpc = _run_seq(self.MLPLocalPreRpc, non_sg_fmrpc)              # :739
-                g_max = ops.max_over_points(non_sg_fmrpc).unsqueeze(1)                  # :741 (serves both globals)
-                ready = torch.cuda.Event()
-                ready.record(side)
-                de_mrpcb = _run_seq_cat_global(self.MLPRpcb, non_sg_fmrpc, g_max).permute(0, 2, 1)    # :749, :753-754
+                _, g_max, de_mrpcb = self.moved_branch(non_sg_fmrpc, ready, side)
             cur.wait_event(ready)                                                       # Encoder2's outputs and g_max
             for t in list(fmrpcs) + [g_max]:
                 if isinstance(t, torch.Tensor):
                     t.record_stream(cur)
-            f = torch.cat([ffpc, fmrpc], dim=-1)                                        # :723
-            out = _run_seq(self.tfMLP, f)                                               # :725
-            if pose_hook is not None:
-                pose_hook(out)
-            non_sg_ffpc = _run_seq(self.MLPLocalPreFpc, non_sg_ffpc)                    # :738
-            de_fpcb = _run_seq_cat_global(self.MLPFpcb, non_sg_ffpc, g_max).permute(0, 2, 1)          # :748, :751-752
-            cur.wait_stream(side)
-            de_mrpcb.record_stream(cur)
-            if not need:
-                return out, out, de_fpcb, de_mrpcb
-            return out, [0], ffpcs[1], ffpcs[2], fmrpcs[1], fmrpcs[2], de_fpcb, de_mrpcb
-
-        f = torch.cat([ffpc, fmrpc], dim=-1)                                        # :723
-        out = _run_seq(self.tfMLP, f)                                               # :725
+        out = self.pose_head(ffpc, fmrpc)
         if pose_hook is not None:
             pose_hook(out)
-
-        non_sg_ffpc = _run_seq(self.MLPLocalPreFpc, non_sg_ffpc)                    # :738
-        non_sg_fmrpc = _run_seq(self.MLPLocalPreRpc, non_sg_fmrpc)                  # :739
-        # :741 — the reference takes the max of non_sg_fmrpc for BOTH globals (its bug, kept)
-        g_max = ops.max_over_points(non_sg_fmrpc).unsqueeze(1)      # one reduction serves both (identical) globals
-        if non_sg_ffpc.is_cuda:
-            # :745-752 without the repeat and the concatenation: the first layer of a head = a per-point product on the
-            # local features + a per-cloud bias from the global one (ops._CatGlobalLinearRelu)
-            de_fpcb = _run_seq_cat_global(self.MLPFpcb, non_sg_ffpc, g_max).permute(0, 2, 1)      # :748, :751-752
-            de_mrpcb = _run_seq_cat_global(self.MLPRpcb, non_sg_fmrpc, g_max).permute(0, 2, 1)    # :749, :753-754
-        else:
-            non_sg_ffpc_global = g_max.expand(-1, N, -1)      # (:745-746 repeat(1, N, 1): the concat below reads the broadcast view)
-            non_sg_fmrpc_global = non_sg_ffpc_global
-            ffpc_feature4seg = torch.cat([non_sg_fmrpc_global, non_sg_ffpc], dim=-1)    # :748
-            fmrpc_feature4seg = torch.cat([non_sg_ffpc_global, non_sg_fmrpc], dim=-1)   # :749
-            de_fpcb = _run_seq(self.MLPFpcb, ffpc_feature4seg).permute(0, 2, 1)         # :751-752
-            de_mrpcb = _run_seq(self.MLPRpcb, fmrpc_feature4seg).permute(0, 2, 1)       # :753-754
+        de_fpcb = self.fixed_branch(non_sg_ffpc, g_max).permute(0, 2, 1)
+        de_mrpcb = de_mrpcb.permute(0, 2, 1)
+        if side is not None:
+            cur.wait_stream(side)
+            de_mrpcb.record_stream(cur)
         if not need:
             return out, out, de_fpcb, de_mrpcb
         return out, [0], ffpcs[1], ffpcs[2], fmrpcs[1], fmrpcs[2], de_fpcb, de_mrpcb
@@ -465,7 +491,7 @@ class TouchedRegraster(_Base):
         the next step's batch: FPS is 0.5 ms of latency-bound launches on 128 workgroups that otherwise stand at the head
         of every step).  The start indices are drawn here, in the reference's order.  Returns the plan for use_plans();
         predict5 picks it up when it is called with the same two tensors and computes it in place otherwise."""
-        if len(fpc.shape) == 2 or not (self.two_streams and fpc.is_cuda):
+        if len(fpc.shape) == 2 or not self.two_streams:
             return None
         if self._plan_stream is None:
             self._plan_stream = torch.cuda.Stream()
@@ -511,28 +537,14 @@ class TouchedRegraster(_Base):
                 or fpc.shape != mrpc.shape:
             return None, None
         B, N, _ = fpc.shape
-        dev = fpc.device
         # fps_generator (a CPU torch.Generator, default None = the global one the reference draws from): with the plan
         # prefetch the draws of step k+1 are made before step k runs, which shifts the global stream for any other
         # consumer between steps (a loader's augmentation); a private generator leaves the global one alone
-        gen = getattr(self, 'fps_generator', None)
-        d1, d2 = (torch.randint(0, n_, (B,), dtype=torch.long, generator=gen) for n_ in (N, 512))
-        d3, d4 = (torch.randint(0, n_, (B,), dtype=torch.long, generator=gen) for n_ in (N, 512))
-        # ONE asynchronous upload from pinned memory: a pageable `.to(dev)` blocks the host until everything queued
-        # before it has run (4 of them per step drained the launch queue at every step start)
-        stage = torch.empty((4, B), dtype=torch.long, pin_memory=True)
-        torch.stack((d1, d2, d3, d4), out=stage)
-        d1, d2, d3, d4 = stage.to(dev, non_blocking=True).unbind(0)
-        xyz = torch.cat([fpc, mrpc], dim=0)
-        f1 = ops.farthest_point_sample(xyz, 512, torch.cat([d1, d3]))
-        x1 = ops.index_points(xyz, f1)
-        f2 = ops.farthest_point_sample(x1, 256, torch.cat([d2, d4]))
-        x2 = ops.index_points(x1, f2)
-        if with_knn:      # (prefetch_plans) the searches too: coordinates only
-            i1, i2 = ops.knn(xyz, x1, 32), ops.knn(x1, x2, 32)
-            return ((x1[:B], i1[:B]), (x2[:B], i2[:B])), ((x1[B:], i1[B:]), (x2[B:], i2[B:]))
-        # the neighbour search itself runs inside each encoder, fused with the group write (idx = None)
-        return ((x1[:B], None), (x2[:B], None)), ((x1[B:], None), (x2[B:], None))
+        d1, d2, d3, d4 = upload_starts(draw_fps_starts(2, B, N, getattr(self, 'fps_generator', None)), fpc.device)
+        # with_knn (prefetch_plans): the searches too; otherwise each runs inside its encoder, fused with the group write
+        plan = sampling_plan(torch.cat([fpc, mrpc], dim=0), torch.cat([d1, d3]), torch.cat([d2, d4]), with_knn)
+        return (tuple((x[:B], i if i is None else i[:B]) for x, i in plan),
+                tuple((x[B:], i if i is None else i[B:]) for x, i in plan))
 
     # ------------------------------------------------------------------ losses
     def chamfer_loss(self, a, b):
@@ -564,7 +576,7 @@ class TouchedRegraster(_Base):
         pose = {}
 
         def fork_emd(o):
-            if self.two_streams and o.is_cuda and self._side_stream is not None:
+            if self.two_streams and self._side_stream is not None:
                 cur = torch.cuda.current_stream()
                 side = self._side_stream
                 side.wait_stream(cur)
@@ -582,14 +594,9 @@ class TouchedRegraster(_Base):
             batch, batch_size, training=True, need=True, pose_hook=pose_hook, attn_strips=_ATTN_STRIPS)      # :933
         fork_emd(out)      # forked after the heads were enqueued (right after the pose head measured slower)
 
-        if attention.is_cuda:      # :937-942: only the FIRST of the 32 top-k indices is used: mean over rows + arg-max, one launch
-            x2att1 = x2[:, ops.colmean_argmax(attention)[1]]
-            x2att2 = mrpc_x2[:, ops.colmean_argmax(mrpc_attention)[1]]
-        else:
-            att1 = attention.mean(dim=1)
-            att2 = mrpc_attention.mean(dim=1)
-            x2att1 = x2[:, torch.topk(att1, 32)[1][:, 0]]
-            x2att2 = mrpc_x2[:, torch.topk(att2, 32)[1][:, 0]]
+        # :937-942: only the FIRST of the 32 top-k indices is used: mean over rows + arg-max, one launch
+        x2att1 = x2[:, ops.colmean_argmax(attention)[1]]
+        x2att2 = mrpc_x2[:, ops.colmean_argmax(mrpc_attention)[1]]
 
         mat, de_mrpc = pose['mat'], pose['de_mrpc']                                 # :947-952 (computed in pose_hook)
         R = mat[:, :3, :3]
@@ -619,20 +626,12 @@ class TouchedRegraster(_Base):
         # :1012 emd2 = earth_mover_distance(x2att1, x2att2) is evaluated further down, in one launch with the two other small
         # terms (:1123-1125); nothing in between reads it
 
-        if de_fpcb.is_cuda:
-            # :1063-1064 cross entropy and :1085-1090 class-1 probability in one launch per head, :1089-1091 top-128 as
-            # one radix-select launch per head (csrc/losstail.hip)
-            loss_fpcb_cel, de_fpcb_idx_sig = ops.boundary_ce(de_fpcb, fpc_idx.reshape(batch_size, N))
-            loss_rpcb_cel, de_mrpcb_idx_sig = ops.boundary_ce(de_mrpcb, rpc_idx.reshape(batch_size, N))
-            de_fpcb_idx = ops.topk_rows(de_fpcb_idx_sig, 128)
-            de_mrpcb_idx = ops.topk_rows(de_mrpcb_idx_sig, 128)
-        else:
-            loss_fpcb_cel = F.cross_entropy(de_fpcb, fpc_idx.squeeze().long())      # :1063-1064
-            loss_rpcb_cel = F.cross_entropy(de_mrpcb, rpc_idx.squeeze().long())
-            de_fpcb_idx_sig = torch.softmax(de_fpcb, dim=1)[:, 1, :]                # :1085-1091
-            de_fpcb_idx = torch.topk(de_fpcb_idx_sig, 128, 1)[1]
-            de_mrpcb_idx_sig = torch.softmax(de_mrpcb, dim=1)[:, 1, :]
-            de_mrpcb_idx = torch.topk(de_mrpcb_idx_sig, 128, 1)[1]
+        # :1063-1064 cross entropy and :1085-1090 class-1 probability in one launch per head, :1089-1091 top-128 as
+        # one radix-select launch per head (csrc/losstail.hip)
+        loss_fpcb_cel, de_fpcb_idx_sig = ops.boundary_ce(de_fpcb, fpc_idx.reshape(batch_size, N))
+        loss_rpcb_cel, de_mrpcb_idx_sig = ops.boundary_ce(de_mrpcb, rpc_idx.reshape(batch_size, N))
+        de_fpcb_idx = ops.topk_rows(de_fpcb_idx_sig, 128)
+        de_mrpcb_idx = ops.topk_rows(de_mrpcb_idx_sig, 128)
         self.log('train/loss_fpcb_cel', loss_fpcb_cel)
         self.log('train/loss_rpcb_cel', loss_rpcb_cel)
 
@@ -658,7 +657,7 @@ class TouchedRegraster(_Base):
         self.log('train/loss_rpcb', loss_mrpcb)
 
         small = [(x2att1, x2att2), (de_fpcb_pts, fpcb), (inverse_de_mrpcb, rpcb)]      # :1012, :1123, :1125
-        if all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.shape[1] <= ops.EMD_SMALL_MAX for pr in small for t in pr):
+        if all(t.dtype == torch.float32 and t.dim() == 3 and t.shape[1] <= ops.EMD_SMALL_MAX for pr in small for t in pr):
             # the three single-workgroup auctions as ONE launch (3 B workgroups instead of B three times; csrc/emd.hip)
             emd2, e_fpcb, e_mrpcb = ops.emd_fused_small_multi(small)
         else:

@@ -1108,6 +1108,43 @@ def linear(x, weight, bias=None, relu=False):
     return _Linear.apply(x, weight, bias, relu)
 
 
+def _f32_rows(t, name):
+    """linear_cols takes its operands where they lie: on the GPU, float32, contiguous - no copy is made for it."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.PznError(f"linear_cols: {name} must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise _lib.PznError(f"linear_cols: {name} must be float32 with contiguous rows; got {t.dtype}, strides {t.stride()}")
+
+
+def linear_cols(x, weight, col0, bias=None, accumulate=False, out=None):
+    """x @ weight[:, col0:col0 + x.shape[-1]].T (+ bias) with the columns of the wider weight read in place: the product
+    of one slice of a concatenated input (include/pzn.h, pzn_linear_slice_fwd_f32) -> [..., weight.shape[0]].  accumulate:
+    the product is added to `out` instead (the bias is not read then).  Forward only: no autograd, nothing saved."""
+    _f32_rows(x, "x")
+    _f32_rows(weight, "weight")
+    if bias is not None:
+        _f32_rows(bias, "bias")
+    if weight.dim() != 2 or x.dim() < 1 or x.shape[-1] == 0:
+        raise _lib.PznError(f"linear_cols expects x[..., Kin], weight[Nout, >= Kin]; got {tuple(x.shape)}, {tuple(weight.shape)}")
+    Kin = x.shape[-1]
+    Nout, ldw = weight.shape
+    if col0 < 0 or col0 + Kin > ldw:
+        raise _lib.PznError(f"linear_cols: columns {col0}..{col0 + Kin} of weight{tuple(weight.shape)}")
+    M = x.numel() // Kin
+    if out is None:
+        if accumulate:
+            raise _lib.PznError("linear_cols: accumulate adds to `out`")
+        out = torch.empty(x.shape[:-1] + (Nout,), dtype=torch.float32, device=x.device)
+    else:
+        _f32_rows(out, "out")
+        if out.numel() != M * Nout:
+            raise _lib.PznError(f"linear_cols: out{tuple(out.shape)} vs {M} rows of {Nout}")
+    with _on(x.device):
+        _call("pzn_linear_slice_fwd_f32", x.data_ptr(), weight.data_ptr() + 4 * col0, ldw, _p(bias), M, Kin, Nout,
+              int(bool(accumulate)), out.data_ptr(), _stream(), flops=2 * M * Kin * Nout)
+    return out
+
+
 class _CatGlobalLinearRelu(torch.autograd.Function):
     """relu(Linear(cat([g.repeat(1, N, 1), x], -1))) without the concatenation (model5_b.py:745-752, first layer of the
     boundary heads): the product splits into x W[:, Cg:]^T per point and g W[:, :Cg]^T + b per CLOUD; the per-cloud part
@@ -1198,8 +1235,7 @@ class _PointMlp3(torch.autograd.Function):
                 Cg = g2.shape[1]
                 if w1.shape[1] != Cg + C:
                     raise _lib.PznError(f"point_mlp3: w1{tuple(w1.shape)} vs {Cg} + {C} input columns")
-                bias1 = mk(B, 64)      # g W1[:, :Cg]^T + b1, the columns read in place (rows of Cg + C floats)
-                _call("pzn_linear_slice_fwd_f32", _p(g2), _p(w1), Cg + C, _p(b1), B, Cg, 64, 0, _p(bias1), st, flops=2 * B * Cg * 64)
+                bias1 = linear_cols(g2, w1, 0, b1)      # [B,64]: g W1[:, :Cg]^T + b1, the columns read in place
             else:
                 bias1 = b1
             _call("pzn_point_mlp3_fwd_f32", _p(x2), M, N, _p(w1) + 4 * Cg, w1.shape[1], _p(bias1), 1 if g is not None else 0,
@@ -1291,11 +1327,10 @@ def pair_head(x, g, w1, b1, w2, b2, w3, b3):
         raise _lib.PznUnsupported(f"pair_head: N = {N} (a multiple of 32) and a 64 -> {C2} -> {C3} tail (32 -> 2) are not "
                                   "a shape the kernel takes")
     dev = x.device
-    c = torch.empty((Km, 64), dtype=torch.float32, device=dev)
     y = torch.empty((Kf, Km, N, C3), dtype=torch.float32, device=dev)
     with _on(dev):
         st = _stream()
-        _call("pzn_linear_slice_fwd_f32", _p(g2), _p(w1), Cg + C, _p(b1), Km, Cg, 64, 0, _p(c), st, flops=2 * Km * Cg * 64)
+        c = linear_cols(g2, w1, 0, b1)      # [Km,64]
         _call("pzn_pair_head_fwd_f32", _p(x), Kf, N, _p(c), Km, _p(w1) + 4 * Cg, Cg + C, _p(w2), _p(b2), _p(w3), _p(b3),
               C2, C3, _p(y), st, flops=2 * Kf * N * (64 * 64 + Km * (64 * C2 + C2 * C3)))
     return y
@@ -1548,8 +1583,7 @@ class _AttnChainFused(torch.autograd.Function):
                 if not fused:
                     y = mk(M, Nout) if y is None else y
                     for i, xi in enumerate(xsl):
-                        _call("pzn_linear_slice_fwd_f32", _p(xi), w_out.data_ptr() + 4 * E * i, 5 * E, _p(b_out), M, E, Nout,
-                              int(i > 0), _p(y), st, flops=2 * M * E * Nout)
+                        linear_cols(xi, w_out, E * i, b_out, i > 0, y)
                     _call("pzn_maxpool_points_fwd_f32", _p(y), B, L, Nout, _p(f_global), _p(arg), st)
                 if y is None:         # (a placeholder keeps the output tuple's shape; it carries no data and no gradient)
                     y = f_global.new_empty((0,))

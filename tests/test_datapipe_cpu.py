@@ -186,3 +186,40 @@ def test_feeder_draws_keep_the_meaning_of_a_seed(mode):
         blocks.append((x / x.norm(p=2, dim=1, keepdim=True) * mag).numpy())
         want = np.concatenate(blocks, axis=1)
         assert want.shape == got.shape and np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("clouds", [1, 2])
+def test_fps_start_draws_keep_the_meaning_of_a_seed(clouds, monkeypatch):
+    """The host draws of a sampling plan against the generator calls written out: per cloud, in order, randint(0, N, (rows,))
+    for the level-1 starts and randint(0, 512, (rows,)) for the level-2 starts - exactly these calls and no other, from the
+    generator that is passed and, with None, from the global one.  (One cloud: assembly's pieces; two: predict5's pair,
+    Encoder's two levels before Encoder2's.)"""
+    import torch
+    from puzzlenet_amd import model5_b
+    rows, N, seed = 5, 1000, 11
+    n1 = model5_b.PCTransformer_nonsort.SA_LEVELS[0][0]
+    assert n1 == 512
+    real, calls = torch.randint, []
+
+    def spy(*a, **k):
+        calls.append((a, k.get("generator")))
+        return real(*a, **k)
+    want_gen = torch.Generator().manual_seed(seed)
+    want = [real(0, n_, (rows,), generator=want_gen) for _ in range(clouds) for n_ in (N, 512)]
+    gen = torch.Generator().manual_seed(seed)
+    monkeypatch.setattr(torch, "randint", spy)
+    got = model5_b.draw_fps_starts(clouds, rows, N, gen)
+    torch.manual_seed(seed)
+    got_global = model5_b.draw_fps_starts(clouds, rows, N, None)
+    after = real(0, 1 << 30, (4,))
+    monkeypatch.setattr(torch, "randint", real)
+    per_cloud = [((0, N, (rows,)), gen), ((0, 512, (rows,)), gen)]
+    assert calls == per_cloud * clouds + [(a, None) for a, _ in per_cloud] * clouds
+    assert len(got) == len(got_global) == 2 * clouds
+    for g, gg, w in zip(got, got_global, want):
+        assert g.dtype == torch.long and g.device.type == "cpu" and torch.equal(g, w) and torch.equal(gg, w)
+    # the global generator was consumed by exactly these calls: what it gives next is what follows them
+    torch.manual_seed(seed)
+    for _ in range(clouds):
+        real(0, N, (rows,)), real(0, 512, (rows,))
+    assert torch.equal(after, real(0, 1 << 30, (4,)))
