@@ -118,6 +118,37 @@ int pzn_icp_refine_f32(const float* a, const int64_t* a_of, const float* b, cons
                        float* T, float* score, float* score0, int32_t* iters_used,
                        int32_t* corr_a, int32_t* corr_b, pzn_stream_t stream);
 
+/* Refine all piece poses of Z placed assemblies jointly over every joint (no counterpart in the reference): one launch, one
+ * workgroup per puzzle, no workspace, no atomics, no grid-wide synchronisation, nothing waits for the device.  Puzzle z has
+ * K poses G0[z] ([K,4,4] row-major, piece frame to root frame), the mask movable[z] ([K] bytes, non-zero = may move) and J
+ * joint rows joints[z] ([J,2] int32: the ordered pair (i, j)).  Row e has the set A_e = a[a_of ? a_of[z J + e] : z J + e]
+ * [ka,3] in piece i's frame and B_e = b[b_of ? b_of[z J + e] : z J + e] [kb,3] in piece j's frame (a_of / b_of: NULL or int64
+ * [Z,J] rows of a / b, so one set can serve many joints).  A row with i < 0 is unused; a row with i or j outside [0, K) or
+ * i == j is skipped in the same way (the device does not report it; callers check their own host copy).  A pair listed twice
+ * counts twice, and a piece that is an end of more than 2 K rows - possible only that way - is never visited.
+ * Energy of a joint: E_e(G) = mean_r min_c |G_i a_r - G_j b_c|^2 + mean_c min_r |G_i a_r - G_j b_c|^2, points moved and
+ * distances formed as pzn_icp_refine_f32 does (fp32, lowest index on ties, sums in a fixed order); E_p = the fp32 sum in row
+ * order of E_e over the rows with i = p or j = p; E = that sum over all rows.
+ * A visit of piece p: the arg-mins of p's joints under G give, per joint, ka pairs of weight 1 / ka and kb pairs of weight
+ * 1 / kb, each (x = the point of p's side in p's frame, y = its partner's fp32 root-frame image); the candidate G_p' is their
+ * weighted least-squares rigid motion (float64 sums, Horn's quaternion in float64, rounded to fp32; a degenerate scatter of
+ * x by pzn_icp_refine_f32's rule keeps R_p and updates t); it is taken iff E_p' < E_p, anything else (NaN included) keeps
+ * G_p.  Only p's joints depend on G_p, so E falls with E_p; the fp32 sum E is held to that too: a candidate under which E
+ * would round above its current value (a matter of the last place) is left, so score <= score0 holds to the bit.  A sweep visits p = 0 .. K-1 in order, skipping pieces that are not movable or have no joint; later pieces see the
+ * earlier pieces' new poses.  The loop ends after `sweeps` sweeps or after a sweep that took nothing.
+ * Out: G[Z,K,4,4] (last rows exactly 0 0 0 1), score[Z] = E(G), score0[Z] = E(G0), joint_score[Z,J] = E_e(G) (0 for a
+ * skipped row), sweeps_used[Z] (int32: sweeps that took at least one candidate), accepted[Z,K] (int32: candidates taken per
+ * piece).  sweeps = 0 returns G0.  The same bits on every run.
+ * 1 <= K <= 64, 0 <= J <= K (K - 1), 1 <= ka, kb <= 1024 (pzn_joint_refine_supported: 1 / 0) and sweeps >= 0,
+ * PZN_EUNSUPPORTED otherwise, before any launch; Z = 0 or J = 0 is a success that launches nothing and writes nothing (the
+ * answer is G0 with scores of 0; ops.joint_refine fills it in). */
+int pzn_joint_refine_supported(int K, int J, int ka, int kb);
+int pzn_joint_refine_f32(const float* a, const int64_t* a_of, const float* b, const int64_t* b_of,
+                         const int32_t* joints, const float* G0, const uint8_t* movable,
+                         int Z, int K, int J, int ka, int kb, int sweeps,
+                         float* G, float* score, float* score0, float* joint_score,
+                         int32_t* sweeps_used, int32_t* accepted, pzn_stream_t stream);
+
 /* pointnet_util.py:118-119  dists.argsort()[:, :, :K] fused with the distance:
  * idx[B,S,K] = the K nearest points of xyz[B,N,3] to each new_xyz[B,S,3],
  * ascending by (distance, index) == a stable ascending sort.  K <= N. */

@@ -29,6 +29,13 @@ network's pose.  It lowers exactly the quantity the walks rank by, so T and scor
 (score never above the unrefined chamfer of the same rows); twist stays the network's output (the project has no SE(3)
 logarithm), every other field is untouched.
 
+refine_assembly(pieces, table, asm) is the step after the greedy walk: the walk composes pair poses along a spanning tree, so a
+piece's pose carries the summed error of the edges between it and the root, and every accepted joint that is no tree edge is
+never asked.  refine_assembly treats the placed assembly as a pose graph - every ordered pair of placed pieces whose table
+score is no larger than the worst tree edge's is a joint - and moves all pieces but the root so that the joints close
+together: block-coordinate descent that can only lower the summed score, one launch (ops.joint_refine, csrc/jointrefine.hip).
+assemble, match_pairs, refine_pairs and the progressive path do not change.
+
 Inference only: eval mode, torch.no_grad(), fp32, one GPU.  Out of scope: any training on merged parts or on more than two
 pieces, beam search or several merges per round, undoing a merge, and more than one GPU.
 """
@@ -45,6 +52,7 @@ Assembly = collections.namedtuple("Assembly", "root edges G placed")
 PieceCodes = collections.namedtuple("PieceCodes", "U V local_f g_max de_mrpcb top_m x2")
 PairBlock = collections.namedtuple("PairBlock", "twist T de_fpcb top_f score")
 Refined = collections.namedtuple("Refined", "T score score0 iters_used")
+JointRefined = collections.namedtuple("JointRefined", "G score score0 sweeps_used accepted joints")
 Progressive = collections.namedtuple("Progressive", "G edges placed cloud piece_id row_id parts")
 
 ENCODER_ROWS = 64      # pieces per encoder call (the fused per-point stem takes up to 64 clouds)
@@ -302,6 +310,63 @@ def assemble(score, T, max_score=None):
         placed[new] = True
         edges.append((i, j, float(s), new))
     return Assembly(root, edges, G, placed)
+
+
+def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None):
+    """Refine all placed poses of a greedy assembly jointly over every joint: pieces [K,N,3] (float32, on the GPU), table =
+    match_pairs' PairTable of them, asm = assemble's Assembly of that table -> JointRefined:
+
+      G [K,4,4]       float32, on the GPU: each piece into the root's frame; the root's and every unplaced piece's pose is
+                      asm.G's (rounded to float32), bit for bit
+      score, score0   0-d tensors: the sum over the joints of the table's score with both sides in the root's frame, under G and
+                      under asm.G; score <= score0
+      sweeps_used     0-d int32, accepted [K] int32: ops.joint_refine's
+      joints          the ordered pairs (i, j) used, a host list in row-major order
+
+    The joints are every (i, j), i != j, both placed, with table.score[i,j] <= joint_score; the default joint_score is the
+    largest score among asm.edges - a definition, not a measurement: the tree edges are then always joints and every placed
+    piece has one.  Joint (i, j) pairs pieces[i][table.top_f[i,j]] with pieces[j][table.top_m[j]] (one set per moved piece,
+    served to all its joints).  Every piece that is placed and not the root may move; sweeps = 0 returns asm.G.
+    One download (the scores the joints are chosen from), one gather and one launch."""
+    if not isinstance(pieces, torch.Tensor) or not pieces.is_cuda:
+        raise _lib.PznError("refine_assembly: pieces must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
+    if pieces.dim() != 3 or pieces.shape[2] != 3 or pieces.dtype != torch.float32:
+        raise _lib.PznError(f"refine_assembly expects float32 pieces[K,N,3]; got {pieces.dtype} {tuple(pieces.shape)}")
+    K, N, _ = pieces.shape
+    G0 = np.asarray(asm.G, dtype=np.float64)
+    placed = np.asarray(asm.placed, dtype=bool)
+    if table.score.shape != (K, K) or table.top_f.shape[:2] != (K, K) or table.top_m.shape[0] != K or G0.shape != (K, 4, 4) \
+            or placed.shape != (K,):
+        raise _lib.PznError(f"refine_assembly: the table and the assembly are not those of K = {K} pieces: score "
+                            f"{tuple(table.score.shape)}, top_f {tuple(table.top_f.shape)}, G {G0.shape}")
+    dev = pieces.device
+    with torch.no_grad():
+        S = table.score.detach().to("cpu", torch.float64).numpy()
+        if joint_score is None:
+            joint_score = max((float(e[2]) for e in asm.edges), default=-np.inf)
+        ok = placed[:, None] & placed[None, :] & ~np.eye(K, dtype=bool) & (S <= float(joint_score))
+        joints = [(int(i), int(j)) for i, j in zip(*np.nonzero(ok))]
+        J = len(joints)
+        g0 = torch.from_numpy(G0.astype(np.float32)).to(dev).reshape(1, K, 4, 4)
+        movable = placed.copy()
+        movable[int(asm.root)] = False
+        mv = torch.from_numpy(movable.astype(np.uint8)).to(dev).reshape(1, K)
+        jl = torch.tensor(joints, dtype=torch.int32).reshape(1, J, 2)
+        k = table.top_m.shape[1]
+        if J > 0:
+            ji = torch.tensor([i for i, _ in joints], dtype=torch.long, device=dev)
+            jj = torch.tensor([j for _, j in joints], dtype=torch.long, device=dev)
+            # one gather over the K N rows of all pieces: the J fixed-side sets, then one moved-side set per piece
+            rows_a = (ji[:, None] * N + table.top_f[ji, jj]).reshape(-1)
+            rows_b = (torch.arange(K, device=dev)[:, None] * N + table.top_m).reshape(-1)
+            picked = ops.index_points(pieces.contiguous().view(1, K * N, 3), torch.cat((rows_a, rows_b)).reshape(1, -1))[0]
+            a, b = picked[:J * k].view(J, k, 3), picked[J * k:].view(K, k, 3)
+            b_of = jj.reshape(1, J)
+        else:
+            a = b = pieces[:0, :k]
+            b_of = None
+        G, score, score0, _, used, accepted = ops.joint_refine(a, b, jl, g0, mv, sweeps, b_of=b_of)
+    return JointRefined(G[0], score[0], score0[0], used[0], accepted[0], joints)
 
 
 def apply(pieces, G):

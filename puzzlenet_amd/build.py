@@ -31,6 +31,7 @@ SOURCES = [
     ("fps.hip", ["-ffp-contract=off"] + NOSLP),
     ("mergefps.hip", ["-ffp-contract=off"] + NOSLP),
     ("icprefine.hip", ["-ffp-contract=off"] + NOSLP),
+    ("jointrefine.hip", ["-ffp-contract=off"] + NOSLP),
     ("knn.hip", ["-ffp-contract=off"]),
     ("group.hip", ["-ffp-contract=off"] + NOSLP),
     ("emd.hip", NOSLP),

@@ -24,7 +24,7 @@
 //     (m2 / tr^2 is about l2 / l1 for a thin set; points exactly on a line, rounded to fp32, sit near 1e-14).
 // Latency-bound: per iteration a serial chain of six barriers, a (ka | kb)-step scan and one lane's float64 solve; the
 // launch is parallel over problems only, and the grid walks when P exceeds ICP_MAX_GRID.
-#include "pzn_common.h"
+#include "pzn_rigid.h"      // the wave sums, horn_rotation, Pose / pose_move: shared with jointrefine.hip
 
 namespace {
 
@@ -32,106 +32,6 @@ constexpr int ICP_T = 256;                 // four wavefronts
 constexpr int ICP_W = ICP_T / PZN_WAVE;
 constexpr int ICP_MAX_K = 1024;            // 36 KB of point images + 4 KB of arg-mins + 0.5 KB of reduction slots: 40.5 KB of LDS at most
 constexpr int ICP_MAX_GRID = 512;          // two workgroups per CU of a 256-CU part; more problems share a workgroup in turn
-constexpr int ICP_SWEEPS = 12;             // cyclic Jacobi sweeps at most (a 4x4 converges in 5 to 7)
-constexpr double ICP_DEGENERATE = 1e-10;
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-  uint64_t u;
-  u = pzn::xor_lane_u64<1>((uint64_t)__double_as_longlong(v)), v += __longlong_as_double((long long)u);
-  u = pzn::xor_lane_u64<2>((uint64_t)__double_as_longlong(v)), v += __longlong_as_double((long long)u);
-  u = pzn::xor_lane_u64<4>((uint64_t)__double_as_longlong(v)), v += __longlong_as_double((long long)u);
-  u = pzn::xor_lane_u64<8>((uint64_t)__double_as_longlong(v)), v += __longlong_as_double((long long)u);
-  u = pzn::xor_lane_u64<16>((uint64_t)__double_as_longlong(v)), v += __longlong_as_double((long long)u);
-  u = pzn::xor_lane_u64<32>((uint64_t)__double_as_longlong(v)), v += __longlong_as_double((long long)u);
-  return v;
-}
-
-__device__ __forceinline__ float wave_sum_f32_dpp(float v) {
-  v = __fadd_rn(v, __uint_as_float(pzn::xor_lane<1>(__float_as_uint(v))));
-  v = __fadd_rn(v, __uint_as_float(pzn::xor_lane<2>(__float_as_uint(v))));
-  v = __fadd_rn(v, __uint_as_float(pzn::xor_lane<4>(__float_as_uint(v))));
-  v = __fadd_rn(v, __uint_as_float(pzn::xor_lane<8>(__float_as_uint(v))));
-  v = __fadd_rn(v, __uint_as_float(pzn::xor_lane<16>(__float_as_uint(v))));
-  v = __fadd_rn(v, __uint_as_float(pzn::xor_lane<32>(__float_as_uint(v))));
-  return v;
-}
-
-// One Jacobi rotation of the symmetric 4x4 A in the (P, Q) plane, accumulated into V (columns = eigenvectors).
-template <int P, int Q>
-__device__ __forceinline__ void jacobi_rot(double (&A)[4][4], double (&V)[4][4]) {
-  const double apq = A[P][Q];
-  if (apq == 0.0) return;
-  const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
-  const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-  const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double x = A[k][P], y = A[k][Q];
-    A[k][P] = c * x - s * y;
-    A[k][Q] = s * x + c * y;
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double x = A[P][k], y = A[Q][k];
-    A[P][k] = c * x - s * y;
-    A[Q][k] = s * x + c * y;
-  }
-  A[P][Q] = A[Q][P] = 0.0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double x = V[k][P], y = V[k][Q];
-    V[k][P] = c * x - s * y;
-    V[k][Q] = s * x + c * y;
-  }
-}
-
-// Horn's closed form: the rotation R (row-major) that maximises sum p . R q for S[u][v] = sum q_u p_v.
-__device__ void horn_rotation(const double (&S)[3][3], double (&R)[9]) {
-  double A[4][4], V[4][4];
-  A[0][0] = S[0][0] + S[1][1] + S[2][2];
-  A[1][1] = S[0][0] - S[1][1] - S[2][2];
-  A[2][2] = -S[0][0] + S[1][1] - S[2][2];
-  A[3][3] = -S[0][0] - S[1][1] + S[2][2];
-  A[0][1] = A[1][0] = S[1][2] - S[2][1];
-  A[0][2] = A[2][0] = S[2][0] - S[0][2];
-  A[0][3] = A[3][0] = S[0][1] - S[1][0];
-  A[1][2] = A[2][1] = S[0][1] + S[1][0];
-  A[1][3] = A[3][1] = S[2][0] + S[0][2];
-  A[2][3] = A[3][2] = S[1][2] + S[2][1];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < ICP_SWEEPS; ++sweep) {
-    const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[0][3] * A[0][3] + A[1][2] * A[1][2] + A[1][3] * A[1][3] +
-                       A[2][3] * A[2][3];
-    const double dia = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2] + A[3][3] * A[3][3];
-    if (off <= 1e-34 * dia) break;
-    jacobi_rot<0, 1>(A, V);
-    jacobi_rot<0, 2>(A, V);
-    jacobi_rot<0, 3>(A, V);
-    jacobi_rot<1, 2>(A, V);
-    jacobi_rot<1, 3>(A, V);
-    jacobi_rot<2, 3>(A, V);
-  }
-  // the column of the largest eigenvalue (first of equals), by selects: no dynamically indexed array
-  double l = A[0][0], w = V[0][0], x = V[1][0], y = V[2][0], z = V[3][0];
-#pragma unroll
-  for (int c = 1; c < 4; ++c) {
-    const bool take = A[c][c] > l;
-    l = take ? A[c][c] : l;
-    w = take ? V[0][c] : w, x = take ? V[1][c] : x, y = take ? V[2][c] : y, z = take ? V[3][c] : z;
-  }
-  const double inv = 1.0 / sqrt(w * w + x * x + y * y + z * z);
-  w *= inv, x *= inv, y *= inv, z *= inv;
-  R[0] = 1.0 - 2.0 * (y * y + z * z), R[1] = 2.0 * (x * y - w * z), R[2] = 2.0 * (x * z + w * y);
-  R[3] = 2.0 * (x * y + w * z), R[4] = 1.0 - 2.0 * (x * x + z * z), R[5] = 2.0 * (y * z - w * x);
-  R[6] = 2.0 * (x * z - w * y), R[7] = 2.0 * (y * z + w * x), R[8] = 1.0 - 2.0 * (x * x + y * y);
-}
-
-struct Pose {
-  float r[9], t[3];
-};
 
 struct Lds {
   float *ax, *ay, *az;      // fixed set, [ka]
@@ -148,9 +48,7 @@ struct Lds {
 __device__ float evaluate(const Lds& L, const Pose& g, int ka, int kb, int tid) {
   for (int j = tid; j < kb; j += ICP_T) {
     const float x = L.bx[j], y = L.by[j], z = L.bz[j];
-    L.tx[j] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(g.r[0], x), __fmul_rn(g.r[1], y)), __fmul_rn(g.r[2], z)), g.t[0]);
-    L.ty[j] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(g.r[3], x), __fmul_rn(g.r[4], y)), __fmul_rn(g.r[5], z)), g.t[1]);
-    L.tz[j] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(g.r[6], x), __fmul_rn(g.r[7], y)), __fmul_rn(g.r[8], z)), g.t[2]);
+    pose_move(g, x, y, z, L.tx[j], L.ty[j], L.tz[j]);
   }
   __syncthreads();
   float s1 = 0.f, s2 = 0.f;

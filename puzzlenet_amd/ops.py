@@ -278,6 +278,84 @@ def icp_refine(a, b, T0, iters, a_of=None, b_of=None, return_corr=False):
     return (T, score, score0, used, ca, cb) if return_corr else (T, score, score0, used)
 
 
+def joint_refine_supported(K, J, ka, kb):
+    return bool(_lib.load().pzn_joint_refine_supported(int(K), int(J), int(ka), int(kb)))
+
+
+def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None):
+    """Z pose graphs refined in one launch (pzn_joint_refine_f32): puzzle z has the poses G0[z] [K,4,4], the mask movable[z]
+    [K] (uint8 or bool) and the joint rows joints[z] [J,2] (int32 ordered pairs (i, j); a row with i < 0 is unused); row e has
+    the set a[a_of[z,e]] [ka,3] in piece i's frame and b[b_of[z,e]] [kb,3] in piece j's (int64 [Z,J]; the caller keeps them
+    inside a / b - they are not checked, that would wait for the device; without a map, a / b hold Z J sets).  Block-coordinate
+    descent over the pieces as include/pzn.h states it, at most `sweeps` sweeps -> (G [Z,K,4,4], score [Z], score0 [Z],
+    joint_score [Z,J], sweeps_used [Z] int32, accepted [Z,K] int32); score = E(G) <= score0 = E(G0); sweeps = 0 returns G0.
+    joints may be a host tensor, the caller's own copy: then every used row is checked (0 <= i, j < K, i != j, no pair twice;
+    PznError) and the list is uploaded; a device tensor is not checked, and the kernel skips such rows.
+    1 <= K <= 64, J <= K (K - 1), 1 <= ka, kb <= 1024 and sweeps >= 0 (PznUnsupported beyond).  Z = 0 or J = 0 launches
+    nothing and returns G0 with scores of 0.  No autograd, nothing waits for the device."""
+    for name, t, dts in (("a", a, (torch.float32,)), ("b", b, (torch.float32,)), ("G0", G0, (torch.float32,)),
+                         ("joints", joints, (torch.int32,)), ("movable", movable, (torch.uint8, torch.bool)),
+                         ("a_of", a_of, (torch.int64,)), ("b_of", b_of, (torch.int64,))):
+        if isinstance(t, torch.Tensor) and t.dtype not in dts:      # (no silent conversion)
+            raise _lib.PznError(f"joint_refine: {name} must be {' or '.join(str(d) for d in dts)}; got {t.dtype}")
+    a, b, G0 = _f32(a, "a"), _f32(b, "b"), _f32(G0, "G0")
+    if a.dim() != 3 or b.dim() != 3 or a.shape[2] != 3 or b.shape[2] != 3:
+        raise _lib.PznError(f"joint_refine: expected a[.,ka,3], b[.,kb,3]; got {tuple(a.shape)}, {tuple(b.shape)}")
+    if G0.dim() != 4 or G0.shape[2:] != (4, 4):
+        raise _lib.PznError(f"joint_refine: expected G0[Z,K,4,4]; got {tuple(G0.shape)}")
+    Z, K, ka, kb = G0.shape[0], G0.shape[1], a.shape[1], b.shape[1]
+    if not isinstance(joints, torch.Tensor) or joints.dim() != 3 or joints.shape[0] != Z or joints.shape[2] != 2:
+        raise _lib.PznError(f"joint_refine: expected joints[{Z},J,2]; got "
+                            f"{tuple(joints.shape) if isinstance(joints, torch.Tensor) else type(joints).__name__}")
+    J = joints.shape[1]
+    if not joints.is_cuda:      # the caller's host copy: a check that waits for nothing
+        i, j = joints[..., 0], joints[..., 1]
+        bad = (i >= 0) & ((i >= K) | (j < 0) | (j >= K) | (i == j))
+        if bool(bad.any()):
+            z, e = (int(v) for v in bad.nonzero()[0])
+            raise _lib.PznError(f"joint_refine: joints[{z},{e}] = ({int(i[z, e])}, {int(j[z, e])}) is no joint of K = {K} pieces")
+        key = torch.where(i >= 0, i.long() * K + j.long(), -1 - torch.arange(J).expand(Z, J))      # unused rows: all different
+        if J > 1 and bool((key.sort(dim=1).values.diff(dim=1) == 0).any()):
+            raise _lib.PznError("joint_refine: a pair (i, j) is listed twice in one puzzle's joints")
+        joints = joints.to(a.device)
+    joints = _req(joints, torch.int32, "joints")
+    movable = _req(movable, movable.dtype if isinstance(movable, torch.Tensor) else torch.uint8, "movable")
+    if movable.shape != (Z, K):
+        raise _lib.PznError(f"joint_refine: expected movable[{Z},{K}]; got {tuple(movable.shape)}")
+    movable = movable.view(torch.uint8)
+    maps = []
+    for name, m, x in (("a_of", a_of, a), ("b_of", b_of, b)):
+        if m is None:
+            if x.shape[0] != Z * J:
+                raise _lib.PznError(f"joint_refine: {name[0]} holds {x.shape[0]} sets for Z J = {Z * J} joint rows and no {name} is given")
+        else:
+            m = _i64(m, name)
+            if m.shape != (Z, J):
+                raise _lib.PznError(f"joint_refine: expected {name}[{Z},{J}]; got {tuple(m.shape)}")
+            if x.shape[0] == 0 and Z * J > 0:
+                raise _lib.PznError(f"joint_refine: {name} indexes an empty {name[0]}")
+        maps.append(m)
+    sweeps = int(sweeps)
+    if sweeps < 0 or not joint_refine_supported(K, J, ka, kb):
+        raise _lib.PznUnsupported(f"joint_refine: K = {K}, J = {J}, ka = {ka}, kb = {kb}, sweeps = {sweeps} "
+                                  "(1 <= K <= 64, J <= K (K - 1), 1 <= ka, kb <= 1024, sweeps >= 0)")
+    dev = a.device
+    if Z == 0 or J == 0:
+        return (G0.clone(), torch.zeros((Z,), dtype=torch.float32, device=dev), torch.zeros((Z,), dtype=torch.float32, device=dev),
+                torch.zeros((Z, J), dtype=torch.float32, device=dev), torch.zeros((Z,), dtype=torch.int32, device=dev),
+                torch.zeros((Z, K), dtype=torch.int32, device=dev))
+    G = torch.empty((Z, K, 4, 4), dtype=torch.float32, device=dev)
+    score = torch.empty((Z,), dtype=torch.float32, device=dev)
+    score0 = torch.empty_like(score)
+    joint_score = torch.empty((Z, J), dtype=torch.float32, device=dev)
+    used = torch.empty((Z,), dtype=torch.int32, device=dev)
+    accepted = torch.empty((Z, K), dtype=torch.int32, device=dev)
+    with _on(dev):
+        _call("pzn_joint_refine_f32", _p(a), _p(maps[0]), _p(b), _p(maps[1]), _p(joints), _p(G0), _p(movable), Z, K, J, ka, kb,
+              sweeps, _p(G), _p(score), _p(score0), _p(joint_score), _p(used), _p(accepted), _stream())
+    return G, score, score0, joint_score, used, accepted
+
+
 def knn(xyz, new_xyz, K):
     xyz, new_xyz = _f32(xyz, "xyz"), _f32(new_xyz, "new_xyz")
     B, N, _ = xyz.shape

@@ -2,7 +2,7 @@
 assembled cloud.
 
     python tools/assemble.py --pieces pieces.npy [--ckpt model.ckpt] [--k 128] [--max-score S] [--out PREFIX] [--progressive]
-                             [--refine N] [--gt PREFIX_gt.npz]
+                             [--refine N] [--joint N] [--gt PREFIX_gt.npz]
 
 pieces.npy holds [K, N, 3] float32 (N = the model's points per piece).  Prints the score table and the edges in
 placement order, writes PREFIX_G.npy ([K,4,4], each piece into the root's frame) and PREFIX_cloud.npy ([K,N,3]).
@@ -11,6 +11,9 @@ points and matched again -; PREFIX_G.npy then maps each piece into the frame of 
 is the [N,3] part around the first pair, PREFIX_piece_id.npy / PREFIX_row_id.npy say where each of its points came from.
 --refine N: every pair pose is refined on its picked boundary points before it is used (assembly.refine_pairs: symmetric
 point-to-point ICP, at most N accepted steps, one launch per table or per round); 0, the default, uses the network's poses.
+--joint N (the greedy walk only): after the walk all placed poses are refined together over every joint - every pair of
+placed pieces that scores no worse than the walk's worst edge - by at most N sweeps of assembly.refine_assembly (one launch);
+PREFIX_G.npy and PREFIX_cloud.npy are then the refined ones, and with --gt the assembly is scored before and after.
 --gt PREFIX_gt.npz (written by tools/fracture.py beside the pieces): the assembly is scored against the truth - per piece the
 rotation error in degrees, the translation error and the mean squared distance of its points from where they belong, the share
 of pieces placed right (assembly.evaluate) and, for the greedy walk, the share of its edges between pieces that touch.
@@ -44,10 +47,13 @@ def main():
     ap.add_argument("--progressive", action="store_true", help="merge placed parts, resample and match again after every placement")
     ap.add_argument("--keep-matched", action="store_true", help="--progressive: keep the matched boundary points in the merged part")
     ap.add_argument("--refine", type=int, default=0, help="ICP steps at most per pair pose on the picked boundary points (0: none)")
+    ap.add_argument("--joint", type=int, default=0, help="sweeps at most of the joint refinement after the greedy walk (0: none)")
     ap.add_argument("--gt", default=None, help="PREFIX_gt.npz of tools/fracture.py: score the assembly against the truth")
     args = ap.parse_args()
     if args.refine < 0:
         sys.exit("--refine: 0 or a number of steps")
+    if args.joint < 0 or (args.joint and args.progressive):
+        sys.exit("--joint: 0 or a number of sweeps, and for the greedy walk only (not with --progressive)")
 
     if not torch.cuda.is_available():
         sys.exit("tools/assemble.py needs a GPU: puzzlenet_amd has no CPU path")
@@ -104,12 +110,21 @@ def main():
     left = [k for k in range(K) if not result.placed[k]]
     if left:
         print(f"not placed: {left}")
-    np.save(args.out + "_G.npy", result.G)
-    np.save(args.out + "_cloud.npy", assembly.apply(x, result.G).cpu().numpy())
+    G = result.G
+    if args.joint:
+        if gt is not None:
+            print(f"against {args.gt} (in the root's frame), before the joint refinement:")
+            report(assembly.evaluate(G, result.placed, gt["pose"], gt["rest"], result.root, result.edges, gt["mates"]))
+        jr = assembly.refine_assembly(x, table, result, sweeps=args.joint)
+        G = jr.G.double().cpu().numpy()
+        print(f"joint refinement over {len(jr.joints)} joints: summed score {float(jr.score0):.6f} -> {float(jr.score):.6f}, "
+              f"{int(jr.sweeps_used)} sweeps, candidates taken per piece {jr.accepted.tolist()}")
+    np.save(args.out + "_G.npy", G)
+    np.save(args.out + "_cloud.npy", assembly.apply(x, G).cpu().numpy())
     print(f"wrote {args.out}_G.npy, {args.out}_cloud.npy")
     if gt is not None:
-        print(f"against {args.gt} (in the root's frame):")
-        report(assembly.evaluate(result.G, result.placed, gt["pose"], gt["rest"], result.root, result.edges, gt["mates"]))
+        print(f"against {args.gt} (in the root's frame){', after the joint refinement' if args.joint else ''}:")
+        report(assembly.evaluate(G, result.placed, gt["pose"], gt["rest"], result.root, result.edges, gt["mates"]))
 
 
 if __name__ == "__main__":

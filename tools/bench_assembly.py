@@ -19,7 +19,9 @@ launch, every pair stopping by the accept rule - against the torch composition a
 for the final score) on the same boundaries and poses, once with 30 fixed iterations (it has no accept rule) and once with as
 many iterations as the LONGEST pair of the fused launch ran (iters_used max + 1: the matched count, since the launch lasts as
 long as its longest problem); device time between two events around each call, alternated in one process; per-iteration
-figures and the library's launches beside them; and (b) match_pairs with refine = 30 against refine = 0 (host wall time around
+figures and the library's launches beside them; (a') assembly.refine_assembly on the greedy walk over the same table and
+over its first 8 pieces' - the time of its one kernel, 30 sweeps at most, with the default joint set and with every ordered
+pair as a joint (there is nothing earlier to compare it with); and (b) match_pairs with refine = 30 against refine = 0 (host wall time around
 a synchronised call, alternated).
 
 Needs a GPU (there is no CPU path)."""
@@ -191,6 +193,26 @@ def refine(args):
     torch.cuda.synchronize()
     k_f = ops.ktimer_stop()
     icp = [v for name, v in k_f.items() if "icp_refine_kernel" in name]
+    # the joint refinement of the greedy assembly (assembly.refine_assembly: one launch of joint_refine_kernel, 30 sweeps at
+    # most) at K = 8 (the first 8 pieces' sub-table) and K = 16: the default joint set and every ordered pair
+    joint = {}
+    for Kj in (8, K):
+        sub = assembly.PairTable(None, table.T[:Kj, :Kj].contiguous(), None, None, table.top_f[:Kj, :Kj].contiguous(),
+                                 table.top_m[:Kj].contiguous(), table.score[:Kj, :Kj].contiguous(), None)
+        asm = assembly.assemble(sub.score, sub.T)
+        for label, limit in (("default_joints", None), ("all_pairs", float("inf"))):
+            run = lambda: assembly.refine_assembly(pieces[:Kj], sub, asm, sweeps=ITERS, joint_score=limit)
+            for _ in range(args.warmup):
+                run()
+            ops.ktimer_start()
+            jr = run()
+            torch.cuda.synchronize()
+            k_j = ops.ktimer_stop()
+            ms = [v[1] for name, v in k_j.items() if "joint_refine_kernel" in name]
+            joint[f"K{Kj}_{label}"] = {"joints": len(jr.joints), "sweeps_used": int(jr.sweeps_used), "kernel_ms": ms[0] if ms else None,
+                                       "device_ms": _spread([_device_ms(run, 1) for _ in range(args.reps)]),
+                                       "score_over_score0": float(jr.score / jr.score0)}
+    print(json.dumps({"joint_refine_kernel_ms": joint}))
     off = ~torch.eye(K, dtype=torch.bool, device=dev)
     f_med, c_med, m_med = statistics.median(f_ms), statistics.median(c_ms), statistics.median(m_ms)
     result = {"tool": "tools/bench_assembly.py --refine", "device": torch.cuda.get_device_name(0), "dtype": "float32", "K": K,
@@ -204,6 +226,7 @@ def refine(args):
                                    "composition": c_med / ITERS},
               "refine_pairs_library_launches": {k_: v[0] for k_, v in k_f.items()},
               "icp_refine_kernel_ms": icp[0][1] if icp else None,
+              "joint_refine_kernel_ms": joint,
               "iters_used_mean": float(r.iters_used.float().mean()), "iters_used_max": int(r.iters_used.max()),
               "score_over_score0_mean_off_diagonal": float((r.score[off] / r.score0[off]).mean()),
               "composition_fixed_score_over_score0_mean_off_diagonal": float((sc.view(K, K)[off] / r.score0[off]).mean())}
