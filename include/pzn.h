@@ -149,6 +149,34 @@ int pzn_joint_refine_f32(const float* a, const int64_t* a_of, const float* b, co
                          float* G, float* score, float* score0, float* joint_score,
                          int32_t* sweeps_used, int32_t* accepted, pzn_stream_t stream);
 
+/* The greedy walk over Z pair tables and the joint list of every walk (no counterpart in the reference; assembly.assemble and
+ * the joint selection of assembly.refine_assembly for Z puzzles): one launch, one wavefront per puzzle, no workspace, no
+ * atomics, nothing waits for the device.  Puzzle z has score[z] ([K,K] fp32) and T[z] ([K,K,4,4] fp32, T[i,j] maps piece j
+ * into piece i's frame) and count[z] pieces (int32 [Z]; NULL: K for every puzzle): only entries with i, j < count[z] exist, and
+ * nothing else of score or T is read.  A count outside [2, K] gives root -1, nothing placed, no edge and no joint.
+ * Key of entry (i, j): its fp32 score; NaN and the diagonal count as +inf.  Keys compare as floats (-0 equals 0); of equal
+ * keys the lowest i K + j is the smaller.
+ * Walk: root[z] = the row of the smallest key; placed = {root}.  A round takes the smallest key among the ordered pairs
+ * with exactly one end placed; the walk stops at a key that is not finite or at (double)key > max_score (+inf: never; NaN is
+ * PZN_EINVAL).  A placed fixed end i gives G[j] = G[i] T[i,j], otherwise G[i] = G[j] inv(T[i,j]) with inv = [R^T, -(R^T t)]
+ * and the last row 0 0 0 1.  Poses are float64 from the fp32 T, every operation rounded on its own: an entry of a 4x4 product
+ * is ((a0 b0 + a1 b1) + a2 b2) + a3 b3 over all four terms, an entry of R^T t is (r0 t0 + r1 t1) + r2 t2.  Unplaced pieces
+ * keep the identity.
+ * Joints: every (i, j), i != j, both placed, with (double)score[i,j] <= joint_score on the score as stored (NaN is never a
+ * joint; +inf is one under joint_score = +inf); joint_score = NaN means the largest edge score of that puzzle, and no joint
+ * where the walk made no edge.
+ * Out: root[Z] int32; edges[Z,K-1,3] int32 rows (i, j, new) in placement order and edge_score[Z,K-1] (the score as stored),
+ * unused rows -1 and +inf; n_edges[Z] int32; G[Z,K,4,4] float64; placed[Z,K] bytes 0 / 1; joints[Z,K(K-1),2] int32 in
+ * row-major order of (i, j), unused rows (-1, -1); n_joints[Z] int32.  The same bits on every run.
+ * 2 <= K <= 64 (pzn_assemble_walk_supported: 1 / 0), PZN_EUNSUPPORTED otherwise, before any launch; Z = 0 is a success that
+ * launches nothing. */
+int pzn_assemble_walk_supported(int K);
+int pzn_assemble_walk_f32(const float* score, const float* T, const int32_t* count,
+                          double max_score, double joint_score, int Z, int K,
+                          int32_t* root, int32_t* edges, float* edge_score, int32_t* n_edges,
+                          double* G, uint8_t* placed, int32_t* joints, int32_t* n_joints,
+                          pzn_stream_t stream);
+
 /* pointnet_util.py:118-119  dists.argsort()[:, :, :K] fused with the distance:
  * idx[B,S,K] = the K nearest points of xyz[B,N,3] to each new_xyz[B,S,3],
  * ascending by (distance, index) == a stable ascending sort.  K <= N. */

@@ -36,6 +36,12 @@ score is no larger than the worst tree edge's is a joint - and moves all pieces 
 together: block-coordinate descent that can only lower the summed score, one launch (ops.joint_refine, csrc/jointrefine.hip).
 assemble, match_pairs, refine_pairs and the progressive path do not change.
 
+A batch of Z puzzles (datapipe.fracture returns one) goes through the same chain without the host in between: match_puzzles (one
+encode_pieces over the Z P pieces, so the encoders see full batches), assemble_batch (the greedy walk and the joint list of all
+Z puzzles in one launch, ops.assemble_walk, csrc/assemblewalk.hip; walk_rule is its numpy statement), refine_assembly_batch (the
+one ops.joint_refine launch for all of them) and evaluate_batch (evaluate in float64 torch on the device).  The per-puzzle
+functions are not touched.
+
 Inference only: eval mode, torch.no_grad(), fp32, one GPU.  Out of scope: any training on merged parts or on more than two
 pieces, beam search or several merges per round, undoing a merge, and more than one GPU.
 """
@@ -442,6 +448,261 @@ def evaluate(G, placed, pose, rest, root, edges=None, mates=None, tol=0.01):
     if edges is not None and mates is not None and len(edges) > 0:
         m = np.asarray(_host(mates) != 0)
         edge_precision = float(np.mean([bool(m[int(e[0]), int(e[1])]) for e in edges]))
+    return Evaluation(rot_deg, trans, msd, part_ok, part_accuracy, edge_precision)
+
+
+# --------------------------------------------------------------------------- a batch of puzzles on the device
+
+AssemblyBatch = collections.namedtuple("AssemblyBatch", "root edges edge_score n_edges G placed movable joints n_joints")
+WalkRule = collections.namedtuple("WalkRule", "root edges edge_score n_edges G placed joints n_joints")
+
+
+def _dot4(a0, b0, a1, b1, a2, b2, a3, b3):
+    return ((a0 * b0 + a1 * b1) + a2 * b2) + a3 * b3
+
+
+def _rule_product(A, B):
+    """The 4x4 product of the walk rule on lists of Python floats (IEEE double): every entry ((a0 b0 + a1 b1) + a2 b2) + a3 b3."""
+    return [[_dot4(A[u][0], B[0][v], A[u][1], B[1][v], A[u][2], B[2][v], A[u][3], B[3][v]) for v in range(4)] for u in range(4)]
+
+
+def _rule_inverse(T):
+    """[R^T, -(R^T t)] with the last row 0 0 0 1; an entry of R^T t is (r0 t0 + r1 t1) + r2 t2."""
+    out = [[T[v][u] for v in range(3)] + [-((T[0][u] * T[0][3] + T[1][u] * T[1][3]) + T[2][u] * T[2][3])] for u in range(3)]
+    out.append([0.0, 0.0, 0.0, 1.0])
+    return out
+
+
+def walk_rule(score, T, count=None, max_score=None, joint_score=None):
+    """The numpy statement of ops.assemble_walk (csrc/assemblewalk.hip, the rule in include/pzn.h), which is held to it bit for
+    bit, G included: assemble() and the joint selection of refine_assembly() for Z puzzles, on the host.  score [Z,K,K] (read as
+    float32), T [Z,K,K,4,4] (float32), count [Z] or None, tensors or arrays -> WalkRule of numpy arrays in the kernel's shapes
+    and types: root [Z] int32, edges [Z,K-1,3] int32, edge_score [Z,K-1] float32, n_edges [Z] int32, G [Z,K,4,4] float64, placed
+    [Z,K] uint8, joints [Z,K(K-1),2] int32, n_joints [Z] int32.
+
+    Key of entry (i, j): its float32 score, NaN and the diagonal as +inf; compared as floats, ties to the lowest i K + j; only
+    i, j < count[z] exist.  The root is the row of the smallest key; a round takes the smallest key among the ordered pairs with
+    exactly one end placed and stops at a key that is not finite or above max_score.  Poses are composed in float64 with every
+    operation rounded on its own (_rule_product, _rule_inverse).  joint_score None: the puzzle's largest edge score."""
+    as_np = lambda a, dt: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(dt)
+    S, P = as_np(score, np.float32), as_np(T, np.float32)
+    Z, K = S.shape[0], S.shape[1]
+    if S.shape != (Z, K, K) or P.shape != (Z, K, K, 4, 4) or K < 2:
+        raise ValueError(f"walk_rule expects score[Z,K,K], T[Z,K,K,4,4] with K >= 2; got {S.shape}, {P.shape}")
+    counts = np.full(Z, K, dtype=np.int64) if count is None else as_np(count, np.int64)
+    inf = float("inf")
+    limit = inf if max_score is None else float(max_score)
+    root = np.full(Z, -1, dtype=np.int32)
+    edges = np.full((Z, K - 1, 3), -1, dtype=np.int32)
+    edge_score = np.full((Z, K - 1), np.inf, dtype=np.float32)
+    n_edges = np.zeros(Z, dtype=np.int32)
+    G = np.tile(np.eye(4), (Z, K, 1, 1))
+    placed = np.zeros((Z, K), dtype=np.uint8)
+    joints = np.full((Z, K * (K - 1), 2), -1, dtype=np.int32)
+    n_joints = np.zeros(Z, dtype=np.int32)
+    for z in range(Z):
+        c = int(counts[z])
+        if not 2 <= c <= K:
+            continue
+        raw = S[z].tolist()                              # float32 values as Python floats (exact)
+        key = [[inf if (i == j or raw[i][j] != raw[i][j]) else raw[i][j] for j in range(c)] for i in range(c)]
+        best, at = inf, (0, 0)                           # the first row-major position of the smallest key
+        for i in range(c):
+            for j in range(c):
+                if key[i][j] < best:
+                    best, at = key[i][j], (i, j)
+        r = at[0]
+        root[z] = r
+        inside = [False] * c
+        inside[r] = True
+        pose = {r: [[1.0 if u == v else 0.0 for v in range(4)] for u in range(4)]}
+        worst = -inf
+        for e in range(c - 1):
+            best, at = inf, None
+            for i in range(c):
+                for j in range(c):
+                    if inside[i] != inside[j] and (at is None or key[i][j] < best):
+                        best, at = key[i][j], (i, j)
+            if at is None or not np.isfinite(best) or best > limit:
+                break
+            i, j = at
+            Tij = P[z, i, j].astype(np.float64).tolist()
+            if inside[i]:
+                new = j
+                pose[j] = _rule_product(pose[i], Tij)
+            else:
+                new = i
+                pose[i] = _rule_product(pose[j], _rule_inverse(Tij))
+            inside[new] = True
+            edges[z, e] = (i, j, new)
+            edge_score[z, e] = S[z, i, j]
+            worst = max(worst, raw[i][j])
+            n_edges[z] = e + 1
+        for p, g in pose.items():
+            G[z, p] = np.array(g, dtype=np.float64)
+        placed[z, :c] = inside
+        js = worst if joint_score is None or joint_score != joint_score else float(joint_score)      # (NaN is the kernel's None)
+        n = 0
+        if n_edges[z] > 0:
+            for i in range(c):
+                for j in range(c):
+                    if i != j and inside[i] and inside[j] and raw[i][j] <= js:
+                        joints[z, n] = (i, j)
+                        n += 1
+        n_joints[z] = n
+    return WalkRule(root, edges, edge_score, n_edges, G, placed, joints, n_joints)
+
+
+def assemble_batch(score, T, count=None, max_score=None, joint_score=None):
+    """assemble() and the joint selection of refine_assembly() for Z puzzles in ONE launch (ops.assemble_walk), everything on
+    the device: score [Z,K,K], T [Z,K,K,4,4] (float32, on the GPU; match_puzzles' fields), count [Z] int32 or None (the pieces of
+    every puzzle), max_score and joint_score as assemble and refine_assembly take them -> AssemblyBatch:
+
+      root [Z] int32            -1 for a puzzle whose count is outside [2, K]
+      edges [Z,K-1,3] int32     (i, j, new) in placement order, unused rows -1;  edge_score [Z,K-1], unused +inf;  n_edges [Z]
+      G [Z,K,4,4] float64       each piece into its root's frame, the identity where not placed
+      placed, movable [Z,K] bool     movable = placed and not the root: what refine_assembly_batch lets move
+      joints [Z,K(K-1),2] int32      the joints of refine_assembly in its order, unused rows (-1, -1);  n_joints [Z]
+
+    Discrete outputs are assemble's bit for bit; G follows walk_rule bit for bit (assemble composes with numpy's matmul, a
+    last-place matter).  Nothing waits for the device."""
+    root, edges, edge_score, n_edges, G, placed, joints, n_joints = ops.assemble_walk(score, T, count, max_score, joint_score)
+    with torch.no_grad():
+        placed = placed.bool()
+        index = torch.arange(placed.shape[1], dtype=torch.int32, device=placed.device)
+        movable = placed & (index[None, :] != root[:, None])
+    return AssemblyBatch(root, edges, edge_score, n_edges, G, placed, movable, joints, n_joints)
+
+
+def match_puzzles(model, pieces, k=128, start=None, refine=0):
+    """match_pairs for Z puzzles of P pieces: pieces [Z,P,N,3] (float32, on the GPU) -> PairTable whose every field carries a
+    leading Z (twist [Z,P,P,6], T [Z,P,P,4,4], de_fpcb [Z,P,P,2,N], de_mrpcb [Z,P,2,N], top_f [Z,P,P,k], top_m [Z,P,k],
+    score [Z,P,P] with +inf on the diagonals, x2 [Z,P,256,3]).  The Z P pieces go through ONE encode_pieces, so the encoders run
+    on full 64-row batches however small a puzzle is; pair_block then runs per puzzle on the slices of the codes.
+    start = (s1[Z,P], s2[Z,P]) as match_pairs takes its starts; refine as match_pairs takes it.  x2 is match_pairs' of the
+    same puzzle and starts bit for bit; the fields behind the few-row layers (twist, and with it T and score) are not equal
+    bit for bit between two calls of match_pairs either, and agree with it as two such calls do.  Nothing waits for the device."""
+    refine = _check_refine(refine, "match_puzzles")
+    if not isinstance(pieces, torch.Tensor) or not pieces.is_cuda:
+        raise _lib.PznError("match_puzzles: pieces must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
+    if pieces.dim() != 4 or pieces.shape[3] != 3 or pieces.dtype != torch.float32 or pieces.shape[0] < 1:
+        raise _lib.PznError(f"match_puzzles expects float32 pieces[Z,P,N,3] with Z >= 1; got {pieces.dtype} {tuple(pieces.shape)}")
+    Z, P, N, _ = pieces.shape
+    if P < 2:
+        raise _lib.PznError(f"match_puzzles: P = {P} pieces a puzzle (>= 2)")
+    pieces = pieces.contiguous()
+    flat = pieces.view(Z * P, N, 3)
+    if start is not None:
+        s1, s2 = (torch.as_tensor(s, dtype=torch.long) for s in start)
+        if tuple(s1.shape) != (Z, P) or tuple(s2.shape) != (Z, P):
+            raise _lib.PznError(f"match_puzzles: start = (s1[{Z},{P}], s2[{Z},{P}]); got {tuple(s1.shape)}, {tuple(s2.shape)}")
+        start = (s1.reshape(Z * P), s2.reshape(Z * P))
+    codes = encode_pieces(model, flat, k, start, _who="match_puzzles", _least=2)
+    blocks = []
+    for z in range(Z):
+        cz = PieceCodes(*(f[z * P:(z + 1) * P] for f in codes))
+        blocks.append(pair_block(model, pieces[z], cz, pieces[z], cz, k, refine))
+    with torch.no_grad():
+        twist, T, y_f, top_f, score = (torch.stack(f, dim=0) for f in zip(*(b._replace(de_fpcb=b.de_fpcb.permute(0, 1, 3, 2))
+                                                                          for b in blocks)))
+        de_fpcb = y_f.permute(0, 1, 2, 4, 3)              # as in match_pairs: a permuted view of the kernel's [.,P,P,N,2]
+        score = score.masked_fill(torch.eye(P, dtype=torch.bool, device=pieces.device), float("inf"))
+        per_piece = lambda f: f.view(Z, P, *f.shape[1:])
+    return PairTable(twist, T, de_fpcb, per_piece(codes.de_mrpcb), top_f, per_piece(codes.top_m), score, per_piece(codes.x2))
+
+
+def refine_assembly_batch(pieces, table, asm, sweeps=30):
+    """refine_assembly for Z puzzles with no download: pieces [Z,P,N,3] (float32, on the GPU), table = match_puzzles' PairTable
+    of them, asm = assemble_batch's AssemblyBatch of that table -> JointRefined whose fields carry a leading Z: G [Z,P,4,4]
+    float32, score, score0, sweeps_used [Z], accepted [Z,P], joints = asm.joints (the device tensor, unused rows (-1, -1)).
+
+    Joint row e = (i, j) of puzzle z pairs pieces[z,i][table.top_f[z,i,j]] with pieces[z,j][table.top_m[z,j]]; which rows those
+    are is known only on the device, so ONE gather picks the set of every ordered pair and of every moved piece - Z P^2 + Z P
+    sets of k points, 12 k Z P (P + 1) bytes (7.1 MB at Z = 64, P = 8, k = 128) - and the rows find theirs through
+    a_of = z P^2 + i P + j and b_of = z P + j, computed from asm.joints in torch (unused rows map to set 0 and are skipped by
+    the kernel).  G0 = asm.G rounded to float32, movable = asm.movable, then the one launch of ops.joint_refine for all Z
+    puzzles.  Per puzzle the result is refine_assembly's bit for bit.  Nothing waits for the device."""
+    if not isinstance(pieces, torch.Tensor) or not pieces.is_cuda:
+        raise _lib.PznError("refine_assembly_batch: pieces must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
+    if pieces.dim() != 4 or pieces.shape[3] != 3 or pieces.dtype != torch.float32:
+        raise _lib.PznError(f"refine_assembly_batch expects float32 pieces[Z,P,N,3]; got {pieces.dtype} {tuple(pieces.shape)}")
+    Z, P, N, _ = pieces.shape
+    J = P * (P - 1)
+    if tuple(table.top_f.shape[:3]) != (Z, P, P) or tuple(table.top_m.shape[:2]) != (Z, P) or tuple(asm.G.shape) != (Z, P, 4, 4) \
+            or tuple(asm.joints.shape) != (Z, J, 2) or tuple(asm.movable.shape) != (Z, P):
+        raise _lib.PznError(f"refine_assembly_batch: the table and the assembly are not those of Z = {Z} puzzles of P = {P} "
+                            f"pieces: top_f {tuple(table.top_f.shape)}, top_m {tuple(table.top_m.shape)}, G {tuple(asm.G.shape)}, "
+                            f"joints {tuple(asm.joints.shape)}")
+    dev = pieces.device
+    with torch.no_grad():
+        k = table.top_m.shape[2]
+        piece_row = torch.arange(Z * P, dtype=torch.long, device=dev).view(Z, P) * N                     # first row of piece (z, p)
+        rows_a = (piece_row[:, :, None, None] + table.top_f).reshape(-1)                                # [Z,P,P,k]
+        rows_b = (piece_row[:, :, None] + table.top_m).reshape(-1)                                      # [Z,P,k]
+        picked = ops.index_points(pieces.contiguous().view(1, Z * P * N, 3), torch.cat((rows_a, rows_b)).reshape(1, -1))[0]
+        a, b = picked[:Z * P * P * k].view(Z * P * P, k, 3), picked[Z * P * P * k:].view(Z * P, k, 3)
+        ji, jj = asm.joints[..., 0].long(), asm.joints[..., 1].long()
+        used = ji >= 0
+        first = torch.arange(Z, dtype=torch.long, device=dev)[:, None]
+        a_of = torch.where(used, (first * P + ji) * P + jj, torch.zeros_like(ji))
+        b_of = torch.where(used, first * P + jj, torch.zeros_like(jj))
+        G, score, score0, _, used_sweeps, accepted = ops.joint_refine(a, b, asm.joints, asm.G.to(torch.float32), asm.movable, sweeps,
+                                                                      a_of=a_of, b_of=b_of)
+    return JointRefined(G, score, score0, used_sweeps, accepted, asm.joints)
+
+
+def _mm(A, B):
+    """[...,a,b] x [...,b,c] in the tensors' own type by products and one sum: small float64 matrices need no GEMM library."""
+    return (A.unsqueeze(-1) * B.unsqueeze(-3)).sum(dim=-2)
+
+
+def evaluate_batch(G, placed, pose, rest, root, edges=None, n_edges=None, mates=None, tol=0.01):
+    """evaluate() for Z puzzles in float64 torch on the device, with its formulas (the atan2 form of the angle included): G
+    [Z,P,4,4] (assemble_batch's, or refine_assembly_batch's), placed [Z,P] bool, pose [Z,P,4,4] and rest [Z,P,n,3]
+    (datapipe.fracture's), root [Z] (integers) -> Evaluation of tensors: rot_deg, trans, msd [Z,P] float64, part_ok [Z,P] bool,
+    part_accuracy [Z] float64 (the share of the pieces other than the root with part_ok) and edge_precision [Z] float64: with
+    edges [Z,P-1,3], n_edges [Z] and mates [Z,P,P], the share of the first n_edges rows whose pair (i, j) is in mates, NaN for a
+    puzzle without an edge; None without all three.  A puzzle with root < 0 (assemble_batch gave it no root) is measured in
+    piece 0's frame with every piece counted: nothing is placed there, so its part accuracy is 0.  Nothing waits for the device."""
+    for name, t in (("G", G), ("placed", placed), ("pose", pose), ("rest", rest), ("root", root)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.PznError(f"evaluate_batch: {name} must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
+    if pose.dim() != 4 or tuple(pose.shape[2:]) != (4, 4):
+        raise _lib.PznError(f"evaluate_batch expects pose[Z,P,4,4]; got {tuple(pose.shape)}")
+    Z, P = pose.shape[0], pose.shape[1]
+    if tuple(G.shape) != (Z, P, 4, 4) or tuple(placed.shape) != (Z, P) or rest.dim() != 4 or tuple(rest.shape[:2]) != (Z, P) \
+            or rest.shape[3] != 3 or tuple(root.shape) != (Z,):
+        raise _lib.PznError(f"evaluate_batch expects G[{Z},{P},4,4], placed[{Z},{P}], rest[{Z},{P},n,3], root[{Z}]; got "
+                            f"{tuple(G.shape)}, {tuple(placed.shape)}, {tuple(rest.shape)}, {tuple(root.shape)}")
+    with torch.no_grad():
+        G, X, R = G.double(), pose.double(), rest.double()
+        rt = root.long()
+        frame = rt.clamp(min=0)
+        Rx, tx = X[..., :3, :3], X[..., :3, 3]
+        inv = torch.zeros_like(X)                                                  # the rigid inverse of every pose
+        inv[..., :3, :3] = Rx.transpose(-1, -2)
+        inv[..., :3, 3] = -_mm(Rx.transpose(-1, -2), tx.unsqueeze(-1)).squeeze(-1)
+        inv[..., 3, 3] = 1.0
+        Xr = X[torch.arange(Z, device=X.device), frame]                            # [Z,4,4]
+        Gt = _mm(Xr[:, None], inv)                                                 # the truth: pose[root] inv(pose[p])
+        dR, dt = G[..., :3, :3] - Gt[..., :3, :3], G[..., :3, 3] - Gt[..., :3, 3]
+        D = _mm(G[..., :3, :3], Gt[..., :3, :3].transpose(-1, -2))
+        skew = torch.stack((D[..., 2, 1] - D[..., 1, 2], D[..., 0, 2] - D[..., 2, 0], D[..., 1, 0] - D[..., 0, 1]), dim=-1)
+        trace = D[..., 0, 0] + D[..., 1, 1] + D[..., 2, 2]
+        rot_deg = torch.rad2deg(torch.atan2(skew.norm(dim=-1), trace - 1.0))
+        trans = dt.norm(dim=-1)
+        x = _mm(R, Rx.transpose(-1, -2)) + tx.unsqueeze(-2)                        # the moved pieces
+        d = _mm(x, dR.transpose(-1, -2)) + dt.unsqueeze(-2)
+        msd = (d * d).sum(dim=-1).mean(dim=-1)
+        part_ok = placed.bool() & (msd < tol)
+        others = torch.arange(P, device=X.device)[None, :] != rt[:, None]
+        part_accuracy = (part_ok & others).sum(dim=1).double() / others.sum(dim=1).double()
+        edge_precision = None
+        if edges is not None and n_edges is not None and mates is not None:
+            ei, ej = edges[..., 0].long().clamp(min=0), edges[..., 1].long().clamp(min=0)
+            live = torch.arange(edges.shape[1], device=X.device)[None, :] < n_edges[:, None]
+            hit = (mates != 0)[torch.arange(Z, device=X.device)[:, None], ei, ej] & live
+            edge_precision = hit.sum(dim=1).double() / live.sum(dim=1).double()      # 0 / 0: NaN where no edge was made
     return Evaluation(rot_deg, trans, msd, part_ok, part_accuracy, edge_precision)
 
 

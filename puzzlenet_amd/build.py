@@ -32,6 +32,7 @@ SOURCES = [
     ("mergefps.hip", ["-ffp-contract=off"] + NOSLP),
     ("icprefine.hip", ["-ffp-contract=off"] + NOSLP),
     ("jointrefine.hip", ["-ffp-contract=off"] + NOSLP),
+    ("assemblewalk.hip", ["-ffp-contract=off"] + NOSLP),
     ("knn.hip", ["-ffp-contract=off"]),
     ("group.hip", ["-ffp-contract=off"] + NOSLP),
     ("emd.hip", NOSLP),

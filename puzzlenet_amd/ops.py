@@ -356,6 +356,52 @@ def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None):
     return G, score, score0, joint_score, used, accepted
 
 
+def assemble_walk_supported(K):
+    return bool(_lib.load().pzn_assemble_walk_supported(int(K)))
+
+
+def assemble_walk(score, T, count=None, max_score=None, joint_score=None):
+    """The greedy walk over Z pair tables and every walk's joint list in one launch (pzn_assemble_walk_f32; include/pzn.h states
+    the rule, assembly.walk_rule is its numpy statement): score [Z,K,K] float32, T [Z,K,K,4,4] float32 (T[z,i,j] maps piece j into
+    piece i's frame), count [Z] int32 (the pieces of every puzzle; None: K; a count outside [2, K] gives root -1 and nothing
+    else), max_score (None: the walk stops only at a key that is not finite), joint_score (None: every puzzle's largest edge
+    score) -> (root [Z] int32, edges [Z,K-1,3] int32 rows (i, j, new), edge_score [Z,K-1] float32, n_edges [Z] int32,
+    G [Z,K,4,4] float64, placed [Z,K] uint8, joints [Z,K(K-1),2] int32, n_joints [Z] int32); unused edge rows are -1 with a score
+    of +inf, unused joint rows (-1, -1).  2 <= K <= 64 (PznUnsupported beyond).  Z = 0 launches nothing.  No autograd, nothing
+    waits for the device."""
+    for name, t, dt in (("score", score, torch.float32), ("T", T, torch.float32), ("count", count, torch.int32)):
+        if isinstance(t, torch.Tensor) and t.dtype != dt:      # (no silent conversion)
+            raise _lib.PznError(f"assemble_walk: {name} must be {dt}; got {t.dtype}")
+    score, T = _f32(score, "score"), _f32(T, "T")
+    if score.dim() != 3 or score.shape[1] != score.shape[2]:
+        raise _lib.PznError(f"assemble_walk: expected score[Z,K,K]; got {tuple(score.shape)}")
+    Z, K = score.shape[0], score.shape[1]
+    if tuple(T.shape) != (Z, K, K, 4, 4):
+        raise _lib.PznError(f"assemble_walk: expected T[{Z},{K},{K},4,4]; got {tuple(T.shape)}")
+    if count is not None:
+        count = _req(count, torch.int32, "count")
+        if tuple(count.shape) != (Z,):
+            raise _lib.PznError(f"assemble_walk: expected count[{Z}]; got {tuple(count.shape)}")
+    max_score = float("inf") if max_score is None else float(max_score)
+    joint_score = float("nan") if joint_score is None else float(joint_score)
+    if max_score != max_score:
+        raise _lib.PznError("assemble_walk: max_score is NaN (None: no limit)")
+    if not assemble_walk_supported(K):
+        raise _lib.PznUnsupported(f"assemble_walk: K = {K} pieces (2 <= K <= 64)")
+    dev = score.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    root, n_edges, n_joints = (torch.empty((Z,), **i32) for _ in range(3))
+    edges = torch.empty((Z, K - 1, 3), **i32)
+    edge_score = torch.empty((Z, K - 1), dtype=torch.float32, device=dev)
+    G = torch.empty((Z, K, 4, 4), dtype=torch.float64, device=dev)
+    placed = torch.empty((Z, K), dtype=torch.uint8, device=dev)
+    joints = torch.empty((Z, K * (K - 1), 2), **i32)
+    with _on(dev):
+        _call("pzn_assemble_walk_f32", _p(score), _p(T), _p(count), max_score, joint_score, Z, K, _p(root), _p(edges), _p(edge_score),
+              _p(n_edges), _p(G), _p(placed), _p(joints), _p(n_joints), _stream())
+    return root, edges, edge_score, n_edges, G, placed, joints, n_joints
+
+
 def knn(xyz, new_xyz, K):
     xyz, new_xyz = _f32(xyz, "xyz"), _f32(new_xyz, "new_xyz")
     B, N, _ = xyz.shape
