@@ -827,6 +827,33 @@ int pzn_fracture_pair_f32(const float* raw, const double* normals, const double*
                           const double* u, double neighbours, int B, int M, int P, int K, int n_min, int cap, float* pieces,
                           int64_t* counts, int64_t* start, int32_t* kind, int32_t* pair, uint8_t* label, double* planes,
                           int32_t* target, int32_t* cand, uint8_t* ok, pzn_stream_t stream);
+/* pzn_fracture_f32 with curved break surfaces, one launch; datapipe.fracture_curved_rule is the statement of this entry point.
+ * Candidate k of step s is a second-order patch through the anchor a (chosen as in pzn_fracture_f32): a paraboloid in the frame
+ * frames[b,s-1,k] (float64 [B,P-1,K,3,3], rows e1, e2, n) with the half curvatures half_curv[b,s-1,k] = (c1, c2) = (kappa1 / 2,
+ * kappa2 / 2) (float64 [B,P-1,K,2]); both are taken as given, neither normalised nor checked.  A point x is on the up side iff
+ * f >= 0, in float64 with every operation rounded on its own (no fma): d = x - a (the float32 coordinates widened, three
+ * subtractions); s1 = (d0 e1[0] + d1 e1[1]) + d2 e1[2], s2 and h likewise with e2 and n; f = (h + (c1 s1) s1) + (c2 s2) s2.
+ * The anchor has d = 0, so it is at exactly 0, on the up side; (0, 0) is the plane with normal n.  Everything else - the target,
+ * the anchor's rank, the first valid candidate else the first most balanced one, the labels, and every output - is as in
+ * pzn_fracture_f32, except: planes float64 [B,P-1,4] is the TANGENT plane at the anchor, (n, -((ax n0 + ay n1) + az n2)), and
+ * anchor int32 [B,P-1] is the cloud row of the anchor taken at every step.
+ * Limits: those of pzn_fracture_f32 (pzn_fracture_curved_supported: 1 / 0), PZN_EUNSUPPORTED otherwise, before any launch. */
+int pzn_fracture_curved_supported(int M, int P, int K);
+int pzn_fracture_curved_f32(const float* raw, const double* frames, const double* half_curv, const double* u_anchor,
+                            const double* u_start, int B, int M, int P, int K, int n_min, int cap, float* pieces,
+                            int64_t* counts, int64_t* start, uint8_t* label, int32_t* order, double* planes, int32_t* target,
+                            int32_t* cand, int32_t* anchor, uint8_t* ok, pzn_stream_t stream);
+/* pzn_fracture_pair_f32 with the curved break surfaces of pzn_fracture_curved_f32 (frames, half_curv in place of normals), one
+ * launch; datapipe.fracture_pair_curved_rule is the statement of this entry point.  The pair, the pieces and every output are as
+ * in pzn_fracture_pair_f32, except: planes holds the tangent planes, and anchor int32 [B,P-1] the cloud row of the anchor taken
+ * at every step (rows from P_b - 1 on, and every row of a sample whose n_pieces is out of range, are zero, like target and cand).
+ * Limits: those of pzn_fracture_f32 (pzn_fracture_pair_curved_supported: 1 / 0), PZN_EUNSUPPORTED otherwise, before any launch. */
+int pzn_fracture_pair_curved_supported(int M, int P, int K);
+int pzn_fracture_pair_curved_f32(const float* raw, const double* frames, const double* half_curv, const double* u_anchor,
+                                 const int32_t* n_pieces, const double* u, double neighbours, int B, int M, int P, int K,
+                                 int n_min, int cap, float* pieces, int64_t* counts, int64_t* start, int32_t* kind,
+                                 int32_t* pair, uint8_t* label, double* planes, int32_t* target, int32_t* cand, int32_t* anchor,
+                                 uint8_t* ok, pzn_stream_t stream);
 /* dataset.py:1363-1366: 0/1 masks [R,N] with ones at the k picked rows idx int64 [R,k] of each cloud. */
 int pzn_pick_mask_f32(const int64_t* idx, int R, int k, int N, float* mask, pzn_stream_t stream);
 

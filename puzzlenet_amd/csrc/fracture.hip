@@ -23,6 +23,13 @@
 // __device__ function for both kernels, for a per-sample number of pieces, chooses a training pair on the device - the two
 // sides of the last cut, or a drawn pair of final pieces with those two as its fallback - and partitions the <= 4 chosen
 // labels only: no `order`, no other piece.
+//
+// fracture_curved_kernel / fracture_pair_curved_kernel (datapipe.fracture_curved_rule / fracture_pair_curved_rule) are the same
+// two bodies with a curved candidate in the plane's place: a paraboloid through the anchor (Quadric, pzn_cut.h) in a frame and
+// with two half curvatures that the host draws per candidate.  The steps and both bodies are templates over what cuts
+// (PlaneCuts, QuadricCuts).  Frame and curvatures are uniform reads per candidate, as the normal is; the anchor table's fourth
+// column, which the planes leave unused, carries the anchor's cloud row; the LDS layout and the launch geometry are those of
+// the plane kernels.
 #include "pzn_common.h"
 
 namespace {
@@ -35,9 +42,70 @@ constexpr int FR_KC = 16;            // anchors held in LDS at a time
 // the dynamic LDS region: every table at a multiple of 16 bytes, the labels last
 constexpr int FR_SLOTS = 0, FR_WBASE = FR_SLOTS + CUT_W * 4, FR_ANCHOR = FR_WBASE + CUT_W * 4, FR_LABELS = FR_ANCHOR + FR_KC * 4 * 4;
 
+// What cuts: the candidates' draws as the host lays them out, [B, P-1, K, ...].
+//   at(step, c)                the same tables from row `step` on, which is candidate c = K step (a sample's first step, or a
+//                              step of a sample)
+//   ROWS                       the anchor table's fourth column holds the anchor's cloud row
+//   through(k, anchor)         candidate k of the step as a surface through the anchor, a row of the LDS table
+//   keep(surface)              what is held of a candidate that may be the one taken (uniform)
+//   record(taken, k, g, pl)    thread 0 only, on the step's tables: the step's row of `planes` (and of `anchor`)
+//   zero_from(i, n)            the whole workgroup, on the sample's tables: rows i .. n-1 of what record writes beside `planes`
+struct PlaneCuts {
+  const double* normals;     // [B, P-1, K, 3]
+  static constexpr bool ROWS = false;
+  using Taken = Plane;
+  __device__ __forceinline__ PlaneCuts at(size_t, size_t c) const { return PlaneCuts{normals + c * 3}; }
+  // the plane through the anchor: the anchor itself evaluates to d + (-d) = 0
+  __device__ __forceinline__ Plane through(int k, const float* anchor) const {
+    const double n0 = normals[3 * k], n1 = normals[3 * k + 1], n2 = normals[3 * k + 2];
+    const double ax = (double)anchor[0], ay = (double)anchor[1], az = (double)anchor[2];
+    return Plane{n0, n1, n2, -__dadd_rn(__dadd_rn(__dmul_rn(ax, n0), __dmul_rn(ay, n1)), __dmul_rn(az, n2))};
+  }
+  static __device__ __forceinline__ const Plane& side(const Plane& q) { return q; }
+  static __device__ __forceinline__ Plane keep(const Plane& q) { return q; }
+  __device__ __forceinline__ void record(const Plane& taken, int, const float*, double* pl) const {
+    pl[0] = taken.n0, pl[1] = taken.n1, pl[2] = taken.n2, pl[3] = taken.off;
+  }
+  __device__ __forceinline__ void zero_from(int, int) const {}
+};
+
+struct QuadricCuts {
+  const double* frames;      // [B, P-1, K, 3, 3]: rows e1, e2, n
+  const double* half_curv;   // [B, P-1, K, 2]
+  int32_t* anchor;           // [B, P-1]: the cloud row of the anchor taken
+  static constexpr bool ROWS = true;
+  struct Through {
+    Quadric q;
+    int row;                 // the anchor's cloud row
+  };
+  using Taken = int;         // the anchor's row is all that is held: thread 0 makes the tangent plane from it once per step
+  __device__ __forceinline__ QuadricCuts at(size_t step, size_t c) const {
+    return QuadricCuts{frames + c * 9, half_curv + c * 2, anchor + step};
+  }
+  __device__ __forceinline__ Through through(int k, const float* anchor_row) const {
+    const double* f = frames + 9 * k;
+    return Through{Quadric{(double)anchor_row[0], (double)anchor_row[1], (double)anchor_row[2], {f[0], f[1], f[2]},
+                           {f[3], f[4], f[5]}, {f[6], f[7], f[8]}, half_curv[2 * k], half_curv[2 * k + 1]},
+                   __float_as_int(anchor_row[3])};
+  }
+  static __device__ __forceinline__ const Quadric& side(const Through& t) { return t.q; }
+  static __device__ __forceinline__ int keep(const Through& t) { return t.row; }
+  // the tangent plane at the anchor: (n, -((ax n0 + ay n1) + az n2))
+  __device__ __forceinline__ void record(int row, int k, const float* g, double* pl) const {
+    const double n0 = frames[9 * k + 6], n1 = frames[9 * k + 7], n2 = frames[9 * k + 8];
+    const double ax = (double)g[3 * row], ay = (double)g[3 * row + 1], az = (double)g[3 * row + 2];
+    pl[0] = n0, pl[1] = n1, pl[2] = n2, pl[3] = -__dadd_rn(__dadd_rn(__dmul_rn(ax, n0), __dmul_rn(ay, n1)), __dmul_rn(az, n2));
+    anchor[0] = row;
+  }
+  __device__ __forceinline__ void zero_from(int i, int n) const {
+    for (i += threadIdx.x; i < n; i += CUT_T) anchor[i] = 0;
+  }
+};
+
+template <class Cuts>
 struct FractureArgs {
   const float* raw;          // [B, M, 3]
-  const double* normals;     // [B, P-1, K, 3]
+  Cuts cuts;                 // [B, P-1, K, ...]
   const double* u_anchor;    // [B, P-1, K]
   const double* u_start;     // [B, P]
   int B, M, P, K, n_min, cap;
@@ -77,11 +145,12 @@ __device__ __forceinline__ FractureBlock fracture_block(unsigned char* smem, con
   return w;
 }
 
-// Steps s = 1 .. steps of the rule on sample blockIdx.x (both kernels; steps <= P - 1, uniform over the workgroup): the labels in
+// Steps s = 1 .. steps of the rule on sample blockIdx.x (every kernel; steps <= P - 1, uniform over the workgroup): the labels in
 // w.lab, the counts per label in cnt (the same in every thread), planes / target / cand rows 0 .. steps - 1 written by thread 0.
-// nrm0, ua0: the sample's normals [P-1,K,3] and anchor draws [P-1,K]; planes, target, cand: the sample's rows.  last_t: the
+// cuts0, ua0: the sample's candidates [P-1,K,...] and anchor draws [P-1,K]; planes, target, cand: the sample's rows.  last_t: the
 // target of the last step.  -> every step had a valid candidate
-__device__ __forceinline__ bool fracture_cuts(const FractureBlock& w, const double* nrm0, const double* ua0, int K, int n_min,
+template <class Cuts>
+__device__ __forceinline__ bool fracture_cuts(const FractureBlock& w, const Cuts& cuts0, const double* ua0, int K, int n_min,
                                               int steps, int (&cnt)[FR_MAX_P], double* planes, int32_t* target, int32_t* cand,
                                               int& last_t) {
   int* slots = w.slots;
@@ -103,11 +172,11 @@ __device__ __forceinline__ bool fracture_cuts(const FractureBlock& w, const doub
     const int c_t = __popcll(tbits);
     const int before = block_excl_scan(c_t, slots, wave_base);      // target members in front of this run
 
-    const double* nrm = nrm0 + (size_t)(s - 1) * K * 3;
+    const Cuts cuts = cuts0.at((size_t)(s - 1), (size_t)(s - 1) * K);
     const double* ua = ua0 + (size_t)(s - 1) * K;
     int chosen = -1, best_k = 0, best_bal = -1, best_up = 0;
     uint64_t sel = 0;        // the run's target members on the DOWN side of the candidate that is taken
-    Plane taken{0.0, 0.0, 0.0, 0.0};
+    typename Cuts::Taken taken{};
     for (int k0 = 0; k0 < K && chosen < 0; k0 += FR_KC) {
       // 2. the anchors of candidates k0 .. k0 + FR_KC - 1 (the table's readers of the chunk before are behind block_sum's barriers)
       const int kn = K - k0 < FR_KC ? K - k0 : FR_KC;
@@ -118,20 +187,19 @@ __device__ __forceinline__ bool fracture_cuts(const FractureBlock& w, const doub
           for (int i = 0; i < r; ++i) m &= m - 1;
           const int j = lo + __ffsll((unsigned long long)m) - 1;
           anchor[4 * kk] = g[3 * j], anchor[4 * kk + 1] = g[3 * j + 1], anchor[4 * kk + 2] = g[3 * j + 2];
+          if constexpr (Cuts::ROWS) anchor[4 * kk + 3] = __int_as_float(j);
         }
       }
       __syncthreads();
       for (int kk = 0; kk < kn; ++kk) {
         const int k = k0 + kk;
-        // 3. the plane through the anchor: the anchor itself evaluates to d + (-d) = 0
-        const double n0 = nrm[3 * k], n1 = nrm[3 * k + 1], n2 = nrm[3 * k + 2];
-        const double ax = (double)anchor[4 * kk], ay = (double)anchor[4 * kk + 1], az = (double)anchor[4 * kk + 2];
-        const Plane q{n0, n1, n2, -__dadd_rn(__dadd_rn(__dmul_rn(ax, n0), __dmul_rn(ay, n1)), __dmul_rn(az, n2))};
+        // 3. the surface through the anchor (the table is read here, in front of block_sum's barriers)
+        const auto q = cuts.through(k, anchor + 4 * kk);
         int c = 0;
         uint64_t down = 0;
         for (uint64_t m = tbits; m != 0; m &= m - 1) {
           const int i = __ffsll((unsigned long long)m) - 1, j = lo + i;
-          const bool up = is_up(g[3 * j], g[3 * j + 1], g[3 * j + 2], q);
+          const bool up = is_up(g[3 * j], g[3 * j + 1], g[3 * j + 2], Cuts::side(q));
           c += up ? 1 : 0;
           down |= (uint64_t)(up ? 0 : 1) << i;
         }
@@ -139,7 +207,7 @@ __device__ __forceinline__ bool fracture_cuts(const FractureBlock& w, const doub
         const int up = block_sum(c, slots);
         const int bal = up < n_t - up ? up : n_t - up;
         const bool valid = up >= n_min && n_t - up >= n_min;
-        if (bal > best_bal || valid) sel = down, taken = q, best_up = up;
+        if (bal > best_bal || valid) sel = down, taken = Cuts::keep(q), best_up = up;
         if (bal > best_bal) best_bal = bal, best_k = k;
         if (valid) {
           chosen = k;
@@ -157,8 +225,7 @@ __device__ __forceinline__ bool fracture_cuts(const FractureBlock& w, const doub
       if (p == s) cnt[p] = n_t - best_up;
     }
     if (tid == 0) {
-      double* pl = planes + (size_t)(s - 1) * 4;
-      pl[0] = taken.n0, pl[1] = taken.n1, pl[2] = taken.n2, pl[3] = taken.off;
+      cuts.record(taken, chosen, g, planes + (size_t)(s - 1) * 4);
       target[s - 1] = t;
       cand[s - 1] = chosen;
     }
@@ -167,8 +234,8 @@ __device__ __forceinline__ bool fracture_cuts(const FractureBlock& w, const doub
   return all_valid;
 }
 
-__global__ __launch_bounds__(CUT_T) void fracture_kernel(FractureArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+template <class Cuts>
+__device__ __forceinline__ void fracture_body(const FractureArgs<Cuts>& a, unsigned char* smem) {
   const int b = blockIdx.x, tid = threadIdx.x;
   const int M = a.M, P = a.P, K = a.K;
   const FractureBlock w = fracture_block(smem, a.raw, M);
@@ -183,7 +250,7 @@ __global__ __launch_bounds__(CUT_T) void fracture_kernel(FractureArgs a) {
 #pragma unroll
   for (int p = 0; p < FR_MAX_P; ++p) cnt[p] = p == 0 ? M : 0;
   int last_t = 0;
-  const bool all_valid = fracture_cuts(w, a.normals + (size_t)b * (P - 1) * K * 3, a.u_anchor + (size_t)b * (P - 1) * K, K, a.n_min,
+  const bool all_valid = fracture_cuts(w, a.cuts.at((size_t)b * (P - 1), (size_t)b * (P - 1) * K), a.u_anchor + (size_t)b * (P - 1) * K, K, a.n_min,
                                        P - 1, cnt, a.planes + (size_t)b * (P - 1) * 4, a.target + (size_t)b * (P - 1),
                                        a.cand + (size_t)b * (P - 1), last_t);
 
@@ -217,14 +284,25 @@ __global__ __launch_bounds__(CUT_T) void fracture_kernel(FractureArgs a) {
   if (tid == 0) a.ok[b] = (all_valid && fits) ? 1 : 0;
 }
 
+__global__ __launch_bounds__(CUT_T) void fracture_kernel(FractureArgs<PlaneCuts> a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  fracture_body(a, smem);
+}
+
+__global__ __launch_bounds__(CUT_T) void fracture_curved_kernel(FractureArgs<QuadricCuts> a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  fracture_body(a, smem);
+}
+
 // The training pair of a fractured sample (datapipe.fracture_pair_rule): the cuts of a P_b-piece fracture, the pair chosen on
 // the device, and only the chosen pieces written - what a loader beside the training step needs of a fracture.
 constexpr int FP_UNIFORMS = 7;       // u_kind, u_a, u_c, u_sU, u_sD, u_sFU, u_sFD
 enum PairKind { SIBLING = 0, NEIGHBOUR = 1 };
 
+template <class Cuts>
 struct FracturePairArgs {
   const float* raw;          // [B, M, 3]
-  const double* normals;     // [B, P-1, K, 3]
+  Cuts cuts;                 // [B, P-1, K, ...]
   const double* u_anchor;    // [B, P-1, K]
   const int32_t* n_pieces;   // [B]: P_b, 2 .. P
   const double* u;           // [B, 7]
@@ -242,8 +320,8 @@ struct FracturePairArgs {
   uint8_t* ok;               // [B]
 };
 
-__global__ __launch_bounds__(CUT_T) void fracture_pair_kernel(FracturePairArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+template <class Cuts>
+__device__ __forceinline__ void fracture_pair_body(const FracturePairArgs<Cuts>& a, unsigned char* smem) {
   const int b = blockIdx.x, tid = threadIdx.x;
   const int M = a.M, P = a.P, K = a.K;
   const FractureBlock w = fracture_block(smem, a.raw, M);
@@ -264,12 +342,14 @@ __global__ __launch_bounds__(CUT_T) void fracture_pair_kernel(FracturePairArgs a
   double* planes = a.planes + (size_t)b * (P - 1) * 4;
   int32_t* target = a.target + (size_t)b * (P - 1);
   int32_t* cand = a.cand + (size_t)b * (P - 1);
+  const Cuts cuts = a.cuts.at((size_t)b * (P - 1), (size_t)b * (P - 1) * K);
   int last_t = 0;
-  const bool all_valid = fracture_cuts(w, a.normals + (size_t)b * (P - 1) * K * 3, a.u_anchor + (size_t)b * (P - 1) * K, K, a.n_min,
-                                       Pb - 1, cnt, planes, target, cand, last_t);
+  const bool all_valid = fracture_cuts(w, cuts, a.u_anchor + (size_t)b * (P - 1) * K, K, a.n_min, Pb - 1, cnt, planes, target,
+                                       cand, last_t);
   // the steps that were not made: zero rows
   for (int i = (Pb - 1) * 4 + tid; i < (P - 1) * 4; i += CUT_T) planes[i] = 0.0;
   for (int i = Pb - 1 + tid; i < P - 1; i += CUT_T) target[i] = 0, cand[i] = 0;
+  cuts.zero_from(Pb - 1, P - 1);
   for (int j = lo; j < hi; ++j) a.label[(size_t)b * M + j] = lab[j];
 
   // the pair (uniform: every thread reads the same draws and holds the same last target)
@@ -323,7 +403,17 @@ __global__ __launch_bounds__(CUT_T) void fracture_pair_kernel(FracturePairArgs a
   }
 }
 
-// the dynamic LDS of either kernel: <= 64.4 KiB
+__global__ __launch_bounds__(CUT_T) void fracture_pair_kernel(FracturePairArgs<PlaneCuts> a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  fracture_pair_body(a, smem);
+}
+
+__global__ __launch_bounds__(CUT_T) void fracture_pair_curved_kernel(FracturePairArgs<QuadricCuts> a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  fracture_pair_body(a, smem);
+}
+
+// the dynamic LDS of every kernel here: <= 64.4 KiB
 int fracture_lds(const void* kernel, int M, size_t* lds) {
   *lds = (size_t)FR_LABELS + ((size_t)M + 15) / 16 * 16;
   if (*lds > 64 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds) != hipSuccess)
@@ -344,10 +434,29 @@ PZN_EXPORT int pzn_fracture_f32(const float* raw, const double* normals, const d
   PZN_CHECK_ARG(raw && normals && u_anchor && u_start && pieces && counts && start && label && order && planes && target && cand && ok);
   PZN_CHECK_ARG(B > 0 && cap > 0 && n_min >= 0);
   if (!pzn_fracture_supported(M, P, K)) return PZN_EUNSUPPORTED;
-  FractureArgs a{raw, normals, u_anchor, u_start, B, M, P, K, n_min, cap, pieces, counts, start, label, order, planes, target, cand, ok};
+  FractureArgs<PlaneCuts> a{raw, {normals}, u_anchor, u_start, B, M, P, K, n_min, cap, pieces, counts, start, label, order, planes,
+                            target, cand, ok};
   size_t lds;
   if (fracture_lds(reinterpret_cast<const void*>(fracture_kernel), M, &lds) != PZN_OK) return PZN_ELAUNCH;
   PZN_LAUNCH(fracture_kernel, dim3(B), dim3(CUT_T), lds, pzn_hip_stream(stream), a);
+  PZN_RETURN_LAUNCH_STATUS();
+}
+
+PZN_EXPORT int pzn_fracture_curved_supported(int M, int P, int K) { return pzn_fracture_supported(M, P, K); }
+
+PZN_EXPORT int pzn_fracture_curved_f32(const float* raw, const double* frames, const double* half_curv, const double* u_anchor,
+                                       const double* u_start, int B, int M, int P, int K, int n_min, int cap, float* pieces,
+                                       int64_t* counts, int64_t* start, uint8_t* label, int32_t* order, double* planes,
+                                       int32_t* target, int32_t* cand, int32_t* anchor, uint8_t* ok, pzn_stream_t stream) {
+  PZN_CHECK_ARG(raw && frames && half_curv && u_anchor && u_start && pieces && counts && start && label && order && planes &&
+                target && cand && anchor && ok);
+  PZN_CHECK_ARG(B > 0 && cap > 0 && n_min >= 0);
+  if (!pzn_fracture_curved_supported(M, P, K)) return PZN_EUNSUPPORTED;
+  FractureArgs<QuadricCuts> a{raw, {frames, half_curv, anchor}, u_anchor, u_start, B, M, P, K, n_min, cap, pieces, counts, start,
+                              label, order, planes, target, cand, ok};
+  size_t lds;
+  if (fracture_lds(reinterpret_cast<const void*>(fracture_curved_kernel), M, &lds) != PZN_OK) return PZN_ELAUNCH;
+  PZN_LAUNCH(fracture_curved_kernel, dim3(B), dim3(CUT_T), lds, pzn_hip_stream(stream), a);
   PZN_RETURN_LAUNCH_STATUS();
 }
 
@@ -361,10 +470,29 @@ PZN_EXPORT int pzn_fracture_pair_f32(const float* raw, const double* normals, co
                 target && cand && ok);
   PZN_CHECK_ARG(B > 0 && cap > 0 && n_min >= 0 && neighbours >= 0.0 && neighbours <= 1.0);
   if (!pzn_fracture_pair_supported(M, P, K)) return PZN_EUNSUPPORTED;
-  FracturePairArgs a{raw, normals, u_anchor, n_pieces, u, neighbours, B, M, P, K, n_min, cap, pieces, counts, start, kind, pair,
-                     label, planes, target, cand, ok};
+  FracturePairArgs<PlaneCuts> a{raw, {normals}, u_anchor, n_pieces, u, neighbours, B, M, P, K, n_min, cap, pieces, counts, start,
+                                kind, pair, label, planes, target, cand, ok};
   size_t lds;
   if (fracture_lds(reinterpret_cast<const void*>(fracture_pair_kernel), M, &lds) != PZN_OK) return PZN_ELAUNCH;
   PZN_LAUNCH(fracture_pair_kernel, dim3(B), dim3(CUT_T), lds, pzn_hip_stream(stream), a);
+  PZN_RETURN_LAUNCH_STATUS();
+}
+
+PZN_EXPORT int pzn_fracture_pair_curved_supported(int M, int P, int K) { return pzn_fracture_supported(M, P, K); }
+
+PZN_EXPORT int pzn_fracture_pair_curved_f32(const float* raw, const double* frames, const double* half_curv, const double* u_anchor,
+                                            const int32_t* n_pieces, const double* u, double neighbours, int B, int M, int P, int K,
+                                            int n_min, int cap, float* pieces, int64_t* counts, int64_t* start, int32_t* kind,
+                                            int32_t* pair, uint8_t* label, double* planes, int32_t* target, int32_t* cand,
+                                            int32_t* anchor, uint8_t* ok, pzn_stream_t stream) {
+  PZN_CHECK_ARG(raw && frames && half_curv && u_anchor && n_pieces && u && pieces && counts && start && kind && pair && label &&
+                planes && target && cand && anchor && ok);
+  PZN_CHECK_ARG(B > 0 && cap > 0 && n_min >= 0 && neighbours >= 0.0 && neighbours <= 1.0);
+  if (!pzn_fracture_pair_curved_supported(M, P, K)) return PZN_EUNSUPPORTED;
+  FracturePairArgs<QuadricCuts> a{raw, {frames, half_curv, anchor}, u_anchor, n_pieces, u, neighbours, B, M, P, K, n_min, cap,
+                                  pieces, counts, start, kind, pair, label, planes, target, cand, ok};
+  size_t lds;
+  if (fracture_lds(reinterpret_cast<const void*>(fracture_pair_curved_kernel), M, &lds) != PZN_OK) return PZN_ELAUNCH;
+  PZN_LAUNCH(fracture_pair_curved_kernel, dim3(B), dim3(CUT_T), lds, pzn_hip_stream(stream), a);
   PZN_RETURN_LAUNCH_STATUS();
 }

@@ -1,8 +1,8 @@
 // pzn_cut.h — what the loader's three cut kernels share (datapipe.hip: plane, solidcut.hip: sphere / cylinder / cone,
-// doublecut.hip: two planes) and fracture.hip (P pieces): the workgroup shape, the float64 plane side test, the workgroup sum,
-// the workgroup exclusive scan behind every stable partition, the FPS start index, the padding of a piece, and the whole
-// single-cut body - the first valid of K candidates, else the most balanced one, written as
-// a stable two-way partition.  Tests pin pieces, counts and start indices bit for bit, so each of these has this one
+// doublecut.hip: two planes) and fracture.hip (P pieces, along planes or paraboloids): the workgroup shape, the float64 side
+// tests of a plane and of a paraboloid, the workgroup sum, the workgroup exclusive scan behind every stable partition, the FPS
+// start index, the padding of a piece, and the whole single-cut body - the first valid of K candidates, else the most balanced
+// one, written as a stable two-way partition.  Tests pin pieces, counts and start indices bit for bit, so each of these has this one
 // definition.  Included inside the translation unit's anonymous namespace, after pzn_common.h; the translation units are
 // built with -ffp-contract=off (float64, every operation individually rounded, like numpy).
 #pragma once
@@ -18,6 +18,27 @@ struct Plane {
 __device__ __forceinline__ bool is_up(float x, float y, float z, const Plane& p) {
   const double d = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn((double)x, p.n0), __dmul_rn((double)y, p.n1)), __dmul_rn((double)z, p.n2)), p.off);
   return d >= 0.0;
+}
+
+// A second-order surface patch through the point a: the paraboloid h + c1 s1^2 + c2 s2^2 = 0 in the frame (e1, e2, n) at a,
+// (s1, s2, h) the coordinates of x - a in that frame and c1, c2 HALF the two curvatures - a bowl (c1 c2 > 0), a cylinder
+// (c2 = 0), a saddle (c1 c2 < 0) or the plane with normal n (0, 0).  The frame is taken as given.
+struct Quadric {
+  double a0, a1, a2;
+  double e1[3], e2[3], n[3];
+  double c1, c2;
+};
+
+// f(x) >= 0 with d = x - a (the float32 coordinates widened, three subtractions), s1 = (d0 e1[0] + d1 e1[1]) + d2 e1[2], s2 and
+// h likewise with e2 and n, f = (h + (c1 s1) s1) + (c2 s2) s2: float64, every operation individually rounded, as numpy
+// evaluates it.  d = 0 at a, so a itself evaluates to exactly 0 and is on the up side.
+__device__ __forceinline__ bool is_up(float x, float y, float z, const Quadric& q) {
+  const double d0 = __dsub_rn((double)x, q.a0), d1 = __dsub_rn((double)y, q.a1), d2 = __dsub_rn((double)z, q.a2);
+  const double s1 = __dadd_rn(__dadd_rn(__dmul_rn(d0, q.e1[0]), __dmul_rn(d1, q.e1[1])), __dmul_rn(d2, q.e1[2]));
+  const double s2 = __dadd_rn(__dadd_rn(__dmul_rn(d0, q.e2[0]), __dmul_rn(d1, q.e2[1])), __dmul_rn(d2, q.e2[2]));
+  const double h = __dadd_rn(__dadd_rn(__dmul_rn(d0, q.n[0]), __dmul_rn(d1, q.n[1])), __dmul_rn(d2, q.n[2]));
+  const double f = __dadd_rn(__dadd_rn(h, __dmul_rn(__dmul_rn(q.c1, s1), s1)), __dmul_rn(__dmul_rn(q.c2, s2), s2));
+  return f >= 0.0;
 }
 
 // sum of one int per thread over the workgroup, the same value returned to every thread (two barriers); slots: CUT_W ints of LDS

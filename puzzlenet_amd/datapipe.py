@@ -378,7 +378,13 @@ distance of the primary pair's boundaries), the fracture itself (label [B,M] uin
 can be recomputed."""
 
 
-def cut_pairs_fracture(raw, normals, u_anchor, pieces, u, twist, n=1024, k=128, neighbours=0.5, cap=None):
+CurvedFracturePair = collections.namedtuple("CurvedFracturePair", FracturePair._fields + ("anchor",))
+CurvedFracturePair.__doc__ = """FracturePair of a curved cut (cut_pairs_fracture(..., frames=, half_curv=)): planes holds the tangent planes at the
+anchors, and anchor [B,P-1] int32 the cloud row of the anchor taken at every step (zero for the cuts a sample did not make)."""
+
+
+def cut_pairs_fracture(raw, normals, u_anchor, pieces, u, twist, n=1024, k=128, neighbours=0.5, cap=None, frames=None,
+                       half_curv=None):
     """cut_pairs for pairs cut out of a fracture (the rule: fracture_pair_rule): every cloud cut into pieces[b] pieces, the pair
     chosen and only its pieces - and the fallback's - compacted in one launch (csrc/fracture.hip, ops.fracture_pair; the cuts
     leave >= n points on both sides, n_min = n); then, as cut_pairs_double does, the sampling of the primary and of the fallback
@@ -386,11 +392,18 @@ def cut_pairs_fracture(raw, normals, u_anchor, pieces, u, twist, n=1024, k=128, 
     counts = -1), the primary pair's boundary, step 8 (`cd` of the two boundaries against CD_ACCEPT) as a device-side select,
     and cut_pairs' tail on the final pair.  Nothing here reads a value back to the host.  raw [B,M,3]; normals [B,P-1,K,3],
     u_anchor [B,P-1,K], u [B,7] float64 draws; pieces: ops.fracture_pair's; twist [B,6].
-    -> ((D, moved U, igt, U, D boundary, U boundary, D mask, U mask), ok [B], FracturePair)"""
+    -> ((D, moved U, igt, U, D boundary, U boundary, D mask, U mask), ok [B], FracturePair)
+    frames [B,P-1,K,3,3] and half_curv [B,P-1,K,2] float64, with normals=None: the cuts are curved (ops.fracture_pair_curved; the
+    rule: fracture_pair_curved_rule) and the record is a CurvedFracturePair, which adds `anchor`."""
     cap = _feeder_cap("cut_pairs_fracture", raw, cap)
     B, M, _ = raw.shape
-    packed, counts, start, kind, pair, label, planes, target, cand, ok = ops.fracture_pair(raw, normals, u_anchor, pieces, u, n,
-                                                                                          neighbours, cap)
+    anchor = None
+    if _curved("cut_pairs_fracture", normals, frames, half_curv):
+        packed, counts, start, kind, pair, label, planes, target, cand, anchor, ok = ops.fracture_pair_curved(
+            raw, frames, half_curv, u_anchor, pieces, u, n, neighbours, cap)
+    else:
+        packed, counts, start, kind, pair, label, planes, target, cand, ok = ops.fracture_pair(raw, normals, u_anchor, pieces, u, n,
+                                                                                              neighbours, cap)
     # [2B,n,3] each: U rows, D rows (every cut left >= n points on its other side, so a piece holds <= M - n).  The primary and
     # the fallback rows are sampled in ONE launch: a sampling launch lasts its n dependent rounds however few workgroups run them
     # (measured: the fallback rows of half the samples alone cost what the primary rows cost), and the picks of a row do not
@@ -404,6 +417,8 @@ def cut_pairs_fracture(raw, normals, u_anchor, pieces, u, twist, n=1024, k=128, 
     both = torch.where(rejected.repeat(2).view(2 * B, 1, 1), fallback, primary)
     top, fbnd = _picks(both, k)
     record = FracturePair(kind, pair, rejected, cd, label, planes, target, cand, primary[:B], primary[B:], bnd[:B], bnd[B:])
+    if anchor is not None:
+        record = CurvedFracturePair(*record, anchor)
     return _finish(both, top, fbnd, twist), ok & (counts[:B] >= n) & (counts[B:2 * B] >= n), record
 
 
@@ -512,10 +527,13 @@ class PairFeeder:
     pieces=P or (lo, hi) (cut="plane", split_twice=False only; 2 <= lo <= hi <= 16): pairs cut out of a fracture - every sample
     is cut into lo + floor(u (hi - lo + 1)) pieces (u drawn per sample on the host) and one pair of final pieces is taken, the
     two sides of the last cut or, for a share `neighbours` of the samples, a drawn pair with those two as its fallback
-    (fracture_pair_rule, cut_pairs_fracture); batch.fracture says what was cut and batch.plane stays None."""
+    (fracture_pair_rule, cut_pairs_fracture); batch.fracture says what was cut and batch.plane stays None.
+    curvature=c (with pieces only; c >= 0, finite): c > 0 breaks along curved surfaces, paraboloids through the anchor with
+    principal curvatures drawn in [-c, c] (fracture_pair_curved_rule; 2.0 is the curvature of the reference's radius-0.5 sphere);
+    batch.fracture is then a CurvedFracturePair.  0.0 is the plane mode: its staging columns, its draws, its bits."""
 
     def __init__(self, raw, device, n=1024, k=128, mag=0.8, candidates=16, seed=0, cut="plane", split_twice=False, pieces=None,
-                 neighbours=0.5):
+                 neighbours=0.5, curvature=None):
         if cut != "plane" and cut not in ops.SOLID_KINDS:
             raise _lib.PznError(f"PairFeeder: cut={cut!r} (one of 'plane', 'sphere', 'cylinder', 'cone')")
         if split_twice and cut != "plane":
@@ -531,6 +549,12 @@ class PairFeeder:
             pieces = (lo, hi)
         if not 0.0 <= float(neighbours) <= 1.0:
             raise _lib.PznError(f"PairFeeder: neighbours={neighbours!r} (a share of the samples, in [0, 1])")
+        if curvature is not None:
+            if pieces is None:
+                raise _lib.PznUnsupported(f"PairFeeder: curvature={curvature!r} bends the cuts of a fracture (pieces=...)")
+            if not isinstance(curvature, (int, float, np.integer, np.floating)) or not 0.0 <= float(curvature) < np.inf:
+                raise _lib.PznError(f"PairFeeder: curvature={curvature!r} (the largest principal curvature, finite and >= 0)")
+        self.curvature = 0.0 if curvature is None else float(curvature)
         self.pieces, self.neighbours = pieces, float(neighbours)
         self.cut, self.split_twice = cut, bool(split_twice)
         raw = torch.as_tensor(raw, dtype=torch.float32)
@@ -547,7 +571,8 @@ class PairFeeder:
         B = self.raw.shape[0]
         self._mode = _DOUBLE_MODE if self.split_twice else (_PLANE_MODE if cut == "plane" else _SOLID_MODE)
         if self.pieces is not None:
-            self._mode = _fracture_pair_mode(*self.pieces)
+            self._mode = (_fracture_pair_curved_mode(*self.pieces, self.curvature) if self.curvature > 0.0 else
+                          _fracture_pair_mode(*self.pieces))
         # one pinned staging block per batch in flight (two: the upload of batch k + 1 may still be queued when k + 2 is drawn)
         self._width = self._mode.cols(self.K)[-1].stop
         self._stage = [torch.empty((B, self._width), dtype=torch.float64, pin_memory=True) for _ in range(3)]
@@ -793,26 +818,65 @@ def fracture_rule(raw, normals, u_anchor, u_start, P, n_min, cap=None):
        planes [P-1,4] float64, target [P-1] int32, cand [P-1] int32, ok: every step had a valid candidate and every count <= cap)"""
     raw = np.asarray(raw, dtype=np.float32)
     normals, u_anchor, u_start = (np.asarray(t, dtype=np.float64) for t in (normals, u_anchor, u_start))
-    M, P = raw.shape[0], int(P)
+    r = _fracture_pieces(raw, _plane_side(normals), u_anchor, u_start, int(P), n_min, cap)
+    del r["anchor"]
+    return r
+
+
+def _fracture_pieces(raw, side, u_anchor, u_start, P, n_min, cap):
+    """fracture_rule / fracture_curved_rule behind their argument conversions: the steps with `side` (see _fracture_steps), then
+    the pieces.  -> the rule's dict with anchor [P-1] int32, the cloud row of the anchor taken at every step"""
+    M = raw.shape[0]
     cap = M if cap is None else int(cap)
-    label, planes, target, cand, ok = _fracture_steps(raw, normals, u_anchor, P, P - 1, n_min)
+    label, planes, target, cand, anchor, ok = _fracture_steps(raw, side, u_anchor, P, P - 1, n_min)
     counts = np.bincount(label, minlength=P).astype(np.int64)
     order = np.argsort(label, kind="stable").astype(np.int32)
     pieces = [_pad_rows(raw[label == p], cap, raw[0]) for p in range(P)]
     start = np.array([_start_index(u_start[p], counts[p]) for p in range(P)], dtype=np.int64)
     return dict(label=label, counts=counts, pieces=pieces, order=order, start=start, planes=planes, target=target, cand=cand,
-                ok=bool(ok and counts.max() <= cap))
+                anchor=anchor, ok=bool(ok and counts.max() <= cap))
 
 
-def _fracture_steps(raw, normals, u_anchor, P, steps, n_min):
-    """Steps s = 1 .. steps (<= P - 1) of fracture_rule on raw [M,3] float32; normals [P-1,K,3], u_anchor [P-1,K] float64.
-    -> (label [M] uint8, planes [P-1,4], target [P-1], cand [P-1] with the rows of the steps not made zero, every step made had
-    a valid candidate)"""
-    M, K = raw.shape[0], normals.shape[1]
+def _plane_side(normals):
+    """The side function of fracture_rule: normals [P-1,K,3] float64 -> side(s, k, a, pts) with a [3] float64 the anchor and pts
+    [m,3] float32 the target's points -> (the plane [4] through a with normal normals[s,k], up [m] bool)"""
+    def side(s, k, a, pts):
+        n = normals[s, k]
+        plane = np.array([n[0], n[1], n[2], -((a[0] * n[0] + a[1] * n[1]) + a[2] * n[2])])
+        return plane, _side64(pts, plane)
+    return side
+
+
+def quadric_value(pts, a, frame, half_curv):
+    """f of fracture_curved_rule: pts [m,3] float32, a [3] float64 the anchor, frame [3,3] float64 (rows e1, e2, n), half_curv [2]
+    float64 (c1, c2) -> f [m] float64 = (h + (c1 s1) s1) + (c2 s2) s2 with d = pts - a (the float32 coordinates widened, three
+    subtractions), s1 = (d0 e1[0] + d1 e1[1]) + d2 e1[2], s2 and h likewise with e2 and n; every operation rounded on its own."""
+    p = np.asarray(pts, dtype=np.float32).astype(np.float64)
+    d0, d1, d2 = p[:, 0] - a[0], p[:, 1] - a[1], p[:, 2] - a[2]
+    s1, s2, h = ((d0 * e[0] + d1 * e[1]) + d2 * e[2] for e in frame)
+    return (h + (half_curv[0] * s1) * s1) + (half_curv[1] * s2) * s2
+
+
+def _quadric_side(frames, half_curv):
+    """The side function of fracture_curved_rule: frames [P-1,K,3,3], half_curv [P-1,K,2] float64 -> side(s, k, a, pts) as
+    _plane_side's -> (the TANGENT plane [4] at a, (n, -((ax n0 + ay n1) + az n2)), up [m] bool = quadric_value >= 0)"""
+    def side(s, k, a, pts):
+        n = frames[s, k, 2]
+        plane = np.array([n[0], n[1], n[2], -((a[0] * n[0] + a[1] * n[1]) + a[2] * n[2])])
+        return plane, quadric_value(pts, a, frames[s, k], half_curv[s, k]) >= 0
+    return side
+
+
+def _fracture_steps(raw, side, u_anchor, P, steps, n_min):
+    """Steps s = 1 .. steps (<= P - 1) of fracture_rule on raw [M,3] float32; u_anchor [P-1,K] float64; side(s - 1, k, anchor,
+    target points) -> (the plane recorded for candidate k, its up side): _plane_side or _quadric_side.
+    -> (label [M] uint8, planes [P-1,4], target [P-1], cand [P-1], anchor [P-1] (the cloud row of the anchor taken) with the rows
+    of the steps not made zero, every step made had a valid candidate)"""
+    M, K = raw.shape[0], u_anchor.shape[1]
     p64 = raw.astype(np.float64)
     label = np.zeros(M, dtype=np.uint8)
     planes = np.zeros((P - 1, 4), dtype=np.float64)
-    target, cand = np.zeros(P - 1, dtype=np.int32), np.zeros(P - 1, dtype=np.int32)
+    target, cand, anchor = (np.zeros(P - 1, dtype=np.int32) for _ in range(3))
     ok = True
     for s in range(1, steps + 1):
         count = np.bincount(label, minlength=P)
@@ -821,22 +885,37 @@ def _fracture_steps(raw, normals, u_anchor, P, steps, n_min):
         n_t = len(members)
         best = None
         for k in range(K):
-            n = normals[s - 1, k]
-            a = p64[members[_start_index(u_anchor[s - 1, k], n_t)]]
-            plane = np.array([n[0], n[1], n[2], -((a[0] * n[0] + a[1] * n[1]) + a[2] * n[2])])
-            up = _side64(raw[members], plane)
+            row = members[_start_index(u_anchor[s - 1, k], n_t)]
+            plane, up = side(s - 1, k, p64[row], raw[members])
             n_up = int(up.sum())
             valid = n_up >= n_min and n_t - n_up >= n_min
             if valid or best is None or min(n_up, n_t - n_up) > best[0]:
-                best = (min(n_up, n_t - n_up), k, plane, up)
+                best = (min(n_up, n_t - n_up), k, plane, up, row)
             if valid:
                 break
         else:
             ok = False
-        _, cand[s - 1], planes[s - 1], up = best
+        _, cand[s - 1], planes[s - 1], up, anchor[s - 1] = best
         target[s - 1] = t
         label[members[~up]] = s
-    return label, planes, target, cand, ok
+    return label, planes, target, cand, anchor, ok
+
+
+def fracture_curved_rule(raw, frames, half_curv, u_anchor, u_start, P, n_min, cap=None):
+    """fracture_rule along curved surfaces: the statement that pzn_fracture_curved_f32 (csrc/fracture.hip) implements and the tests
+    hold it to, bit for bit.  Candidate k of step s is a second-order patch through the anchor a, a paraboloid in a tangent frame:
+      frames     [P-1,K,3,3] float64: an orthonormal frame (rows e1, e2, n) per candidate, taken as given
+      half_curv  [P-1,K,2] float64: c1 = kappa1 / 2, c2 = kappa2 / 2 - a bowl (c1 c2 > 0), a cylinder (c2 = 0), a saddle
+                 (c1 c2 < 0), the plane with normal n (0, 0)
+    and a point is on the up side iff quadric_value >= 0 (float64, every operation rounded on its own): the anchor has d = 0, so it
+    evaluates to exactly 0 and is on the up side, and the surface always meets the target.  Steps 1, 2, 4 and 5 of fracture_rule -
+    the target, the anchor's rank from u_anchor, the first valid candidate else the first most balanced one, up keeps t and down
+    becomes s - and the other arguments are unchanged.
+    -> fracture_rule's dict, where planes [P-1,4] is the TANGENT plane at the anchor, (n, -((ax n0 + ay n1) + az n2)), and with
+       anchor [P-1] int32, the cloud row of the anchor taken at every step"""
+    raw = np.asarray(raw, dtype=np.float32)
+    frames, half_curv, u_anchor, u_start = (np.asarray(t, dtype=np.float64) for t in (frames, half_curv, u_anchor, u_start))
+    return _fracture_pieces(raw, _quadric_side(frames, half_curv), u_anchor, u_start, int(P), n_min, cap)
 
 
 # A training pair cut out of a fracture, as the FEEDER samples it (PairFeeder(pieces=...)).
@@ -880,11 +959,27 @@ def fracture_pair_rule(raw, normals, u_anchor, u, pieces, P, n_min, neighbours, 
        (-1 there), start [4], label [M] uint8, planes [P-1,4], target [P-1], cand [P-1], ok)"""
     raw = np.asarray(raw, dtype=np.float32)
     normals, u_anchor, u = (np.asarray(t, dtype=np.float64) for t in (normals, u_anchor, u))
+    r = _fracture_pair(raw, _plane_side(normals), u_anchor, u, pieces, P, n_min, neighbours, cap)
+    del r["anchor"]
+    return r
+
+
+def fracture_pair_curved_rule(raw, frames, half_curv, u_anchor, u, pieces, P, n_min, neighbours, cap=None):
+    """fracture_pair_rule with the cuts of fracture_curved_rule (frames [P-1,K,3,3], half_curv [P-1,K,2] float64 in place of
+    normals): the statement that pzn_fracture_pair_curved_f32 implements.  -> fracture_pair_rule's dict, where planes holds the
+    tangent planes, and with anchor [P-1] int32 (rows from P_b - 1 on are zero)"""
+    raw = np.asarray(raw, dtype=np.float32)
+    frames, half_curv, u_anchor, u = (np.asarray(t, dtype=np.float64) for t in (frames, half_curv, u_anchor, u))
+    return _fracture_pair(raw, _quadric_side(frames, half_curv), u_anchor, u, pieces, P, n_min, neighbours, cap)
+
+
+def _fracture_pair(raw, side, u_anchor, u, pieces, P, n_min, neighbours, cap):
+    """fracture_pair_rule / fracture_pair_curved_rule behind their argument conversions -> the rule's dict with anchor [P-1]"""
     M, P, Pb = raw.shape[0], int(P), int(pieces)
     if not 2 <= Pb <= P or not 0.0 <= neighbours <= 1.0 or u.shape != (7,):
         raise _lib.PznError(f"fracture_pair_rule: pieces = {Pb} of P = {P}, neighbours = {neighbours}, u {u.shape}")
     cap = M if cap is None else int(cap)
-    label, planes, target, cand, ok = _fracture_steps(raw, normals, u_anchor, P, Pb - 1, n_min)
+    label, planes, target, cand, anchor, ok = _fracture_steps(raw, side, u_anchor, P, Pb - 1, n_min)
     sibling = (int(target[Pb - 2]), Pb - 1)
     kind, pair = SIBLING, sibling + (-1, -1)
     if Pb >= 3 and u[0] < neighbours:
@@ -897,7 +992,7 @@ def fracture_pair_rule(raw, normals, u_anchor, u, pieces, P, n_min, neighbours, 
     counts = np.array([-1 if r is None else len(r) for r in rows], dtype=np.int64)
     start = np.array([0 if cnt < 0 else _start_index(u[3 + i], cnt) for i, cnt in enumerate(counts)], dtype=np.int64)
     return dict(kind=kind, pair=np.array(pair, dtype=np.int32), pieces=[None if r is None else _pad_rows(r, cap, raw[0]) for r in rows],
-                counts=counts, start=start, label=label, planes=planes, target=target, cand=cand,
+                counts=counts, start=start, label=label, planes=planes, target=target, cand=cand, anchor=anchor,
                 ok=bool(ok and counts.max() <= cap))
 
 
@@ -910,7 +1005,24 @@ touch, ok [B] bool, and the kernel's label [B,M] uint8, planes [B,P-1,4] float64
 int64."""
 
 
-def fracture(raw, normals, u_anchor, u_start, twist, n=1024, n_min=None, k=128, cap=None):
+CurvedFracture = collections.namedtuple("CurvedFracture", Fracture._fields + ("anchor", "frames", "half_curv"))
+CurvedFracture.__doc__ = """Fracture along curved surfaces (datapipe.fracture(..., frames=, half_curv=)): the fields of Fracture, where planes
+[B,P-1,4] holds the tangent plane at the anchor, then anchor [B,P-1] int32 (the cloud row of the anchor taken at every step) and the
+frames [B,P-1,K,3,3] and half_curv [B,P-1,K,2] float64 the cuts were made with: candidate cand[b,s] of them, through
+raw[b, anchor[b,s]], is the surface between target[b,s] and s + 1."""
+
+
+def _curved(who, normals, frames, half_curv):
+    """frames and half_curv of the fracture forms: both (-> True; the normals are not read) or neither (-> False)"""
+    if (frames is None) != (half_curv is None):
+        raise _lib.PznError(f"{who}: frames and half_curv come together (a curved cut), or neither (planes)")
+    if frames is not None and normals is not None:
+        raise _lib.PznError(f"{who}: normals with frames and half_curv (a curved cut's normal is the third row of its frame; pass "
+                            f"normals=None)")
+    return frames is not None
+
+
+def fracture(raw, normals, u_anchor, u_start, twist, n=1024, n_min=None, k=128, cap=None, frames=None, half_curv=None):
     """A batch of P-piece samples with ground truth: every cloud cut into P pieces in one launch (ops.fracture, csrc/fracture.hip;
     the rule: fracture_rule), every piece sampled to n points and moved, and which pieces touch.  raw [B,M,3] f32 on the GPU;
     normals [B,P-1,K,3], u_anchor [B,P-1,K], u_start [B,P] float64 draws (draw_fracture_batch); twist [B,P,6]; n_min: points both
@@ -923,14 +1035,22 @@ def fracture(raw, normals, u_anchor, u_start, twist, n=1024, n_min=None, k=128, 
               nearest to piece c (the diagonal: a piece against itself)
       cd      mean + mean of ops.chamfer(rest[b,a][top[b,a,c]], rest[b,c][top[b,c,a]]) - what cut_pairs_double calls cd
       mates   cd <= CD_ACCEPT (the reference's 0.015, dataset.py:1255), False on the diagonal
-      ok      the kernel's ok (a valid candidate at every step, every piece within cap) and every piece holds >= n points"""
+      ok      the kernel's ok (a valid candidate at every step, every piece within cap) and every piece holds >= n points
+    frames [B,P-1,K,3,3] and half_curv [B,P-1,K,2] float64 (draw_fracture_curved_batch), with normals=None: the cuts are curved
+    (ops.fracture_curved; the rule: fracture_curved_rule) and a CurvedFracture comes back - the same fields, then anchor, frames,
+    half_curv."""
     cap = _feeder_cap("fracture", raw, cap)
+    curved = _curved("fracture", normals, frames, half_curv)
     n, k = int(n), int(k)
     n_min = n if n_min is None else int(n_min)
     B, M, P = raw.shape[0], raw.shape[1], u_start.shape[-1]
     if not isinstance(twist, torch.Tensor) or not twist.is_cuda or tuple(twist.shape) != (B, P, 6):
         raise _lib.PznError(f"fracture: twist as [B, P, 6] = [{B}, {P}, 6] on the GPU; got {tuple(twist.shape)}")
-    packed, counts, start, label, order, planes, target, cand, ok = ops.fracture(raw, normals, u_anchor, u_start, n_min, cap)
+    if curved:
+        packed, counts, start, label, order, planes, target, cand, anchor, ok = ops.fracture_curved(raw, frames, half_curv, u_anchor,
+                                                                                                     u_start, n_min, cap)
+    else:
+        packed, counts, start, label, order, planes, target, cand, ok = ops.fracture(raw, normals, u_anchor, u_start, n_min, cap)
     idx = ops.farthest_point_sample(packed, n, start, background=True, counts=counts, max_count=0)      # [P B,n]
     rest = ops.index_points(packed, idx).view(P, B, n, 3).transpose(0, 1).contiguous()               # dataset.py:1147-1163
     cnt = counts.view(P, B)
@@ -947,8 +1067,9 @@ def fracture(raw, normals, u_anchor, u_start, twist, n=1024, n_min=None, k=128, 
     cd1, cd2 = ops.chamfer(bnd.reshape(B * P * P, k, 3), bnd.transpose(1, 2).reshape(B * P * P, k, 3))
     cd = (cd1.mean(1) + cd2.mean(1)).view(B, P, P)
     mates = (cd <= CD_ACCEPT) & ~torch.eye(P, dtype=torch.bool, device=raw.device)
-    return Fracture(moved, pose, rest, src, top.view(B, P, P, k), cd, mates, ok & (cnt >= n).all(0), label, planes, target, cand,
-                    cnt.t().contiguous())
+    f = Fracture(moved, pose, rest, src, top.view(B, P, P, k), cd, mates, ok & (cnt >= n).all(0), label, planes, target, cand,
+                 cnt.t().contiguous())
+    return CurvedFracture(*f, anchor, frames, half_curv) if curved else f
 
 
 def _fracture_cols(P, K):       # normals, anchor draws, start fractions, twists
@@ -971,6 +1092,98 @@ def _draw_fracture_cuts(rng, B, P, K, out, normals, u_anchor):
     v = rng.randn(B, (P - 1) * K, 3)
     out[:, normals] = (v / np.linalg.norm(v, axis=2, keepdims=True)).reshape(B, -1)
     out[:, u_anchor] = rng.rand(B, (P - 1) * K)
+
+
+def _fracture_curved_cols(P, K):        # frames, half curvatures, anchor draws, start fractions, twists
+    return _cols(9 * (P - 1) * K, 2 * (P - 1) * K, (P - 1) * K, P, 6 * P)
+
+
+def _draw_fracture_curved_cuts(rng, B, P, K, curvature, out, frames, half_curv, u_anchor):
+    """The cut draws of a curved fracture (both forms): those of _draw_fracture_cuts (normals, anchor uniforms), then per candidate
+    a tangent rng.randn(3), made orthogonal to the normal n (Gram-Schmidt) and normalised - the coordinate axis least aligned with
+    n in its place where less than 1e-12 of it is left - as e1, e2 = n x e1, and the curvatures rng.rand(2) mapped to
+    [-curvature, curvature], stored as halves."""
+    R = (P - 1) * K
+    cuts = np.empty((B, 4 * R), dtype=np.float64)
+    _draw_fracture_cuts(rng, B, P, K, cuts, slice(0, 3 * R), slice(3 * R, 4 * R))
+    n = cuts[:, :3 * R].reshape(B, R, 3)
+    out[:, u_anchor] = cuts[:, 3 * R:]
+    t = rng.randn(B, R, 3)
+    e1 = t - (t * n).sum(2, keepdims=True) * n
+    short = np.linalg.norm(e1, axis=2) < 1e-12
+    if short.any():
+        axis = np.eye(3)[np.argmin(np.abs(n[short]), axis=1)]
+        e1[short] = axis - (axis * n[short]).sum(1, keepdims=True) * n[short]
+    e1 /= np.linalg.norm(e1, axis=2, keepdims=True)
+    out[:, frames] = np.stack([e1, np.cross(n, e1), n], axis=2).reshape(B, 9 * R)
+    out[:, half_curv] = ((2.0 * rng.rand(B, R, 2) - 1.0) * curvature / 2.0).reshape(B, 2 * R)
+
+
+def draw_fracture_curved_batch(rng, gen, B, P, K, mag, curvature, out):
+    """draw_fracture_batch for curved cuts into out [B, width] float64 (columns: _fracture_curved_cols(P, K)): the cut draws of
+    _draw_fracture_curved_cuts with curvatures up to `curvature`, then the start uniforms and the twists as the plane form draws
+    them."""
+    frames, half_curv, u_anchor, u_start, tw = _fracture_curved_cols(P, K)
+    _draw_fracture_curved_cuts(rng, B, P, K, curvature, out, frames, half_curv, u_anchor)
+    out[:, u_start] = rng.rand(B, P)
+    twist = np.empty((B * P, 6), dtype=np.float64)
+    _draw_twist(gen, mag, twist)
+    out[:, tw] = twist.reshape(B, 6 * P)
+
+
+def fracture_curved_draws(rng, gen, B, P, K, mag, curvature):
+    """draw_fracture_curved_batch into a fresh row, split: -> (frames [B,P-1,K,3,3], half_curv [B,P-1,K,2], u_anchor [B,P-1,K],
+    u_start [B,P], twist [B,P,6]), float64 numpy arrays."""
+    cols = _fracture_curved_cols(P, K)
+    out = np.empty((B, cols[-1].stop), dtype=np.float64)
+    draw_fracture_curved_batch(rng, gen, B, P, K, mag, curvature, out)
+    frames, half_curv, u_anchor, u_start, tw = cols
+    return (out[:, frames].reshape(B, P - 1, K, 3, 3), out[:, half_curv].reshape(B, P - 1, K, 2),
+            out[:, u_anchor].reshape(B, P - 1, K), out[:, u_start].copy(), out[:, tw].reshape(B, P, 6))
+
+
+def fracture_arguments(rng, gen, B, P, K, mag, curvature):
+    """The host draws of a fracture batch as the keyword arguments of datapipe.fracture that follow `raw` (float64 numpy arrays):
+    fracture_draws' for curvature 0 (planes), fracture_curved_draws' with normals=None above it.  What the tools' --curvature
+    does."""
+    if not 0.0 <= curvature < np.inf:
+        raise _lib.PznError(f"fracture_arguments: curvature={curvature!r} (the largest principal curvature, finite and >= 0)")
+    if curvature == 0:
+        return dict(zip(("normals", "u_anchor", "u_start", "twist"), fracture_draws(rng, gen, B, P, K, mag)))
+    names = ("frames", "half_curv", "u_anchor", "u_start", "twist")
+    return dict(zip(names, fracture_curved_draws(rng, gen, B, P, K, mag, curvature)), normals=None)
+
+
+def _fracture_pair_curved_cols(P, K):   # frames, half curvatures, anchor draws, the number of pieces, uniforms, twist
+    return _cols(9 * (P - 1) * K, 2 * (P - 1) * K, (P - 1) * K, 1, ops.FRACTURE_PAIR_UNIFORMS, 6)
+
+
+def draw_fracture_pair_curved_batch(rng, gen, B, lo, hi, K, mag, curvature, out):
+    """draw_fracture_pair_batch for curved cuts into out [B, width] float64 (columns: _fracture_pair_curved_cols(hi, K)): the cut
+    draws of _draw_fracture_curved_cuts for P = hi, then the number of pieces, the seven uniforms and the twist as the plane form
+    draws them."""
+    frames, half_curv, u_anchor, pc, u, tw = _fracture_pair_curved_cols(hi, K)
+    _draw_fracture_curved_cuts(rng, B, hi, K, curvature, out, frames, half_curv, u_anchor)
+    out[:, pc] = np.minimum(hi, lo + np.floor(rng.rand(B, 1) * (hi - lo + 1)))
+    out[:, u] = rng.rand(B, ops.FRACTURE_PAIR_UNIFORMS)                         # u_kind, u_a, u_c, u_sU, u_sD, u_sFU, u_sFD
+    _draw_twist(gen, mag, out[:, tw])
+
+
+def _build_fracture_pair_curved(f, d):
+    B, K, P = d.shape[0], f.K, f.pieces[1]
+    frames, half_curv, u_anchor, pc, u, tw = _fracture_pair_curved_cols(P, K)
+    tensors, ok, record = cut_pairs_fracture(f.raw, None, d[:, u_anchor].reshape(B, P - 1, K), d[:, pc].reshape(B).to(torch.int32),
+                                             d[:, u], d[:, tw], n=f.n, k=f.k, neighbours=f.neighbours,
+                                             frames=d[:, frames].reshape(B, P - 1, K, 3, 3),
+                                             half_curv=d[:, half_curv].reshape(B, P - 1, K, 2))
+    return tensors, ok, dict(fracture=record)
+
+
+def _fracture_pair_curved_mode(lo, hi, curvature):
+    """The feeder mode of PairFeeder(pieces=(lo, hi), curvature=c) with c > 0, as _fracture_pair_mode binds the range."""
+    return _FeederMode(lambda K: _fracture_pair_curved_cols(hi, K),
+                       lambda rng, gen, B, K, mag, out: draw_fracture_pair_curved_batch(rng, gen, B, lo, hi, K, mag, curvature, out),
+                       _build_fracture_pair_curved)
 
 
 def _fracture_pair_cols(P, K):  # normals, anchor draws, the number of pieces, uniforms, twist

@@ -754,12 +754,85 @@ def fracture(raw, normals, u_anchor, u_start, n_min, cap):
     return pieces, counts, start, label, order, planes, target, cand, ok.to(torch.bool)
 
 
+def fracture_curved_supported(M, P, K):
+    return bool(_lib.load().pzn_fracture_curved_supported(int(M), int(P), int(K)))
+
+
+def _curved_cut_args(who, supported, raw, frames, half_curv, u_anchor, last, cap, n_min):
+    """The argument checks the two curved fracture forms share (those of fracture / fracture_pair): raw f32 [B,M,3]; frames
+    [B,P-1,K,3,3], half_curv [B,P-1,K,2], u_anchor [B,P-1,K] and `last` = (name, tensor, columns or None: P) float64 [B,columns],
+    all on the GPU.  -> (B, M, P, K)"""
+    for name, t, dt in (("raw", raw, torch.float32), ("frames", frames, torch.float64), ("half_curv", half_curv, torch.float64),
+                        ("u_anchor", u_anchor, torch.float64), (last[0], last[1], torch.float64)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.PznError(f"{who}: {name} must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
+        if t.dtype != dt:
+            raise _lib.PznError(f"{who}: {name} must be {dt}; got {t.dtype}")
+    if raw.dim() != 3 or raw.shape[2] != 3 or raw.shape[0] == 0 or raw.shape[1] == 0:
+        raise _lib.PznError(f"{who}: raw as [B, M, 3]; got {tuple(raw.shape)}")
+    B, M, _ = raw.shape
+    if frames.dim() != 5 or frames.shape[0] != B or tuple(frames.shape[3:]) != (3, 3):
+        raise _lib.PznError(f"{who}: frames as [B, P - 1, K, 3, 3]; got {tuple(frames.shape)}")
+    P, K = frames.shape[1] + 1, frames.shape[2]
+    if not supported(M, P, max(K, 1)):
+        raise _lib.PznUnsupported(f"{who}: M = {M} points into P = {P} pieces (2 <= P <= 16, M <= 65536)")
+    name, t, cols = last
+    cols = P if cols is None else cols
+    if K < 1 or tuple(half_curv.shape) != (B, P - 1, K, 2) or tuple(u_anchor.shape) != (B, P - 1, K) or tuple(t.shape) != (B, cols):
+        raise _lib.PznError(f"{who}: half_curv as [B, P - 1, K, 2], u_anchor as [B, P - 1, K] with P = {P}, K >= 1, and {name} as "
+                            f"[B, {cols}]; got {tuple(half_curv.shape)}, {tuple(u_anchor.shape)}, {tuple(t.shape)}")
+    if int(cap) < 1 or int(n_min) < 0:
+        raise _lib.PznError(f"{who}: cap = {cap}, n_min = {n_min}")
+    return B, M, P, K
+
+
+def fracture_curved(raw, frames, half_curv, u_anchor, u_start, n_min, cap):
+    """ops.fracture along curved surfaces, one launch (pzn_fracture_curved_f32; the rule: datapipe.fracture_curved_rule): candidate
+    k of a cut is the paraboloid through the anchor in the frame frames[b,s-1,k] (rows e1, e2, n; [B,P-1,K,3,3]) with the half
+    curvatures half_curv[b,s-1,k] ([B,P-1,K,2]), both float64 and taken as given (no silent conversion: PznError)
+    -> (pieces, counts, start, label, order, planes, target, cand as ops.fracture returns them, planes [B,P-1,4] the TANGENT
+        plane at the anchor; anchor [B,P-1] int32, the cloud row of the anchor taken; ok [B] bool)
+    2 <= P <= 16, K >= 1, M <= 65536 (PznUnsupported beyond).  Nothing waits for the device."""
+    B, M, P, K = _curved_cut_args("fracture_curved", fracture_curved_supported, raw, frames, half_curv, u_anchor,
+                                  ("u_start", u_start, None), cap, n_min)
+    cap, n_min = int(cap), int(n_min)
+    raw, frames, half_curv, u_anchor, u_start = (t.contiguous() for t in (raw, frames, half_curv, u_anchor, u_start))
+    dev = raw.device
+    pieces, counts, start, ok = _cut_outputs(raw, P, cap)
+    label = torch.empty((B, M), dtype=torch.uint8, device=dev)
+    order = torch.empty((B, M), dtype=torch.int32, device=dev)
+    planes = torch.empty((B, P - 1, 4), dtype=torch.float64, device=dev)
+    target = torch.empty((B, P - 1), dtype=torch.int32, device=dev)
+    cand = torch.empty((B, P - 1), dtype=torch.int32, device=dev)
+    anchor = torch.empty((B, P - 1), dtype=torch.int32, device=dev)
+    with _on(dev):
+        _call("pzn_fracture_curved_f32", _p(raw), _p(frames), _p(half_curv), _p(u_anchor), _p(u_start), B, M, P, K, n_min, cap,
+              _p(pieces), _p(counts), _p(start), _p(label), _p(order), _p(planes), _p(target), _p(cand), _p(anchor), _p(ok),
+              _stream())
+    return pieces, counts, start, label, order, planes, target, cand, anchor, ok.to(torch.bool)
+
+
 FRACTURE_PAIR_KINDS = ("sibling", "neighbour")      # the `kind` codes of pzn_fracture_pair_f32
 FRACTURE_PAIR_UNIFORMS = 7                          # u_kind, u_a, u_c, u_sU, u_sD, u_sFU, u_sFD
 
 
 def fracture_pair_supported(M, P, K):
     return bool(_lib.load().pzn_fracture_pair_supported(int(M), int(P), int(K)))
+
+
+def _pair_pieces(who, pieces, B, P, dev):
+    """The number of pieces of every sample as the pair launches take it: an int32 tensor [B] on the GPU is passed on unread,
+    anything else is checked on the host (2 <= P_b <= P) and uploaded."""
+    if isinstance(pieces, torch.Tensor) and pieces.is_cuda:
+        if pieces.dtype != torch.int32 or tuple(pieces.shape) != (B,):
+            raise _lib.PznError(f"{who}: pieces on the GPU as int32 [B]; got {pieces.dtype} {tuple(pieces.shape)}")
+        return pieces
+    host = torch.as_tensor(pieces).reshape(-1)
+    if host.numel() == 1:
+        host = host.expand(B)
+    if host.is_floating_point() or host.numel() != B or int(host.min()) < 2 or int(host.max()) > P:
+        raise _lib.PznError(f"{who}: pieces as an integer or B = {B} integers in 2 .. P = {P}; got {pieces!r}")
+    return host.to(torch.int32).to(dev)
 
 
 def fracture_pair(raw, normals, u_anchor, pieces, u, n_min, neighbours, cap):
@@ -792,16 +865,7 @@ def fracture_pair(raw, normals, u_anchor, pieces, u, n_min, neighbours, cap):
     if cap < 1 or n_min < 0 or not 0.0 <= neighbours <= 1.0:
         raise _lib.PznError(f"fracture_pair: cap = {cap}, n_min = {n_min}, neighbours = {neighbours}")
     dev = raw.device
-    if isinstance(pieces, torch.Tensor) and pieces.is_cuda:
-        if pieces.dtype != torch.int32 or tuple(pieces.shape) != (B,):
-            raise _lib.PznError(f"fracture_pair: pieces on the GPU as int32 [B]; got {pieces.dtype} {tuple(pieces.shape)}")
-    else:
-        host = torch.as_tensor(pieces).reshape(-1)
-        if host.numel() == 1:
-            host = host.expand(B)
-        if host.is_floating_point() or host.numel() != B or int(host.min()) < 2 or int(host.max()) > P:
-            raise _lib.PznError(f"fracture_pair: pieces as an integer or B = {B} integers in 2 .. P = {P}; got {pieces!r}")
-        pieces = host.to(torch.int32).to(dev)
+    pieces = _pair_pieces("fracture_pair", pieces, B, P, dev)
     raw, normals, u_anchor, pieces, u = (t.contiguous() for t in (raw, normals, u_anchor, pieces, u))
     out, counts, start, ok = _cut_outputs(raw, 4, cap)
     kind = torch.empty((B,), dtype=torch.int32, device=dev)
@@ -814,6 +878,40 @@ def fracture_pair(raw, normals, u_anchor, pieces, u, n_min, neighbours, cap):
         _call("pzn_fracture_pair_f32", _p(raw), _p(normals), _p(u_anchor), _p(pieces), _p(u), neighbours, B, M, P, K, n_min, cap,
               _p(out), _p(counts), _p(start), _p(kind), _p(pair), _p(label), _p(planes), _p(target), _p(cand), _p(ok), _stream())
     return out, counts, start, kind, pair, label, planes, target, cand, ok.to(torch.bool)
+
+
+def fracture_pair_curved_supported(M, P, K):
+    return bool(_lib.load().pzn_fracture_pair_curved_supported(int(M), int(P), int(K)))
+
+
+def fracture_pair_curved(raw, frames, half_curv, u_anchor, pieces, u, n_min, neighbours, cap):
+    """ops.fracture_pair along the curved surfaces of ops.fracture_curved, one launch (pzn_fracture_pair_curved_f32; the rule:
+    datapipe.fracture_pair_curved_rule): frames [B,P-1,K,3,3] and half_curv [B,P-1,K,2] float64 in place of normals; pieces, u,
+    neighbours as ops.fracture_pair takes them
+    -> (pieces, counts, start, kind, pair, label, planes, target, cand as ops.fracture_pair returns them, planes the TANGENT
+        planes; anchor [B,P-1] int32, zero where a step was not made; ok [B] bool)
+    2 <= P <= 16, K >= 1, M <= 65536 (PznUnsupported beyond)."""
+    B, M, P, K = _curved_cut_args("fracture_pair_curved", fracture_pair_curved_supported, raw, frames, half_curv, u_anchor,
+                                  ("u", u, FRACTURE_PAIR_UNIFORMS), cap, n_min)
+    cap, n_min, neighbours = int(cap), int(n_min), float(neighbours)
+    if not 0.0 <= neighbours <= 1.0:
+        raise _lib.PznError(f"fracture_pair_curved: neighbours = {neighbours}")
+    dev = raw.device
+    pieces = _pair_pieces("fracture_pair_curved", pieces, B, P, dev)
+    raw, frames, half_curv, u_anchor, pieces, u = (t.contiguous() for t in (raw, frames, half_curv, u_anchor, pieces, u))
+    out, counts, start, ok = _cut_outputs(raw, 4, cap)
+    kind = torch.empty((B,), dtype=torch.int32, device=dev)
+    pair = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    label = torch.empty((B, M), dtype=torch.uint8, device=dev)
+    planes = torch.empty((B, P - 1, 4), dtype=torch.float64, device=dev)
+    target = torch.empty((B, P - 1), dtype=torch.int32, device=dev)
+    cand = torch.empty((B, P - 1), dtype=torch.int32, device=dev)
+    anchor = torch.empty((B, P - 1), dtype=torch.int32, device=dev)
+    with _on(dev):
+        _call("pzn_fracture_pair_curved_f32", _p(raw), _p(frames), _p(half_curv), _p(u_anchor), _p(pieces), _p(u), neighbours, B, M,
+              P, K, n_min, cap, _p(out), _p(counts), _p(start), _p(kind), _p(pair), _p(label), _p(planes), _p(target), _p(cand),
+              _p(anchor), _p(ok), _stream())
+    return out, counts, start, kind, pair, label, planes, target, cand, anchor, ok.to(torch.bool)
 
 
 def pick_mask(idx, N):

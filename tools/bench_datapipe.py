@@ -3,6 +3,7 @@ to N, labelled and moved — next to the training step's consumption rate, and t
 piece on one host core (the dominant cost of the reference's per-sample CPU pipeline).
 
     python tools/bench_datapipe.py [--cut {plane,sphere,cylinder,cone}] [--random_slice] [--reps 30] [--fracture]
+                                   [--pieces P] [--curvature 2.0]
 
 Then the loader's batch as PairFeeder builds it, B = 64, M = 10000, N = 2048, 16 candidates: datapipe.cut_pairs (plane) and, with
 --cut a solid, datapipe.cut_pairs_solid of that kind next to the tensor form datapipe.make_pairs_solid on the same clouds with the
@@ -15,7 +16,11 @@ events, and the whole datapipe.fracture call (n = 256, k = 64) on a host clock a
 and the ratio of the two launches are written to profiles/fracture_batch.txt.
 --pieces P: only the fracture feeder's batch (datapipe.cut_pairs_fracture, PairFeeder(pieces=P)) beside the plane batch on the same
 clouds, B = 64, M = 10000, N = 2048, 16 candidates, alternating inside every repetition; and its cut launch and its two sampling
-launches beside the plane batch's, each alone between two device events (profiles/fracture_feeder_batch.txt holds a run)."""
+launches beside the plane batch's, each alone between two device events (profiles/fracture_feeder_batch.txt holds a run).
+--curvature C (with --fracture or --pieces; default 2.0, 0: planes only): the curved forms beside the plane forms on the same
+clouds, normals and anchors - the ops.fracture_curved launch and the whole curved datapipe.fracture call with --fracture, the
+ops.fracture_pair_curved launch and the curved cut_pairs_fracture batch with --pieces - and the ratios curved / plane
+(profiles/fracture_curved_batch.txt holds a run)."""
 import argparse, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -26,16 +31,25 @@ ap.add_argument("--random_slice", action="store_true")
 ap.add_argument("--reps", type=int, default=30)
 ap.add_argument("--fracture", action="store_true")
 ap.add_argument("--pieces", type=int, default=0)
+ap.add_argument("--curvature", type=float, default=2.0)
 a = ap.parse_args()
 dev = torch.device('cuda:0')
 g = torch.Generator().manual_seed(0)
 
 
-def bench_fracture(reps):
+def _again(rng):
+    """A generator in rng's state: the curved draws begin with the plane draws' normals and anchors."""
+    twin = np.random.RandomState()
+    twin.set_state(rng.get_state())
+    return twin
+
+
+def bench_fracture(reps, curvature):
     from puzzlenet_amd import ops
     B, M, P, K, n, k = 64, 10000, 8, 16, 256, 64
     rng = np.random.RandomState(0)
     raw = torch.from_numpy((rng.rand(B, M, 3) - 0.5).astype(np.float32)).to(dev)
+    twin = _again(rng)
     normals, u_anchor, u_start, twist = (torch.from_numpy(np.ascontiguousarray(t)).to(dev)
                                          for t in datapipe.fracture_draws(rng, torch.Generator().manual_seed(0), B, P, K, 0.8))
     pn, pz, pu = torch.from_numpy(rng.rand(B, K, 3)).to(dev), torch.from_numpy(rng.rand(B, K) / 3 - 0.4).to(dev), torch.from_numpy(rng.rand(B, 2)).to(dev)
@@ -43,8 +57,18 @@ def bench_fracture(reps):
     print('fracture: valid %d/%d, smallest piece %d, mates per sample %.1f' % (int(f.ok.sum()), B, int(f.counts.min()), float(f.mates.sum()) / 2 / B), flush=True)
     launches = {"ops.fracture (P = 8)": lambda: ops.fracture(raw, normals, u_anchor, u_start, n, M),
                 "ops.cut_compact (the single cut)": lambda: ops.cut_compact(raw, pn, pz, pu, n, M)}
+    if curvature > 0:
+        frames, half_curv, c_anchor, c_start, c_twist = (
+            torch.from_numpy(np.ascontiguousarray(t)).to(dev)
+            for t in datapipe.fracture_curved_draws(twin, torch.Generator().manual_seed(0), B, P, K, 0.8, curvature))
+        assert torch.equal(frames[:, :, :, 2], normals) and torch.equal(c_anchor, u_anchor)
+        fc = datapipe.fracture(raw, None, c_anchor, c_start, c_twist, n=n, k=k, frames=frames, half_curv=half_curv)
+        print('curved fracture, curvature %g: valid %d/%d, smallest piece %d, mates per sample %.1f, mean candidate taken %.2f (planes: %.2f)' % (
+            curvature, int(fc.ok.sum()), B, int(fc.counts.min()), float(fc.mates.sum()) / 2 / B, float(fc.cand.float().mean()),
+            float(f.cand.float().mean())), flush=True)
+        launches["ops.fracture_curved (P = 8)"] = lambda: ops.fracture_curved(raw, frames, half_curv, c_anchor, c_start, n, M)
     lt = {name: [] for name in launches}
-    whole = []
+    whole, whole_curved = [], []
     for rep in range(reps + 3):                          # (three warm-up rounds of everything)
         for name, fn in launches.items():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -58,9 +82,15 @@ def bench_fracture(reps):
         torch.cuda.synchronize()
         if rep >= 3:
             whole.append((time.perf_counter() - t0) * 1e3)
-    fr_us, cut_us = (float(np.median(lt[name])) for name in launches)
+        if curvature > 0:
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            datapipe.fracture(raw, None, c_anchor, c_start, c_twist, n=n, k=k, frames=frames, half_curv=half_curv)
+            torch.cuda.synchronize()
+            if rep >= 3:
+                whole_curved.append((time.perf_counter() - t0) * 1e3)
+    fr_us, cut_us = (float(np.median(lt[name])) for name in list(launches)[:2])
     lines = ['tools/bench_datapipe.py --fracture --reps %d: B = %d, M = %d, P = %d, K = %d, n_min = n = %d, k = %d (medians of %d)' % (reps, B, M, P, K, n, k, reps)]
-    for name in launches:
+    for name in list(launches)[:2]:
         t = np.sort(np.array(lt[name]))
         lines.append('launch: %-34s %.0f us between events (min %.0f, max %.0f)' % (name, np.median(t), t[0], t[-1]))
     lines.append('ratio fracture / cut_compact: %.2f (%d cuts and a %d-way partition against 1 cut and a 2-way one)' % (fr_us / cut_us, P - 1, P))
@@ -70,13 +100,20 @@ def bench_fracture(reps):
     out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'fracture_batch.txt')
     with open(out, 'w') as fh:
         fh.write('\n'.join(lines) + '\n')
+    if curvature > 0:
+        t, w = np.sort(np.array(lt["ops.fracture_curved (P = 8)"])), np.sort(np.array(whole_curved))
+        print('launch: %-34s %.0f us between events (min %.0f, max %.0f), curvature %g' % ("ops.fracture_curved (P = 8)", np.median(t), t[0], t[-1], curvature))
+        print('ratio fracture_curved / fracture: %.2f (three dot products and four more float64 operations per side test against one dot product)' % (np.median(t) / fr_us))
+        print('datapipe.fracture with surfaces, the whole call: %.2f ms per batch on the host clock (min %.2f, max %.2f), valid %d/%d' % (
+            np.median(w), w[0], w[-1], int(fc.ok.sum()), B), flush=True)
 
 
-def bench_pieces(P, reps):
+def bench_pieces(P, reps, curvature):
     from puzzlenet_amd import ops
     B, M, N, K = 64, 10000, 2048, 16
     rng = np.random.RandomState(0)
     raw = torch.from_numpy((rng.rand(B, M, 3) - 0.5).astype(np.float32)).to(dev)
+    twin = _again(rng)
     cols = datapipe._fracture_pair_cols(P, K)
     row = np.empty((B, cols[-1].stop))
     datapipe.draw_fracture_pair_batch(rng, torch.Generator().manual_seed(0), B, P, P, K, 0.8, row)
@@ -101,6 +138,20 @@ def bench_pieces(P, reps):
                 "FPS of the fallback pair (%d of %d samples)" % (n_nb, B):
                     lambda: ops.farthest_point_sample(p4[2 * B:], N, s4[2 * B:], background=True, counts=c4[2 * B:], max_count=mc),
                 "FPS of all four rows, one launch (what runs)": lambda: ops.farthest_point_sample(p4, N, s4, background=True, counts=c4, max_count=mc)}
+    if curvature > 0:
+        ccols = datapipe._fracture_pair_curved_cols(P, K)
+        crow = np.empty((B, ccols[-1].stop))
+        datapipe.draw_fracture_pair_curved_batch(twin, torch.Generator().manual_seed(0), B, P, P, K, 0.8, curvature, crow)
+        c = torch.from_numpy(crow).to(dev)
+        frames, half_curv = c[:, ccols[0]].reshape(B, P - 1, K, 3, 3).contiguous(), c[:, ccols[1]].reshape(B, P - 1, K, 2).contiguous()
+        c_anchor, c_u7, c_tw = c[:, ccols[2]].reshape(B, P - 1, K).contiguous(), c[:, ccols[4]].contiguous(), c[:, ccols[5]].contiguous()
+        assert torch.equal(frames[:, :, :, 2], normals) and torch.equal(c_anchor, u_anchor)
+        curved = lambda: datapipe.cut_pairs_fracture(raw, None, c_anchor, pieces, c_u7, c_tw, n=N, frames=frames, half_curv=half_curv)
+        _, cok, crec = curved()
+        print('curved fracture pairs, P = %d, curvature %g: valid %d/%d, NEIGHBOUR %d, replaced by the sibling pair %d' % (
+            P, curvature, int(cok.sum()), B, int((crec.kind == datapipe.NEIGHBOUR).sum()), int(crec.rejected.sum())), flush=True)
+        forms["curved: cut_pairs_fracture (P = %d)" % P] = curved
+        launches["fracture_pair_curved (P = %d)" % P] = lambda: ops.fracture_pair_curved(raw, frames, half_curv, c_anchor, pieces, c_u7, N, 0.5, M)
     times, ltimes = {name: [] for name in forms}, {name: [] for name in launches}
     for rep in range(reps + 3):                          # (three warm-up rounds of everything; the forms alternate)
         for name, fn in forms.items():
@@ -123,13 +174,18 @@ def bench_pieces(P, reps):
     for name, t in ltimes.items():
         t = np.sort(np.array(t))
         print('launch: %-45s %.0f us between events (min %.0f, max %.0f)' % (name, np.median(t), t[0], t[-1]), flush=True)
+    if curvature > 0:
+        med = lambda d, name: float(np.median(d[name]))
+        print('ratio fracture_pair_curved / fracture_pair: %.2f; ratio of the batches, curved / plane fracture: %.2f' % (
+            med(ltimes, "fracture_pair_curved (P = %d)" % P) / med(ltimes, "fracture_pair (P = %d)" % P),
+            med(times, "curved: cut_pairs_fracture (P = %d)" % P) / med(times, "fracture: cut_pairs_fracture (P = %d)" % P)), flush=True)
 
 
 if a.fracture:
-    bench_fracture(a.reps)
+    bench_fracture(a.reps, a.curvature)
     sys.exit(0)
 if a.pieces:
-    bench_pieces(a.pieces, a.reps)
+    bench_pieces(a.pieces, a.reps, a.curvature)
     sys.exit(0)
 for (B, M, N) in [(64, 6000, 1024), (64, 10000, 2048), (64, 12000, 2048)]:
     raw = (torch.rand(B, M, 3, generator=g) - 0.5).to(dev)

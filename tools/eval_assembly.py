@@ -1,9 +1,10 @@
 """The assembly score of a model as a mean over a batch of fractured puzzles, with one download at the end:
 
     python tools/eval_assembly.py [--batch 64] [--pieces 8] [--m 20000] [--k 128] [--candidates 16] [--mag 0.8] [--seed 0]
-                                  [--ckpt model.ckpt] [--refine N] [--joint N] [--max-score S]
+                                  [--curvature 2.0] [--ckpt model.ckpt] [--refine N] [--joint N] [--max-score S]
 
-B seeded uniform clouds of M points are each cut into P pieces that belong together (datapipe.fracture; every piece sampled to
+B seeded uniform clouds of M points are each cut into P pieces that belong together (datapipe.fracture, along curved surfaces
+with principal curvatures up to --curvature, along planes with --curvature 0; every piece sampled to
 the model's N points and moved by its own pose), then the chain of puzzlenet_amd.assembly runs on the whole batch on the device:
 match_puzzles (every piece encoded once, the encoders on full batches; --refine N: every pair pose refined on its picked
 boundaries by at most N ICP steps), assemble_batch (the greedy walk and the joint list of all puzzles, one launch), with --joint N
@@ -45,7 +46,9 @@ def main():
     ap.add_argument("--m", type=int, default=20000, help="points of every synthetic cloud")
     ap.add_argument("--n", type=int, default=1024, help="points per piece (the model's)")
     ap.add_argument("--k", type=int, default=128, help="boundary points picked per piece and pair")
-    ap.add_argument("--candidates", type=int, default=16, help="candidate planes per cut")
+    ap.add_argument("--candidates", type=int, default=16, help="candidate surfaces per cut")
+    ap.add_argument("--curvature", type=float, default=2.0,
+                    help="largest principal curvature of a break surface (2.0: a sphere of radius 0.5; 0: planes)")
     ap.add_argument("--mag", type=float, default=0.8, help="magnitude of every piece's twist")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ckpt", default=None, help="reference checkpoint (puzzlenet_amd.checkpoint); closed-form weights if absent")
@@ -73,10 +76,12 @@ def main():
 
     rng = np.random.RandomState(args.seed)
     raw = (rng.rand(B, M, 3) - 0.5).astype(np.float32)
-    draws = datapipe.fracture_draws(rng, torch.Generator().manual_seed(args.seed), B, P, args.candidates, args.mag)
-    to = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    if not 0.0 <= args.curvature < float("inf"):
+        sys.exit(f"--curvature {args.curvature}: finite and >= 0")
+    draws = datapipe.fracture_arguments(rng, torch.Generator().manual_seed(args.seed), B, P, args.candidates, args.mag, args.curvature)
+    to = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(dev)
     with torch.no_grad():
-        f = datapipe.fracture(to(raw), *(to(d) for d in draws), n=N, k=args.k, cap=min(M, 32768))
+        f = datapipe.fracture(to(raw), n=N, k=args.k, cap=min(M, 32768), **{name: to(d) for name, d in draws.items()})
         table = assembly.match_puzzles(model, f.pieces, k=args.k, refine=args.refine)
         asm = assembly.assemble_batch(table.score, table.T, max_score=args.max_score)
         rows = [metrics(assembly.evaluate_batch(asm.G, asm.placed, f.pose, f.rest, asm.root, asm.edges, asm.n_edges, f.mates), asm, f.ok)]

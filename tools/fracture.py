@@ -1,14 +1,18 @@
 """Cut a cloud into P pieces that belong together, with the answers: the input tools/assemble.py takes and the truth its
 --gt scores against (puzzlenet_amd.datapipe.fracture, one launch of csrc/fracture.hip for the cut).
 
-    python tools/fracture.py [--cloud cloud.npy] [--pieces 8] [--n 1024] [--k 128] [--candidates 16] [--mag 0.8] [--seed 0]
-                             [--out PREFIX]
+    python tools/fracture.py [--cloud cloud.npy] [--pieces 8] [--n 1024] [--k 128] [--candidates 16] [--curvature 2.0] [--mag 0.8]
+                             [--seed 0] [--out PREFIX]
 
 cloud.npy holds [M, 3] float32 (M <= 65536; a piece may hold at most 32768 points); without it a seeded uniform cloud of --m
 points in [-0.5, 0.5)^3 is cut.  Writes PREFIX_pieces.npy ([P, n, 3] float32: every piece sampled to n points and moved by a
 random rigid motion of magnitude --mag) and PREFIX_gt.npz with pose [P,4,4] (moved piece = pose applied to the piece where it
 belongs), rest [P,n,3], label [M] (the piece of every cloud point), src [P,n] (the cloud row of every sampled point), mates
 [P,P] and cd [P,P] (which pieces touch: the chamfer distance of the k-point boundaries against 0.015), planes [P-1,4].
+The break surfaces are curved: paraboloids through a point of the piece they cut, with principal curvatures drawn in
+[-C, C] for --curvature C (2.0: the curvature of a sphere of radius 0.5); planes then holds the tangent planes there, and
+PREFIX_gt.npz also anchor [P-1] (the cloud row each surface goes through), frame [P-1,3,3] (rows e1, e2, n) and half_curv [P-1,2]
+of the surface taken at every cut.  --curvature 0 cuts with planes.
 Needs a GPU; there is no CPU path."""
 import argparse
 import os
@@ -29,6 +33,8 @@ def main():
     ap.add_argument("--n-min", type=int, default=None, help="points both sides of a cut must hold (default: --n)")
     ap.add_argument("--k", type=int, default=128, help="boundary points per piece and pair")
     ap.add_argument("--candidates", type=int, default=16, help="candidate planes per cut")
+    ap.add_argument("--curvature", type=float, default=2.0,
+                    help="largest principal curvature of a break surface (0: planes)")
     ap.add_argument("--mag", type=float, default=0.8, help="magnitude of every piece's twist")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default="fracture", help="prefix of the two files written")
@@ -46,11 +52,12 @@ def main():
     else:
         cloud = (rng.rand(args.m, 3) - 0.5).astype(np.float32)
     M, P = cloud.shape[0], args.pieces
-    normals, u_anchor, u_start, twist = datapipe.fracture_draws(rng, torch.Generator().manual_seed(args.seed), 1, P,
-                                                                args.candidates, args.mag)
-    to = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-    f = datapipe.fracture(to(cloud[None]), to(normals), to(u_anchor), to(u_start), to(twist), n=args.n, n_min=args.n_min,
-                          k=args.k, cap=min(M, 32768))
+    if not 0.0 <= args.curvature < float("inf"):
+        sys.exit(f"--curvature {args.curvature}: finite and >= 0")
+    to = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    draws = datapipe.fracture_arguments(rng, torch.Generator().manual_seed(args.seed), 1, P, args.candidates, args.mag, args.curvature)
+    f = datapipe.fracture(to(cloud[None]), n=args.n, n_min=args.n_min, k=args.k, cap=min(M, 32768),
+                          **{name: to(d) for name, d in draws.items()})
     counts = f.counts[0].tolist()
     print(f"{M} points into {P} pieces: {counts}")
     if not bool(f.ok[0]):
@@ -62,8 +69,13 @@ def main():
         print(cd)
     print("mates:", [(a, b) for a in range(P) for b in range(a + 1, P) if mates[a, b]])
     np.save(args.out + "_pieces.npy", f.pieces[0].cpu().numpy())
+    surfaces = {}
+    if args.curvature > 0:
+        taken = f.cand[0].cpu().numpy()
+        surfaces = dict(anchor=f.anchor[0].cpu().numpy(), frame=draws["frames"][0, np.arange(P - 1), taken],
+                        half_curv=draws["half_curv"][0, np.arange(P - 1), taken])
     np.savez(args.out + "_gt.npz", pose=f.pose[0].cpu().numpy(), rest=f.rest[0].cpu().numpy(), label=f.label[0].cpu().numpy(),
-             src=f.src[0].cpu().numpy(), mates=mates, cd=cd, planes=f.planes[0].cpu().numpy())
+             src=f.src[0].cpu().numpy(), mates=mates, cd=cd, planes=f.planes[0].cpu().numpy(), **surfaces)
     print(f"wrote {args.out}_pieces.npy, {args.out}_gt.npz")
 
 

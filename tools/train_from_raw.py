@@ -3,7 +3,7 @@ labels, random motion on a background stream: the reference's loader processes, 
 :98-105) -> engine.TrainStep, a fresh batch every step, nothing synchronises.
 
     python tools/train_from_raw.py [--batch 64] [--points 2048] [--raw 10000] [--steps 20] [--cut {plane,sphere,cylinder,cone}]
-                                     [--random_slice] [--pieces P [--pieces_min L] [--neighbours q]]
+                                     [--random_slice] [--pieces P [--pieces_min L] [--neighbours q] [--curvature C]]
 
 --cut sphere | cylinder | cone: the reference's mesh cuts (dataset.py:715-759; "bed_sphere" is its documented training
 command) in place of the plane.  The cone (apex and base one unit from the origin) holds every point within 0.447 of the
@@ -12,6 +12,8 @@ origin, so for it the shells are twice as large.
 the plane only.
 --pieces P [--pieces_min L] [--neighbours q]: pairs cut out of fractures of L .. P pieces (L = P without --pieces_min), a share q of
 them drawn among all final pieces (PairFeeder(pieces=(L, P), neighbours=q)); with the plane only, without --random_slice.
+--curvature C (with --pieces; default 2.0, the curvature of the reference's radius-0.5 sphere): the fractures break along curved
+surfaces with principal curvatures in [-C, C] (PairFeeder(..., curvature=C)); 0: along planes.
 """
 import argparse, os, sys, time
 import numpy as np, torch
@@ -29,8 +31,10 @@ ap.add_argument("--random_slice", action="store_true")
 ap.add_argument("--pieces", type=int, default=0)
 ap.add_argument("--pieces_min", type=int, default=0)
 ap.add_argument("--neighbours", type=float, default=0.5)
+ap.add_argument("--curvature", type=float, default=2.0)
 a = ap.parse_args()
 pieces = None if not a.pieces else (a.pieces_min or a.pieces, a.pieces)
+curvature = a.curvature if pieces else None      # (the feeder refuses a curvature without pieces: the other cuts have none)
 dev = torch.device("cuda:0")
 B, N, M = a.batch, a.points, a.raw
 rng = np.random.RandomState(0)
@@ -42,7 +46,8 @@ if a.cut == "cone":
 cfg = Cfg(); cfg.num_points = N
 torch.manual_seed(0)
 model = model5_b.TouchedRegraster(cfg).to(dev)
-feeder = datapipe.PairFeeder(raw, dev, n=N, seed=0, cut=a.cut, split_twice=a.random_slice, pieces=pieces, neighbours=a.neighbours)
+feeder = datapipe.PairFeeder(raw, dev, n=N, seed=0, cut=a.cut, split_twice=a.random_slice, pieces=pieces, neighbours=a.neighbours,
+                             curvature=curvature)
 runner = engine.TrainStep(model, feeder.next_batch(), cfg.lr, world=1)
 nxt = feeder.next_batch()
 losses, mem, oks, doubles, fractures = [], [], [nxt.ok], [nxt.double], [nxt.fracture]
