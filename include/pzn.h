@@ -177,6 +177,30 @@ int pzn_assemble_walk_f32(const float* score, const float* T, const int32_t* cou
                           double* G, uint8_t* placed, int32_t* joints, int32_t* n_joints,
                           pzn_stream_t stream);
 
+/* One round of Z progressive walks (no counterpart in the reference; the choice and the ledger of assembly.ProgressiveAssembler
+ * for Z puzzles in lockstep): one launch, one wavefront per puzzle, no workspace, no atomics, nothing waits for the device.
+ * Slots are not compacted: puzzle z has P slots, a merged part stays in the fixed part's slot i and slot j dies, so a part in
+ * slot s lives in original piece s's frame.  State of puzzle z, updated in place: alive[P] (bytes 0 / 1: the slot holds a part),
+ * part[P] (int32: the slot of the part that holds original piece p), G[P,4,4] (float64: piece p into its part's frame), done
+ * (byte), n_edges (int32), edges[P-1,4] (int32 rows (label_i, label_j, i, j), a part's label = its lowest member piece; unused
+ * rows -1), edge_score[P-1] (fp32, the score as stored; unused rows +inf).  A fresh state: alive 1 (0 at or beyond a puzzle's
+ * piece count), part[p] = p, G the identity, done 0, n_edges 0.
+ * Key of entry (i, j) of score[z] ([P,P] fp32): its score; NaN, the diagonal and any pair with a dead end count as +inf.  Keys
+ * compare as floats (-0 equals 0); of equal keys the lowest i P + j is the smaller.
+ * Stop: done set, fewer than two slots alive, n_edges outside [0, P - 2], the smallest key not finite, or (double)key >
+ * max_score (+inf: never; NaN is PZN_EINVAL): done = 1, took = 0, pick = (0, 0), and nothing else of the state changes.
+ * Merge otherwise: for every p with part[p] == j, G[p] = T[z,i,j] G[p] (T fp32 widened to float64, an entry of the product is
+ * ((a0 b0 + a1 b1) + a2 b2) + a3 b3 with every operation rounded on its own) and part[p] = i; alive[j] = 0; the row
+ * (label_i, label_j, i, j) with the labels from before the merge and its score are appended; took = 1, pick = (i, j).
+ * Out: took[Z] bytes, pick[Z,2] int64.  The same bits on every run.
+ * 2 <= P <= 64 (pzn_progressive_round_supported: 1 / 0), PZN_EUNSUPPORTED otherwise, before any launch; Z = 0 is a success
+ * that launches nothing. */
+int pzn_progressive_round_supported(int P);
+int pzn_progressive_round_f32(const float* score, const float* T, double max_score, int Z, int P,
+                              uint8_t* alive, int32_t* part, double* G, uint8_t* done, int32_t* n_edges,
+                              int32_t* edges, float* edge_score, uint8_t* took, int64_t* pick,
+                              pzn_stream_t stream);
+
 /* pointnet_util.py:118-119  dists.argsort()[:, :, :K] fused with the distance:
  * idx[B,S,K] = the K nearest points of xyz[B,N,3] to each new_xyz[B,S,3],
  * ascending by (distance, index) == a stable ascending sort.  K <= N. */
@@ -659,6 +683,18 @@ int pzn_pair_head_supported(int N, int C2, int C3);
 int pzn_pair_head_fwd_f32(const float* x, int Kf, int N, const float* c, int Km, const float* W1, int ldw1,
                           const float* W2, const float* b2, const float* W3, const float* b3, int C2, int C3,
                           float* y, pzn_stream_t stream);
+/* The same head for Z puzzles in one launch, block-diagonal: the fixed piece (z, i) meets only the moved pieces (z, 0 .. Km-1)
+ * of its own puzzle,
+ *   y[z, i, j, p, :] = (relu(relu(x[z, i, p, :] W1^T + c[z, j, :]) W2^T + b2)) W3^T + b3     for z < Z, i < Kf, j < Km, p < N,
+ * x[Z, Kf, N, 64], c[Z, Km, 64], y[Z, Kf, Km, N, 2].  The work item is a (32-row tile, chunk of moved pieces) pair over the tiles
+ * of ALL puzzles (the j range is split until the launch fills the chip, counting every puzzle's tiles); the tile's piece gives z,
+ * which offsets c and y and nothing else, so y[z] has the bits of pzn_pair_head_fwd_f32 on x[z], c[z] - that entry is the
+ * Z = 1 case.  Shapes, alignment and PZN_EUNSUPPORTED as above, checked before any launch; Z = 0 is a success that launches
+ * nothing. */
+int pzn_pair_head_blocks_supported(int N, int C2, int C3);
+int pzn_pair_head_blocks_fwd_f32(const float* x, int Z, int Kf, int N, const float* c, int Km, const float* W1,
+                                 int ldw1, const float* W2, const float* b2, const float* W3, const float* b3,
+                                 int C2, int C3, float* y, pzn_stream_t stream);
 
 /* The encoder's out projection and the max over the points in ONE launch (model5_b.py:466-475):
  *   out[b,l,:] = cat(x[0] .. x[nslice-1])[b,l,:] W^T + bias   (W[Nout, nslice*E]; the concatenation is never built),

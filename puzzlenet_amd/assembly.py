@@ -42,8 +42,17 @@ Z puzzles in one launch, ops.assemble_walk, csrc/assemblewalk.hip; walk_rule is 
 one ops.joint_refine launch for all of them) and evaluate_batch (evaluate in float64 torch on the device).  The per-puzzle
 functions are not touched.
 
+The progressive walk takes a batch the same way: pair_block_batch is pair_block stage by stage with every stage ONCE for all Z
+puzzles (the pair head in block-diagonal form, ops.pair_head_blocks; match_puzzles is one call of it), and ProgressiveBatch /
+assemble_progressive_batch walk the Z puzzles in lockstep, P - 1 rounds with nothing waiting for the device: every round one
+ops.progressive_round launch chooses all Z merges and books them in a float64 ledger on the device (csrc/progressive.hip;
+progressive_round_rule is its numpy statement; slots die instead of being compacted, so shapes never change), one
+ops.merge_resample launch merges, one encode_pieces call encodes the Z merged parts, and two pair_block_batch calls give the new
+row and column of all Z tables.  Not done there: dead slots are still paired, stopped puzzles are still encoded, and a progressive
+part is not refined jointly.
+
 Inference only: eval mode, torch.no_grad(), fp32, one GPU.  Out of scope: any training on merged parts or on more than two
-pieces, beam search or several merges per round, undoing a merge, and more than one GPU.
+pieces, beam search or several merges per round within a puzzle, undoing a merge, and more than one GPU.
 """
 import collections
 
@@ -574,41 +583,107 @@ def assemble_batch(score, T, count=None, max_score=None, joint_score=None):
     return AssemblyBatch(root, edges, edge_score, n_edges, G, placed, movable, joints, n_joints)
 
 
-def match_puzzles(model, pieces, k=128, start=None, refine=0):
-    """match_pairs for Z puzzles of P pieces: pieces [Z,P,N,3] (float32, on the GPU) -> PairTable whose every field carries a
-    leading Z (twist [Z,P,P,6], T [Z,P,P,4,4], de_fpcb [Z,P,P,2,N], de_mrpcb [Z,P,2,N], top_f [Z,P,P,k], top_m [Z,P,k],
-    score [Z,P,P] with +inf on the diagonals, x2 [Z,P,256,3]).  The Z P pieces go through ONE encode_pieces, so the encoders run
-    on full 64-row batches however small a puzzle is; pair_block then runs per puzzle on the slices of the codes.
-    start = (s1[Z,P], s2[Z,P]) as match_pairs takes its starts; refine as match_pairs takes it.  x2 is match_pairs' of the
-    same puzzle and starts bit for bit; the fields behind the few-row layers (twist, and with it T and score) are not equal
-    bit for bit between two calls of match_pairs either, and agree with it as two such calls do.  Nothing waits for the device."""
-    refine = _check_refine(refine, "match_puzzles")
+def _pair_fixed_head_blocks(seq, local, g):
+    """_pair_fixed_head for Z puzzles: local [Z,Kf,N,64], g [Z,Km,64] -> [Z,Kf,Km,N,2] in one pair_head_blocks launch, or (shapes
+    it does not take) _pair_fixed_head's fallback puzzle by puzzle."""
+    mods = list(seq)
+    if len(mods) == 5 and ops.pair_head_blocks_supported(local.shape[2], mods[2].out_features, mods[4].out_features):
+        l1, l2, l3 = mods[0], mods[2], mods[4]
+        return ops.pair_head_blocks(local, g, l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias)
+    return torch.stack([_pair_fixed_head(seq, local[z], g[z]) for z in range(local.shape[0])], dim=0)
+
+
+def _puzzle_rows(pieces, top):
+    """pieces [Z,K,N,3] and picked rows top [Z,K,...] of every piece -> their points [..., 3] by ONE gather over the flattened
+    [1, Z K N, 3] rows (as refine_assembly_batch does it)."""
+    Z, K, N = pieces.shape[0], pieces.shape[1], pieces.shape[2]
+    first = (torch.arange(Z * K, dtype=torch.long, device=pieces.device) * N).view(Z, K, *([1] * (top.dim() - 2)))
+    return ops.index_points(pieces.reshape(1, Z * K * N, 3), (first + top).reshape(1, -1))[0].view(*top.shape, 3)
+
+
+def pair_block_batch(model, pieces_f, codes_f, pieces_m, codes_m, k=128, refine=0):
+    """pair_block for Z puzzles, block-diagonal: pieces_f [Z,Kf,N,3] in the fixed role meet only the pieces_m [Z,Km,N,3] of their
+    own puzzle -> PairBlock whose every field carries a leading Z (twist [Z,Kf,Km,6], T [Z,Kf,Km,4,4], de_fpcb [Z,Kf,Km,2,N], top_f
+    [Z,Kf,Km,k], score [Z,Kf,Km]).  codes_* are PieceCodes whose fields are [Z,K,...] views of one encode_pieces call over Z K pieces.
+    It is pair_block stage by stage, each stage ONCE for all puzzles: the pose head's four layers on the Z Kf Km rows relu(U + V),
+    se3.exp, one ops.pair_head_blocks launch, softmax and one topk_rows, one gather per side over the flattened rows, then the
+    transform and ops.chamfer or (refine > 0) the one ops.icp_refine launch.  de_fpcb has pair_block's bits (the blocked head does
+    not know about z); the fields behind the few-row layers agree with pair_block's as two calls of it do.  Nothing waits for
+    the device."""
+    refine = _check_refine(refine, "pair_block_batch")
+    for name, t in (("pieces_f", pieces_f), ("pieces_m", pieces_m)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.PznError(f"pair_block_batch: {name} must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
+        if t.dim() != 4 or t.shape[3] != 3 or t.dtype != torch.float32:
+            raise _lib.PznError(f"pair_block_batch expects float32 {name}[Z,K,N,3]; got {t.dtype} {tuple(t.shape)}")
+    Z, Kf, N = pieces_f.shape[0], pieces_f.shape[1], pieces_f.shape[2]
+    Km = pieces_m.shape[1]
+    if pieces_m.shape[0] != Z or pieces_m.shape[2] != N or Z < 1 or Kf < 1 or Km < 1:
+        raise _lib.PznError(f"pair_block_batch: pieces_f {tuple(pieces_f.shape)} and pieces_m {tuple(pieces_m.shape)} are not the "
+                            "pieces of the same Z >= 1 puzzles")
+    if tuple(codes_f.U.shape[:2]) != (Z, Kf) or tuple(codes_f.local_f.shape[:3]) != (Z, Kf, N) or tuple(codes_m.V.shape[:2]) != (Z, Km) \
+            or tuple(codes_m.g_max.shape[:2]) != (Z, Km) or tuple(codes_m.top_m.shape[:2]) != (Z, Km):
+        raise _lib.PznError(f"pair_block_batch: the codes are not [Z,K,...] views of Z = {Z} puzzles of {Kf} and {Km} pieces")
+    k = int(k)
+    with torch.no_grad():
+        hidden = torch.relu(codes_f.U[:, :, None] + codes_m.V[:, None]).reshape(Z * Kf * Km, -1)
+        twist = run_seq(list(model.tfMLP)[2:], hidden).view(Z, Kf, Km, 6)
+        T = se3.exp(twist)
+
+        y_f = _pair_fixed_head_blocks(model.MLPFpcb, codes_f.local_f, codes_m.g_max)          # [Z,Kf,Km,N,2]
+        de_fpcb = y_f.permute(0, 1, 2, 4, 3)
+
+        p_f = torch.softmax(y_f, dim=-1)[..., 1].reshape(Z * Kf * Km, N)
+        top_f = ops.topk_rows(p_f, k).view(Z, Kf, Km, k)
+        Bf = _puzzle_rows(pieces_f, top_f).view(Z * Kf * Km, k, 3)                            # pieces_f[z,i][top_f[z,i,j]]
+        Bm = _puzzle_rows(pieces_m, codes_m.top_m).view(Z * Km, -1, 3)                        # pieces_m[z,j][top_m[z,j]]
+        if refine > 0:
+            # problem (z, i, j) reads the moved set z Km + j
+            b_of = (torch.arange(Z, dtype=torch.long, device=T.device)[:, None, None] * Km
+                    + torch.arange(Km, dtype=torch.long, device=T.device)[None, None, :]).expand(Z, Kf, Km).reshape(-1)
+            Tr, score, _, _ = ops.icp_refine(Bf, Bm, T.reshape(Z * Kf * Km, 4, 4), refine, b_of=b_of)
+            return PairBlock(twist, Tr.view(Z, Kf, Km, 4, 4), de_fpcb, top_f, score.view(Z, Kf, Km))
+        Bm = Bm.view(Z, 1, Km, -1, 3).expand(Z, Kf, Km, -1, 3).reshape(Z * Kf * Km, -1, 3)
+        d1, d2 = ops.chamfer(Bf, se3.transform_points(T.reshape(Z * Kf * Km, 4, 4), Bm))
+        score = (d1.mean(dim=1) + d2.mean(dim=1)).view(Z, Kf, Km)
+    return PairBlock(twist, T, de_fpcb, top_f, score)
+
+
+def _match_puzzles(model, pieces, k, start, refine, who):
+    """match_puzzles' body -> (pieces contiguous, PieceCodes of [Z,P,...] views, the square PairBlock, diagonal not masked)."""
+    refine = _check_refine(refine, who)
     if not isinstance(pieces, torch.Tensor) or not pieces.is_cuda:
-        raise _lib.PznError("match_puzzles: pieces must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
+        raise _lib.PznError(f"{who}: pieces must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
     if pieces.dim() != 4 or pieces.shape[3] != 3 or pieces.dtype != torch.float32 or pieces.shape[0] < 1:
-        raise _lib.PznError(f"match_puzzles expects float32 pieces[Z,P,N,3] with Z >= 1; got {pieces.dtype} {tuple(pieces.shape)}")
+        raise _lib.PznError(f"{who} expects float32 pieces[Z,P,N,3] with Z >= 1; got {pieces.dtype} {tuple(pieces.shape)}")
     Z, P, N, _ = pieces.shape
     if P < 2:
-        raise _lib.PznError(f"match_puzzles: P = {P} pieces a puzzle (>= 2)")
+        raise _lib.PznError(f"{who}: P = {P} pieces a puzzle (>= 2)")
     pieces = pieces.contiguous()
     flat = pieces.view(Z * P, N, 3)
     if start is not None:
         s1, s2 = (torch.as_tensor(s, dtype=torch.long) for s in start)
         if tuple(s1.shape) != (Z, P) or tuple(s2.shape) != (Z, P):
-            raise _lib.PznError(f"match_puzzles: start = (s1[{Z},{P}], s2[{Z},{P}]); got {tuple(s1.shape)}, {tuple(s2.shape)}")
+            raise _lib.PznError(f"{who}: start = (s1[{Z},{P}], s2[{Z},{P}]); got {tuple(s1.shape)}, {tuple(s2.shape)}")
         start = (s1.reshape(Z * P), s2.reshape(Z * P))
-    codes = encode_pieces(model, flat, k, start, _who="match_puzzles", _least=2)
-    blocks = []
-    for z in range(Z):
-        cz = PieceCodes(*(f[z * P:(z + 1) * P] for f in codes))
-        blocks.append(pair_block(model, pieces[z], cz, pieces[z], cz, k, refine))
+    codes = encode_pieces(model, flat, k, start, _who=who, _least=2)
+    codes = PieceCodes(*(f.view(Z, P, *f.shape[1:]) for f in codes))
+    return pieces, codes, pair_block_batch(model, pieces, codes, pieces, codes, k, refine)
+
+
+def match_puzzles(model, pieces, k=128, start=None, refine=0):
+    """match_pairs for Z puzzles of P pieces: pieces [Z,P,N,3] (float32, on the GPU) -> PairTable whose every field carries a
+    leading Z (twist [Z,P,P,6], T [Z,P,P,4,4], de_fpcb [Z,P,P,2,N], de_mrpcb [Z,P,2,N], top_f [Z,P,P,k], top_m [Z,P,k],
+    score [Z,P,P] with +inf on the diagonals, x2 [Z,P,256,3]).  The Z P pieces go through ONE encode_pieces, so the encoders run
+    on full 64-row batches however small a puzzle is, and ONE pair_block_batch: the number of library launches does not depend on Z.
+    start = (s1[Z,P], s2[Z,P]) as match_pairs takes its starts; refine as match_pairs takes it.  x2 is match_pairs' of the
+    same puzzle and starts bit for bit; the fields behind the few-row layers (twist, and with it T and score) are not equal
+    bit for bit between two calls of match_pairs either, and agree with it as two such calls do.  Nothing waits for the device."""
+    pieces, codes, blk = _match_puzzles(model, pieces, k, start, refine, "match_puzzles")
+    P = pieces.shape[1]
     with torch.no_grad():
-        twist, T, y_f, top_f, score = (torch.stack(f, dim=0) for f in zip(*(b._replace(de_fpcb=b.de_fpcb.permute(0, 1, 3, 2))
-                                                                          for b in blocks)))
-        de_fpcb = y_f.permute(0, 1, 2, 4, 3)              # as in match_pairs: a permuted view of the kernel's [.,P,P,N,2]
-        score = score.masked_fill(torch.eye(P, dtype=torch.bool, device=pieces.device), float("inf"))
-        per_piece = lambda f: f.view(Z, P, *f.shape[1:])
-    return PairTable(twist, T, de_fpcb, per_piece(codes.de_mrpcb), top_f, per_piece(codes.top_m), score, per_piece(codes.x2))
+        score = blk.score.masked_fill(torch.eye(P, dtype=torch.bool, device=pieces.device), float("inf"))
+    return PairTable(blk.twist, blk.T, blk.de_fpcb, codes.de_mrpcb, blk.top_f, codes.top_m, score, codes.x2)
 
 
 def refine_assembly_batch(pieces, table, asm, sweeps=30):
@@ -901,3 +976,246 @@ class ProgressiveAssembler:
 def assemble_progressive(model, pieces, k=128, start=None, max_score=None, drop_matched=True, generator=None, refine=0):
     """ProgressiveAssembler(...).step() until one part is left or the walk stops -> Progressive."""
     return ProgressiveAssembler(model, pieces, k, start, max_score, drop_matched, generator, refine).run()
+
+
+# --------------------------------------------------------------------------- progressive assembly, a batch of puzzles in lockstep
+
+ProgressiveState = ops.ProgressiveState
+ProgressiveBatchResult = collections.namedtuple(
+    "ProgressiveBatchResult", "G edges edge_score n_edges root placed part alive parts piece_id row_id dropped")
+
+
+def progressive_start(Z, P, count=None):
+    """The fresh state of Z progressive walks over P slots as numpy arrays, in the kernel's shapes and types (ops.progressive_state
+    is the same on the device) -> ProgressiveState(alive [Z,P] uint8, part [Z,P] int32, G [Z,P,4,4] float64, done [Z] uint8,
+    n_edges [Z] int32, edges [Z,P-1,4] int32, edge_score [Z,P-1] float32): slots at or beyond count[z] start dead."""
+    alive = np.ones((Z, P), dtype=np.uint8)
+    if count is not None:
+        alive = (np.arange(P)[None, :] < np.asarray(count, dtype=np.int64).reshape(Z, 1)).astype(np.uint8)
+    return ProgressiveState(alive, np.tile(np.arange(P, dtype=np.int32), (Z, 1)), np.tile(np.eye(4), (Z, P, 1, 1)),
+                            np.zeros(Z, dtype=np.uint8), np.zeros(Z, dtype=np.int32), np.full((Z, P - 1, 4), -1, dtype=np.int32),
+                            np.full((Z, P - 1), np.inf, dtype=np.float32))
+
+
+def progressive_round_rule(score, T, state, max_score=None):
+    """The numpy statement of ops.progressive_round (csrc/progressive.hip, the rule in include/pzn.h), which is held to it bit for
+    bit, G included: one round of Z progressive walks on the host.  score [Z,P,P] (read as float32), T [Z,P,P,4,4] (float32),
+    state = a ProgressiveState (tensors or arrays; it is not changed) -> (the new ProgressiveState of numpy arrays, took [Z] uint8,
+    pick [Z,2] int64).
+
+    Slots are not compacted: a merged part stays in the fixed part's slot i and slot j dies, so row-major order over the live
+    slots is the compacted order of ProgressiveAssembler and "the first row-major minimum" is the same pair as _choose's.
+    Key of (i, j): its float32 score; NaN, the diagonal and any pair with a dead end count as +inf; keys compare as floats, ties
+    to the lowest i P + j.  Stop (done = 1, took = 0, pick = (0, 0), nothing else changes): done is set, fewer than two slots are
+    alive, n_edges is outside [0, P - 2], the smallest key is not finite or it is above max_score.  Merge otherwise: for every p
+    with part[p] == j, G[p] = T[i,j] G[p] (_rule_product: float64 from the float32 T, every operation rounded on its own) and
+    part[p] = i; alive[j] = 0; the row (label_i, label_j, i, j) - a label is the part's lowest member piece, before the merge -
+    and the score as stored are appended; took = 1, pick = (i, j)."""
+    as_np = lambda a, dt: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(dt)
+    S, X = as_np(score, np.float32), as_np(T, np.float32)
+    Z, P = S.shape[0], S.shape[1]
+    if S.shape != (Z, P, P) or X.shape != (Z, P, P, 4, 4) or P < 2:
+        raise ValueError(f"progressive_round_rule expects score[Z,P,P], T[Z,P,P,4,4] with P >= 2; got {S.shape}, {X.shape}")
+    types = (np.uint8, np.int32, np.float64, np.uint8, np.int32, np.int32, np.float32)
+    alive, part, G, done, n_edges, edges, edge_score = (as_np(f, dt).copy() for f, dt in zip(state, types))
+    took = np.zeros(Z, dtype=np.uint8)
+    pick = np.zeros((Z, 2), dtype=np.int64)
+    inf = float("inf")
+    limit = inf if max_score is None else float(max_score)
+    for z in range(Z):
+        live = [s for s in range(P) if alive[z, s]]
+        ne = int(n_edges[z])
+        stop = bool(done[z]) or len(live) < 2 or not 0 <= ne < P - 1
+        if not stop:
+            raw = S[z].tolist()                          # float32 values as Python floats (exact)
+            best, at = inf, None                         # the first row-major position of the smallest key
+            for i in live:
+                for j in live:
+                    key = inf if (i == j or raw[i][j] != raw[i][j]) else raw[i][j]
+                    if at is None or key < best:
+                        best, at = key, (i, j)
+            stop = not np.isfinite(best) or best > limit
+        if stop:
+            done[z] = 1
+            continue
+        i, j = at
+        Tij = X[z, i, j].astype(np.float64).tolist()
+        label = lambda s: min((p for p in range(P) if part[z, p] == s), default=s)
+        row = (label(i), label(j), i, j)
+        for p in range(P):
+            if part[z, p] == j:
+                G[z, p] = np.array(_rule_product(Tij, G[z, p].tolist()), dtype=np.float64)
+                part[z, p] = i
+        alive[z, j] = 0
+        edges[z, ne] = row
+        edge_score[z, ne] = S[z, i, j]
+        n_edges[z] = ne + 1
+        took[z] = 1
+        pick[z] = (i, j)
+    return ProgressiveState(alive, part, G, done, n_edges, edges, edge_score), took, pick
+
+
+class ProgressiveBatch:
+    """ProgressiveAssembler for Z puzzles of P pieces in lockstep, with no host in between: every round ALL puzzles choose their
+    merge in one launch (ops.progressive_round; progressive_round_rule is its statement), merge in one launch
+    (ops.merge_resample), encode the Z merged parts in ONE encode_pieces call - the encoders see batches of Z, not of 1 - and compute
+    the new row [Z,1,P] and the new column [Z,P,1] of all Z tables by one pair_block_batch each.
+
+    Slots are not compacted: a merged part stays in the fixed part's slot i, slot j dies; shapes never change and the part in slot s
+    lives in original piece s's frame.  State, all on the device: parts [Z,P,N,3], codes (PieceCodes of [Z,P,...]), table (PairTable
+    with a leading Z; rows and columns of dead slots and the diagonal have score +inf), piece_id / row_id [Z,P,N] int64 (which
+    original piece and row every point is), ledger (ops.ProgressiveState: alive, part, G float64, done, n_edges, edges, edge_score),
+    took / pick of the last round, dropped (per round, the (piece, row) pairs the merges left out).
+
+    pieces [Z,P,N,3], k, refine as match_puzzles takes them; start = (s1[Z,P], s2[Z,P]); max_score stops a puzzle at its first
+    minimum above it (the others go on); merge_starts [Z,P-1] int64 are the merges' start rows, drawn with torch.randint(0, N) from
+    `generator` when None; count [Z]: the pieces of every puzzle, slots at or beyond it start dead.  A stopped puzzle keeps every bit
+    of its state: what a round computed for it is discarded through torch.where(took, new, old).  Every table entry outside row i,
+    column i and the dead slots is kept bit for bit.
+
+    Not done here: dead slots are still paired every round (up to half of the block work is wasted), stopped puzzles are still
+    encoded, and a progressive part is not refined jointly.  Inference only: eval mode, no_grad, fp32, one GPU."""
+
+    def __init__(self, model, pieces, k=128, start=None, max_score=None, drop_matched=True, generator=None, merge_starts=None,
+                 refine=0, count=None):
+        who = "ProgressiveBatch"
+        self.refine = _check_refine(refine, who)
+        if isinstance(pieces, torch.Tensor) and pieces.dim() == 4:
+            _check_pieces(model, pieces[0], k, who, 2)
+        pieces, codes, blk = _match_puzzles(model, pieces, k, start, self.refine, who)
+        Z, P, N, _ = pieces.shape
+        k = int(k)
+        if drop_matched and 2 * k > N:
+            raise _lib.PznError(f"{who}: drop_matched needs k <= N / 2 (k = {k}, N = {N}): the rows kept of a union must fill "
+                                "the merged part")
+        if not ops.merge_resample_supported(N, N, N):
+            raise _lib.PznUnsupported(f"{who}: two parts of N = {N} points are not a union merge_resample takes")
+        if not ops.progressive_round_supported(P):
+            raise _lib.PznUnsupported(f"{who}: P = {P} pieces a puzzle (2 <= P <= 64)")
+        if max_score is not None and float(max_score) != float(max_score):
+            raise _lib.PznError(f"{who}: max_score is NaN (None: no limit)")
+        self.model, self.k, self.max_score, self.drop_matched = model, k, max_score, bool(drop_matched)
+        dev = pieces.device
+        with torch.no_grad():
+            if count is not None:
+                count = torch.as_tensor(count).to(dev)
+                if tuple(count.shape) != (Z,) or count.dtype.is_floating_point:
+                    raise _lib.PznError(f"{who}: count must be {Z} integers; got {count.dtype} {tuple(count.shape)}")
+            self.ledger = ops.progressive_state(Z, P, dev, count)
+            if merge_starts is None:
+                stage = torch.empty((Z, P - 1), dtype=torch.long, pin_memory=True)
+                torch.randint(0, N, (Z, P - 1), dtype=torch.long, generator=generator, out=stage)
+                self._stage = stage      # (alive until the copy has run)
+                merge_starts = stage.to(dev, non_blocking=True)
+            else:
+                merge_starts = torch.as_tensor(merge_starts)
+                if tuple(merge_starts.shape) != (Z, P - 1) or merge_starts.dtype != torch.long:
+                    raise _lib.PznError(f"{who}: merge_starts must be int64 [{Z},{P - 1}]; got {merge_starts.dtype} "
+                                        f"{tuple(merge_starts.shape)}")
+                merge_starts = merge_starts.to(dev)
+            self.merge_starts = merge_starts
+            self.parts = pieces.clone()
+            self.codes = codes
+            self._eye = torch.eye(P, dtype=torch.bool, device=dev)
+            self._z = torch.arange(Z, dtype=torch.long, device=dev)
+            self._y_f = blk.de_fpcb.permute(0, 1, 2, 4, 3)      # the kernel's [Z,P,P,N,2]; de_fpcb is its permuted view
+            self._twist, self._T, self._top_f = blk.twist, blk.T, blk.top_f
+            self._score = blk.score.masked_fill(self._dead(), float("inf"))
+            self.piece_id = torch.arange(P, dtype=torch.long, device=dev)[None, :, None].expand(Z, P, N).contiguous()
+            self.row_id = torch.arange(N, dtype=torch.long, device=dev)[None, None, :].expand(Z, P, N).contiguous()
+            self.took = torch.zeros((Z,), dtype=torch.uint8, device=dev)
+            self.pick = torch.zeros((Z, 2), dtype=torch.long, device=dev)
+        self.dropped = []
+        self.rounds = 0
+
+    def _dead(self):
+        """[Z,P,P] bool: the diagonal and every pair with a dead end."""
+        a = self.ledger.alive.bool()
+        return ~(a[:, :, None] & a[:, None, :]) | self._eye
+
+    @property
+    def table(self):
+        c = self.codes
+        return PairTable(self._twist, self._T, self._y_f.permute(0, 1, 2, 4, 3), c.de_mrpcb, self._top_f, c.top_m, self._score, c.x2)
+
+    def step(self):
+        """One round of all Z puzzles.  Nothing here waits for the device: the picks stay there, every gather and every write-back
+        is indexed by them, and whether a puzzle took its merge is a torch.where."""
+        Z, P, N = self.parts.shape[0], self.parts.shape[1], self.parts.shape[2]
+        if self.rounds >= P - 1:
+            raise _lib.PznError(f"ProgressiveBatch: all {P - 1} rounds of P = {P} pieces are made")
+        k, z = self.k, self._z
+        with torch.no_grad():
+            # 1. every puzzle chooses (and its ledger is updated) on the device
+            took, pick = ops.progressive_round(self._score, self._T, self.ledger, self.max_score)
+            i, j = pick[:, 0], pick[:, 1]
+            tk = took.bool()
+            wide = lambda t: tk.view(Z, *([1] * (t.dim() - 1)))
+
+            # 2. merge: part j moved into part i's frame, the union resampled to N points; Z merges, one launch
+            da = self._top_f[z, i, j] if self.drop_matched else None
+            db = self.codes.top_m[z, j] if self.drop_matched else None
+            merged, src = ops.merge_resample(self.parts[z, i], self.parts[z, j], self._T[z, i, j], self.merge_starts[:, self.rounds],
+                                             N, da, db)
+            pid = torch.cat((self.piece_id[z, i], self.piece_id[z, j]), dim=1).gather(1, src)
+            rid = torch.cat((self.row_id[z, i], self.row_id[z, j]), dim=1).gather(1, src)
+            if self.drop_matched:
+                rows = torch.stack((torch.stack((self.piece_id[z, i].gather(1, da), self.row_id[z, i].gather(1, da)), dim=-1),
+                                    torch.stack((self.piece_id[z, j].gather(1, db), self.row_id[z, j].gather(1, db)), dim=-1)), dim=1)
+                self.dropped.append(torch.where(wide(rows), rows, torch.full_like(rows, -1)))          # [Z,2,k,2]
+            self.rounds += 1
+
+            # 3. the merged parts come out in pick order: their sampling plans cost no FPS; one encode_pieces over all Z
+            code = encode_pieces(self.model, merged, k, plan=pick_order_plan(merged), _who="ProgressiveBatch")
+
+            # 4. the state of a puzzle that took its merge moves on, slot i; a stopped one is written back as it was
+            def put(old, new):
+                old[z, i] = torch.where(wide(new), new, old[z, i])
+            put(self.parts, merged)
+            put(self.piece_id, pid)
+            put(self.row_id, rid)
+            for old, new in zip(self.codes, code):
+                put(old, new)
+
+            # 5. the new row and the new column of all Z tables, one blocked launch chain each
+            one = PieceCodes(*(f.unsqueeze(1) for f in code))
+            m1 = merged.unsqueeze(1)
+            row = pair_block_batch(self.model, m1, one, self.parts, self.codes, k, self.refine)      # [Z,1,P]
+            col = pair_block_batch(self.model, self.parts, self.codes, m1, one, k, self.refine)      # [Z,P,1]
+            for old, r, c in ((self._twist, row.twist, col.twist), (self._T, row.T, col.T),
+                              (self._y_f, row.de_fpcb.permute(0, 1, 2, 4, 3), col.de_fpcb.permute(0, 1, 2, 4, 3)),
+                              (self._top_f, row.top_f, col.top_f), (self._score, row.score, col.score)):
+                old[z, :, i] = torch.where(wide(c[:, :, 0]), c[:, :, 0], old[z, :, i])
+                old[z, i] = torch.where(wide(r[:, 0]), r[:, 0], old[z, i])
+            self._score.masked_fill_(self._dead(), float("inf"))
+            self.took, self.pick = took, pick
+        return took, pick
+
+    def run(self):
+        """The P - 1 rounds (a count the host knows: stopped puzzles idle) -> result()."""
+        while self.rounds < self.parts.shape[1] - 1:
+            self.step()
+        return self.result()
+
+    def result(self):
+        """-> ProgressiveBatchResult of device tensors: G [Z,P,4,4] float64, edges [Z,P-1,4] int32 rows (label_i, label_j, i, j),
+        edge_score [Z,P-1], n_edges [Z], root [Z] int32 (the slot - and so the frame piece - of the part that holds the first edge's
+        fixed piece; -1 without an edge), placed [Z,P] bool (the members of that part; none without an edge), part, alive, parts,
+        piece_id, row_id (the final state) and dropped [rounds,Z,2,k,2] int64 (per round and side - fixed, moved - the (piece, row)
+        pairs left out; -1 where the puzzle made no merge; None without drop_matched).  It feeds evaluate_batch(r.G, r.placed,
+        pose, rest, r.root, r.edges, r.n_edges, mates) as it is.  Nothing waits for the device."""
+        s = self.ledger
+        with torch.no_grad():
+            has = s.n_edges > 0
+            first = s.edges[:, 0, 0].long().clamp(min=0)
+            root = torch.where(has, s.part.gather(1, first[:, None])[:, 0], torch.full_like(s.n_edges, -1))
+            placed = (s.part == root[:, None]) & has[:, None]
+            dropped = torch.stack(self.dropped, dim=0) if self.dropped else None
+        return ProgressiveBatchResult(s.G, s.edges, s.edge_score, s.n_edges, root, placed, s.part, s.alive.bool(), self.parts,
+                                      self.piece_id, self.row_id, dropped)
+
+
+def assemble_progressive_batch(model, pieces, k=128, start=None, max_score=None, drop_matched=True, generator=None,
+                               merge_starts=None, refine=0, count=None):
+    """ProgressiveBatch(...).run(): the P - 1 lockstep rounds of Z puzzles -> ProgressiveBatchResult."""
+    return ProgressiveBatch(model, pieces, k, start, max_score, drop_matched, generator, merge_starts, refine, count).run()

@@ -19,6 +19,7 @@
 //     the place of (i, j) after the joints of the rows before: row-major order with no scan through memory.
 // Every index into score and T is formed from an i, j < count[z] <= K.  No atomics: the same bits on every run.
 #include "pzn_common.h"
+#include "pzn_walk.h"      // the key, the 64-lane arg-min and the float64 dot product, shared with progressive.hip
 
 #pragma clang fp contract(off)
 
@@ -28,38 +29,6 @@ constexpr int AW_T = 256;                       // four wavefronts = four puzzle
 constexpr int AW_W = AW_T / PZN_WAVE;
 constexpr int AW_MAX_K = 64;                    // a piece per lane
 constexpr int AW_MAX_GRID = 256;                // 1024 puzzles in flight; more take their turn in the same wavefronts
-
-// fp32 -> dword with the floats' order (no NaN reaches it)
-__device__ __forceinline__ uint32_t ordered(float x) {
-  const uint32_t u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float unordered(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
-// the key of entry (i, j) with score s: NaN and the diagonal are +inf, -0 is +0
-__device__ __forceinline__ uint64_t entry(float s, int i, int j, int K) {
-  float k = (i == j || s != s) ? __builtin_inff() : s;
-  k = k == 0.f ? 0.f : k;
-  return ((uint64_t)ordered(k) << 32) | (uint32_t)(i * K + j);
-}
-
-__device__ __forceinline__ uint64_t wave_min_u64_dpp(uint64_t v) {
-  uint64_t o;
-  o = pzn::xor_lane_u64<1>(v), v = o < v ? o : v;
-  o = pzn::xor_lane_u64<2>(v), v = o < v ? o : v;
-  o = pzn::xor_lane_u64<4>(v), v = o < v ? o : v;
-  o = pzn::xor_lane_u64<8>(v), v = o < v ? o : v;
-  o = pzn::xor_lane_u64<16>(v), v = o < v ? o : v;
-  o = pzn::xor_lane_u64<32>(v), v = o < v ? o : v;
-  return v;
-}
-
-__device__ __forceinline__ double dot4(double a0, double b0, double a1, double b1, double a2, double b2, double a3, double b3) {
-  return ((a0 * b0 + a1 * b1) + a2 * b2) + a3 * b3;
-}
 
 __global__ __launch_bounds__(AW_T) void assemble_walk_kernel(const float* __restrict__ score, const float* __restrict__ T,
                                                              const int32_t* __restrict__ count, double max_score,

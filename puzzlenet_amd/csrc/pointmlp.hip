@@ -238,14 +238,17 @@ __global__ __launch_bounds__(PM_FWD_WAVES * 64) void point_mlp3_fwd_kernel(PmFwd
 // pieces: the tile is read once, A = W1_loc x computed once and kept in registers (zero-seeded: the bias is added behind
 // the products), and for every j the rest of the chain runs on relu(A + c_j) and only the 32 x 2 logits are written.
 // Nothing is kept for a backward pass; every output element has one owner and one summation order.
+// Block-diagonal form (Z puzzles, pzn_pair_head_blocks_fwd_f32): the tiles of all Z Kf fixed pieces are one list, the tile's
+// piece gives its puzzle z = piece / Kf, and z only offsets the bias rows (c[z]) and, through the piece, the output; the
+// arithmetic of an item does not know about z, so puzzle z's block has the bits of the one-puzzle launch on its slices.
 struct PmPairArgs {
-  const float* x;          // [Kf, N, 64]
-  const float* c;          // [Km, 64]
+  const float* x;          // [Z Kf, N, 64]
+  const float* c;          // [Z, Km, 64]
   const float* w1;         // [64, ldw1]: the local half of the first layer
   const float *w2, *b2;    // [32, 64], [32]
   const float *w3, *b3;    // [2, 32], [2]
-  float* y;                // [Kf, Km, N, 2]
-  int ldw1, Km, N, tiles_per_piece, ntiles, chunk, nchunks, nitems;
+  float* y;                // [Z Kf, Km, N, 2]
+  int ldw1, Kf, Km, N, tiles_per_piece, ntiles, chunk, nchunks, nitems;
 };
 
 // x = relu(a + bias[feature]) (the feature is the row of a transposed tile)
@@ -295,9 +298,10 @@ __global__ __launch_bounds__(PM_FWD_WAVES * 64) void pair_head_fwd_kernel(PmPair
     ZERO16(A[1]);
     pm_layer<2, 4>(A, X, img1, lane);
     float* yrow = a.y + (((long)piece * a.Km + j0) * a.N + prow + lane) * 2;
+    const float* cz = a.c + (long)(piece / a.Kf) * a.Km * PM_C;      // the bias rows of the piece's own puzzle
     for (int j = j0; j < j1; ++j, yrow += (long)a.N * 2) {
       floatx16 H1[2];
-      pm_bias_relu(H1, A, a.c + (long)j * PM_C, h);
+      pm_bias_relu(H1, A, cz + (long)j * PM_C, h);
       floatx16 H2[1];
       H2[0] = B2[0];
       pm_layer<1, 4>(H2, H1, img2, lane);
@@ -758,16 +762,20 @@ PZN_EXPORT int pzn_pair_head_supported(int N, int C2, int C3) {
   return pm_enabled() && N > 0 && N % 32 == 0 && C2 == 32 && C3 == 2;
 }
 
-// y[i, j, p, :] = (relu(relu(x[i, p] W1^T + c[j]) W2^T + b2)) W3^T + b3 for every fixed piece i < Kf and moved piece j < Km;
-// forward only, one launch, no workspace.  W1[64, ldw1] is the local half of the first layer (a column slice, ldw1 >= 64),
-// c[j] the folded global half (g_j W1[:, :64]^T + b1).
-PZN_EXPORT int pzn_pair_head_fwd_f32(const float* x, int Kf, int N, const float* c, int Km, const float* W1, int ldw1,
-                                     const float* W2, const float* b2, const float* W3, const float* b3, int C2, int C3,
-                                     float* y, pzn_stream_t stream) {
-  PZN_CHECK_ARG(x && c && W1 && W2 && b2 && W3 && b3 && y && Kf > 0 && Km > 0 && N > 0 && ldw1 >= 64);
+// y[z, i, j, p, :] = (relu(relu(x[z, i, p] W1^T + c[z, j]) W2^T + b2)) W3^T + b3 for every puzzle z < Z, fixed piece i < Kf and
+// moved piece j < Km of the same puzzle; forward only, one launch, no workspace.  W1[64, ldw1] is the local half of the first layer
+// (a column slice, ldw1 >= 64), c[z, j] the folded global half (g_zj W1[:, :64]^T + b1).  Z = 0 launches nothing.
+PZN_EXPORT int pzn_pair_head_blocks_supported(int N, int C2, int C3) { return pzn_pair_head_supported(N, C2, C3); }
+
+PZN_EXPORT int pzn_pair_head_blocks_fwd_f32(const float* x, int Z, int Kf, int N, const float* c, int Km, const float* W1, int ldw1,
+                                            const float* W2, const float* b2, const float* W3, const float* b3, int C2, int C3,
+                                            float* y, pzn_stream_t stream) {
+  PZN_CHECK_ARG(Z >= 0 && Kf > 0 && Km > 0 && N > 0 && ldw1 >= 64);
   if (!pzn_pair_head_supported(N, C2, C3)) return PZN_EUNSUPPORTED;
-  const long long ntiles = (long long)Kf * (N / 32);
-  // moved pieces per work item: as long as the tiles alone do not give every SIMD two wavefronts, split the j range
+  if (Z == 0) return PZN_OK;
+  PZN_CHECK_ARG(x && c && W1 && W2 && b2 && W3 && b3 && y);
+  const long long ntiles = (long long)Z * Kf * (N / 32);
+  // moved pieces per work item: as long as the tiles of ALL puzzles do not give every SIMD two wavefronts, split the j range
   constexpr int SLOTS = 256 * PM_FWD_WAVES;
   int nchunks = ntiles >= SLOTS ? 1 : (int)((SLOTS + ntiles - 1) / ntiles);
   if (nchunks > Km) nchunks = Km;
@@ -775,13 +783,21 @@ PZN_EXPORT int pzn_pair_head_fwd_f32(const float* x, int Kf, int N, const float*
   nchunks = (Km + chunk - 1) / chunk;
   if (ntiles * nchunks > 0x3fffffffLL) return PZN_EUNSUPPORTED;      // (the walk adds one grid stride to an item index)
   PZN_CHECK_ARG(pm_aligned16(x) && pm_aligned16(c) && pm_aligned16(b2) && pm_aligned16(y));
-  PmPairArgs a{x, c, W1, W2, b2, W3, b3, y, ldw1, Km, N, N / 32, (int)ntiles, chunk, nchunks, (int)(ntiles * nchunks)};
+  PmPairArgs a{x, c, W1, W2, b2, W3, b3, y, ldw1, Kf, Km, N, N / 32, (int)ntiles, chunk, nchunks, (int)(ntiles * nchunks)};
   const int nwg = (a.nitems + PM_FWD_WAVES - 1) / PM_FWD_WAVES;
   const dim3 grid(nwg < 256 ? nwg : 256), block(PM_FWD_WAVES * 64);
   constexpr int lds = pm_fwd_lds<32, 2>();
   if (pm_set_lds(pair_head_fwd_kernel, lds) != PZN_OK) return PZN_ELAUNCH;
   PZN_LAUNCH(pair_head_fwd_kernel, grid, block, lds, pzn_hip_stream(stream), a);
   PZN_RETURN_LAUNCH_STATUS();
+}
+
+// The one-puzzle table: the Z = 1 case of the launch above (the same items, chunks and bits as before the block form existed).
+PZN_EXPORT int pzn_pair_head_fwd_f32(const float* x, int Kf, int N, const float* c, int Km, const float* W1, int ldw1,
+                                     const float* W2, const float* b2, const float* W3, const float* b3, int C2, int C3,
+                                     float* y, pzn_stream_t stream) {
+  PZN_CHECK_ARG(x && c && W1 && W2 && b2 && W3 && b3 && y && Kf > 0 && Km > 0 && N > 0 && ldw1 >= 64);
+  return pzn_pair_head_blocks_fwd_f32(x, 1, Kf, N, c, Km, W1, ldw1, W2, b2, W3, b3, C2, C3, y, stream);
 }
 
 namespace {

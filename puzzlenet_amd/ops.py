@@ -4,6 +4,7 @@ torch is used for device memory, the current HIP stream and autograd plumbing
 only: every computation below is a call into libpzn.so with raw device
 pointers.  Inputs must live on a HIP device; there is no CPU path.
 """
+import collections
 import ctypes
 import os
 import weakref
@@ -400,6 +401,75 @@ def assemble_walk(score, T, count=None, max_score=None, joint_score=None):
         _call("pzn_assemble_walk_f32", _p(score), _p(T), _p(count), max_score, joint_score, Z, K, _p(root), _p(edges), _p(edge_score),
               _p(n_edges), _p(G), _p(placed), _p(joints), _p(n_joints), _stream())
     return root, edges, edge_score, n_edges, G, placed, joints, n_joints
+
+
+ProgressiveState = collections.namedtuple("ProgressiveState", "alive part G done n_edges edges edge_score")
+_PROGRESSIVE_TYPES = (torch.uint8, torch.int32, torch.float64, torch.uint8, torch.int32, torch.int32, torch.float32)
+
+
+def progressive_round_supported(P):
+    return bool(_lib.load().pzn_progressive_round_supported(int(P)))
+
+
+def progressive_state(Z, P, device, count=None):
+    """The fresh state of Z progressive walks over P slots (include/pzn.h, pzn_progressive_round_f32) -> ProgressiveState of
+    device tensors: alive [Z,P] uint8 (1; 0 for the slots at or beyond count[z], count [Z] integers on the device or None), part
+    [Z,P] int32 (part[p] = p), G [Z,P,4,4] float64 (identity), done [Z] uint8 (0), n_edges [Z] int32 (0), edges [Z,P-1,4] int32
+    (-1), edge_score [Z,P-1] float32 (+inf).  Nothing waits for the device."""
+    Z, P = int(Z), int(P)
+    slot = torch.arange(P, dtype=torch.int32, device=device)
+    if count is None:
+        alive = torch.ones((Z, P), dtype=torch.uint8, device=device)
+    else:
+        if not isinstance(count, torch.Tensor) or not count.is_cuda or tuple(count.shape) != (Z,) or count.dtype.is_floating_point:
+            raise _lib.PznError(f"progressive_state: count must be an integer tensor [{Z}] on the GPU")
+        alive = (slot[None, :] < count[:, None]).to(torch.uint8)
+    return ProgressiveState(alive, slot[None, :].repeat(Z, 1), torch.eye(4, dtype=torch.float64, device=device).repeat(Z, P, 1, 1),
+                            torch.zeros((Z,), dtype=torch.uint8, device=device), torch.zeros((Z,), dtype=torch.int32, device=device),
+                            torch.full((Z, max(P - 1, 0), 4), -1, dtype=torch.int32, device=device),
+                            torch.full((Z, max(P - 1, 0)), float("inf"), dtype=torch.float32, device=device))
+
+
+def progressive_round(score, T, state, max_score=None):
+    """One round of Z progressive walks in one launch (pzn_progressive_round_f32; include/pzn.h states the rule,
+    assembly.progressive_round_rule is its numpy statement): score [Z,P,P] float32, T [Z,P,P,4,4] float32 (T[z,i,j] maps the part
+    in slot j into slot i's frame), state = a ProgressiveState of contiguous device tensors in its own types (progressive_state
+    makes one), which is UPDATED IN PLACE, max_score (None: a walk stops only at a key that is not finite) -> (took [Z] uint8,
+    pick [Z,2] int64): took = 1 and pick = (i, j) where puzzle z merged slot j into slot i, took = 0 and the safe pick (0, 0)
+    where it stopped (its done is set and nothing else of its state has changed).  2 <= P <= 64 (PznUnsupported beyond).
+    Z = 0 launches nothing.  No autograd, nothing waits for the device."""
+    for name, t in (("score", score), ("T", T)):
+        if isinstance(t, torch.Tensor) and t.dtype != torch.float32:      # (no silent conversion)
+            raise _lib.PznError(f"progressive_round: {name} must be torch.float32; got {t.dtype}")
+    score, T = _f32(score, "score"), _f32(T, "T")
+    if score.dim() != 3 or score.shape[1] != score.shape[2]:
+        raise _lib.PznError(f"progressive_round: expected score[Z,P,P]; got {tuple(score.shape)}")
+    Z, P = score.shape[0], score.shape[1]
+    if tuple(T.shape) != (Z, P, P, 4, 4):
+        raise _lib.PznError(f"progressive_round: expected T[{Z},{P},{P},4,4]; got {tuple(T.shape)}")
+    if not isinstance(state, ProgressiveState):
+        raise _lib.PznError(f"progressive_round: state must be a ProgressiveState; got {type(state).__name__}")
+    shapes = ((Z, P), (Z, P), (Z, P, 4, 4), (Z,), (Z,), (Z, max(P - 1, 0), 4), (Z, max(P - 1, 0)))
+    for name, t, dt, shape in zip(ProgressiveState._fields, state, _PROGRESSIVE_TYPES, shapes):
+        # the state is written in place: a converted or compacted copy would take the update with it
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != score.device or t.dtype != dt or tuple(t.shape) != shape \
+                or not t.is_contiguous():
+            raise _lib.PznError(f"progressive_round: state.{name} must be a contiguous {dt} tensor {list(shape)} on {score.device}; got "
+                                f"{(t.dtype, tuple(t.shape), str(t.device)) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    max_score = float("inf") if max_score is None else float(max_score)
+    if max_score != max_score:
+        raise _lib.PznError("progressive_round: max_score is NaN (None: no limit)")
+    if not progressive_round_supported(P):
+        raise _lib.PznUnsupported(f"progressive_round: P = {P} slots (2 <= P <= 64)")
+    dev = score.device
+    took = torch.empty((Z,), dtype=torch.uint8, device=dev)
+    pick = torch.empty((Z, 2), dtype=torch.int64, device=dev)
+    if Z > 0:
+        with _on(dev):
+            s = state
+            _call("pzn_progressive_round_f32", _p(score), _p(T), max_score, Z, P, _p(s.alive), _p(s.part), _p(s.G), _p(s.done),
+                  _p(s.n_edges), _p(s.edges), _p(s.edge_score), _p(took), _p(pick), _stream())
+    return took, pick
 
 
 def knn(xyz, new_xyz, K):
@@ -1555,6 +1625,45 @@ def pair_head(x, g, w1, b1, w2, b2, w3, b3):
         c = linear_cols(g2, w1, 0, b1)      # [Km,64]
         _call("pzn_pair_head_fwd_f32", _p(x), Kf, N, _p(c), Km, _p(w1) + 4 * Cg, Cg + C, _p(w2), _p(b2), _p(w3), _p(b3),
               C2, C3, _p(y), st, flops=2 * Kf * N * (64 * 64 + Km * (64 * C2 + C2 * C3)))
+    return y
+
+
+def pair_head_blocks_supported(N, C2, C3):
+    return bool(_lib.load().pzn_pair_head_blocks_supported(int(N), int(C2), int(C3)))
+
+
+def pair_head_blocks(x, g, w1, b1, w2, b2, w3, b3):
+    """pair_head for Z puzzles in one launch, block-diagonal (csrc/pointmlp.hip, pair_head_fwd_kernel behind
+    pzn_pair_head_blocks_fwd_f32): x[Z,Kf,N,64] local features of the fixed-role pieces, g[Z,Km,64] the moved pieces' global
+    vectors -> y[Z,Kf,Km,N,2] with y[z] = pair_head(x[z], g[z], ...) bit for bit: the fixed piece (z, i) meets only the moved
+    pieces of its own puzzle.  One linear_cols over the Z Km global vectors, then one launch; Z = 0 launches nothing.
+    Forward only: no autograd, nothing saved."""
+    x = _f32(x.detach(), "x")
+    g = _f32(g.detach(), "g")
+    w1, b1, w2, b2, w3, b3 = (_f32(t.detach(), n) for t, n in ((w1, "w1"), (b1, "b1"), (w2, "w2"), (b2, "b2"), (w3, "w3"), (b3, "b3")))
+    if x.dim() != 4 or x.shape[3] != 64:
+        raise _lib.PznError(f"pair_head_blocks expects x[Z,Kf,N,64]; got {tuple(x.shape)}")
+    Z, Kf, N, C = x.shape
+    if g.dim() != 3 or g.shape[0] != Z:
+        raise _lib.PznError(f"pair_head_blocks expects g[{Z},Km,Cg]; got {tuple(g.shape)}")
+    Km, Cg = g.shape[1], g.shape[2]
+    C2, C3 = w2.shape[0], w3.shape[0]
+    if w1.shape != (64, Cg + C) or w2.shape[1] != 64 or w3.shape[1] != C2:
+        raise _lib.PznError(f"pair_head_blocks: w1{tuple(w1.shape)}, w2{tuple(w2.shape)}, w3{tuple(w3.shape)} vs {Cg} + {C} input columns")
+    if Kf < 1 or Km < 1:
+        raise _lib.PznError(f"pair_head_blocks: Kf = {Kf}, Km = {Km} pieces a puzzle (>= 1)")
+    if not pair_head_blocks_supported(N, C2, C3):
+        raise _lib.PznUnsupported(f"pair_head_blocks: N = {N} (a multiple of 32) and a 64 -> {C2} -> {C3} tail (32 -> 2) are not "
+                                  "a shape the kernel takes")
+    dev = x.device
+    y = torch.empty((Z, Kf, Km, N, C3), dtype=torch.float32, device=dev)
+    if Z == 0:
+        return y
+    with _on(dev):
+        st = _stream()
+        c = linear_cols(g.reshape(Z * Km, Cg), w1, 0, b1)      # [Z Km,64]
+        _call("pzn_pair_head_blocks_fwd_f32", _p(x), Z, Kf, N, _p(c), Km, _p(w1) + 4 * Cg, Cg + C, _p(w2), _p(b2), _p(w3), _p(b3),
+              C2, C3, _p(y), st, flops=2 * Z * Kf * N * (64 * 64 + Km * (64 * C2 + C2 * C3)))
     return y
 
 

@@ -2,6 +2,7 @@
 
     python tools/eval_assembly.py [--batch 64] [--pieces 8] [--m 20000] [--k 128] [--candidates 16] [--mag 0.8] [--seed 0]
                                   [--curvature 2.0] [--ckpt model.ckpt] [--refine N] [--joint N] [--max-score S]
+                                  [--progressive] [--time R] [--json out.json]
 
 B seeded uniform clouds of M points are each cut into P pieces that belong together (datapipe.fracture, along curved surfaces
 with principal curvatures up to --curvature, along planes with --curvature 0; every piece sampled to
@@ -12,7 +13,12 @@ refine_assembly_batch (all placed poses of every puzzle refined together over ev
 evaluate_batch against the fracture's truth.  Nothing waits for the device until the metrics - a few numbers per puzzle - are
 downloaded once.  Prints the means over the valid fractures: part accuracy, edge precision, and over the placed pieces other
 than the root the rotation error in degrees, the translation error and the mean squared distance; with --joint both before and
-after the joint refinement.  Without --ckpt the weights are the closed-form pseudo-random ones and the poses mean nothing.
+after the joint refinement.  --progressive reports the same means for the progressive walk (assemble_progressive_batch: all
+puzzles in lockstep, P - 1 rounds, every round one choice launch, one merge launch, one encoder batch and two blocked pair blocks)
+beside the greedy one, on the same fractures and table starts, still with the one download.  --time R (with --progressive) then
+times the batched progressive walk and, beside it, a loop of assemble_progressive over the same puzzles - the per-puzzle path, which
+downloads its table every round - R times each in turn after one warm-up of each, a host clock around work that ends in a device
+synchronise, and counts the library launches of one round; --json writes those numbers to a file.  Without --ckpt the weights are the closed-form pseudo-random ones and the poses mean nothing.
 Needs a GPU; there is no CPU path."""
 import argparse
 import os
@@ -55,9 +61,14 @@ def main():
     ap.add_argument("--refine", type=int, default=0, help="ICP steps at most per pair pose on the picked boundary points (0: none)")
     ap.add_argument("--joint", type=int, default=0, help="sweeps at most of the joint refinement after the walk (0: none)")
     ap.add_argument("--max-score", type=float, default=None, help="stop placing pieces above this boundary distance")
+    ap.add_argument("--progressive", action="store_true", help="also the progressive walk of the whole batch, in lockstep")
+    ap.add_argument("--time", type=int, default=0, help="with --progressive: repeats of the timed batched walk and per-puzzle loop")
+    ap.add_argument("--json", default=None, help="with --time: write the timings and launch counts to this file")
     args = ap.parse_args()
     if args.refine < 0 or args.joint < 0:
         sys.exit("--refine, --joint: 0 or a number of steps / sweeps")
+    if args.time < 0 or (args.time and not args.progressive) or (args.json and not args.time):
+        sys.exit("--time R >= 0 goes with --progressive, --json with --time")
     if not torch.cuda.is_available():
         sys.exit("tools/eval_assembly.py needs a GPU: puzzlenet_amd has no CPU path")
     from puzzlenet_amd import assembly, checkpoint, datapipe, model5_b
@@ -82,7 +93,9 @@ def main():
     to = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(dev)
     with torch.no_grad():
         f = datapipe.fracture(to(raw), n=N, k=args.k, cap=min(M, 32768), **{name: to(d) for name, d in draws.items()})
-        table = assembly.match_puzzles(model, f.pieces, k=args.k, refine=args.refine)
+        # the FPS starts of the table, drawn as match_puzzles draws them, so that the progressive walk can start from the same ones
+        s1, s2 = (s.view(B, P) for s in model5_b.draw_fps_starts(1, B * P, N, model.fps_generator))
+        table = assembly.match_puzzles(model, f.pieces, k=args.k, start=(s1, s2), refine=args.refine)
         asm = assembly.assemble_batch(table.score, table.T, max_score=args.max_score)
         rows = [metrics(assembly.evaluate_batch(asm.G, asm.placed, f.pose, f.rest, asm.root, asm.edges, asm.n_edges, f.mates), asm, f.ok)]
         extra = torch.zeros(3, dtype=torch.float64, device=dev)
@@ -91,15 +104,88 @@ def main():
             rows.append(metrics(assembly.evaluate_batch(jr.G, asm.placed, f.pose, f.rest, asm.root, asm.edges, asm.n_edges, f.mates),
                                 asm, f.ok))
             extra = torch.stack((jr.score0.double().mean(), jr.score.double().mean(), jr.sweeps_used.double().mean()))
+        if args.progressive:
+            walk = lambda: assembly.assemble_progressive_batch(model, f.pieces, k=args.k, start=(s1, s2), max_score=args.max_score,
+                                                               generator=torch.Generator().manual_seed(args.seed), refine=args.refine)
+            pr = walk()
+            rows.append(metrics(assembly.evaluate_batch(pr.G, pr.placed, f.pose, f.rest, pr.root, pr.edges, pr.n_edges, f.mates), pr, f.ok))
+            rows.append(torch.stack((pr.n_edges.double().mean(),)))
         head = torch.stack((f.ok.double().sum(), asm.n_joints.double().mean(), asm.n_edges.double().mean()))
         host = torch.cat([head, extra] + rows).cpu().tolist()                       # the one download
     print(f"{B} clouds of {M} points into {P} pieces of {N}: {int(host[0])} valid fractures; per puzzle {host[2]:.2f} edges, "
           f"{host[1]:.1f} joints")
     names = ("part accuracy", "edge precision", "rotation (deg)", "translation", "msd", "share placed")
-    for label, at in (("greedy walk", 6),) + ((("after the joint refinement", 12),) if args.joint else ()):
+    at_p = 18 if args.joint else 12
+    for label, at in (("greedy walk", 6),) + ((("after the joint refinement", 12),) if args.joint else ()) \
+            + ((("progressive walk", at_p),) if args.progressive else ()):
         print(f"{label}: " + ", ".join(f"{n} {v:.6g}" for n, v in zip(names, host[at:at + 6])))
     if args.joint:
         print(f"joint refinement: mean summed score {host[3]:.6f} -> {host[4]:.6f}, {host[5]:.1f} sweeps")
+    if args.progressive:
+        print(f"progressive walk: per puzzle {host[at_p + 6]:.2f} edges in {P - 1} lockstep rounds")
+    if args.time:
+        time_progressive(args, model, f, (s1, s2), walk)
+
+
+def time_progressive(args, model, f, start, walk):
+    """The batched progressive walk against a loop of assemble_progressive over the same puzzles, in turn, and the library launches
+    of one round of each."""
+    import json
+    import statistics
+    import time
+    from puzzlenet_amd import assembly, ops
+    B, P = f.pieces.shape[0], f.pieces.shape[1]
+    s1, s2 = start
+
+    def loop():
+        g = torch.Generator().manual_seed(args.seed)
+        return [assembly.assemble_progressive(model, f.pieces[z], k=args.k, start=(s1[z], s2[z]), max_score=args.max_score, generator=g,
+                                              refine=args.refine) for z in range(B)]
+
+    def clock(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    def launches(fn):
+        real, calls = ops._call, []
+
+        def spy(name, *a, **k):
+            calls.append(name)
+            return real(name, *a, **k)
+        ops._call = spy
+        try:
+            fn()
+        finally:
+            ops._call = real
+        return len(calls)
+
+    with torch.no_grad():
+        clock(walk), clock(loop)                                                  # warm-up: every shape of both paths
+        ms = {"batched": [], "loop": []}
+        for _ in range(args.time):
+            ms["batched"].append(clock(walk))
+            ms["loop"].append(clock(loop))
+        pb = assembly.ProgressiveBatch(model, f.pieces, k=args.k, start=start, max_score=args.max_score, refine=args.refine)
+        one = assembly.ProgressiveAssembler(model, f.pieces[0], k=args.k, start=(s1[0], s2[0]), max_score=args.max_score,
+                                            refine=args.refine)
+        n_round, n_one = launches(pb.step), launches(one.step)
+    out = {"puzzles": B, "pieces": P, "points": f.pieces.shape[2], "k": args.k, "refine": args.refine, "repeats": args.time,
+           "batched_ms": ms["batched"], "loop_ms": ms["loop"],
+           "batched_ms_median": statistics.median(ms["batched"]), "loop_ms_median": statistics.median(ms["loop"]),
+           "rounds_batched": P - 1, "rounds_loop_at_most": B * (P - 1),
+           "library_launches_per_round_batched": n_round, "library_launches_per_round_one_puzzle": n_one,
+           "what": "wall time (host clock, device synchronised) of assemble_progressive_batch over all puzzles, construction included, "
+                   "and of a loop of assemble_progressive over the same puzzles in the same process, alternating, after one warm-up each"}
+    print(f"batched progressive walk: median {out['batched_ms_median']:.1f} ms of {args.time} ({min(ms['batched']):.1f} .. "
+          f"{max(ms['batched']):.1f}); loop of assemble_progressive: median {out['loop_ms_median']:.1f} ms ({min(ms['loop']):.1f} .. "
+          f"{max(ms['loop']):.1f}); library launches per round: {n_round} for {B} puzzles, {n_one} for one")
+    if args.json:
+        with open(args.json, "w") as fh:
+            json.dump(out, fh, indent=1)
+            fh.write("\n")
 
 
 if __name__ == "__main__":
