@@ -177,6 +177,46 @@ int pzn_assemble_walk_f32(const float* score, const float* T, const int32_t* cou
                           double* G, uint8_t* placed, int32_t* joints, int32_t* n_joints,
                           pzn_stream_t stream);
 
+/* The beam walk over Z pair tables, scored by the placed pieces' votes (no counterpart in the reference; assembly.beam_rule is
+ * the numpy statement): one launch, one wavefront per puzzle, no workspace, no atomics, nothing waits for the device.
+ * score, T, count, max_score and joint_score are pzn_assemble_walk_f32's; keys, their order and ties, the root, the pose
+ * arithmetic (an entry of a product is dot4(a0,b0,a1,b1,a2,b2,a3,b3) = ((a0 b0 + a1 b1) + a2 b2) + a3 b3, the rigid inverse) and
+ * the meaning of count are its own, word for word.  moment[z] ([K,4,4] float64): moment[n] = the mean over piece n's picked
+ * boundary points x of (x, 1) (x, 1)^T.  beam B, branch C; weight (double; NaN is PZN_EINVAL); vote_score (double; NaN means
+ * max_score).
+ * Hypothesis: a placed set, a float64 pose for every placed piece, its edges in placement order and a float64 cost.  Round 0
+ * has one: {root}, cost 0.
+ * Candidates of a hypothesis: the ordered pairs (i, j), i, j < count, with exactly one end placed, a finite key and
+ * (double)key <= max_score; the first C of them in the order (key, i K + j), rank = the position 0 .. C-1.  (The list ends at
+ * the first key that fails, as the walk stops there: a key of -inf ends it as well.)  Several candidates may place the same
+ * piece through different entries.
+ * Child of candidate (i, j): its new piece n and pose Gn follow the walk's rule.  Its votes: over the hypothesis' placed pieces
+ * p in ascending order, entry (p, n) and then entry (n, p), without the candidate's own entry and without an entry whose key
+ * is not finite or has (double)key > vote_score.  A vote predicts Q = G[p] T[p,n] or Q = G[p] inv(T[n,p]) and disagrees by d:
+ * D = Q - Gn on rows 0..2; for row u, m_v = dot4(M[v][0], D[u][0], M[v][1], D[u][1], M[v][2], D[u][2], M[v][3], D[u][3]) with
+ * M = moment[n] and q_u = dot4(D[u][0], m_0, D[u][1], m_1, D[u][2], m_2, D[u][3], m_3); d = (q_0 + q_1) + q_2 - the mean over
+ * n's boundary points of |Q x - Gn x|^2, in the unit of score.  penalty = (0 + d_1 + d_2 + ...) summed in vote order, divided by
+ * the number of votes; 0 with no vote.  Child cost = (parent cost + (double)key) + weight * penalty, every operation rounded on
+ * its own; with weight == 0 the last term is neither computed nor added; a NaN cost becomes +inf.
+ * Selection: all children of the round in the order (cost, parent slot, rank) - costs compare as doubles, -0 equals 0 -, each
+ * kept unless a kept child has the same placed set, until B are kept; the kept order is the next round's slot order.  A
+ * hypothesis without a candidate has no child; a round without any child ends the walk.  All live hypotheses hold the same
+ * number of pieces.
+ * Out: the result is slot 0, in pzn_assemble_walk_f32's outputs (root, edges, edge_score, n_edges, G, placed, and joints /
+ * n_joints by the walk's joint rule from the result's own edges); cost[Z,B] float64 in slot order, unused slots +inf;
+ * n_hyp[Z] int32, the live hypotheses.  A count outside [2, K] gives the walk's empty answer and n_hyp 0.  With B = C = 1
+ * every walk output is pzn_assemble_walk_f32's bit for bit, whatever weight is.  The same bits on every run.
+ * 2 <= K <= 64, 1 <= B, C <= 8 (pzn_assemble_beam_supported: 1 / 0; each of a round's B C children has a lane, two generations of
+ * hypotheses are 2 B (128 K + 4 (K - 1) + 16) bytes of LDS), PZN_EUNSUPPORTED otherwise, before any launch; Z = 0 is a success
+ * that launches nothing. */
+int pzn_assemble_beam_supported(int K, int B, int C);
+int pzn_assemble_beam_f32(const float* score, const float* T, const double* moment, const int32_t* count,
+                          int beam, int branch, double weight, double max_score, double vote_score,
+                          double joint_score, int Z, int K,
+                          int32_t* root, int32_t* edges, float* edge_score, int32_t* n_edges,
+                          double* G, uint8_t* placed, int32_t* joints, int32_t* n_joints,
+                          double* cost, int32_t* n_hyp, pzn_stream_t stream);
+
 /* One round of Z progressive walks (no counterpart in the reference; the choice and the ledger of assembly.ProgressiveAssembler
  * for Z puzzles in lockstep): one launch, one wavefront per puzzle, no workspace, no atomics, nothing waits for the device.
  * Slots are not compacted: puzzle z has P slots, a merged part stays in the fixed part's slot i and slot j dies, so a part in

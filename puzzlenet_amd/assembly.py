@@ -42,6 +42,13 @@ Z puzzles in one launch, ops.assemble_walk, csrc/assemblewalk.hip; walk_rule is 
 one ops.joint_refine launch for all of them) and evaluate_batch (evaluate in float64 torch on the device).  The per-puzzle
 functions are not touched.
 
+assemble_beam_batch stands beside assemble_batch: a beam in place of the greedy walk, which takes the smallest entry every round
+and never checks it.  `beam` hypotheses live side by side, each extended by its `branch` smallest entries, and a child pays its
+entry's score plus `weight` times what the entries of the other placed pieces say against its pose - how far apart, in the mean
+square, the two predictions put the new piece's picked boundary points, read off one 4x4 second-moment matrix per piece
+(boundary_moments) -: the cycles a spanning tree never asks.  One launch for Z puzzles (ops.assemble_beam, csrc/assemblebeam.hip;
+beam_rule is its numpy statement); its result feeds refine_assembly_batch and evaluate_batch as assemble_batch's does.
+
 The progressive walk takes a batch the same way: pair_block_batch is pair_block stage by stage with every stage ONCE for all Z
 puzzles (the pair head in block-diagonal form, ops.pair_head_blocks; match_puzzles is one call of it), and ProgressiveBatch /
 assemble_progressive_batch walk the Z puzzles in lockstep, P - 1 rounds with nothing waiting for the device: every round one
@@ -52,7 +59,7 @@ row and column of all Z tables.  Not done there: dead slots are still paired, st
 part is not refined jointly.
 
 Inference only: eval mode, torch.no_grad(), fp32, one GPU.  Out of scope: any training on merged parts or on more than two
-pieces, beam search or several merges per round within a puzzle, undoing a merge, and more than one GPU.
+pieces, a beam or several merges per round of the progressive walk, undoing a merge, and more than one GPU.
 """
 import collections
 
@@ -581,6 +588,204 @@ def assemble_batch(score, T, count=None, max_score=None, joint_score=None):
         index = torch.arange(placed.shape[1], dtype=torch.int32, device=placed.device)
         movable = placed & (index[None, :] != root[:, None])
     return AssemblyBatch(root, edges, edge_score, n_edges, G, placed, movable, joints, n_joints)
+
+
+# --------------------------------------------------------------------------- the beam walk scored by the placed pieces' votes
+
+BeamBatch = collections.namedtuple("BeamBatch", AssemblyBatch._fields + ("cost", "n_hyp"))
+BeamRule = collections.namedtuple("BeamRule", WalkRule._fields + ("cost", "n_hyp"))
+
+
+def boundary_moments(pieces, top_m):
+    """The second-moment matrix of every piece's picked boundary points in homogeneous form, the `moment` input of
+    assemble_beam_batch: pieces [Z,P,N,3] (float32, on the GPU), top_m [Z,P,k] (match_puzzles' field) -> [Z,P,4,4] float64 on the
+    device, moment[z,p] = the mean over x = pieces[z,p][top_m[z,p]] of (x, 1) (x, 1)^T.  With it mean_x |Q x - G x|^2 is
+    sum_u D_u M D_u^T over the rows of D = Q - G: what two poses of piece p disagree by on its boundary, with no point read.
+    Nothing waits for the device."""
+    for name, t in (("pieces", pieces), ("top_m", top_m)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.PznError(f"boundary_moments: {name} must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
+    if pieces.dim() != 4 or pieces.shape[3] != 3 or pieces.dtype != torch.float32:
+        raise _lib.PznError(f"boundary_moments expects float32 pieces[Z,P,N,3]; got {pieces.dtype} {tuple(pieces.shape)}")
+    Z, P = pieces.shape[0], pieces.shape[1]
+    if top_m.dim() != 3 or tuple(top_m.shape[:2]) != (Z, P) or top_m.shape[2] < 1 or top_m.dtype != torch.long:
+        raise _lib.PznError(f"boundary_moments expects int64 top_m[{Z},{P},k]; got {top_m.dtype} {tuple(top_m.shape)}")
+    with torch.no_grad():
+        x = _puzzle_rows(pieces.contiguous(), top_m).double()                                  # [Z,P,k,3]
+        xh = torch.cat((x, torch.ones_like(x[..., :1])), dim=-1)
+        return (xh.unsqueeze(-1) * xh.unsqueeze(-2)).mean(dim=2)
+
+
+def _rule_products(A, B):
+    """_rule_product on stacks [n,4,4] of float64 matrices, element-wise (every numpy operation rounds on its own)."""
+    out = np.empty_like(A)
+    for u in range(4):
+        for v in range(4):
+            out[:, u, v] = _dot4(A[:, u, 0], B[:, 0, v], A[:, u, 1], B[:, 1, v], A[:, u, 2], B[:, 2, v], A[:, u, 3], B[:, 3, v])
+    return out
+
+
+def _rule_inverses(T):
+    """_rule_inverse on a stack [n,4,4]."""
+    out = np.zeros_like(T)
+    for u in range(3):
+        for v in range(3):
+            out[:, u, v] = T[:, v, u]
+        out[:, u, 3] = -((T[:, 0, u] * T[:, 0, 3] + T[:, 1, u] * T[:, 1, 3]) + T[:, 2, u] * T[:, 2, 3])
+    out[:, 3, 3] = 1.0
+    return out
+
+
+def beam_rule(score, T, moment, count=None, beam=4, branch=4, weight=1.0, max_score=None, vote_score=None, joint_score=None):
+    """The numpy statement of ops.assemble_beam (csrc/assemblebeam.hip, the rule in include/pzn.h), which is held to it bit for
+    bit, G and cost included.  score [Z,K,K] (read as float32), T [Z,K,K,4,4] (float32), moment [Z,K,4,4] (float64), count [Z]
+    or None, tensors or arrays -> BeamRule: walk_rule's fields in its shapes and types, cost [Z,beam] float64 and n_hyp [Z] int32.
+
+    Keys, ties, the root, the pose arithmetic and count are walk_rule's.  A hypothesis is a placed set with its poses, edges and
+    a float64 cost; its candidates are the first `branch` ordered pairs with one end placed in the order (key, i K + j), keys
+    finite and <= max_score.  A child costs (parent + key) + weight * penalty, penalty = the mean, summed in vote order, of the
+    disagreement d of every other entry between a placed piece p (ascending; (p, n) then (n, p); keys finite and <= vote_score)
+    and the new piece n: D = G[p] T[p,n] - Gn or G[p] inv(T[n,p]) - Gn on rows 0..2, d = sum_u D_u M[n] D_u^T with the rule's
+    dot4 order.  The round's children are ordered by (cost, parent slot, rank) and the first `beam` distinct placed sets live on.
+    The result is slot 0.  Written with element-wise float64 only: no matmul, whose summation order is not fixed."""
+    as_np = lambda a, dt: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(dt)
+    S, P, M = as_np(score, np.float32), as_np(T, np.float32), as_np(moment, np.float64)
+    Z, K = S.shape[0], S.shape[1]
+    B, C, weight = int(beam), int(branch), float(weight)
+    if S.shape != (Z, K, K) or P.shape != (Z, K, K, 4, 4) or M.shape != (Z, K, 4, 4) or K < 2:
+        raise ValueError(f"beam_rule expects score[Z,K,K], T[Z,K,K,4,4], moment[Z,K,4,4] with K >= 2; got {S.shape}, {P.shape}, "
+                         f"{M.shape}")
+    if B < 1 or C < 1 or weight != weight:
+        raise ValueError(f"beam_rule: beam = {B}, branch = {C} (>= 1), weight = {weight} (not NaN)")
+    counts = np.full(Z, K, dtype=np.int64) if count is None else as_np(count, np.int64)
+    inf = float("inf")
+    limit = inf if max_score is None else float(max_score)
+    vlimit = limit if vote_score is None or vote_score != vote_score else float(vote_score)
+    root = np.full(Z, -1, dtype=np.int32)
+    edges = np.full((Z, K - 1, 3), -1, dtype=np.int32)
+    edge_score = np.full((Z, K - 1), np.inf, dtype=np.float32)
+    n_edges = np.zeros(Z, dtype=np.int32)
+    G = np.tile(np.eye(4), (Z, K, 1, 1))
+    placed = np.zeros((Z, K), dtype=np.uint8)
+    joints = np.full((Z, K * (K - 1), 2), -1, dtype=np.int32)
+    n_joints = np.zeros(Z, dtype=np.int32)
+    cost = np.full((Z, B), np.inf, dtype=np.float64)
+    n_hyp = np.zeros(Z, dtype=np.int32)
+    with np.errstate(all="ignore"):
+        for z in range(Z):
+            c = int(counts[z])
+            if not 2 <= c <= K:
+                continue
+            raw = S[z, :c, :c].astype(np.float64)
+            key = np.where(np.isnan(raw) | np.eye(c, dtype=bool), inf, raw) + 0.0            # (-0 is +0)
+            flat_of = np.arange(c)[:, None] * K + np.arange(c)[None, :]
+            r = int(np.flatnonzero(key.reshape(-1) == key.min())[0]) // c                    # the first row-major position
+            root[z] = r
+            Pz, Mz = P[z].astype(np.float64), M[z]
+            first = np.zeros(c, dtype=bool)
+            first[r] = True
+            pose0 = np.zeros((c, 4, 4))
+            pose0[r] = np.eye(4)
+            hyps = [(first, pose0, [], 0.0)]                                                 # (inside, poses, edges, cost)
+            for _ in range(c - 1):
+                kids = []                                                                    # (slot, rank, i, j, new, key)
+                for slot, (inside, _, _, _) in enumerate(hyps):
+                    at = np.flatnonzero((inside[:, None] != inside[None, :]).reshape(-1))
+                    kv, fv = key.reshape(-1)[at], flat_of.reshape(-1)[at]
+                    for rank, q in enumerate(np.lexsort((fv, kv))[:C]):
+                        if not np.isfinite(kv[q]) or kv[q] > limit:      # (as the walk stops: a key of -inf ends the list too)
+                            break
+                        i, j = divmod(int(fv[q]), K)
+                        kids.append((slot, rank, i, j, j if inside[i] else i, float(kv[q])))
+                if not kids:
+                    break
+                # the children's poses: G[new] = G[i] T[i,j], or G[j] inv(T[i,j])
+                Tij = np.stack([Pz[i, j] for _, _, i, j, _, _ in kids])
+                fwd = np.array([new == j for _, _, _, j, new, _ in kids])
+                src = np.stack([hyps[slot][1][i if new == j else j] for slot, _, i, j, new, _ in kids])
+                Gn = _rule_products(src, np.where(fwd[:, None, None], Tij, _rule_inverses(Tij)))
+                costs = [hyps[slot][3] + k for slot, _, _, _, _, k in kids]
+                if weight != 0.0:
+                    votes = []                                                               # (child, p, a, b) in vote order
+                    for ci, (slot, _, i, j, new, _) in enumerate(kids):
+                        for p in np.flatnonzero(hyps[slot][0]):
+                            for a, b in ((int(p), new), (new, int(p))):
+                                if (a, b) != (i, j) and np.isfinite(key[a, b]) and key[a, b] <= vlimit:
+                                    votes.append((ci, int(p), a, b))
+                    total, n_votes = [0.0] * len(kids), [0] * len(kids)
+                    if votes:
+                        Tab = np.stack([Pz[a, b] for _, _, a, b in votes])
+                        vfwd = np.array([a == p for _, p, a, _ in votes])
+                        Gp = np.stack([hyps[kids[ci][0]][1][p] for ci, p, _, _ in votes])
+                        Q = _rule_products(Gp, np.where(vfwd[:, None, None], Tab, _rule_inverses(Tab)))
+                        D = Q[:, :3, :] - np.stack([Gn[ci, :3, :] for ci, _, _, _ in votes])
+                        Mn = np.stack([Mz[kids[ci][4]] for ci, _, _, _ in votes])
+                        qs = []
+                        for u in range(3):
+                            m = [_dot4(Mn[:, v, 0], D[:, u, 0], Mn[:, v, 1], D[:, u, 1], Mn[:, v, 2], D[:, u, 2], Mn[:, v, 3], D[:, u, 3])
+                                 for v in range(4)]
+                            qs.append(_dot4(D[:, u, 0], m[0], D[:, u, 1], m[1], D[:, u, 2], m[2], D[:, u, 3], m[3]))
+                        d = ((qs[0] + qs[1]) + qs[2]).tolist()
+                        for (ci, _, _, _), dv in zip(votes, d):
+                            total[ci] = total[ci] + dv
+                            n_votes[ci] += 1
+                    costs = [base + weight * (t / n if n else 0.0) for base, t, n in zip(costs, total, n_votes)]
+                costs = [inf if x != x else x for x in costs]
+                nxt, seen = [], set()
+                for ci in sorted(range(len(kids)), key=lambda ci: (costs[ci], kids[ci][0], kids[ci][1])):
+                    slot, _, i, j, new, _ = kids[ci]
+                    inside = hyps[slot][0].copy()
+                    inside[new] = True
+                    if inside.tobytes() in seen:
+                        continue
+                    seen.add(inside.tobytes())
+                    poses = hyps[slot][1].copy()
+                    poses[new] = Gn[ci]
+                    nxt.append((inside, poses, hyps[slot][2] + [(i, j, new)], costs[ci]))
+                    if len(nxt) == B:
+                        break
+                hyps = nxt
+            inside, poses, es, _ = hyps[0]
+            n_hyp[z] = len(hyps)
+            cost[z, :len(hyps)] = [h[3] for h in hyps]
+            worst = -inf
+            for e, (i, j, new) in enumerate(es):
+                edges[z, e] = (i, j, new)
+                edge_score[z, e] = S[z, i, j]
+                worst = max(worst, float(raw[i, j]))
+            n_edges[z] = len(es)
+            G[z, :c][inside] = poses[inside]
+            placed[z, :c] = inside
+            js = worst if joint_score is None or joint_score != joint_score else float(joint_score)
+            n = 0
+            if es:
+                for i in range(c):
+                    for j in range(c):
+                        if i != j and inside[i] and inside[j] and raw[i, j] <= js:
+                            joints[z, n] = (i, j)
+                            n += 1
+            n_joints[z] = n
+    return BeamRule(root, edges, edge_score, n_edges, G, placed, joints, n_joints, cost, n_hyp)
+
+
+def assemble_beam_batch(score, T, moment, count=None, beam=4, branch=4, weight=1.0, max_score=None, vote_score=None,
+                        joint_score=None):
+    """assemble_batch with a beam in place of the greedy walk, ONE launch for Z puzzles (ops.assemble_beam; beam_rule is its
+    numpy statement): `beam` hypotheses live side by side, each extended by its `branch` smallest entries, and a child is
+    charged its entry's score plus `weight` times how far the entries of the OTHER placed pieces put the new piece's boundary
+    from where this entry puts it (moment = boundary_moments(pieces, table.top_m)) - the cycles a spanning tree never asks.
+    weight = 1 is a definition: both terms are mean squared distances of the moved piece's k boundary points.  vote_score
+    (None: max_score) is the largest score an entry may have to vote.  -> BeamBatch: AssemblyBatch's fields for the cheapest
+    hypothesis, cost [Z,beam] float64 of all that lived (unused +inf) and n_hyp [Z] int32.  refine_assembly_batch and
+    evaluate_batch take it as they take an AssemblyBatch.  beam = branch = 1 is assemble_batch bit for bit.  Nothing waits for
+    the device."""
+    root, edges, edge_score, n_edges, G, placed, joints, n_joints, cost, n_hyp = ops.assemble_beam(
+        score, T, moment, count, beam, branch, weight, max_score, vote_score, joint_score)
+    with torch.no_grad():
+        placed = placed.bool()
+        index = torch.arange(placed.shape[1], dtype=torch.int32, device=placed.device)
+        movable = placed & (index[None, :] != root[:, None])
+    return BeamBatch(root, edges, edge_score, n_edges, G, placed, movable, joints, n_joints, cost, n_hyp)
 
 
 def _pair_fixed_head_blocks(seq, local, g):

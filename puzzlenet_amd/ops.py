@@ -403,6 +403,61 @@ def assemble_walk(score, T, count=None, max_score=None, joint_score=None):
     return root, edges, edge_score, n_edges, G, placed, joints, n_joints
 
 
+def assemble_beam_supported(K, beam=4, branch=4):
+    return bool(_lib.load().pzn_assemble_beam_supported(int(K), int(beam), int(branch)))
+
+
+def assemble_beam(score, T, moment, count=None, beam=4, branch=4, weight=1.0, max_score=None, vote_score=None, joint_score=None):
+    """The beam walk over Z pair tables, scored by the placed pieces' votes, in one launch (pzn_assemble_beam_f32; include/pzn.h
+    states the rule, assembly.beam_rule is its numpy statement): score, T, count, max_score and joint_score as assemble_walk takes
+    them, moment [Z,K,4,4] float64 (assembly.boundary_moments), beam and branch in 1 .. 8, weight (not NaN), vote_score (None:
+    max_score) -> assemble_walk's eight outputs for the cheapest hypothesis, then cost [Z,beam] float64 (slot order, unused
+    +inf) and n_hyp [Z] int32.  2 <= K <= 64 (PznUnsupported beyond).  Z = 0 launches nothing.  No autograd, nothing waits
+    for the device."""
+    for name, t, dt in (("score", score, torch.float32), ("T", T, torch.float32), ("moment", moment, torch.float64),
+                        ("count", count, torch.int32)):
+        if isinstance(t, torch.Tensor) and t.dtype != dt:      # (no silent conversion)
+            raise _lib.PznError(f"assemble_beam: {name} must be {dt}; got {t.dtype}")
+    score, T = _f32(score, "score"), _f32(T, "T")
+    if score.dim() != 3 or score.shape[1] != score.shape[2]:
+        raise _lib.PznError(f"assemble_beam: expected score[Z,K,K]; got {tuple(score.shape)}")
+    Z, K = score.shape[0], score.shape[1]
+    if tuple(T.shape) != (Z, K, K, 4, 4):
+        raise _lib.PznError(f"assemble_beam: expected T[{Z},{K},{K},4,4]; got {tuple(T.shape)}")
+    moment = _req(moment, torch.float64, "moment")
+    if tuple(moment.shape) != (Z, K, 4, 4):
+        raise _lib.PznError(f"assemble_beam: expected moment[{Z},{K},4,4]; got {tuple(moment.shape)}")
+    if count is not None:
+        count = _req(count, torch.int32, "count")
+        if tuple(count.shape) != (Z,):
+            raise _lib.PznError(f"assemble_beam: expected count[{Z}]; got {tuple(count.shape)}")
+    beam, branch, weight = int(beam), int(branch), float(weight)
+    max_score = float("inf") if max_score is None else float(max_score)
+    vote_score = float("nan") if vote_score is None else float(vote_score)
+    joint_score = float("nan") if joint_score is None else float(joint_score)
+    if max_score != max_score:
+        raise _lib.PznError("assemble_beam: max_score is NaN (None: no limit)")
+    if weight != weight:
+        raise _lib.PznError("assemble_beam: weight is NaN")
+    if not assemble_beam_supported(K, beam, branch):
+        raise _lib.PznUnsupported(f"assemble_beam: K = {K} pieces, beam = {beam}, branch = {branch} (2 <= K <= 64, 1 <= beam, "
+                                  "branch <= 8)")
+    dev = score.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    root, n_edges, n_joints, n_hyp = (torch.empty((Z,), **i32) for _ in range(4))
+    edges = torch.empty((Z, K - 1, 3), **i32)
+    edge_score = torch.empty((Z, K - 1), dtype=torch.float32, device=dev)
+    G = torch.empty((Z, K, 4, 4), dtype=torch.float64, device=dev)
+    placed = torch.empty((Z, K), dtype=torch.uint8, device=dev)
+    joints = torch.empty((Z, K * (K - 1), 2), **i32)
+    cost = torch.empty((Z, beam), dtype=torch.float64, device=dev)
+    with _on(dev):
+        _call("pzn_assemble_beam_f32", _p(score), _p(T), _p(moment), _p(count), beam, branch, weight, max_score, vote_score,
+              joint_score, Z, K, _p(root), _p(edges), _p(edge_score), _p(n_edges), _p(G), _p(placed), _p(joints), _p(n_joints),
+              _p(cost), _p(n_hyp), _stream())
+    return root, edges, edge_score, n_edges, G, placed, joints, n_joints, cost, n_hyp
+
+
 ProgressiveState = collections.namedtuple("ProgressiveState", "alive part G done n_edges edges edge_score")
 _PROGRESSIVE_TYPES = (torch.uint8, torch.int32, torch.float64, torch.uint8, torch.int32, torch.int32, torch.float32)
 

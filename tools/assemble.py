@@ -2,7 +2,7 @@
 assembled cloud.
 
     python tools/assemble.py --pieces pieces.npy [--ckpt model.ckpt] [--k 128] [--max-score S] [--out PREFIX] [--progressive]
-                             [--refine N] [--joint N] [--gt PREFIX_gt.npz]
+                             [--refine N] [--joint N] [--gt PREFIX_gt.npz] [--beam B] [--branch C] [--vote-weight W]
 
 pieces.npy holds [K, N, 3] float32 (N = the model's points per piece).  Prints the score table and the edges in
 placement order, writes PREFIX_G.npy ([K,4,4], each piece into the root's frame) and PREFIX_cloud.npy ([K,N,3]).
@@ -14,6 +14,9 @@ point-to-point ICP, at most N accepted steps, one launch per table or per round)
 --joint N (the greedy walk only): after the walk all placed poses are refined together over every joint - every pair of
 placed pieces that scores no worse than the walk's worst edge - by at most N sweeps of assembly.refine_assembly (one launch);
 PREFIX_G.npy and PREFIX_cloud.npy are then the refined ones, and with --gt the assembly is scored before and after.
+--beam B (the table walk only, with --branch C and --vote-weight W): the beam walk of assembly.assemble_beam_batch in place of the
+greedy one - B hypotheses, each extended by its C smallest entries, a child charged W times what the other placed pieces'
+entries say against its pose -; everything after the walk is the same.
 --gt PREFIX_gt.npz (written by tools/fracture.py beside the pieces): the assembly is scored against the truth - per piece the
 rotation error in degrees, the translation error and the mean squared distance of its points from where they belong, the share
 of pieces placed right (assembly.evaluate) and, for the greedy walk, the share of its edges between pieces that touch.
@@ -49,7 +52,12 @@ def main():
     ap.add_argument("--refine", type=int, default=0, help="ICP steps at most per pair pose on the picked boundary points (0: none)")
     ap.add_argument("--joint", type=int, default=0, help="sweeps at most of the joint refinement after the greedy walk (0: none)")
     ap.add_argument("--gt", default=None, help="PREFIX_gt.npz of tools/fracture.py: score the assembly against the truth")
+    ap.add_argument("--beam", type=int, default=0, help="B: the beam walk with B hypotheses in place of the greedy walk (1 .. 8; 0: greedy)")
+    ap.add_argument("--branch", type=int, default=4, help="C: with --beam, the candidates every hypothesis is extended by (1 .. 8)")
+    ap.add_argument("--vote-weight", type=float, default=1.0, help="W: with --beam, the weight of the placed pieces' votes in a child's cost")
     args = ap.parse_args()
+    if args.beam and (args.progressive or not (1 <= args.beam <= 8 and 1 <= args.branch <= 8) or args.vote_weight != args.vote_weight):
+        sys.exit("--beam B, --branch C: 1 .. 8, --vote-weight: a number, and not with --progressive")
     if args.refine < 0:
         sys.exit("--refine: 0 or a number of steps")
     if args.joint < 0 or (args.joint and args.progressive):
@@ -98,7 +106,16 @@ def main():
             report(assembly.evaluate(res.G, res.placed, gt["pose"], gt["rest"], root))
         return
     table = assembly.match_pairs(model, x, k=args.k, refine=args.refine)
-    result = assembly.assemble(table.score, table.T, max_score=args.max_score)
+    if args.beam:
+        moment = assembly.boundary_moments(x[None], table.top_m[None])
+        b = assembly.assemble_beam_batch(table.score[None], table.T[None], moment, beam=args.beam, branch=args.branch,
+                                         weight=args.vote_weight, max_score=args.max_score)
+        n = int(b.n_edges[0])
+        edges = [(i, j, s, new) for (i, j, new), s in zip(b.edges[0, :n].tolist(), b.edge_score[0, :n].tolist())]
+        result = assembly.Assembly(int(b.root[0]), edges, b.G[0].cpu().numpy(), b.placed[0].cpu().numpy())
+        print(f"beam walk: beam {args.beam}, branch {args.branch}, vote weight {args.vote_weight:g}; cost {float(b.cost[0, 0]):.6f}")
+    else:
+        result = assembly.assemble(table.score, table.T, max_score=args.max_score)
 
     score = table.score.cpu().numpy()
     print(f"score[fixed i, moved j] ({K} pieces of {N} points, k = {args.k}):")

@@ -8,6 +8,7 @@ event pair around every kernel launch, ops.ktimer_start / ktimer_stop), beside t
     python tools/bench_assembly.py --progressive [--reps 20] [--out profiles/assembly_progressive_k16.json]
     python tools/bench_assembly.py --refine [--reps 20] [--out profiles/assembly_refine_k16.json]
     python tools/bench_assembly.py --batch 64 [--reps 10] [--out profiles/assembly_batch.json]
+    python tools/bench_assembly.py --beam [--batch 64] [--reps 20] [--out profiles/assembly_beam.json]
 
 --progressive measures instead (a) ops.merge_resample against the unfused chain se3.transform_points -> cat ->
 farthest_point_sample -> index_points on the same inputs (Na = Nb = 1024 and 2048, M = 1 and 16; device time between two
@@ -32,6 +33,11 @@ over the per-puzzle functions match_pairs, assemble, refine_assembly, evaluate; 
 host wall time around a call that ends in a device synchronise, the two alternated in one process; beside them the per-launch
 device time of assemble_walk_kernel (the library's own event pair, ops.ktimer_start / ktimer_stop) and the part accuracy either
 path reports (closed-form weights: the number means nothing, it only has to be the same question).
+
+--beam [--batch Z] measures instead, on Z = 64 fractured puzzles of P = 8 and of P = 16 pieces (the same clouds and starts as
+--batch): the per-launch device time of assemble_beam_kernel (assembly.assemble_beam_batch, weight 1) at (beam, branch) = (1, 1),
+(4, 4) and (8, 8), of assemble_walk_kernel on the same tables (the library's own event pair, ops.ktimer_start / ktimer_stop), and
+the device time of the match_puzzles call that made the table - the cost the walk stands beside.
 
 Needs a GPU (there is no CPU path)."""
 import argparse
@@ -320,6 +326,63 @@ def batch(args):
         fh.write(json.dumps(result, indent=1) + "\n")
 
 
+def beam(args):
+    import numpy as np
+    from oracle import model_ref as mr
+    from puzzlenet_amd import assembly, datapipe, model5_b, ops
+    Z, M, CAND = args.batch or 64, 20000, 16
+    dev = torch.device("cuda:0")
+    model = model5_b.TouchedRegraster(mr.Cfg(num_points=N))
+    mr.fill_params(model)
+    model.to(dev)
+    result = {"tool": f"tools/bench_assembly.py --beam --batch {Z}", "device": torch.cuda.get_device_name(0), "dtype": "float32", "Z": Z,
+              "N": N, "k": TOP, "M": M, "weight": 1.0,
+              "timing": "kernels: the library's own event pair per launch (ops.ktimer_*), us; match_puzzles: device time between two "
+                        "events around one call, ms"}
+
+    def kernel_us(fn, name):
+        fn()
+        ops.ktimer_start()
+        for _ in range(args.reps):
+            fn()
+        torch.cuda.synchronize()
+        rows = ops.ktimer_stop()
+        hit = [v for k_, v in rows.items() if name in k_]
+        if len(hit) != 1 or hit[0][0] != args.reps:
+            sys.exit(f"kernel timer: expected {args.reps} launches of {name} in one row, got {rows}")
+        return 1e3 * hit[0][1] / hit[0][0]
+
+    for P in (8, 16):
+        rng = np.random.RandomState(16)
+        raw = (rng.rand(Z, M, 3) - 0.5).astype(np.float32)
+        draws = datapipe.fracture_draws(rng, torch.Generator().manual_seed(16), Z, P, CAND, 0.8)
+        to = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+        g = torch.Generator().manual_seed(17)
+        s1, s2 = torch.randint(0, N, (Z, P), generator=g), torch.randint(0, 512, (Z, P), generator=g)
+        with torch.no_grad():
+            f = datapipe.fracture(to(raw), *(to(d) for d in draws), n=N, k=TOP)
+            match = lambda: assembly.match_puzzles(model, f.pieces, k=TOP, start=(s1, s2))
+            for _ in range(args.warmup):
+                table = match()
+            match_ms = sorted(_device_ms(match, 1) for _ in range(args.reps))
+            moment = assembly.boundary_moments(f.pieces, table.top_m)
+            row = {"P": P, "match_puzzles_device_ms": _spread(match_ms),
+                   "assemble_walk_kernel_us": kernel_us(lambda: assembly.assemble_batch(table.score, table.T), "assemble_walk_kernel")}
+            greedy = assembly.assemble_batch(table.score, table.T)
+            for B, C in ((1, 1), (4, 4), (8, 8)):
+                run = lambda: assembly.assemble_beam_batch(table.score, table.T, moment, beam=B, branch=C)
+                us = kernel_us(run, "assemble_beam_kernel")
+                same = float((run().edges == greedy.edges).all(dim=2).all(dim=1).double().mean().cpu())
+                row[f"assemble_beam_kernel_us_B{B}_C{C}"] = us
+                row[f"share_of_puzzles_with_the_greedy_tree_B{B}_C{C}"] = same
+            row["beam_8_8_over_match_puzzles"] = row["assemble_beam_kernel_us_B8_C8"] * 1e-3 / row["match_puzzles_device_ms"]["median_ms"]
+        print(json.dumps(row))
+        result[f"P{P}"] = row
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write(json.dumps(result, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -327,16 +390,20 @@ def main():
     ap.add_argument("--progressive", action="store_true")
     ap.add_argument("--refine", action="store_true")
     ap.add_argument("--batch", type=int, default=0, help="Z: time the batched chain on Z fractured puzzles against the per-puzzle loop")
+    ap.add_argument("--beam", action="store_true", help="time the beam walk's launch beside the greedy walk's and match_puzzles")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
         name = "assembly_progressive_k16.json" if args.progressive else ("assembly_refine_k16.json" if args.refine else "assembly_k16.json")
         name = "assembly_batch.json" if args.batch else name
+        name = "assembly_beam.json" if args.beam else name
         args.out = os.path.join(ROOT, "profiles", name)
     if args.reps < (5 if args.batch else 20):
         sys.exit("--reps: at least 20 timed repetitions each (--batch, whose loop side takes seconds a repetition: at least 5)")
     if not torch.cuda.is_available():
         sys.exit("tools/bench_assembly.py needs a GPU: puzzlenet_amd has no CPU path")
+    if args.beam:
+        return beam(args)
     if args.batch:
         return batch(args)
     if args.progressive:

@@ -2,7 +2,7 @@
 
     python tools/eval_assembly.py [--batch 64] [--pieces 8] [--m 20000] [--k 128] [--candidates 16] [--mag 0.8] [--seed 0]
                                   [--curvature 2.0] [--ckpt model.ckpt] [--refine N] [--joint N] [--max-score S]
-                                  [--progressive] [--time R] [--json out.json]
+                                  [--progressive] [--time R] [--json out.json] [--beam B] [--branch C] [--vote-weight W]
 
 B seeded uniform clouds of M points are each cut into P pieces that belong together (datapipe.fracture, along curved surfaces
 with principal curvatures up to --curvature, along planes with --curvature 0; every piece sampled to
@@ -11,7 +11,9 @@ match_puzzles (every piece encoded once, the encoders on full batches; --refine 
 boundaries by at most N ICP steps), assemble_batch (the greedy walk and the joint list of all puzzles, one launch), with --joint N
 refine_assembly_batch (all placed poses of every puzzle refined together over every joint, at most N sweeps, one launch), and
 evaluate_batch against the fracture's truth.  Nothing waits for the device until the metrics - a few numbers per puzzle - are
-downloaded once.  Prints the means over the valid fractures: part accuracy, edge precision, and over the placed pieces other
+downloaded once.  --beam B (with --branch C, --vote-weight W) also runs the beam walk scored by the placed pieces' votes
+(boundary_moments and assemble_beam_batch, one launch) on the same table and prints its means beside the greedy walk's, with
+--joint both before and after the joint refinement of its own result.  Prints the means over the valid fractures: part accuracy, edge precision, and over the placed pieces other
 than the root the rotation error in degrees, the translation error and the mean squared distance; with --joint both before and
 after the joint refinement.  --progressive reports the same means for the progressive walk (assemble_progressive_batch: all
 puzzles in lockstep, P - 1 rounds, every round one choice launch, one merge launch, one encoder batch and two blocked pair blocks)
@@ -64,11 +66,16 @@ def main():
     ap.add_argument("--progressive", action="store_true", help="also the progressive walk of the whole batch, in lockstep")
     ap.add_argument("--time", type=int, default=0, help="with --progressive: repeats of the timed batched walk and per-puzzle loop")
     ap.add_argument("--json", default=None, help="with --time: write the timings and launch counts to this file")
+    ap.add_argument("--beam", type=int, default=0, help="B: also the beam walk with B hypotheses (1 .. 8; 0: the greedy walk alone)")
+    ap.add_argument("--branch", type=int, default=4, help="C: with --beam, the candidates every hypothesis is extended by (1 .. 8)")
+    ap.add_argument("--vote-weight", type=float, default=1.0, help="W: with --beam, the weight of the placed pieces' votes in a child's cost")
     args = ap.parse_args()
     if args.refine < 0 or args.joint < 0:
         sys.exit("--refine, --joint: 0 or a number of steps / sweeps")
     if args.time < 0 or (args.time and not args.progressive) or (args.json and not args.time):
         sys.exit("--time R >= 0 goes with --progressive, --json with --time")
+    if args.beam and not (1 <= args.beam <= 8 and 1 <= args.branch <= 8 and args.vote_weight == args.vote_weight):
+        sys.exit("--beam B, --branch C: 1 .. 8; --vote-weight: a number")
     if not torch.cuda.is_available():
         sys.exit("tools/eval_assembly.py needs a GPU: puzzlenet_amd has no CPU path")
     from puzzlenet_amd import assembly, checkpoint, datapipe, model5_b
@@ -110,19 +117,36 @@ def main():
             pr = walk()
             rows.append(metrics(assembly.evaluate_batch(pr.G, pr.placed, f.pose, f.rest, pr.root, pr.edges, pr.n_edges, f.mates), pr, f.ok))
             rows.append(torch.stack((pr.n_edges.double().mean(),)))
+        if args.beam:
+            moment = assembly.boundary_moments(f.pieces, table.top_m)
+            bm = assembly.assemble_beam_batch(table.score, table.T, moment, beam=args.beam, branch=args.branch, weight=args.vote_weight,
+                                              max_score=args.max_score)
+            rows.append(metrics(assembly.evaluate_batch(bm.G, bm.placed, f.pose, f.rest, bm.root, bm.edges, bm.n_edges, f.mates), bm, f.ok))
+            if args.joint:
+                bj = assembly.refine_assembly_batch(f.pieces, table, bm, sweeps=args.joint)
+                rows.append(metrics(assembly.evaluate_batch(bj.G, bm.placed, f.pose, f.rest, bm.root, bm.edges, bm.n_edges, f.mates),
+                                    bm, f.ok))
+            same = (bm.edges == asm.edges).all(dim=2).all(dim=1).double().mean()
+            rows.append(torch.stack((bm.n_edges.double().mean(), same)))
         head = torch.stack((f.ok.double().sum(), asm.n_joints.double().mean(), asm.n_edges.double().mean()))
         host = torch.cat([head, extra] + rows).cpu().tolist()                       # the one download
     print(f"{B} clouds of {M} points into {P} pieces of {N}: {int(host[0])} valid fractures; per puzzle {host[2]:.2f} edges, "
           f"{host[1]:.1f} joints")
     names = ("part accuracy", "edge precision", "rotation (deg)", "translation", "msd", "share placed")
     at_p = 18 if args.joint else 12
+    at_b = at_p + (7 if args.progressive else 0)
+    beam_label = f"beam walk (beam {args.beam}, branch {args.branch}, vote weight {args.vote_weight:g})"
     for label, at in (("greedy walk", 6),) + ((("after the joint refinement", 12),) if args.joint else ()) \
-            + ((("progressive walk", at_p),) if args.progressive else ()):
+            + ((("progressive walk", at_p),) if args.progressive else ()) + (((beam_label, at_b),) if args.beam else ()) \
+            + ((("beam walk after the joint refinement", at_b + 6),) if args.beam and args.joint else ()):
         print(f"{label}: " + ", ".join(f"{n} {v:.6g}" for n, v in zip(names, host[at:at + 6])))
     if args.joint:
         print(f"joint refinement: mean summed score {host[3]:.6f} -> {host[4]:.6f}, {host[5]:.1f} sweeps")
     if args.progressive:
         print(f"progressive walk: per puzzle {host[at_p + 6]:.2f} edges in {P - 1} lockstep rounds")
+    if args.beam:
+        at = at_b + (12 if args.joint else 6)
+        print(f"beam walk: per puzzle {host[at]:.2f} edges; the greedy walk's tree in {100 * host[at + 1]:.1f} % of the puzzles")
     if args.time:
         time_progressive(args, model, f, (s1, s2), walk)
 
