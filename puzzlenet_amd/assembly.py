@@ -1,62 +1,65 @@
 """Multi-piece assembly: match every ordered pair of K pieces with each piece encoded ONCE, then
-put the pieces together greedily by the distance between the matched boundaries (the reference's README describes this
-end use and ships no code for it).
+put the pieces together by the distance between the matched boundaries (the reference's README describes this end use and
+ships no code for it).  Every device function takes Z puzzles at once; the per-puzzle functions are the same code at Z = 1.
 
 In eval mode nothing in predict5 mixes batch rows (BatchNorm1d(num_points) uses its running statistics, everything else
-is per row), so the all-pairs table factors exactly:
+is per row), so the all-pairs table factors exactly.
 
+Per piece (encode_pieces -> PieceCodes, one call over all Z K pieces, so the encoders see full batches):
   * Encoder and Encoder2 run once per piece (2 K encoder rows instead of 2 K (K - 1)) on ONE sampling / neighbour plan per
     piece: FPS and kNN depend on coordinates only.
   * Pose head: the first tfMLP layer on cat([ffpc_i, fmrpc_j]) is U_i + V_j with U = ffpc W1[:, :1024]^T and
-    V = fmrpc W1[:, 1024:]^T + b1; the other four layers run on the K^2 rows relu(U_i + V_j).
+    V = fmrpc W1[:, 1024:]^T + b1.
   * Moved-side boundary head: both "global" vectors are the max over the MOVED piece's local features (TouchedRegraster.moved_branch,
-    the reference's line 741), so de_mrpcb depends on j only: K rows.
+    the reference's line 741), so de_mrpcb and its top-k depend on j only: K rows.
+
+Per pair (pair_block_batch -> PairBlock, the one statement of these stages, block-diagonal over the puzzles; pair_block is
+its Z = 1 case):
+  * the other four pose-head layers on the rows relu(U_i + V_j), then se3.exp;
   * Fixed-side boundary head: de_fpcb[i, j] = MLPFpcb(cat([g_j, local_i])), the only per-point work that depends on the
-    pair: one launch of ops.pair_head (csrc/pointmlp.hip, pair_head_fwd_kernel), which computes the first-layer product
-    of a tile once and loops over the moved pieces in registers.
+    pair: one launch of ops.pair_head_blocks (csrc/pointmlp.hip, pair_head_fwd_kernel), which computes the first-layer
+    product of a tile once and loops over the moved pieces in registers (_pair_fixed_head, with the fallback for other shapes);
+  * softmax, top-k, one gather per side, then the transform and the chamfer: the score of a pair;
+  * refine = N > 0 instead of those two: every pair pose moves to where the two picked boundaries meet, symmetric
+    point-to-point ICP on the k picked points of each side, all pairs in ONE launch (_refine_gathered: ops.icp_refine,
+    csrc/icprefine.hip; refine_pairs is the same on boundaries the caller names), at most N accepted steps from the network's
+    pose.  It lowers exactly the quantity the walks rank by, so T and score are the refined ones (score never above the
+    unrefined chamfer of the same rows); twist stays the network's output (the project has no SE(3) logarithm).  refine = 0
+    is the default, and not one launch more.
 
-match_pairs is encode_pieces (everything that depends on one piece) and pair_block (the rectangular [Kf, Km] block) plus the
-diagonal fill.  ProgressiveAssembler uses the same two for what the greedy walk leaves out - it never looks at a merged
-shape -: every round it takes the smallest score, merges the two parts on the device (ops.merge_resample: the moved part
-under its pose, the union resampled to N points by farthest point sampling with the matched boundary points left out, the
-origin of every point kept), encodes the merged part alone - its sampling plan is read off its pick order, no FPS - and
-computes only its row and its column of the table again.
+The table: match_puzzles is one encode_pieces, one square pair_block_batch and the diagonal fill (_match_puzzles, _table);
+match_pairs is match_puzzles on pieces[None].
 
-refine=N (pair_block, match_pairs, ProgressiveAssembler, assemble_progressive; default 0 = none, and not one launch more)
-lets every pair pose move to where the two picked boundaries meet: refine_pairs runs symmetric point-to-point ICP on the k
-picked points of each side, all pairs in ONE launch (ops.icp_refine, csrc/icprefine.hip), at most N accepted steps from the
-network's pose.  It lowers exactly the quantity the walks rank by, so T and score of the block or table are the refined ones
-(score never above the unrefined chamfer of the same rows); twist stays the network's output (the project has no SE(3)
-logarithm), every other field is untouched.
+The walks over a table:
+  * assemble: greedy, on the host in float64 - the reference the device walks are tested against, as evaluate is for
+    evaluate_batch.
+  * assemble_batch: the greedy walk and the joint list of Z puzzles in one launch (ops.assemble_walk, csrc/assemblewalk.hip;
+    walk_rule is its numpy statement).
+  * assemble_beam_batch: a beam in place of the greedy walk, which takes the smallest entry every round and never checks it.
+    `beam` hypotheses live side by side, each extended by its `branch` smallest entries, and a child pays its entry's score
+    plus `weight` times what the entries of the other placed pieces say against its pose - how far apart, in the mean square,
+    the two predictions put the new piece's picked boundary points, read off one 4x4 second-moment matrix per piece
+    (boundary_moments) -: the cycles a spanning tree never asks.  One launch (ops.assemble_beam, csrc/assemblebeam.hip;
+    beam_rule is its numpy statement).
+  * refine_assembly / refine_assembly_batch: the step after a walk.  The walk composes pair poses along a spanning tree, so a
+    piece's pose carries the summed error of the edges between it and the root, and every accepted joint that is no tree edge
+    is never asked.  The placed assembly is a pose graph - every ordered pair of placed pieces whose table score is no larger
+    than the worst tree edge's is a joint - and all pieces but the root move so that the joints close together:
+    block-coordinate descent that can only lower the summed score, one launch (ops.joint_refine, csrc/jointrefine.hip).
+    refine_assembly chooses the joints on the host and gathers only their sets; the batch form reads them from the walk's
+    output on the device.
+  * evaluate / evaluate_batch: the score of an assembly against datapipe.fracture's ground truth.
 
-refine_assembly(pieces, table, asm) is the step after the greedy walk: the walk composes pair poses along a spanning tree, so a
-piece's pose carries the summed error of the edges between it and the root, and every accepted joint that is no tree edge is
-never asked.  refine_assembly treats the placed assembly as a pose graph - every ordered pair of placed pieces whose table
-score is no larger than the worst tree edge's is a joint - and moves all pieces but the root so that the joints close
-together: block-coordinate descent that can only lower the summed score, one launch (ops.joint_refine, csrc/jointrefine.hip).
-assemble, match_pairs, refine_pairs and the progressive path do not change.
-
-A batch of Z puzzles (datapipe.fracture returns one) goes through the same chain without the host in between: match_puzzles (one
-encode_pieces over the Z P pieces, so the encoders see full batches), assemble_batch (the greedy walk and the joint list of all
-Z puzzles in one launch, ops.assemble_walk, csrc/assemblewalk.hip; walk_rule is its numpy statement), refine_assembly_batch (the
-one ops.joint_refine launch for all of them) and evaluate_batch (evaluate in float64 torch on the device).  The per-puzzle
-functions are not touched.
-
-assemble_beam_batch stands beside assemble_batch: a beam in place of the greedy walk, which takes the smallest entry every round
-and never checks it.  `beam` hypotheses live side by side, each extended by its `branch` smallest entries, and a child pays its
-entry's score plus `weight` times what the entries of the other placed pieces say against its pose - how far apart, in the mean
-square, the two predictions put the new piece's picked boundary points, read off one 4x4 second-moment matrix per piece
-(boundary_moments) -: the cycles a spanning tree never asks.  One launch for Z puzzles (ops.assemble_beam, csrc/assemblebeam.hip;
-beam_rule is its numpy statement); its result feeds refine_assembly_batch and evaluate_batch as assemble_batch's does.
-
-The progressive walk takes a batch the same way: pair_block_batch is pair_block stage by stage with every stage ONCE for all Z
-puzzles (the pair head in block-diagonal form, ops.pair_head_blocks; match_puzzles is one call of it), and ProgressiveBatch /
-assemble_progressive_batch walk the Z puzzles in lockstep, P - 1 rounds with nothing waiting for the device: every round one
-ops.progressive_round launch chooses all Z merges and books them in a float64 ledger on the device (csrc/progressive.hip;
-progressive_round_rule is its numpy statement; slots die instead of being compacted, so shapes never change), one
-ops.merge_resample launch merges, one encode_pieces call encodes the Z merged parts, and two pair_block_batch calls give the new
-row and column of all Z tables.  Not done there: dead slots are still paired, stopped puzzles are still encoded, and a progressive
-part is not refined jointly.
+The progressive walks do what the walks above leave out - those never look at a merged shape -: every round the pair of the
+smallest score is merged on the device (ops.merge_resample: the moved part under its pose, the union resampled to N points by
+farthest point sampling with the matched boundary points left out, the origin of every point kept), the merged part is
+encoded alone - its sampling plan is read off its pick order, no FPS - and only its row and its column of the table are
+computed again (two pair_block calls).  ProgressiveAssembler walks one puzzle with the choice and the ledger on the host
+(MergeLedger) and compacts its state; ProgressiveBatch walks Z puzzles in lockstep, P - 1 rounds with nothing waiting for the
+device: one ops.progressive_round launch chooses all Z merges and books them in a float64 ledger on the device
+(csrc/progressive.hip; progressive_round_rule is its numpy statement; slots die instead of being compacted, so shapes never
+change), one ops.merge_resample launch, one encode_pieces call and two pair_block_batch calls.  Not done there: dead slots
+are still paired, stopped puzzles are still encoded, and a progressive part is not refined jointly.
 
 Inference only: eval mode, torch.no_grad(), fp32, one GPU.  Out of scope: any training on merged parts or on more than two
 pieces, a beam or several merges per round of the progressive walk, undoing a merge, and more than one GPU.
@@ -94,22 +97,34 @@ def _encode(enc, pieces, plan):
 
 
 def _pair_fixed_head(seq, local, g):
-    """MLPFpcb over every (fixed i, moved j) pair -> [K,K,N,2]: one pair_head launch, or (shapes it does not take) one
-    boundary-head call per moved piece with its global vector expanded over the fixed pieces."""
+    """MLPFpcb over every (fixed i, moved j) pair of every puzzle: local [Z,Kf,N,64], g [Z,Km,64] -> [Z,Kf,Km,N,2] in one
+    pair_head_blocks launch, or (shapes it does not take) one boundary-head call per puzzle and moved piece with its global
+    vector expanded over the fixed pieces."""
     mods = list(seq)
-    K, N = local.shape[0], local.shape[1]
-    if len(mods) == 5 and ops.pair_head_supported(N, mods[2].out_features, mods[4].out_features):
+    Z, Kf, N = local.shape[0], local.shape[1], local.shape[2]
+    if len(mods) == 5 and ops.pair_head_blocks_supported(N, mods[2].out_features, mods[4].out_features):
         l1, l2, l3 = mods[0], mods[2], mods[4]
-        return ops.pair_head(local, g, l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias)
-    cols = [run_seq_cat_global(seq, local, g[j:j + 1].expand(K, -1).reshape(K, 1, -1).contiguous()) for j in range(g.shape[0])]
-    return torch.stack(cols, dim=1)
+        return ops.pair_head_blocks(local, g, l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias)
+    return torch.stack([torch.stack([run_seq_cat_global(seq, local[z], g[z, j:j + 1].expand(Kf, -1).reshape(Kf, 1, -1).contiguous())
+                                     for j in range(g.shape[1])], dim=1) for z in range(Z)], dim=0)
+
+
+def _on_gpu(who, **tensors):
+    for name, t in tensors.items():
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.PznError(f"{who}: {name} must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
+
+
+def _clouds(who, lead, **tensors):
+    """Every tensor is float32 [*lead, N, 3] on the GPU (lead names the leading dimensions, "K" or "Z,P")."""
+    _on_gpu(who, **tensors)
+    for name, t in tensors.items():
+        if t.dim() != lead.count(",") + 3 or t.shape[-1] != 3 or t.dtype != torch.float32:
+            raise _lib.PznError(f"{who} expects float32 {name}[{lead},N,3]; got {t.dtype} {tuple(t.shape)}")
 
 
 def _check_pieces(model, pieces, k, who, least=1):
-    if not isinstance(pieces, torch.Tensor) or not pieces.is_cuda:
-        raise _lib.PznError(f"{who}: pieces must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
-    if pieces.dim() != 3 or pieces.shape[2] != 3 or pieces.dtype != torch.float32:
-        raise _lib.PznError(f"{who} expects float32 pieces[K,N,3]; got {pieces.dtype} {tuple(pieces.shape)}")
+    _clouds(who, "K", pieces=pieces)
     K, N, _ = pieces.shape
     if K < least or N != model.num_points:
         raise _lib.PznError(f"{who}: K = {K} pieces (>= {least}) of N = {N} points (the model takes {model.num_points})")
@@ -174,12 +189,15 @@ def encode_pieces(model, pieces, k=128, start=None, plan=None, _who="encode_piec
 
 
 def _refine_gathered(Bf, Bm, T, iters):
-    """refine_pairs on boundaries that are gathered already: Bf [Kf Km,k,3] per pair, Bm [Km,k,3] per moved piece (served to
-    every fixed piece through b_of), T [Kf,Km,4,4] -> Refined.  One launch."""
-    Kf, Km = T.shape[0], T.shape[1]
-    b_of = torch.arange(Km, dtype=torch.long, device=T.device).repeat(Kf)              # problem i Km + j reads Bm[j]
-    Tr, score, score0, used = ops.icp_refine(Bf, Bm, T.reshape(Kf * Km, 4, 4), iters, b_of=b_of)
-    return Refined(Tr.view(Kf, Km, 4, 4), score.view(Kf, Km), score0.view(Kf, Km), used.view(Kf, Km))
+    """refine_pairs on boundaries that are gathered already, for any leading puzzle dimensions of T [...,Kf,Km,4,4]: Bf
+    [Z Kf Km,k,3] per pair, Bm [Z Km,k,3] per moved piece (served to every fixed piece of its puzzle: problem (z, i, j) reads
+    Bm[z Km + j]) -> Refined with T's leading dimensions.  One launch."""
+    Kf, Km = T.shape[-4], T.shape[-3]
+    Z = T.numel() // (Kf * Km * 16)
+    b_of = torch.arange(Z * Km, dtype=torch.long, device=T.device).view(Z, 1, Km).expand(Z, Kf, Km).reshape(-1)
+    Tr, score, score0, used = ops.icp_refine(Bf, Bm, T.reshape(Z * Kf * Km, 4, 4), iters, b_of=b_of)
+    lead = T.shape[:-2]
+    return Refined(Tr.view(*lead, 4, 4), score.view(lead), score0.view(lead), used.view(lead))
 
 
 def refine_pairs(pieces_f, top_f, pieces_m, top_m, T, iters=30):
@@ -189,9 +207,7 @@ def refine_pairs(pieces_f, top_f, pieces_m, top_m, T, iters=30):
     -> Refined(T [Kf,Km,4,4], score [Kf,Km], score0 [Kf,Km], iters_used [Kf,Km] int32).  score is the table's quantity (mean
     + mean of the squared nearest-neighbour distances) under the returned pose and never above score0, the same under T.
     All Kf Km problems run in one launch (ops.icp_refine); nothing waits for the device."""
-    for name, t in (("pieces_f", pieces_f), ("pieces_m", pieces_m), ("T", T), ("top_f", top_f), ("top_m", top_m)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _lib.PznError(f"refine_pairs: {name} must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
+    _on_gpu("refine_pairs", pieces_f=pieces_f, pieces_m=pieces_m, T=T, top_f=top_f, top_m=top_m)
     if pieces_f.dim() != 3 or pieces_m.dim() != 3 or pieces_f.shape[2] != 3 or pieces_m.shape[2] != 3:
         raise _lib.PznError(f"refine_pairs expects pieces_f[Kf,N,3], pieces_m[Km,N,3]; got {tuple(pieces_f.shape)}, "
                             f"{tuple(pieces_m.shape)}")
@@ -217,32 +233,23 @@ def pair_block(model, pieces_f, codes_f, pieces_m, codes_m, k=128, refine=0):
     role, from their PieceCodes -> PairBlock(twist [Kf,Km,6], T [Kf,Km,4,4], de_fpcb [Kf,Km,2,N], top_f [Kf,Km,k],
     score [Kf,Km]); entries as match_pairs documents them (no diagonal is masked here).  refine > 0: T and score are those
     of refine_pairs(..., iters=refine) from the network's pose, one launch in place of the transform and the chamfer; twist
-    stays the network's output."""
+    stays the network's output.  It is pair_block_batch for one puzzle."""
     refine = _check_refine(refine, "pair_block")
-    Kf, N = pieces_f.shape[0], pieces_f.shape[1]
-    Km = pieces_m.shape[0]
-    k = int(k)
-    with torch.no_grad():
-        # pose head: the four layers after the split first one run on the Kf Km rows relu(U_i + V_j)
-        hidden = torch.relu(codes_f.U[:, None] + codes_m.V[None]).reshape(Kf * Km, -1)
-        twist = run_seq(list(model.tfMLP)[2:], hidden).view(Kf, Km, 6)
-        T = se3.exp(twist)
+    one = lambda codes: PieceCodes(*(f[None] for f in codes))
+    blk = pair_block_batch(model, pieces_f[None], one(codes_f), pieces_m[None], one(codes_m), k, refine)
+    return PairBlock(*(f[0] for f in blk))
 
-        y_f = _pair_fixed_head(model.MLPFpcb, codes_f.local_f, codes_m.g_max)                # [Kf,Km,N,2]
-        de_fpcb = y_f.permute(0, 1, 3, 2)
 
-        # the k points of largest class-1 probability (softmax over two logits) and the boundary-to-boundary distance
-        p_f = torch.softmax(y_f, dim=-1)[..., 1].reshape(Kf * Km, N)
-        top_f = ops.topk_rows(p_f, k).view(Kf, Km, k)
-        Bf = ops.index_points(pieces_f, top_f.reshape(Kf, Km * k)).view(Kf * Km, k, 3)       # pieces_f[i][top_f[i, j]]
-        Bm = ops.index_points(pieces_m, codes_m.top_m)                                       # pieces_m[j][top_m[j]]
-        if refine > 0:
-            r = _refine_gathered(Bf, Bm, T, refine)
-            return PairBlock(twist, r.T, de_fpcb, top_f, r.score)
-        Bm = se3.transform_points(T.reshape(Kf * Km, 4, 4), Bm.unsqueeze(0).expand(Kf, -1, -1, -1).reshape(Kf * Km, k, 3))
-        d1, d2 = ops.chamfer(Bf, Bm)
-        score = (d1.mean(dim=1) + d2.mean(dim=1)).view(Kf, Km)
-    return PairBlock(twist, T, de_fpcb, top_f, score)
+def _diagonal(pieces):
+    """The [K,K] bool diagonal for pieces [...,K,N,3]."""
+    return torch.eye(pieces.shape[-3], dtype=torch.bool, device=pieces.device)
+
+
+def _table(codes, blk, mask=None):
+    """The PairTable of pieces with the PieceCodes `codes` and their square PairBlock; score is +inf where mask (None: blk's
+    score is masked already)."""
+    score = blk.score if mask is None else blk.score.masked_fill(mask, float("inf"))
+    return PairTable(blk.twist, blk.T, blk.de_fpcb, codes.de_mrpcb, blk.top_f, codes.top_m, score, codes.x2)
 
 
 def match_pairs(model, pieces, k=128, start=None, refine=0):
@@ -261,19 +268,17 @@ def match_pairs(model, pieces, k=128, start=None, refine=0):
     start = (s1[K], s2[K]): int64 FPS start indices of the two set-abstraction levels; None draws them with
     torch.randint(0, N, (K,)) then torch.randint(0, 512, (K,)) from model.fps_generator (the global generator when that
     is None).  Any K is taken: the encoders run on 64 pieces at a time.  Nothing here waits for the device.
-    It is encode_pieces, the square pair_block and the diagonal fill.
+    It is match_puzzles for the one puzzle pieces[None]: encode_pieces, the square pair block and the diagonal fill.
 
     refine = N > 0: T and score are refined on the picked rows (refine_pairs, at most N accepted ICP steps from se3.exp(twist),
     one launch for the table; the diagonal is refined like any pair and then masked); twist stays the network's output, so
     T is no longer se3.exp(twist); every other field is what refine = 0 gives, bit for bit."""
     refine = _check_refine(refine, "match_pairs")
-    codes = encode_pieces(model, pieces, k, start, _who="match_pairs", _least=2)
-    pieces = pieces.contiguous()
-    blk = pair_block(model, pieces, codes, pieces, codes, k, refine)
-    K = pieces.shape[0]
-    with torch.no_grad():
-        score = blk.score.masked_fill(torch.eye(K, dtype=torch.bool, device=pieces.device), float("inf"))
-    return PairTable(blk.twist, blk.T, blk.de_fpcb, codes.de_mrpcb, blk.top_f, codes.top_m, score, codes.x2)
+    _check_pieces(model, pieces, k, "match_pairs", 2)
+    if start is not None:
+        start = tuple(torch.as_tensor(s, dtype=torch.long)[None] for s in start)
+    pieces, codes, blk = _match_puzzles(model, pieces[None], k, start, refine, "match_pairs")
+    return PairTable(*(f[0] for f in _table(codes, blk, _diagonal(pieces))))
 
 
 def _host(a):
@@ -350,10 +355,7 @@ def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None):
     piece has one.  Joint (i, j) pairs pieces[i][table.top_f[i,j]] with pieces[j][table.top_m[j]] (one set per moved piece,
     served to all its joints).  Every piece that is placed and not the root may move; sweeps = 0 returns asm.G.
     One download (the scores the joints are chosen from), one gather and one launch."""
-    if not isinstance(pieces, torch.Tensor) or not pieces.is_cuda:
-        raise _lib.PznError("refine_assembly: pieces must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
-    if pieces.dim() != 3 or pieces.shape[2] != 3 or pieces.dtype != torch.float32:
-        raise _lib.PznError(f"refine_assembly expects float32 pieces[K,N,3]; got {pieces.dtype} {tuple(pieces.shape)}")
+    _clouds("refine_assembly", "K", pieces=pieces)
     K, N, _ = pieces.shape
     G0 = np.asarray(asm.G, dtype=np.float64)
     placed = np.asarray(asm.placed, dtype=bool)
@@ -393,8 +395,7 @@ def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None):
 
 def apply(pieces, G):
     """The pieces [K,N,3] (on the GPU) in the root's frame: G[k] applied to piece k."""
-    if not isinstance(pieces, torch.Tensor) or not pieces.is_cuda:
-        raise _lib.PznError("apply: pieces must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
+    _on_gpu("apply", pieces=pieces)
     g = torch.as_tensor(np.asarray(G) if not isinstance(G, torch.Tensor) else G).to(pieces.device, torch.float32)
     return se3.transform_points(g.contiguous(), pieces.contiguous())
 
@@ -489,6 +490,29 @@ def _rule_inverse(T):
     return out
 
 
+def _as_np(a, dt):
+    return (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(dt)
+
+
+def _rule_outputs(Z, K):
+    """The walk's eight outputs as the kernels leave a puzzle that makes no edge -> WalkRule of numpy arrays."""
+    return WalkRule(np.full(Z, -1, dtype=np.int32), np.full((Z, K - 1, 3), -1, dtype=np.int32),
+                    np.full((Z, K - 1), np.inf, dtype=np.float32), np.zeros(Z, dtype=np.int32), np.tile(np.eye(4), (Z, K, 1, 1)),
+                    np.zeros((Z, K), dtype=np.uint8), np.full((Z, K * (K - 1), 2), -1, dtype=np.int32), np.zeros(Z, dtype=np.int32))
+
+
+def _rule_joints(inside, raw, limit, out):
+    """The joints of a finished walk, row-major: every (i, j), i != j, both inside, with raw[i][j] <= limit, written to the
+    first rows of out [K (K - 1),2] -> their number."""
+    n = 0
+    for i in range(len(inside)):
+        for j in range(len(inside)):
+            if i != j and inside[i] and inside[j] and raw[i][j] <= limit:
+                out[n] = (i, j)
+                n += 1
+    return n
+
+
 def walk_rule(score, T, count=None, max_score=None, joint_score=None):
     """The numpy statement of ops.assemble_walk (csrc/assemblewalk.hip, the rule in include/pzn.h), which is held to it bit for
     bit, G included: assemble() and the joint selection of refine_assembly() for Z puzzles, on the host.  score [Z,K,K] (read as
@@ -500,22 +524,14 @@ def walk_rule(score, T, count=None, max_score=None, joint_score=None):
     i, j < count[z] exist.  The root is the row of the smallest key; a round takes the smallest key among the ordered pairs with
     exactly one end placed and stops at a key that is not finite or above max_score.  Poses are composed in float64 with every
     operation rounded on its own (_rule_product, _rule_inverse).  joint_score None: the puzzle's largest edge score."""
-    as_np = lambda a, dt: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(dt)
-    S, P = as_np(score, np.float32), as_np(T, np.float32)
+    S, P = _as_np(score, np.float32), _as_np(T, np.float32)
     Z, K = S.shape[0], S.shape[1]
     if S.shape != (Z, K, K) or P.shape != (Z, K, K, 4, 4) or K < 2:
         raise ValueError(f"walk_rule expects score[Z,K,K], T[Z,K,K,4,4] with K >= 2; got {S.shape}, {P.shape}")
-    counts = np.full(Z, K, dtype=np.int64) if count is None else as_np(count, np.int64)
+    counts = np.full(Z, K, dtype=np.int64) if count is None else _as_np(count, np.int64)
     inf = float("inf")
     limit = inf if max_score is None else float(max_score)
-    root = np.full(Z, -1, dtype=np.int32)
-    edges = np.full((Z, K - 1, 3), -1, dtype=np.int32)
-    edge_score = np.full((Z, K - 1), np.inf, dtype=np.float32)
-    n_edges = np.zeros(Z, dtype=np.int32)
-    G = np.tile(np.eye(4), (Z, K, 1, 1))
-    placed = np.zeros((Z, K), dtype=np.uint8)
-    joints = np.full((Z, K * (K - 1), 2), -1, dtype=np.int32)
-    n_joints = np.zeros(Z, dtype=np.int32)
+    out = root, edges, edge_score, n_edges, G, placed, joints, n_joints = _rule_outputs(Z, K)
     for z in range(Z):
         c = int(counts[z])
         if not 2 <= c <= K:
@@ -558,15 +574,17 @@ def walk_rule(score, T, count=None, max_score=None, joint_score=None):
             G[z, p] = np.array(g, dtype=np.float64)
         placed[z, :c] = inside
         js = worst if joint_score is None or joint_score != joint_score else float(joint_score)      # (NaN is the kernel's None)
-        n = 0
         if n_edges[z] > 0:
-            for i in range(c):
-                for j in range(c):
-                    if i != j and inside[i] and inside[j] and raw[i][j] <= js:
-                        joints[z, n] = (i, j)
-                        n += 1
-        n_joints[z] = n
-    return WalkRule(root, edges, edge_score, n_edges, G, placed, joints, n_joints)
+            n_joints[z] = _rule_joints(inside, raw, js, joints[z])
+    return out
+
+
+def _placed_movable(placed, root):
+    """The kernel's placed bytes [Z,K] as bool, and movable = placed and not the root."""
+    with torch.no_grad():
+        placed = placed.bool()
+        index = torch.arange(placed.shape[1], dtype=torch.int32, device=placed.device)
+        return placed, placed & (index[None, :] != root[:, None])
 
 
 def assemble_batch(score, T, count=None, max_score=None, joint_score=None):
@@ -583,10 +601,7 @@ def assemble_batch(score, T, count=None, max_score=None, joint_score=None):
     Discrete outputs are assemble's bit for bit; G follows walk_rule bit for bit (assemble composes with numpy's matmul, a
     last-place matter).  Nothing waits for the device."""
     root, edges, edge_score, n_edges, G, placed, joints, n_joints = ops.assemble_walk(score, T, count, max_score, joint_score)
-    with torch.no_grad():
-        placed = placed.bool()
-        index = torch.arange(placed.shape[1], dtype=torch.int32, device=placed.device)
-        movable = placed & (index[None, :] != root[:, None])
+    placed, movable = _placed_movable(placed, root)
     return AssemblyBatch(root, edges, edge_score, n_edges, G, placed, movable, joints, n_joints)
 
 
@@ -602,16 +617,13 @@ def boundary_moments(pieces, top_m):
     device, moment[z,p] = the mean over x = pieces[z,p][top_m[z,p]] of (x, 1) (x, 1)^T.  With it mean_x |Q x - G x|^2 is
     sum_u D_u M D_u^T over the rows of D = Q - G: what two poses of piece p disagree by on its boundary, with no point read.
     Nothing waits for the device."""
-    for name, t in (("pieces", pieces), ("top_m", top_m)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _lib.PznError(f"boundary_moments: {name} must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
-    if pieces.dim() != 4 or pieces.shape[3] != 3 or pieces.dtype != torch.float32:
-        raise _lib.PznError(f"boundary_moments expects float32 pieces[Z,P,N,3]; got {pieces.dtype} {tuple(pieces.shape)}")
-    Z, P = pieces.shape[0], pieces.shape[1]
+    _on_gpu("boundary_moments", top_m=top_m)
+    _clouds("boundary_moments", "Z,P", pieces=pieces)
+    Z, P, N = pieces.shape[0], pieces.shape[1], pieces.shape[2]
     if top_m.dim() != 3 or tuple(top_m.shape[:2]) != (Z, P) or top_m.shape[2] < 1 or top_m.dtype != torch.long:
         raise _lib.PznError(f"boundary_moments expects int64 top_m[{Z},{P},k]; got {top_m.dtype} {tuple(top_m.shape)}")
     with torch.no_grad():
-        x = _puzzle_rows(pieces.contiguous(), top_m).double()                                  # [Z,P,k,3]
+        x = ops.index_points(pieces.contiguous().view(Z * P, N, 3), top_m.reshape(Z * P, -1)).view(Z, P, -1, 3).double()
         xh = torch.cat((x, torch.ones_like(x[..., :1])), dim=-1)
         return (xh.unsqueeze(-1) * xh.unsqueeze(-2)).mean(dim=2)
 
@@ -648,8 +660,7 @@ def beam_rule(score, T, moment, count=None, beam=4, branch=4, weight=1.0, max_sc
     and the new piece n: D = G[p] T[p,n] - Gn or G[p] inv(T[n,p]) - Gn on rows 0..2, d = sum_u D_u M[n] D_u^T with the rule's
     dot4 order.  The round's children are ordered by (cost, parent slot, rank) and the first `beam` distinct placed sets live on.
     The result is slot 0.  Written with element-wise float64 only: no matmul, whose summation order is not fixed."""
-    as_np = lambda a, dt: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(dt)
-    S, P, M = as_np(score, np.float32), as_np(T, np.float32), as_np(moment, np.float64)
+    S, P, M = _as_np(score, np.float32), _as_np(T, np.float32), _as_np(moment, np.float64)
     Z, K = S.shape[0], S.shape[1]
     B, C, weight = int(beam), int(branch), float(weight)
     if S.shape != (Z, K, K) or P.shape != (Z, K, K, 4, 4) or M.shape != (Z, K, 4, 4) or K < 2:
@@ -657,18 +668,11 @@ def beam_rule(score, T, moment, count=None, beam=4, branch=4, weight=1.0, max_sc
                          f"{M.shape}")
     if B < 1 or C < 1 or weight != weight:
         raise ValueError(f"beam_rule: beam = {B}, branch = {C} (>= 1), weight = {weight} (not NaN)")
-    counts = np.full(Z, K, dtype=np.int64) if count is None else as_np(count, np.int64)
+    counts = np.full(Z, K, dtype=np.int64) if count is None else _as_np(count, np.int64)
     inf = float("inf")
     limit = inf if max_score is None else float(max_score)
     vlimit = limit if vote_score is None or vote_score != vote_score else float(vote_score)
-    root = np.full(Z, -1, dtype=np.int32)
-    edges = np.full((Z, K - 1, 3), -1, dtype=np.int32)
-    edge_score = np.full((Z, K - 1), np.inf, dtype=np.float32)
-    n_edges = np.zeros(Z, dtype=np.int32)
-    G = np.tile(np.eye(4), (Z, K, 1, 1))
-    placed = np.zeros((Z, K), dtype=np.uint8)
-    joints = np.full((Z, K * (K - 1), 2), -1, dtype=np.int32)
-    n_joints = np.zeros(Z, dtype=np.int32)
+    out = root, edges, edge_score, n_edges, G, placed, joints, n_joints = _rule_outputs(Z, K)
     cost = np.full((Z, B), np.inf, dtype=np.float64)
     n_hyp = np.zeros(Z, dtype=np.int32)
     with np.errstate(all="ignore"):
@@ -757,15 +761,9 @@ def beam_rule(score, T, moment, count=None, beam=4, branch=4, weight=1.0, max_sc
             G[z, :c][inside] = poses[inside]
             placed[z, :c] = inside
             js = worst if joint_score is None or joint_score != joint_score else float(joint_score)
-            n = 0
             if es:
-                for i in range(c):
-                    for j in range(c):
-                        if i != j and inside[i] and inside[j] and raw[i, j] <= js:
-                            joints[z, n] = (i, j)
-                            n += 1
-            n_joints[z] = n
-    return BeamRule(root, edges, edge_score, n_edges, G, placed, joints, n_joints, cost, n_hyp)
+                n_joints[z] = _rule_joints(inside, raw, js, joints[z])
+    return BeamRule(*out, cost, n_hyp)
 
 
 def assemble_beam_batch(score, T, moment, count=None, beam=4, branch=4, weight=1.0, max_score=None, vote_score=None,
@@ -781,46 +779,21 @@ def assemble_beam_batch(score, T, moment, count=None, beam=4, branch=4, weight=1
     the device."""
     root, edges, edge_score, n_edges, G, placed, joints, n_joints, cost, n_hyp = ops.assemble_beam(
         score, T, moment, count, beam, branch, weight, max_score, vote_score, joint_score)
-    with torch.no_grad():
-        placed = placed.bool()
-        index = torch.arange(placed.shape[1], dtype=torch.int32, device=placed.device)
-        movable = placed & (index[None, :] != root[:, None])
+    placed, movable = _placed_movable(placed, root)
     return BeamBatch(root, edges, edge_score, n_edges, G, placed, movable, joints, n_joints, cost, n_hyp)
-
-
-def _pair_fixed_head_blocks(seq, local, g):
-    """_pair_fixed_head for Z puzzles: local [Z,Kf,N,64], g [Z,Km,64] -> [Z,Kf,Km,N,2] in one pair_head_blocks launch, or (shapes
-    it does not take) _pair_fixed_head's fallback puzzle by puzzle."""
-    mods = list(seq)
-    if len(mods) == 5 and ops.pair_head_blocks_supported(local.shape[2], mods[2].out_features, mods[4].out_features):
-        l1, l2, l3 = mods[0], mods[2], mods[4]
-        return ops.pair_head_blocks(local, g, l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias)
-    return torch.stack([_pair_fixed_head(seq, local[z], g[z]) for z in range(local.shape[0])], dim=0)
-
-
-def _puzzle_rows(pieces, top):
-    """pieces [Z,K,N,3] and picked rows top [Z,K,...] of every piece -> their points [..., 3] by ONE gather over the flattened
-    [1, Z K N, 3] rows (as refine_assembly_batch does it)."""
-    Z, K, N = pieces.shape[0], pieces.shape[1], pieces.shape[2]
-    first = (torch.arange(Z * K, dtype=torch.long, device=pieces.device) * N).view(Z, K, *([1] * (top.dim() - 2)))
-    return ops.index_points(pieces.reshape(1, Z * K * N, 3), (first + top).reshape(1, -1))[0].view(*top.shape, 3)
 
 
 def pair_block_batch(model, pieces_f, codes_f, pieces_m, codes_m, k=128, refine=0):
     """pair_block for Z puzzles, block-diagonal: pieces_f [Z,Kf,N,3] in the fixed role meet only the pieces_m [Z,Km,N,3] of their
     own puzzle -> PairBlock whose every field carries a leading Z (twist [Z,Kf,Km,6], T [Z,Kf,Km,4,4], de_fpcb [Z,Kf,Km,2,N], top_f
     [Z,Kf,Km,k], score [Z,Kf,Km]).  codes_* are PieceCodes whose fields are [Z,K,...] views of one encode_pieces call over Z K pieces.
-    It is pair_block stage by stage, each stage ONCE for all puzzles: the pose head's four layers on the Z Kf Km rows relu(U + V),
-    se3.exp, one ops.pair_head_blocks launch, softmax and one topk_rows, one gather per side over the flattened rows, then the
-    transform and ops.chamfer or (refine > 0) the one ops.icp_refine launch.  de_fpcb has pair_block's bits (the blocked head does
-    not know about z); the fields behind the few-row layers agree with pair_block's as two calls of it do.  Nothing waits for
-    the device."""
+    Every stage runs ONCE for all puzzles: the pose head's four layers on the Z Kf Km rows relu(U + V), se3.exp, one
+    ops.pair_head_blocks launch, softmax and one topk_rows, one gather per side, then the transform and ops.chamfer or
+    (refine > 0) the one ops.icp_refine launch.  de_fpcb has the same bits whatever Z is (the blocked head does not know about
+    z); the fields behind the few-row layers agree between batches as two calls on the same batch do.  Nothing waits for the
+    device."""
     refine = _check_refine(refine, "pair_block_batch")
-    for name, t in (("pieces_f", pieces_f), ("pieces_m", pieces_m)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _lib.PznError(f"pair_block_batch: {name} must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
-        if t.dim() != 4 or t.shape[3] != 3 or t.dtype != torch.float32:
-            raise _lib.PznError(f"pair_block_batch expects float32 {name}[Z,K,N,3]; got {t.dtype} {tuple(t.shape)}")
+    _clouds("pair_block_batch", "Z,K", pieces_f=pieces_f, pieces_m=pieces_m)
     Z, Kf, N = pieces_f.shape[0], pieces_f.shape[1], pieces_f.shape[2]
     Km = pieces_m.shape[1]
     if pieces_m.shape[0] != Z or pieces_m.shape[2] != N or Z < 1 or Kf < 1 or Km < 1:
@@ -831,23 +804,23 @@ def pair_block_batch(model, pieces_f, codes_f, pieces_m, codes_m, k=128, refine=
         raise _lib.PznError(f"pair_block_batch: the codes are not [Z,K,...] views of Z = {Z} puzzles of {Kf} and {Km} pieces")
     k = int(k)
     with torch.no_grad():
+        # pose head: the four layers after the split first one run on the Z Kf Km rows relu(U_i + V_j)
         hidden = torch.relu(codes_f.U[:, :, None] + codes_m.V[:, None]).reshape(Z * Kf * Km, -1)
         twist = run_seq(list(model.tfMLP)[2:], hidden).view(Z, Kf, Km, 6)
         T = se3.exp(twist)
 
-        y_f = _pair_fixed_head_blocks(model.MLPFpcb, codes_f.local_f, codes_m.g_max)          # [Z,Kf,Km,N,2]
+        y_f = _pair_fixed_head(model.MLPFpcb, codes_f.local_f, codes_m.g_max)                 # [Z,Kf,Km,N,2]
         de_fpcb = y_f.permute(0, 1, 2, 4, 3)
 
+        # the k points of largest class-1 probability (softmax over two logits) and the boundary-to-boundary distance
         p_f = torch.softmax(y_f, dim=-1)[..., 1].reshape(Z * Kf * Km, N)
         top_f = ops.topk_rows(p_f, k).view(Z, Kf, Km, k)
-        Bf = _puzzle_rows(pieces_f, top_f).view(Z * Kf * Km, k, 3)                            # pieces_f[z,i][top_f[z,i,j]]
-        Bm = _puzzle_rows(pieces_m, codes_m.top_m).view(Z * Km, -1, 3)                        # pieces_m[z,j][top_m[z,j]]
+        # pieces_f[z,i][top_f[z,i,j]] per pair, pieces_m[z,j][top_m[z,j]] per moved piece
+        Bf = ops.index_points(pieces_f.reshape(Z * Kf, N, 3), top_f.reshape(Z * Kf, Km * k)).view(Z * Kf * Km, k, 3)
+        Bm = ops.index_points(pieces_m.reshape(Z * Km, N, 3), codes_m.top_m.reshape(Z * Km, -1))
         if refine > 0:
-            # problem (z, i, j) reads the moved set z Km + j
-            b_of = (torch.arange(Z, dtype=torch.long, device=T.device)[:, None, None] * Km
-                    + torch.arange(Km, dtype=torch.long, device=T.device)[None, None, :]).expand(Z, Kf, Km).reshape(-1)
-            Tr, score, _, _ = ops.icp_refine(Bf, Bm, T.reshape(Z * Kf * Km, 4, 4), refine, b_of=b_of)
-            return PairBlock(twist, Tr.view(Z, Kf, Km, 4, 4), de_fpcb, top_f, score.view(Z, Kf, Km))
+            r = _refine_gathered(Bf, Bm, T, refine)
+            return PairBlock(twist, r.T, de_fpcb, top_f, r.score)
         Bm = Bm.view(Z, 1, Km, -1, 3).expand(Z, Kf, Km, -1, 3).reshape(Z * Kf * Km, -1, 3)
         d1, d2 = ops.chamfer(Bf, se3.transform_points(T.reshape(Z * Kf * Km, 4, 4), Bm))
         score = (d1.mean(dim=1) + d2.mean(dim=1)).view(Z, Kf, Km)
@@ -857,13 +830,10 @@ def pair_block_batch(model, pieces_f, codes_f, pieces_m, codes_m, k=128, refine=
 def _match_puzzles(model, pieces, k, start, refine, who):
     """match_puzzles' body -> (pieces contiguous, PieceCodes of [Z,P,...] views, the square PairBlock, diagonal not masked)."""
     refine = _check_refine(refine, who)
-    if not isinstance(pieces, torch.Tensor) or not pieces.is_cuda:
-        raise _lib.PznError(f"{who}: pieces must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
-    if pieces.dim() != 4 or pieces.shape[3] != 3 or pieces.dtype != torch.float32 or pieces.shape[0] < 1:
-        raise _lib.PznError(f"{who} expects float32 pieces[Z,P,N,3] with Z >= 1; got {pieces.dtype} {tuple(pieces.shape)}")
+    _clouds(who, "Z,P", pieces=pieces)
     Z, P, N, _ = pieces.shape
-    if P < 2:
-        raise _lib.PznError(f"{who}: P = {P} pieces a puzzle (>= 2)")
+    if Z < 1 or P < 2:
+        raise _lib.PznError(f"{who}: Z = {Z} puzzles (>= 1) of P = {P} pieces (>= 2)")
     pieces = pieces.contiguous()
     flat = pieces.view(Z * P, N, 3)
     if start is not None:
@@ -885,10 +855,7 @@ def match_puzzles(model, pieces, k=128, start=None, refine=0):
     same puzzle and starts bit for bit; the fields behind the few-row layers (twist, and with it T and score) are not equal
     bit for bit between two calls of match_pairs either, and agree with it as two such calls do.  Nothing waits for the device."""
     pieces, codes, blk = _match_puzzles(model, pieces, k, start, refine, "match_puzzles")
-    P = pieces.shape[1]
-    with torch.no_grad():
-        score = blk.score.masked_fill(torch.eye(P, dtype=torch.bool, device=pieces.device), float("inf"))
-    return PairTable(blk.twist, blk.T, blk.de_fpcb, codes.de_mrpcb, blk.top_f, codes.top_m, score, codes.x2)
+    return _table(codes, blk, _diagonal(pieces))
 
 
 def refine_assembly_batch(pieces, table, asm, sweeps=30):
@@ -902,10 +869,7 @@ def refine_assembly_batch(pieces, table, asm, sweeps=30):
     a_of = z P^2 + i P + j and b_of = z P + j, computed from asm.joints in torch (unused rows map to set 0 and are skipped by
     the kernel).  G0 = asm.G rounded to float32, movable = asm.movable, then the one launch of ops.joint_refine for all Z
     puzzles.  Per puzzle the result is refine_assembly's bit for bit.  Nothing waits for the device."""
-    if not isinstance(pieces, torch.Tensor) or not pieces.is_cuda:
-        raise _lib.PznError("refine_assembly_batch: pieces must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
-    if pieces.dim() != 4 or pieces.shape[3] != 3 or pieces.dtype != torch.float32:
-        raise _lib.PznError(f"refine_assembly_batch expects float32 pieces[Z,P,N,3]; got {pieces.dtype} {tuple(pieces.shape)}")
+    _clouds("refine_assembly_batch", "Z,P", pieces=pieces)
     Z, P, N, _ = pieces.shape
     J = P * (P - 1)
     if tuple(table.top_f.shape[:3]) != (Z, P, P) or tuple(table.top_m.shape[:2]) != (Z, P) or tuple(asm.G.shape) != (Z, P, 4, 4) \
@@ -944,9 +908,7 @@ def evaluate_batch(G, placed, pose, rest, root, edges=None, n_edges=None, mates=
     edges [Z,P-1,3], n_edges [Z] and mates [Z,P,P], the share of the first n_edges rows whose pair (i, j) is in mates, NaN for a
     puzzle without an edge; None without all three.  A puzzle with root < 0 (assemble_batch gave it no root) is measured in
     piece 0's frame with every piece counted: nothing is placed there, so its part accuracy is 0.  Nothing waits for the device."""
-    for name, t in (("G", G), ("placed", placed), ("pose", pose), ("rest", rest), ("root", root)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _lib.PznError(f"evaluate_batch: {name} must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
+    _on_gpu("evaluate_batch", G=G, placed=placed, pose=pose, rest=rest, root=root)
     if pose.dim() != 4 or tuple(pose.shape[2:]) != (4, 4):
         raise _lib.PznError(f"evaluate_batch expects pose[Z,P,4,4]; got {tuple(pose.shape)}")
     Z, P = pose.shape[0], pose.shape[1]
@@ -1034,6 +996,15 @@ class MergeLedger:
         return i if i < j else i - 1
 
 
+def _check_merge(who, N, k, drop_matched):
+    """What both progressive walks ask before they start: two N-point parts must merge into one."""
+    if drop_matched and 2 * k > N:
+        raise _lib.PznError(f"{who}: drop_matched needs k <= N / 2 (k = {k}, N = {N}): the rows kept of a union must fill "
+                            "the merged part")
+    if not ops.merge_resample_supported(N, N, N):
+        raise _lib.PznUnsupported(f"{who}: two parts of N = {N} points are not a union merge_resample takes")
+
+
 def _del1(x, j):
     return torch.cat((x[:j], x[j + 1:]), dim=0)
 
@@ -1058,11 +1029,7 @@ class ProgressiveAssembler:
 
     def __init__(self, model, pieces, k=128, start=None, max_score=None, drop_matched=True, generator=None, refine=0):
         K, N, k = _check_pieces(model, pieces, k, "ProgressiveAssembler", 2)
-        if drop_matched and 2 * k > N:
-            raise _lib.PznError(f"ProgressiveAssembler: drop_matched needs k <= N / 2 (k = {k}, N = {N}): the rows kept "
-                                "of a union must fill the merged part")
-        if not ops.merge_resample_supported(N, N, N):
-            raise _lib.PznUnsupported(f"ProgressiveAssembler: two parts of N = {N} points are not a union merge_resample takes")
+        _check_merge("ProgressiveAssembler", N, k, drop_matched)
         self.model, self.k, self.max_score, self.drop_matched = model, k, max_score, bool(drop_matched)
         self.refine = _check_refine(refine, "ProgressiveAssembler")
         dev = pieces.device
@@ -1074,9 +1041,7 @@ class ProgressiveAssembler:
         self.parts = pieces.contiguous().clone()
         self.codes = encode_pieces(model, self.parts, k, (s1, s2), _who="ProgressiveAssembler", _least=2)
         blk = pair_block(model, self.parts, self.codes, self.parts, self.codes, k, self.refine)
-        eye = torch.eye(K, dtype=torch.bool, device=dev)
-        self.table = PairTable(blk.twist, blk.T, blk.de_fpcb, self.codes.de_mrpcb, blk.top_f, self.codes.top_m,
-                               blk.score.masked_fill(eye, float("inf")), self.codes.x2)
+        self.table = _table(self.codes, blk, _diagonal(self.parts))
         self.piece_id = torch.arange(K, dtype=torch.long, device=dev)[:, None].expand(K, N).contiguous()
         self.row_id = torch.arange(N, dtype=torch.long, device=dev)[None].expand(K, N).contiguous()
         self.ledger = MergeLedger(K)
@@ -1147,15 +1112,15 @@ class ProgressiveAssembler:
             self.codes = PieceCodes(*fields)
             row = pair_block(self.model, merged, code, self.parts, self.codes, k, self.refine)      # [1, K' - 1]
             col = pair_block(self.model, self.parts, self.codes, merged, code, k, self.refine)      # [K' - 1, 1]
-            upd = {}
+            upd = []
             for name in PairBlock._fields:
                 x = _del2(getattr(t, name), j)
                 x[:, n] = getattr(col, name)[:, 0]
                 x[n] = getattr(row, name)[0]
-                upd[name] = x
-            upd["score"][n, n] = float("inf")
-            self.table = PairTable(upd["twist"], upd["T"], upd["de_fpcb"], self.codes.de_mrpcb, upd["top_f"], self.codes.top_m,
-                                   upd["score"], self.codes.x2)
+                upd.append(x)
+            upd = PairBlock(*upd)
+            upd.score[n, n] = float("inf")
+            self.table = _table(self.codes, upd)
         return self.ledger.edges[-1]
 
     def run(self):
@@ -1216,13 +1181,12 @@ def progressive_round_rule(score, T, state, max_score=None):
     with part[p] == j, G[p] = T[i,j] G[p] (_rule_product: float64 from the float32 T, every operation rounded on its own) and
     part[p] = i; alive[j] = 0; the row (label_i, label_j, i, j) - a label is the part's lowest member piece, before the merge -
     and the score as stored are appended; took = 1, pick = (i, j)."""
-    as_np = lambda a, dt: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(dt)
-    S, X = as_np(score, np.float32), as_np(T, np.float32)
+    S, X = _as_np(score, np.float32), _as_np(T, np.float32)
     Z, P = S.shape[0], S.shape[1]
     if S.shape != (Z, P, P) or X.shape != (Z, P, P, 4, 4) or P < 2:
         raise ValueError(f"progressive_round_rule expects score[Z,P,P], T[Z,P,P,4,4] with P >= 2; got {S.shape}, {X.shape}")
     types = (np.uint8, np.int32, np.float64, np.uint8, np.int32, np.int32, np.float32)
-    alive, part, G, done, n_edges, edges, edge_score = (as_np(f, dt).copy() for f, dt in zip(state, types))
+    alive, part, G, done, n_edges, edges, edge_score = (_as_np(f, dt).copy() for f, dt in zip(state, types))
     took = np.zeros(Z, dtype=np.uint8)
     pick = np.zeros((Z, 2), dtype=np.int64)
     inf = float("inf")
@@ -1290,11 +1254,7 @@ class ProgressiveBatch:
         pieces, codes, blk = _match_puzzles(model, pieces, k, start, self.refine, who)
         Z, P, N, _ = pieces.shape
         k = int(k)
-        if drop_matched and 2 * k > N:
-            raise _lib.PznError(f"{who}: drop_matched needs k <= N / 2 (k = {k}, N = {N}): the rows kept of a union must fill "
-                                "the merged part")
-        if not ops.merge_resample_supported(N, N, N):
-            raise _lib.PznUnsupported(f"{who}: two parts of N = {N} points are not a union merge_resample takes")
+        _check_merge(who, N, k, drop_matched)
         if not ops.progressive_round_supported(P):
             raise _lib.PznUnsupported(f"{who}: P = {P} pieces a puzzle (2 <= P <= 64)")
         if max_score is not None and float(max_score) != float(max_score):
@@ -1321,7 +1281,7 @@ class ProgressiveBatch:
             self.merge_starts = merge_starts
             self.parts = pieces.clone()
             self.codes = codes
-            self._eye = torch.eye(P, dtype=torch.bool, device=dev)
+            self._eye = _diagonal(pieces)
             self._z = torch.arange(Z, dtype=torch.long, device=dev)
             self._y_f = blk.de_fpcb.permute(0, 1, 2, 4, 3)      # the kernel's [Z,P,P,N,2]; de_fpcb is its permuted view
             self._twist, self._T, self._top_f = blk.twist, blk.T, blk.top_f
@@ -1340,8 +1300,7 @@ class ProgressiveBatch:
 
     @property
     def table(self):
-        c = self.codes
-        return PairTable(self._twist, self._T, self._y_f.permute(0, 1, 2, 4, 3), c.de_mrpcb, self._top_f, c.top_m, self._score, c.x2)
+        return _table(self.codes, PairBlock(self._twist, self._T, self._y_f.permute(0, 1, 2, 4, 3), self._top_f, self._score))
 
     def step(self):
         """One round of all Z puzzles.  Nothing here waits for the device: the picks stay there, every gather and every write-back

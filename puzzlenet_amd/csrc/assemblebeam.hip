@@ -19,7 +19,7 @@
 //   * the next generation: the wavefront copies each winner's parent poses and edges, the winner's lane adds its own.
 // Every index into score, T and moment is formed from i, j < count[z] <= K.  No atomics: the same bits on every run.
 #include "pzn_common.h"
-#include "pzn_walk.h"      // the key, the 64-lane arg-min and the float64 dot product of the greedy walk
+#include "pzn_walk.h"      // the key, the 64-lane arg-min, the stop test, the float64 dot product and the result tail of the walk
 
 #pragma clang fp contract(off)
 
@@ -121,8 +121,7 @@ __global__ __launch_bounds__(AB_T) void assemble_beam_kernel(const float* __rest
             next = wave_min_u64_dpp(next);
             const uint32_t w_key = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(next >> 32));
             if (w_key == 0xffffffffu) break;                                            // no pair left
-            const float key = unordered(w_key);
-            if (!(fabsf(key) < __builtin_inff()) || (double)key > max_score) break;     // nor any later one
+            if (stops(w_key, max_score)) break;                                         // nor any later one
             last = next;
             if (grp == h * C + rank) mine = next;
           }
@@ -268,31 +267,14 @@ __global__ __launch_bounds__(AB_T) void assemble_beam_kernel(const float* __rest
       e[0] = my_i, e[1] = my_j, e[2] = my_nw;
       edge_score[(size_t)z * (K - 1) + lane] = my_s;
     }
-    if (lane < K) placed[(size_t)z * K + lane] = (uint8_t)((in >> lane) & 1);
     for (int e = lane; e < 16 * K; e += PZN_WAVE) {
       const double id = ((e >> 2) & 3) == (e & 3) ? 1.0 : 0.0;
       G[(size_t)z * K * 16 + e] = ((in >> (e >> 4)) & 1) ? pose[(size_t)(cur * B) * K * 16 + e] : id;
     }
     if (lane < B) cost[(size_t)z * B + lane] = lane < H ? hcost[cur * B + lane] : __builtin_inf();
 
-    // the joints, by the walk's rule from the result's own edges
-    const double limit = joint_score != joint_score ? worst : joint_score;
-    int nj = 0;
-    int32_t* jz = joints + (size_t)z * JR * 2;
-    if (ne > 0) {
-      for (int i = 0; i < c; ++i) {
-        if (!((in >> i) & 1)) continue;
-        bool ok = false;
-        if (lane < c && lane != i && ((in >> lane) & 1)) ok = (double)S[i * K + lane] <= limit;
-        const uint64_t m = __ballot(ok);
-        if (ok) {
-          const int at = nj + __popcll(m & (((uint64_t)1 << lane) - 1));
-          jz[2 * at] = i, jz[2 * at + 1] = lane;
-        }
-        nj += __popcll(m);
-      }
-    }
-    for (int e = nj + lane; e < JR; e += PZN_WAVE) jz[2 * e] = -1, jz[2 * e + 1] = -1;
+    // the placed bytes and the joints, by the walk's rule from the result's own edges
+    const int nj = walk_tail(in, c, K, ne, worst, joint_score, S, lane, placed + (size_t)z * K, joints + (size_t)z * JR * 2);
     if (lane == 0) root[z] = r, n_edges[z] = ne, n_joints[z] = nj, n_hyp[z] = H;
     pzn::wave_lds_sync();      // the hypotheses are replaced by the next puzzle's
   }

@@ -15,11 +15,10 @@
 //     each, ((a0 b0 + a1 b1) + a2 b2) + a3 b3 with every operation rounded on its own (the file is built with
 //     -ffp-contract=off, and the pragma below says it again);
 //   * edge e stays in lane e's registers until the end (K - 1 <= 63 edges);
-//   * the joints: for every placed row i in turn, lane j tests entry (i, j) (a coalesced row), the ballot's prefix count is
-//     the place of (i, j) after the joints of the rows before: row-major order with no scan through memory.
+//   * the placed bytes and the joints are pzn_walk.h's walk_tail, shared with assemblebeam.hip.
 // Every index into score and T is formed from an i, j < count[z] <= K.  No atomics: the same bits on every run.
 #include "pzn_common.h"
-#include "pzn_walk.h"      // the key, the 64-lane arg-min and the float64 dot product, shared with progressive.hip
+#include "pzn_walk.h"      // the key, the 64-lane arg-min, the stop test, the float64 dot product and the result tail
 
 #pragma clang fp contract(off)
 
@@ -81,8 +80,7 @@ __global__ __launch_bounds__(AW_T) void assemble_walk_kernel(const float* __rest
         const uint32_t w_key = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(w >> 32));
         const int flat = __builtin_amdgcn_readfirstlane((int)(uint32_t)w);
         if ((w_key & (uint32_t)flat) == 0xffffffffu) break;      // no candidate left
-        const float key = unordered(w_key);
-        if (!(fabsf(key) < __builtin_inff()) || (double)key > max_score) break;
+        if (stops(w_key, max_score)) break;
         const int i = flat / K, j = flat - i * K;
         const bool fwd = (in >> i) & 1;           // the fixed end is placed: G[j] = G[i] T[i,j]
         const int nw = fwd ? j : i, src = fwd ? i : j;
@@ -126,27 +124,9 @@ __global__ __launch_bounds__(AW_T) void assemble_walk_kernel(const float* __rest
       e[0] = my_i, e[1] = my_j, e[2] = my_new;
       edge_score[(size_t)z * (K - 1) + lane] = my_s;
     }
-    if (lane < K) placed[(size_t)z * K + lane] = (uint8_t)((in >> lane) & 1);
     for (int e = lane; e < 16 * K; e += PZN_WAVE) G[(size_t)z * K * 16 + e] = g[e];
 
-    // the joints: placed i != j with (double)score[i,j] <= limit on the raw score, row-major
-    const double limit = joint_score != joint_score ? worst : joint_score;
-    int nj = 0;
-    int32_t* jz = joints + (size_t)z * JR * 2;
-    if (ne > 0) {
-      for (int i = 0; i < c; ++i) {               // (wavefront-uniform: `in`, c and nj are the same in every lane)
-        if (!((in >> i) & 1)) continue;
-        bool ok = false;
-        if (lane < c && lane != i && ((in >> lane) & 1)) ok = (double)S[i * K + lane] <= limit;
-        const uint64_t m = __ballot(ok);
-        if (ok) {
-          const int at = nj + __popcll(m & (((uint64_t)1 << lane) - 1));
-          jz[2 * at] = i, jz[2 * at + 1] = lane;
-        }
-        nj += __popcll(m);
-      }
-    }
-    for (int e = nj + lane; e < JR; e += PZN_WAVE) jz[2 * e] = -1, jz[2 * e + 1] = -1;
+    const int nj = walk_tail(in, c, K, ne, worst, joint_score, S, lane, placed + (size_t)z * K, joints + (size_t)z * JR * 2);
     if (lane == 0) root[z] = r, n_edges[z] = ne, n_joints[z] = nj;
     pzn::wave_lds_sync();      // the poses are replaced by the next puzzle's
   }

@@ -55,9 +55,8 @@ __global__ __launch_bounds__(PR_T) void progressive_round_kernel(const float* __
       best = wave_min_u64_dpp(best);
       const uint32_t w_key = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(best >> 32));
       flat = __builtin_amdgcn_readfirstlane((int)(uint32_t)best);
-      const float key = unordered(w_key);
       // (two live slots always give a candidate; its key may be +inf)
-      stop = best == NONE || !(fabsf(key) < __builtin_inff()) || (double)key > max_score;
+      stop = best == NONE || stops(w_key, max_score);
     }
     if (stop) {
       if (lane == 0) {

@@ -1,7 +1,9 @@
-// pzn_walk.h — what the walks over pair tables share (assemblewalk.hip, progressive.hip): the key of a table entry, the
-// 64-lane lexicographic arg-min over (key, i K + j) and the order-fixed float64 dot product the poses are composed with.  One
-// statement of each, so "the smallest key, the lowest i K + j on ties" and "every operation rounded on its own" mean the same
-// in both kernels.  Files that include it are built with -ffp-contract=off and say so again with the pragma.
+// pzn_walk.h — what the walks over pair tables share (assemblewalk.hip, assemblebeam.hip, progressive.hip): the key of a table
+// entry, the 64-lane lexicographic arg-min over (key, i K + j), the stop test on a round's winning key, the order-fixed float64
+// dot product the poses are composed with, and the tail of a walk's result (assemblewalk.hip, assemblebeam.hip): the placed
+// bytes and the joint list.  One statement of each, so "the smallest key, the lowest i K + j on ties", "the walk stops here"
+// and "every operation rounded on its own" mean the same in every kernel.  Files that include it are built with
+// -ffp-contract=off and say so again with the pragma.
 #ifndef PZN_WALK_H_
 #define PZN_WALK_H_
 
@@ -39,8 +41,43 @@ __device__ __forceinline__ uint64_t wave_min_u64_dpp(uint64_t v) {
   return v;
 }
 
+// a round ends the walk at a winning key (the high dword of the 64-lane minimum) that is not finite or above max_score
+__device__ __forceinline__ bool stops(uint32_t w_key, double max_score) {
+  const float key = unordered(w_key);
+  return !(fabsf(key) < __builtin_inff()) || (double)key > max_score;
+}
+
 __device__ __forceinline__ double dot4(double a0, double b0, double a1, double b1, double a2, double b2, double a3, double b3) {
   return ((a0 * b0 + a1 * b1) + a2 * b2) + a3 * b3;
+}
+
+// The tail of a walk's result for one puzzle, by its wavefront: `in` is the placed set (bit p = piece p), c the puzzle's
+// pieces, ne its edges, worst its largest edge score, S its [K,K] scores; placed [K] and joints [K (K - 1), 2] are the puzzle's
+// rows of the outputs -> the number of joints.  The joints are the placed i != j with (double)score[i,j] <= limit on the raw
+// score, limit = joint_score or (NaN) worst: for every placed row i in turn, lane j tests entry (i, j) (a coalesced row) and
+// the ballot's prefix count is the place of (i, j) after the joints of the rows before - row-major order with no scan through
+// memory.  Unused rows are (-1, -1).  (`in`, c, ne and the count are the same in every lane.)
+__device__ __forceinline__ int walk_tail(uint64_t in, int c, int K, int ne, double worst, double joint_score,
+                                         const float* __restrict__ S, int lane, uint8_t* __restrict__ placed,
+                                         int32_t* __restrict__ joints) {
+  if (lane < K) placed[lane] = (uint8_t)((in >> lane) & 1);
+  const double limit = joint_score != joint_score ? worst : joint_score;
+  int nj = 0;
+  if (ne > 0) {
+    for (int i = 0; i < c; ++i) {
+      if (!((in >> i) & 1)) continue;
+      bool ok = false;
+      if (lane < c && lane != i && ((in >> lane) & 1)) ok = (double)S[i * K + lane] <= limit;
+      const uint64_t m = __ballot(ok);
+      if (ok) {
+        const int at = nj + __popcll(m & (((uint64_t)1 << lane) - 1));
+        joints[2 * at] = i, joints[2 * at + 1] = lane;
+      }
+      nj += __popcll(m);
+    }
+  }
+  for (int e = nj + lane; e < K * (K - 1); e += PZN_WAVE) joints[2 * e] = -1, joints[2 * e + 1] = -1;
+  return nj;
 }
 
 }  // namespace

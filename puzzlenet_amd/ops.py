@@ -361,6 +361,41 @@ def assemble_walk_supported(K):
     return bool(_lib.load().pzn_assemble_walk_supported(int(K)))
 
 
+def _walk_args(who, score, T, count, max_score, joint_score):
+    """What assemble_walk and assemble_beam take alike, checked -> (score, T, count, max_score, joint_score, Z, K) as the
+    library takes them: no limit is +inf, no joint_score NaN."""
+    for name, t, dt in (("score", score, torch.float32), ("T", T, torch.float32), ("count", count, torch.int32)):
+        if isinstance(t, torch.Tensor) and t.dtype != dt:      # (no silent conversion)
+            raise _lib.PznError(f"{who}: {name} must be {dt}; got {t.dtype}")
+    score, T = _f32(score, "score"), _f32(T, "T")
+    if score.dim() != 3 or score.shape[1] != score.shape[2]:
+        raise _lib.PznError(f"{who}: expected score[Z,K,K]; got {tuple(score.shape)}")
+    Z, K = score.shape[0], score.shape[1]
+    if tuple(T.shape) != (Z, K, K, 4, 4):
+        raise _lib.PznError(f"{who}: expected T[{Z},{K},{K},4,4]; got {tuple(T.shape)}")
+    if count is not None:
+        count = _req(count, torch.int32, "count")
+        if tuple(count.shape) != (Z,):
+            raise _lib.PznError(f"{who}: expected count[{Z}]; got {tuple(count.shape)}")
+    max_score = float("inf") if max_score is None else float(max_score)
+    joint_score = float("nan") if joint_score is None else float(joint_score)
+    if max_score != max_score:
+        raise _lib.PznError(f"{who}: max_score is NaN (None: no limit)")
+    return score, T, count, max_score, joint_score, Z, K
+
+
+def _walk_outputs(Z, K, dev):
+    """-> (root, edges, edge_score, n_edges, G, placed, joints, n_joints), not initialised."""
+    i32 = dict(dtype=torch.int32, device=dev)
+    root, n_edges, n_joints = (torch.empty((Z,), **i32) for _ in range(3))
+    edges = torch.empty((Z, K - 1, 3), **i32)
+    edge_score = torch.empty((Z, K - 1), dtype=torch.float32, device=dev)
+    G = torch.empty((Z, K, 4, 4), dtype=torch.float64, device=dev)
+    placed = torch.empty((Z, K), dtype=torch.uint8, device=dev)
+    joints = torch.empty((Z, K * (K - 1), 2), **i32)
+    return root, edges, edge_score, n_edges, G, placed, joints, n_joints
+
+
 def assemble_walk(score, T, count=None, max_score=None, joint_score=None):
     """The greedy walk over Z pair tables and every walk's joint list in one launch (pzn_assemble_walk_f32; include/pzn.h states
     the rule, assembly.walk_rule is its numpy statement): score [Z,K,K] float32, T [Z,K,K,4,4] float32 (T[z,i,j] maps piece j into
@@ -370,37 +405,14 @@ def assemble_walk(score, T, count=None, max_score=None, joint_score=None):
     G [Z,K,4,4] float64, placed [Z,K] uint8, joints [Z,K(K-1),2] int32, n_joints [Z] int32); unused edge rows are -1 with a score
     of +inf, unused joint rows (-1, -1).  2 <= K <= 64 (PznUnsupported beyond).  Z = 0 launches nothing.  No autograd, nothing
     waits for the device."""
-    for name, t, dt in (("score", score, torch.float32), ("T", T, torch.float32), ("count", count, torch.int32)):
-        if isinstance(t, torch.Tensor) and t.dtype != dt:      # (no silent conversion)
-            raise _lib.PznError(f"assemble_walk: {name} must be {dt}; got {t.dtype}")
-    score, T = _f32(score, "score"), _f32(T, "T")
-    if score.dim() != 3 or score.shape[1] != score.shape[2]:
-        raise _lib.PznError(f"assemble_walk: expected score[Z,K,K]; got {tuple(score.shape)}")
-    Z, K = score.shape[0], score.shape[1]
-    if tuple(T.shape) != (Z, K, K, 4, 4):
-        raise _lib.PznError(f"assemble_walk: expected T[{Z},{K},{K},4,4]; got {tuple(T.shape)}")
-    if count is not None:
-        count = _req(count, torch.int32, "count")
-        if tuple(count.shape) != (Z,):
-            raise _lib.PznError(f"assemble_walk: expected count[{Z}]; got {tuple(count.shape)}")
-    max_score = float("inf") if max_score is None else float(max_score)
-    joint_score = float("nan") if joint_score is None else float(joint_score)
-    if max_score != max_score:
-        raise _lib.PznError("assemble_walk: max_score is NaN (None: no limit)")
+    score, T, count, max_score, joint_score, Z, K = _walk_args("assemble_walk", score, T, count, max_score, joint_score)
     if not assemble_walk_supported(K):
         raise _lib.PznUnsupported(f"assemble_walk: K = {K} pieces (2 <= K <= 64)")
-    dev = score.device
-    i32 = dict(dtype=torch.int32, device=dev)
-    root, n_edges, n_joints = (torch.empty((Z,), **i32) for _ in range(3))
-    edges = torch.empty((Z, K - 1, 3), **i32)
-    edge_score = torch.empty((Z, K - 1), dtype=torch.float32, device=dev)
-    G = torch.empty((Z, K, 4, 4), dtype=torch.float64, device=dev)
-    placed = torch.empty((Z, K), dtype=torch.uint8, device=dev)
-    joints = torch.empty((Z, K * (K - 1), 2), **i32)
-    with _on(dev):
+    out = root, edges, edge_score, n_edges, G, placed, joints, n_joints = _walk_outputs(Z, K, score.device)
+    with _on(score.device):
         _call("pzn_assemble_walk_f32", _p(score), _p(T), _p(count), max_score, joint_score, Z, K, _p(root), _p(edges), _p(edge_score),
               _p(n_edges), _p(G), _p(placed), _p(joints), _p(n_joints), _stream())
-    return root, edges, edge_score, n_edges, G, placed, joints, n_joints
+    return out
 
 
 def assemble_beam_supported(K, beam=4, branch=4):
@@ -414,43 +426,23 @@ def assemble_beam(score, T, moment, count=None, beam=4, branch=4, weight=1.0, ma
     max_score) -> assemble_walk's eight outputs for the cheapest hypothesis, then cost [Z,beam] float64 (slot order, unused
     +inf) and n_hyp [Z] int32.  2 <= K <= 64 (PznUnsupported beyond).  Z = 0 launches nothing.  No autograd, nothing waits
     for the device."""
-    for name, t, dt in (("score", score, torch.float32), ("T", T, torch.float32), ("moment", moment, torch.float64),
-                        ("count", count, torch.int32)):
-        if isinstance(t, torch.Tensor) and t.dtype != dt:      # (no silent conversion)
-            raise _lib.PznError(f"assemble_beam: {name} must be {dt}; got {t.dtype}")
-    score, T = _f32(score, "score"), _f32(T, "T")
-    if score.dim() != 3 or score.shape[1] != score.shape[2]:
-        raise _lib.PznError(f"assemble_beam: expected score[Z,K,K]; got {tuple(score.shape)}")
-    Z, K = score.shape[0], score.shape[1]
-    if tuple(T.shape) != (Z, K, K, 4, 4):
-        raise _lib.PznError(f"assemble_beam: expected T[{Z},{K},{K},4,4]; got {tuple(T.shape)}")
+    if isinstance(moment, torch.Tensor) and moment.dtype != torch.float64:      # (no silent conversion)
+        raise _lib.PznError(f"assemble_beam: moment must be {torch.float64}; got {moment.dtype}")
+    score, T, count, max_score, joint_score, Z, K = _walk_args("assemble_beam", score, T, count, max_score, joint_score)
     moment = _req(moment, torch.float64, "moment")
     if tuple(moment.shape) != (Z, K, 4, 4):
         raise _lib.PznError(f"assemble_beam: expected moment[{Z},{K},4,4]; got {tuple(moment.shape)}")
-    if count is not None:
-        count = _req(count, torch.int32, "count")
-        if tuple(count.shape) != (Z,):
-            raise _lib.PznError(f"assemble_beam: expected count[{Z}]; got {tuple(count.shape)}")
     beam, branch, weight = int(beam), int(branch), float(weight)
-    max_score = float("inf") if max_score is None else float(max_score)
     vote_score = float("nan") if vote_score is None else float(vote_score)
-    joint_score = float("nan") if joint_score is None else float(joint_score)
-    if max_score != max_score:
-        raise _lib.PznError("assemble_beam: max_score is NaN (None: no limit)")
     if weight != weight:
         raise _lib.PznError("assemble_beam: weight is NaN")
     if not assemble_beam_supported(K, beam, branch):
         raise _lib.PznUnsupported(f"assemble_beam: K = {K} pieces, beam = {beam}, branch = {branch} (2 <= K <= 64, 1 <= beam, "
                                   "branch <= 8)")
     dev = score.device
-    i32 = dict(dtype=torch.int32, device=dev)
-    root, n_edges, n_joints, n_hyp = (torch.empty((Z,), **i32) for _ in range(4))
-    edges = torch.empty((Z, K - 1, 3), **i32)
-    edge_score = torch.empty((Z, K - 1), dtype=torch.float32, device=dev)
-    G = torch.empty((Z, K, 4, 4), dtype=torch.float64, device=dev)
-    placed = torch.empty((Z, K), dtype=torch.uint8, device=dev)
-    joints = torch.empty((Z, K * (K - 1), 2), **i32)
+    root, edges, edge_score, n_edges, G, placed, joints, n_joints = _walk_outputs(Z, K, dev)
     cost = torch.empty((Z, beam), dtype=torch.float64, device=dev)
+    n_hyp = torch.empty((Z,), dtype=torch.int32, device=dev)
     with _on(dev):
         _call("pzn_assemble_beam_f32", _p(score), _p(T), _p(moment), _p(count), beam, branch, weight, max_score, vote_score,
               joint_score, Z, K, _p(root), _p(edges), _p(edge_score), _p(n_edges), _p(G), _p(placed), _p(joints), _p(n_joints),

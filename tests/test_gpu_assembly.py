@@ -128,11 +128,11 @@ def test_fallback_equals_fast_path(case, dev, monkeypatch):
     logits to rounding."""
     from puzzlenet_amd import assembly, ops
     calls = []
-    real = ops.pair_head
-    monkeypatch.setattr(ops, "pair_head", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    real = ops.pair_head_blocks
+    monkeypatch.setattr(ops, "pair_head_blocks", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
     fast = assembly.match_pairs(case["model"], case["pieces"].to(dev), k=TOP, start=case["start"])
     assert calls == [1]                                   # the fast path is what ran above
-    monkeypatch.setattr(ops, "pair_head_supported", lambda *a: False)
+    monkeypatch.setattr(ops, "pair_head_blocks_supported", lambda *a: False)
     slow = assembly.match_pairs(case["model"], case["pieces"].to(dev), k=TOP, start=case["start"])
     assert calls == [1]
     assert slow.de_fpcb.shape == fast.de_fpcb.shape
