@@ -417,6 +417,28 @@ int pzn_linear_maxpool_wgrad_f32(const float* dout, const int32_t* argmax,
                                  const float* out, const float* x, int R, int Kin,
                                  int Nout, float* dW, float* db, int accumulate,
                                  pzn_stream_t stream);
+/* A chain of L nn.Linear layers (each + ReLU where relu[i] != 0) on FEW rows, one launch per layer each way and one small
+ * reduce launch at the end (csrc/fewrows.hip): the pose head, model5_b.py:559-569 on cat([ffpc, fmrpc]).
+ *   widths[L + 1] = input width, then every layer's output width; W[i] = [widths[i + 1], widths[i]] dense, bias[i] or NULL.
+ *   The input rows are x0[M, k0] and, when k1 > 0, x1[M, k1] beside them (k0 + k1 = widths[0]): the concatenation is
+ *   never built.  y[i] = [M, widths[i + 1]], i < L: every layer's output, the last one the result (the backward reads all).
+ *   bwd: dy[M, widths[L]] -> dx0[M, k0], dx1[M, k1] (both NULL: no input gradient), dW[i] / db[i] (dW[i] NULL: none for
+ *   layer i; db[i] may be NULL), overwritten, or added to where accumulate[i] != 0.
+ * No atomics: a layer's workgroups store partial sums over chunks of the reduction range, the next launch adds them in a
+ * fixed order while it loads its operand; results are bit-identical from run to run.
+ * widths, W, bias, relu, y, dW, db, accumulate are HOST arrays.  workspace: pzn_fewrow_chain_workspace_bytes bytes.
+ * Limits: 1 <= M <= 128, 1 <= L <= 16, widths[0] >= 256, inner widths > 64, split-precision modes only
+ * (pzn_fewrow_chain_supported: 1 / 0), every device pointer 16-byte aligned: PZN_EUNSUPPORTED otherwise, before any
+ * launch (compose pzn_linear_* then). */
+int pzn_fewrow_chain_supported(int M, int L, const int* widths);
+size_t pzn_fewrow_chain_workspace_bytes(int M, int L, const int* widths);
+int pzn_fewrow_chain_fwd_f32(const float* x0, int k0, const float* x1, int k1, int M, int L, const int* widths,
+                             const float* const* W, const float* const* bias, const int* relu, float* const* y,
+                             void* workspace, size_t workspace_bytes, pzn_stream_t stream);
+int pzn_fewrow_chain_bwd_f32(const float* dy, const float* x0, int k0, const float* x1, int k1, int M, int L,
+                             const int* widths, const float* const* W, const int* relu, const float* const* y,
+                             float* dx0, float* dx1, float* const* dW, float* const* db, const int* accumulate,
+                             void* workspace, size_t workspace_bytes, pzn_stream_t stream);
 /* Matrix-core path of every dense entry point below: 0 = exact fp32 (v_mfma_f32_32x32x2_f32),
  * 1 = bf16x3 split precision (x = x1+x2+x3 in bf16, six v_mfma_f32_32x32x16_bf16 products,
  * fp32 accumulate: fp32-GEMM accuracy at up to 2.67x the matrix-pipe rate), 2 = auto (default;

@@ -41,6 +41,7 @@ SOURCES = [
     ("emd64.hip", NOSLP),
     ("chamfer.hip", NOSLP),
     ("gemm.hip", NOSLP),
+    ("fewrows.hip", NOSLP),
     ("attnfused.hip", NOSLP),
     ("attnchain.hip", NOSLP),
     ("salevel.hip", NOSLP),

@@ -261,6 +261,7 @@ _ATTN_STRIPS = True
 # the per-point stem (:447-448) as one launch each way (csrc/stem.hip, ops.stem) where its shape is supported (B <= 64); False =
 # always the four launches (2 linear + 2 BatchNorm) it replaces, which larger batches use (tests compare the two through this flag)
 _STEM_FUSED = True
+_ROWS_CHAIN = True   # the pose head (:723-725) as the few-row chain of csrc/fewrows.hip; False = cat + one ops.linear per layer (tests compare the two)
 _STEM_TWO = True     # the stem's output under two names (set abstraction / boundary branch): their gradients are added inside its backward launch
 
 
@@ -301,6 +302,19 @@ def run_seq(seq, x):
         x = ops.linear(x, lin.weight, lin.bias, relu=relu)
         i += 2 if relu else 1
     return x
+
+
+def run_seq_parts(seq, parts):
+    """run_seq on cat(parts, -1) for [M, k] row tensors: a Linear / ReLU stack on few rows runs as one chain of launches each
+    way with every part read where it lies (ops.mlp_rows, csrc/fewrows.hip); the concatenation and run_seq otherwise."""
+    mods = list(seq)
+    lins = [m for m in mods if isinstance(m, nn.Linear)]
+    if _ROWS_CHAIN and lins and isinstance(mods[0], nn.Linear) and all(isinstance(m, (nn.Linear, nn.ReLU)) for m in mods):
+        relus = [i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU) for i, m in enumerate(mods) if isinstance(m, nn.Linear)]
+        plain = len(lins) + sum(relus) == len(mods)              # (no ReLU behind a ReLU)
+        if plain and all(p.dim() == 2 for p in parts) and ops.mlp_rows_supported(parts, [m.weight for m in lins], [m.bias for m in lins]):
+            return ops.mlp_rows(parts, [m.weight for m in lins], [m.bias for m in lins], relus)
+    return run_seq(seq, parts[0] if len(parts) == 1 else torch.cat(list(parts), dim=-1))
 
 
 def run_seq_cat_global(seq, x, g):
@@ -422,7 +436,7 @@ class TouchedRegraster(_Base):
 
     def pose_head(self, ffpc, fmrpc):
         """:723-725: tfMLP on the two global features side by side -> the twist [B,6]."""
-        return run_seq(self.tfMLP, torch.cat([ffpc, fmrpc], dim=-1))
+        return run_seq_parts(self.tfMLP, (ffpc, fmrpc))
 
     def moved_branch(self, feat, ready=None, stream=None):
         """:739, :741, :749, :753-754: the moved cloud's per-point features [B,N,64] -> (local [B,N,64], g_max [B,1,64], logits

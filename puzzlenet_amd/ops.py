@@ -1447,6 +1447,119 @@ def linear(x, weight, bias=None, relu=False):
     return _Linear.apply(x, weight, bias, relu)
 
 
+def _ptrs(ts):
+    """Array of device pointers, one per problem, for the nprob entry points."""
+    return (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+
+
+_ROWS_PLANS = {}      # (M, widths) -> (widths as a C array, workspace bytes)
+
+
+def _rows_plan(M, widths):
+    pl = _ROWS_PLANS.get((M, widths))
+    if pl is None:
+        arr = (ctypes.c_int * len(widths))(*widths)
+        pl = _ROWS_PLANS[(M, widths)] = (arr, _lib.load().pzn_fewrow_chain_workspace_bytes(M, len(widths) - 1, arr))
+    return pl
+
+
+def _rows_dense(t):
+    return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+            and t.data_ptr() % 16 == 0)
+
+
+def mlp_rows_supported(parts, weights, biases):
+    """Whether the few-row chain (include/pzn.h, pzn_fewrow_chain_*) takes this stack: one or two [M, k] input parts side
+    by side, M <= 128, dense float32 operands where they lie, the split-precision matrix-core modes."""
+    if not (1 <= len(parts) <= 2 and len(weights) == len(biases) >= 1):
+        return False
+    if not all(_rows_dense(t) and t.dim() == 2 for t in tuple(parts) + tuple(weights)):
+        return False
+    if not all(b is None or (_rows_dense(b) and b.dim() == 1) for b in biases):
+        return False
+    M = parts[0].shape[0]
+    widths = (sum(p_.shape[1] for p_ in parts),) + tuple(w.shape[0] for w in weights)
+    if any(p_.shape[0] != M for p_ in parts) or any(w.shape[1] != k for w, k in zip(weights, widths)):
+        return False
+    if any(b is not None and b.shape[0] != n for b, n in zip(biases, widths[1:])):
+        return False
+    if not (1 <= M <= 128 and len(weights) <= 16):
+        return False
+    return bool(_lib.load().pzn_fewrow_chain_supported(M, len(weights), _rows_plan(M, widths)[0]))
+
+
+class _MlpRows(torch.autograd.Function):
+    """A stack of nn.Linear (+ReLU) on few rows as one chain of launches each way (csrc/fewrows.hip): the same tensors and
+    gradients as the composed ops.linear calls on cat(parts, -1), summed in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, n_parts, relus, *ts):
+        L = len(relus)
+        parts, weights, biases = ts[:n_parts], ts[n_parts:n_parts + L], ts[n_parts + L:]
+        M, k0 = parts[0].shape
+        x1 = parts[1] if n_parts == 2 else None
+        k1 = x1.shape[1] if n_parts == 2 else 0
+        widths = (k0 + k1,) + tuple(w.shape[0] for w in weights)
+        arr, nbytes = _rows_plan(M, widths)
+        dev = parts[0].device
+        ys = [torch.empty((M, n), dtype=torch.float32, device=dev) for n in widths[1:]]
+        ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
+        relu_arr = (ctypes.c_int * L)(*[int(bool(r)) for r in relus])
+        flops = 2 * M * sum(a * b for a, b in zip(widths, widths[1:]))
+        with _on(dev):
+            _call("pzn_fewrow_chain_fwd_f32", _p(parts[0]), k0, _p(x1), k1, M, L, arr, _ptrs(weights), _ptrs(biases), relu_arr,
+                  _ptrs(ys), ws.data_ptr(), nbytes, _stream(), flops=flops)
+        ctx.save_for_backward(*parts, *weights, *ys)
+        ctx.bias_refs = biases
+        ctx.plan = (n_parts, L, M, k0, k1, arr, nbytes, relu_arr, flops)
+        return ys[-1]
+
+    @staticmethod
+    def backward(ctx, dy):
+        n_parts, L, M, k0, k1, arr, nbytes, relu_arr, flops = ctx.plan
+        saved = ctx.saved_tensors
+        parts, weights, ys = saved[:n_parts], saved[n_parts:n_parts + L], saved[n_parts + L:]
+        biases = ctx.bias_refs
+        needs = ctx.needs_input_grad
+        dy = _f32(dy, "dy").reshape(M, weights[-1].shape[0])
+        dev = dy.device
+        dparts = [torch.empty_like(p_) if needs[2 + j] else None for j, p_ in enumerate(parts)]
+        dWs, dbs, tw, tb, acc = [None] * L, [None] * L, [None] * L, [None] * L, [0] * L
+        for i, (w, b) in enumerate(zip(weights, biases)):
+            need_w, need_b = needs[2 + n_parts + i], b is not None and needs[2 + n_parts + L + i]
+            if not (need_w or need_b):
+                continue
+            sw, sb = _sink(w, need_w), _sink(b, need_b)
+            if sw is not None and (sb is not None or b is None):
+                tw[i], tb[i], acc[i] = sw, sb, 1
+            else:
+                dWs[i] = tw[i] = torch.empty_like(w)
+                dbs[i] = tb[i] = None if b is None else torch.empty_like(b)
+        ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
+        with _on(dev):
+            _call("pzn_fewrow_chain_bwd_f32", _p(dy), _p(parts[0]), k0, _p(parts[1]) if n_parts == 2 else None, k1, M, L, arr,
+                  _ptrs(weights), relu_arr, _ptrs(ys), _p(dparts[0]), _p(dparts[1]) if n_parts == 2 else None, _ptrs(tw),
+                  _ptrs(tb), (ctypes.c_int * L)(*acc), ws.data_ptr(), nbytes, _stream(), flops=2 * flops)
+        return (None, None, *dparts, *dWs, *dbs)
+
+
+def mlp_rows(parts, weights, biases, relus=None):
+    """act(... act(cat(parts, -1) W_1^T + b_1) ...) for one or two [M, k] parts: nn.Linear layers with a ReLU behind each
+    where relus[i] (default: behind every layer but the last, the nn.Sequential of model5_b._seq).  Few rows (M <= 128) run
+    as the chain of csrc/fewrows.hip - one launch per layer each way, bit-identical from run to run; every other stack,
+    and the exact-fp32 mode, as the ops.linear calls it stands for."""
+    parts, weights, biases = tuple(parts), tuple(weights), tuple(biases)
+    relus = tuple(i + 1 < len(weights) for i in range(len(weights))) if relus is None else tuple(bool(r) for r in relus)
+    if len(relus) != len(weights):
+        raise _lib.PznError(f"mlp_rows: {len(weights)} layers, {len(relus)} ReLU flags")
+    if mlp_rows_supported(parts, weights, biases):
+        return _MlpRows.apply(len(parts), relus, *parts, *weights, *biases)
+    x = parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
+    for w, b, r in zip(weights, biases, relus):
+        x = linear(x, w, b, relu=r)
+    return x
+
+
 def _f32_rows(t, name):
     """linear_cols takes its operands where they lie: on the GPU, float32, contiguous - no copy is made for it."""
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
@@ -1859,11 +1972,6 @@ def attention_block_supported(x, dk):
 
 def attention_block(x, wq, bq, wk, bk, wv, bv, wo, bo):
     return _AttentionBlock.apply(x, wq, bq, wk, bk, wv, bv, wo, bo)
-
-
-def _ptrs(ts):
-    """Array of device pointers, one per problem, for the nprob entry points."""
-    return (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
 
 
 def attention_chain_fused_available():
