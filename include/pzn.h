@@ -217,6 +217,42 @@ int pzn_assemble_beam_f32(const float* score, const float* T, const double* mome
                           double* G, uint8_t* placed, int32_t* joints, int32_t* n_joints,
                           double* cost, int32_t* n_hyp, pzn_stream_t stream);
 
+/* The forest walk over Z pair tables: a pile of pieces of several objects, sorted and assembled (no counterpart in the
+ * reference; assembly.forest_rule is the numpy statement): one launch, one wavefront per pile, no workspace, no atomics, nothing
+ * waits for the device.  score, T, count, max_score and joint_score are pzn_assemble_walk_f32's; keys, their order and ties, the
+ * stop test, the pose arithmetic and the meaning of count are its own, word for word.  A piece is inside once it has a pose,
+ * outside until then; only pieces < count[z] are either.
+ * Walk: while a piece is outside, a component starts and grows.
+ *   Start: with two or more pieces outside, the root of the new component is the row i of the smallest key among the entries
+ *   (i, j), i != j, with both ends outside (of equal keys the lowest i K + j) - with nothing inside yet, the walk's root -; with
+ *   one piece outside, that piece.  The root's pose is the identity, and it is inside.
+ *   Rounds: the walk's.  A round takes the smallest key among the ordered pairs with exactly one end inside, whichever component
+ *   that end is in, and stops the component at a key that is not finite or at (double)key > max_score.  The new piece's pose is
+ *   G[j] = G[i] T[i,j] or G[i] = G[j] inv(T[i,j]) from the pose of the end inside, and it belongs to the component that is
+ *   growing.  (On a table without -inf every entry between an older component and the outside has failed the stop test already,
+ *   so the end inside is in the growing component and the pose in its root's frame.)
+ * The components are numbered in the order they start; every start places a piece, so there are at most count of them, and a
+ * component may be a single piece.  On a table without -inf they are the connected components of the graph whose edges are the
+ * entries with a finite key <= max_score (single linkage).
+ * Joints: every (i, j), i != j, in the same component, with (double)score[i,j] <= joint_score on the score as stored;
+ * joint_score = NaN means the largest edge score of the pile, and no joint in a pile without an edge.
+ * Out: pzn_assemble_walk_f32's eight outputs - root[Z] = roots[z,0]; edges[Z,K-1,3], edge_score[Z,K-1] and n_edges[Z] over all
+ * components in placement order (at most count - 1 edges); G[Z,K,4,4], piece p into the frame of its own component's root;
+ * placed[Z,K], 1 for every p < count; joints[Z,K(K-1),2] row-major, n_joints[Z] - then component[Z,K] int32 (the component of
+ * every piece, -1 at and beyond count), roots[Z,K] int32 (the root of component q, unused -1) and n_components[Z] int32.  A count
+ * outside [2, K] gives the walk's empty answer, all components -1 and n_components 0.  The first component is the walk's
+ * result: its root, its edges as the first edges, its poses bit for bit; where the walk places every piece, all eight shared
+ * outputs are the walk's.  The same bits on every run.
+ * 2 <= K <= 64 (pzn_assemble_forest_supported: 1 / 0), PZN_EUNSUPPORTED otherwise, before any launch; Z = 0 is a success that
+ * launches nothing. */
+int pzn_assemble_forest_supported(int K);
+int pzn_assemble_forest_f32(const float* score, const float* T, const int32_t* count,
+                            double max_score, double joint_score, int Z, int K,
+                            int32_t* root, int32_t* edges, float* edge_score, int32_t* n_edges,
+                            double* G, uint8_t* placed, int32_t* joints, int32_t* n_joints,
+                            int32_t* component, int32_t* roots, int32_t* n_components,
+                            pzn_stream_t stream);
+
 /* One round of Z progressive walks (no counterpart in the reference; the choice and the ledger of assembly.ProgressiveAssembler
  * for Z puzzles in lockstep): one launch, one wavefront per puzzle, no workspace, no atomics, nothing waits for the device.
  * Slots are not compacted: puzzle z has P slots, a merged part stays in the fixed part's slot i and slot j dies, so a part in

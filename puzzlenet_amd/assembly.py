@@ -41,6 +41,11 @@ The walks over a table:
     the two predictions put the new piece's picked boundary points, read off one 4x4 second-moment matrix per piece
     (boundary_moments) -: the cycles a spanning tree never asks.  One launch (ops.assemble_beam, csrc/assemblebeam.hip;
     beam_rule is its numpy statement).
+  * assemble_forest_batch: the greedy walk for a pile that holds the pieces of several objects.  The walks above grow one tree
+    from one root and leave what it does not reach unplaced; here the pieces left over start a new component from a new root,
+    until every piece is in one - which pieces belong together, and how each group goes together.  One launch
+    (ops.assemble_forest, csrc/assembleforest.hip; forest_rule is its numpy statement).  evaluate_pile / evaluate_pile_batch
+    score a sorted pile against datapipe.pile's answers.
   * refine_assembly / refine_assembly_batch: the step after a walk.  The walk composes pair poses along a spanning tree, so a
     piece's pose carries the summed error of the edges between it and the root, and every accepted joint that is no tree edge
     is never asked.  The placed assembly is a pose graph - every ordered pair of placed pieces whose table score is no larger
@@ -501,16 +506,89 @@ def _rule_outputs(Z, K):
                     np.zeros((Z, K), dtype=np.uint8), np.full((Z, K * (K - 1), 2), -1, dtype=np.int32), np.zeros(Z, dtype=np.int32))
 
 
-def _rule_joints(inside, raw, limit, out):
-    """The joints of a finished walk, row-major: every (i, j), i != j, both inside, with raw[i][j] <= limit, written to the
-    first rows of out [K (K - 1),2] -> their number."""
+def _rule_joints(comp, raw, limit, out):
+    """The joints of a finished walk, row-major: every (i, j), i != j, inside and in one component (comp[p] = the component of
+    piece p, -1 outside), with raw[i][j] <= limit, written to the first rows of out [K (K - 1),2] -> their number."""
     n = 0
-    for i in range(len(inside)):
-        for j in range(len(inside)):
-            if i != j and inside[i] and inside[j] and raw[i][j] <= limit:
+    for i in range(len(comp)):
+        for j in range(len(comp)):
+            if i != j and comp[i] >= 0 and comp[i] == comp[j] and raw[i][j] <= limit:
                 out[n] = (i, j)
                 n += 1
     return n
+
+
+def _rule_table(score, T, count, max_score, who):
+    """What walk_rule and forest_rule read alike -> (S float32 [Z,K,K], P float32 [Z,K,K,4,4], counts [Z], the stop limit)."""
+    S, P = _as_np(score, np.float32), _as_np(T, np.float32)
+    Z, K = S.shape[0], S.shape[1]
+    if S.shape != (Z, K, K) or P.shape != (Z, K, K, 4, 4) or K < 2:
+        raise ValueError(f"{who} expects score[Z,K,K], T[Z,K,K,4,4] with K >= 2; got {S.shape}, {P.shape}")
+    counts = np.full(Z, K, dtype=np.int64) if count is None else _as_np(count, np.int64)
+    return S, P, counts, float("inf") if max_score is None else float(max_score)
+
+
+def _rule_keys(raw, c):
+    """The keys of a puzzle's first c pieces from its scores (float32 values as Python floats): NaN and the diagonal are +inf."""
+    inf = float("inf")
+    return [[inf if (i == j or raw[i][j] != raw[i][j]) else raw[i][j] for j in range(c)] for i in range(c)]
+
+
+def _rule_root(key, inside):
+    """The row of the smallest key among the entries (i, j), i != j, with both ends outside, the first row-major position on ties
+    (two or more pieces are outside)."""
+    best, at = float("inf"), None
+    for i in range(len(key)):
+        for j in range(len(key)):
+            if i != j and not inside[i] and not inside[j] and (at is None or key[i][j] < best):
+                best, at = key[i][j], (i, j)
+    return at[0]
+
+
+def _rule_grow(key, raw, Pz, limit, r, inside, pose, made):
+    """One tree of the walk: r goes inside with the identity, then rounds - the smallest key among the ordered pairs with exactly
+    one end inside, the first row-major position on ties - until none is left or the key is not finite or above limit.  inside
+    and pose {piece: 4x4 as lists} are updated, the edges (i, j, new) appended to made -> the pieces placed, r first."""
+    inf = float("inf")
+    inside[r] = True
+    pose[r] = [[1.0 if u == v else 0.0 for v in range(4)] for u in range(4)]
+    new_ones = [r]
+    while True:
+        best, at = inf, None
+        for i in range(len(key)):
+            for j in range(len(key)):
+                if inside[i] != inside[j] and (at is None or key[i][j] < best):
+                    best, at = key[i][j], (i, j)
+        if at is None or not np.isfinite(best) or best > limit:
+            return new_ones
+        i, j = at
+        Tij = Pz[i, j].astype(np.float64).tolist()
+        if inside[i]:
+            new = j
+            pose[j] = _rule_product(pose[i], Tij)
+        else:
+            new = i
+            pose[i] = _rule_product(pose[j], _rule_inverse(Tij))
+        inside[new] = True
+        new_ones.append(new)
+        made.append((i, j, new))
+
+
+def _rule_finish(z, out, S, raw, made, pose, comp, joint_score):
+    """The outputs of puzzle z behind its root from its edges, poses and components (comp [c], -1 outside)."""
+    _, edges, edge_score, n_edges, G, placed, joints, n_joints = out[:8]
+    worst = -float("inf")
+    for e, (i, j, new) in enumerate(made):
+        edges[z, e] = (i, j, new)
+        edge_score[z, e] = S[z, i, j]
+        worst = max(worst, raw[i][j])
+    n_edges[z] = len(made)
+    for p, g in pose.items():
+        G[z, p] = np.array(g, dtype=np.float64)
+    placed[z, :len(comp)] = [q >= 0 for q in comp]
+    js = worst if joint_score is None or joint_score != joint_score else float(joint_score)      # (NaN is the kernel's None)
+    if made:
+        n_joints[z] = _rule_joints(comp, raw, js, joints[z])
 
 
 def walk_rule(score, T, count=None, max_score=None, joint_score=None):
@@ -524,58 +602,60 @@ def walk_rule(score, T, count=None, max_score=None, joint_score=None):
     i, j < count[z] exist.  The root is the row of the smallest key; a round takes the smallest key among the ordered pairs with
     exactly one end placed and stops at a key that is not finite or above max_score.  Poses are composed in float64 with every
     operation rounded on its own (_rule_product, _rule_inverse).  joint_score None: the puzzle's largest edge score."""
-    S, P = _as_np(score, np.float32), _as_np(T, np.float32)
+    S, P, counts, limit = _rule_table(score, T, count, max_score, "walk_rule")
     Z, K = S.shape[0], S.shape[1]
-    if S.shape != (Z, K, K) or P.shape != (Z, K, K, 4, 4) or K < 2:
-        raise ValueError(f"walk_rule expects score[Z,K,K], T[Z,K,K,4,4] with K >= 2; got {S.shape}, {P.shape}")
-    counts = np.full(Z, K, dtype=np.int64) if count is None else _as_np(count, np.int64)
-    inf = float("inf")
-    limit = inf if max_score is None else float(max_score)
-    out = root, edges, edge_score, n_edges, G, placed, joints, n_joints = _rule_outputs(Z, K)
+    out = _rule_outputs(Z, K)
     for z in range(Z):
         c = int(counts[z])
         if not 2 <= c <= K:
             continue
         raw = S[z].tolist()                              # float32 values as Python floats (exact)
-        key = [[inf if (i == j or raw[i][j] != raw[i][j]) else raw[i][j] for j in range(c)] for i in range(c)]
-        best, at = inf, (0, 0)                           # the first row-major position of the smallest key
-        for i in range(c):
-            for j in range(c):
-                if key[i][j] < best:
-                    best, at = key[i][j], (i, j)
-        r = at[0]
-        root[z] = r
-        inside = [False] * c
-        inside[r] = True
-        pose = {r: [[1.0 if u == v else 0.0 for v in range(4)] for u in range(4)]}
-        worst = -inf
-        for e in range(c - 1):
-            best, at = inf, None
-            for i in range(c):
-                for j in range(c):
-                    if inside[i] != inside[j] and (at is None or key[i][j] < best):
-                        best, at = key[i][j], (i, j)
-            if at is None or not np.isfinite(best) or best > limit:
-                break
-            i, j = at
-            Tij = P[z, i, j].astype(np.float64).tolist()
-            if inside[i]:
-                new = j
-                pose[j] = _rule_product(pose[i], Tij)
-            else:
-                new = i
-                pose[i] = _rule_product(pose[j], _rule_inverse(Tij))
-            inside[new] = True
-            edges[z, e] = (i, j, new)
-            edge_score[z, e] = S[z, i, j]
-            worst = max(worst, raw[i][j])
-            n_edges[z] = e + 1
-        for p, g in pose.items():
-            G[z, p] = np.array(g, dtype=np.float64)
-        placed[z, :c] = inside
-        js = worst if joint_score is None or joint_score != joint_score else float(joint_score)      # (NaN is the kernel's None)
-        if n_edges[z] > 0:
-            n_joints[z] = _rule_joints(inside, raw, js, joints[z])
+        key = _rule_keys(raw, c)
+        inside, pose, made = [False] * c, {}, []
+        out.root[z] = _rule_root(key, inside)
+        _rule_grow(key, raw, P[z], limit, int(out.root[z]), inside, pose, made)
+        _rule_finish(z, out, S, raw, made, pose, [0 if p else -1 for p in inside], joint_score)
+    return out
+
+
+ForestRule = collections.namedtuple("ForestRule", WalkRule._fields + ("component", "roots", "n_components"))
+
+
+def forest_rule(score, T, count=None, max_score=None, joint_score=None):
+    """The numpy statement of ops.assemble_forest (csrc/assembleforest.hip, the rule in include/pzn.h), which is held to it bit
+    for bit, G included: walk_rule for a pile that holds the pieces of several objects.  The arguments, the keys, their order and
+    ties, the stop test, the pose arithmetic and count are walk_rule's (its helpers run here).  Where the walk stops with pieces
+    < count still outside, a new component starts: its root is the row of the smallest key among the entries with both ends
+    outside (_rule_root - with nothing inside, the walk's root), or the one piece left; the root is inside with the identity, and
+    the rounds go on, over the ordered pairs with exactly one end inside whichever component that end is in, until no piece is
+    outside.  -> ForestRule: WalkRule's fields - root = roots[:, 0], the edges of all components in placement order, G[p] into
+    the frame of piece p's own root, placed 1 for every p < count, joints only inside a component (joint_score None: the pile's
+    largest edge score; no joint in a pile without an edge) - then component [Z,K] int32 (in the order the components start, -1 at
+    and beyond count), roots [Z,K] int32 (unused -1) and n_components [Z] int32.  A count outside [2, K]: the walk's empty answer
+    and no component.
+
+    On a table without -inf every entry between an older component and the outside has failed the stop test, so a round's end
+    inside is in the growing component, and the components are the connected components of the graph whose edges are the entries
+    with a finite key <= max_score.  The first component is walk_rule's result."""
+    S, P, counts, limit = _rule_table(score, T, count, max_score, "forest_rule")
+    Z, K = S.shape[0], S.shape[1]
+    out = ForestRule(*_rule_outputs(Z, K), np.full((Z, K), -1, dtype=np.int32), np.full((Z, K), -1, dtype=np.int32),
+                     np.zeros(Z, dtype=np.int32))
+    for z in range(Z):
+        c = int(counts[z])
+        if not 2 <= c <= K:
+            continue
+        raw = S[z].tolist()                              # float32 values as Python floats (exact)
+        key = _rule_keys(raw, c)
+        inside, pose, made = [False] * c, {}, []
+        q = 0
+        while not all(inside):
+            r = inside.index(False) if inside.count(False) == 1 else _rule_root(key, inside)
+            out.roots[z, q] = r
+            out.component[z, _rule_grow(key, raw, P[z], limit, r, inside, pose, made)] = q
+            q += 1
+        out.root[z], out.n_components[z] = out.roots[z, 0], q
+        _rule_finish(z, out, S, raw, made, pose, out.component[z, :c].tolist(), joint_score)
     return out
 
 
@@ -603,6 +683,134 @@ def assemble_batch(score, T, count=None, max_score=None, joint_score=None):
     root, edges, edge_score, n_edges, G, placed, joints, n_joints = ops.assemble_walk(score, T, count, max_score, joint_score)
     placed, movable = _placed_movable(placed, root)
     return AssemblyBatch(root, edges, edge_score, n_edges, G, placed, movable, joints, n_joints)
+
+
+# --------------------------------------------------------------------------- a pile of several objects: the forest walk
+
+ForestBatch = collections.namedtuple("ForestBatch", AssemblyBatch._fields + ("component", "roots", "n_components"))
+PileEvaluation = collections.namedtuple("PileEvaluation", "pair_precision pair_recall pair_pose_recall n_components exact msd")
+
+
+def assemble_forest_batch(score, T, count=None, max_score=None, joint_score=None):
+    """assemble_batch for piles that hold the pieces of several objects, ONE launch for Z piles (ops.assemble_forest; forest_rule
+    is its numpy statement): where the greedy walk stops with pieces left over, the pieces outside start a new component from a
+    new root, until every piece < count is in one - which pieces belong together, and how each group goes together.  With
+    refine > 0 a table's score is the distance of the two picked boundaries where they meet, so max_score is a geometric
+    threshold: the components are the connected components of the entries below it.  The arguments are assemble_batch's ->
+    ForestBatch: AssemblyBatch's fields (root = roots[:, 0]; edges over all components in placement order; G [Z,K,4,4] float64,
+    each piece into the frame of its own component's root; placed: every piece < count; movable = placed and not the root of any
+    component; joints only inside a component), then component [Z,K] int32 (-1 at and beyond count), roots [Z,K] int32 (the root
+    of component q, unused -1) and n_components [Z] int32.  refine_assembly_batch takes it as it takes an AssemblyBatch: no joint
+    crosses components and no root moves, so its one launch refines every component of every pile.  Nothing waits for the
+    device."""
+    root, edges, edge_score, n_edges, G, placed, joints, n_joints, component, roots, n_components = ops.assemble_forest(
+        score, T, count, max_score, joint_score)
+    with torch.no_grad():
+        placed = placed.bool()
+        index = torch.arange(placed.shape[1], dtype=torch.int32, device=placed.device)
+        is_root = (roots[:, :, None] == index[None, None, :]).any(dim=1)
+    return ForestBatch(root, edges, edge_score, n_edges, G, placed, placed & ~is_root, joints, n_joints, component, roots,
+                       n_components)
+
+
+def _pile_msd(G, X, R):
+    """msd [...,K,K] of evaluate_pile for G, X = pose [...,K,4,4] and R = rest [...,K,n,3], float64 numpy arrays or torch tensors
+    alike: msd[p,q] = the mean over x = X[q] R[q] of |inv(G[p]) G[q] x - X[p] inv(X[q]) x|^2 with the rigid inverse.  Written
+    with element-wise operations in one order (the walk rule's dot4 and inverse), so that the difference of the two relative
+    poses - a difference of nearly equal matrices for a good assembly - has the same bits on the host and on the device."""
+    xp = torch if isinstance(G, torch.Tensor) else np
+    K = X.shape[-3]
+
+    def inv_rows(T):            # rows 0..2 of [R^T, -(R^T t)], entries [...,K]
+        return [[T[..., v, u] for v in range(3)]
+                + [-((T[..., 0, u] * T[..., 0, 3] + T[..., 1, u] * T[..., 1, 3]) + T[..., 2, u] * T[..., 2, 3])] for u in range(3)]
+
+    Gi, Xi = inv_rows(G), inv_rows(X)
+    last = (0.0, 0.0, 0.0, 1.0)                                                    # the last row of a rigid motion
+    x = [((X[..., c, 0, None] * R[..., 0] + X[..., c, 1, None] * R[..., 1]) + X[..., c, 2, None] * R[..., 2]) + X[..., c, 3, None]
+         for c in range(3)]                                                        # the moved pieces' coordinates, [...,K,n] each
+    rows = []
+    for p in range(K):
+        sq = None
+        for u in range(3):
+            # row u of inv(G[p]) G[q] - X[p] inv(X[q]) for every q: four entries [...,K]
+            D = [_dot4(Gi[u][0][..., p, None], G[..., 0, v], Gi[u][1][..., p, None], G[..., 1, v], Gi[u][2][..., p, None], G[..., 2, v],
+                       Gi[u][3][..., p, None], G[..., 3, v])
+                 - _dot4(X[..., p, None, u, 0], Xi[0][v], X[..., p, None, u, 1], Xi[1][v], X[..., p, None, u, 2], Xi[2][v],
+                         X[..., p, None, u, 3], last[v]) for v in range(4)]
+            d = ((D[0][..., None] * x[0] + D[1][..., None] * x[1]) + D[2][..., None] * x[2]) + D[3][..., None]
+            sq = d * d if sq is None else sq + d * d
+        rows.append(sq.mean(-1))
+    return xp.stack(rows, -2)
+
+
+def _pile_masks(component, object_of, live, off):
+    """-> (together, belong) [...,K,K] bool over the ordered pairs p != q (off: the [K,K] off-diagonal) of live pieces [...,K]: in
+    one component, of one object.  numpy arrays or torch tensors."""
+    pairs = live[..., :, None] & live[..., None, :] & off
+    together = pairs & (component[..., :, None] == component[..., None, :]) & (component[..., :, None] >= 0)
+    return together, pairs & (object_of[..., :, None] == object_of[..., None, :])
+
+
+def evaluate_pile(G, component, pose, rest, object_of, count=None, tol=0.01):
+    """The score of a sorted and assembled pile against the truth, on the host in float64.  G [K,4,4] maps piece p into the frame
+    of its component's root, component [K] (assemble_forest_batch's of one pile; pieces with the same value >= 0 are together),
+    pose [K,4,4], rest [K,n,3] and object_of [K] are datapipe.pile's of one pile; only pieces < count are counted (None: K).
+    Over the ordered pairs (p, q), p != q: together = in one component, belong = of one object, and msd[p,q] = the mean over
+    the points x = pose[q] rest[q] of moved piece q of |inv(G[p]) G[q] x - pose[p] inv(pose[q]) x|^2: how far the assembly puts
+    q from where it belongs, seen from p.  -> PileEvaluation:
+      pair_precision      together & belong over together
+      pair_recall         together & belong over belong
+      pair_pose_recall    together & belong & (msd < tol) over belong; tol is evaluate's definition, not a measurement
+      n_components        the number of components among the pieces counted
+      exact               the components are the objects
+      msd [K,K]           float64
+    An empty denominator gives NaN.  Pairs are counted and not pieces: a share of pieces in the right component is inflated by
+    singletons, which are trivially right, and here a singleton only costs recall."""
+    G, X, R = _host(G), _host(pose), _host(rest)
+    comp, obj = _as_np(component, np.int64), _as_np(object_of, np.int64)
+    K = X.shape[0]
+    if G.shape != (K, 4, 4) or X.shape != (K, 4, 4) or R.ndim != 3 or R.shape[0] != K or R.shape[2] != 3 or comp.shape != (K,) \
+            or obj.shape != (K,):
+        raise ValueError(f"evaluate_pile expects G[K,4,4], component[K], pose[K,4,4], rest[K,n,3], object_of[K]; got {G.shape}, "
+                         f"{comp.shape}, {X.shape}, {R.shape}, {obj.shape}")
+    live = np.arange(K) < (K if count is None else int(count))
+    together, belong = _pile_masks(comp, obj, live, ~np.eye(K, dtype=bool))
+    msd = _pile_msd(G, X, R)
+    both = together & belong
+    with np.errstate(invalid="ignore"):
+        ratios = [float(np.float64(a.sum()) / np.float64(b.sum())) for a, b in
+                  ((both, together), (both, belong), (both & (msd < tol), belong))]
+    return PileEvaluation(*ratios, len(set(comp[live & (comp >= 0)].tolist())), bool((together == belong).all()), msd)
+
+
+def evaluate_pile_batch(G, component, pose, rest, object_of, count=None, tol=0.01):
+    """evaluate_pile() for Z piles in float64 torch on the device, with its formulas in its order of operations: G [Z,K,4,4]
+    (assemble_forest_batch's, or refine_assembly_batch's), component [Z,K], pose [Z,K,4,4], rest [Z,K,n,3], object_of [Z,K]
+    (datapipe.pile's), count [Z] (integers on the device) or None -> PileEvaluation of tensors: the three ratios [Z] float64 (NaN
+    for an empty denominator), n_components [Z] int64, exact [Z] bool, msd [Z,K,K] float64.  K passes of element-wise work on
+    [Z,K,n] values, no [Z,K,K,n] intermediate.  Nothing waits for the device."""
+    _on_gpu("evaluate_pile_batch", G=G, component=component, pose=pose, rest=rest, object_of=object_of)
+    if pose.dim() != 4 or tuple(pose.shape[2:]) != (4, 4):
+        raise _lib.PznError(f"evaluate_pile_batch expects pose[Z,K,4,4]; got {tuple(pose.shape)}")
+    Z, K = pose.shape[0], pose.shape[1]
+    if tuple(G.shape) != (Z, K, 4, 4) or tuple(component.shape) != (Z, K) or tuple(object_of.shape) != (Z, K) or rest.dim() != 4 \
+            or tuple(rest.shape[:2]) != (Z, K) or rest.shape[3] != 3 or (count is not None and tuple(count.shape) != (Z,)):
+        raise _lib.PznError(f"evaluate_pile_batch expects G[{Z},{K},4,4], component[{Z},{K}], rest[{Z},{K},n,3], object_of[{Z},{K}], "
+                            f"count[{Z}]; got {tuple(G.shape)}, {tuple(component.shape)}, {tuple(rest.shape)}, "
+                            f"{tuple(object_of.shape)}")
+    with torch.no_grad():
+        comp = component.long()
+        index = torch.arange(K, device=comp.device)
+        live = index[None, :] < count[:, None] if count is not None else torch.ones_like(comp, dtype=torch.bool)
+        together, belong = _pile_masks(comp, object_of.long(), live, index[:, None] != index[None, :])
+        msd = _pile_msd(G.double(), pose.double(), rest.double())
+        both = together & belong
+        n = lambda m: m.sum(dim=(1, 2)).double()
+        # a piece opens its component when no counted piece before it is in the same one
+        opens = live & (comp >= 0) & ~(together & (index[None, :] < index[:, None])).any(dim=2)
+        return PileEvaluation(n(both) / n(together), n(both) / n(belong), n(both & (msd < tol)) / n(belong), opens.sum(dim=1),
+                              (together == belong).all(dim=2).all(dim=1), msd)
 
 
 # --------------------------------------------------------------------------- the beam walk scored by the placed pieces' votes
@@ -762,7 +970,7 @@ def beam_rule(score, T, moment, count=None, beam=4, branch=4, weight=1.0, max_sc
             placed[z, :c] = inside
             js = worst if joint_score is None or joint_score != joint_score else float(joint_score)
             if es:
-                n_joints[z] = _rule_joints(inside, raw, js, joints[z])
+                n_joints[z] = _rule_joints(np.where(inside, 0, -1), raw, js, joints[z])
     return BeamRule(*out, cost, n_hyp)
 
 

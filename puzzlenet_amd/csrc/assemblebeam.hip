@@ -274,7 +274,7 @@ __global__ __launch_bounds__(AB_T) void assemble_beam_kernel(const float* __rest
     if (lane < B) cost[(size_t)z * B + lane] = lane < H ? hcost[cur * B + lane] : __builtin_inf();
 
     // the placed bytes and the joints, by the walk's rule from the result's own edges
-    const int nj = walk_tail(in, c, K, ne, worst, joint_score, S, lane, placed + (size_t)z * K, joints + (size_t)z * JR * 2);
+    const int nj = walk_tail(in, c, K, ne, worst, joint_score, S, lane, 0, placed + (size_t)z * K, joints + (size_t)z * JR * 2);
     if (lane == 0) root[z] = r, n_edges[z] = ne, n_joints[z] = nj, n_hyp[z] = H;
     pzn::wave_lds_sync();      // the hypotheses are replaced by the next puzzle's
   }

@@ -126,7 +126,7 @@ __global__ __launch_bounds__(AW_T) void assemble_walk_kernel(const float* __rest
     }
     for (int e = lane; e < 16 * K; e += PZN_WAVE) G[(size_t)z * K * 16 + e] = g[e];
 
-    const int nj = walk_tail(in, c, K, ne, worst, joint_score, S, lane, placed + (size_t)z * K, joints + (size_t)z * JR * 2);
+    const int nj = walk_tail(in, c, K, ne, worst, joint_score, S, lane, 0, placed + (size_t)z * K, joints + (size_t)z * JR * 2);
     if (lane == 0) root[z] = r, n_edges[z] = ne, n_joints[z] = nj;
     pzn::wave_lds_sync();      // the poses are replaced by the next puzzle's
   }

@@ -1,6 +1,6 @@
-// pzn_walk.h — what the walks over pair tables share (assemblewalk.hip, assemblebeam.hip, progressive.hip): the key of a table
+// pzn_walk.h — what the walks over pair tables share (assemblewalk.hip, assemblebeam.hip, assembleforest.hip, progressive.hip): the key of a table
 // entry, the 64-lane lexicographic arg-min over (key, i K + j), the stop test on a round's winning key, the order-fixed float64
-// dot product the poses are composed with, and the tail of a walk's result (assemblewalk.hip, assemblebeam.hip): the placed
+// dot product the poses are composed with, and the tail of a walk's result (the three assemble*.hip): the placed
 // bytes and the joint list.  One statement of each, so "the smallest key, the lowest i K + j on ties", "the walk stops here"
 // and "every operation rounded on its own" mean the same in every kernel.  Files that include it are built with
 // -ffp-contract=off and say so again with the pragma.
@@ -52,13 +52,14 @@ __device__ __forceinline__ double dot4(double a0, double b0, double a1, double b
 }
 
 // The tail of a walk's result for one puzzle, by its wavefront: `in` is the placed set (bit p = piece p), c the puzzle's
-// pieces, ne its edges, worst its largest edge score, S its [K,K] scores; placed [K] and joints [K (K - 1), 2] are the puzzle's
-// rows of the outputs -> the number of joints.  The joints are the placed i != j with (double)score[i,j] <= limit on the raw
-// score, limit = joint_score or (NaN) worst: for every placed row i in turn, lane j tests entry (i, j) (a coalesced row) and
-// the ballot's prefix count is the place of (i, j) after the joints of the rows before - row-major order with no scan through
+// pieces, ne its edges, worst its largest edge score, S its [K,K] scores, my_comp the component of piece `lane` (read for placed
+// pieces only; the one-tree walks pass 0); placed [K] and joints [K (K - 1), 2] are the puzzle's rows of the outputs -> the
+// number of joints.  The joints are the placed i != j of one component with (double)score[i,j] <= limit on the raw score,
+// limit = joint_score or (NaN) worst: for every placed row i in turn, lane j tests entry (i, j) (a coalesced row) and the
+// ballot's prefix count is the place of (i, j) after the joints of the rows before - row-major order with no scan through
 // memory.  Unused rows are (-1, -1).  (`in`, c, ne and the count are the same in every lane.)
 __device__ __forceinline__ int walk_tail(uint64_t in, int c, int K, int ne, double worst, double joint_score,
-                                         const float* __restrict__ S, int lane, uint8_t* __restrict__ placed,
+                                         const float* __restrict__ S, int lane, int my_comp, uint8_t* __restrict__ placed,
                                          int32_t* __restrict__ joints) {
   if (lane < K) placed[lane] = (uint8_t)((in >> lane) & 1);
   const double limit = joint_score != joint_score ? worst : joint_score;
@@ -66,8 +67,9 @@ __device__ __forceinline__ int walk_tail(uint64_t in, int c, int K, int ne, doub
   if (ne > 0) {
     for (int i = 0; i < c; ++i) {
       if (!((in >> i) & 1)) continue;
+      const int comp_i = __builtin_amdgcn_readlane(my_comp, i);
       bool ok = false;
-      if (lane < c && lane != i && ((in >> lane) & 1)) ok = (double)S[i * K + lane] <= limit;
+      if (lane < c && lane != i && ((in >> lane) & 1) && my_comp == comp_i) ok = (double)S[i * K + lane] <= limit;
       const uint64_t m = __ballot(ok);
       if (ok) {
         const int at = nj + __popcll(m & (((uint64_t)1 << lane) - 1));

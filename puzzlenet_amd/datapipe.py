@@ -1072,6 +1072,43 @@ def fracture(raw, normals, u_anchor, u_start, twist, n=1024, n_min=None, k=128, 
     return CurvedFracture(*f, anchor, frames, half_curv) if curved else f
 
 
+Pile = collections.namedtuple("Pile", "pieces pose rest object_of source mates cd ok")
+Pile.__doc__ = """Z piles that hold the pieces of Q objects each, with their answers (datapipe.pile): pieces [Z,K,n,3] the moved pieces
+(K = Q P; assembly.match_puzzles takes them), pose [Z,K,4,4], rest [Z,K,n,3], object_of [Z,K] int32 the object 0 .. Q-1 of every
+piece, source [Z,K] int32 its slot q P + p before the shuffle, mates [Z,K,K] bool the fracture's inside an object and False across,
+cd [Z,K,K] float32 the fracture's inside an object and +inf across, ok [Z] bool (every object of the pile is ok)."""
+
+
+def pile(frac, objects, perm=None):
+    """Regroup a Fracture or CurvedFracture of B = Z Q samples into Z piles of the pieces of Q = `objects` objects each: pile z holds
+    the K = Q P pieces of samples z Q .. z Q + Q - 1, piece p of object q in slot q P + p, then shuffled: position k of pile z
+    holds slot perm[z,k] (perm [Z,K] int64, every row a permutation of 0 .. K-1, on the fracture's device; None: the identity),
+    so the objects are no contiguous blocks.  -> Pile.  assembly.truth_table(pile.pose[z], pile.mates[z], pile.cd[z]) is the table
+    a perfect matcher returns for pile z, +inf between the objects.  Indexing only, on the device the fracture lives on; nothing
+    waits for it."""
+    Q = int(objects)
+    B, P = frac.pose.shape[0], frac.pose.shape[1]
+    if Q < 1 or B % Q:
+        raise _lib.PznError(f"pile: objects = {Q} does not divide the fracture's B = {B} samples")
+    Z, K = B // Q, Q * P
+    dev = frac.pose.device
+    if perm is None:
+        perm = torch.arange(K, dtype=torch.int64, device=dev).expand(Z, K)
+    if not isinstance(perm, torch.Tensor) or perm.dtype != torch.int64 or tuple(perm.shape) != (Z, K) or perm.device != dev:
+        raise _lib.PznError(f"pile: perm as int64 [Z, K] = [{Z}, {K}] on {dev}; got {getattr(perm, 'dtype', type(perm))} "
+                            f"{tuple(getattr(perm, 'shape', ()))}")
+    z = torch.arange(Z, device=dev)[:, None]
+    pieces, pose, rest = (t.reshape(Z, K, *t.shape[2:])[z, perm] for t in (frac.pieces, frac.pose, frac.rest))
+    object_of = perm // P
+    same = object_of[:, :, None] == object_of[:, None, :]
+    # entry (a, c) of a pile is entry (p_a, p_c) of its object's sample where a and c are of one object (masked elsewhere)
+    b = z[:, :, None] * Q + object_of[:, :, None]
+    pa, pc = (perm % P)[:, :, None], (perm % P)[:, None, :]
+    mates = frac.mates[b, pa, pc] & same
+    cd = torch.where(same, frac.cd[b, pa, pc], frac.cd.new_full((), float("inf")))
+    return Pile(pieces, pose, rest, object_of.to(torch.int32), perm.to(torch.int32), mates, cd, frac.ok.view(Z, Q).all(dim=1))
+
+
 def _fracture_cols(P, K):       # normals, anchor draws, start fractions, twists
     return _cols(3 * (P - 1) * K, (P - 1) * K, P, 6 * P)
 

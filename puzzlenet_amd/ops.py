@@ -415,6 +415,32 @@ def assemble_walk(score, T, count=None, max_score=None, joint_score=None):
     return out
 
 
+def assemble_forest_supported(K):
+    return bool(_lib.load().pzn_assemble_forest_supported(int(K)))
+
+
+def assemble_forest(score, T, count=None, max_score=None, joint_score=None):
+    """The forest walk over Z pair tables - a pile of pieces of several objects sorted into components, each assembled in its own
+    root's frame - and every component's joints in one launch (pzn_assemble_forest_f32; include/pzn.h states the rule,
+    assembly.forest_rule is its numpy statement): the arguments are assemble_walk's -> its eight outputs in its shapes and types
+    (root = roots[:, 0]; edges over all components in placement order; placed is 1 for every piece < count; joints never cross
+    components), then component [Z,K] int32 (-1 at and beyond count), roots [Z,K] int32 (the root of component q, unused -1) and
+    n_components [Z] int32.  2 <= K <= 64 (PznUnsupported beyond).  Z = 0 launches nothing.  No autograd, nothing waits for the
+    device."""
+    score, T, count, max_score, joint_score, Z, K = _walk_args("assemble_forest", score, T, count, max_score, joint_score)
+    if not assemble_forest_supported(K):
+        raise _lib.PznUnsupported(f"assemble_forest: K = {K} pieces (2 <= K <= 64)")
+    dev = score.device
+    root, edges, edge_score, n_edges, G, placed, joints, n_joints = _walk_outputs(Z, K, dev)
+    component, roots = (torch.empty((Z, K), dtype=torch.int32, device=dev) for _ in range(2))
+    n_components = torch.empty((Z,), dtype=torch.int32, device=dev)
+    with _on(dev):
+        _call("pzn_assemble_forest_f32", _p(score), _p(T), _p(count), max_score, joint_score, Z, K, _p(root), _p(edges),
+              _p(edge_score), _p(n_edges), _p(G), _p(placed), _p(joints), _p(n_joints), _p(component), _p(roots), _p(n_components),
+              _stream())
+    return root, edges, edge_score, n_edges, G, placed, joints, n_joints, component, roots, n_components
+
+
 def assemble_beam_supported(K, beam=4, branch=4):
     return bool(_lib.load().pzn_assemble_beam_supported(int(K), int(beam), int(branch)))
 

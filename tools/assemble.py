@@ -2,7 +2,7 @@
 assembled cloud.
 
     python tools/assemble.py --pieces pieces.npy [--ckpt model.ckpt] [--k 128] [--max-score S] [--out PREFIX] [--progressive]
-                             [--refine N] [--joint N] [--gt PREFIX_gt.npz] [--beam B] [--branch C] [--vote-weight W]
+                             [--refine N] [--joint N] [--gt PREFIX_gt.npz] [--beam B] [--branch C] [--vote-weight W] [--forest]
 
 pieces.npy holds [K, N, 3] float32 (N = the model's points per piece).  Prints the score table and the edges in
 placement order, writes PREFIX_G.npy ([K,4,4], each piece into the root's frame) and PREFIX_cloud.npy ([K,N,3]).
@@ -17,6 +17,11 @@ PREFIX_G.npy and PREFIX_cloud.npy are then the refined ones, and with --gt the a
 --beam B (the table walk only, with --branch C and --vote-weight W): the beam walk of assembly.assemble_beam_batch in place of the
 greedy one - B hypotheses, each extended by its C smallest entries, a child charged W times what the other placed pieces'
 entries say against its pose -; everything after the walk is the same.
+--forest (the table walk only): the pieces may be a pile of several objects - the forest walk of assembly.assemble_forest_batch in
+place of the greedy one: where the walk stops (a score that is not finite or above --max-score), the pieces left over start a new
+component from a new root, until every piece is in one.  Prints the components; PREFIX_G.npy maps each piece into the frame of its
+own component's root, PREFIX_component.npy holds the component of every piece, and --joint N refines every component in one launch
+(assembly.refine_assembly_batch).  Not with --gt, which holds the truth of one object.
 --gt PREFIX_gt.npz (written by tools/fracture.py beside the pieces): the assembly is scored against the truth - per piece the
 rotation error in degrees, the translation error and the mean squared distance of its points from where they belong, the share
 of pieces placed right (assembly.evaluate) and, for the greedy walk, the share of its edges between pieces that touch.
@@ -39,6 +44,28 @@ def report(ev):
     print(f"part accuracy {ev.part_accuracy:.3f}" + ("" if ev.edge_precision is None else f", edge precision {ev.edge_precision:.3f}"))
 
 
+def forest(args, x, table):
+    """--forest: the forest walk over the table of a pile, its components, and with --joint their refinement in one launch."""
+    from puzzlenet_amd import assembly
+    one = assembly.PairTable(*(f[None] for f in table))
+    fb = assembly.assemble_forest_batch(one.score, one.T, max_score=args.max_score)
+    G = fb.G[0]
+    comp, n, nc = fb.component[0].tolist(), int(fb.n_edges[0]), int(fb.n_components[0])
+    for (i, j, new), s in zip(fb.edges[0, :n].tolist(), fb.edge_score[0, :n].tolist()):
+        print(f"  place piece {new} in component {comp[new]}: pair (fixed {i}, moved {j}), score {s:.6f}")
+    for q, r in enumerate(fb.roots[0, :nc].tolist()):
+        print(f"component {q}: root piece {r}, pieces {[p for p, c in enumerate(comp) if c == q]}")
+    if args.joint:
+        jr = assembly.refine_assembly_batch(x[None], one, fb, sweeps=args.joint)
+        G = jr.G[0].double()
+        print(f"joint refinement over {int(fb.n_joints[0])} joints: summed score {float(jr.score0[0]):.6f} -> {float(jr.score[0]):.6f}, "
+              f"{int(jr.sweeps_used[0])} sweeps, candidates taken per piece {jr.accepted[0].tolist()}")
+    np.save(args.out + "_G.npy", G.cpu().numpy())
+    np.save(args.out + "_component.npy", np.asarray(comp, dtype=np.int32))
+    np.save(args.out + "_cloud.npy", assembly.apply(x, G).cpu().numpy())
+    print(f"wrote {args.out}_G.npy, {args.out}_component.npy, {args.out}_cloud.npy (every component in its own root's frame)")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--pieces", required=True, help=".npy file with [K, N, 3] float32 pieces")
@@ -55,7 +82,10 @@ def main():
     ap.add_argument("--beam", type=int, default=0, help="B: the beam walk with B hypotheses in place of the greedy walk (1 .. 8; 0: greedy)")
     ap.add_argument("--branch", type=int, default=4, help="C: with --beam, the candidates every hypothesis is extended by (1 .. 8)")
     ap.add_argument("--vote-weight", type=float, default=1.0, help="W: with --beam, the weight of the placed pieces' votes in a child's cost")
+    ap.add_argument("--forest", action="store_true", help="a pile of several objects: the forest walk, a component per object")
     args = ap.parse_args()
+    if args.forest and (args.progressive or args.beam or args.gt):
+        sys.exit("--forest: the table walk only (not with --progressive or --beam), and without --gt")
     if args.beam and (args.progressive or not (1 <= args.beam <= 8 and 1 <= args.branch <= 8) or args.vote_weight != args.vote_weight):
         sys.exit("--beam B, --branch C: 1 .. 8, --vote-weight: a number, and not with --progressive")
     if args.refine < 0:
@@ -106,6 +136,8 @@ def main():
             report(assembly.evaluate(res.G, res.placed, gt["pose"], gt["rest"], root))
         return
     table = assembly.match_pairs(model, x, k=args.k, refine=args.refine)
+    if args.forest:
+        return forest(args, x, table)
     if args.beam:
         moment = assembly.boundary_moments(x[None], table.top_m[None])
         b = assembly.assemble_beam_batch(table.score[None], table.T[None], moment, beam=args.beam, branch=args.branch,

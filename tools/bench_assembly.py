@@ -9,6 +9,7 @@ event pair around every kernel launch, ops.ktimer_start / ktimer_stop), beside t
     python tools/bench_assembly.py --refine [--reps 20] [--out profiles/assembly_refine_k16.json]
     python tools/bench_assembly.py --batch 64 [--reps 10] [--out profiles/assembly_batch.json]
     python tools/bench_assembly.py --beam [--batch 64] [--reps 20] [--out profiles/assembly_beam.json]
+    python tools/bench_assembly.py --forest [--batch 64] [--reps 20] [--out profiles/assemble_forest.txt]
 
 --progressive measures instead (a) ops.merge_resample against the unfused chain se3.transform_points -> cat ->
 farthest_point_sample -> index_points on the same inputs (Na = Nb = 1024 and 2048, M = 1 and 16; device time between two
@@ -38,6 +39,11 @@ path reports (closed-form weights: the number means nothing, it only has to be t
 --batch): the per-launch device time of assemble_beam_kernel (assembly.assemble_beam_batch, weight 1) at (beam, branch) = (1, 1),
 (4, 4) and (8, 8), of assemble_walk_kernel on the same tables (the library's own event pair, ops.ktimer_start / ktimer_stop), and
 the device time of the match_puzzles call that made the table - the cost the walk stands beside.
+
+--forest [--batch Z] measures instead, on Z = 64 tables of tests/_walk_cases.py of K = 16 and of K = 64 pieces, the per-launch
+device time of assemble_forest_kernel (ops.assemble_forest) beside assemble_walk_kernel on the same tables (the library's own event
+pair): kind `random` without a threshold - one component, the cost of the state the forest adds - and kind `max_score` - the walk
+stops in mid-range and the forest restarts many times.
 
 Needs a GPU (there is no CPU path)."""
 import argparse
@@ -383,6 +389,48 @@ def beam(args):
         fh.write(json.dumps(result, indent=1) + "\n")
 
 
+def forest(args):
+    """The forest walk's launch beside the greedy walk's on the same tables (the table kinds of tests/_walk_cases.py): `random`
+    without a threshold - one component, the cost of the added state - and `max_score` - the walk stops in mid-range and the
+    forest restarts many times."""
+    from puzzlenet_amd import ops
+    from tests import _walk_cases as wc
+    Z = args.batch or 64
+    dev = torch.device("cuda:0")
+
+    def kernel_us(fn, name):
+        for _ in range(max(args.warmup, 1)):
+            fn()
+        ops.ktimer_start()
+        for _ in range(args.reps):
+            fn()
+        torch.cuda.synchronize()
+        rows = ops.ktimer_stop()
+        hit = [v for k_, v in rows.items() if name in k_]
+        if len(hit) != 1 or hit[0][0] != args.reps:
+            sys.exit(f"kernel timer: expected {args.reps} launches of {name} in one row, got {rows}")
+        return 1e3 * hit[0][1] / hit[0][0]
+
+    lines = [f"tools/bench_assembly.py --forest --batch {Z} --reps {args.reps} on {torch.cuda.get_device_name(0)}",
+             "the library's own event pair per launch (ops.ktimer_*), mean over the timed launches after the warm-up, us;",
+             f"Z = {Z} tables of tests/_walk_cases.py (seed 2000), one launch each; assemble_walk_kernel is the one built beside the",
+             "forest kernel (its result tail takes a component per piece and is handed 0)", ""]
+    for kind in ("random", "max_score"):
+        for K in (16, 64):
+            S, T, m = wc.make(kind, Z, K, 2000)
+            s, t = torch.from_numpy(S).to(dev), torch.from_numpy(T).to(dev)
+            out = ops.assemble_forest(s, t, max_score=m)
+            walk = kernel_us(lambda: ops.assemble_walk(s, t, max_score=m), "assemble_walk_kernel")
+            frst = kernel_us(lambda: ops.assemble_forest(s, t, max_score=m), "assemble_forest_kernel")
+            lines.append(f"{kind:9s} K = {K:2d}: assemble_walk_kernel {walk:8.1f} us, assemble_forest_kernel {frst:8.1f} us, forest / walk "
+                         f"{frst / walk:5.2f}; components per pile {float(out[10].double().mean()):.1f}, forest edges per pile "
+                         f"{float(out[3].double().mean()):.1f}")
+            print(lines[-1])
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -391,17 +439,21 @@ def main():
     ap.add_argument("--refine", action="store_true")
     ap.add_argument("--batch", type=int, default=0, help="Z: time the batched chain on Z fractured puzzles against the per-puzzle loop")
     ap.add_argument("--beam", action="store_true", help="time the beam walk's launch beside the greedy walk's and match_puzzles")
+    ap.add_argument("--forest", action="store_true", help="time the forest walk's launch beside the greedy walk's on the same tables")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
         name = "assembly_progressive_k16.json" if args.progressive else ("assembly_refine_k16.json" if args.refine else "assembly_k16.json")
         name = "assembly_batch.json" if args.batch else name
         name = "assembly_beam.json" if args.beam else name
+        name = "assemble_forest.txt" if args.forest else name
         args.out = os.path.join(ROOT, "profiles", name)
     if args.reps < (5 if args.batch else 20):
         sys.exit("--reps: at least 20 timed repetitions each (--batch, whose loop side takes seconds a repetition: at least 5)")
     if not torch.cuda.is_available():
         sys.exit("tools/bench_assembly.py needs a GPU: puzzlenet_amd has no CPU path")
+    if args.forest:
+        return forest(args)
     if args.beam:
         return beam(args)
     if args.batch:

@@ -3,6 +3,7 @@
     python tools/eval_assembly.py [--batch 64] [--pieces 8] [--m 20000] [--k 128] [--candidates 16] [--mag 0.8] [--seed 0]
                                   [--curvature 2.0] [--ckpt model.ckpt] [--refine N] [--joint N] [--max-score S]
                                   [--progressive] [--time R] [--json out.json] [--beam B] [--branch C] [--vote-weight W]
+                                  [--objects Q]
 
 B seeded uniform clouds of M points are each cut into P pieces that belong together (datapipe.fracture, along curved surfaces
 with principal curvatures up to --curvature, along planes with --curvature 0; every piece sampled to
@@ -21,6 +22,11 @@ beside the greedy one, on the same fractures and table starts, still with the on
 times the batched progressive walk and, beside it, a loop of assemble_progressive over the same puzzles - the per-puzzle path, which
 downloads its table every round - R times each in turn after one warm-up of each, a host clock around work that ends in a device
 synchronise, and counts the library launches of one round; --json writes those numbers to a file.  Without --ckpt the weights are the closed-form pseudo-random ones and the poses mean nothing.
+--objects Q sorts mixed piles in place of puzzles: the B fractures are regrouped into B / Q piles of the Q P pieces of Q objects each
+under a seeded shuffle (datapipe.pile), matched as one puzzle of Q P pieces, walked by the forest walk (assemble_forest_batch, one
+launch; --max-score is the boundary distance above which two pieces do not belong together), with --joint refined component by
+component in the same one launch, and scored by evaluate_pile_batch: pair precision, pair recall and pair pose recall over the
+ordered pairs of pieces, the number of components and the share of piles sorted exactly, as means over the valid piles.
 Needs a GPU; there is no CPU path."""
 import argparse
 import os
@@ -47,6 +53,40 @@ def metrics(ev, asm, ok):
                         mean_pieces(ev.msd), counted.sum() / others.double().sum()))
 
 
+def sort_piles(args, model, f, dev):
+    """--objects Q: the forest walk over piles of Q fractures each, and the pile metrics as means over the valid piles."""
+    from puzzlenet_amd import assembly, datapipe
+    B, P, Q = f.pose.shape[0], f.pose.shape[1], args.objects
+    Z, K = B // Q, Q * P
+    g = torch.Generator().manual_seed(args.seed)
+    perm = torch.stack([torch.randperm(K, generator=g) for _ in range(Z)]).to(dev)
+    pile = datapipe.pile(f, objects=Q, perm=perm)
+    table = assembly.match_puzzles(model, pile.pieces, k=args.k, refine=args.refine)
+    forest = assembly.assemble_forest_batch(table.score, table.T, max_score=args.max_score)
+    valid = pile.ok.double()
+
+    def row(G):
+        ev = assembly.evaluate_pile_batch(G, forest.component, pile.pose, pile.rest, pile.object_of)
+        mean = lambda x: torch.nansum(x.double() * valid) / (valid * ~torch.isnan(x.double())).sum()
+        return torch.stack([mean(x) for x in (ev.pair_precision, ev.pair_recall, ev.pair_pose_recall, ev.n_components, ev.exact)])
+
+    rows = [row(forest.G)]
+    extra = torch.zeros(3, dtype=torch.float64, device=dev)
+    if args.joint:
+        jr = assembly.refine_assembly_batch(pile.pieces, table, forest, sweeps=args.joint)
+        rows.append(row(jr.G))
+        extra = torch.stack((jr.score0.double().mean(), jr.score.double().mean(), jr.sweeps_used.double().mean()))
+    head = torch.stack((valid.sum(), forest.n_joints.double().mean(), forest.n_edges.double().mean()))
+    host = torch.cat([head, extra] + rows).cpu().tolist()                           # the one download
+    print(f"{Z} piles of {Q} objects, {K} pieces of {f.pieces.shape[2]} points each: {int(host[0])} valid piles; per pile "
+          f"{host[2]:.2f} edges, {host[1]:.1f} joints")
+    names = ("pair precision", "pair recall", "pair pose recall", "components", "share sorted exactly")
+    for label, at in (("forest walk", 6),) + ((("after the joint refinement", 11),) if args.joint else ()):
+        print(f"{label}: " + ", ".join(f"{n} {v:.6g}" for n, v in zip(names, host[at:at + 5])))
+    if args.joint:
+        print(f"joint refinement: mean summed score {host[3]:.6f} -> {host[4]:.6f}, {host[5]:.1f} sweeps")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--batch", type=int, default=64, help="B: clouds, one puzzle each")
@@ -69,7 +109,13 @@ def main():
     ap.add_argument("--beam", type=int, default=0, help="B: also the beam walk with B hypotheses (1 .. 8; 0: the greedy walk alone)")
     ap.add_argument("--branch", type=int, default=4, help="C: with --beam, the candidates every hypothesis is extended by (1 .. 8)")
     ap.add_argument("--vote-weight", type=float, default=1.0, help="W: with --beam, the weight of the placed pieces' votes in a child's cost")
+    ap.add_argument("--objects", type=int, default=1,
+                    help="Q: sort piles of the pieces of Q objects each with the forest walk (Q divides --batch, Q P <= 64; 1: puzzles)")
     args = ap.parse_args()
+    if args.objects < 1 or args.batch % args.objects or args.objects * args.pieces > 64:
+        sys.exit("--objects Q: Q >= 1 divides --batch, and Q * --pieces <= 64")
+    if args.objects > 1 and (args.progressive or args.beam):
+        sys.exit("--objects goes with the forest walk alone: no --progressive, no --beam")
     if args.refine < 0 or args.joint < 0:
         sys.exit("--refine, --joint: 0 or a number of steps / sweeps")
     if args.time < 0 or (args.time and not args.progressive) or (args.json and not args.time):
@@ -100,6 +146,8 @@ def main():
     to = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(dev)
     with torch.no_grad():
         f = datapipe.fracture(to(raw), n=N, k=args.k, cap=min(M, 32768), **{name: to(d) for name, d in draws.items()})
+        if args.objects > 1:
+            return sort_piles(args, model, f, dev)
         # the FPS starts of the table, drawn as match_puzzles draws them, so that the progressive walk can start from the same ones
         s1, s2 = (s.view(B, P) for s in model5_b.draw_fps_starts(1, B * P, N, model.fps_generator))
         table = assembly.match_puzzles(model, f.pieces, k=args.k, start=(s1, s2), refine=args.refine)
