@@ -253,6 +253,50 @@ int pzn_assemble_forest_f32(const float* score, const float* T, const int32_t* c
                             int32_t* component, int32_t* roots, int32_t* n_components,
                             pzn_stream_t stream);
 
+/* The forest beam over Z pair tables: pzn_assemble_beam_f32 with pzn_assemble_forest_f32's restarts (no counterpart in the
+ * reference; assembly.forest_beam_rule is the numpy statement): one launch, one wavefront per pile, no workspace, no atomics,
+ * nothing waits for the device.  score, T, moment, count, beam B, branch C, weight, max_score, vote_score and joint_score are
+ * pzn_assemble_beam_f32's; keys, their order and ties, count, the stop test, the pose arithmetic (dot4, the rigid inverse,
+ * float64, every operation rounded on its own) and the joint rule are the walk's, word for word.  restart_cost (double): NaN
+ * means max_score where that is finite, else 0 - single linkage under a threshold t is what minimises the sum of the edge scores
+ * + t (the number of components), and the beam's cost extends that objective by the votes; without a threshold a restart only
+ * happens at a wall of non-finite keys, where nothing was refused.
+ * Hypothesis: a placed set, a float64 pose and a component for every placed piece, the roots of its components in the order
+ * they started, its edges in placement order and a float64 cost.  Round 0 has one: the beam's root (the row of the smallest key)
+ * as component 0 with the identity, cost 0.  There are exactly count - 1 rounds; every child places exactly one piece, so all live
+ * hypotheses hold the same number of pieces, and a hypothesis always has a child.
+ * Candidates of a hypothesis: the beam's - the first C ordered pairs with exactly one end placed in the order (key, i K + j), keys
+ * finite and (double)key <= max_score; the placed end may be in any component, and the new piece joins the component of the
+ * placed end.
+ * Growth child of candidate (i, j): cost = (parent + (double)key) + weight * penalty as in the beam, the voters being the placed
+ * pieces p of the component the new piece joins: p ascending, entry (p, n) then (n, p), not the candidate's own entry, keys
+ * finite and (double)key <= vote_score.  Pieces of other components live in unrelated frames and do not vote.
+ * Restart: a hypothesis with no candidate has one child of rank 0.  Its new root is the forest walk's: with two or more pieces
+ * outside, the row i of the smallest key among the entries (i, j), i != j, with both ends outside (of equal keys the lowest
+ * i K + j); with one piece outside, that piece.  The root gets the identity and opens the next component; the restart adds no
+ * edge and costs parent + restart_cost (no penalty term).
+ * Selection: the beam's - a NaN cost is +inf, the order is (cost, parent slot, rank), each child kept unless a kept child has the
+ * same placed set, until B are kept.
+ * Out: the result is slot 0, in pzn_assemble_forest_f32's eleven outputs - root[Z] = roots[z,0]; edges, edge_score, n_edges over
+ * all components in placement order (n_edges + n_components = count); G[p] in the frame of p's own root; placed 1 for every
+ * p < count; joints only inside a component, from the result's own edges; component[Z,K], roots[Z,K], n_components[Z] - then
+ * cost[Z,B] float64 in slot order (unused +inf) and n_hyp[Z] int32.  A count outside [2, K] gives the walk's empty answer, no
+ * component and n_hyp 0.  With B = C = 1 the eleven outputs are pzn_assemble_forest_f32's bit for bit, whatever weight is; on a
+ * table where no live hypothesis ever lacks a candidate the ten shared outputs are pzn_assemble_beam_f32's bit for bit and
+ * n_components is 1.  The same bits on every run.
+ * 2 <= K <= 64, 1 <= B, C <= 8 (pzn_assemble_forest_beam_supported: 1 / 0; two generations of hypotheses are
+ * 2 B (128 K + 16 + 4 (K - 1) + 4 + 2 K) bytes of LDS - poses, cost and placed set, edges, the two counts, a component byte and a
+ * root byte per piece: 137472 of 163840 bytes at K = 64, B = 8), PZN_EUNSUPPORTED otherwise, before any launch; Z = 0 is a
+ * success that launches nothing. */
+int pzn_assemble_forest_beam_supported(int K, int B, int C);
+int pzn_assemble_forest_beam_f32(const float* score, const float* T, const double* moment, const int32_t* count,
+                                 int beam, int branch, double weight, double max_score, double vote_score,
+                                 double joint_score, double restart_cost, int Z, int K,
+                                 int32_t* root, int32_t* edges, float* edge_score, int32_t* n_edges,
+                                 double* G, uint8_t* placed, int32_t* joints, int32_t* n_joints,
+                                 int32_t* component, int32_t* roots, int32_t* n_components,
+                                 double* cost, int32_t* n_hyp, pzn_stream_t stream);
+
 /* One round of Z progressive walks (no counterpart in the reference; the choice and the ledger of assembly.ProgressiveAssembler
  * for Z puzzles in lockstep): one launch, one wavefront per puzzle, no workspace, no atomics, nothing waits for the device.
  * Slots are not compacted: puzzle z has P slots, a merged part stays in the fixed part's slot i and slot j dies, so a part in

@@ -19,7 +19,7 @@
 //   * the next generation: the wavefront copies each winner's parent poses and edges, the winner's lane adds its own.
 // Every index into score, T and moment is formed from i, j < count[z] <= K.  No atomics: the same bits on every run.
 #include "pzn_common.h"
-#include "pzn_walk.h"      // the key, the 64-lane arg-min, the stop test, the float64 dot product and the result tail of the walk
+#include "pzn_walk.h"      // the key, the 64-lane arg-min, the stop test, the float64 dot product, the beam's helpers, the result tail
 
 #pragma clang fp contract(off)
 
@@ -32,32 +32,6 @@ constexpr int AB_MAX_GRID = 2048;
 constexpr size_t AB_MAX_LDS = 160 * 1024;       // a CU's LDS on gfx950
 
 size_t ab_lds_bytes(int K, int B) { return (size_t)2 * B * ((size_t)K * 16 * sizeof(double) + 16 + (size_t)(K - 1) * 4); }
-
-// doubles -> qword with the doubles' order (no NaN reaches it), -0 as +0
-__device__ __forceinline__ uint64_t ordered64(double x) {
-  x = x == 0.0 ? 0.0 : x;
-  const uint64_t u = (uint64_t)__double_as_longlong(x);
-  return (u >> 63) ? ~u : (u | ((uint64_t)1 << 63));
-}
-
-__device__ __forceinline__ uint64_t lane_u64(uint64_t v, int l) {
-  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, l, PZN_WAVE), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), l, PZN_WAVE);
-  return ((uint64_t)hi << 32) | lo;
-}
-
-// the right factor of a pose product, b[4 k + v] = B[k][v]: T[i,j] as stored, or its rigid inverse [R^T, -(R^T t)] with the
-// last row 0 0 0 1 (the walk's arithmetic, entry for entry)
-__device__ __forceinline__ void right_factor(const float* __restrict__ t, bool fwd, double* b) {
-  double d[16];
-#pragma unroll
-  for (int e = 0; e < 16; ++e) d[e] = (double)t[e];
-  const double i0 = -((d[0] * d[3] + d[4] * d[7]) + d[8] * d[11]);
-  const double i1 = -((d[1] * d[3] + d[5] * d[7]) + d[9] * d[11]);
-  const double i2 = -((d[2] * d[3] + d[6] * d[7]) + d[10] * d[11]);
-  const double inv[16] = {d[0], d[4], d[8], i0, d[1], d[5], d[9], i1, d[2], d[6], d[10], i2, 0.0, 0.0, 0.0, 1.0};
-#pragma unroll
-  for (int e = 0; e < 16; ++e) b[e] = fwd ? d[e] : inv[e];
-}
 
 __global__ __launch_bounds__(AB_T) void assemble_beam_kernel(const float* __restrict__ score, const float* __restrict__ T,
                                                              const double* __restrict__ moment, const int32_t* __restrict__ count,

@@ -1,6 +1,8 @@
-// pzn_walk.h — what the walks over pair tables share (assemblewalk.hip, assemblebeam.hip, assembleforest.hip, progressive.hip): the key of a table
+// pzn_walk.h — what the walks over pair tables share (assemblewalk.hip, assemblebeam.hip, assembleforest.hip, assembleforestbeam.hip,
+// progressive.hip): the key of a table
 // entry, the 64-lane lexicographic arg-min over (key, i K + j), the stop test on a round's winning key, the order-fixed float64
-// dot product the poses are composed with, and the tail of a walk's result (the three assemble*.hip): the placed
+// dot product the poses are composed with, the beam walks' ordered cost bits, lane reads and right factor, and the tail of a walk's
+// result (the assemble*.hip): the placed
 // bytes and the joint list.  One statement of each, so "the smallest key, the lowest i K + j on ties", "the walk stops here"
 // and "every operation rounded on its own" mean the same in every kernel.  Files that include it are built with
 // -ffp-contract=off and say so again with the pragma.
@@ -49,6 +51,34 @@ __device__ __forceinline__ bool stops(uint32_t w_key, double max_score) {
 
 __device__ __forceinline__ double dot4(double a0, double b0, double a1, double b1, double a2, double b2, double a3, double b3) {
   return ((a0 * b0 + a1 * b1) + a2 * b2) + a3 * b3;
+}
+
+// ---- what the beam walks share (assemblebeam.hip, assembleforestbeam.hip)
+
+// doubles -> qword with the doubles' order (no NaN reaches it), -0 as +0
+__device__ __forceinline__ uint64_t ordered64(double x) {
+  x = x == 0.0 ? 0.0 : x;
+  const uint64_t u = (uint64_t)__double_as_longlong(x);
+  return (u >> 63) ? ~u : (u | ((uint64_t)1 << 63));
+}
+
+__device__ __forceinline__ uint64_t lane_u64(uint64_t v, int l) {
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, l, PZN_WAVE), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), l, PZN_WAVE);
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// the right factor of a pose product, b[4 k + v] = B[k][v]: T[i,j] as stored, or its rigid inverse [R^T, -(R^T t)] with the
+// last row 0 0 0 1 (the walk's arithmetic, entry for entry)
+__device__ __forceinline__ void right_factor(const float* __restrict__ t, bool fwd, double* b) {
+  double d[16];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) d[e] = (double)t[e];
+  const double i0 = -((d[0] * d[3] + d[4] * d[7]) + d[8] * d[11]);
+  const double i1 = -((d[1] * d[3] + d[5] * d[7]) + d[9] * d[11]);
+  const double i2 = -((d[2] * d[3] + d[6] * d[7]) + d[10] * d[11]);
+  const double inv[16] = {d[0], d[4], d[8], i0, d[1], d[5], d[9], i1, d[2], d[6], d[10], i2, 0.0, 0.0, 0.0, 1.0};
+#pragma unroll
+  for (int e = 0; e < 16; ++e) b[e] = fwd ? d[e] : inv[e];
 }
 
 // The tail of a walk's result for one puzzle, by its wavefront: `in` is the placed set (bit p = piece p), c the puzzle's

@@ -362,7 +362,7 @@ def assemble_walk_supported(K):
 
 
 def _walk_args(who, score, T, count, max_score, joint_score):
-    """What assemble_walk and assemble_beam take alike, checked -> (score, T, count, max_score, joint_score, Z, K) as the
+    """What the assemble_* walks take alike, checked -> (score, T, count, max_score, joint_score, Z, K) as the
     library takes them: no limit is +inf, no joint_score NaN."""
     for name, t, dt in (("score", score, torch.float32), ("T", T, torch.float32), ("count", count, torch.int32)):
         if isinstance(t, torch.Tensor) and t.dtype != dt:      # (no silent conversion)
@@ -474,6 +474,44 @@ def assemble_beam(score, T, moment, count=None, beam=4, branch=4, weight=1.0, ma
               joint_score, Z, K, _p(root), _p(edges), _p(edge_score), _p(n_edges), _p(G), _p(placed), _p(joints), _p(n_joints),
               _p(cost), _p(n_hyp), _stream())
     return root, edges, edge_score, n_edges, G, placed, joints, n_joints, cost, n_hyp
+
+
+def assemble_forest_beam_supported(K, beam=4, branch=4):
+    return bool(_lib.load().pzn_assemble_forest_beam_supported(int(K), int(beam), int(branch)))
+
+
+def assemble_forest_beam(score, T, moment, count=None, beam=4, branch=4, weight=1.0, max_score=None, vote_score=None,
+                         joint_score=None, restart_cost=None):
+    """The forest beam over Z pair tables - the beam walk scored by the placed pieces' votes, with the forest walk's restarts - in
+    one launch (pzn_assemble_forest_beam_f32; include/pzn.h states the rule, assembly.forest_beam_rule is its numpy statement): the
+    arguments are assemble_beam's and restart_cost, what a new component costs (None or NaN: max_score where that is finite, else
+    0) -> assemble_forest's eleven outputs for the cheapest hypothesis, then cost [Z,beam] float64 (slot order, unused +inf) and
+    n_hyp [Z] int32.  2 <= K <= 64, beam and branch in 1 .. 8 (PznUnsupported beyond).  Z = 0 launches nothing.  No autograd,
+    nothing waits for the device."""
+    who = "assemble_forest_beam"
+    if isinstance(moment, torch.Tensor) and moment.dtype != torch.float64:      # (no silent conversion)
+        raise _lib.PznError(f"{who}: moment must be {torch.float64}; got {moment.dtype}")
+    score, T, count, max_score, joint_score, Z, K = _walk_args(who, score, T, count, max_score, joint_score)
+    moment = _req(moment, torch.float64, "moment")
+    if tuple(moment.shape) != (Z, K, 4, 4):
+        raise _lib.PznError(f"{who}: expected moment[{Z},{K},4,4]; got {tuple(moment.shape)}")
+    beam, branch, weight = int(beam), int(branch), float(weight)
+    vote_score = float("nan") if vote_score is None else float(vote_score)
+    restart_cost = float("nan") if restart_cost is None else float(restart_cost)
+    if weight != weight:
+        raise _lib.PznError(f"{who}: weight is NaN")
+    if not assemble_forest_beam_supported(K, beam, branch):
+        raise _lib.PznUnsupported(f"{who}: K = {K} pieces, beam = {beam}, branch = {branch} (2 <= K <= 64, 1 <= beam, branch <= 8)")
+    dev = score.device
+    root, edges, edge_score, n_edges, G, placed, joints, n_joints = _walk_outputs(Z, K, dev)
+    component, roots = (torch.empty((Z, K), dtype=torch.int32, device=dev) for _ in range(2))
+    n_components, n_hyp = (torch.empty((Z,), dtype=torch.int32, device=dev) for _ in range(2))
+    cost = torch.empty((Z, beam), dtype=torch.float64, device=dev)
+    with _on(dev):
+        _call("pzn_assemble_forest_beam_f32", _p(score), _p(T), _p(moment), _p(count), beam, branch, weight, max_score, vote_score,
+              joint_score, restart_cost, Z, K, _p(root), _p(edges), _p(edge_score), _p(n_edges), _p(G), _p(placed), _p(joints),
+              _p(n_joints), _p(component), _p(roots), _p(n_components), _p(cost), _p(n_hyp), _stream())
+    return root, edges, edge_score, n_edges, G, placed, joints, n_joints, component, roots, n_components, cost, n_hyp
 
 
 ProgressiveState = collections.namedtuple("ProgressiveState", "alive part G done n_edges edges edge_score")

@@ -22,6 +22,9 @@ place of the greedy one: where the walk stops (a score that is not finite or abo
 component from a new root, until every piece is in one.  Prints the components; PREFIX_G.npy maps each piece into the frame of its
 own component's root, PREFIX_component.npy holds the component of every piece, and --joint N refines every component in one launch
 (assembly.refine_assembly_batch).  Not with --gt, which holds the truth of one object.
+--forest --beam B (with --branch C and --vote-weight W): the forest beam of assembly.assemble_forest_beam_batch in place of the
+forest walk - the beam walk inside every component, a piece charged by the votes of the component it joins, a new component
+charged --max-score -; everything after the walk is --forest's.
 --gt PREFIX_gt.npz (written by tools/fracture.py beside the pieces): the assembly is scored against the truth - per piece the
 rotation error in degrees, the translation error and the mean squared distance of its points from where they belong, the share
 of pieces placed right (assembly.evaluate) and, for the greedy walk, the share of its edges between pieces that touch.
@@ -45,10 +48,17 @@ def report(ev):
 
 
 def forest(args, x, table):
-    """--forest: the forest walk over the table of a pile, its components, and with --joint their refinement in one launch."""
+    """--forest: the forest walk over the table of a pile - with --beam the forest beam -, its components, and with --joint their
+    refinement in one launch."""
     from puzzlenet_amd import assembly
     one = assembly.PairTable(*(f[None] for f in table))
-    fb = assembly.assemble_forest_batch(one.score, one.T, max_score=args.max_score)
+    if args.beam:
+        moment = assembly.boundary_moments(x[None], one.top_m)
+        fb = assembly.assemble_forest_beam_batch(one.score, one.T, moment, beam=args.beam, branch=args.branch, weight=args.vote_weight,
+                                                 max_score=args.max_score)
+        print(f"forest beam: beam {args.beam}, branch {args.branch}, vote weight {args.vote_weight:g}; cost {float(fb.cost[0, 0]):.6f}")
+    else:
+        fb = assembly.assemble_forest_batch(one.score, one.T, max_score=args.max_score)
     G = fb.G[0]
     comp, n, nc = fb.component[0].tolist(), int(fb.n_edges[0]), int(fb.n_components[0])
     for (i, j, new), s in zip(fb.edges[0, :n].tolist(), fb.edge_score[0, :n].tolist()):
@@ -84,8 +94,8 @@ def main():
     ap.add_argument("--vote-weight", type=float, default=1.0, help="W: with --beam, the weight of the placed pieces' votes in a child's cost")
     ap.add_argument("--forest", action="store_true", help="a pile of several objects: the forest walk, a component per object")
     args = ap.parse_args()
-    if args.forest and (args.progressive or args.beam or args.gt):
-        sys.exit("--forest: the table walk only (not with --progressive or --beam), and without --gt")
+    if args.forest and (args.progressive or args.gt):
+        sys.exit("--forest: the table walk only (not with --progressive), and without --gt")
     if args.beam and (args.progressive or not (1 <= args.beam <= 8 and 1 <= args.branch <= 8) or args.vote_weight != args.vote_weight):
         sys.exit("--beam B, --branch C: 1 .. 8, --vote-weight: a number, and not with --progressive")
     if args.refine < 0:

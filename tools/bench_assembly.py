@@ -10,6 +10,7 @@ event pair around every kernel launch, ops.ktimer_start / ktimer_stop), beside t
     python tools/bench_assembly.py --batch 64 [--reps 10] [--out profiles/assembly_batch.json]
     python tools/bench_assembly.py --beam [--batch 64] [--reps 20] [--out profiles/assembly_beam.json]
     python tools/bench_assembly.py --forest [--batch 64] [--reps 20] [--out profiles/assemble_forest.txt]
+    python tools/bench_assembly.py --forest-beam [--batch 64] [--reps 20] [--out profiles/assemble_forest_beam.txt]
 
 --progressive measures instead (a) ops.merge_resample against the unfused chain se3.transform_points -> cat ->
 farthest_point_sample -> index_points on the same inputs (Na = Nb = 1024 and 2048, M = 1 and 16; device time between two
@@ -44,6 +45,12 @@ the device time of the match_puzzles call that made the table - the cost the wal
 device time of assemble_forest_kernel (ops.assemble_forest) beside assemble_walk_kernel on the same tables (the library's own event
 pair): kind `random` without a threshold - one component, the cost of the state the forest adds - and kind `max_score` - the walk
 stops in mid-range and the forest restarts many times.
+
+--forest-beam [--batch Z] measures instead the per-launch device time of assemble_forest_beam_kernel (ops.assemble_forest_beam,
+weight 1; the library's own event pair) at K = 16 and 64 and (beam, branch) = (1, 1), (4, 4) and (8, 8) on two kinds of table:
+tables without a restart (kind `random` of tests/_beam_cases.py, no threshold) beside assemble_beam_kernel on the same tables - the
+two do the same work there but for a few bytes of bookkeeping per child -, and tables with restarts (kind `max_score`, and the
+planted piles of tests/_forest_beam_cases.py: 2 objects of 8 pieces, 4 of 16) beside assemble_forest_kernel.
 
 Needs a GPU (there is no CPU path)."""
 import argparse
@@ -431,6 +438,67 @@ def forest(args):
         fh.write("\n".join(lines) + "\n")
 
 
+def forest_beam(args):
+    """The forest beam's launch beside the beam's on tables without a restart, and beside the forest walk's on tables with
+    restarts (kind `max_score`) and on planted piles."""
+    from puzzlenet_amd import ops
+    from tests import _beam_cases as bc
+    from tests import _forest_beam_cases as fb
+    Z = args.batch or 64
+    dev = torch.device("cuda:0")
+
+    def kernel_us(fn, name):
+        for _ in range(max(args.warmup, 1)):
+            fn()
+        ops.ktimer_start()
+        for _ in range(args.reps):
+            fn()
+        torch.cuda.synchronize()
+        rows = ops.ktimer_stop()
+        hit = [v for k_, v in rows.items() if name in k_]
+        if len(hit) != 1 or hit[0][0] != args.reps:
+            sys.exit(f"kernel timer: expected {args.reps} launches of {name} in one row, got {rows}")
+        return 1e3 * hit[0][1] / hit[0][0]
+
+    lines = [f"tools/bench_assembly.py --forest-beam --batch {Z} --reps {args.reps} on {torch.cuda.get_device_name(0)}",
+             "the library's own event pair per launch (ops.ktimer_*), mean over the timed launches after the warm-up, us;",
+             f"Z = {Z} tables, one launch each, weight 1", "",
+             "tables without a restart (tests/_beam_cases.py, kind random, seed 2100, no threshold): beside assemble_beam_kernel"]
+    say = lambda line: (lines.append(line), print(line))
+    for K in (16, 64):
+        S, T, M, _ = bc.make("random", Z, K, 2100)
+        s, t, m = (torch.from_numpy(x).to(dev) for x in (S, T, M))
+        for B, C in ((1, 1), (4, 4), (8, 8)):
+            a, b = ops.assemble_beam(s, t, m, beam=B, branch=C), ops.assemble_forest_beam(s, t, m, beam=B, branch=C)
+            if not all(torch.equal(x, y) for x, y in zip(a, b[:8] + b[11:])):
+                sys.exit(f"K = {K}, beam {B}, branch {C}: the forest beam is not the beam on a table without a restart")
+            beam_us = kernel_us(lambda: ops.assemble_beam(s, t, m, beam=B, branch=C), "assemble_beam_kernel")
+            fb_us = kernel_us(lambda: ops.assemble_forest_beam(s, t, m, beam=B, branch=C), "assemble_forest_beam_kernel")
+            say(f"random    K = {K:2d} B = {B} C = {C}: assemble_beam_kernel {beam_us:9.1f} us, assemble_forest_beam_kernel {fb_us:9.1f} us, "
+                f"forest beam / beam {fb_us / beam_us:5.2f}")
+    say("")
+    say("tables with restarts (kind max_score, seed 2100; planted piles of tests/_forest_beam_cases.py, seeds 0 .. Z - 1, 2 objects of 8")
+    say("pieces and 4 of 16, max_score 0.03): beside assemble_forest_kernel")
+    for kind, K in (("max_score", 16), ("max_score", 64), ("piles 2x8", 16), ("piles 4x16", 64)):
+        if kind == "max_score":
+            S, T, M, ms = bc.make(kind, Z, K, 2100)
+        else:
+            S, T, M, _, _, ms = fb.piles(range(Z), 2 if K == 16 else 4, 8 if K == 16 else 16)
+        s, t, m = (torch.from_numpy(x).to(dev) for x in (S, T, M))
+        frst = kernel_us(lambda: ops.assemble_forest(s, t, max_score=ms), "assemble_forest_kernel")
+        greedy = ops.assemble_forest(s, t, max_score=ms)
+        for B, C in ((1, 1), (4, 4), (8, 8)):
+            out = ops.assemble_forest_beam(s, t, m, beam=B, branch=C, max_score=ms)
+            same = float((out[1] == greedy[1]).all(dim=2).all(dim=1).double().mean())
+            fb_us = kernel_us(lambda: ops.assemble_forest_beam(s, t, m, beam=B, branch=C, max_score=ms), "assemble_forest_beam_kernel")
+            say(f"{kind:10s} K = {K:2d} B = {B} C = {C}: assemble_forest_kernel {frst:8.1f} us, assemble_forest_beam_kernel {fb_us:9.1f} us, "
+                f"forest beam / forest {fb_us / frst:7.2f}; components per pile {float(out[10].double().mean()):.1f}, the forest walk's "
+                f"edges in {100 * same:.0f} % of the piles")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -440,6 +508,8 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="Z: time the batched chain on Z fractured puzzles against the per-puzzle loop")
     ap.add_argument("--beam", action="store_true", help="time the beam walk's launch beside the greedy walk's and match_puzzles")
     ap.add_argument("--forest", action="store_true", help="time the forest walk's launch beside the greedy walk's on the same tables")
+    ap.add_argument("--forest-beam", action="store_true",
+                    help="time the forest beam's launch beside the beam's and the forest walk's on the same tables")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
@@ -447,11 +517,14 @@ def main():
         name = "assembly_batch.json" if args.batch else name
         name = "assembly_beam.json" if args.beam else name
         name = "assemble_forest.txt" if args.forest else name
+        name = "assemble_forest_beam.txt" if args.forest_beam else name
         args.out = os.path.join(ROOT, "profiles", name)
     if args.reps < (5 if args.batch else 20):
         sys.exit("--reps: at least 20 timed repetitions each (--batch, whose loop side takes seconds a repetition: at least 5)")
     if not torch.cuda.is_available():
         sys.exit("tools/bench_assembly.py needs a GPU: puzzlenet_amd has no CPU path")
+    if args.forest_beam:
+        return forest_beam(args)
     if args.forest:
         return forest(args)
     if args.beam:

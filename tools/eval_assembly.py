@@ -27,6 +27,9 @@ under a seeded shuffle (datapipe.pile), matched as one puzzle of Q P pieces, wal
 launch; --max-score is the boundary distance above which two pieces do not belong together), with --joint refined component by
 component in the same one launch, and scored by evaluate_pile_batch: pair precision, pair recall and pair pose recall over the
 ordered pairs of pieces, the number of components and the share of piles sorted exactly, as means over the valid piles.
+--objects Q --beam B (with --branch C, --vote-weight W) also runs the forest beam (boundary_moments and assemble_forest_beam_batch,
+one launch: the beam walk with the forest walk's restarts, a restart charged --max-score) on the same tables and prints its row
+beside the forest walk's, with --joint both rows after the joint refinement of their own results too.
 Needs a GPU; there is no CPU path."""
 import argparse
 import os
@@ -54,7 +57,8 @@ def metrics(ev, asm, ok):
 
 
 def sort_piles(args, model, f, dev):
-    """--objects Q: the forest walk over piles of Q fractures each, and the pile metrics as means over the valid piles."""
+    """--objects Q: the forest walk over piles of Q fractures each - with --beam B the forest beam beside it, on the same tables -
+    and the pile metrics as means over the valid piles."""
     from puzzlenet_amd import assembly, datapipe
     B, P, Q = f.pose.shape[0], f.pose.shape[1], args.objects
     Z, K = B // Q, Q * P
@@ -63,28 +67,44 @@ def sort_piles(args, model, f, dev):
     pile = datapipe.pile(f, objects=Q, perm=perm)
     table = assembly.match_puzzles(model, pile.pieces, k=args.k, refine=args.refine)
     forest = assembly.assemble_forest_batch(table.score, table.T, max_score=args.max_score)
+    walks = [("forest walk", forest)]
+    if args.beam:
+        moment = assembly.boundary_moments(pile.pieces, table.top_m)
+        walks.append((f"forest beam (beam {args.beam}, branch {args.branch}, vote weight {args.vote_weight:g})",
+                      assembly.assemble_forest_beam_batch(table.score, table.T, moment, beam=args.beam, branch=args.branch,
+                                                          weight=args.vote_weight, max_score=args.max_score)))
     valid = pile.ok.double()
 
-    def row(G):
-        ev = assembly.evaluate_pile_batch(G, forest.component, pile.pose, pile.rest, pile.object_of)
+    def row(G, asm):
+        ev = assembly.evaluate_pile_batch(G, asm.component, pile.pose, pile.rest, pile.object_of)
         mean = lambda x: torch.nansum(x.double() * valid) / (valid * ~torch.isnan(x.double())).sum()
         return torch.stack([mean(x) for x in (ev.pair_precision, ev.pair_recall, ev.pair_pose_recall, ev.n_components, ev.exact)])
 
-    rows = [row(forest.G)]
-    extra = torch.zeros(3, dtype=torch.float64, device=dev)
-    if args.joint:
-        jr = assembly.refine_assembly_batch(pile.pieces, table, forest, sweeps=args.joint)
-        rows.append(row(jr.G))
-        extra = torch.stack((jr.score0.double().mean(), jr.score.double().mean(), jr.sweeps_used.double().mean()))
-    head = torch.stack((valid.sum(), forest.n_joints.double().mean(), forest.n_edges.double().mean()))
-    host = torch.cat([head, extra] + rows).cpu().tolist()                           # the one download
-    print(f"{Z} piles of {Q} objects, {K} pieces of {f.pieces.shape[2]} points each: {int(host[0])} valid piles; per pile "
-          f"{host[2]:.2f} edges, {host[1]:.1f} joints")
+    labels, rows, heads = [], [], [valid.sum()[None]]
+    for label, asm in walks:
+        labels.append(label)
+        rows.append(row(asm.G, asm))
+        extra = torch.zeros(3, dtype=torch.float64, device=dev)
+        if args.joint:
+            jr = assembly.refine_assembly_batch(pile.pieces, table, asm, sweeps=args.joint)
+            labels.append(f"{label.split(' (')[0]} after the joint refinement")
+            rows.append(row(jr.G, asm))
+            extra = torch.stack((jr.score0.double().mean(), jr.score.double().mean(), jr.sweeps_used.double().mean()))
+        heads.append(torch.cat((torch.stack((asm.n_joints.double().mean(), asm.n_edges.double().mean())), extra)))
+    if args.beam:
+        heads.append((walks[1][1].edges == forest.edges).all(dim=2).all(dim=1).double().mean()[None])
+    host = torch.cat(heads + rows).cpu().tolist()                                   # the one download
+    print(f"{Z} piles of {Q} objects, {K} pieces of {f.pieces.shape[2]} points each: {int(host[0])} valid piles")
+    at = 1 + 5 * len(walks) + (1 if args.beam else 0)
     names = ("pair precision", "pair recall", "pair pose recall", "components", "share sorted exactly")
-    for label, at in (("forest walk", 6),) + ((("after the joint refinement", 11),) if args.joint else ()):
-        print(f"{label}: " + ", ".join(f"{n} {v:.6g}" for n, v in zip(names, host[at:at + 5])))
-    if args.joint:
-        print(f"joint refinement: mean summed score {host[3]:.6f} -> {host[4]:.6f}, {host[5]:.1f} sweeps")
+    for n, label in enumerate(labels):
+        print(f"{label}: " + ", ".join(f"{name} {v:.6g}" for name, v in zip(names, host[at + 5 * n:at + 5 * n + 5])))
+    for n, (label, _) in enumerate(walks):
+        h = host[1 + 5 * n:6 + 5 * n]
+        print(f"{label.split(' (')[0]}: per pile {h[1]:.2f} edges, {h[0]:.1f} joints"
+              + (f"; joint refinement: mean summed score {h[2]:.6f} -> {h[3]:.6f}, {h[4]:.1f} sweeps" if args.joint else ""))
+    if args.beam:
+        print(f"forest beam: the forest walk's edges in {100 * host[at - 1]:.1f} % of the piles")
 
 
 def main():
@@ -106,7 +126,7 @@ def main():
     ap.add_argument("--progressive", action="store_true", help="also the progressive walk of the whole batch, in lockstep")
     ap.add_argument("--time", type=int, default=0, help="with --progressive: repeats of the timed batched walk and per-puzzle loop")
     ap.add_argument("--json", default=None, help="with --time: write the timings and launch counts to this file")
-    ap.add_argument("--beam", type=int, default=0, help="B: also the beam walk with B hypotheses (1 .. 8; 0: the greedy walk alone)")
+    ap.add_argument("--beam", type=int, default=0, help="B: also the beam walk with B hypotheses - with --objects, the forest beam (1 .. 8; 0: the greedy walk alone)")
     ap.add_argument("--branch", type=int, default=4, help="C: with --beam, the candidates every hypothesis is extended by (1 .. 8)")
     ap.add_argument("--vote-weight", type=float, default=1.0, help="W: with --beam, the weight of the placed pieces' votes in a child's cost")
     ap.add_argument("--objects", type=int, default=1,
@@ -114,8 +134,8 @@ def main():
     args = ap.parse_args()
     if args.objects < 1 or args.batch % args.objects or args.objects * args.pieces > 64:
         sys.exit("--objects Q: Q >= 1 divides --batch, and Q * --pieces <= 64")
-    if args.objects > 1 and (args.progressive or args.beam):
-        sys.exit("--objects goes with the forest walk alone: no --progressive, no --beam")
+    if args.objects > 1 and args.progressive:
+        sys.exit("--objects goes with the forest walk alone: no --progressive")
     if args.refine < 0 or args.joint < 0:
         sys.exit("--refine, --joint: 0 or a number of steps / sweeps")
     if args.time < 0 or (args.time and not args.progressive) or (args.json and not args.time):
