@@ -44,12 +44,12 @@ The walks over a table:
   * assemble_forest_batch: the greedy walk for a pile that holds the pieces of several objects.  The walks above grow one tree
     from one root and leave what it does not reach unplaced; here the pieces left over start a new component from a new root,
     until every piece is in one - which pieces belong together, and how each group goes together.  One launch
-    (ops.assemble_forest, csrc/assembleforest.hip; forest_rule is its numpy statement).  evaluate_pile / evaluate_pile_batch
+    (ops.assemble_forest, csrc/assemblewalk.hip; forest_rule is its numpy statement).  evaluate_pile / evaluate_pile_batch
     score a sorted pile against datapipe.pile's answers.
   * assemble_forest_beam_batch: the beam for such a pile.  The forest walk is greedy inside every component, and the beam grows
     one tree; here a beam hypothesis that finds no admissible entry restarts from a new root as the forest walk does, at the
     price `restart_cost` (by default max_score, what single linkage under a threshold charges a component), and a piece is
-    charged by the votes of the component it joins alone.  One launch (ops.assemble_forest_beam, csrc/assembleforestbeam.hip;
+    charged by the votes of the component it joins alone.  One launch (ops.assemble_forest_beam, csrc/assemblebeam.hip;
     forest_beam_rule is its numpy statement); beam = branch = 1 is the forest walk, a table without a restart gives the beam.
   * refine_assembly / refine_assembly_batch: the step after a walk.  The walk composes pair poses along a spanning tree, so a
     piece's pose carries the summed error of the edges between it and the root, and every accepted joint that is no tree edge
@@ -523,12 +523,17 @@ def _rule_joints(comp, raw, limit, out):
     return n
 
 
-def _rule_table(score, T, count, max_score, who):
-    """What walk_rule and forest_rule read alike -> (S float32 [Z,K,K], P float32 [Z,K,K,4,4], counts [Z], the stop limit)."""
+def _rule_table(score, T, count, max_score, who, M=None):
+    """What the rules read alike -> (S float32 [Z,K,K], P float32 [Z,K,K,4,4], counts [Z], the stop limit).  M: the beam rules'
+    moment, already a float64 array, checked beside the other two."""
     S, P = _as_np(score, np.float32), _as_np(T, np.float32)
     Z, K = S.shape[0], S.shape[1]
-    if S.shape != (Z, K, K) or P.shape != (Z, K, K, 4, 4) or K < 2:
-        raise ValueError(f"{who} expects score[Z,K,K], T[Z,K,K,4,4] with K >= 2; got {S.shape}, {P.shape}")
+    want, got = "score[Z,K,K], T[Z,K,K,4,4]", f"{S.shape}, {P.shape}"
+    bad = S.shape != (Z, K, K) or P.shape != (Z, K, K, 4, 4) or K < 2
+    if M is not None:
+        want, got, bad = want + ", moment[Z,K,4,4]", got + f", {M.shape}", bad or M.shape != (Z, K, 4, 4)
+    if bad:
+        raise ValueError(f"{who} expects {want} with K >= 2; got {got}")
     counts = np.full(Z, K, dtype=np.int64) if count is None else _as_np(count, np.int64)
     return S, P, counts, float("inf") if max_score is None else float(max_score)
 
@@ -627,7 +632,7 @@ ForestRule = collections.namedtuple("ForestRule", WalkRule._fields + ("component
 
 
 def forest_rule(score, T, count=None, max_score=None, joint_score=None):
-    """The numpy statement of ops.assemble_forest (csrc/assembleforest.hip, the rule in include/pzn.h), which is held to it bit
+    """The numpy statement of ops.assemble_forest (csrc/assemblewalk.hip, the rule in include/pzn.h), which is held to it bit
     for bit, G included: walk_rule for a pile that holds the pieces of several objects.  The arguments, the keys, their order and
     ties, the stop test, the pose arithmetic and count are walk_rule's (its helpers run here).  Where the walk stops with pieces
     < count still outside, a new component starts: its root is the row of the smallest key among the entries with both ends
@@ -672,6 +677,14 @@ def _placed_movable(placed, root):
         return placed, placed & (index[None, :] != root[:, None])
 
 
+def _forest_movable(placed, roots):
+    """The kernel's placed bytes [Z,K] as bool, and movable = placed and not the root of any component (roots [Z,K], unused -1)."""
+    with torch.no_grad():
+        placed = placed.bool()
+        index = torch.arange(placed.shape[1], dtype=torch.int32, device=placed.device)
+        return placed, placed & ~(roots[:, :, None] == index[None, None, :]).any(dim=1)
+
+
 def assemble_batch(score, T, count=None, max_score=None, joint_score=None):
     """assemble() and the joint selection of refine_assembly() for Z puzzles in ONE launch (ops.assemble_walk), everything on
     the device: score [Z,K,K], T [Z,K,K,4,4] (float32, on the GPU; match_puzzles' fields), count [Z] int32 or None (the pieces of
@@ -710,12 +723,8 @@ def assemble_forest_batch(score, T, count=None, max_score=None, joint_score=None
     device."""
     root, edges, edge_score, n_edges, G, placed, joints, n_joints, component, roots, n_components = ops.assemble_forest(
         score, T, count, max_score, joint_score)
-    with torch.no_grad():
-        placed = placed.bool()
-        index = torch.arange(placed.shape[1], dtype=torch.int32, device=placed.device)
-        is_root = (roots[:, :, None] == index[None, None, :]).any(dim=1)
-    return ForestBatch(root, edges, edge_score, n_edges, G, placed, placed & ~is_root, joints, n_joints, component, roots,
-                       n_components)
+    placed, movable = _forest_movable(placed, roots)
+    return ForestBatch(root, edges, edge_score, n_edges, G, placed, movable, joints, n_joints, component, roots, n_components)
 
 
 def _pile_msd(G, X, R):
@@ -861,147 +870,6 @@ def _rule_inverses(T):
     return out
 
 
-def beam_rule(score, T, moment, count=None, beam=4, branch=4, weight=1.0, max_score=None, vote_score=None, joint_score=None):
-    """The numpy statement of ops.assemble_beam (csrc/assemblebeam.hip, the rule in include/pzn.h), which is held to it bit for
-    bit, G and cost included.  score [Z,K,K] (read as float32), T [Z,K,K,4,4] (float32), moment [Z,K,4,4] (float64), count [Z]
-    or None, tensors or arrays -> BeamRule: walk_rule's fields in its shapes and types, cost [Z,beam] float64 and n_hyp [Z] int32.
-
-    Keys, ties, the root, the pose arithmetic and count are walk_rule's.  A hypothesis is a placed set with its poses, edges and
-    a float64 cost; its candidates are the first `branch` ordered pairs with one end placed in the order (key, i K + j), keys
-    finite and <= max_score.  A child costs (parent + key) + weight * penalty, penalty = the mean, summed in vote order, of the
-    disagreement d of every other entry between a placed piece p (ascending; (p, n) then (n, p); keys finite and <= vote_score)
-    and the new piece n: D = G[p] T[p,n] - Gn or G[p] inv(T[n,p]) - Gn on rows 0..2, d = sum_u D_u M[n] D_u^T with the rule's
-    dot4 order.  The round's children are ordered by (cost, parent slot, rank) and the first `beam` distinct placed sets live on.
-    The result is slot 0.  Written with element-wise float64 only: no matmul, whose summation order is not fixed."""
-    S, P, M = _as_np(score, np.float32), _as_np(T, np.float32), _as_np(moment, np.float64)
-    Z, K = S.shape[0], S.shape[1]
-    B, C, weight = int(beam), int(branch), float(weight)
-    if S.shape != (Z, K, K) or P.shape != (Z, K, K, 4, 4) or M.shape != (Z, K, 4, 4) or K < 2:
-        raise ValueError(f"beam_rule expects score[Z,K,K], T[Z,K,K,4,4], moment[Z,K,4,4] with K >= 2; got {S.shape}, {P.shape}, "
-                         f"{M.shape}")
-    if B < 1 or C < 1 or weight != weight:
-        raise ValueError(f"beam_rule: beam = {B}, branch = {C} (>= 1), weight = {weight} (not NaN)")
-    counts = np.full(Z, K, dtype=np.int64) if count is None else _as_np(count, np.int64)
-    inf = float("inf")
-    limit = inf if max_score is None else float(max_score)
-    vlimit = limit if vote_score is None or vote_score != vote_score else float(vote_score)
-    out = root, edges, edge_score, n_edges, G, placed, joints, n_joints = _rule_outputs(Z, K)
-    cost = np.full((Z, B), np.inf, dtype=np.float64)
-    n_hyp = np.zeros(Z, dtype=np.int32)
-    with np.errstate(all="ignore"):
-        for z in range(Z):
-            c = int(counts[z])
-            if not 2 <= c <= K:
-                continue
-            raw = S[z, :c, :c].astype(np.float64)
-            key = np.where(np.isnan(raw) | np.eye(c, dtype=bool), inf, raw) + 0.0            # (-0 is +0)
-            flat_of = np.arange(c)[:, None] * K + np.arange(c)[None, :]
-            r = int(np.flatnonzero(key.reshape(-1) == key.min())[0]) // c                    # the first row-major position
-            root[z] = r
-            Pz, Mz = P[z].astype(np.float64), M[z]
-            first = np.zeros(c, dtype=bool)
-            first[r] = True
-            pose0 = np.zeros((c, 4, 4))
-            pose0[r] = np.eye(4)
-            hyps = [(first, pose0, [], 0.0)]                                                 # (inside, poses, edges, cost)
-            for _ in range(c - 1):
-                kids = []                                                                    # (slot, rank, i, j, new, key)
-                for slot, (inside, _, _, _) in enumerate(hyps):
-                    at = np.flatnonzero((inside[:, None] != inside[None, :]).reshape(-1))
-                    kv, fv = key.reshape(-1)[at], flat_of.reshape(-1)[at]
-                    for rank, q in enumerate(np.lexsort((fv, kv))[:C]):
-                        if not np.isfinite(kv[q]) or kv[q] > limit:      # (as the walk stops: a key of -inf ends the list too)
-                            break
-                        i, j = divmod(int(fv[q]), K)
-                        kids.append((slot, rank, i, j, j if inside[i] else i, float(kv[q])))
-                if not kids:
-                    break
-                # the children's poses: G[new] = G[i] T[i,j], or G[j] inv(T[i,j])
-                Tij = np.stack([Pz[i, j] for _, _, i, j, _, _ in kids])
-                fwd = np.array([new == j for _, _, _, j, new, _ in kids])
-                src = np.stack([hyps[slot][1][i if new == j else j] for slot, _, i, j, new, _ in kids])
-                Gn = _rule_products(src, np.where(fwd[:, None, None], Tij, _rule_inverses(Tij)))
-                costs = [hyps[slot][3] + k for slot, _, _, _, _, k in kids]
-                if weight != 0.0:
-                    votes = []                                                               # (child, p, a, b) in vote order
-                    for ci, (slot, _, i, j, new, _) in enumerate(kids):
-                        for p in np.flatnonzero(hyps[slot][0]):
-                            for a, b in ((int(p), new), (new, int(p))):
-                                if (a, b) != (i, j) and np.isfinite(key[a, b]) and key[a, b] <= vlimit:
-                                    votes.append((ci, int(p), a, b))
-                    total, n_votes = [0.0] * len(kids), [0] * len(kids)
-                    if votes:
-                        Tab = np.stack([Pz[a, b] for _, _, a, b in votes])
-                        vfwd = np.array([a == p for _, p, a, _ in votes])
-                        Gp = np.stack([hyps[kids[ci][0]][1][p] for ci, p, _, _ in votes])
-                        Q = _rule_products(Gp, np.where(vfwd[:, None, None], Tab, _rule_inverses(Tab)))
-                        D = Q[:, :3, :] - np.stack([Gn[ci, :3, :] for ci, _, _, _ in votes])
-                        Mn = np.stack([Mz[kids[ci][4]] for ci, _, _, _ in votes])
-                        qs = []
-                        for u in range(3):
-                            m = [_dot4(Mn[:, v, 0], D[:, u, 0], Mn[:, v, 1], D[:, u, 1], Mn[:, v, 2], D[:, u, 2], Mn[:, v, 3], D[:, u, 3])
-                                 for v in range(4)]
-                            qs.append(_dot4(D[:, u, 0], m[0], D[:, u, 1], m[1], D[:, u, 2], m[2], D[:, u, 3], m[3]))
-                        d = ((qs[0] + qs[1]) + qs[2]).tolist()
-                        for (ci, _, _, _), dv in zip(votes, d):
-                            total[ci] = total[ci] + dv
-                            n_votes[ci] += 1
-                    costs = [base + weight * (t / n if n else 0.0) for base, t, n in zip(costs, total, n_votes)]
-                costs = [inf if x != x else x for x in costs]
-                nxt, seen = [], set()
-                for ci in sorted(range(len(kids)), key=lambda ci: (costs[ci], kids[ci][0], kids[ci][1])):
-                    slot, _, i, j, new, _ = kids[ci]
-                    inside = hyps[slot][0].copy()
-                    inside[new] = True
-                    if inside.tobytes() in seen:
-                        continue
-                    seen.add(inside.tobytes())
-                    poses = hyps[slot][1].copy()
-                    poses[new] = Gn[ci]
-                    nxt.append((inside, poses, hyps[slot][2] + [(i, j, new)], costs[ci]))
-                    if len(nxt) == B:
-                        break
-                hyps = nxt
-            inside, poses, es, _ = hyps[0]
-            n_hyp[z] = len(hyps)
-            cost[z, :len(hyps)] = [h[3] for h in hyps]
-            worst = -inf
-            for e, (i, j, new) in enumerate(es):
-                edges[z, e] = (i, j, new)
-                edge_score[z, e] = S[z, i, j]
-                worst = max(worst, float(raw[i, j]))
-            n_edges[z] = len(es)
-            G[z, :c][inside] = poses[inside]
-            placed[z, :c] = inside
-            js = worst if joint_score is None or joint_score != joint_score else float(joint_score)
-            if es:
-                n_joints[z] = _rule_joints(np.where(inside, 0, -1), raw, js, joints[z])
-    return BeamRule(*out, cost, n_hyp)
-
-
-def assemble_beam_batch(score, T, moment, count=None, beam=4, branch=4, weight=1.0, max_score=None, vote_score=None,
-                        joint_score=None):
-    """assemble_batch with a beam in place of the greedy walk, ONE launch for Z puzzles (ops.assemble_beam; beam_rule is its
-    numpy statement): `beam` hypotheses live side by side, each extended by its `branch` smallest entries, and a child is
-    charged its entry's score plus `weight` times how far the entries of the OTHER placed pieces put the new piece's boundary
-    from where this entry puts it (moment = boundary_moments(pieces, table.top_m)) - the cycles a spanning tree never asks.
-    weight = 1 is a definition: both terms are mean squared distances of the moved piece's k boundary points.  vote_score
-    (None: max_score) is the largest score an entry may have to vote.  -> BeamBatch: AssemblyBatch's fields for the cheapest
-    hypothesis, cost [Z,beam] float64 of all that lived (unused +inf) and n_hyp [Z] int32.  refine_assembly_batch and
-    evaluate_batch take it as they take an AssemblyBatch.  beam = branch = 1 is assemble_batch bit for bit.  Nothing waits for
-    the device."""
-    root, edges, edge_score, n_edges, G, placed, joints, n_joints, cost, n_hyp = ops.assemble_beam(
-        score, T, moment, count, beam, branch, weight, max_score, vote_score, joint_score)
-    placed, movable = _placed_movable(placed, root)
-    return BeamBatch(root, edges, edge_score, n_edges, G, placed, movable, joints, n_joints, cost, n_hyp)
-
-
-# --------------------------------------------------------------------------- the forest beam: the beam walk over a mixed pile
-
-ForestBeamBatch = collections.namedtuple("ForestBeamBatch", ForestBatch._fields + ("cost", "n_hyp"))
-ForestBeamRule = collections.namedtuple("ForestBeamRule", ForestRule._fields + ("cost", "n_hyp"))
-
-
 def _restart_charge(restart_cost, limit):
     """restart_cost as the rule reads it: None or NaN is max_score (limit) where that is finite, 0 otherwise."""
     if restart_cost is None or restart_cost != restart_cost:
@@ -1009,39 +877,23 @@ def _restart_charge(restart_cost, limit):
     return float(restart_cost)
 
 
-def forest_beam_rule(score, T, moment, count=None, beam=4, branch=4, weight=1.0, max_score=None, vote_score=None, joint_score=None,
-                     restart_cost=None):
-    """The numpy statement of ops.assemble_forest_beam (csrc/assembleforestbeam.hip, the rule in include/pzn.h), which is held
-    to it bit for bit, G and cost included: beam_rule with forest_rule's restarts.  The arguments are beam_rule's and restart_cost
-    (float; None or NaN: max_score where that is finite, else 0) -> ForestBeamRule: forest_rule's fields in its shapes and types,
-    cost [Z,beam] float64 and n_hyp [Z] int32.
-
-    Keys, ties, count, the stop test, the pose arithmetic, the candidates, a growth child's cost and the selection are
-    beam_rule's.  A hypothesis also holds the component of every placed piece and the roots of its components; the new piece of a
-    growth child joins the component of the candidate's placed end, and only the placed pieces of that component vote - the
-    others live in unrelated frames.  A hypothesis without a candidate has one child of rank 0, a restart: forest_rule's new root
-    (_rule_root over its outside pieces, or the one piece left) with the identity opens the next component, adds no edge and
-    costs parent + restart_cost.  So every hypothesis has a child, every child places one piece, and there are exactly count - 1
-    rounds.  The result is slot 0.  Single linkage under a threshold t minimises the sum of the edge scores + t (the number of
-    components): the default restart_cost extends the beam's cost to that objective.
-
-    beam = branch = 1 is forest_rule on every shared field; on a table where no live hypothesis ever lacks a candidate every
-    shared field, cost and n_hyp are beam_rule's.  Element-wise float64 only, no matmul."""
-    S, P, M = _as_np(score, np.float32), _as_np(T, np.float32), _as_np(moment, np.float64)
-    Z, K = S.shape[0], S.shape[1]
+def _beam_rule_body(who, restarts, score, T, moment, count, beam, branch, weight, max_score, vote_score, joint_score, restart_cost):
+    """beam_rule (restarts False) and forest_beam_rule (True): one statement of the candidates, the child's pose, the votes, the
+    selection and the result -> the fields of BeamRule or of ForestBeamRule.  A hypothesis is (inside, poses, edges, cost,
+    component, roots).  Without restarts a hypothesis without a candidate has no child, a round without any child ends the walk,
+    there is one component (so its pieces, the voters, are all the placed ones) and the forest's three fields do not exist."""
+    M = _as_np(moment, np.float64)
     B, C, weight = int(beam), int(branch), float(weight)
-    if S.shape != (Z, K, K) or P.shape != (Z, K, K, 4, 4) or M.shape != (Z, K, 4, 4) or K < 2:
-        raise ValueError(f"forest_beam_rule expects score[Z,K,K], T[Z,K,K,4,4], moment[Z,K,4,4] with K >= 2; got {S.shape}, "
-                         f"{P.shape}, {M.shape}")
+    S, P, counts, limit = _rule_table(score, T, count, max_score, who, M)
+    Z, K = S.shape[0], S.shape[1]
     if B < 1 or C < 1 or weight != weight:
-        raise ValueError(f"forest_beam_rule: beam = {B}, branch = {C} (>= 1), weight = {weight} (not NaN)")
-    counts = np.full(Z, K, dtype=np.int64) if count is None else _as_np(count, np.int64)
+        raise ValueError(f"{who}: beam = {B}, branch = {C} (>= 1), weight = {weight} (not NaN)")
     inf = float("inf")
-    limit = inf if max_score is None else float(max_score)
     vlimit = limit if vote_score is None or vote_score != vote_score else float(vote_score)
     charge = _restart_charge(restart_cost, limit)
-    out = ForestRule(*_rule_outputs(Z, K), np.full((Z, K), -1, dtype=np.int32), np.full((Z, K), -1, dtype=np.int32),
-                     np.zeros(Z, dtype=np.int32))
+    out = _rule_outputs(Z, K)
+    if restarts:
+        out = ForestRule(*out, np.full((Z, K), -1, dtype=np.int32), np.full((Z, K), -1, dtype=np.int32), np.zeros(Z, dtype=np.int32))
     cost = np.full((Z, B), np.inf, dtype=np.float64)
     n_hyp = np.zeros(Z, dtype=np.int32)
     with np.errstate(all="ignore"):
@@ -1061,7 +913,7 @@ def forest_beam_rule(score, T, moment, count=None, beam=4, branch=4, weight=1.0,
             pose0[r] = np.eye(4)
             comp0 = np.full(c, -1, dtype=np.int64)
             comp0[r] = 0
-            hyps = [(first, pose0, [], 0.0, comp0, [r])]                     # (inside, poses, edges, cost, component, roots)
+            hyps = [(first, pose0, [], 0.0, comp0, [r])]
             for _ in range(c - 1):
                 kids = []                                                    # (slot, rank, i, j, new, key); i = -1: a restart
                 for slot, (inside, _, _, _, _, _) in enumerate(hyps):
@@ -1069,17 +921,20 @@ def forest_beam_rule(score, T, moment, count=None, beam=4, branch=4, weight=1.0,
                     kv, fv = key.reshape(-1)[at], flat_of.reshape(-1)[at]
                     grown = False
                     for rank, q in enumerate(np.lexsort((fv, kv))[:C]):
-                        if not np.isfinite(kv[q]) or kv[q] > limit:
+                        if not np.isfinite(kv[q]) or kv[q] > limit:      # (as the walk stops: a key of -inf ends the list too)
                             break
                         i, j = divmod(int(fv[q]), K)
                         kids.append((slot, rank, i, j, j if inside[i] else i, float(kv[q])))
                         grown = True
-                    if not grown:
+                    if restarts and not grown:
                         outside = np.flatnonzero(~inside)
                         new = int(outside[0]) if len(outside) == 1 else _rule_root(key_rows, inside.tolist())
                         kids.append((slot, 0, -1, -1, new, charge))
+                if not kids:                                                 # (with restarts every hypothesis has a child)
+                    break
+                # the children's poses: G[new] = G[i] T[i,j], or G[j] inv(T[i,j]); a restart's root has the identity
                 grow = [ci for ci, kid in enumerate(kids) if kid[2] >= 0]
-                Gn = np.tile(np.eye(4), (len(kids), 1, 1))                                   # a restart's root has the identity
+                Gn = np.tile(np.eye(4), (len(kids), 1, 1))
                 if grow:
                     Tij = np.stack([Pz[kids[ci][2], kids[ci][3]] for ci in grow])
                     fwd = np.array([kids[ci][4] == kids[ci][3] for ci in grow])
@@ -1137,21 +992,74 @@ def forest_beam_rule(score, T, moment, count=None, beam=4, branch=4, weight=1.0,
             inside, poses, es, _, comp, rts = hyps[0]
             n_hyp[z] = len(hyps)
             cost[z, :len(hyps)] = [h[3] for h in hyps]
-            out.root[z], out.n_components[z] = rts[0], len(rts)
-            out.roots[z, :len(rts)] = rts
-            out.component[z, :c] = comp
-            worst = -inf
-            for e, (i, j, new) in enumerate(es):
-                out.edges[z, e] = (i, j, new)
-                out.edge_score[z, e] = S[z, i, j]
-                worst = max(worst, float(raw[i, j]))
-            out.n_edges[z] = len(es)
-            out.G[z, :c][inside] = poses[inside]
-            out.placed[z, :c] = inside
-            js = worst if joint_score is None or joint_score != joint_score else float(joint_score)
-            if es:
-                out.n_joints[z] = _rule_joints(comp.tolist(), raw, js, out.joints[z])
-    return ForestBeamRule(*out, cost, n_hyp)
+            out.root[z] = rts[0]
+            if restarts:
+                out.n_components[z] = len(rts)
+                out.roots[z, :len(rts)] = rts
+                out.component[z, :c] = comp
+            _rule_finish(z, out, S, raw, es, {int(p): poses[p] for p in np.flatnonzero(inside)}, comp.tolist(), joint_score)
+    return (*out, cost, n_hyp)
+
+
+def beam_rule(score, T, moment, count=None, beam=4, branch=4, weight=1.0, max_score=None, vote_score=None, joint_score=None):
+    """The numpy statement of ops.assemble_beam (csrc/assemblebeam.hip, the rule in include/pzn.h), which is held to it bit for
+    bit, G and cost included.  score [Z,K,K] (read as float32), T [Z,K,K,4,4] (float32), moment [Z,K,4,4] (float64), count [Z]
+    or None, tensors or arrays -> BeamRule: walk_rule's fields in its shapes and types, cost [Z,beam] float64 and n_hyp [Z] int32.
+
+    Keys, ties, the root, the pose arithmetic and count are walk_rule's.  A hypothesis is a placed set with its poses, edges and
+    a float64 cost; its candidates are the first `branch` ordered pairs with one end placed in the order (key, i K + j), keys
+    finite and <= max_score.  A child costs (parent + key) + weight * penalty, penalty = the mean, summed in vote order, of the
+    disagreement d of every other entry between a placed piece p (ascending; (p, n) then (n, p); keys finite and <= vote_score)
+    and the new piece n: D = G[p] T[p,n] - Gn or G[p] inv(T[n,p]) - Gn on rows 0..2, d = sum_u D_u M[n] D_u^T with the rule's
+    dot4 order.  The round's children are ordered by (cost, parent slot, rank) and the first `beam` distinct placed sets live on.
+    The result is slot 0.  Written with element-wise float64 only: no matmul, whose summation order is not fixed."""
+    return BeamRule(*_beam_rule_body("beam_rule", False, score, T, moment, count, beam, branch, weight, max_score, vote_score,
+                                     joint_score, None))
+
+
+def assemble_beam_batch(score, T, moment, count=None, beam=4, branch=4, weight=1.0, max_score=None, vote_score=None,
+                        joint_score=None):
+    """assemble_batch with a beam in place of the greedy walk, ONE launch for Z puzzles (ops.assemble_beam; beam_rule is its
+    numpy statement): `beam` hypotheses live side by side, each extended by its `branch` smallest entries, and a child is
+    charged its entry's score plus `weight` times how far the entries of the OTHER placed pieces put the new piece's boundary
+    from where this entry puts it (moment = boundary_moments(pieces, table.top_m)) - the cycles a spanning tree never asks.
+    weight = 1 is a definition: both terms are mean squared distances of the moved piece's k boundary points.  vote_score
+    (None: max_score) is the largest score an entry may have to vote.  -> BeamBatch: AssemblyBatch's fields for the cheapest
+    hypothesis, cost [Z,beam] float64 of all that lived (unused +inf) and n_hyp [Z] int32.  refine_assembly_batch and
+    evaluate_batch take it as they take an AssemblyBatch.  beam = branch = 1 is assemble_batch bit for bit.  Nothing waits for
+    the device."""
+    root, edges, edge_score, n_edges, G, placed, joints, n_joints, cost, n_hyp = ops.assemble_beam(
+        score, T, moment, count, beam, branch, weight, max_score, vote_score, joint_score)
+    placed, movable = _placed_movable(placed, root)
+    return BeamBatch(root, edges, edge_score, n_edges, G, placed, movable, joints, n_joints, cost, n_hyp)
+
+
+# --------------------------------------------------------------------------- the forest beam: the beam walk over a mixed pile
+
+ForestBeamBatch = collections.namedtuple("ForestBeamBatch", ForestBatch._fields + ("cost", "n_hyp"))
+ForestBeamRule = collections.namedtuple("ForestBeamRule", ForestRule._fields + ("cost", "n_hyp"))
+
+
+def forest_beam_rule(score, T, moment, count=None, beam=4, branch=4, weight=1.0, max_score=None, vote_score=None, joint_score=None,
+                     restart_cost=None):
+    """The numpy statement of ops.assemble_forest_beam (csrc/assemblebeam.hip, the rule in include/pzn.h), which is held
+    to it bit for bit, G and cost included: beam_rule with forest_rule's restarts.  The arguments are beam_rule's and restart_cost
+    (float; None or NaN: max_score where that is finite, else 0) -> ForestBeamRule: forest_rule's fields in its shapes and types,
+    cost [Z,beam] float64 and n_hyp [Z] int32.
+
+    Keys, ties, count, the stop test, the pose arithmetic, the candidates, a growth child's cost and the selection are
+    beam_rule's.  A hypothesis also holds the component of every placed piece and the roots of its components; the new piece of a
+    growth child joins the component of the candidate's placed end, and only the placed pieces of that component vote - the
+    others live in unrelated frames.  A hypothesis without a candidate has one child of rank 0, a restart: forest_rule's new root
+    (_rule_root over its outside pieces, or the one piece left) with the identity opens the next component, adds no edge and
+    costs parent + restart_cost.  So every hypothesis has a child, every child places one piece, and there are exactly count - 1
+    rounds.  The result is slot 0.  Single linkage under a threshold t minimises the sum of the edge scores + t (the number of
+    components): the default restart_cost extends the beam's cost to that objective.
+
+    beam = branch = 1 is forest_rule on every shared field; on a table where no live hypothesis ever lacks a candidate every
+    shared field, cost and n_hyp are beam_rule's.  Element-wise float64 only, no matmul."""
+    return ForestBeamRule(*_beam_rule_body("forest_beam_rule", True, score, T, moment, count, beam, branch, weight, max_score,
+                                           vote_score, joint_score, restart_cost))
 
 
 def assemble_forest_beam_batch(score, T, moment, count=None, beam=4, branch=4, weight=1.0, max_score=None, vote_score=None,
@@ -1168,12 +1076,9 @@ def assemble_forest_beam_batch(score, T, moment, count=None, beam=4, branch=4, w
     assemble_forest_batch bit for bit.  Nothing waits for the device."""
     root, edges, edge_score, n_edges, G, placed, joints, n_joints, component, roots, n_components, cost, n_hyp = \
         ops.assemble_forest_beam(score, T, moment, count, beam, branch, weight, max_score, vote_score, joint_score, restart_cost)
-    with torch.no_grad():
-        placed = placed.bool()
-        index = torch.arange(placed.shape[1], dtype=torch.int32, device=placed.device)
-        is_root = (roots[:, :, None] == index[None, None, :]).any(dim=1)
-    return ForestBeamBatch(root, edges, edge_score, n_edges, G, placed, placed & ~is_root, joints, n_joints, component, roots,
-                           n_components, cost, n_hyp)
+    placed, movable = _forest_movable(placed, roots)
+    return ForestBeamBatch(root, edges, edge_score, n_edges, G, placed, movable, joints, n_joints, component, roots, n_components,
+                           cost, n_hyp)
 
 
 def pair_block_batch(model, pieces_f, codes_f, pieces_m, codes_m, k=128, refine=0):

@@ -34,8 +34,6 @@ SOURCES = [
     ("jointrefine.hip", ["-ffp-contract=off"] + NOSLP),
     ("assemblewalk.hip", ["-ffp-contract=off"] + NOSLP),
     ("assemblebeam.hip", ["-ffp-contract=off"] + NOSLP),
-    ("assembleforest.hip", ["-ffp-contract=off"] + NOSLP),
-    ("assembleforestbeam.hip", ["-ffp-contract=off"] + NOSLP),
     ("progressive.hip", ["-ffp-contract=off"] + NOSLP),
     ("knn.hip", ["-ffp-contract=off"]),
     ("group.hip", ["-ffp-contract=off"] + NOSLP),

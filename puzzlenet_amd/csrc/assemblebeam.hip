@@ -1,6 +1,10 @@
-// assemblebeam.hip — the beam walk over Z pair tables, scored by the placed pieces' votes, for gfx950
-// (assembly.assemble_beam_batch).  include/pzn.h states the rule; assembly.beam_rule is its numpy statement, and every output
-// here is held to that bit for bit, the float64 poses and costs included.
+// assemblebeam.hip — the beam walks over Z pair tables, scored by the placed pieces' votes, for gfx950: one body, two kernels.
+//   * assemble_beam_kernel (assembly.assemble_beam_batch): B hypotheses of one tree each, C children of each per round;
+//   * assemble_forest_beam_kernel (assembly.assemble_forest_beam_batch): the same beam with the forest walk's restarts - a
+//     hypothesis that finds no admissible entry opens a new component from a new root, so the beam sorts and assembles a pile
+//     that holds several objects.
+// include/pzn.h states the rules; assembly.beam_rule and assembly.forest_beam_rule are their numpy statements, and every
+// output here is held to those bit for bit, the float64 poses and costs included.
 //
 // One wavefront per puzzle, one puzzle per workgroup, a capped grid with a loop over puzzles; no barrier (a wavefront's own LDS
 // accesses execute in order, pzn::wave_lds_sync tells the compiler).  A hypothesis lives in LDS: its K float64 poses, its cost,
@@ -17,6 +21,16 @@
 //     rank) is a 64-lane minimum of the cost's ordered bits and the lowest lane of the ballot of its ties; a winner whose
 //     placed set equals a kept child's is dropped; B winners at most;
 //   * the next generation: the wavefront copies each winner's parent poses and edges, the winner's lane adds its own.
+// Without FOREST a hypothesis without a candidate has no child, and a round without any child ends the walk (on a table without
+// -inf that is every live hypothesis in the same round: they fill the root's component together).
+// What FOREST adds to the body: a hypothesis holds the component of every piece and the roots of its components as bytes, and
+// the numbers of its components and edges in one dword (2 B (4 + 2 K) bytes more; the plain beam does not carve them out) - an
+// edge has the place of its number and not of the round, since a restart makes none;
+//   * a hypothesis whose first candidate pass finds nothing admissible gets the lanes of its rank 0 for the restart child; the
+//     new root is the forest walk's: the fold over the table masked to entries with both ends outside and one 64-lane minimum,
+//     or the one piece left; the child has the identity, no edge, no vote, and costs parent + restart_cost;
+//   * a vote is valid only from a piece of the component the new piece joins (the component of the candidate's placed end);
+//   * three more outputs.  Every hypothesis has a child in every round: count - 1 rounds, each placing one piece.
 // Every index into score, T and moment is formed from i, j < count[z] <= K.  No atomics: the same bits on every run.
 #include "pzn_common.h"
 #include "pzn_walk.h"      // the key, the 64-lane arg-min, the stop test, the float64 dot product, the beam's helpers, the result tail
@@ -31,24 +45,34 @@ constexpr int AB_MAX_B = 8, AB_MAX_C = 8;       // B C <= 64: every child has a 
 constexpr int AB_MAX_GRID = 2048;
 constexpr size_t AB_MAX_LDS = 160 * 1024;       // a CU's LDS on gfx950
 
-size_t ab_lds_bytes(int K, int B) { return (size_t)2 * B * ((size_t)K * 16 * sizeof(double) + 16 + (size_t)(K - 1) * 4); }
+// per hypothesis: K poses, cost and placed set, K - 1 edges; the forest adds (components | edges << 16), K component bytes,
+// K root bytes
+size_t ab_lds_bytes(int K, int B, bool forest) {
+  return (size_t)2 * B * ((size_t)K * 16 * sizeof(double) + 16 + (size_t)(K - 1) * 4 + (forest ? 4 + (size_t)2 * K : 0));
+}
 
-__global__ __launch_bounds__(AB_T) void assemble_beam_kernel(const float* __restrict__ score, const float* __restrict__ T,
-                                                             const double* __restrict__ moment, const int32_t* __restrict__ count,
-                                                             double max_score, double vote_score, double joint_score, double weight,
-                                                             int Z, int K, int B, int C, int L, int32_t* __restrict__ root,
-                                                             int32_t* __restrict__ edges, float* __restrict__ edge_score,
-                                                             int32_t* __restrict__ n_edges, double* __restrict__ G,
-                                                             uint8_t* __restrict__ placed, int32_t* __restrict__ joints,
-                                                             int32_t* __restrict__ n_joints, double* __restrict__ cost,
-                                                             int32_t* __restrict__ n_hyp) {
+template <bool FOREST>
+__device__ __forceinline__ void beam_walk_body(
+    const float* __restrict__ score, const float* __restrict__ T, const double* __restrict__ moment,
+    const int32_t* __restrict__ count, double max_score, double vote_score, double joint_score, double weight, double restart_cost,
+    int Z, int K, int B, int C, int L, int32_t* __restrict__ root, int32_t* __restrict__ edges, float* __restrict__ edge_score,
+    int32_t* __restrict__ n_edges, double* __restrict__ G, uint8_t* __restrict__ placed, int32_t* __restrict__ joints,
+    int32_t* __restrict__ n_joints, int32_t* __restrict__ component, int32_t* __restrict__ roots,
+    int32_t* __restrict__ n_components, double* __restrict__ cost, int32_t* __restrict__ n_hyp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int lane = (int)threadIdx.x;
   const int E = K - 1, KK = K * K, JR = K * (K - 1);
   double* pose = reinterpret_cast<double*>(smem_raw);                           // [2][B][K][16]
   double* hcost = pose + (size_t)2 * B * K * 16;                                // [2][B]
   uint64_t* hin = reinterpret_cast<uint64_t*>(hcost + 2 * B);                   // [2][B] placed sets
-  uint32_t* hedge = reinterpret_cast<uint32_t*>(hin + 2 * B);                   // [2][B][K-1]
+  uint32_t* hedge = reinterpret_cast<uint32_t*>(hin + 2 * B);                   // [2][B][K-1], by edge number
+  uint32_t* hnum = nullptr;                                                     // FOREST: [2][B] components | edges << 16
+  uint8_t *hcomp = nullptr, *hroot = nullptr;                                   // FOREST: [2][B][K] each, below
+  if constexpr (FOREST) {
+    hnum = hedge + (size_t)2 * B * E;
+    hcomp = reinterpret_cast<uint8_t*>(hnum + 2 * B);                           // the component of every placed piece
+    hroot = hcomp + (size_t)2 * B * K;                                          // the root of every component
+  }
   const uint64_t NONE = ~(uint64_t)0;
   const double vlimit = vote_score != vote_score ? max_score : vote_score;
   const int grp = lane / L, sub = lane - grp * L;                               // child slot C + rank is lanes grp L .. grp L + L-1
@@ -64,6 +88,7 @@ __global__ __launch_bounds__(AB_T) void assemble_beam_kernel(const float* __rest
 
     int cur = 0, H = 0, ne = 0, r = -1;
     if (live) {
+      [[maybe_unused]] const uint64_t all = c == 64 ? NONE : (((uint64_t)1 << c) - 1);      // FOREST
       uint64_t best = NONE;
       for (int t = lane; t < cc; t += PZN_WAVE) {
         const int i = t / c, j = t - i * c;
@@ -73,13 +98,17 @@ __global__ __launch_bounds__(AB_T) void assemble_beam_kernel(const float* __rest
       best = wave_min_u64_dpp(best);
       r = __builtin_amdgcn_readfirstlane((int)((uint32_t)best / (uint32_t)K));
       if (lane < 16) pose[16 * r + lane] = (lane >> 2) == (lane & 3) ? 1.0 : 0.0;      // generation 0, slot 0
-      if (lane == 0) hcost[0] = 0.0, hin[0] = (uint64_t)1 << r;
+      if (lane == 0) {
+        hcost[0] = 0.0, hin[0] = (uint64_t)1 << r;
+        if constexpr (FOREST) hnum[0] = 1u, hcomp[r] = 0, hroot[0] = (uint8_t)r;
+      }
       pzn::wave_lds_sync();
       H = 1;
 
       for (int round = 0; round + 1 < c; ++round) {
-        // the candidates of every live hypothesis
+        // the candidates of every live hypothesis, or (FOREST) its restart
         uint64_t mine = NONE;
+        int restart = -1;                         // FOREST: the new root, in the lanes of a restart child
         for (int h = 0; h < H; ++h) {
           const uint64_t in_h = hin[cur * B + h];
           uint64_t last = 0;                      // (below every key)
@@ -99,25 +128,52 @@ __global__ __launch_bounds__(AB_T) void assemble_beam_kernel(const float* __rest
             last = next;
             if (grp == h * C + rank) mine = next;
           }
+          if constexpr (FOREST) {
+            if (last == 0) {                      // nothing admissible: a new component starts (in_h != all before the last round's end)
+              const uint64_t out = all & ~in_h;
+              int nr;
+              if ((out & (out - 1)) == 0) {
+                nr = (int)__builtin_ctzll(out);
+              } else {
+                uint64_t low = NONE;
+                for (int t = lane; t < cc; t += PZN_WAVE) {
+                  const int i = t / c, j = t - i * c;
+                  if ((out >> i) & (out >> j) & 1) {
+                    const uint64_t k = entry(S[i * K + j], i, j, K);
+                    low = k < low ? k : low;
+                  }
+                }
+                low = wave_min_u64_dpp(low);
+                nr = __builtin_amdgcn_readfirstlane((int)((uint32_t)low / (uint32_t)K));
+              }
+              if (grp == h * C) restart = nr;
+            }
+          }
         }
 
         // the children, L lanes each: every lane composes the child's pose (the same bits), the votes are dealt out
-        const bool has = mine != NONE;
+        const bool grow = mine != NONE, has = grow || restart >= 0;
         double ccost = __builtin_inf();
         double gn[16], m[16];
         uint64_t in_p = 0, cin = 0;                // the parent's placed set, the child's
-        int flat = 0, nw = 0;
+        uint32_t pnum = 0;                         // FOREST: the parent's components | edges << 16
+        int flat = 0, nw = 0, jc = 0;              // the entry, the new piece, FOREST: the component it joins
         bool fwd = false;
 #pragma unroll
-        for (int e = 0; e < 16; ++e) gn[e] = 0.0, m[e] = 0.0;
+        for (int e = 0; e < 16; ++e) gn[e] = ((e >> 2) == (e & 3)) ? 1.0 : 0.0, m[e] = 0.0;
+        const uint8_t* pcomp = nullptr;            // FOREST: the parent's components (read if `has`)
+        if constexpr (FOREST) pcomp = hcomp + (size_t)(cur * B + my_slot) * K;
         if (has) {
+          in_p = hin[cur * B + my_slot];
+          if constexpr (FOREST) pnum = hnum[cur * B + my_slot];
+        }
+        if (grow) {
           flat = (int)(uint32_t)mine;
           const float key = unordered((uint32_t)(mine >> 32));
           const int i = flat / K, j = flat - i * K;
-          in_p = hin[cur * B + my_slot];
           fwd = (in_p >> i) & 1;                   // the fixed end is placed: G[j] = G[i] T[i,j]
           nw = fwd ? j : i;
-          cin = in_p | ((uint64_t)1 << nw);
+          if constexpr (FOREST) jc = (int)pcomp[fwd ? i : j];
           const double* hp = pose + ((size_t)(cur * B + my_slot) * K) * 16;             // the parent's poses
           double b[16];
           right_factor(Tz + (size_t)flat * 16, fwd, b);
@@ -134,16 +190,25 @@ __global__ __launch_bounds__(AB_T) void assemble_beam_kernel(const float* __rest
 #pragma unroll
             for (int e = 0; e < 16; ++e) m[e] = Mz[16 * nw + e];
           }
+        } else if (FOREST && has) {                // a restart: the new root with the identity opens component `pnum & 0xffff`
+          nw = restart;
+          jc = (int)(pnum & 0xffffu);
+          ccost = hcost[cur * B + my_slot] + restart_cost;
         }
+        cin = in_p | (has ? (uint64_t)1 << nw : 0);
         if (weight != 0.0) {
-          // vote v = 2 p + dir: entry (p, n), then (n, p), p ascending.  Lane `sub` of a child takes votes sub, sub + L, ...; after
-          // every L votes their disagreements are added to the child's ONE running sum in vote order, in all its lanes alike.
+          // vote v = 2 p + dir: entry (p, n), then (n, p), p ascending over the placed pieces (FOREST: of the joined component).
+          // Lane `sub` of a child takes votes sub, sub + L, ...; after every L votes their disagreements are added to the child's
+          // ONE running sum in vote order, in all its lanes alike.
           double sum = 0.0;
           int votes = 0;
           for (int v0 = 0; v0 < 2 * c; v0 += L) {                                       // (wavefront-uniform)
             const int v = v0 + sub, p = v >> 1;
             const int vf = (v & 1) ? nw * K + p : p * K + nw;
-            bool valid = has && v < 2 * c && ((in_p >> p) & 1) && vf != flat;           // (not the candidate's own entry)
+            bool valid = grow && v < 2 * c && ((in_p >> p) & 1) && vf != flat;          // (not the candidate's own entry)
+            if constexpr (FOREST) {
+              if (valid) valid = (int)pcomp[p] == jc;                                   // (p < c: a byte of the parent's row)
+            }
             if (valid) {
               const float s = S[vf];
               const float k = s != s ? __builtin_inff() : s;
@@ -173,7 +238,7 @@ __global__ __launch_bounds__(AB_T) void assemble_beam_kernel(const float* __rest
               if (__shfl((int)valid, from, PZN_WAVE)) sum = sum + dt, ++votes;
             }
           }
-          if (has) {
+          if (grow) {                              // (a restart has no penalty term)
             const double penalty = votes ? sum / (double)votes : 0.0;
             ccost = ccost + weight * penalty;
           }
@@ -182,7 +247,7 @@ __global__ __launch_bounds__(AB_T) void assemble_beam_kernel(const float* __rest
 
         // selection: (cost, slot, rank) = (cost, lane); the first B distinct placed sets
         uint64_t remaining = __ballot(has && sub == 0);        // a child's first lane stands for it: lane order is still (slot, rank)
-        if (remaining == 0) break;                 // a round without any child ends the walk
+        if (remaining == 0) break;                 // a round without any child ends the walk (FOREST: every hypothesis has one)
         const uint64_t ckey = ordered64(ccost);
         uint64_t kept = 0;
         int nk = 0, my_new = -1;
@@ -199,31 +264,58 @@ __global__ __launch_bounds__(AB_T) void assemble_beam_kernel(const float* __rest
           }
         }
 
-        // the next generation
+        // the next generation: the parent's poses and edges (FOREST: components and roots), then the winner's own
         const int nxt = cur ^ 1;
         for (int s = 0; s < nk; ++s) {
           const int h = __builtin_ctzll(__ballot(my_new == s)) / L / C;
+          int ne_h = round, nc_h = 0;              // the parent's edges - one a round, but for restarts - and FOREST: components
+          if constexpr (FOREST) {
+            const uint32_t num = hnum[cur * B + h];
+            nc_h = (int)(num & 0xffffu), ne_h = (int)(num >> 16);
+          }
           const double* from = pose + ((size_t)(cur * B + h) * K) * 16;
           double* to = pose + ((size_t)(nxt * B + s) * K) * 16;
           for (int e = lane; e < 16 * c; e += PZN_WAVE) to[e] = from[e];
-          for (int e = lane; e < round; e += PZN_WAVE) hedge[(nxt * B + s) * E + e] = hedge[(cur * B + h) * E + e];
+          for (int e = lane; e < ne_h; e += PZN_WAVE) hedge[(nxt * B + s) * E + e] = hedge[(cur * B + h) * E + e];
+          if constexpr (FOREST) {
+            for (int e = lane; e < c; e += PZN_WAVE) hcomp[(nxt * B + s) * K + e] = hcomp[(cur * B + h) * K + e];
+            for (int e = lane; e < nc_h; e += PZN_WAVE) hroot[(nxt * B + s) * K + e] = hroot[(cur * B + h) * K + e];
+          }
         }
         pzn::wave_lds_sync();
         if (my_new >= 0) {
-          double* to = pose + ((size_t)(nxt * B + my_new) * K + nw) * 16;
+          const int at = nxt * B + my_new;
+          const int nc_p = (int)(pnum & 0xffffu), ne_p = FOREST ? (int)(pnum >> 16) : round;      // nc_p <= round + 1 < K, ne_p <= round < K - 1
+          double* to = pose + ((size_t)at * K + nw) * 16;
 #pragma unroll
           for (int e = 0; e < 16; ++e) to[e] = gn[e];
-          hcost[nxt * B + my_new] = ccost;
-          hin[nxt * B + my_new] = cin;
-          hedge[(nxt * B + my_new) * E + round] = (uint32_t)flat | ((uint32_t)fwd << 16);
+          hcost[at] = ccost;
+          hin[at] = cin;
+          if constexpr (FOREST) hcomp[at * K + nw] = (uint8_t)jc;
+          if (grow) {
+            hedge[at * E + ne_p] = (uint32_t)flat | ((uint32_t)fwd << 16);
+            if constexpr (FOREST) hnum[at] = pnum + (1u << 16);
+          } else if constexpr (FOREST) {
+            hroot[at * K + nc_p] = (uint8_t)nw;
+            hnum[at] = pnum + 1u;
+          }
         }
         pzn::wave_lds_sync();
-        cur = nxt, H = nk, ++ne;
+        cur = nxt, H = nk;
+        if constexpr (!FOREST) ++ne;               // (an edge a round)
       }
     }
 
     // the result is slot 0: the walk's outputs
     const uint64_t in = H > 0 ? hin[cur * B] : 0;
+    int nc = 0, my_comp = 0, my_root = -1;         // FOREST: components, the component of piece `lane`, the root of component `lane`
+    if constexpr (FOREST) {
+      const uint32_t num = H > 0 ? hnum[cur * B] : 0;
+      nc = (int)(num & 0xffffu), ne = (int)(num >> 16);
+      my_comp = (H > 0 && lane < c) ? (int)hcomp[(cur * B) * K + lane] : -1;      // (every piece < c is placed)
+      my_root = lane < nc ? (int)hroot[(cur * B) * K + lane] : -1;
+      r = __builtin_amdgcn_readfirstlane(my_root);                               // (lane 0: the first component's)
+    }
     int my_i = -1, my_j = -1, my_nw = -1;
     float my_s = __builtin_inff();
     uint32_t top = 0;
@@ -245,20 +337,72 @@ __global__ __launch_bounds__(AB_T) void assemble_beam_kernel(const float* __rest
       const double id = ((e >> 2) & 3) == (e & 3) ? 1.0 : 0.0;
       G[(size_t)z * K * 16 + e] = ((in >> (e >> 4)) & 1) ? pose[(size_t)(cur * B) * K * 16 + e] : id;
     }
+    if constexpr (FOREST) {
+      if (lane < K) component[(size_t)z * K + lane] = my_comp, roots[(size_t)z * K + lane] = my_root;
+    }
     if (lane < B) cost[(size_t)z * B + lane] = lane < H ? hcost[cur * B + lane] : __builtin_inf();
 
-    // the placed bytes and the joints, by the walk's rule from the result's own edges
-    const int nj = walk_tail(in, c, K, ne, worst, joint_score, S, lane, 0, placed + (size_t)z * K, joints + (size_t)z * JR * 2);
-    if (lane == 0) root[z] = r, n_edges[z] = ne, n_joints[z] = nj, n_hyp[z] = H;
+    // the placed bytes and the joints (FOREST: of every component), by the walk's rule from the result's own edges
+    const int nj = walk_tail(in, c, K, ne, worst, joint_score, S, lane, my_comp, placed + (size_t)z * K, joints + (size_t)z * JR * 2);
+    if (lane == 0) {
+      root[z] = r, n_edges[z] = ne, n_joints[z] = nj, n_hyp[z] = H;
+      if constexpr (FOREST) n_components[z] = nc;
+    }
     pzn::wave_lds_sync();      // the hypotheses are replaced by the next puzzle's
   }
 }
 
+__global__ __launch_bounds__(AB_T) void assemble_beam_kernel(const float* __restrict__ score, const float* __restrict__ T,
+                                                             const double* __restrict__ moment, const int32_t* __restrict__ count,
+                                                             double max_score, double vote_score, double joint_score, double weight,
+                                                             int Z, int K, int B, int C, int L, int32_t* __restrict__ root,
+                                                             int32_t* __restrict__ edges, float* __restrict__ edge_score,
+                                                             int32_t* __restrict__ n_edges, double* __restrict__ G,
+                                                             uint8_t* __restrict__ placed, int32_t* __restrict__ joints,
+                                                             int32_t* __restrict__ n_joints, double* __restrict__ cost,
+                                                             int32_t* __restrict__ n_hyp) {
+  beam_walk_body<false>(score, T, moment, count, max_score, vote_score, joint_score, weight, 0.0, Z, K, B, C, L, root, edges,
+                        edge_score, n_edges, G, placed, joints, n_joints, nullptr, nullptr, nullptr, cost, n_hyp);
+}
+
+__global__ __launch_bounds__(AB_T) void assemble_forest_beam_kernel(
+    const float* __restrict__ score, const float* __restrict__ T, const double* __restrict__ moment,
+    const int32_t* __restrict__ count, double max_score, double vote_score, double joint_score, double weight, double restart_cost,
+    int Z, int K, int B, int C, int L, int32_t* __restrict__ root, int32_t* __restrict__ edges, float* __restrict__ edge_score,
+    int32_t* __restrict__ n_edges, double* __restrict__ G, uint8_t* __restrict__ placed, int32_t* __restrict__ joints,
+    int32_t* __restrict__ n_joints, int32_t* __restrict__ component, int32_t* __restrict__ roots,
+    int32_t* __restrict__ n_components, double* __restrict__ cost, int32_t* __restrict__ n_hyp) {
+  beam_walk_body<true>(score, T, moment, count, max_score, vote_score, joint_score, weight, restart_cost, Z, K, B, C, L, root, edges,
+                       edge_score, n_edges, G, placed, joints, n_joints, component, roots, n_components, cost, n_hyp);
+}
+
+bool ab_supported(int K, int B, int C, bool forest) {
+  return K >= 2 && K <= AB_MAX_K && B >= 1 && B <= AB_MAX_B && C >= 1 && C <= AB_MAX_C && ab_lds_bytes(K, B, forest) <= AB_MAX_LDS;
+}
+
+// the launch of either kernel: its LDS (allowed by attribute above 64 KB), a workgroup per puzzle up to the cap, and the lanes
+// per child, which go in front of `outputs...` in the kernel's arguments
+template <typename Kernel, typename... Args>
+int ab_launch(Kernel kernel, bool forest, hipStream_t st, int Z, int K, int beam, int branch, Args... args) {
+  const size_t lds = ab_lds_bytes(K, beam, forest);
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return PZN_ELAUNCH;
+  const int grid = Z < AB_MAX_GRID ? Z : AB_MAX_GRID;
+  PZN_LAUNCH(kernel, dim3(grid), dim3(AB_T), lds, st, args...);
+  PZN_RETURN_LAUNCH_STATUS();
+}
+
+// lanes per child: the largest power of two with B C lanes <= 64
+int ab_lanes(int beam, int branch) {
+  int lanes = 1;
+  while (2 * lanes * beam * branch <= PZN_WAVE) lanes *= 2;
+  return lanes;
+}
+
 }  // namespace
 
-PZN_EXPORT int pzn_assemble_beam_supported(int K, int B, int C) {
-  return K >= 2 && K <= AB_MAX_K && B >= 1 && B <= AB_MAX_B && C >= 1 && C <= AB_MAX_C && ab_lds_bytes(K, B) <= AB_MAX_LDS;
-}
+PZN_EXPORT int pzn_assemble_beam_supported(int K, int B, int C) { return ab_supported(K, B, C, false); }
 
 PZN_EXPORT int pzn_assemble_beam_f32(const float* score, const float* T, const double* moment, const int32_t* count, int beam,
                                      int branch, double weight, double max_score, double vote_score, double joint_score, int Z,
@@ -270,15 +414,27 @@ PZN_EXPORT int pzn_assemble_beam_f32(const float* score, const float* T, const d
   PZN_CHECK_ARG(max_score == max_score && weight == weight);
   if (Z == 0) return PZN_OK;
   PZN_CHECK_ARG(score && T && moment && root && edges && edge_score && n_edges && G && placed && joints && n_joints && cost && n_hyp);
-  hipStream_t st = pzn_hip_stream(stream);
-  const size_t lds = ab_lds_bytes(K, beam);
-  if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_beam_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return PZN_ELAUNCH;
-  const int grid = Z < AB_MAX_GRID ? Z : AB_MAX_GRID;
-  int lanes = 1;                                  // lanes per child: the largest power of two with B C lanes <= 64
-  while (2 * lanes * beam * branch <= PZN_WAVE) lanes *= 2;
-  PZN_LAUNCH(assemble_beam_kernel, dim3(grid), dim3(AB_T), lds, st, score, T, moment, count, max_score, vote_score, joint_score,
-             weight, Z, K, beam, branch, lanes, root, edges, edge_score, n_edges, G, placed, joints, n_joints, cost, n_hyp);
-  PZN_RETURN_LAUNCH_STATUS();
+  return ab_launch(assemble_beam_kernel, false, pzn_hip_stream(stream), Z, K, beam, branch, score, T, moment, count, max_score,
+                   vote_score, joint_score, weight, Z, K, beam, branch, ab_lanes(beam, branch), root, edges, edge_score, n_edges, G,
+                   placed, joints, n_joints, cost, n_hyp);
+}
+
+PZN_EXPORT int pzn_assemble_forest_beam_supported(int K, int B, int C) { return ab_supported(K, B, C, true); }
+
+PZN_EXPORT int pzn_assemble_forest_beam_f32(const float* score, const float* T, const double* moment, const int32_t* count,
+                                            int beam, int branch, double weight, double max_score, double vote_score,
+                                            double joint_score, double restart_cost, int Z, int K, int32_t* root, int32_t* edges,
+                                            float* edge_score, int32_t* n_edges, double* G, uint8_t* placed, int32_t* joints,
+                                            int32_t* n_joints, int32_t* component, int32_t* roots, int32_t* n_components,
+                                            double* cost, int32_t* n_hyp, pzn_stream_t stream) {
+  if (!pzn_assemble_forest_beam_supported(K, beam, branch)) return PZN_EUNSUPPORTED;
+  PZN_CHECK_ARG(Z >= 0);
+  PZN_CHECK_ARG(max_score == max_score && weight == weight);
+  if (Z == 0) return PZN_OK;
+  PZN_CHECK_ARG(score && T && moment && root && edges && edge_score && n_edges && G && placed && joints && n_joints && component &&
+                roots && n_components && cost && n_hyp);
+  if (restart_cost != restart_cost) restart_cost = (max_score - max_score == 0.0) ? max_score : 0.0;      // NaN: a finite max_score, else 0
+  return ab_launch(assemble_forest_beam_kernel, true, pzn_hip_stream(stream), Z, K, beam, branch, score, T, moment, count, max_score,
+                   vote_score, joint_score, weight, restart_cost, Z, K, beam, branch, ab_lanes(beam, branch), root, edges,
+                   edge_score, n_edges, G, placed, joints, n_joints, component, roots, n_components, cost, n_hyp);
 }

@@ -1,11 +1,10 @@
-// pzn_walk.h — what the walks over pair tables share (assemblewalk.hip, assemblebeam.hip, assembleforest.hip, assembleforestbeam.hip,
-// progressive.hip): the key of a table
+// pzn_walk.h — what the walks over pair tables share (assemblewalk.hip, assemblebeam.hip, progressive.hip): the key of a table
 // entry, the 64-lane lexicographic arg-min over (key, i K + j), the stop test on a round's winning key, the order-fixed float64
-// dot product the poses are composed with, the beam walks' ordered cost bits, lane reads and right factor, and the tail of a walk's
-// result (the assemble*.hip): the placed
-// bytes and the joint list.  One statement of each, so "the smallest key, the lowest i K + j on ties", "the walk stops here"
-// and "every operation rounded on its own" mean the same in every kernel.  Files that include it are built with
-// -ffp-contract=off and say so again with the pragma.
+// dot product the poses are composed with, the greedy walks' sixteen-lane pose product, the beam walks' ordered cost bits, lane
+// reads and right factor, and the tail of a walk's result (assemblewalk.hip, assemblebeam.hip): the placed bytes and the joint
+// list.  One statement of each, so "the smallest key, the lowest i K + j on ties", "the walk stops here" and "every operation
+// rounded on its own" mean the same in every kernel.  Files that include it are built with -ffp-contract=off and say so again
+// with the pragma.
 #ifndef PZN_WALK_H_
 #define PZN_WALK_H_
 
@@ -53,7 +52,7 @@ __device__ __forceinline__ double dot4(double a0, double b0, double a1, double b
   return ((a0 * b0 + a1 * b1) + a2 * b2) + a3 * b3;
 }
 
-// ---- what the beam walks share (assemblebeam.hip, assembleforestbeam.hip)
+// ---- what the beam walks share (assemblebeam.hip)
 
 // doubles -> qword with the doubles' order (no NaN reaches it), -0 as +0
 __device__ __forceinline__ uint64_t ordered64(double x) {
@@ -79,6 +78,30 @@ __device__ __forceinline__ void right_factor(const float* __restrict__ t, bool f
   const double inv[16] = {d[0], d[4], d[8], i0, d[1], d[5], d[9], i1, d[2], d[6], d[10], i2, 0.0, 0.0, 0.0, 1.0};
 #pragma unroll
   for (int e = 0; e < 16; ++e) b[e] = fwd ? d[e] : inv[e];
+}
+
+// The greedy walks' pose product g[nw] = g[src] B over the [K][16] float64 poses g in LDS, B = T[i,j] as t stores it (fwd) or
+// its rigid inverse: the wavefront's first sixteen lanes, one entry each - lane 4 u + v takes column v of B and row u of
+// g[src] (right_factor's arithmetic entry for entry, but a column a lane and not the whole factor).  nw != src: no lane reads
+// what another writes.
+__device__ __forceinline__ void compose_pose16(double* g, int src, int nw, const float* __restrict__ t, bool fwd, int lane) {
+  if (lane < 16) {
+    const int u = lane >> 2, v = lane & 3;
+    double b0, b1, b2, b3;
+    if (fwd) {
+      b0 = (double)t[v], b1 = (double)t[4 + v], b2 = (double)t[8 + v], b3 = (double)t[12 + v];
+    } else if (v < 3) {
+      b0 = (double)t[4 * v], b1 = (double)t[4 * v + 1], b2 = (double)t[4 * v + 2], b3 = 0.0;
+    } else {
+      const double t0 = (double)t[3], t1 = (double)t[7], t2 = (double)t[11];
+      b0 = -(((double)t[0] * t0 + (double)t[4] * t1) + (double)t[8] * t2);
+      b1 = -(((double)t[1] * t0 + (double)t[5] * t1) + (double)t[9] * t2);
+      b2 = -(((double)t[2] * t0 + (double)t[6] * t1) + (double)t[10] * t2);
+      b3 = 1.0;
+    }
+    const double* a = g + 16 * src + 4 * u;
+    g[16 * nw + lane] = dot4(a[0], b0, a[1], b1, a[2], b2, a[3], b3);
+  }
 }
 
 // The tail of a walk's result for one puzzle, by its wavefront: `in` is the placed set (bit p = piece p), c the puzzle's

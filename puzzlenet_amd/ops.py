@@ -415,6 +415,12 @@ def assemble_walk(score, T, count=None, max_score=None, joint_score=None):
     return out
 
 
+def _forest_outputs(Z, K, dev):
+    """What the forest walks add to _walk_outputs -> (component [Z,K], roots [Z,K], n_components [Z]) int32, not initialised."""
+    component, roots = (torch.empty((Z, K), dtype=torch.int32, device=dev) for _ in range(2))
+    return component, roots, torch.empty((Z,), dtype=torch.int32, device=dev)
+
+
 def assemble_forest_supported(K):
     return bool(_lib.load().pzn_assemble_forest_supported(int(K)))
 
@@ -430,15 +436,36 @@ def assemble_forest(score, T, count=None, max_score=None, joint_score=None):
     score, T, count, max_score, joint_score, Z, K = _walk_args("assemble_forest", score, T, count, max_score, joint_score)
     if not assemble_forest_supported(K):
         raise _lib.PznUnsupported(f"assemble_forest: K = {K} pieces (2 <= K <= 64)")
-    dev = score.device
-    root, edges, edge_score, n_edges, G, placed, joints, n_joints = _walk_outputs(Z, K, dev)
-    component, roots = (torch.empty((Z, K), dtype=torch.int32, device=dev) for _ in range(2))
-    n_components = torch.empty((Z,), dtype=torch.int32, device=dev)
-    with _on(dev):
+    out = root, edges, edge_score, n_edges, G, placed, joints, n_joints, component, roots, n_components = \
+        _walk_outputs(Z, K, score.device) + _forest_outputs(Z, K, score.device)
+    with _on(score.device):
         _call("pzn_assemble_forest_f32", _p(score), _p(T), _p(count), max_score, joint_score, Z, K, _p(root), _p(edges),
               _p(edge_score), _p(n_edges), _p(G), _p(placed), _p(joints), _p(n_joints), _p(component), _p(roots), _p(n_components),
               _stream())
-    return root, edges, edge_score, n_edges, G, placed, joints, n_joints, component, roots, n_components
+    return out
+
+
+def _beam_args(who, supported, score, T, moment, count, beam, branch, weight, max_score, vote_score, joint_score):
+    """What the beam walks take alike, checked (`supported`: the caller's own test) -> (score, T, moment, count, beam, branch,
+    weight, max_score, vote_score, joint_score, Z, K) as the library takes them: no vote_score is NaN."""
+    if isinstance(moment, torch.Tensor) and moment.dtype != torch.float64:      # (no silent conversion)
+        raise _lib.PznError(f"{who}: moment must be {torch.float64}; got {moment.dtype}")
+    score, T, count, max_score, joint_score, Z, K = _walk_args(who, score, T, count, max_score, joint_score)
+    moment = _req(moment, torch.float64, "moment")
+    if tuple(moment.shape) != (Z, K, 4, 4):
+        raise _lib.PznError(f"{who}: expected moment[{Z},{K},4,4]; got {tuple(moment.shape)}")
+    beam, branch, weight = int(beam), int(branch), float(weight)
+    vote_score = float("nan") if vote_score is None else float(vote_score)
+    if weight != weight:
+        raise _lib.PznError(f"{who}: weight is NaN")
+    if not supported(K, beam, branch):
+        raise _lib.PznUnsupported(f"{who}: K = {K} pieces, beam = {beam}, branch = {branch} (2 <= K <= 64, 1 <= beam, branch <= 8)")
+    return score, T, moment, count, beam, branch, weight, max_score, vote_score, joint_score, Z, K
+
+
+def _beam_outputs(Z, beam, dev):
+    """-> (cost [Z,beam] float64, n_hyp [Z] int32), not initialised."""
+    return torch.empty((Z, beam), dtype=torch.float64, device=dev), torch.empty((Z,), dtype=torch.int32, device=dev)
 
 
 def assemble_beam_supported(K, beam=4, branch=4):
@@ -452,28 +479,15 @@ def assemble_beam(score, T, moment, count=None, beam=4, branch=4, weight=1.0, ma
     max_score) -> assemble_walk's eight outputs for the cheapest hypothesis, then cost [Z,beam] float64 (slot order, unused
     +inf) and n_hyp [Z] int32.  2 <= K <= 64 (PznUnsupported beyond).  Z = 0 launches nothing.  No autograd, nothing waits
     for the device."""
-    if isinstance(moment, torch.Tensor) and moment.dtype != torch.float64:      # (no silent conversion)
-        raise _lib.PznError(f"assemble_beam: moment must be {torch.float64}; got {moment.dtype}")
-    score, T, count, max_score, joint_score, Z, K = _walk_args("assemble_beam", score, T, count, max_score, joint_score)
-    moment = _req(moment, torch.float64, "moment")
-    if tuple(moment.shape) != (Z, K, 4, 4):
-        raise _lib.PznError(f"assemble_beam: expected moment[{Z},{K},4,4]; got {tuple(moment.shape)}")
-    beam, branch, weight = int(beam), int(branch), float(weight)
-    vote_score = float("nan") if vote_score is None else float(vote_score)
-    if weight != weight:
-        raise _lib.PznError("assemble_beam: weight is NaN")
-    if not assemble_beam_supported(K, beam, branch):
-        raise _lib.PznUnsupported(f"assemble_beam: K = {K} pieces, beam = {beam}, branch = {branch} (2 <= K <= 64, 1 <= beam, "
-                                  "branch <= 8)")
-    dev = score.device
-    root, edges, edge_score, n_edges, G, placed, joints, n_joints = _walk_outputs(Z, K, dev)
-    cost = torch.empty((Z, beam), dtype=torch.float64, device=dev)
-    n_hyp = torch.empty((Z,), dtype=torch.int32, device=dev)
-    with _on(dev):
+    score, T, moment, count, beam, branch, weight, max_score, vote_score, joint_score, Z, K = _beam_args(
+        "assemble_beam", assemble_beam_supported, score, T, moment, count, beam, branch, weight, max_score, vote_score, joint_score)
+    out = root, edges, edge_score, n_edges, G, placed, joints, n_joints, cost, n_hyp = \
+        _walk_outputs(Z, K, score.device) + _beam_outputs(Z, beam, score.device)
+    with _on(score.device):
         _call("pzn_assemble_beam_f32", _p(score), _p(T), _p(moment), _p(count), beam, branch, weight, max_score, vote_score,
               joint_score, Z, K, _p(root), _p(edges), _p(edge_score), _p(n_edges), _p(G), _p(placed), _p(joints), _p(n_joints),
               _p(cost), _p(n_hyp), _stream())
-    return root, edges, edge_score, n_edges, G, placed, joints, n_joints, cost, n_hyp
+    return out
 
 
 def assemble_forest_beam_supported(K, beam=4, branch=4):
@@ -488,30 +502,18 @@ def assemble_forest_beam(score, T, moment, count=None, beam=4, branch=4, weight=
     0) -> assemble_forest's eleven outputs for the cheapest hypothesis, then cost [Z,beam] float64 (slot order, unused +inf) and
     n_hyp [Z] int32.  2 <= K <= 64, beam and branch in 1 .. 8 (PznUnsupported beyond).  Z = 0 launches nothing.  No autograd,
     nothing waits for the device."""
-    who = "assemble_forest_beam"
-    if isinstance(moment, torch.Tensor) and moment.dtype != torch.float64:      # (no silent conversion)
-        raise _lib.PznError(f"{who}: moment must be {torch.float64}; got {moment.dtype}")
-    score, T, count, max_score, joint_score, Z, K = _walk_args(who, score, T, count, max_score, joint_score)
-    moment = _req(moment, torch.float64, "moment")
-    if tuple(moment.shape) != (Z, K, 4, 4):
-        raise _lib.PznError(f"{who}: expected moment[{Z},{K},4,4]; got {tuple(moment.shape)}")
-    beam, branch, weight = int(beam), int(branch), float(weight)
-    vote_score = float("nan") if vote_score is None else float(vote_score)
+    score, T, moment, count, beam, branch, weight, max_score, vote_score, joint_score, Z, K = _beam_args(
+        "assemble_forest_beam", assemble_forest_beam_supported, score, T, moment, count, beam, branch, weight, max_score, vote_score,
+        joint_score)
     restart_cost = float("nan") if restart_cost is None else float(restart_cost)
-    if weight != weight:
-        raise _lib.PznError(f"{who}: weight is NaN")
-    if not assemble_forest_beam_supported(K, beam, branch):
-        raise _lib.PznUnsupported(f"{who}: K = {K} pieces, beam = {beam}, branch = {branch} (2 <= K <= 64, 1 <= beam, branch <= 8)")
     dev = score.device
-    root, edges, edge_score, n_edges, G, placed, joints, n_joints = _walk_outputs(Z, K, dev)
-    component, roots = (torch.empty((Z, K), dtype=torch.int32, device=dev) for _ in range(2))
-    n_components, n_hyp = (torch.empty((Z,), dtype=torch.int32, device=dev) for _ in range(2))
-    cost = torch.empty((Z, beam), dtype=torch.float64, device=dev)
+    out = root, edges, edge_score, n_edges, G, placed, joints, n_joints, component, roots, n_components, cost, n_hyp = \
+        _walk_outputs(Z, K, dev) + _forest_outputs(Z, K, dev) + _beam_outputs(Z, beam, dev)
     with _on(dev):
         _call("pzn_assemble_forest_beam_f32", _p(score), _p(T), _p(moment), _p(count), beam, branch, weight, max_score, vote_score,
               joint_score, restart_cost, Z, K, _p(root), _p(edges), _p(edge_score), _p(n_edges), _p(G), _p(placed), _p(joints),
               _p(n_joints), _p(component), _p(roots), _p(n_components), _p(cost), _p(n_hyp), _stream())
-    return root, edges, edge_score, n_edges, G, placed, joints, n_joints, component, roots, n_components, cost, n_hyp
+    return out
 
 
 ProgressiveState = collections.namedtuple("ProgressiveState", "alive part G done n_edges edges edge_score")

@@ -1,4 +1,4 @@
-"""GPU: ops.assemble_forest (csrc/assembleforest.hip, assemble_forest_kernel) against assembly.forest_rule - the numpy statement of the
+"""GPU: ops.assemble_forest (csrc/assemblewalk.hip, assemble_forest_kernel) against assembly.forest_rule - the numpy statement of the
 rule in include/pzn.h, itself held to single linkage and to walk_rule in tests/test_assembly_forest_cpu.py - with np.array_equal on all
 eleven outputs, the float64 poses included: both sides compose them in IEEE double in the same order, so there is no tolerance.  Then
 the chain a pile goes through - datapipe.fracture, datapipe.pile, truth_table, assemble_forest_batch, refine_assembly_batch,

@@ -1,4 +1,4 @@
-"""GPU: ops.assemble_forest_beam (csrc/assembleforestbeam.hip, assemble_forest_beam_kernel) against assembly.forest_beam_rule -
+"""GPU: ops.assemble_forest_beam (csrc/assemblebeam.hip, assemble_forest_beam_kernel) against assembly.forest_beam_rule -
 the numpy statement of the rule in include/pzn.h, itself held to forest_rule, to beam_rule and to a scalar replay in
 tests/test_assembly_forest_beam_cpu.py - bit for bit in all thirteen outputs, the float64 poses and costs included: both sides do
 the same IEEE double operations in the same order, so there is no tolerance.  Then against the two kernels it joins,

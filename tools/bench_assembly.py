@@ -54,6 +54,7 @@ planted piles of tests/_forest_beam_cases.py: 2 objects of 8 pieces, 4 of 16) be
 
 Needs a GPU (there is no CPU path)."""
 import argparse
+import functools
 import json
 import os
 import statistics
@@ -94,6 +95,23 @@ def _device_ms(fn, calls):
     b.record()
     torch.cuda.synchronize()
     return a.elapsed_time(b) / calls
+
+
+def _kernel_us(fn, name, reps, warmup):
+    """Mean device time in us of the launches of the one kernel whose name holds `name`, over `reps` calls of fn after `warmup`
+    untimed ones (the library's own event pair per launch, ops.ktimer_start / ktimer_stop)."""
+    from puzzlenet_amd import ops
+    for _ in range(warmup):
+        fn()
+    ops.ktimer_start()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    rows = ops.ktimer_stop()
+    hit = [v for k_, v in rows.items() if name in k_]
+    if len(hit) != 1 or hit[0][0] != reps:
+        sys.exit(f"kernel timer: expected {reps} launches of {name} in one row, got {rows}")
+    return 1e3 * hit[0][1] / hit[0][0]
 
 
 def progressive(args):
@@ -353,17 +371,7 @@ def beam(args):
               "timing": "kernels: the library's own event pair per launch (ops.ktimer_*), us; match_puzzles: device time between two "
                         "events around one call, ms"}
 
-    def kernel_us(fn, name):
-        fn()
-        ops.ktimer_start()
-        for _ in range(args.reps):
-            fn()
-        torch.cuda.synchronize()
-        rows = ops.ktimer_stop()
-        hit = [v for k_, v in rows.items() if name in k_]
-        if len(hit) != 1 or hit[0][0] != args.reps:
-            sys.exit(f"kernel timer: expected {args.reps} launches of {name} in one row, got {rows}")
-        return 1e3 * hit[0][1] / hit[0][0]
+    kernel_us = functools.partial(_kernel_us, reps=args.reps, warmup=1)
 
     for P in (8, 16):
         rng = np.random.RandomState(16)
@@ -405,18 +413,7 @@ def forest(args):
     Z = args.batch or 64
     dev = torch.device("cuda:0")
 
-    def kernel_us(fn, name):
-        for _ in range(max(args.warmup, 1)):
-            fn()
-        ops.ktimer_start()
-        for _ in range(args.reps):
-            fn()
-        torch.cuda.synchronize()
-        rows = ops.ktimer_stop()
-        hit = [v for k_, v in rows.items() if name in k_]
-        if len(hit) != 1 or hit[0][0] != args.reps:
-            sys.exit(f"kernel timer: expected {args.reps} launches of {name} in one row, got {rows}")
-        return 1e3 * hit[0][1] / hit[0][0]
+    kernel_us = functools.partial(_kernel_us, reps=args.reps, warmup=max(args.warmup, 1))
 
     lines = [f"tools/bench_assembly.py --forest --batch {Z} --reps {args.reps} on {torch.cuda.get_device_name(0)}",
              "the library's own event pair per launch (ops.ktimer_*), mean over the timed launches after the warm-up, us;",
@@ -447,18 +444,7 @@ def forest_beam(args):
     Z = args.batch or 64
     dev = torch.device("cuda:0")
 
-    def kernel_us(fn, name):
-        for _ in range(max(args.warmup, 1)):
-            fn()
-        ops.ktimer_start()
-        for _ in range(args.reps):
-            fn()
-        torch.cuda.synchronize()
-        rows = ops.ktimer_stop()
-        hit = [v for k_, v in rows.items() if name in k_]
-        if len(hit) != 1 or hit[0][0] != args.reps:
-            sys.exit(f"kernel timer: expected {args.reps} launches of {name} in one row, got {rows}")
-        return 1e3 * hit[0][1] / hit[0][0]
+    kernel_us = functools.partial(_kernel_us, reps=args.reps, warmup=max(args.warmup, 1))
 
     lines = [f"tools/bench_assembly.py --forest-beam --batch {Z} --reps {args.reps} on {torch.cuda.get_device_name(0)}",
              "the library's own event pair per launch (ops.ktimer_*), mean over the timed launches after the warm-up, us;",
