@@ -117,6 +117,29 @@ int pzn_icp_refine_f32(const float* a, const int64_t* a_of, const float* b, cons
                        const float* T0, int P, int ka, int kb, int iters,
                        float* T, float* score, float* score0, int32_t* iters_used,
                        int32_t* corr_a, int32_t* corr_b, pzn_stream_t stream);
+/* pzn_icp_refine_f32 for partial contact: of each direction's rows only a fixed number counts, keep_a of the ka rows of a and
+ * keep_b of the kb rows of b, so the faces of a piece that belong to other neighbours neither score nor pull.  Inputs, the
+ * arithmetic of a pose and of a distance, the row minima and their arg-mins are pzn_icp_refine_f32's.
+ * Kept set of a direction under a pose: its m rows with the smallest (row minimum, row index) in lexicographic order - among
+ * equal minima the lowest row index is kept; exactly m rows whatever the ties.
+ * Objective E(T) = (sum of the kept a-row minima) / keep_a + (sum of the kept b-row minima) / keep_b, the kept minima added
+ * in pzn_icp_refine_f32's order with the other rows skipped.  One iteration: the keep_a + keep_b pairs of the kept rows
+ * alone, each of one weight, give the candidate (centroids, cross-covariance, the degenerate rule and Horn's solve as there,
+ * the divisor keep_a + keep_b); E(T') < E(T), each with its own pose's kept sets, takes it, anything else (NaN included)
+ * stops.  So score <= score0 holds to the bit.
+ * Out: T, score, score0, iters_used, corr_a / corr_b with pzn_icp_refine_f32's meaning (corr_* hold the arg-min of EVERY
+ * row, kept or not), and, when non-NULL, kept_a[P,keep_a] / kept_b[P,keep_b] (int32, ascending): the rows kept under the
+ * RETURNED T, whether or not the last candidate was rejected (the kernel holds the current pose's mask and the candidate's
+ * side by side); with iters = 0 the rows kept under T0.  The same bits on every run.
+ * keep_a = ka and keep_b = kb is pzn_icp_refine_f32 bit for bit on every shared output, with kept_* = 0 .. k-1.
+ * 1 <= ka, kb <= 1024, 1 <= keep_a <= ka, 1 <= keep_b <= kb (pzn_icp_refine_trim_supported: 1 / 0) and iters >= 0,
+ * PZN_EUNSUPPORTED otherwise, before any launch; P = 0 is a success that launches nothing. */
+int pzn_icp_refine_trim_supported(int ka, int kb, int keep_a, int keep_b);
+int pzn_icp_refine_trim_f32(const float* a, const int64_t* a_of, const float* b, const int64_t* b_of,
+                            const float* T0, int P, int ka, int kb, int keep_a, int keep_b, int iters,
+                            float* T, float* score, float* score0, int32_t* iters_used,
+                            int32_t* corr_a, int32_t* corr_b, int32_t* kept_a, int32_t* kept_b,
+                            pzn_stream_t stream);
 
 /* Refine all piece poses of Z placed assemblies jointly over every joint (no counterpart in the reference): one launch, one
  * workgroup per puzzle, no workspace, no atomics, no grid-wide synchronisation, nothing waits for the device.  Puzzle z has

@@ -75,6 +75,8 @@ Inference only: eval mode, torch.no_grad(), fp32, one GPU.  Out of scope: any tr
 pieces, a beam or several merges per round of the progressive walk, undoing a merge, and more than one GPU.
 """
 import collections
+import math
+import numbers
 
 import numpy as np
 import torch
@@ -82,13 +84,34 @@ import torch
 from . import _lib, ops, se3
 from .model5_b import draw_fps_starts, pick_order_plan, run_seq, run_seq_cat_global, sampling_plan, upload_starts
 
-PairTable = collections.namedtuple("PairTable", "twist T de_fpcb de_mrpcb top_f top_m score x2")
+class PairTable(collections.namedtuple("PairTable", "twist T de_fpcb de_mrpcb top_f top_m score x2")):
+    __slots__ = ()
+    kept_f = kept_m = None      # (no field: a table that carries kept sets is a TrimmedPairTable, below)
+
+
+
 Assembly = collections.namedtuple("Assembly", "root edges G placed")
 PieceCodes = collections.namedtuple("PieceCodes", "U V local_f g_max de_mrpcb top_m x2")
-PairBlock = collections.namedtuple("PairBlock", "twist T de_fpcb top_f score")
-Refined = collections.namedtuple("Refined", "T score score0 iters_used")
+class PairBlock(collections.namedtuple("PairBlock", "twist T de_fpcb top_f score")):
+    __slots__ = ()
+    kept_f = kept_m = None
+
+
+class Refined(collections.namedtuple("Refined", "T score score0 iters_used")):
+    __slots__ = ()
+    kept_f = kept_m = None
+
+
+
 JointRefined = collections.namedtuple("JointRefined", "G score score0 sweeps_used accepted joints")
 Progressive = collections.namedtuple("Progressive", "G edges placed cloud piece_id row_id parts")
+
+# keep < 1 (partial contact): the same tuples with the trailing fields kept_f [...,Kf,Km,m_f] and kept_m [...,Kf,Km,m_m].  The
+# untrimmed types answer kept_f / kept_m with None and keep their fields, so whatever walks over the fields of today's table
+# meets tensors only; code that rebuilds a tuple field by field uses type(t)(...).
+TrimmedPairTable = collections.namedtuple("TrimmedPairTable", PairTable._fields + ("kept_f", "kept_m"))
+TrimmedPairBlock = collections.namedtuple("TrimmedPairBlock", PairBlock._fields + ("kept_f", "kept_m"))
+TrimmedRefined = collections.namedtuple("TrimmedRefined", Refined._fields + ("kept_f", "kept_m"))
 
 ENCODER_ROWS = 64      # pieces per encoder call (the fused per-point stem takes up to 64 clouds)
 
@@ -198,25 +221,51 @@ def encode_pieces(model, pieces, k=128, start=None, plan=None, _who="encode_piec
     return PieceCodes(U, V, local_f, g_max.squeeze(1), de_mrpcb.permute(0, 2, 1), top_m, plan[1][0])
 
 
-def _refine_gathered(Bf, Bm, T, iters):
+def _keep_counts(keep, k_f, k_m, who):
+    """keep as the pair functions take it - a fraction in (0, 1] of the picked rows, or a pair (fixed side, moved side) of
+    such (Python or numpy real numbers) - -> None where every row is kept (today's path), otherwise the counts (m_f, m_m) =
+    ceil(f k), at least 1, that ops.icp_refine takes as keep: known on the host, nothing waits for the device.  The product is
+    formed in double arithmetic and one within 1e-9 above an integer counts as that integer (0.07 x 100 is 7.000000000000001
+    in binary and means 7 rows, not 8)."""
+    fs = tuple(keep) if isinstance(keep, (tuple, list)) else (keep, keep)
+    if len(fs) != 2 or not all(isinstance(f, numbers.Real) and not isinstance(f, (bool, np.bool_)) and 0.0 < f <= 1.0 for f in fs):
+        raise _lib.PznError(f"{who}: keep = {keep!r} (a fraction in (0, 1] of the picked rows, or a pair (fixed, moved) of such)")
+    if fs[0] == 1.0 and fs[1] == 1.0:
+        return None
+    return tuple(min(k, max(1, math.ceil(float(f) * k - 1e-9))) for f, k in zip(fs, (int(k_f), int(k_m))))
+
+
+def _refine_gathered(Bf, Bm, T, iters, keep=None):
     """refine_pairs on boundaries that are gathered already, for any leading puzzle dimensions of T [...,Kf,Km,4,4]: Bf
     [Z Kf Km,k,3] per pair, Bm [Z Km,k,3] per moved piece (served to every fixed piece of its puzzle: problem (z, i, j) reads
-    Bm[z Km + j]) -> Refined with T's leading dimensions.  One launch."""
+    Bm[z Km + j]) -> Refined with T's leading dimensions.  One launch.  keep = (m_f, m_m) counts (_keep_counts): the trimmed
+    launch, iters = 0 included -> TrimmedRefined with kept_f [...,m_f] and kept_m [...,m_m]; None: the untrimmed launch."""
     Kf, Km = T.shape[-4], T.shape[-3]
     Z = T.numel() // (Kf * Km * 16)
     b_of = torch.arange(Z * Km, dtype=torch.long, device=T.device).view(Z, 1, Km).expand(Z, Kf, Km).reshape(-1)
-    Tr, score, score0, used = ops.icp_refine(Bf, Bm, T.reshape(Z * Kf * Km, 4, 4), iters, b_of=b_of)
     lead = T.shape[:-2]
-    return Refined(Tr.view(*lead, 4, 4), score.view(lead), score0.view(lead), used.view(lead))
+    if keep is None:
+        Tr, score, score0, used = ops.icp_refine(Bf, Bm, T.reshape(Z * Kf * Km, 4, 4), iters, b_of=b_of)
+        return Refined(Tr.view(*lead, 4, 4), score.view(lead), score0.view(lead), used.view(lead))
+    Tr, score, score0, used, kept_f, kept_m = ops.icp_refine(Bf, Bm, T.reshape(Z * Kf * Km, 4, 4), iters, b_of=b_of, keep=keep,
+                                                             return_kept=True)
+    return TrimmedRefined(Tr.view(*lead, 4, 4), score.view(lead), score0.view(lead), used.view(lead), kept_f.view(*lead, keep[0]),
+                          kept_m.view(*lead, keep[1]))
 
 
-def refine_pairs(pieces_f, top_f, pieces_m, top_m, T, iters=30):
+def refine_pairs(pieces_f, top_f, pieces_m, top_m, T, iters=30, keep=1.0):
     """Refine every pair pose on its matched boundaries: for pieces_f [Kf,N,3] with picked rows top_f [Kf,Km,k], pieces_m
     [Km,N,3] with top_m [Km,k] and poses T [Kf,Km,4,4] (T[i,j] maps moved piece j into fixed piece i's frame), symmetric
     point-to-point ICP between pieces_f[i][top_f[i,j]] and pieces_m[j][top_m[j]] from T[i,j], at most `iters` accepted steps
     -> Refined(T [Kf,Km,4,4], score [Kf,Km], score0 [Kf,Km], iters_used [Kf,Km] int32).  score is the table's quantity (mean
     + mean of the squared nearest-neighbour distances) under the returned pose and never above score0, the same under T.
-    All Kf Km problems run in one launch (ops.icp_refine); nothing waits for the device."""
+    All Kf Km problems run in one launch (ops.icp_refine); nothing waits for the device.
+    keep (a fraction in (0, 1] of the k picked rows, or a pair (fixed side, moved side)): partial contact - only the
+    ceil(f k) rows of each side that lie closest to the other side under the pose at hand count, in the score and in every
+    step (the trimmed launch; include/pzn.h states the rule), so the picked rows on faces towards other neighbours neither
+    score nor pull.  The result is then a TrimmedRefined: Refined's fields, then kept_f [Kf,Km,m_f] and kept_m [Kf,Km,m_m]
+    (int32, ascending), positions into top_f[i,j] and top_m[j] of the rows kept under the returned pose.  keep = 1.0 is the
+    untrimmed launch and a Refined, whose kept_f and kept_m are None."""
     _on_gpu("refine_pairs", pieces_f=pieces_f, pieces_m=pieces_m, T=T, top_f=top_f, top_m=top_m)
     if pieces_f.dim() != 3 or pieces_m.dim() != 3 or pieces_f.shape[2] != 3 or pieces_m.shape[2] != 3:
         raise _lib.PznError(f"refine_pairs expects pieces_f[Kf,N,3], pieces_m[Km,N,3]; got {tuple(pieces_f.shape)}, "
@@ -225,10 +274,11 @@ def refine_pairs(pieces_f, top_f, pieces_m, top_m, T, iters=30):
     if top_f.dim() != 3 or top_f.shape[:2] != (Kf, Km) or top_m.dim() != 2 or top_m.shape[0] != Km or T.shape != (Kf, Km, 4, 4):
         raise _lib.PznError(f"refine_pairs expects top_f[{Kf},{Km},k], top_m[{Km},k], T[{Kf},{Km},4,4]; got "
                             f"{tuple(top_f.shape)}, {tuple(top_m.shape)}, {tuple(T.shape)}")
+    counts = _keep_counts(keep, top_f.shape[2], top_m.shape[1], "refine_pairs")
     with torch.no_grad():
         Bf = ops.index_points(pieces_f, top_f.reshape(Kf, -1)).view(Kf * Km, top_f.shape[2], 3)
         Bm = ops.index_points(pieces_m, top_m)
-        return _refine_gathered(Bf, Bm, T.contiguous(), iters)
+        return _refine_gathered(Bf, Bm, T.contiguous(), iters, counts)
 
 
 def _check_refine(refine, who):
@@ -238,16 +288,17 @@ def _check_refine(refine, who):
     return refine
 
 
-def pair_block(model, pieces_f, codes_f, pieces_m, codes_m, k=128, refine=0):
+def pair_block(model, pieces_f, codes_f, pieces_m, codes_m, k=128, refine=0, keep=1.0):
     """The rectangular block of the pair table with pieces_f [Kf,N,3] in the fixed role and pieces_m [Km,N,3] in the moved
     role, from their PieceCodes -> PairBlock(twist [Kf,Km,6], T [Kf,Km,4,4], de_fpcb [Kf,Km,2,N], top_f [Kf,Km,k],
     score [Kf,Km]); entries as match_pairs documents them (no diagonal is masked here).  refine > 0: T and score are those
     of refine_pairs(..., iters=refine) from the network's pose, one launch in place of the transform and the chamfer; twist
-    stays the network's output.  It is pair_block_batch for one puzzle."""
+    stays the network's output.  keep as pair_block_batch takes it (kept_f [Kf,Km,m_f], kept_m [Kf,Km,m_m]).  It is
+    pair_block_batch for one puzzle."""
     refine = _check_refine(refine, "pair_block")
     one = lambda codes: PieceCodes(*(f[None] for f in codes))
-    blk = pair_block_batch(model, pieces_f[None], one(codes_f), pieces_m[None], one(codes_m), k, refine)
-    return PairBlock(*(f[0] for f in blk))
+    blk = pair_block_batch(model, pieces_f[None], one(codes_f), pieces_m[None], one(codes_m), k, refine, keep)
+    return type(blk)(*(f[0] for f in blk))
 
 
 def _diagonal(pieces):
@@ -259,10 +310,11 @@ def _table(codes, blk, mask=None):
     """The PairTable of pieces with the PieceCodes `codes` and their square PairBlock; score is +inf where mask (None: blk's
     score is masked already)."""
     score = blk.score if mask is None else blk.score.masked_fill(mask, float("inf"))
-    return PairTable(blk.twist, blk.T, blk.de_fpcb, codes.de_mrpcb, blk.top_f, codes.top_m, score, codes.x2)
+    fields = (blk.twist, blk.T, blk.de_fpcb, codes.de_mrpcb, blk.top_f, codes.top_m, score, codes.x2)
+    return PairTable(*fields) if blk.kept_f is None else TrimmedPairTable(*fields, blk.kept_f, blk.kept_m)
 
 
-def match_pairs(model, pieces, k=128, start=None, refine=0):
+def match_pairs(model, pieces, k=128, start=None, refine=0, keep=1.0):
     """All K (K - 1) ordered pairs of `pieces` [K,N,3] (float32, on the GPU, N = model.num_points, K >= 2) through
     predict5's eval path with every piece encoded once -> PairTable, index order [fixed i, moved j]:
 
@@ -282,13 +334,22 @@ def match_pairs(model, pieces, k=128, start=None, refine=0):
 
     refine = N > 0: T and score are refined on the picked rows (refine_pairs, at most N accepted ICP steps from se3.exp(twist),
     one launch for the table; the diagonal is refined like any pair and then masked); twist stays the network's output, so
-    T is no longer se3.exp(twist); every other field is what refine = 0 gives, bit for bit."""
+    T is no longer se3.exp(twist); every other field is what refine = 0 gives, bit for bit.
+
+    keep (a fraction in (0, 1] of the k picked rows, or a pair (fixed side, moved side); 1.0: every row, today's table): a
+    piece has several fracture faces and only part of one mates with a given neighbour, while top_m[j] is picked for piece j
+    alone.  With keep < 1 only the ceil(f k) rows of each side closest to the other side count (refine_pairs states it),
+    always through the one trimmed launch - at refine = 0 it runs with no step, so T stays se3.exp(twist) and score is the
+    trimmed score under it.  The table is then a TrimmedPairTable: PairTable's fields, then kept_f [K,K,m_f] and kept_m
+    [K,K,m_m] (int32: positions into top_f[i,j] and top_m[j] of the rows kept under T[i,j]); at keep = 1.0 it is a PairTable,
+    whose kept_f and kept_m are None.  Every other field but T and score is what keep = 1.0 gives."""
     refine = _check_refine(refine, "match_pairs")
     _check_pieces(model, pieces, k, "match_pairs", 2)
     if start is not None:
         start = tuple(torch.as_tensor(s, dtype=torch.long)[None] for s in start)
-    pieces, codes, blk = _match_puzzles(model, pieces[None], k, start, refine, "match_pairs")
-    return PairTable(*(f[0] for f in _table(codes, blk, _diagonal(pieces))))
+    pieces, codes, blk = _match_puzzles(model, pieces[None], k, start, refine, "match_pairs", keep)
+    table = _table(codes, blk, _diagonal(pieces))
+    return type(table)(*(f[0] for f in table))
 
 
 def _host(a):
@@ -364,7 +425,12 @@ def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None):
     largest score among asm.edges - a definition, not a measurement: the tree edges are then always joints and every placed
     piece has one.  Joint (i, j) pairs pieces[i][table.top_f[i,j]] with pieces[j][table.top_m[j]] (one set per moved piece,
     served to all its joints).  Every piece that is placed and not the root may move; sweeps = 0 returns asm.G.
-    One download (the scores the joints are chosen from), one gather and one launch."""
+    One download (the scores the joints are chosen from), one gather and one launch.
+
+    A table that carries kept sets (match_pairs(..., keep < 1)): joint (i, j) pairs pieces[i][top_f[i,j][kept_f[i,j]]] with
+    pieces[j][top_m[j][kept_m[i,j]]] - m_f and m_m rows, the moved-side set now one per ordered pair.  The kernel and its
+    energy are the same, the untrimmed one over the rows the pair refinement kept: the joint refinement FREEZES the kept
+    sets, it does not trim again under its own poses."""
     _clouds("refine_assembly", "K", pieces=pieces)
     K, N, _ = pieces.shape
     G0 = np.asarray(asm.G, dtype=np.float64)
@@ -391,11 +457,16 @@ def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None):
             ji = torch.tensor([i for i, _ in joints], dtype=torch.long, device=dev)
             jj = torch.tensor([j for _, j in joints], dtype=torch.long, device=dev)
             # one gather over the K N rows of all pieces: the J fixed-side sets, then one moved-side set per piece
-            rows_a = (ji[:, None] * N + table.top_f[ji, jj]).reshape(-1)
-            rows_b = (torch.arange(K, device=dev)[:, None] * N + table.top_m).reshape(-1)
+            if table.kept_f is None:
+                rows_a = (ji[:, None] * N + table.top_f[ji, jj]).reshape(-1)
+                rows_b = (torch.arange(K, device=dev)[:, None] * N + table.top_m).reshape(-1)
+                ka, nb, b_of = k, K, jj.reshape(1, J)
+            else:      # the kept rows of every joint: a moved-side set per ordered pair
+                rows_a = (ji[:, None] * N + table.top_f[ji, jj].gather(1, table.kept_f[ji, jj].long())).reshape(-1)
+                rows_b = (jj[:, None] * N + table.top_m[jj].gather(1, table.kept_m[ji, jj].long())).reshape(-1)
+                ka, nb, b_of = table.kept_f.shape[-1], J, None
             picked = ops.index_points(pieces.contiguous().view(1, K * N, 3), torch.cat((rows_a, rows_b)).reshape(1, -1))[0]
-            a, b = picked[:J * k].view(J, k, 3), picked[J * k:].view(K, k, 3)
-            b_of = jj.reshape(1, J)
+            a, b = picked[:J * ka].view(J, ka, 3), picked[J * ka:].view(nb, -1, 3)
         else:
             a = b = pieces[:0, :k]
             b_of = None
@@ -1081,7 +1152,7 @@ def assemble_forest_beam_batch(score, T, moment, count=None, beam=4, branch=4, w
                            cost, n_hyp)
 
 
-def pair_block_batch(model, pieces_f, codes_f, pieces_m, codes_m, k=128, refine=0):
+def pair_block_batch(model, pieces_f, codes_f, pieces_m, codes_m, k=128, refine=0, keep=1.0):
     """pair_block for Z puzzles, block-diagonal: pieces_f [Z,Kf,N,3] in the fixed role meet only the pieces_m [Z,Km,N,3] of their
     own puzzle -> PairBlock whose every field carries a leading Z (twist [Z,Kf,Km,6], T [Z,Kf,Km,4,4], de_fpcb [Z,Kf,Km,2,N], top_f
     [Z,Kf,Km,k], score [Z,Kf,Km]).  codes_* are PieceCodes whose fields are [Z,K,...] views of one encode_pieces call over Z K pieces.
@@ -1089,7 +1160,9 @@ def pair_block_batch(model, pieces_f, codes_f, pieces_m, codes_m, k=128, refine=
     ops.pair_head_blocks launch, softmax and one topk_rows, one gather per side, then the transform and ops.chamfer or
     (refine > 0) the one ops.icp_refine launch.  de_fpcb has the same bits whatever Z is (the blocked head does not know about
     z); the fields behind the few-row layers agree between batches as two calls on the same batch do.  Nothing waits for the
-    device."""
+    device.  keep as match_pairs documents it: anything but 1.0 on both sides replaces the transform and the chamfer, or the
+    untrimmed launch, by the one trimmed ops.icp_refine launch (iters = refine, 0 included) -> TrimmedPairBlock with kept_f
+    [Z,Kf,Km,m_f], kept_m [Z,Kf,Km,m_m]; 1.0 is today's path untouched and a PairBlock, whose kept_* are None."""
     refine = _check_refine(refine, "pair_block_batch")
     _clouds("pair_block_batch", "Z,K", pieces_f=pieces_f, pieces_m=pieces_m)
     Z, Kf, N = pieces_f.shape[0], pieces_f.shape[1], pieces_f.shape[2]
@@ -1101,6 +1174,7 @@ def pair_block_batch(model, pieces_f, codes_f, pieces_m, codes_m, k=128, refine=
             or tuple(codes_m.g_max.shape[:2]) != (Z, Km) or tuple(codes_m.top_m.shape[:2]) != (Z, Km):
         raise _lib.PznError(f"pair_block_batch: the codes are not [Z,K,...] views of Z = {Z} puzzles of {Kf} and {Km} pieces")
     k = int(k)
+    counts = _keep_counts(keep, k, codes_m.top_m.shape[-1], "pair_block_batch")
     with torch.no_grad():
         # pose head: the four layers after the split first one run on the Z Kf Km rows relu(U_i + V_j)
         hidden = torch.relu(codes_f.U[:, :, None] + codes_m.V[:, None]).reshape(Z * Kf * Km, -1)
@@ -1116,6 +1190,9 @@ def pair_block_batch(model, pieces_f, codes_f, pieces_m, codes_m, k=128, refine=
         # pieces_f[z,i][top_f[z,i,j]] per pair, pieces_m[z,j][top_m[z,j]] per moved piece
         Bf = ops.index_points(pieces_f.reshape(Z * Kf, N, 3), top_f.reshape(Z * Kf, Km * k)).view(Z * Kf * Km, k, 3)
         Bm = ops.index_points(pieces_m.reshape(Z * Km, N, 3), codes_m.top_m.reshape(Z * Km, -1))
+        if counts is not None:      # partial contact: the trimmed launch, with no step at refine = 0
+            r = _refine_gathered(Bf, Bm, T.contiguous(), refine, counts)
+            return TrimmedPairBlock(twist, r.T, de_fpcb, top_f, r.score, r.kept_f, r.kept_m)
         if refine > 0:
             r = _refine_gathered(Bf, Bm, T, refine)
             return PairBlock(twist, r.T, de_fpcb, top_f, r.score)
@@ -1125,7 +1202,7 @@ def pair_block_batch(model, pieces_f, codes_f, pieces_m, codes_m, k=128, refine=
     return PairBlock(twist, T, de_fpcb, top_f, score)
 
 
-def _match_puzzles(model, pieces, k, start, refine, who):
+def _match_puzzles(model, pieces, k, start, refine, who, keep=1.0):
     """match_puzzles' body -> (pieces contiguous, PieceCodes of [Z,P,...] views, the square PairBlock, diagonal not masked)."""
     refine = _check_refine(refine, who)
     _clouds(who, "Z,P", pieces=pieces)
@@ -1141,18 +1218,19 @@ def _match_puzzles(model, pieces, k, start, refine, who):
         start = (s1.reshape(Z * P), s2.reshape(Z * P))
     codes = encode_pieces(model, flat, k, start, _who=who, _least=2)
     codes = PieceCodes(*(f.view(Z, P, *f.shape[1:]) for f in codes))
-    return pieces, codes, pair_block_batch(model, pieces, codes, pieces, codes, k, refine)
+    return pieces, codes, pair_block_batch(model, pieces, codes, pieces, codes, k, refine, keep)
 
 
-def match_puzzles(model, pieces, k=128, start=None, refine=0):
+def match_puzzles(model, pieces, k=128, start=None, refine=0, keep=1.0):
     """match_pairs for Z puzzles of P pieces: pieces [Z,P,N,3] (float32, on the GPU) -> PairTable whose every field carries a
     leading Z (twist [Z,P,P,6], T [Z,P,P,4,4], de_fpcb [Z,P,P,2,N], de_mrpcb [Z,P,2,N], top_f [Z,P,P,k], top_m [Z,P,k],
     score [Z,P,P] with +inf on the diagonals, x2 [Z,P,256,3]).  The Z P pieces go through ONE encode_pieces, so the encoders run
     on full 64-row batches however small a puzzle is, and ONE pair_block_batch: the number of library launches does not depend on Z.
-    start = (s1[Z,P], s2[Z,P]) as match_pairs takes its starts; refine as match_pairs takes it.  x2 is match_pairs' of the
+    start = (s1[Z,P], s2[Z,P]) as match_pairs takes its starts; refine and keep as match_pairs takes them (kept_f [Z,P,P,m_f],
+    kept_m [Z,P,P,m_m]).  x2 is match_pairs' of the
     same puzzle and starts bit for bit; the fields behind the few-row layers (twist, and with it T and score) are not equal
     bit for bit between two calls of match_pairs either, and agree with it as two such calls do.  Nothing waits for the device."""
-    pieces, codes, blk = _match_puzzles(model, pieces, k, start, refine, "match_puzzles")
+    pieces, codes, blk = _match_puzzles(model, pieces, k, start, refine, "match_puzzles", keep)
     return _table(codes, blk, _diagonal(pieces))
 
 
@@ -1166,7 +1244,13 @@ def refine_assembly_batch(pieces, table, asm, sweeps=30):
     sets of k points, 12 k Z P (P + 1) bytes (7.1 MB at Z = 64, P = 8, k = 128) - and the rows find theirs through
     a_of = z P^2 + i P + j and b_of = z P + j, computed from asm.joints in torch (unused rows map to set 0 and are skipped by
     the kernel).  G0 = asm.G rounded to float32, movable = asm.movable, then the one launch of ops.joint_refine for all Z
-    puzzles.  Per puzzle the result is refine_assembly's bit for bit.  Nothing waits for the device."""
+    puzzles.  Per puzzle the result is refine_assembly's bit for bit.  Nothing waits for the device.
+
+    A table that carries kept sets (match_puzzles(..., keep < 1)): the set of ordered pair (z, i, j) is its kept rows,
+    pieces[z,i][top_f[z,i,j][kept_f[z,i,j]]] and pieces[z,j][top_m[z,j][kept_m[z,i,j]]] - 2 Z P^2 sets of m_f and m_m points,
+    b_of = a_of per ordered pair; the counts are the table's shapes, known on the host.  The kernel and its energy are the same,
+    the untrimmed one over the rows the pair refinement kept: the joint refinement freezes the kept sets, it does not trim
+    again."""
     _clouds("refine_assembly_batch", "Z,P", pieces=pieces)
     Z, P, N, _ = pieces.shape
     J = P * (P - 1)
@@ -1179,15 +1263,23 @@ def refine_assembly_batch(pieces, table, asm, sweeps=30):
     with torch.no_grad():
         k = table.top_m.shape[2]
         piece_row = torch.arange(Z * P, dtype=torch.long, device=dev).view(Z, P) * N                     # first row of piece (z, p)
-        rows_a = (piece_row[:, :, None, None] + table.top_f).reshape(-1)                                # [Z,P,P,k]
-        rows_b = (piece_row[:, :, None] + table.top_m).reshape(-1)                                      # [Z,P,k]
-        picked = ops.index_points(pieces.contiguous().view(1, Z * P * N, 3), torch.cat((rows_a, rows_b)).reshape(1, -1))[0]
-        a, b = picked[:Z * P * P * k].view(Z * P * P, k, 3), picked[Z * P * P * k:].view(Z * P, k, 3)
         ji, jj = asm.joints[..., 0].long(), asm.joints[..., 1].long()
         used = ji >= 0
         first = torch.arange(Z, dtype=torch.long, device=dev)[:, None]
         a_of = torch.where(used, (first * P + ji) * P + jj, torch.zeros_like(ji))
-        b_of = torch.where(used, first * P + jj, torch.zeros_like(jj))
+        if table.kept_f is None:
+            rows_a = (piece_row[:, :, None, None] + table.top_f).reshape(-1)                            # [Z,P,P,k]
+            rows_b = (piece_row[:, :, None] + table.top_m).reshape(-1)                                  # [Z,P,k]
+            ka, nb = k, Z * P
+            b_of = torch.where(used, first * P + jj, torch.zeros_like(jj))
+        else:      # the kept rows of every ordered pair, on both sides
+            rows_a = (piece_row[:, :, None, None] + table.top_f.gather(3, table.kept_f.long())).reshape(-1)       # [Z,P,P,m_f]
+            top_m = table.top_m[:, None].expand(Z, P, P, k)
+            rows_b = (piece_row[:, None, :, None] + top_m.gather(3, table.kept_m.long())).reshape(-1)             # [Z,P,P,m_m]
+            ka, nb = table.kept_f.shape[-1], Z * P * P
+            b_of = a_of
+        picked = ops.index_points(pieces.contiguous().view(1, Z * P * N, 3), torch.cat((rows_a, rows_b)).reshape(1, -1))[0]
+        a, b = picked[:Z * P * P * ka].view(Z * P * P, ka, 3), picked[Z * P * P * ka:].view(nb, -1, 3)
         G, score, score0, _, used_sweeps, accepted = ops.joint_refine(a, b, asm.joints, asm.G.to(torch.float32), asm.movable, sweeps,
                                                                       a_of=a_of, b_of=b_of)
     return JointRefined(G, score, score0, used_sweeps, accepted, asm.joints)

@@ -24,13 +24,24 @@
 //     (m2 / tr^2 is about l2 / l1 for a thin set; points exactly on a line, rounded to fp32, sit near 1e-14).
 // Latency-bound: per iteration a serial chain of six barriers, a (ka | kb)-step scan and one lane's float64 solve; the
 // launch is parallel over problems only, and the grid walks when P exceeds ICP_MAX_GRID.
+//
+// TRIMMED form (icp_trim_kernel, pzn_icp_refine_trim_f32): the same body with TRIM = true, for pieces of which only a part
+// mates.  Of each direction's rows only the m_a (m_b) with the smallest (row minimum, row index) count, in E - the kept
+// minima summed in today's order, divided by m_a and m_b - and as pairs of the step (divisor m_a + m_b).  What it adds per
+// evaluation: every row's minimum goes to LDS, one more barrier, and every row RANKS itself by counting the rows of its
+// direction that precede it in (value, index) order - all lanes read the same address, a broadcast, O(k) per row like the
+// scan - kept iff rank < m: exactly m rows whatever the ties, the same on every run.  The kept rows live in a byte mask; there
+// are TWO masks, the current pose's and the one the candidate's evaluation writes, swapped when the candidate is taken, so
+// the kept set of the returned pose survives a rejected candidate and kept_a / kept_b are written once, at the end.
+// icp_refine_kernel is the TRIM = false instantiation: no minima in LDS, no ranking, no mask, the instructions it had before.
 #include "pzn_rigid.h"      // the wave sums, horn_rotation, Pose / pose_move: shared with jointrefine.hip
 
 namespace {
 
 constexpr int ICP_T = 256;                 // four wavefronts
 constexpr int ICP_W = ICP_T / PZN_WAVE;
-constexpr int ICP_MAX_K = 1024;            // 36 KB of point images + 4 KB of arg-mins + 0.5 KB of reduction slots: 40.5 KB of LDS at most
+constexpr int ICP_MAX_K = 1024;            // 36 KB of point images + 4 KB of arg-mins + 0.5 KB of reduction slots: 40.5 KB of LDS at most;
+                                           // trimmed: + 8 KB of row minima + 2 x 2 KB of kept masks = 52.5 KB at most
 constexpr int ICP_MAX_GRID = 512;          // two workgroups per CU of a 256-CU part; more problems share a workgroup in turn
 
 struct Lds {
@@ -38,6 +49,8 @@ struct Lds {
   float *bx, *by, *bz;      // moved set as given, [kb]
   float *tx, *ty, *tz;      // moved set under the pose being evaluated, [kb]
   unsigned short* corr;     // [ka + kb] arg-min of every row under the pose evaluated last (a row's owner alone touches it)
+  float* rmin;              // trimmed only: [ka + kb] the minimum of every row under the pose evaluated last
+  unsigned char* keep;      // trimmed only: [2][ka + kb] kept masks (1 = kept); which is the current pose's is the caller's flip
   double* redd;             // [ICP_W][15] wave partials of the float64 sums
   float* rede;              // [ICP_W][2] wave partials of the two objective sums
   float* cand;              // [12] the candidate pose, thread 0 -> everyone
@@ -45,7 +58,10 @@ struct Lds {
 
 // E(pose): moves b into (tx, ty, tz), scans, leaves every row's arg-min in L.corr -> the objective, the same bits in every
 // thread.  Three barriers; on entry no thread may still be reading tx / rede (every caller comes from a barrier).
-__device__ float evaluate(const Lds& L, const Pose& g, int ka, int kb, int tid) {
+// TRIM: every row's minimum goes to L.rmin, a fourth barrier, then every row counts the rows of its direction before it in
+// (minimum, index) order - kept iff fewer than ma (mb) - marks itself in `keep` [ka + kb] and only kept minima are summed.
+template <bool TRIM>
+__device__ float evaluate(const Lds& L, const Pose& g, int ka, int kb, int ma, int mb, unsigned char* keep, int tid) {
   for (int j = tid; j < kb; j += ICP_T) {
     const float x = L.bx[j], y = L.by[j], z = L.bz[j];
     pose_move(g, x, y, z, L.tx[j], L.ty[j], L.tz[j]);
@@ -73,10 +89,37 @@ __device__ float evaluate(const Lds& L, const Pose& g, int ka, int kb, int tid) 
       arg = take ? c : arg;
     }
     L.corr[r] = (unsigned short)arg;
-    if (fixed_row)
-      s1 = __fadd_rn(s1, best);
-    else
-      s2 = __fadd_rn(s2, best);
+    if constexpr (TRIM) {
+      L.rmin[r] = best;
+    } else {
+      if (fixed_row)
+        s1 = __fadd_rn(s1, best);
+      else
+        s2 = __fadd_rn(s2, best);
+    }
+  }
+  if constexpr (TRIM) {
+    __syncthreads();      // every row's minimum is in rmin
+    for (int r = tid; r < rows; r += ICP_T) {
+      const bool fixed_row = r < ka;
+      const int own = fixed_row ? r : r - ka;
+      const float* v = fixed_row ? L.rmin : L.rmin + ka;
+      const int n = fixed_row ? ka : kb;
+      const float mine = v[own];      // (never NaN: a NaN distance never passes d < best)
+      int before = 0;
+      for (int c = 0; c < n; ++c) {      // one address for the whole wave: a broadcast read
+        const float o = v[c];
+        before += (o < mine || (o == mine && c < own)) ? 1 : 0;
+      }
+      const bool kept = before < (fixed_row ? ma : mb);
+      keep[r] = kept ? 1 : 0;
+      if (kept) {
+        if (fixed_row)
+          s1 = __fadd_rn(s1, mine);
+        else
+          s2 = __fadd_rn(s2, mine);
+      }
+    }
   }
   s1 = wave_sum_f32_dpp(s1);
   s2 = wave_sum_f32_dpp(s2);
@@ -85,18 +128,21 @@ __device__ float evaluate(const Lds& L, const Pose& g, int ka, int kb, int tid) 
   float e1 = L.rede[0], e2 = L.rede[1];
 #pragma unroll
   for (int w = 1; w < ICP_W; ++w) e1 = __fadd_rn(e1, L.rede[2 * w]), e2 = __fadd_rn(e2, L.rede[2 * w + 1]);
-  const float e = __fadd_rn(__fdiv_rn(e1, (float)ka), __fdiv_rn(e2, (float)kb));
+  const float e = __fadd_rn(__fdiv_rn(e1, (float)(TRIM ? ma : ka)), __fdiv_rn(e2, (float)(TRIM ? mb : kb)));
   __syncthreads();      // rede and tx are free again
   return e;
 }
 
 // The candidate from the correspondences in L.corr and the current pose (kept when the pairs are degenerate).  Three barriers.
-__device__ Pose candidate(const Lds& L, const Pose& cur, int ka, int kb, int tid) {
+// TRIM: the pairs of the rows marked in `keep` alone, npairs = ma + mb of them (otherwise all ka + kb rows; npairs is not read).
+template <bool TRIM>
+__device__ Pose candidate(const Lds& L, const Pose& cur, int ka, int kb, int npairs, const unsigned char* keep, int tid) {
   const int rows = ka + kb;
   const int lane = tid & (PZN_WAVE - 1), wave = tid / PZN_WAVE;
   // pass 1: centroids of the fixed-side points p and the moved-side points q of the ka + kb pairs
   double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (int r = tid; r < rows; r += ICP_T) {
+    if (TRIM && !keep[r]) continue;
     const int c = L.corr[r];
     const int ia = r < ka ? r : c, ib = r < ka ? c : r - ka;
     s[0] += (double)L.ax[ia], s[1] += (double)L.ay[ia], s[2] += (double)L.az[ia];
@@ -114,7 +160,7 @@ __device__ Pose candidate(const Lds& L, const Pose& cur, int ka, int kb, int tid
     double v = L.redd[k];
 #pragma unroll
     for (int w = 1; w < ICP_W; ++w) v += L.redd[15 * w + k];
-    cen[k] = v / (double)rows;
+    cen[k] = v / (double)(TRIM ? npairs : rows);
   }
   __syncthreads();      // redd is written again below
   // pass 2: S[u][v] = sum qd_u pd_v (9) and the upper triangle of C = sum qd qd^T (6)
@@ -122,6 +168,7 @@ __device__ Pose candidate(const Lds& L, const Pose& cur, int ka, int kb, int tid
 #pragma unroll
   for (int k = 0; k < 15; ++k) m[k] = 0.0;
   for (int r = tid; r < rows; r += ICP_T) {
+    if (TRIM && !keep[r]) continue;
     const int c = L.corr[r];
     const int ia = r < ka ? r : c, ib = r < ka ? c : r - ka;
     const double px = (double)L.ax[ia] - cen[0], py = (double)L.ay[ia] - cen[1], pz = (double)L.az[ia] - cen[2];
@@ -183,12 +230,36 @@ __device__ __forceinline__ void store_corr(const Lds& L, int p, int ka, int kb, 
   }
 }
 
-__global__ __launch_bounds__(ICP_T) void icp_refine_kernel(const float* __restrict__ a, const int64_t* __restrict__ a_of,
-                                                           const float* __restrict__ b, const int64_t* __restrict__ b_of,
-                                                           const float* __restrict__ T0, int P, int ka, int kb, int iters,
-                                                           float* __restrict__ T, float* __restrict__ score,
-                                                           float* __restrict__ score0, int32_t* __restrict__ iters_used,
-                                                           int32_t* __restrict__ corr_a, int32_t* __restrict__ corr_b) {
+// The arguments both kernels take.
+#define ICP_PARAMS                                                                                                          \
+  const float *__restrict__ a, const int64_t *__restrict__ a_of, const float *__restrict__ b,                               \
+      const int64_t *__restrict__ b_of, const float *__restrict__ T0, int P, int ka, int kb, int iters,                     \
+      float *__restrict__ T, float *__restrict__ score, float *__restrict__ score0, int32_t *__restrict__ iters_used,       \
+      int32_t *__restrict__ corr_a, int32_t *__restrict__ corr_b
+
+// What only the trimmed kernel takes, as the kernel's last argument.  The untrimmed form is empty, so icp_refine_kernel keeps
+// the arguments it had, and the names of the two argument types are what tells the two instantiations apart in a trace.
+struct icp_trim_kernel_args {
+  static constexpr bool TRIM = true;
+  int ma, mb;                   // rows kept of a and of b
+  int32_t *kept_a, *kept_b;     // [P,ma], [P,mb] or NULL
+};
+struct icp_refine_kernel_args {
+  static constexpr bool TRIM = false;
+  static constexpr int ma = 0, mb = 0;
+  static constexpr int32_t *kept_a = nullptr, *kept_b = nullptr;
+};
+
+// The one body of both kernels: icp_refine_kernel = icp_kernel<icp_refine_kernel_args>, icp_trim_kernel =
+// icp_kernel<icp_trim_kernel_args>.  The body stands in the kernel itself and the untrimmed form sets up its LDS exactly as
+// it did before there was a second form: its instructions are then the earlier kernel's, one for one (an inlined body
+// function between the two cost the untrimmed launch 3 % through another register allocation).
+template <typename Args>
+__global__ __launch_bounds__(ICP_T) void icp_kernel(ICP_PARAMS, Args trim) {
+  constexpr bool TRIM = Args::TRIM;
+  const int ma = trim.ma, mb = trim.mb;
+  int32_t* const kept_a = trim.kept_a;
+  int32_t* const kept_b = trim.kept_b;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   Lds L;
   L.redd = reinterpret_cast<double*>(smem_raw);                       // [ICP_W][15]
@@ -197,7 +268,10 @@ __global__ __launch_bounds__(ICP_T) void icp_refine_kernel(const float* __restri
   L.ax = L.cand + 12, L.ay = L.ax + ka, L.az = L.ay + ka;
   L.bx = L.az + ka, L.by = L.bx + kb, L.bz = L.by + kb;
   L.tx = L.bz + kb, L.ty = L.tx + kb, L.tz = L.ty + kb;
-  L.corr = reinterpret_cast<unsigned short*>(L.tz + kb);              // [ka + kb]
+  L.rmin = TRIM ? L.tz + kb : nullptr;                                                 // [ka + kb], trimmed only
+  L.corr = reinterpret_cast<unsigned short*>(L.tz + kb + (TRIM ? ka + kb : 0));         // [ka + kb]
+  L.keep = TRIM ? reinterpret_cast<unsigned char*>(L.corr + ka + kb) : nullptr;         // [2][ka + kb], trimmed only
+  const int npairs = TRIM ? ma + mb : 0;      // (the untrimmed candidate divides by its own ka + kb)
   const int tid = (int)threadIdx.x;
 
   for (int p = (int)blockIdx.x; p < P; p += (int)gridDim.x) {      // (workgroup-uniform)
@@ -222,18 +296,34 @@ __global__ __launch_bounds__(ICP_T) void icp_refine_kernel(const float* __restri
     }
     __syncthreads();
 
-    float e = evaluate(L, cur, ka, kb, tid);
+    int flip = 0;      // which kept mask is the current pose's (workgroup-uniform; trimmed only)
+    float e = evaluate<TRIM>(L, cur, ka, kb, ma, mb, L.keep, tid);
     const float e0 = e;
     int used = 0;
     for (int it = 0; it < iters; ++it) {      // (e, and with it the exit, is the same in every thread)
       // the correspondences this candidate is built from (L.corr is overwritten by its evaluation)
       store_corr(L, p, ka, kb, tid, corr_a, corr_b);
-      const Pose nxt = candidate(L, cur, ka, kb, tid);
-      const float en = evaluate(L, nxt, ka, kb, tid);
+      const Pose nxt = candidate<TRIM>(L, cur, ka, kb, npairs, L.keep + flip * (ka + kb), tid);
+      const float en = evaluate<TRIM>(L, nxt, ka, kb, ma, mb, L.keep + (flip ^ 1) * (ka + kb), tid);      // (the other mask)
       if (!(en < e)) break;
-      cur = nxt, e = en, ++used;
+      cur = nxt, e = en, ++used, flip ^= 1;
     }
     if (iters == 0) store_corr(L, p, ka, kb, tid, corr_a, corr_b);      // the correspondences under T0
+    if constexpr (TRIM) {
+      // the rows kept under the returned pose, ascending: a kept row's place is the number of kept rows before it (the mask
+      // was complete at the last barrier of the evaluation that wrote it)
+      const unsigned char* kp = L.keep + flip * (ka + kb);
+      for (int r = tid; r < ka + kb; r += ICP_T) {
+        const bool fixed_row = r < ka;
+        int32_t* out = fixed_row ? kept_a : kept_b;
+        if (!kp[r] || !out) continue;
+        const int own = fixed_row ? r : r - ka, m = fixed_row ? ma : mb;
+        const unsigned char* side = fixed_row ? kp : kp + ka;
+        int pos = 0;
+        for (int c = 0; c < own; ++c) pos += side[c];
+        if (pos < m) out[(size_t)p * m + pos] = own;      // (always: exactly m rows of a direction are kept)
+      }
+    }
     if (tid < 16) {
       const int u = tid >> 2, v = tid & 3;
       float val = 0.f;
@@ -249,6 +339,13 @@ __global__ __launch_bounds__(ICP_T) void icp_refine_kernel(const float* __restri
   }
 }
 
+// Bytes of LDS of a launch: reduction slots, the three point images, the arg-mins; trimmed: the row minima and two masks.
+size_t icp_lds_bytes(int ka, int kb, bool trim) {
+  const size_t rows = (size_t)ka + (size_t)kb;
+  return ICP_W * 15 * sizeof(double) + (ICP_W * 2 + 12) * sizeof(float) + 3 * ((size_t)ka + 2 * (size_t)kb) * sizeof(float) +
+         rows * sizeof(unsigned short) + (trim ? rows * sizeof(float) + 2 * rows : 0);
+}
+
 }  // namespace
 
 PZN_EXPORT int pzn_icp_refine_supported(int ka, int kb) { return ka >= 1 && kb >= 1 && ka <= ICP_MAX_K && kb <= ICP_MAX_K; }
@@ -261,10 +358,27 @@ PZN_EXPORT int pzn_icp_refine_f32(const float* a, const int64_t* a_of, const flo
   if (P == 0) return PZN_OK;
   PZN_CHECK_ARG(a && b && T0 && T && score && score0 && iters_used);
   hipStream_t st = pzn_hip_stream(stream);
-  const size_t lds = ICP_W * 15 * sizeof(double) + (ICP_W * 2 + 12) * sizeof(float) +
-                     3 * ((size_t)ka + 2 * (size_t)kb) * sizeof(float) + ((size_t)ka + kb) * sizeof(unsigned short);
   const int grid = P < ICP_MAX_GRID ? P : ICP_MAX_GRID;
-  PZN_LAUNCH(icp_refine_kernel, dim3(grid), dim3(ICP_T), lds, st, a, a_of, b, b_of, T0, P, ka, kb, iters, T, score, score0,
-             iters_used, corr_a, corr_b);
+  PZN_LAUNCH(icp_kernel<icp_refine_kernel_args>, dim3(grid), dim3(ICP_T), icp_lds_bytes(ka, kb, false), st, a, a_of, b, b_of, T0, P, ka, kb, iters,
+             T, score, score0, iters_used, corr_a, corr_b, icp_refine_kernel_args{});
+  PZN_RETURN_LAUNCH_STATUS();
+}
+
+PZN_EXPORT int pzn_icp_refine_trim_supported(int ka, int kb, int keep_a, int keep_b) {
+  return pzn_icp_refine_supported(ka, kb) && keep_a >= 1 && keep_a <= ka && keep_b >= 1 && keep_b <= kb;
+}
+
+PZN_EXPORT int pzn_icp_refine_trim_f32(const float* a, const int64_t* a_of, const float* b, const int64_t* b_of, const float* T0,
+                                       int P, int ka, int kb, int keep_a, int keep_b, int iters, float* T, float* score,
+                                       float* score0, int32_t* iters_used, int32_t* corr_a, int32_t* corr_b, int32_t* kept_a,
+                                       int32_t* kept_b, pzn_stream_t stream) {
+  if (!pzn_icp_refine_trim_supported(ka, kb, keep_a, keep_b) || iters < 0) return PZN_EUNSUPPORTED;
+  PZN_CHECK_ARG(P >= 0);
+  if (P == 0) return PZN_OK;
+  PZN_CHECK_ARG(a && b && T0 && T && score && score0 && iters_used);
+  hipStream_t st = pzn_hip_stream(stream);
+  const int grid = P < ICP_MAX_GRID ? P : ICP_MAX_GRID;
+  PZN_LAUNCH(icp_kernel<icp_trim_kernel_args>, dim3(grid), dim3(ICP_T), icp_lds_bytes(ka, kb, true), st, a, a_of, b, b_of, T0, P, ka, kb, iters, T,
+             score, score0, iters_used, corr_a, corr_b, icp_trim_kernel_args{keep_a, keep_b, kept_a, kept_b});
   PZN_RETURN_LAUNCH_STATUS();
 }

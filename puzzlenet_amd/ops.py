@@ -232,14 +232,23 @@ def icp_refine_supported(ka, kb):
     return bool(_lib.load().pzn_icp_refine_supported(int(ka), int(kb)))
 
 
-def icp_refine(a, b, T0, iters, a_of=None, b_of=None, return_corr=False):
+def icp_refine_trim_supported(ka, kb, keep_a, keep_b):
+    return bool(_lib.load().pzn_icp_refine_trim_supported(int(ka), int(kb), int(keep_a), int(keep_b)))
+
+
+def icp_refine(a, b, T0, iters, a_of=None, b_of=None, return_corr=False, keep=None, return_kept=False):
     """P pose refinements in one launch (pzn_icp_refine_f32): symmetric point-to-point ICP of the moved set b[.,kb,3] onto the
     fixed set a[.,ka,3] from T0[P,4,4], at most `iters` accepted steps per problem -> (T [P,4,4], score [P], score0 [P],
     iters_used [P] int32), and with return_corr the correspondences the last candidate was built from, corr_a [P,ka] and
     corr_b [P,kb] (int32).  score = E(T) <= score0 = E(T0), E as include/pzn.h states it; iters = 0 returns T0.
     Problem p reads a[a_of[p]] and b[b_of[p]] (int64 [P]; the caller keeps them inside a / b - they are not checked, that
     would wait for the device); without a map, a / b hold P sets.  1 <= ka, kb <= 1024 and iters >= 0 (PznUnsupported
-    beyond).  No autograd, nothing waits for the device."""
+    beyond).  No autograd, nothing waits for the device.
+    keep = (m_a, m_b), ints: the trimmed refinement for partial contact (pzn_icp_refine_trim_f32, one launch of its own
+    kernel): of each direction's rows only the m with the smallest (minimum, index) count in E and as pairs of the step;
+    1 <= m_a <= ka, 1 <= m_b <= kb (PznUnsupported beyond, before any launch).  return_kept appends kept_a [P,m_a] and kept_b
+    [P,m_b] (int32, ascending): the rows kept under the returned T.  keep = None is the untrimmed launch, untouched; with it
+    return_kept gives 0 .. k-1."""
     for name, t, dt in (("a", a, torch.float32), ("b", b, torch.float32), ("T0", T0, torch.float32), ("a_of", a_of, torch.int64),
                         ("b_of", b_of, torch.int64)):
         if isinstance(t, torch.Tensor) and t.dtype != dt:      # (no silent conversion: a pose refined in another precision)
@@ -265,6 +274,11 @@ def icp_refine(a, b, T0, iters, a_of=None, b_of=None, return_corr=False):
     iters = int(iters)
     if iters < 0 or not icp_refine_supported(ka, kb):
         raise _lib.PznUnsupported(f"icp_refine: ka = {ka}, kb = {kb}, iters = {iters} (1 <= ka, kb <= 1024, iters >= 0)")
+    if keep is not None:
+        if not isinstance(keep, (tuple, list)) or len(keep) != 2 or not all(isinstance(m, int) and not isinstance(m, bool) for m in keep):
+            raise _lib.PznError(f"icp_refine: keep = (m_a, m_b) as ints; got {keep!r}")
+        if not icp_refine_trim_supported(ka, kb, keep[0], keep[1]):
+            raise _lib.PznUnsupported(f"icp_refine: keep = {tuple(keep)} of ka = {ka}, kb = {kb} rows (1 <= m_a <= ka, 1 <= m_b <= kb)")
     dev = a.device
     T = torch.empty((P, 4, 4), dtype=torch.float32, device=dev)
     score = torch.empty((P,), dtype=torch.float32, device=dev)
@@ -272,11 +286,21 @@ def icp_refine(a, b, T0, iters, a_of=None, b_of=None, return_corr=False):
     used = torch.empty((P,), dtype=torch.int32, device=dev)
     ca = torch.empty((P, ka), dtype=torch.int32, device=dev) if return_corr else None
     cb = torch.empty((P, kb), dtype=torch.int32, device=dev) if return_corr else None
+    kept = ()
+    if return_kept and keep is None:
+        kept = tuple(torch.arange(k, dtype=torch.int32, device=dev).expand(P, k).contiguous() for k in (ka, kb))
+    elif return_kept:
+        kept = tuple(torch.empty((P, m), dtype=torch.int32, device=dev) for m in keep)
     if P > 0:
         with _on(dev):
-            _call("pzn_icp_refine_f32", _p(a), _p(maps[0]), _p(b), _p(maps[1]), _p(T0), P, ka, kb, iters, _p(T), _p(score),
-                  _p(score0), _p(used), _p(ca), _p(cb), _stream())
-    return (T, score, score0, used, ca, cb) if return_corr else (T, score, score0, used)
+            if keep is None:
+                _call("pzn_icp_refine_f32", _p(a), _p(maps[0]), _p(b), _p(maps[1]), _p(T0), P, ka, kb, iters, _p(T), _p(score),
+                      _p(score0), _p(used), _p(ca), _p(cb), _stream())
+            else:
+                _call("pzn_icp_refine_trim_f32", _p(a), _p(maps[0]), _p(b), _p(maps[1]), _p(T0), P, ka, kb, keep[0], keep[1], iters,
+                      _p(T), _p(score), _p(score0), _p(used), _p(ca), _p(cb), _p(kept[0]) if kept else None,
+                      _p(kept[1]) if kept else None, _stream())
+    return ((T, score, score0, used, ca, cb) if return_corr else (T, score, score0, used)) + kept
 
 
 def joint_refine_supported(K, J, ka, kb):

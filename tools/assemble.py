@@ -2,7 +2,7 @@
 assembled cloud.
 
     python tools/assemble.py --pieces pieces.npy [--ckpt model.ckpt] [--k 128] [--max-score S] [--out PREFIX] [--progressive]
-                             [--refine N] [--joint N] [--gt PREFIX_gt.npz] [--beam B] [--branch C] [--vote-weight W] [--forest]
+                             [--refine N] [--keep F] [--joint N] [--gt PREFIX_gt.npz] [--beam B] [--branch C] [--vote-weight W] [--forest]
 
 pieces.npy holds [K, N, 3] float32 (N = the model's points per piece).  Prints the score table and the edges in
 placement order, writes PREFIX_G.npy ([K,4,4], each piece into the root's frame) and PREFIX_cloud.npy ([K,N,3]).
@@ -51,7 +51,7 @@ def forest(args, x, table):
     """--forest: the forest walk over the table of a pile - with --beam the forest beam -, its components, and with --joint their
     refinement in one launch."""
     from puzzlenet_amd import assembly
-    one = assembly.PairTable(*(f[None] for f in table))
+    one = type(table)(*(f[None] for f in table))
     if args.beam:
         moment = assembly.boundary_moments(x[None], one.top_m)
         fb = assembly.assemble_forest_beam_batch(one.score, one.T, moment, beam=args.beam, branch=args.branch, weight=args.vote_weight,
@@ -87,6 +87,8 @@ def main():
     ap.add_argument("--progressive", action="store_true", help="merge placed parts, resample and match again after every placement")
     ap.add_argument("--keep-matched", action="store_true", help="--progressive: keep the matched boundary points in the merged part")
     ap.add_argument("--refine", type=int, default=0, help="ICP steps at most per pair pose on the picked boundary points (0: none)")
+    ap.add_argument("--keep", type=float, default=1.0, help="partial contact: the share of the picked boundary points of each side "
+                    "that counts in a pair's score and refinement, those closest to the other side (1.0: all; not with --progressive)")
     ap.add_argument("--joint", type=int, default=0, help="sweeps at most of the joint refinement after the greedy walk (0: none)")
     ap.add_argument("--gt", default=None, help="PREFIX_gt.npz of tools/fracture.py: score the assembly against the truth")
     ap.add_argument("--beam", type=int, default=0, help="B: the beam walk with B hypotheses in place of the greedy walk (1 .. 8; 0: greedy)")
@@ -100,6 +102,8 @@ def main():
         sys.exit("--beam B, --branch C: 1 .. 8, --vote-weight: a number, and not with --progressive")
     if args.refine < 0:
         sys.exit("--refine: 0 or a number of steps")
+    if not 0.0 < args.keep <= 1.0 or (args.keep < 1.0 and args.progressive):
+        sys.exit("--keep: a share in (0, 1], and 1.0 with --progressive (the progressive walk does not trim)")
     if args.joint < 0 or (args.joint and args.progressive):
         sys.exit("--joint: 0 or a number of sweeps, and for the greedy walk only (not with --progressive)")
 
@@ -145,7 +149,7 @@ def main():
             print(f"against {args.gt} (the part around the first pair, in piece {root}'s frame):")
             report(assembly.evaluate(res.G, res.placed, gt["pose"], gt["rest"], root))
         return
-    table = assembly.match_pairs(model, x, k=args.k, refine=args.refine)
+    table = assembly.match_pairs(model, x, k=args.k, refine=args.refine, keep=args.keep)
     if args.forest:
         return forest(args, x, table)
     if args.beam:

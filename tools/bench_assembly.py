@@ -25,7 +25,9 @@ many iterations as the LONGEST pair of the fused launch ran (iters_used max + 1:
 long as its longest problem); device time between two events around each call, alternated in one process; per-iteration
 figures and the library's launches beside them; (a') assembly.refine_assembly on the greedy walk over the same table and
 over its first 8 pieces' - the time of its one kernel, 30 sweeps at most, with the default joint set and with every ordered
-pair as a joint (there is nothing earlier to compare it with); and (b) match_pairs with refine = 30 against refine = 0 (host wall time around
+pair as a joint (there is nothing earlier to compare it with); (a'') the trimmed launch of refine_pairs at keep = 0.5 on the
+same boundaries and poses beside the untrimmed one - the time of each one's kernel per launch (the library's own event pair),
+each in a run of its own launches in one process; and (b) match_pairs with refine = 30 against refine = 0 (host wall time around
 a synchronised call, alternated).
 
 --batch Z measures instead the whole chain on Z fractured puzzles of P = 8 pieces (datapipe.fracture on seeded clouds of 20000
@@ -239,6 +241,21 @@ def refine(args):
     torch.cuda.synchronize()
     k_f = ops.ktimer_stop()
     icp = [v for name, v in k_f.items() if "icp_refine_kernel" in name]
+    # the trimmed launch at keep = 0.5 of both sides beside the untrimmed one: kernel time per launch
+
+    def trimmed():
+        return assembly.refine_pairs(pieces, table.top_f, pieces, table.top_m, table.T, ITERS, keep=0.5)
+
+    # (each kernel in a run of its own launches, the sequence the untrimmed kernel had before there was a second one)
+    u_ms = [_kernel_us(fused, "icp_refine_kernel", 1, 0) / 1e3 for _ in range(args.reps)]
+    for _ in range(args.warmup):
+        trimmed()
+    t_ms = [_kernel_us(trimmed, "icp_trim_kernel", 1, 0) / 1e3 for _ in range(args.reps)]
+    rt = trimmed()
+    trim = {"keep": 0.5, "icp_refine_kernel_ms": _spread(u_ms), "icp_trim_kernel_ms": _spread(t_ms),
+            "trim_over_untrimmed_median": statistics.median(t_ms) / statistics.median(u_ms),
+            "iters_used_mean": float(rt.iters_used.float().mean()), "iters_used_max": int(rt.iters_used.max())}
+    print(json.dumps({"trimmed_launch": trim}))
     # the joint refinement of the greedy assembly (assembly.refine_assembly: one launch of joint_refine_kernel, 30 sweeps at
     # most) at K = 8 (the first 8 pieces' sub-table) and K = 16: the default joint set and every ordered pair
     joint = {}
@@ -272,6 +289,7 @@ def refine(args):
                                    "composition": c_med / ITERS},
               "refine_pairs_library_launches": {k_: v[0] for k_, v in k_f.items()},
               "icp_refine_kernel_ms": icp[0][1] if icp else None,
+              "trimmed_launch": trim,
               "joint_refine_kernel_ms": joint,
               "iters_used_mean": float(r.iters_used.float().mean()), "iters_used_max": int(r.iters_used.max()),
               "score_over_score0_mean_off_diagonal": float((r.score[off] / r.score0[off]).mean()),

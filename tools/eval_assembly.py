@@ -1,7 +1,7 @@
 """The assembly score of a model as a mean over a batch of fractured puzzles, with one download at the end:
 
     python tools/eval_assembly.py [--batch 64] [--pieces 8] [--m 20000] [--k 128] [--candidates 16] [--mag 0.8] [--seed 0]
-                                  [--curvature 2.0] [--ckpt model.ckpt] [--refine N] [--joint N] [--max-score S]
+                                  [--curvature 2.0] [--ckpt model.ckpt] [--refine N] [--keep F] [--joint N] [--max-score S]
                                   [--progressive] [--time R] [--json out.json] [--beam B] [--branch C] [--vote-weight W]
                                   [--objects Q]
 
@@ -65,7 +65,7 @@ def sort_piles(args, model, f, dev):
     g = torch.Generator().manual_seed(args.seed)
     perm = torch.stack([torch.randperm(K, generator=g) for _ in range(Z)]).to(dev)
     pile = datapipe.pile(f, objects=Q, perm=perm)
-    table = assembly.match_puzzles(model, pile.pieces, k=args.k, refine=args.refine)
+    table = assembly.match_puzzles(model, pile.pieces, k=args.k, refine=args.refine, keep=args.keep)
     forest = assembly.assemble_forest_batch(table.score, table.T, max_score=args.max_score)
     walks = [("forest walk", forest)]
     if args.beam:
@@ -121,6 +121,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ckpt", default=None, help="reference checkpoint (puzzlenet_amd.checkpoint); closed-form weights if absent")
     ap.add_argument("--refine", type=int, default=0, help="ICP steps at most per pair pose on the picked boundary points (0: none)")
+    ap.add_argument("--keep", type=float, default=1.0, help="partial contact: the share of the picked boundary points of each side "
+                    "that counts in a pair's score and refinement, those closest to the other side (1.0: all; the progressive "
+                    "walks do not trim)")
     ap.add_argument("--joint", type=int, default=0, help="sweeps at most of the joint refinement after the walk (0: none)")
     ap.add_argument("--max-score", type=float, default=None, help="stop placing pieces above this boundary distance")
     ap.add_argument("--progressive", action="store_true", help="also the progressive walk of the whole batch, in lockstep")
@@ -138,6 +141,8 @@ def main():
         sys.exit("--objects goes with the forest walk alone: no --progressive")
     if args.refine < 0 or args.joint < 0:
         sys.exit("--refine, --joint: 0 or a number of steps / sweeps")
+    if not 0.0 < args.keep <= 1.0:
+        sys.exit("--keep: a share in (0, 1]")
     if args.time < 0 or (args.time and not args.progressive) or (args.json and not args.time):
         sys.exit("--time R >= 0 goes with --progressive, --json with --time")
     if args.beam and not (1 <= args.beam <= 8 and 1 <= args.branch <= 8 and args.vote_weight == args.vote_weight):
@@ -170,7 +175,7 @@ def main():
             return sort_piles(args, model, f, dev)
         # the FPS starts of the table, drawn as match_puzzles draws them, so that the progressive walk can start from the same ones
         s1, s2 = (s.view(B, P) for s in model5_b.draw_fps_starts(1, B * P, N, model.fps_generator))
-        table = assembly.match_puzzles(model, f.pieces, k=args.k, start=(s1, s2), refine=args.refine)
+        table = assembly.match_puzzles(model, f.pieces, k=args.k, start=(s1, s2), refine=args.refine, keep=args.keep)
         asm = assembly.assemble_batch(table.score, table.T, max_score=args.max_score)
         rows = [metrics(assembly.evaluate_batch(asm.G, asm.placed, f.pose, f.rest, asm.root, asm.edges, asm.n_edges, f.mates), asm, f.ok)]
         extra = torch.zeros(3, dtype=torch.float64, device=dev)
