@@ -140,6 +140,40 @@ int pzn_icp_refine_trim_f32(const float* a, const int64_t* a_of, const float* b,
                             float* T, float* score, float* score0, int32_t* iters_used,
                             int32_t* corr_a, int32_t* corr_b, int32_t* kept_a, int32_t* kept_b,
                             pzn_stream_t stream);
+/* pzn_icp_refine_trim_f32 with the two counts found per problem and per EVALUATION of a pose instead of given per launch
+ * (Trimmed ICP's search for the overlap, its objective e(xi) / xi^(1 + lambda) with 1 + lambda = power): a sibling pair mates
+ * along a whole face, two pieces across an older cut along a corner, and one launch serves both.  In place of keep_a, keep_b
+ * the launch takes the least counts 1 <= lo_a <= ka, 1 <= lo_b <= kb and an integer power p in [1, 4].  The rule:
+ *  1. row minima, arg-mins and the (value, row index) order of each direction: the trimmed kernel's, ranked by counting;
+ *  2. one direction with n rows: its minima in that order, w_1 <= ... <= w_n, their float32 prefix sums S_m, and
+ *     phi(m) = (double)S_m / m^(p+1), the power by repeated multiplication in float64 (exact: m <= 1024, p + 1 <= 5), the
+ *     division in float64.  Order of the prefix sums (the same on every run): thread t of 256 adds w_(4t+1) .. w_(4t+4) one
+ *     after the other from 0 (values past n count as 0); each wavefront scans its 64 thread totals inclusively, lane l adding
+ *     lane l - d's running value for d = 1, 2, 4, 8, 16, 32 in turn; the totals of the wavefronts before a thread's are added
+ *     in wavefront order from 0; S_(4t+i) = ((that offset + the scan's value of the lane before, 0 for lane 0) + the thread's
+ *     own running sum up to i), every addition rounded to float32;
+ *  3. count: m* = the m in [lo, n] with the smallest phi, among equal phi the LARGEST m (all minima zero keeps every row);
+ *  4. kept set: rank < m*, as in the trimmed kernel;
+ *  5. e_a, e_b: what the trimmed kernel computes for those counts (kept minima in row-ownership order, butterfly, wave order,
+ *     one correctly rounded division by m*), not taken from the prefix sums;
+ *  6. objective F = e_a r_a + e_b r_b, each product and the sum rounded to float32, r = (float)(q^p) with q = (double)n /
+ *     (double)m* and the power by repeated multiplication in float64 (F = n^p phi(m*) per direction, up to rounding);
+ *  7. score = e_a + e_b, the trimmed kernel's E at these counts: the quantity, in the units, a trimmed table compares;
+ *  8. step: the trimmed step over the m_a + m_b kept pairs of the current pose; the candidate is taken iff F' < F, each with
+ *     its own pose's counts and kept sets; anything else (NaN included) stops.  F falls along a run; score need not;
+ *  9. the counts, like the kept masks, belong to a pose and swap on acceptance: every output is the RETURNED pose's.
+ * Out beside the trimmed launch's T, score, score0 (E under T0 at T0's counts), iters_used, corr_a, corr_b: count_a[P],
+ * count_b[P] (int32), objective[P] (float32, F), and when non-NULL kept_a[P,ka] / kept_b[P,kb] (int32): the count kept rows
+ * ascending, then -1 up to the row's end.  lo_a = ka and lo_b = kb gives r = 1, F = E and pzn_icp_refine_trim_f32 with
+ * keep = (ka, kb) bit for bit, hence pzn_icp_refine_f32.  60.5 KB of LDS at ka = kb = 1024.
+ * Supported (pzn_icp_refine_auto_supported: 1 / 0) for 1 <= ka, kb <= 1024, 1 <= lo_a <= ka, 1 <= lo_b <= kb, 1 <= power <= 4;
+ * otherwise, and for iters < 0, PZN_EUNSUPPORTED before any launch; P = 0 is a success that launches nothing. */
+int pzn_icp_refine_auto_supported(int ka, int kb, int lo_a, int lo_b, int power);
+int pzn_icp_refine_auto_f32(const float* a, const int64_t* a_of, const float* b, const int64_t* b_of,
+                            const float* T0, int P, int ka, int kb, int lo_a, int lo_b, int power, int iters,
+                            float* T, float* score, float* score0, int32_t* iters_used,
+                            int32_t* corr_a, int32_t* corr_b, int32_t* count_a, int32_t* count_b, float* objective,
+                            int32_t* kept_a, int32_t* kept_b, pzn_stream_t stream);
 
 /* Refine all piece poses of Z placed assemblies jointly over every joint (no counterpart in the reference): one launch, one
  * workgroup per puzzle, no workspace, no atomics, no grid-wide synchronisation, nothing waits for the device.  Puzzle z has

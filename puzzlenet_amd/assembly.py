@@ -113,6 +113,26 @@ TrimmedPairTable = collections.namedtuple("TrimmedPairTable", PairTable._fields 
 TrimmedPairBlock = collections.namedtuple("TrimmedPairBlock", PairBlock._fields + ("kept_f", "kept_m"))
 TrimmedRefined = collections.namedtuple("TrimmedRefined", Refined._fields + ("kept_f", "kept_m"))
 
+# keep = "auto" / AutoKeep(...): the share of every pair is found on the device, per pair and per evaluated pose (include/pzn.h,
+# pzn_icp_refine_auto_f32).  The trimmed tuples' fields, then count_f, count_m [...,Kf,Km] (int32: the rows kept of each side
+# under T[i,j]) and objective [...,Kf,Km] (the F the refinement lowered); kept_f [...,Kf,Km,k] and kept_m [...,Kf,Km,k] hold the
+# kept positions ascending and -1 behind the count.  score stays the trimmed score at those counts: what max_score is held to.
+_AUTO_FIELDS = ("count_f", "count_m", "objective")
+AutoPairTable = collections.namedtuple("AutoPairTable", TrimmedPairTable._fields + _AUTO_FIELDS)
+AutoPairBlock = collections.namedtuple("AutoPairBlock", TrimmedPairBlock._fields + _AUTO_FIELDS)
+AutoRefined = collections.namedtuple("AutoRefined", TrimmedRefined._fields + _AUTO_FIELDS)
+
+
+class AutoKeep(collections.namedtuple("AutoKeep", "least power", defaults=(0.25, 3))):
+    """keep=AutoKeep(least, power) on the pair functions (keep="auto" is AutoKeep()): of each side no fewer than ceil(least k)
+    rows are kept (least a fraction in (0, 1], or a pair (fixed side, moved side); the rule of a keep fraction), and the count
+    m minimises (sum of the m smallest row minima) / m^(power + 1): power = 3 is Trimmed ICP's objective with its published
+    lambda = 2, an integer in [1, 4]."""
+    __slots__ = ()
+
+
+_AutoCounts = collections.namedtuple("_AutoCounts", "lo_f lo_m power")      # what _keep_counts makes of an AutoKeep
+
 ENCODER_ROWS = 64      # pieces per encoder call (the fused per-point stem takes up to 64 clouds)
 
 
@@ -226,20 +246,33 @@ def _keep_counts(keep, k_f, k_m, who):
     such (Python or numpy real numbers) - -> None where every row is kept (today's path), otherwise the counts (m_f, m_m) =
     ceil(f k), at least 1, that ops.icp_refine takes as keep: known on the host, nothing waits for the device.  The product is
     formed in double arithmetic and one within 1e-9 above an integer counts as that integer (0.07 x 100 is 7.000000000000001
-    in binary and means 7 rows, not 8)."""
-    fs = tuple(keep) if isinstance(keep, (tuple, list)) else (keep, keep)
+    in binary and means 7 rows, not 8).
+    keep = "auto" or an AutoKeep -> _AutoCounts(lo_f, lo_m, power), the least counts by the same ceil rule (least = 1.0
+    included: the auto launch with every row kept) and the power, an int in [1, 4]: what ops.icp_refine takes as auto."""
+    power, shares = None, keep
+    if isinstance(keep, str):
+        if keep != "auto":
+            raise _lib.PznError(f"{who}: keep = {keep!r} (the one word it takes is 'auto')")
+        keep = AutoKeep()
+    if isinstance(keep, AutoKeep):
+        power, shares = keep.power, keep.least
+        if not isinstance(power, numbers.Integral) or isinstance(power, (bool, np.bool_)) or not 1 <= power <= 4:
+            raise _lib.PznError(f"{who}: keep = {keep!r} (power: an integer in [1, 4])")
+    fs = tuple(shares) if isinstance(shares, (tuple, list)) else (shares, shares)
     if len(fs) != 2 or not all(isinstance(f, numbers.Real) and not isinstance(f, (bool, np.bool_)) and 0.0 < f <= 1.0 for f in fs):
         raise _lib.PznError(f"{who}: keep = {keep!r} (a fraction in (0, 1] of the picked rows, or a pair (fixed, moved) of such)")
-    if fs[0] == 1.0 and fs[1] == 1.0:
+    if power is None and fs[0] == 1.0 and fs[1] == 1.0:
         return None
-    return tuple(min(k, max(1, math.ceil(float(f) * k - 1e-9))) for f, k in zip(fs, (int(k_f), int(k_m))))
+    counts = tuple(min(k, max(1, math.ceil(float(f) * k - 1e-9))) for f, k in zip(fs, (int(k_f), int(k_m))))
+    return counts if power is None else _AutoCounts(*counts, int(power))
 
 
 def _refine_gathered(Bf, Bm, T, iters, keep=None):
     """refine_pairs on boundaries that are gathered already, for any leading puzzle dimensions of T [...,Kf,Km,4,4]: Bf
     [Z Kf Km,k,3] per pair, Bm [Z Km,k,3] per moved piece (served to every fixed piece of its puzzle: problem (z, i, j) reads
     Bm[z Km + j]) -> Refined with T's leading dimensions.  One launch.  keep = (m_f, m_m) counts (_keep_counts): the trimmed
-    launch, iters = 0 included -> TrimmedRefined with kept_f [...,m_f] and kept_m [...,m_m]; None: the untrimmed launch."""
+    launch, iters = 0 included -> TrimmedRefined with kept_f [...,m_f] and kept_m [...,m_m]; None: the untrimmed launch;
+    _AutoCounts: the auto launch -> AutoRefined with kept_f [...,k], kept_m [...,k] padded with -1."""
     Kf, Km = T.shape[-4], T.shape[-3]
     Z = T.numel() // (Kf * Km * 16)
     b_of = torch.arange(Z * Km, dtype=torch.long, device=T.device).view(Z, 1, Km).expand(Z, Kf, Km).reshape(-1)
@@ -247,6 +280,12 @@ def _refine_gathered(Bf, Bm, T, iters, keep=None):
     if keep is None:
         Tr, score, score0, used = ops.icp_refine(Bf, Bm, T.reshape(Z * Kf * Km, 4, 4), iters, b_of=b_of)
         return Refined(Tr.view(*lead, 4, 4), score.view(lead), score0.view(lead), used.view(lead))
+    if isinstance(keep, _AutoCounts):
+        Tr, score, score0, used, count_f, count_m, objective, kept_f, kept_m = ops.icp_refine(
+            Bf, Bm, T.reshape(Z * Kf * Km, 4, 4), iters, b_of=b_of, auto=tuple(keep), return_kept=True)
+        return AutoRefined(Tr.view(*lead, 4, 4), score.view(lead), score0.view(lead), used.view(lead),
+                           kept_f.view(*lead, Bf.shape[1]), kept_m.view(*lead, Bm.shape[1]), count_f.view(lead), count_m.view(lead),
+                           objective.view(lead))
     Tr, score, score0, used, kept_f, kept_m = ops.icp_refine(Bf, Bm, T.reshape(Z * Kf * Km, 4, 4), iters, b_of=b_of, keep=keep,
                                                              return_kept=True)
     return TrimmedRefined(Tr.view(*lead, 4, 4), score.view(lead), score0.view(lead), used.view(lead), kept_f.view(*lead, keep[0]),
@@ -265,7 +304,11 @@ def refine_pairs(pieces_f, top_f, pieces_m, top_m, T, iters=30, keep=1.0):
     step (the trimmed launch; include/pzn.h states the rule), so the picked rows on faces towards other neighbours neither
     score nor pull.  The result is then a TrimmedRefined: Refined's fields, then kept_f [Kf,Km,m_f] and kept_m [Kf,Km,m_m]
     (int32, ascending), positions into top_f[i,j] and top_m[j] of the rows kept under the returned pose.  keep = 1.0 is the
-    untrimmed launch and a Refined, whose kept_f and kept_m are None."""
+    untrimmed launch and a Refined, whose kept_f and kept_m are None.
+    keep = "auto" or an AutoKeep: the counts are found per pair and per evaluated pose on the device (the auto launch) ->
+    AutoRefined: TrimmedRefined's fields with kept_f [Kf,Km,k], kept_m [Kf,Km,k] padded with -1 behind the count, then count_f,
+    count_m [Kf,Km] (int32) and objective [Kf,Km], the F that fell; score is the trimmed score at the returned counts and may
+    exceed score0."""
     _on_gpu("refine_pairs", pieces_f=pieces_f, pieces_m=pieces_m, T=T, top_f=top_f, top_m=top_m)
     if pieces_f.dim() != 3 or pieces_m.dim() != 3 or pieces_f.shape[2] != 3 or pieces_m.shape[2] != 3:
         raise _lib.PznError(f"refine_pairs expects pieces_f[Kf,N,3], pieces_m[Km,N,3]; got {tuple(pieces_f.shape)}, "
@@ -311,6 +354,8 @@ def _table(codes, blk, mask=None):
     score is masked already)."""
     score = blk.score if mask is None else blk.score.masked_fill(mask, float("inf"))
     fields = (blk.twist, blk.T, blk.de_fpcb, codes.de_mrpcb, blk.top_f, codes.top_m, score, codes.x2)
+    if isinstance(blk, AutoPairBlock):
+        return AutoPairTable(*fields, blk.kept_f, blk.kept_m, blk.count_f, blk.count_m, blk.objective)
     return PairTable(*fields) if blk.kept_f is None else TrimmedPairTable(*fields, blk.kept_f, blk.kept_m)
 
 
@@ -342,7 +387,14 @@ def match_pairs(model, pieces, k=128, start=None, refine=0, keep=1.0):
     always through the one trimmed launch - at refine = 0 it runs with no step, so T stays se3.exp(twist) and score is the
     trimmed score under it.  The table is then a TrimmedPairTable: PairTable's fields, then kept_f [K,K,m_f] and kept_m
     [K,K,m_m] (int32: positions into top_f[i,j] and top_m[j] of the rows kept under T[i,j]); at keep = 1.0 it is a PairTable,
-    whose kept_f and kept_m are None.  Every other field but T and score is what keep = 1.0 gives."""
+    whose kept_f and kept_m are None.  Every other field but T and score is what keep = 1.0 gives.
+
+    keep = "auto" or AutoKeep(least=0.25, power=3): a fracture has no one share - siblings mate along a whole face, pieces
+    across an older cut along a corner - so the counts are found per pair and per evaluated pose on the device (AutoKeep and
+    include/pzn.h state the rule), again through one launch, refine = 0 included.  The table is an AutoPairTable: the
+    trimmed table's fields with kept_f, kept_m [K,K,k] padded with -1 behind the count, then count_f, count_m [K,K] (int32) and
+    objective [K,K].  score is the trimmed score at each pair's own counts, so one max_score means the same for every pair;
+    the walks and evaluate_* read score and T as ever.  refine_assembly refuses such a table (PznUnsupported)."""
     refine = _check_refine(refine, "match_pairs")
     _check_pieces(model, pieces, k, "match_pairs", 2)
     if start is not None:
@@ -410,6 +462,17 @@ def assemble(score, T, max_score=None):
     return Assembly(root, edges, G, placed)
 
 
+AUTO_JOINT_MESSAGE = ("a table made with keep='auto' carries a kept count per pair, and joint_refine_kernel takes one (ka, kb) per "
+                      "launch: joint refinement with per-joint counts is not built yet (padding a set by repeating rows would "
+                      "change the joint energy); make the table with a keep fraction to refine it jointly")
+
+
+def _no_auto_joints(table, who):
+    """The joint refinements take tables whose kept sets have one size; an AutoPairTable's differ per joint."""
+    if isinstance(table, AutoPairTable):
+        raise _lib.PznUnsupported(f"{who}: {AUTO_JOINT_MESSAGE}")
+
+
 def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None):
     """Refine all placed poses of a greedy assembly jointly over every joint: pieces [K,N,3] (float32, on the GPU), table =
     match_pairs' PairTable of them, asm = assemble's Assembly of that table -> JointRefined:
@@ -430,7 +493,8 @@ def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None):
     A table that carries kept sets (match_pairs(..., keep < 1)): joint (i, j) pairs pieces[i][top_f[i,j][kept_f[i,j]]] with
     pieces[j][top_m[j][kept_m[i,j]]] - m_f and m_m rows, the moved-side set now one per ordered pair.  The kernel and its
     energy are the same, the untrimmed one over the rows the pair refinement kept: the joint refinement FREEZES the kept
-    sets, it does not trim again under its own poses."""
+    sets, it does not trim again under its own poses.  An AutoPairTable is refused (PznUnsupported, _no_auto_joints says why)."""
+    _no_auto_joints(table, "refine_assembly")
     _clouds("refine_assembly", "K", pieces=pieces)
     K, N, _ = pieces.shape
     G0 = np.asarray(asm.G, dtype=np.float64)
@@ -1162,7 +1226,8 @@ def pair_block_batch(model, pieces_f, codes_f, pieces_m, codes_m, k=128, refine=
     z); the fields behind the few-row layers agree between batches as two calls on the same batch do.  Nothing waits for the
     device.  keep as match_pairs documents it: anything but 1.0 on both sides replaces the transform and the chamfer, or the
     untrimmed launch, by the one trimmed ops.icp_refine launch (iters = refine, 0 included) -> TrimmedPairBlock with kept_f
-    [Z,Kf,Km,m_f], kept_m [Z,Kf,Km,m_m]; 1.0 is today's path untouched and a PairBlock, whose kept_* are None."""
+    [Z,Kf,Km,m_f], kept_m [Z,Kf,Km,m_m]; 1.0 is today's path untouched and a PairBlock, whose kept_* are None; "auto" or an
+    AutoKeep: the one auto launch -> AutoPairBlock (kept_* [Z,Kf,Km,k] padded with -1, count_f, count_m, objective [Z,Kf,Km])."""
     refine = _check_refine(refine, "pair_block_batch")
     _clouds("pair_block_batch", "Z,K", pieces_f=pieces_f, pieces_m=pieces_m)
     Z, Kf, N = pieces_f.shape[0], pieces_f.shape[1], pieces_f.shape[2]
@@ -1190,6 +1255,9 @@ def pair_block_batch(model, pieces_f, codes_f, pieces_m, codes_m, k=128, refine=
         # pieces_f[z,i][top_f[z,i,j]] per pair, pieces_m[z,j][top_m[z,j]] per moved piece
         Bf = ops.index_points(pieces_f.reshape(Z * Kf, N, 3), top_f.reshape(Z * Kf, Km * k)).view(Z * Kf * Km, k, 3)
         Bm = ops.index_points(pieces_m.reshape(Z * Km, N, 3), codes_m.top_m.reshape(Z * Km, -1))
+        if isinstance(counts, _AutoCounts):      # the share found per pair: the auto launch, with no step at refine = 0
+            r = _refine_gathered(Bf, Bm, T.contiguous(), refine, counts)
+            return AutoPairBlock(twist, r.T, de_fpcb, top_f, r.score, r.kept_f, r.kept_m, r.count_f, r.count_m, r.objective)
         if counts is not None:      # partial contact: the trimmed launch, with no step at refine = 0
             r = _refine_gathered(Bf, Bm, T.contiguous(), refine, counts)
             return TrimmedPairBlock(twist, r.T, de_fpcb, top_f, r.score, r.kept_f, r.kept_m)
@@ -1250,7 +1318,8 @@ def refine_assembly_batch(pieces, table, asm, sweeps=30):
     pieces[z,i][top_f[z,i,j][kept_f[z,i,j]]] and pieces[z,j][top_m[z,j][kept_m[z,i,j]]] - 2 Z P^2 sets of m_f and m_m points,
     b_of = a_of per ordered pair; the counts are the table's shapes, known on the host.  The kernel and its energy are the same,
     the untrimmed one over the rows the pair refinement kept: the joint refinement freezes the kept sets, it does not trim
-    again."""
+    again.  An AutoPairTable is refused (PznUnsupported: its counts differ per joint, the kernel takes one pair per launch)."""
+    _no_auto_joints(table, "refine_assembly_batch")
     _clouds("refine_assembly_batch", "Z,P", pieces=pieces)
     Z, P, N, _ = pieces.shape
     J = P * (P - 1)

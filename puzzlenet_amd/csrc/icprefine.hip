@@ -34,6 +34,18 @@
 // are TWO masks, the current pose's and the one the candidate's evaluation writes, swapped when the candidate is taken, so
 // the kept set of the returned pose survives a rejected candidate and kept_a / kept_b are written once, at the end.
 // icp_refine_kernel is the TRIM = false instantiation: no minima in LDS, no ranking, no mask, the instructions it had before.
+//
+// AUTO form (icp_auto_kernel, pzn_icp_refine_auto_f32): the trimmed body with AUTO = true, the counts no longer the caller's
+// but found per problem and per evaluation of a pose (the rule is stated in include/pzn.h).  What an evaluation gains: after
+// the ranking every row writes its minimum to sorted[rank] of its direction (ranks are a permutation, so this IS the sort)
+// and keeps its rank in a register; a barrier; thread t adds the four sorted values 4t .. 4t+3 of each direction one after
+// the other, the wave scans the thread totals (Hillis-Steele, lane l adds lane l - d for d = 1 .. 32), the four wave totals
+// go through LDS and are added in wave order: float32 prefix sums S_m in one fixed order; each thread forms
+// phi(m) = (double)S_m / m^(p+1) for its own four m in [lo, n] (one float64 division a row), and the lexicographic arg-min of
+// (phi, larger m) is a butterfly and four LDS slots per direction.  The two counts are then workgroup-uniform, the kept
+// masks are written from the ranks in registers and the kept minima summed exactly as the trimmed form sums them.  The loop
+// compares F = e_a (ka / m_a)^p + e_b (kb / m_b)^p where the other two compare E; counts, like masks, belong to a pose.
+// The other two instantiations compile to the instructions they had (every addition stands under if constexpr (AUTO)).
 #include "pzn_rigid.h"      // the wave sums, horn_rotation, Pose / pose_move: shared with jointrefine.hip
 
 namespace {
@@ -41,7 +53,9 @@ namespace {
 constexpr int ICP_T = 256;                 // four wavefronts
 constexpr int ICP_W = ICP_T / PZN_WAVE;
 constexpr int ICP_MAX_K = 1024;            // 36 KB of point images + 4 KB of arg-mins + 0.5 KB of reduction slots: 40.5 KB of LDS at most;
-                                           // trimmed: + 8 KB of row minima + 2 x 2 KB of kept masks = 52.5 KB at most
+                                           // trimmed: + 8 KB of row minima + 2 x 2 KB of kept masks = 52.5 KB at most;
+                                           // auto: + 8 KB of sorted minima = 60.5 KB at most, under the 64 KB of a plain launch
+constexpr int ICP_SLOTS = 2 * ICP_MAX_K / ICP_T;      // rows a thread owns at most (auto: their ranks stay in registers)
 constexpr int ICP_MAX_GRID = 512;          // two workgroups per CU of a 256-CU part; more problems share a workgroup in turn
 
 struct Lds {
@@ -51,17 +65,31 @@ struct Lds {
   unsigned short* corr;     // [ka + kb] arg-min of every row under the pose evaluated last (a row's owner alone touches it)
   float* rmin;              // trimmed only: [ka + kb] the minimum of every row under the pose evaluated last
   unsigned char* keep;      // trimmed only: [2][ka + kb] kept masks (1 = kept); which is the current pose's is the caller's flip
+  float* sorted;            // auto only: [ka + kb] every direction's row minima in (value, index) order
   double* redd;             // [ICP_W][15] wave partials of the float64 sums
   float* rede;              // [ICP_W][2] wave partials of the two objective sums
   float* cand;              // [12] the candidate pose, thread 0 -> everyone
 };
 
+// What an evaluation of the auto form takes and leaves beside E.
+struct AutoEval {
+  int power;      // in: p of phi(m) = S_m / m^(p+1)
+  int ma, mb;     // out: the counts of the pose evaluated
+  float F;        // out: e_a (ka / ma)^p + e_b (kb / mb)^p
+};
+
+// (phi, m) before (ophi, om) in the arg-min's order: the smaller phi, among equal phi the larger m
+__device__ __forceinline__ bool phi_before(double phi, int m, double ophi, int om) { return phi < ophi || (phi == ophi && m > om); }
+
 // E(pose): moves b into (tx, ty, tz), scans, leaves every row's arg-min in L.corr -> the objective, the same bits in every
 // thread.  Three barriers; on entry no thread may still be reading tx / rede (every caller comes from a barrier).
 // TRIM: every row's minimum goes to L.rmin, a fourth barrier, then every row counts the rows of its direction before it in
 // (minimum, index) order - kept iff fewer than ma (mb) - marks itself in `keep` [ka + kb] and only kept minima are summed.
-template <bool TRIM>
-__device__ float evaluate(const Lds& L, const Pose& g, int ka, int kb, int ma, int mb, unsigned char* keep, int tid) {
+// AUTO: ma, mb come in as the least counts lo_a, lo_b; the counts of this pose are found (header comment; two barriers for the
+// sort and the prefix sums, one for the arg-min) and leave in `au` with the objective F; the value returned stays E at them.
+template <bool TRIM, bool AUTO = false>
+__device__ float evaluate(const Lds& L, const Pose& g, int ka, int kb, int ma, int mb, unsigned char* keep, int tid,
+                          AutoEval* au = nullptr) {
   for (int j = tid; j < kb; j += ICP_T) {
     const float x = L.bx[j], y = L.by[j], z = L.bz[j];
     pose_move(g, x, y, z, L.tx[j], L.ty[j], L.tz[j]);
@@ -98,7 +126,114 @@ __device__ float evaluate(const Lds& L, const Pose& g, int ka, int kb, int ma, i
         s2 = __fadd_rn(s2, best);
     }
   }
-  if constexpr (TRIM) {
+  if constexpr (AUTO) {
+    __syncthreads();      // every row's minimum is in rmin
+    int rank[ICP_SLOTS];
+#pragma unroll
+    for (int s = 0; s < ICP_SLOTS; ++s) {      // (constant slot indices: the ranks stay in registers)
+      const int r = tid + s * ICP_T;
+      rank[s] = 0;
+      if (r < rows) {
+        const bool fixed_row = r < ka;
+        const int own = fixed_row ? r : r - ka;
+        const float* v = fixed_row ? L.rmin : L.rmin + ka;
+        const int n = fixed_row ? ka : kb;
+        const float mine = v[own];
+        int before = 0;
+        for (int c = 0; c < n; ++c) {
+          const float o = v[c];
+          before += (o < mine || (o == mine && c < own)) ? 1 : 0;
+        }
+        rank[s] = before;
+        (fixed_row ? L.sorted : L.sorted + ka)[before] = mine;      // before < n: the ranks of a direction are a permutation
+      }
+    }
+    __syncthreads();      // both directions' minima stand sorted
+    const int lane = tid & (PZN_WAVE - 1), wave = tid / PZN_WAVE;
+    float c[2][4], exc[2];
+#pragma unroll
+    for (int d = 0; d < 2; ++d) {
+      const float* w = d ? L.sorted + ka : L.sorted;
+      const int n = d ? kb : ka;
+      float run = 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int at = 4 * tid + i;
+        run = __fadd_rn(run, at < n ? w[at] : 0.f);
+        c[d][i] = run;
+      }
+      float inc = run;
+#pragma unroll
+      for (int step = 1; step < PZN_WAVE; step *= 2) {
+        const float o = __shfl_up(inc, step, PZN_WAVE);
+        inc = lane >= step ? __fadd_rn(inc, o) : inc;
+      }
+      const float up = __shfl_up(inc, 1, PZN_WAVE);
+      exc[d] = lane == 0 ? 0.f : up;
+      if (lane == PZN_WAVE - 1) L.rede[2 * wave + d] = inc;
+    }
+    __syncthreads();      // the wave totals
+    double bphi[2];
+    int bm[2];
+#pragma unroll
+    for (int d = 0; d < 2; ++d) {
+      const int n = d ? kb : ka, lo = d ? mb : ma;
+      float off = 0.f;
+#pragma unroll
+      for (int w = 0; w < ICP_W - 1; ++w) off = w < wave ? __fadd_rn(off, L.rede[2 * w + d]) : off;
+      const float base = __fadd_rn(off, exc[d]);
+      bphi[d] = (double)__builtin_inff(), bm[d] = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int m = 4 * tid + i + 1;
+        const double dm = (double)m;
+        double q = dm;
+        for (int j = 0; j < au->power; ++j) q *= dm;      // m^(p+1), exact: m <= 1024, p + 1 <= 5
+        const double phi = (double)__fadd_rn(base, c[d][i]) / q;
+        const bool take = m >= lo && m <= n && phi_before(phi, m, bphi[d], bm[d]);
+        bphi[d] = take ? phi : bphi[d], bm[d] = take ? m : bm[d];
+      }
+#define ICP_PHI_STEP(J)                                                                                         \
+  {                                                                                                             \
+    const double ophi = __longlong_as_double((long long)pzn::xor_lane_u64<J>((uint64_t)__double_as_longlong(bphi[d]))); \
+    const int om = (int)pzn::xor_lane<J>((uint32_t)bm[d]);                                                      \
+    const bool take = phi_before(ophi, om, bphi[d], bm[d]);                                                     \
+    bphi[d] = take ? ophi : bphi[d], bm[d] = take ? om : bm[d];                                                 \
+  }
+      ICP_PHI_STEP(1) ICP_PHI_STEP(2) ICP_PHI_STEP(4) ICP_PHI_STEP(8) ICP_PHI_STEP(16) ICP_PHI_STEP(32)
+#undef ICP_PHI_STEP
+      if (lane == 0) L.redd[15 * wave + 2 * d] = bphi[d], L.redd[15 * wave + 2 * d + 1] = (double)bm[d];
+    }
+    __syncthreads();      // the four waves' best (phi, m) of both directions
+#pragma unroll
+    for (int d = 0; d < 2; ++d) {
+      double phi = L.redd[2 * d];
+      int m = (int)L.redd[2 * d + 1];
+#pragma unroll
+      for (int w = 1; w < ICP_W; ++w) {
+        const double ophi = L.redd[15 * w + 2 * d];
+        const int om = (int)L.redd[15 * w + 2 * d + 1];
+        const bool take = phi_before(ophi, om, phi, m);
+        phi = take ? ophi : phi, m = take ? om : m;
+      }
+      (d ? mb : ma) = m;      // in [lo, n]: the same value in every thread
+    }
+#pragma unroll
+    for (int s = 0; s < ICP_SLOTS; ++s) {
+      const int r = tid + s * ICP_T;
+      if (r < rows) {
+        const bool fixed_row = r < ka;
+        const bool kept = rank[s] < (fixed_row ? ma : mb);
+        keep[r] = kept ? 1 : 0;
+        if (kept) {
+          if (fixed_row)
+            s1 = __fadd_rn(s1, L.rmin[r]);
+          else
+            s2 = __fadd_rn(s2, L.rmin[r]);
+        }
+      }
+    }
+  } else if constexpr (TRIM) {
     __syncthreads();      // every row's minimum is in rmin
     for (int r = tid; r < rows; r += ICP_T) {
       const bool fixed_row = r < ka;
@@ -128,8 +263,16 @@ __device__ float evaluate(const Lds& L, const Pose& g, int ka, int kb, int ma, i
   float e1 = L.rede[0], e2 = L.rede[1];
 #pragma unroll
   for (int w = 1; w < ICP_W; ++w) e1 = __fadd_rn(e1, L.rede[2 * w]), e2 = __fadd_rn(e2, L.rede[2 * w + 1]);
-  const float e = __fadd_rn(__fdiv_rn(e1, (float)(TRIM ? ma : ka)), __fdiv_rn(e2, (float)(TRIM ? mb : kb)));
-  __syncthreads();      // rede and tx are free again
+  const float ea = __fdiv_rn(e1, (float)(TRIM ? ma : ka)), eb = __fdiv_rn(e2, (float)(TRIM ? mb : kb));
+  const float e = __fadd_rn(ea, eb);
+  if constexpr (AUTO) {
+    const double qa = (double)ka / (double)ma, qb = (double)kb / (double)mb;
+    double ra = qa, rb = qb;
+    for (int j = 1; j < au->power; ++j) ra *= qa, rb *= qb;
+    au->ma = ma, au->mb = mb;
+    au->F = __fadd_rn(__fmul_rn(ea, (float)ra), __fmul_rn(eb, (float)rb));
+  }
+  __syncthreads();      // rede and tx are free again (auto: redd too)
   return e;
 }
 
@@ -240,23 +383,33 @@ __device__ __forceinline__ void store_corr(const Lds& L, int p, int ka, int kb, 
 // What only the trimmed kernel takes, as the kernel's last argument.  The untrimmed form is empty, so icp_refine_kernel keeps
 // the arguments it had, and the names of the two argument types are what tells the two instantiations apart in a trace.
 struct icp_trim_kernel_args {
-  static constexpr bool TRIM = true;
+  static constexpr bool TRIM = true, AUTO = false;
   int ma, mb;                   // rows kept of a and of b
   int32_t *kept_a, *kept_b;     // [P,ma], [P,mb] or NULL
 };
 struct icp_refine_kernel_args {
-  static constexpr bool TRIM = false;
+  static constexpr bool TRIM = false, AUTO = false;
   static constexpr int ma = 0, mb = 0;
   static constexpr int32_t *kept_a = nullptr, *kept_b = nullptr;
 };
 
-// The one body of both kernels: icp_refine_kernel = icp_kernel<icp_refine_kernel_args>, icp_trim_kernel =
+// The auto form: ma, mb are the least counts lo_a, lo_b; kept_a [P,ka], kept_b [P,kb] are padded with -1 behind the count.
+struct icp_auto_kernel_args {
+  static constexpr bool TRIM = true, AUTO = true;
+  int ma, mb;
+  int32_t *kept_a, *kept_b;     // [P,ka], [P,kb] or NULL
+  int power;
+  int32_t *count_a, *count_b;   // [P]
+  float* objective;             // [P]
+};
+
+// The one body of the kernels (icp_auto_kernel = icp_kernel<icp_auto_kernel_args>): icp_refine_kernel = icp_kernel<icp_refine_kernel_args>, icp_trim_kernel =
 // icp_kernel<icp_trim_kernel_args>.  The body stands in the kernel itself and the untrimmed form sets up its LDS exactly as
 // it did before there was a second form: its instructions are then the earlier kernel's, one for one (an inlined body
 // function between the two cost the untrimmed launch 3 % through another register allocation).
 template <typename Args>
 __global__ __launch_bounds__(ICP_T) void icp_kernel(ICP_PARAMS, Args trim) {
-  constexpr bool TRIM = Args::TRIM;
+  constexpr bool TRIM = Args::TRIM, AUTO = Args::AUTO;
   const int ma = trim.ma, mb = trim.mb;
   int32_t* const kept_a = trim.kept_a;
   int32_t* const kept_b = trim.kept_b;
@@ -269,7 +422,8 @@ __global__ __launch_bounds__(ICP_T) void icp_kernel(ICP_PARAMS, Args trim) {
   L.bx = L.az + ka, L.by = L.bx + kb, L.bz = L.by + kb;
   L.tx = L.bz + kb, L.ty = L.tx + kb, L.tz = L.ty + kb;
   L.rmin = TRIM ? L.tz + kb : nullptr;                                                 // [ka + kb], trimmed only
-  L.corr = reinterpret_cast<unsigned short*>(L.tz + kb + (TRIM ? ka + kb : 0));         // [ka + kb]
+  L.sorted = AUTO ? L.rmin + ka + kb : nullptr;                                        // [ka + kb], auto only
+  L.corr = reinterpret_cast<unsigned short*>(L.tz + kb + (TRIM ? ka + kb : 0) + (AUTO ? ka + kb : 0));      // [ka + kb]
   L.keep = TRIM ? reinterpret_cast<unsigned char*>(L.corr + ka + kb) : nullptr;         // [2][ka + kb], trimmed only
   const int npairs = TRIM ? ma + mb : 0;      // (the untrimmed candidate divides by its own ka + kb)
   const int tid = (int)threadIdx.x;
@@ -297,15 +451,22 @@ __global__ __launch_bounds__(ICP_T) void icp_kernel(ICP_PARAMS, Args trim) {
     __syncthreads();
 
     int flip = 0;      // which kept mask is the current pose's (workgroup-uniform; trimmed only)
-    float e = evaluate<TRIM>(L, cur, ka, kb, ma, mb, L.keep, tid);
+    [[maybe_unused]] AutoEval ac, an;      // auto only: the counts and F of the current pose and of the candidate
+    if constexpr (AUTO) ac.power = an.power = trim.power;
+    float e = evaluate<TRIM, AUTO>(L, cur, ka, kb, ma, mb, L.keep, tid, &ac);
     const float e0 = e;
     int used = 0;
     for (int it = 0; it < iters; ++it) {      // (e, and with it the exit, is the same in every thread)
       // the correspondences this candidate is built from (L.corr is overwritten by its evaluation)
       store_corr(L, p, ka, kb, tid, corr_a, corr_b);
-      const Pose nxt = candidate<TRIM>(L, cur, ka, kb, npairs, L.keep + flip * (ka + kb), tid);
-      const float en = evaluate<TRIM>(L, nxt, ka, kb, ma, mb, L.keep + (flip ^ 1) * (ka + kb), tid);      // (the other mask)
-      if (!(en < e)) break;
+      const Pose nxt = candidate<TRIM>(L, cur, ka, kb, AUTO ? ac.ma + ac.mb : npairs, L.keep + flip * (ka + kb), tid);
+      const float en = evaluate<TRIM, AUTO>(L, nxt, ka, kb, ma, mb, L.keep + (flip ^ 1) * (ka + kb), tid, &an);      // (the other mask)
+      if constexpr (AUTO) {
+        if (!(an.F < ac.F)) break;      // F is what falls; the score follows the counts
+        ac = an;
+      } else {
+        if (!(en < e)) break;
+      }
       cur = nxt, e = en, ++used, flip ^= 1;
     }
     if (iters == 0) store_corr(L, p, ka, kb, tid, corr_a, corr_b);      // the correspondences under T0
@@ -317,12 +478,22 @@ __global__ __launch_bounds__(ICP_T) void icp_kernel(ICP_PARAMS, Args trim) {
         const bool fixed_row = r < ka;
         int32_t* out = fixed_row ? kept_a : kept_b;
         if (!kp[r] || !out) continue;
-        const int own = fixed_row ? r : r - ka, m = fixed_row ? ma : mb;
+        const int own = fixed_row ? r : r - ka, m = AUTO ? (fixed_row ? ac.ma : ac.mb) : (fixed_row ? ma : mb);
+        const int stride = AUTO ? (fixed_row ? ka : kb) : m;
         const unsigned char* side = fixed_row ? kp : kp + ka;
         int pos = 0;
         for (int c = 0; c < own; ++c) pos += side[c];
-        if (pos < m) out[(size_t)p * m + pos] = own;      // (always: exactly m rows of a direction are kept)
+        if (pos < m) out[(size_t)p * stride + pos] = own;      // (always: exactly m rows of a direction are kept)
       }
+    }
+    if constexpr (AUTO) {
+      for (int r = tid; r < ka + kb; r += ICP_T) {      // -1 behind the count
+        const bool fixed_row = r < ka;
+        int32_t* out = fixed_row ? kept_a : kept_b;
+        const int own = fixed_row ? r : r - ka;
+        if (out && own >= (fixed_row ? ac.ma : ac.mb)) out[(size_t)p * (fixed_row ? ka : kb) + own] = -1;
+      }
+      if (tid == 0) trim.count_a[p] = ac.ma, trim.count_b[p] = ac.mb, trim.objective[p] = ac.F;
     }
     if (tid < 16) {
       const int u = tid >> 2, v = tid & 3;
@@ -339,11 +510,12 @@ __global__ __launch_bounds__(ICP_T) void icp_kernel(ICP_PARAMS, Args trim) {
   }
 }
 
-// Bytes of LDS of a launch: reduction slots, the three point images, the arg-mins; trimmed: the row minima and two masks.
-size_t icp_lds_bytes(int ka, int kb, bool trim) {
+// Bytes of LDS of a launch: reduction slots, the three point images, the arg-mins; trimmed: the row minima and two masks;
+// automatic: the sorted minima too.
+size_t icp_lds_bytes(int ka, int kb, bool trim, bool automatic = false) {
   const size_t rows = (size_t)ka + (size_t)kb;
   return ICP_W * 15 * sizeof(double) + (ICP_W * 2 + 12) * sizeof(float) + 3 * ((size_t)ka + 2 * (size_t)kb) * sizeof(float) +
-         rows * sizeof(unsigned short) + (trim ? rows * sizeof(float) + 2 * rows : 0);
+         rows * sizeof(unsigned short) + (trim ? rows * sizeof(float) + 2 * rows : 0) + (automatic ? rows * sizeof(float) : 0);
 }
 
 }  // namespace
@@ -380,5 +552,25 @@ PZN_EXPORT int pzn_icp_refine_trim_f32(const float* a, const int64_t* a_of, cons
   const int grid = P < ICP_MAX_GRID ? P : ICP_MAX_GRID;
   PZN_LAUNCH(icp_kernel<icp_trim_kernel_args>, dim3(grid), dim3(ICP_T), icp_lds_bytes(ka, kb, true), st, a, a_of, b, b_of, T0, P, ka, kb, iters, T,
              score, score0, iters_used, corr_a, corr_b, icp_trim_kernel_args{keep_a, keep_b, kept_a, kept_b});
+  PZN_RETURN_LAUNCH_STATUS();
+}
+
+PZN_EXPORT int pzn_icp_refine_auto_supported(int ka, int kb, int lo_a, int lo_b, int power) {
+  return pzn_icp_refine_trim_supported(ka, kb, lo_a, lo_b) && power >= 1 && power <= 4;
+}
+
+PZN_EXPORT int pzn_icp_refine_auto_f32(const float* a, const int64_t* a_of, const float* b, const int64_t* b_of, const float* T0,
+                                       int P, int ka, int kb, int lo_a, int lo_b, int power, int iters, float* T, float* score,
+                                       float* score0, int32_t* iters_used, int32_t* corr_a, int32_t* corr_b, int32_t* count_a,
+                                       int32_t* count_b, float* objective, int32_t* kept_a, int32_t* kept_b, pzn_stream_t stream) {
+  if (!pzn_icp_refine_auto_supported(ka, kb, lo_a, lo_b, power) || iters < 0) return PZN_EUNSUPPORTED;
+  PZN_CHECK_ARG(P >= 0);
+  if (P == 0) return PZN_OK;
+  PZN_CHECK_ARG(a && b && T0 && T && score && score0 && iters_used && count_a && count_b && objective);
+  hipStream_t st = pzn_hip_stream(stream);
+  const int grid = P < ICP_MAX_GRID ? P : ICP_MAX_GRID;
+  PZN_LAUNCH(icp_kernel<icp_auto_kernel_args>, dim3(grid), dim3(ICP_T), icp_lds_bytes(ka, kb, true, true), st, a, a_of, b, b_of, T0, P, ka, kb,
+             iters, T, score, score0, iters_used, corr_a, corr_b,
+             icp_auto_kernel_args{lo_a, lo_b, kept_a, kept_b, power, count_a, count_b, objective});
   PZN_RETURN_LAUNCH_STATUS();
 }

@@ -236,7 +236,11 @@ def icp_refine_trim_supported(ka, kb, keep_a, keep_b):
     return bool(_lib.load().pzn_icp_refine_trim_supported(int(ka), int(kb), int(keep_a), int(keep_b)))
 
 
-def icp_refine(a, b, T0, iters, a_of=None, b_of=None, return_corr=False, keep=None, return_kept=False):
+def icp_refine_auto_supported(ka, kb, lo_a, lo_b, power):
+    return bool(_lib.load().pzn_icp_refine_auto_supported(int(ka), int(kb), int(lo_a), int(lo_b), int(power)))
+
+
+def icp_refine(a, b, T0, iters, a_of=None, b_of=None, return_corr=False, keep=None, return_kept=False, auto=None):
     """P pose refinements in one launch (pzn_icp_refine_f32): symmetric point-to-point ICP of the moved set b[.,kb,3] onto the
     fixed set a[.,ka,3] from T0[P,4,4], at most `iters` accepted steps per problem -> (T [P,4,4], score [P], score0 [P],
     iters_used [P] int32), and with return_corr the correspondences the last candidate was built from, corr_a [P,ka] and
@@ -248,7 +252,14 @@ def icp_refine(a, b, T0, iters, a_of=None, b_of=None, return_corr=False, keep=No
     kernel): of each direction's rows only the m with the smallest (minimum, index) count in E and as pairs of the step;
     1 <= m_a <= ka, 1 <= m_b <= kb (PznUnsupported beyond, before any launch).  return_kept appends kept_a [P,m_a] and kept_b
     [P,m_b] (int32, ascending): the rows kept under the returned T.  keep = None is the untrimmed launch, untouched; with it
-    return_kept gives 0 .. k-1."""
+    return_kept gives 0 .. k-1.
+    auto = (lo_a, lo_b, power), ints, exclusive with keep: the counts are found per problem and per evaluated pose
+    (pzn_icp_refine_auto_f32, one launch of its own kernel; include/pzn.h states the rule): the m in [lo, k] with the
+    smallest (prefix sum of the sorted minima) / m^(power + 1), the step taken iff the objective F falls.  1 <= lo_a <= ka,
+    1 <= lo_b <= kb, 1 <= power <= 4 (PznUnsupported beyond, before any launch).  The result is then (T, score, score0,
+    iters_used[, corr_a, corr_b], count_a [P] int32, count_b [P] int32, objective [P]) and with return_kept kept_a [P,ka],
+    kept_b [P,kb] (int32): the kept rows ascending, then -1.  score is the trimmed E at the returned pose's counts and may
+    exceed score0; objective never exceeds the F of T0.  auto = (ka, kb, p) is keep = (ka, kb) bit for bit."""
     for name, t, dt in (("a", a, torch.float32), ("b", b, torch.float32), ("T0", T0, torch.float32), ("a_of", a_of, torch.int64),
                         ("b_of", b_of, torch.int64)):
         if isinstance(t, torch.Tensor) and t.dtype != dt:      # (no silent conversion: a pose refined in another precision)
@@ -279,6 +290,14 @@ def icp_refine(a, b, T0, iters, a_of=None, b_of=None, return_corr=False, keep=No
             raise _lib.PznError(f"icp_refine: keep = (m_a, m_b) as ints; got {keep!r}")
         if not icp_refine_trim_supported(ka, kb, keep[0], keep[1]):
             raise _lib.PznUnsupported(f"icp_refine: keep = {tuple(keep)} of ka = {ka}, kb = {kb} rows (1 <= m_a <= ka, 1 <= m_b <= kb)")
+    if auto is not None:
+        if keep is not None:
+            raise _lib.PznError("icp_refine: keep and auto exclude each other (counts given, or counts found)")
+        if not isinstance(auto, (tuple, list)) or len(auto) != 3 or not all(isinstance(m, int) and not isinstance(m, bool) for m in auto):
+            raise _lib.PznError(f"icp_refine: auto = (lo_a, lo_b, power) as ints; got {auto!r}")
+        if not icp_refine_auto_supported(ka, kb, *auto):
+            raise _lib.PznUnsupported(f"icp_refine: auto = {tuple(auto)} of ka = {ka}, kb = {kb} rows (1 <= lo_a <= ka, 1 <= lo_b <= kb, "
+                                      "1 <= power <= 4)")
     dev = a.device
     T = torch.empty((P, 4, 4), dtype=torch.float32, device=dev)
     score = torch.empty((P,), dtype=torch.float32, device=dev)
@@ -286,21 +305,30 @@ def icp_refine(a, b, T0, iters, a_of=None, b_of=None, return_corr=False, keep=No
     used = torch.empty((P,), dtype=torch.int32, device=dev)
     ca = torch.empty((P, ka), dtype=torch.int32, device=dev) if return_corr else None
     cb = torch.empty((P, kb), dtype=torch.int32, device=dev) if return_corr else None
-    kept = ()
-    if return_kept and keep is None:
+    kept = found = ()
+    if auto is not None:
+        found = (torch.empty((P,), dtype=torch.int32, device=dev), torch.empty((P,), dtype=torch.int32, device=dev),
+                 torch.empty((P,), dtype=torch.float32, device=dev))
+        if return_kept:
+            kept = tuple(torch.empty((P, k), dtype=torch.int32, device=dev) for k in (ka, kb))
+    elif return_kept and keep is None:
         kept = tuple(torch.arange(k, dtype=torch.int32, device=dev).expand(P, k).contiguous() for k in (ka, kb))
     elif return_kept:
         kept = tuple(torch.empty((P, m), dtype=torch.int32, device=dev) for m in keep)
     if P > 0:
         with _on(dev):
-            if keep is None:
+            if auto is not None:
+                _call("pzn_icp_refine_auto_f32", _p(a), _p(maps[0]), _p(b), _p(maps[1]), _p(T0), P, ka, kb, auto[0], auto[1], auto[2],
+                      iters, _p(T), _p(score), _p(score0), _p(used), _p(ca), _p(cb), _p(found[0]), _p(found[1]), _p(found[2]),
+                      _p(kept[0]) if kept else None, _p(kept[1]) if kept else None, _stream())
+            elif keep is None:
                 _call("pzn_icp_refine_f32", _p(a), _p(maps[0]), _p(b), _p(maps[1]), _p(T0), P, ka, kb, iters, _p(T), _p(score),
                       _p(score0), _p(used), _p(ca), _p(cb), _stream())
             else:
                 _call("pzn_icp_refine_trim_f32", _p(a), _p(maps[0]), _p(b), _p(maps[1]), _p(T0), P, ka, kb, keep[0], keep[1], iters,
                       _p(T), _p(score), _p(score0), _p(used), _p(ca), _p(cb), _p(kept[0]) if kept else None,
                       _p(kept[1]) if kept else None, _stream())
-    return ((T, score, score0, used, ca, cb) if return_corr else (T, score, score0, used)) + kept
+    return ((T, score, score0, used, ca, cb) if return_corr else (T, score, score0, used)) + found + kept
 
 
 def joint_refine_supported(K, J, ka, kb):

@@ -2,7 +2,7 @@
 assembled cloud.
 
     python tools/assemble.py --pieces pieces.npy [--ckpt model.ckpt] [--k 128] [--max-score S] [--out PREFIX] [--progressive]
-                             [--refine N] [--keep F] [--joint N] [--gt PREFIX_gt.npz] [--beam B] [--branch C] [--vote-weight W] [--forest]
+                             [--refine N] [--keep F|auto] [--joint N] [--gt PREFIX_gt.npz] [--beam B] [--branch C] [--vote-weight W] [--forest]
 
 pieces.npy holds [K, N, 3] float32 (N = the model's points per piece).  Prints the score table and the edges in
 placement order, writes PREFIX_G.npy ([K,4,4], each piece into the root's frame) and PREFIX_cloud.npy ([K,N,3]).
@@ -76,6 +76,11 @@ def forest(args, x, table):
     print(f"wrote {args.out}_G.npy, {args.out}_component.npy, {args.out}_cloud.npy (every component in its own root's frame)")
 
 
+def keep_arg(text):
+    """--keep: a share in (0, 1], or the word auto (the share found per pair on the device)."""
+    return "auto" if text == "auto" else float(text)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--pieces", required=True, help=".npy file with [K, N, 3] float32 pieces")
@@ -87,8 +92,9 @@ def main():
     ap.add_argument("--progressive", action="store_true", help="merge placed parts, resample and match again after every placement")
     ap.add_argument("--keep-matched", action="store_true", help="--progressive: keep the matched boundary points in the merged part")
     ap.add_argument("--refine", type=int, default=0, help="ICP steps at most per pair pose on the picked boundary points (0: none)")
-    ap.add_argument("--keep", type=float, default=1.0, help="partial contact: the share of the picked boundary points of each side "
-                    "that counts in a pair's score and refinement, those closest to the other side (1.0: all; not with --progressive)")
+    ap.add_argument("--keep", type=keep_arg, default=1.0, help="partial contact: the share of the picked boundary points of each side "
+                    "that counts in a pair's score and refinement, those closest to the other side (1.0: all; not with --progressive), "
+                    "or the word auto: the share is found per pair on the device (not with --joint)")
     ap.add_argument("--joint", type=int, default=0, help="sweeps at most of the joint refinement after the greedy walk (0: none)")
     ap.add_argument("--gt", default=None, help="PREFIX_gt.npz of tools/fracture.py: score the assembly against the truth")
     ap.add_argument("--beam", type=int, default=0, help="B: the beam walk with B hypotheses in place of the greedy walk (1 .. 8; 0: greedy)")
@@ -102,8 +108,11 @@ def main():
         sys.exit("--beam B, --branch C: 1 .. 8, --vote-weight: a number, and not with --progressive")
     if args.refine < 0:
         sys.exit("--refine: 0 or a number of steps")
-    if not 0.0 < args.keep <= 1.0 or (args.keep < 1.0 and args.progressive):
-        sys.exit("--keep: a share in (0, 1], and 1.0 with --progressive (the progressive walk does not trim)")
+    if (args.keep != "auto" and not 0.0 < args.keep <= 1.0) or (args.keep != 1.0 and args.progressive):
+        sys.exit("--keep: a share in (0, 1] or the word auto, and 1.0 with --progressive (the progressive walk does not trim)")
+    if args.keep == "auto" and args.joint:
+        from puzzlenet_amd import assembly
+        sys.exit(f"--joint with --keep auto: {assembly.AUTO_JOINT_MESSAGE}")
     if args.joint < 0 or (args.joint and args.progressive):
         sys.exit("--joint: 0 or a number of sweeps, and for the greedy walk only (not with --progressive)")
 

@@ -27,7 +27,8 @@ figures and the library's launches beside them; (a') assembly.refine_assembly on
 over its first 8 pieces' - the time of its one kernel, 30 sweeps at most, with the default joint set and with every ordered
 pair as a joint (there is nothing earlier to compare it with); (a'') the trimmed launch of refine_pairs at keep = 0.5 on the
 same boundaries and poses beside the untrimmed one - the time of each one's kernel per launch (the library's own event pair),
-each in a run of its own launches in one process; and (b) match_pairs with refine = 30 against refine = 0 (host wall time around
+each in a run of its own launches in one process; (a''') the auto launch (keep = "auto": the share found per pair on the
+device) the same way, with its ratio to the trimmed launch; and (b) match_pairs with refine = 30 against refine = 0 (host wall time around
 a synchronised call, alternated).
 
 --batch Z measures instead the whole chain on Z fractured puzzles of P = 8 pieces (datapipe.fracture on seeded clouds of 20000
@@ -256,6 +257,21 @@ def refine(args):
             "trim_over_untrimmed_median": statistics.median(t_ms) / statistics.median(u_ms),
             "iters_used_mean": float(rt.iters_used.float().mean()), "iters_used_max": int(rt.iters_used.max())}
     print(json.dumps({"trimmed_launch": trim}))
+    # the auto launch (the share found per pair and per evaluated pose, AutoKeep's defaults) on the same boundaries and poses
+
+    def found():
+        return assembly.refine_pairs(pieces, table.top_f, pieces, table.top_m, table.T, ITERS, keep="auto")
+
+    for _ in range(args.warmup):
+        found()
+    a_ms = [_kernel_us(found, "icp_auto_kernel", 1, 0) / 1e3 for _ in range(args.reps)]
+    ra = found()
+    auto = {"keep": "auto", "least": assembly.AutoKeep().least, "power": assembly.AutoKeep().power, "icp_auto_kernel_ms": _spread(a_ms),
+            "auto_over_trim_median": statistics.median(a_ms) / statistics.median(t_ms),
+            "auto_over_untrimmed_median": statistics.median(a_ms) / statistics.median(u_ms),
+            "iters_used_mean": float(ra.iters_used.float().mean()), "iters_used_max": int(ra.iters_used.max()),
+            "count_f_mean": float(ra.count_f.float().mean()), "count_m_mean": float(ra.count_m.float().mean())}
+    print(json.dumps({"auto_launch": auto}))
     # the joint refinement of the greedy assembly (assembly.refine_assembly: one launch of joint_refine_kernel, 30 sweeps at
     # most) at K = 8 (the first 8 pieces' sub-table) and K = 16: the default joint set and every ordered pair
     joint = {}
@@ -290,6 +306,7 @@ def refine(args):
               "refine_pairs_library_launches": {k_: v[0] for k_, v in k_f.items()},
               "icp_refine_kernel_ms": icp[0][1] if icp else None,
               "trimmed_launch": trim,
+              "auto_launch": auto,
               "joint_refine_kernel_ms": joint,
               "iters_used_mean": float(r.iters_used.float().mean()), "iters_used_max": int(r.iters_used.max()),
               "score_over_score0_mean_off_diagonal": float((r.score[off] / r.score0[off]).mean()),

@@ -1,7 +1,7 @@
 """The assembly score of a model as a mean over a batch of fractured puzzles, with one download at the end:
 
     python tools/eval_assembly.py [--batch 64] [--pieces 8] [--m 20000] [--k 128] [--candidates 16] [--mag 0.8] [--seed 0]
-                                  [--curvature 2.0] [--ckpt model.ckpt] [--refine N] [--keep F] [--joint N] [--max-score S]
+                                  [--curvature 2.0] [--ckpt model.ckpt] [--refine N] [--keep F|auto] [--joint N] [--max-score S]
                                   [--progressive] [--time R] [--json out.json] [--beam B] [--branch C] [--vote-weight W]
                                   [--objects Q]
 
@@ -107,6 +107,11 @@ def sort_piles(args, model, f, dev):
         print(f"forest beam: the forest walk's edges in {100 * host[at - 1]:.1f} % of the piles")
 
 
+def keep_arg(text):
+    """--keep: a share in (0, 1], or the word auto (the share found per pair on the device)."""
+    return "auto" if text == "auto" else float(text)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--batch", type=int, default=64, help="B: clouds, one puzzle each")
@@ -121,9 +126,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ckpt", default=None, help="reference checkpoint (puzzlenet_amd.checkpoint); closed-form weights if absent")
     ap.add_argument("--refine", type=int, default=0, help="ICP steps at most per pair pose on the picked boundary points (0: none)")
-    ap.add_argument("--keep", type=float, default=1.0, help="partial contact: the share of the picked boundary points of each side "
+    ap.add_argument("--keep", type=keep_arg, default=1.0, help="partial contact: the share of the picked boundary points of each side "
                     "that counts in a pair's score and refinement, those closest to the other side (1.0: all; the progressive "
-                    "walks do not trim)")
+                    "walks do not trim), or the word auto: the share is found per pair on the device (not with --joint)")
     ap.add_argument("--joint", type=int, default=0, help="sweeps at most of the joint refinement after the walk (0: none)")
     ap.add_argument("--max-score", type=float, default=None, help="stop placing pieces above this boundary distance")
     ap.add_argument("--progressive", action="store_true", help="also the progressive walk of the whole batch, in lockstep")
@@ -141,8 +146,11 @@ def main():
         sys.exit("--objects goes with the forest walk alone: no --progressive")
     if args.refine < 0 or args.joint < 0:
         sys.exit("--refine, --joint: 0 or a number of steps / sweeps")
-    if not 0.0 < args.keep <= 1.0:
-        sys.exit("--keep: a share in (0, 1]")
+    if args.keep != "auto" and not 0.0 < args.keep <= 1.0:
+        sys.exit("--keep: a share in (0, 1] or the word auto")
+    if args.keep == "auto" and args.joint:
+        from puzzlenet_amd import assembly
+        sys.exit(f"--joint with --keep auto: {assembly.AUTO_JOINT_MESSAGE}")
     if args.time < 0 or (args.time and not args.progressive) or (args.json and not args.time):
         sys.exit("--time R >= 0 goes with --progressive, --json with --time")
     if args.beam and not (1 <= args.beam <= 8 and 1 <= args.branch <= 8 and args.vote_weight == args.vote_weight):
