@@ -205,6 +205,29 @@ int pzn_joint_refine_f32(const float* a, const int64_t* a_of, const float* b, co
                          int Z, int K, int J, int ka, int kb, int sweeps,
                          float* G, float* score, float* score0, float* joint_score,
                          int32_t* sweeps_used, int32_t* accepted, pzn_stream_t stream);
+/* pzn_joint_refine_f32 with a point count per set instead of one per launch (the joints of a table whose kept counts differ
+ * per pair, pzn_icp_refine_auto_f32's): the same kernel body, the same limits (pzn_joint_refine_supported), the same outputs.
+ * na: NULL or int32 with one entry per SET of a, indexed by the set and not by the row - row z J + e reads
+ * na[a_of ? a_of[z J + e] : z J + e] - so one array serves every joint that uses the set; nb likewise for b.  NULL means ka /
+ * kb for every set.  Set s of a holds na[s] points in its FIRST rows; the rows behind them are never read and may hold
+ * anything, NaN included.  ka, kb stay the strides of a and b and size the LDS, whose footprint does not change.
+ * Wherever pzn_joint_refine_f32's contract says ka / kb for row e, this one reads that row's na / nb:
+ * E_e = (sum of the na row minima) / na + (sum of the nb row minima) / nb, the divisors (float)na and (float)nb; row r < na is
+ * a row of A and row na + c one of B, a thread owning rows tid, tid + 256, ... of these na + nb; the pairs of a visit weigh
+ * 1 / na and 1 / nb (float64).  The reference point, Horn's solve, the degenerate rule, the acceptance E_p' < E_p and the held
+ * fp32 total are unchanged.  The sets are frozen: nothing is trimmed again under the joint poses.
+ * A row whose na is outside [1, ka] or whose nb is outside [1, kb] is skipped exactly like a row with a bad (i, j):
+ * joint_score 0, no part in any E_p or visit (the device does not report it; callers check their own host copy).  The counts
+ * of a row with a bad (i, j) are not read, and neither are its a_of / b_of.
+ * na = nb = NULL: every output is pzn_joint_refine_f32's, bit for bit (it is that launch); so is every output with all
+ * counts equal to ka / kb, and with all sets at one (m_a, m_b) the outputs are those of pzn_joint_refine_f32 on the sets cut
+ * to [m_a,3] / [m_b,3]. */
+int pzn_joint_refine_counts_f32(const float* a, const int64_t* a_of, const int32_t* na,
+                                const float* b, const int64_t* b_of, const int32_t* nb,
+                                const int32_t* joints, const float* G0, const uint8_t* movable,
+                                int Z, int K, int J, int ka, int kb, int sweeps,
+                                float* G, float* score, float* score0, float* joint_score,
+                                int32_t* sweeps_used, int32_t* accepted, pzn_stream_t stream);
 
 /* The greedy walk over Z pair tables and the joint list of every walk (no counterpart in the reference; assembly.assemble and
  * the joint selection of assembly.refine_assembly for Z puzzles): one launch, one wavefront per puzzle, no workspace, no

@@ -394,7 +394,8 @@ def match_pairs(model, pieces, k=128, start=None, refine=0, keep=1.0):
     include/pzn.h state the rule), again through one launch, refine = 0 included.  The table is an AutoPairTable: the
     trimmed table's fields with kept_f, kept_m [K,K,k] padded with -1 behind the count, then count_f, count_m [K,K] (int32) and
     objective [K,K].  score is the trimmed score at each pair's own counts, so one max_score means the same for every pair;
-    the walks and evaluate_* read score and T as ever.  refine_assembly refuses such a table (PznUnsupported)."""
+    the walks and evaluate_* read score and T as ever.  refine_assembly takes such a table with kept="frozen"
+    (a count per joint) and refuses it by default (PznUnsupported)."""
     refine = _check_refine(refine, "match_pairs")
     _check_pieces(model, pieces, k, "match_pairs", 2)
     if start is not None:
@@ -462,18 +463,22 @@ def assemble(score, T, max_score=None):
     return Assembly(root, edges, G, placed)
 
 
-AUTO_JOINT_MESSAGE = ("a table made with keep='auto' carries a kept count per pair, and joint_refine_kernel takes one (ka, kb) per "
-                      "launch: joint refinement with per-joint counts is not built yet (padding a set by repeating rows would "
-                      "change the joint energy); make the table with a keep fraction to refine it jointly")
+AUTO_JOINT_MESSAGE = ("a table made with keep='auto' carries a kept count per pair, chosen under the pair's own pose: pass "
+                      "kept='frozen' to refine it jointly over exactly those sets (the joint refinement does not trim again "
+                      "under its own poses), or make the table with a keep fraction")
 
 
-def _no_auto_joints(table, who):
-    """The joint refinements take tables whose kept sets have one size; an AutoPairTable's differ per joint."""
-    if isinstance(table, AutoPairTable):
+def _kept_mode(kept, table, who):
+    """The `kept` keyword of the joint refinements: None or "frozen" (PznError for anything else, before any tensor is
+    touched).  Both refine over the kept sets the table carries, as they are; an AutoPairTable's were chosen per pair under
+    the pair pose, and freezing them is a choice the caller has to name: None refuses such a table."""
+    if kept is not None and not (isinstance(kept, str) and kept == "frozen"):
+        raise _lib.PznError(f"{who}: kept must be None or 'frozen'; got {kept!r}")
+    if kept is None and isinstance(table, AutoPairTable):
         raise _lib.PznUnsupported(f"{who}: {AUTO_JOINT_MESSAGE}")
 
 
-def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None):
+def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None, kept=None):
     """Refine all placed poses of a greedy assembly jointly over every joint: pieces [K,N,3] (float32, on the GPU), table =
     match_pairs' PairTable of them, asm = assemble's Assembly of that table -> JointRefined:
 
@@ -493,8 +498,15 @@ def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None):
     A table that carries kept sets (match_pairs(..., keep < 1)): joint (i, j) pairs pieces[i][top_f[i,j][kept_f[i,j]]] with
     pieces[j][top_m[j][kept_m[i,j]]] - m_f and m_m rows, the moved-side set now one per ordered pair.  The kernel and its
     energy are the same, the untrimmed one over the rows the pair refinement kept: the joint refinement FREEZES the kept
-    sets, it does not trim again under its own poses.  An AutoPairTable is refused (PznUnsupported, _no_auto_joints says why)."""
-    _no_auto_joints(table, "refine_assembly")
+    sets, it does not trim again under its own poses.
+
+    kept: None or "frozen" (anything else is a PznError).  "frozen" names that freezing and changes nothing for the tables
+    above.  An AutoPairTable (keep="auto") carries a count per pair, found under the pair's pose; it is refused by default
+    (PznUnsupported, AUTO_JOINT_MESSAGE) and refined with kept="frozen": joint (i, j) pairs the count_f[i,j] rows
+    pieces[i][top_f[i,j][kept_f[i,j][:count_f[i,j]]]] with the count_m[i,j] rows of pieces[j] likewise, J sets of stride k
+    a side (the -1 padding gathers row 0 of the set, which the kernel never reads) and the counts as ops.joint_refine's
+    na / nb: still one gather and one launch, with every 1 / ka and 1 / kb of the energy that joint's own count."""
+    _kept_mode(kept, table, "refine_assembly")
     _clouds("refine_assembly", "K", pieces=pieces)
     K, N, _ = pieces.shape
     G0 = np.asarray(asm.G, dtype=np.float64)
@@ -517,6 +529,7 @@ def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None):
         mv = torch.from_numpy(movable.astype(np.uint8)).to(dev).reshape(1, K)
         jl = torch.tensor(joints, dtype=torch.int32).reshape(1, J, 2)
         k = table.top_m.shape[1]
+        cnt_a = cnt_b = None
         if J > 0:
             ji = torch.tensor([i for i, _ in joints], dtype=torch.long, device=dev)
             jj = torch.tensor([j for _, j in joints], dtype=torch.long, device=dev)
@@ -526,15 +539,19 @@ def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None):
                 rows_b = (torch.arange(K, device=dev)[:, None] * N + table.top_m).reshape(-1)
                 ka, nb, b_of = k, K, jj.reshape(1, J)
             else:      # the kept rows of every joint: a moved-side set per ordered pair
-                rows_a = (ji[:, None] * N + table.top_f[ji, jj].gather(1, table.kept_f[ji, jj].long())).reshape(-1)
-                rows_b = (jj[:, None] * N + table.top_m[jj].gather(1, table.kept_m[ji, jj].long())).reshape(-1)
+                kept_f, kept_m = table.kept_f[ji, jj].long(), table.kept_m[ji, jj].long()
+                if isinstance(table, AutoPairTable):      # count rows, then -1: a count per set, the padding never read
+                    kept_f, kept_m = kept_f.clamp(min=0), kept_m.clamp(min=0)
+                    cnt_a, cnt_b = table.count_f[ji, jj].to(torch.int32), table.count_m[ji, jj].to(torch.int32)
+                rows_a = (ji[:, None] * N + table.top_f[ji, jj].gather(1, kept_f)).reshape(-1)
+                rows_b = (jj[:, None] * N + table.top_m[jj].gather(1, kept_m)).reshape(-1)
                 ka, nb, b_of = table.kept_f.shape[-1], J, None
             picked = ops.index_points(pieces.contiguous().view(1, K * N, 3), torch.cat((rows_a, rows_b)).reshape(1, -1))[0]
             a, b = picked[:J * ka].view(J, ka, 3), picked[J * ka:].view(nb, -1, 3)
         else:
             a = b = pieces[:0, :k]
             b_of = None
-        G, score, score0, _, used, accepted = ops.joint_refine(a, b, jl, g0, mv, sweeps, b_of=b_of)
+        G, score, score0, _, used, accepted = ops.joint_refine(a, b, jl, g0, mv, sweeps, b_of=b_of, na=cnt_a, nb=cnt_b)
     return JointRefined(G[0], score[0], score0[0], used[0], accepted[0], joints)
 
 
@@ -1302,7 +1319,7 @@ def match_puzzles(model, pieces, k=128, start=None, refine=0, keep=1.0):
     return _table(codes, blk, _diagonal(pieces))
 
 
-def refine_assembly_batch(pieces, table, asm, sweeps=30):
+def refine_assembly_batch(pieces, table, asm, sweeps=30, kept=None):
     """refine_assembly for Z puzzles with no download: pieces [Z,P,N,3] (float32, on the GPU), table = match_puzzles' PairTable
     of them, asm = assemble_batch's AssemblyBatch of that table -> JointRefined whose fields carry a leading Z: G [Z,P,4,4]
     float32, score, score0, sweeps_used [Z], accepted [Z,P], joints = asm.joints (the device tensor, unused rows (-1, -1)).
@@ -1318,8 +1335,13 @@ def refine_assembly_batch(pieces, table, asm, sweeps=30):
     pieces[z,i][top_f[z,i,j][kept_f[z,i,j]]] and pieces[z,j][top_m[z,j][kept_m[z,i,j]]] - 2 Z P^2 sets of m_f and m_m points,
     b_of = a_of per ordered pair; the counts are the table's shapes, known on the host.  The kernel and its energy are the same,
     the untrimmed one over the rows the pair refinement kept: the joint refinement freezes the kept sets, it does not trim
-    again.  An AutoPairTable is refused (PznUnsupported: its counts differ per joint, the kernel takes one pair per launch)."""
-    _no_auto_joints(table, "refine_assembly_batch")
+    again.
+
+    kept: refine_assembly's keyword.  An AutoPairTable is refused by default (PznUnsupported, AUTO_JOINT_MESSAGE); with
+    kept="frozen" its 2 Z P^2 sets have stride k, the -1 padding of kept_* gathers row 0 of the set, and the counts travel as
+    ops.joint_refine's na = count_f and nb = count_m, one per ordered pair and found by the kernel through the same a_of:
+    one gather, one launch, nothing waits for the device."""
+    _kept_mode(kept, table, "refine_assembly_batch")
     _clouds("refine_assembly_batch", "Z,P", pieces=pieces)
     Z, P, N, _ = pieces.shape
     J = P * (P - 1)
@@ -1331,6 +1353,7 @@ def refine_assembly_batch(pieces, table, asm, sweeps=30):
     dev = pieces.device
     with torch.no_grad():
         k = table.top_m.shape[2]
+        cnt_a = cnt_b = None
         piece_row = torch.arange(Z * P, dtype=torch.long, device=dev).view(Z, P) * N                     # first row of piece (z, p)
         ji, jj = asm.joints[..., 0].long(), asm.joints[..., 1].long()
         used = ji >= 0
@@ -1342,15 +1365,19 @@ def refine_assembly_batch(pieces, table, asm, sweeps=30):
             ka, nb = k, Z * P
             b_of = torch.where(used, first * P + jj, torch.zeros_like(jj))
         else:      # the kept rows of every ordered pair, on both sides
-            rows_a = (piece_row[:, :, None, None] + table.top_f.gather(3, table.kept_f.long())).reshape(-1)       # [Z,P,P,m_f]
+            kept_f, kept_m = table.kept_f.long(), table.kept_m.long()
+            if isinstance(table, AutoPairTable):      # count rows, then -1: a count per set, the padding never read
+                kept_f, kept_m = kept_f.clamp(min=0), kept_m.clamp(min=0)
+                cnt_a, cnt_b = table.count_f.reshape(-1).to(torch.int32), table.count_m.reshape(-1).to(torch.int32)
+            rows_a = (piece_row[:, :, None, None] + table.top_f.gather(3, kept_f)).reshape(-1)                    # [Z,P,P,m_f]
             top_m = table.top_m[:, None].expand(Z, P, P, k)
-            rows_b = (piece_row[:, None, :, None] + top_m.gather(3, table.kept_m.long())).reshape(-1)             # [Z,P,P,m_m]
+            rows_b = (piece_row[:, None, :, None] + top_m.gather(3, kept_m)).reshape(-1)                          # [Z,P,P,m_m]
             ka, nb = table.kept_f.shape[-1], Z * P * P
             b_of = a_of
         picked = ops.index_points(pieces.contiguous().view(1, Z * P * N, 3), torch.cat((rows_a, rows_b)).reshape(1, -1))[0]
         a, b = picked[:Z * P * P * ka].view(Z * P * P, ka, 3), picked[Z * P * P * ka:].view(nb, -1, 3)
         G, score, score0, _, used_sweeps, accepted = ops.joint_refine(a, b, asm.joints, asm.G.to(torch.float32), asm.movable, sweeps,
-                                                                      a_of=a_of, b_of=b_of)
+                                                                      a_of=a_of, b_of=b_of, na=cnt_a, nb=cnt_b)
     return JointRefined(G, score, score0, used_sweeps, accepted, asm.joints)
 
 

@@ -25,6 +25,10 @@
 // loop bound and every branch around a barrier depends on the joint list, `movable` and E values that are the same bits in
 // all 256 threads.  A joint row with i or j outside [0, K) or i == j is skipped everywhere (joint_score 0).  A pair listed
 // twice counts twice; a piece that is an end of more than 2 K rows (only possible that way) is never visited.
+// The same body with a count per set (joint_refine_counts_kernel behind pzn_joint_refine_counts_f32; the body's template
+// argument COUNTS): the ka and kb of a row above are then na / nb of that row's sets, read by all threads from one address,
+// and a row with a count outside [1, ka] / [1, kb] is skipped like a bad (i, j); ka and kb remain the strides of the sets
+// and the size of the LDS images.
 #include "pzn_rigid.h"
 
 namespace {
@@ -54,7 +58,8 @@ struct Sets {
   const int64_t* a_of;
   const float* b;
   const int64_t* b_of;
-  int ka, kb;
+  int ka, kb;                   // the strides of a and b, and what sizes the LDS
+  const int32_t *na, *nb;       // points per set of a / of b, indexed by the set (COUNTS launches; NULL: ka / kb everywhere)
 };
 
 __device__ __forceinline__ Pose load_pose(const float* g) {
@@ -68,13 +73,15 @@ __device__ __forceinline__ Pose load_pose(const float* g) {
 
 // E_e of joint row `row` (global index z * J + e) with `own_is_b ? B : A` as the own side under `own` and the other side
 // under `far`.  SUMS: every row adds its pair to acc (shifted by ref, which the first call of a visit sets: have_ref).
-// Three barriers; on entry no thread may still be reading the images or rede (every caller comes from a barrier).
+// The sets hold ka and kb points (the row's counts: S.ka / S.kb without counts, 1 <= ka <= S.ka and 1 <= kb <= S.kb with them,
+// the same value in every thread); rows of a set behind its count are never read, and the LDS behind it holds whatever an
+// earlier joint left.  Three barriers; on entry no thread may still be reading the images or rede (every caller comes from a
+// barrier).
 template <bool SUMS>
-__device__ float eval_joint(const Lds& L, const Sets& S, size_t row, bool own_is_b, const Pose& own, const Pose& far, int tid,
-                            double (&acc)[JR_SUMS], float (&ref)[6], bool& have_ref) {
-  const int ka = S.ka, kb = S.kb;
-  const float* ga = S.a + (size_t)(S.a_of ? S.a_of[row] : (int64_t)row) * ka * 3;
-  const float* gb = S.b + (size_t)(S.b_of ? S.b_of[row] : (int64_t)row) * kb * 3;
+__device__ float eval_joint(const Lds& L, const Sets& S, size_t row, int ka, int kb, bool own_is_b, const Pose& own,
+                            const Pose& far, int tid, double (&acc)[JR_SUMS], float (&ref)[6], bool& have_ref) {
+  const float* ga = S.a + (size_t)(S.a_of ? S.a_of[row] : (int64_t)row) * S.ka * 3;
+  const float* gb = S.b + (size_t)(S.b_of ? S.b_of[row] : (int64_t)row) * S.kb * 3;
   const float* gown = own_is_b ? gb : ga;
   const float* gfar = own_is_b ? ga : gb;
   const int kown = own_is_b ? kb : ka, kfar = own_is_b ? ka : kb;
@@ -219,10 +226,25 @@ __device__ Pose candidate(const Lds& L, const Pose& cur, double (&acc)[JR_SUMS],
 
 __device__ __forceinline__ bool joint_ok(int i, int j, int K) { return i >= 0 && j >= 0 && i < K && j < K && i != j; }
 
+// Whether joint row `row` = (i, j) counts, and the sizes of its two sets.  COUNTS: na / nb of the row's sets (read by every
+// thread from the same address: workgroup-uniform, and only for a row whose (i, j) is a joint, so the set maps of unused rows
+// are never followed); a count outside [1, ka] or [1, kb] skips the row like a bad (i, j).
+template <bool COUNTS>
+__device__ __forceinline__ bool row_ok(const Sets& S, size_t row, int i, int j, int K, int& na, int& nb) {
+  na = S.ka, nb = S.kb;
+  if (!joint_ok(i, j, K)) return false;
+  if (COUNTS) {
+    if (S.na) na = S.na[S.a_of ? S.a_of[row] : (int64_t)row];
+    if (S.nb) nb = S.nb[S.b_of ? S.b_of[row] : (int64_t)row];
+    return na >= 1 && na <= S.ka && nb >= 1 && nb <= S.kb;
+  }
+  return true;
+}
+
 // The fp32 sum, in list order, of E_e over the joints of piece p (all joints: p < 0) with piece p under `gp`.  Thread 0 leaves
 // every E_e in `out` (LDS): out[e] for a p < 0 pass (0 for a skipped row), out[t] for the t-th joint of piece p otherwise (NULL:
 // nowhere); readers come after a barrier.  -> the number of joints met in `met`.
-template <bool SUMS>
+template <bool SUMS, bool COUNTS>
 __device__ float eval_joints(const Lds& L, const Sets& S, const int32_t* __restrict__ jl, size_t row0, int J, int K, int p,
                              const Pose& gp, int tid, double (&acc)[JR_SUMS], float (&ref)[6], bool& have_ref, int& met,
                              float* out) {
@@ -230,13 +252,14 @@ __device__ float eval_joints(const Lds& L, const Sets& S, const int32_t* __restr
   met = 0;
   for (int e = 0; e < J; ++e) {      // (workgroup-uniform: the list is the same for every thread)
     const int i = jl[2 * e], j = jl[2 * e + 1];
-    const bool ok = joint_ok(i, j, K);
+    int na, nb;
+    const bool ok = row_ok<COUNTS>(S, row0 + e, i, j, K, na, nb);
     if (p < 0 && out && tid == 0 && !ok) out[e] = 0.f;
     if (!ok || (p >= 0 && i != p && j != p)) continue;
     const bool own_is_b = p < 0 || j == p;
     const Pose own = p < 0 ? load_pose(L.G + 12 * j) : gp;
     const Pose far = load_pose(L.G + 12 * (own_is_b ? i : j));
-    const float ee = eval_joint<SUMS>(L, S, row0 + e, own_is_b, own, far, tid, acc, ref, have_ref);
+    const float ee = eval_joint<SUMS>(L, S, row0 + e, na, nb, own_is_b, own, far, tid, acc, ref, have_ref);
     if (out && tid == 0) out[p < 0 ? e : met] = ee;
     E = __fadd_rn(E, ee);
     ++met;
@@ -245,13 +268,17 @@ __device__ float eval_joints(const Lds& L, const Sets& S, const int32_t* __restr
 }
 
 // The fp32 sum of L.js over all rows in list order (a skipped row holds 0, which changes no bit of a sum of energies), with
-// the joints of piece p taken from L.jn instead (p < 0: none); commit: thread 0 moves those into L.js.
-__device__ float total_with(const Lds& L, const int32_t* __restrict__ jl, int J, int K, int p, bool commit, int tid) {
+// the joints of piece p taken from L.jn instead (p < 0: none; the rows eval_joints met, by the same rule: row_ok and an end
+// at p); commit: thread 0 moves those into L.js.
+template <bool COUNTS>
+__device__ float total_with(const Lds& L, const Sets& S, const int32_t* __restrict__ jl, size_t row0, int J, int K, int p,
+                            bool commit, int tid) {
   float tot = 0.f;
   int t = 0;
   for (int e = 0; e < J; ++e) {
     const int i = jl[2 * e], j = jl[2 * e + 1];
-    const bool mine = p >= 0 && joint_ok(i, j, K) && (i == p || j == p);
+    int na, nb;
+    const bool mine = p >= 0 && (i == p || j == p) && row_ok<COUNTS>(S, row0 + e, i, j, K, na, nb);
     const float v = mine ? L.jn[t] : L.js[e];
     if (commit && mine && tid == 0) L.js[e] = v;
     t += mine ? 1 : 0;
@@ -260,14 +287,18 @@ __device__ float total_with(const Lds& L, const int32_t* __restrict__ jl, int J,
   return tot;
 }
 
-__global__ __launch_bounds__(JR_T) void joint_refine_kernel(const float* __restrict__ a, const int64_t* __restrict__ a_of,
-                                                            const float* __restrict__ b, const int64_t* __restrict__ b_of,
-                                                            const int32_t* __restrict__ joints, const float* __restrict__ G0,
-                                                            const uint8_t* __restrict__ movable, int Z, int K, int J, int ka,
-                                                            int kb, int sweeps, float* __restrict__ G, float* __restrict__ score,
-                                                            float* __restrict__ score0, float* __restrict__ joint_score,
-                                                            int32_t* __restrict__ sweeps_used, int32_t* __restrict__ accepted) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+// The one body of both kernels below: COUNTS = false is joint_refine_kernel (na, nb are not looked at), true is
+// joint_refine_counts_kernel.
+template <bool COUNTS>
+__device__ __forceinline__ void joint_refine_body(unsigned char* smem_raw, const float* __restrict__ a,
+                                                  const int64_t* __restrict__ a_of, const int32_t* __restrict__ na,
+                                                  const float* __restrict__ b, const int64_t* __restrict__ b_of,
+                                                  const int32_t* __restrict__ nb, const int32_t* __restrict__ joints,
+                                                  const float* __restrict__ G0, const uint8_t* __restrict__ movable, int Z, int K,
+                                                  int J, int ka, int kb, int sweeps, float* __restrict__ G,
+                                                  float* __restrict__ score, float* __restrict__ score0,
+                                                  float* __restrict__ joint_score, int32_t* __restrict__ sweeps_used,
+                                                  int32_t* __restrict__ accepted) {
   const int kmax = ((ka > kb ? ka : kb) + 3) & ~3;      // the stride of the images: a multiple of four floats
   Lds L;
   L.redd = reinterpret_cast<double*>(smem_raw);                       // [JR_W][JR_SUMS]
@@ -281,7 +312,7 @@ __global__ __launch_bounds__(JR_T) void joint_refine_kernel(const float* __restr
   L.js = reinterpret_cast<float*>(L.taken + K);                       // [J]
   L.jn = L.js + J;                                                    // [2 K]
   const int tid = (int)threadIdx.x;
-  const Sets S = {a, a_of, b, b_of, ka, kb};
+  const Sets S = {a, a_of, b, b_of, ka, kb, na, nb};
 
   for (int z = (int)blockIdx.x; z < Z; z += (int)gridDim.x) {      // (workgroup-uniform)
     const int32_t* jl = joints + (size_t)z * J * 2;
@@ -300,9 +331,9 @@ __global__ __launch_bounds__(JR_T) void joint_refine_kernel(const float* __restr
     bool have_ref = true;
     int met;
     const Pose none = load_pose(L.G);
-    eval_joints<false>(L, S, jl, row0, J, K, -1, none, tid, acc, ref, have_ref, met, L.js);
+    eval_joints<false, COUNTS>(L, S, jl, row0, J, K, -1, none, tid, acc, ref, have_ref, met, L.js);
     __syncthreads();
-    const float e0 = total_with(L, jl, J, K, -1, false, tid);
+    const float e0 = total_with<COUNTS>(L, S, jl, row0, J, K, -1, false, tid);
     float e = e0;      // E under the current poses: the sum of L.js, the same bits in every thread
     int used = 0;
     for (int sw = 0; sw < sweeps; ++sw) {
@@ -313,18 +344,18 @@ __global__ __launch_bounds__(JR_T) void joint_refine_kernel(const float* __restr
 #pragma unroll
         for (int k = 0; k < JR_SUMS; ++k) acc[k] = 0.0;
         have_ref = false;
-        const float ep = eval_joints<true>(L, S, jl, row0, J, K, p, cur, tid, acc, ref, have_ref, met, nullptr);
+        const float ep = eval_joints<true, COUNTS>(L, S, jl, row0, J, K, p, cur, tid, acc, ref, have_ref, met, nullptr);
         if (met == 0 || met > 2 * K) continue;      // (more than 2 (K - 1) rows only where the list repeats a pair: L.jn holds 2 K)
         const Pose nxt = candidate(L, cur, acc, ref, tid);
-        const float en = eval_joints<false>(L, S, jl, row0, J, K, p, nxt, tid, acc, ref, have_ref, met, L.jn);
+        const float en = eval_joints<false, COUNTS>(L, S, jl, row0, J, K, p, nxt, tid, acc, ref, have_ref, met, L.jn);
         if (!(en < ep)) continue;      // (the same bits in every thread)
         __syncthreads();               // L.jn is written
         // E_p fell, so E falls - in exact arithmetic.  The fp32 sum over all rows is held to it too: a candidate whose
         // total would round ABOVE the current one is left (a last-place matter: score <= score0 holds to the bit)
-        const float et = total_with(L, jl, J, K, p, false, tid);
+        const float et = total_with<COUNTS>(L, S, jl, row0, J, K, p, false, tid);
         if (!(et <= e)) continue;
         __syncthreads();               // every thread has read L.js
-        total_with(L, jl, J, K, p, true, tid);
+        total_with<COUNTS>(L, S, jl, row0, J, K, p, true, tid);
         if (tid < 12) L.G[12 * p + tid] = L.cand[tid];
         if (tid == 0) L.taken[p] += 1;
         e = et;
@@ -346,16 +377,42 @@ __global__ __launch_bounds__(JR_T) void joint_refine_kernel(const float* __restr
   }
 }
 
+__global__ __launch_bounds__(JR_T) void joint_refine_kernel(const float* __restrict__ a, const int64_t* __restrict__ a_of,
+                                                            const float* __restrict__ b, const int64_t* __restrict__ b_of,
+                                                            const int32_t* __restrict__ joints, const float* __restrict__ G0,
+                                                            const uint8_t* __restrict__ movable, int Z, int K, int J, int ka,
+                                                            int kb, int sweeps, float* __restrict__ G, float* __restrict__ score,
+                                                            float* __restrict__ score0, float* __restrict__ joint_score,
+                                                            int32_t* __restrict__ sweeps_used, int32_t* __restrict__ accepted) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  joint_refine_body<false>(smem_raw, a, a_of, nullptr, b, b_of, nullptr, joints, G0, movable, Z, K, J, ka, kb, sweeps, G, score,
+                           score0, joint_score, sweeps_used, accepted);
+}
+
+__global__ __launch_bounds__(JR_T) void joint_refine_counts_kernel(
+    const float* __restrict__ a, const int64_t* __restrict__ a_of, const int32_t* __restrict__ na, const float* __restrict__ b,
+    const int64_t* __restrict__ b_of, const int32_t* __restrict__ nb, const int32_t* __restrict__ joints,
+    const float* __restrict__ G0, const uint8_t* __restrict__ movable, int Z, int K, int J, int ka, int kb, int sweeps,
+    float* __restrict__ G, float* __restrict__ score, float* __restrict__ score0, float* __restrict__ joint_score,
+    int32_t* __restrict__ sweeps_used, int32_t* __restrict__ accepted) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  joint_refine_body<true>(smem_raw, a, a_of, na, b, b_of, nb, joints, G0, movable, Z, K, J, ka, kb, sweeps, G, score, score0,
+                          joint_score, sweeps_used, accepted);
+}
+
 }  // namespace
 
 PZN_EXPORT int pzn_joint_refine_supported(int K, int J, int ka, int kb) {
   return K >= 1 && K <= JR_MAX_PIECES && J >= 0 && J <= K * (K - 1) && ka >= 1 && kb >= 1 && ka <= JR_MAX_K && kb <= JR_MAX_K;
 }
 
-PZN_EXPORT int pzn_joint_refine_f32(const float* a, const int64_t* a_of, const float* b, const int64_t* b_of,
-                                    const int32_t* joints, const float* G0, const uint8_t* movable, int Z, int K, int J, int ka,
-                                    int kb, int sweeps, float* G, float* score, float* score0, float* joint_score,
-                                    int32_t* sweeps_used, int32_t* accepted, pzn_stream_t stream) {
+namespace {
+
+// na = nb = NULL launches joint_refine_kernel, anything else joint_refine_counts_kernel.
+int joint_refine_launch(const float* a, const int64_t* a_of, const int32_t* na, const float* b, const int64_t* b_of,
+                        const int32_t* nb, const int32_t* joints, const float* G0, const uint8_t* movable, int Z, int K, int J,
+                        int ka, int kb, int sweeps, float* G, float* score, float* score0, float* joint_score,
+                        int32_t* sweeps_used, int32_t* accepted, pzn_stream_t stream) {
   if (!pzn_joint_refine_supported(K, J, ka, kb) || sweeps < 0) return PZN_EUNSUPPORTED;
   PZN_CHECK_ARG(Z >= 0);
   if (Z == 0 || J == 0) return PZN_OK;
@@ -365,7 +422,31 @@ PZN_EXPORT int pzn_joint_refine_f32(const float* a, const int64_t* a_of, const f
   const size_t lds = JR_W * JR_SUMS * sizeof(double) + (JR_W * 2 + 12 + 12 * (size_t)K + 9 * kmax) * sizeof(float) +
                      (size_t)K * sizeof(int) + ((size_t)J + 2 * (size_t)K) * sizeof(float);
   const int grid = Z < JR_MAX_GRID ? Z : JR_MAX_GRID;
-  PZN_LAUNCH(joint_refine_kernel, dim3(grid), dim3(JR_T), lds, st, a, a_of, b, b_of, joints, G0, movable, Z, K, J, ka, kb, sweeps,
-             G, score, score0, joint_score, sweeps_used, accepted);
+  if (!na && !nb)
+    PZN_LAUNCH(joint_refine_kernel, dim3(grid), dim3(JR_T), lds, st, a, a_of, b, b_of, joints, G0, movable, Z, K, J, ka, kb,
+               sweeps, G, score, score0, joint_score, sweeps_used, accepted);
+  else
+    PZN_LAUNCH(joint_refine_counts_kernel, dim3(grid), dim3(JR_T), lds, st, a, a_of, na, b, b_of, nb, joints, G0, movable, Z, K,
+               J, ka, kb, sweeps, G, score, score0, joint_score, sweeps_used, accepted);
   PZN_RETURN_LAUNCH_STATUS();
+}
+
+}  // namespace
+
+PZN_EXPORT int pzn_joint_refine_f32(const float* a, const int64_t* a_of, const float* b, const int64_t* b_of,
+                                    const int32_t* joints, const float* G0, const uint8_t* movable, int Z, int K, int J, int ka,
+                                    int kb, int sweeps, float* G, float* score, float* score0, float* joint_score,
+                                    int32_t* sweeps_used, int32_t* accepted, pzn_stream_t stream) {
+  return joint_refine_launch(a, a_of, nullptr, b, b_of, nullptr, joints, G0, movable, Z, K, J, ka, kb, sweeps, G, score, score0,
+                             joint_score, sweeps_used, accepted, stream);
+}
+
+// With both counts NULL this is the launch above: the same kernel, so the same bits.
+PZN_EXPORT int pzn_joint_refine_counts_f32(const float* a, const int64_t* a_of, const int32_t* na, const float* b,
+                                           const int64_t* b_of, const int32_t* nb, const int32_t* joints, const float* G0,
+                                           const uint8_t* movable, int Z, int K, int J, int ka, int kb, int sweeps, float* G,
+                                           float* score, float* score0, float* joint_score, int32_t* sweeps_used,
+                                           int32_t* accepted, pzn_stream_t stream) {
+  return joint_refine_launch(a, a_of, na, b, b_of, nb, joints, G0, movable, Z, K, J, ka, kb, sweeps, G, score, score0,
+                             joint_score, sweeps_used, accepted, stream);
 }

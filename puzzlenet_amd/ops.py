@@ -335,7 +335,7 @@ def joint_refine_supported(K, J, ka, kb):
     return bool(_lib.load().pzn_joint_refine_supported(int(K), int(J), int(ka), int(kb)))
 
 
-def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None):
+def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None, na=None, nb=None):
     """Z pose graphs refined in one launch (pzn_joint_refine_f32): puzzle z has the poses G0[z] [K,4,4], the mask movable[z]
     [K] (uint8 or bool) and the joint rows joints[z] [J,2] (int32 ordered pairs (i, j); a row with i < 0 is unused); row e has
     the set a[a_of[z,e]] [ka,3] in piece i's frame and b[b_of[z,e]] [kb,3] in piece j's (int64 [Z,J]; the caller keeps them
@@ -344,11 +344,17 @@ def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None):
     joint_score [Z,J], sweeps_used [Z] int32, accepted [Z,K] int32); score = E(G) <= score0 = E(G0); sweeps = 0 returns G0.
     joints may be a host tensor, the caller's own copy: then every used row is checked (0 <= i, j < K, i != j, no pair twice;
     PznError) and the list is uploaded; a device tensor is not checked, and the kernel skips such rows.
+    na / nb (int32 [a.shape[0]] / [b.shape[0]]): a point count per SET of a / of b - set s holds na[s] points in its first
+    rows, what lies behind them is never read (NaN is fine), and every ka / kb of the energy and of a visit is that row's count
+    (pzn_joint_refine_counts_f32; ka, kb stay the strides).  Like joints: a host tensor is checked (1 <= n <= ka; PznError) and
+    uploaded, a device tensor is not, and the kernel skips a row with a count out of range (joint_score 0).  With both None
+    the launch is pzn_joint_refine_f32; one of them alone leaves the other side at its full size.
     1 <= K <= 64, J <= K (K - 1), 1 <= ka, kb <= 1024 and sweeps >= 0 (PznUnsupported beyond).  Z = 0 or J = 0 launches
     nothing and returns G0 with scores of 0.  No autograd, nothing waits for the device."""
     for name, t, dts in (("a", a, (torch.float32,)), ("b", b, (torch.float32,)), ("G0", G0, (torch.float32,)),
                          ("joints", joints, (torch.int32,)), ("movable", movable, (torch.uint8, torch.bool)),
-                         ("a_of", a_of, (torch.int64,)), ("b_of", b_of, (torch.int64,))):
+                         ("a_of", a_of, (torch.int64,)), ("b_of", b_of, (torch.int64,)), ("na", na, (torch.int32,)),
+                         ("nb", nb, (torch.int32,))):
         if isinstance(t, torch.Tensor) and t.dtype not in dts:      # (no silent conversion)
             raise _lib.PznError(f"joint_refine: {name} must be {' or '.join(str(d) for d in dts)}; got {t.dtype}")
     a, b, G0 = _f32(a, "a"), _f32(b, "b"), _f32(G0, "G0")
@@ -388,6 +394,22 @@ def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None):
             if x.shape[0] == 0 and Z * J > 0:
                 raise _lib.PznError(f"joint_refine: {name} indexes an empty {name[0]}")
         maps.append(m)
+    counts = []
+    for name, n, x, cap in (("na", na, a, ka), ("nb", nb, b, kb)):
+        if n is not None:
+            if not isinstance(n, torch.Tensor) or n.shape != (x.shape[0],):
+                raise _lib.PznError(f"joint_refine: expected {name}[{x.shape[0]}] (one count per set of {name[1]}); got "
+                                    f"{tuple(n.shape) if isinstance(n, torch.Tensor) else type(n).__name__}")
+            if n.device.type not in ("cpu", "cuda"):
+                raise _lib.PznError(f"joint_refine: {name} must be on the GPU or a host tensor; got one on {n.device}")
+            if not n.is_cuda:      # the caller's host copy, as for joints
+                bad = (n < 1) | (n > cap)
+                if bool(bad.any()):
+                    s = int(bad.nonzero()[0])
+                    raise _lib.PznError(f"joint_refine: {name}[{s}] = {int(n[s])} is no count of a set of {cap} rows")
+                n = n.to(a.device)
+            n = _req(n, torch.int32, name)
+        counts.append(n)
     sweeps = int(sweeps)
     if sweeps < 0 or not joint_refine_supported(K, J, ka, kb):
         raise _lib.PznUnsupported(f"joint_refine: K = {K}, J = {J}, ka = {ka}, kb = {kb}, sweeps = {sweeps} "
@@ -404,8 +426,13 @@ def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None):
     used = torch.empty((Z,), dtype=torch.int32, device=dev)
     accepted = torch.empty((Z, K), dtype=torch.int32, device=dev)
     with _on(dev):
-        _call("pzn_joint_refine_f32", _p(a), _p(maps[0]), _p(b), _p(maps[1]), _p(joints), _p(G0), _p(movable), Z, K, J, ka, kb,
-              sweeps, _p(G), _p(score), _p(score0), _p(joint_score), _p(used), _p(accepted), _stream())
+        if counts[0] is None and counts[1] is None:
+            _call("pzn_joint_refine_f32", _p(a), _p(maps[0]), _p(b), _p(maps[1]), _p(joints), _p(G0), _p(movable), Z, K, J, ka, kb,
+                  sweeps, _p(G), _p(score), _p(score0), _p(joint_score), _p(used), _p(accepted), _stream())
+        else:
+            _call("pzn_joint_refine_counts_f32", _p(a), _p(maps[0]), _p(counts[0]), _p(b), _p(maps[1]), _p(counts[1]), _p(joints),
+                  _p(G0), _p(movable), Z, K, J, ka, kb, sweeps, _p(G), _p(score), _p(score0), _p(joint_score), _p(used),
+                  _p(accepted), _stream())
     return G, score, score0, joint_score, used, accepted
 
 

@@ -13,7 +13,8 @@ is the [N,3] part around the first pair, PREFIX_piece_id.npy / PREFIX_row_id.npy
 point-to-point ICP, at most N accepted steps, one launch per table or per round); 0, the default, uses the network's poses.
 --joint N (the greedy walk only): after the walk all placed poses are refined together over every joint - every pair of
 placed pieces that scores no worse than the walk's worst edge - by at most N sweeps of assembly.refine_assembly (one launch);
-PREFIX_G.npy and PREFIX_cloud.npy are then the refined ones, and with --gt the assembly is scored before and after.
+PREFIX_G.npy and PREFIX_cloud.npy are then the refined ones, and with --gt the assembly is scored before and after.  With
+--keep auto every joint is refined over the rows its own pair kept (refine_assembly(..., kept="frozen"): a count per joint).
 --beam B (the table walk only, with --branch C and --vote-weight W): the beam walk of assembly.assemble_beam_batch in place of the
 greedy one - B hypotheses, each extended by its C smallest entries, a child charged W times what the other placed pieces'
 entries say against its pose -; everything after the walk is the same.
@@ -66,7 +67,7 @@ def forest(args, x, table):
     for q, r in enumerate(fb.roots[0, :nc].tolist()):
         print(f"component {q}: root piece {r}, pieces {[p for p, c in enumerate(comp) if c == q]}")
     if args.joint:
-        jr = assembly.refine_assembly_batch(x[None], one, fb, sweeps=args.joint)
+        jr = assembly.refine_assembly_batch(x[None], one, fb, sweeps=args.joint, kept="frozen" if args.keep == "auto" else None)
         G = jr.G[0].double()
         print(f"joint refinement over {int(fb.n_joints[0])} joints: summed score {float(jr.score0[0]):.6f} -> {float(jr.score[0]):.6f}, "
               f"{int(jr.sweeps_used[0])} sweeps, candidates taken per piece {jr.accepted[0].tolist()}")
@@ -94,7 +95,7 @@ def main():
     ap.add_argument("--refine", type=int, default=0, help="ICP steps at most per pair pose on the picked boundary points (0: none)")
     ap.add_argument("--keep", type=keep_arg, default=1.0, help="partial contact: the share of the picked boundary points of each side "
                     "that counts in a pair's score and refinement, those closest to the other side (1.0: all; not with --progressive), "
-                    "or the word auto: the share is found per pair on the device (not with --joint)")
+                    "or the word auto: the share is found per pair on the device (with --joint the kept sets are refined as the pair refinement left them: kept='frozen')")
     ap.add_argument("--joint", type=int, default=0, help="sweeps at most of the joint refinement after the greedy walk (0: none)")
     ap.add_argument("--gt", default=None, help="PREFIX_gt.npz of tools/fracture.py: score the assembly against the truth")
     ap.add_argument("--beam", type=int, default=0, help="B: the beam walk with B hypotheses in place of the greedy walk (1 .. 8; 0: greedy)")
@@ -110,9 +111,6 @@ def main():
         sys.exit("--refine: 0 or a number of steps")
     if (args.keep != "auto" and not 0.0 < args.keep <= 1.0) or (args.keep != 1.0 and args.progressive):
         sys.exit("--keep: a share in (0, 1] or the word auto, and 1.0 with --progressive (the progressive walk does not trim)")
-    if args.keep == "auto" and args.joint:
-        from puzzlenet_amd import assembly
-        sys.exit(f"--joint with --keep auto: {assembly.AUTO_JOINT_MESSAGE}")
     if args.joint < 0 or (args.joint and args.progressive):
         sys.exit("--joint: 0 or a number of sweeps, and for the greedy walk only (not with --progressive)")
 
@@ -187,7 +185,7 @@ def main():
         if gt is not None:
             print(f"against {args.gt} (in the root's frame), before the joint refinement:")
             report(assembly.evaluate(G, result.placed, gt["pose"], gt["rest"], result.root, result.edges, gt["mates"]))
-        jr = assembly.refine_assembly(x, table, result, sweeps=args.joint)
+        jr = assembly.refine_assembly(x, table, result, sweeps=args.joint, kept="frozen" if args.keep == "auto" else None)
         G = jr.G.double().cpu().numpy()
         print(f"joint refinement over {len(jr.joints)} joints: summed score {float(jr.score0):.6f} -> {float(jr.score):.6f}, "
               f"{int(jr.sweeps_used)} sweeps, candidates taken per piece {jr.accepted.tolist()}")

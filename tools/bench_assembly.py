@@ -25,7 +25,9 @@ many iterations as the LONGEST pair of the fused launch ran (iters_used max + 1:
 long as its longest problem); device time between two events around each call, alternated in one process; per-iteration
 figures and the library's launches beside them; (a') assembly.refine_assembly on the greedy walk over the same table and
 over its first 8 pieces' - the time of its one kernel, 30 sweeps at most, with the default joint set and with every ordered
-pair as a joint (there is nothing earlier to compare it with); (a'') the trimmed launch of refine_pairs at keep = 0.5 on the
+pair as a joint (there is nothing earlier to compare it with), and the K = 8 default-joints figure again on the keep = 0.5
+table and on the auto table (kept="frozen": joint_refine_counts_kernel, a count per joint; field joint_refine_counts_kernel_ms,
+with the joints' mean counts); (a'') the trimmed launch of refine_pairs at keep = 0.5 on the
 same boundaries and poses beside the untrimmed one - the time of each one's kernel per launch (the library's own event pair),
 each in a run of its own launches in one process; (a''') the auto launch (keep = "auto": the share found per pair on the
 device) the same way, with its ratio to the trimmed launch; and (b) match_pairs with refine = 30 against refine = 0 (host wall time around
@@ -292,6 +294,33 @@ def refine(args):
                                        "device_ms": _spread([_device_ms(run, 1) for _ in range(args.reps)]),
                                        "score_over_score0": float(jr.score / jr.score0)}
     print(json.dumps({"joint_refine_kernel_ms": joint}))
+    # the same K = 8 default-joints measurement on tables that carry kept sets, refined above from the same poses: the
+    # kept-fraction table (keep = 0.5: 64 rows a side, pzn_joint_refine_f32) and the auto table (a count per joint, sets of
+    # stride k, pzn_joint_refine_counts_f32 through kept="frozen"), with the mean counts of the joints' sets beside the time
+    joint_counts = {}
+    eye8 = torch.eye(8, dtype=torch.bool, device=dev)
+    for label, rr, kind, kept in (("keep_0.5", rt, assembly.TrimmedPairTable, None), ("keep_auto", ra, assembly.AutoPairTable, "frozen")):
+        extra = [getattr(rr, f)[:8, :8].contiguous() for f in kind._fields[8:]]
+        sub = kind(None, rr.T[:8, :8].contiguous(), None, None, table.top_f[:8, :8].contiguous(), table.top_m[:8].contiguous(),
+                   rr.score[:8, :8].masked_fill(eye8, float("inf")), None, *extra)
+        asm = assembly.assemble(sub.score, sub.T)
+        run = lambda: assembly.refine_assembly(pieces[:8], sub, asm, sweeps=ITERS, kept=kept)
+        for _ in range(args.warmup):
+            run()
+        ops.ktimer_start()
+        jr = run()
+        torch.cuda.synchronize()
+        k_j = ops.ktimer_stop()
+        ms = [v[1] for name, v in k_j.items() if "joint_refine" in name]      # (either kernel: the launch says which)
+        ji, jj = (torch.tensor(x, device=dev) for x in zip(*jr.joints))
+        cf = sub.count_f[ji, jj].float().mean() if kept else sub.kept_f.shape[-1]
+        cm = sub.count_m[ji, jj].float().mean() if kept else sub.kept_m.shape[-1]
+        joint_counts[f"K8_default_joints_{label}"] = {
+            "kernel": next((name for name in k_j if "joint_refine" in name), None), "joints": len(jr.joints),
+            "count_f_mean": float(cf), "count_m_mean": float(cm), "stride": sub.kept_f.shape[-1],
+            "sweeps_used": int(jr.sweeps_used), "kernel_ms": ms[0] if ms else None,
+            "device_ms": _spread([_device_ms(run, 1) for _ in range(args.reps)]), "score_over_score0": float(jr.score / jr.score0)}
+    print(json.dumps({"joint_refine_counts_kernel_ms": joint_counts}))
     off = ~torch.eye(K, dtype=torch.bool, device=dev)
     f_med, c_med, m_med = statistics.median(f_ms), statistics.median(c_ms), statistics.median(m_ms)
     result = {"tool": "tools/bench_assembly.py --refine", "device": torch.cuda.get_device_name(0), "dtype": "float32", "K": K,
@@ -308,6 +337,7 @@ def refine(args):
               "trimmed_launch": trim,
               "auto_launch": auto,
               "joint_refine_kernel_ms": joint,
+              "joint_refine_counts_kernel_ms": joint_counts,
               "iters_used_mean": float(r.iters_used.float().mean()), "iters_used_max": int(r.iters_used.max()),
               "score_over_score0_mean_off_diagonal": float((r.score[off] / r.score0[off]).mean()),
               "composition_fixed_score_over_score0_mean_off_diagonal": float((sc.view(K, K)[off] / r.score0[off]).mean())}

@@ -86,7 +86,7 @@ def sort_piles(args, model, f, dev):
         rows.append(row(asm.G, asm))
         extra = torch.zeros(3, dtype=torch.float64, device=dev)
         if args.joint:
-            jr = assembly.refine_assembly_batch(pile.pieces, table, asm, sweeps=args.joint)
+            jr = assembly.refine_assembly_batch(pile.pieces, table, asm, sweeps=args.joint, kept="frozen" if args.keep == "auto" else None)
             labels.append(f"{label.split(' (')[0]} after the joint refinement")
             rows.append(row(jr.G, asm))
             extra = torch.stack((jr.score0.double().mean(), jr.score.double().mean(), jr.sweeps_used.double().mean()))
@@ -128,7 +128,7 @@ def main():
     ap.add_argument("--refine", type=int, default=0, help="ICP steps at most per pair pose on the picked boundary points (0: none)")
     ap.add_argument("--keep", type=keep_arg, default=1.0, help="partial contact: the share of the picked boundary points of each side "
                     "that counts in a pair's score and refinement, those closest to the other side (1.0: all; the progressive "
-                    "walks do not trim), or the word auto: the share is found per pair on the device (not with --joint)")
+                    "walks do not trim), or the word auto: the share is found per pair on the device (with --joint the kept sets are refined as the pair refinement left them: kept='frozen')")
     ap.add_argument("--joint", type=int, default=0, help="sweeps at most of the joint refinement after the walk (0: none)")
     ap.add_argument("--max-score", type=float, default=None, help="stop placing pieces above this boundary distance")
     ap.add_argument("--progressive", action="store_true", help="also the progressive walk of the whole batch, in lockstep")
@@ -148,9 +148,6 @@ def main():
         sys.exit("--refine, --joint: 0 or a number of steps / sweeps")
     if args.keep != "auto" and not 0.0 < args.keep <= 1.0:
         sys.exit("--keep: a share in (0, 1] or the word auto")
-    if args.keep == "auto" and args.joint:
-        from puzzlenet_amd import assembly
-        sys.exit(f"--joint with --keep auto: {assembly.AUTO_JOINT_MESSAGE}")
     if args.time < 0 or (args.time and not args.progressive) or (args.json and not args.time):
         sys.exit("--time R >= 0 goes with --progressive, --json with --time")
     if args.beam and not (1 <= args.beam <= 8 and 1 <= args.branch <= 8 and args.vote_weight == args.vote_weight):
@@ -188,7 +185,7 @@ def main():
         rows = [metrics(assembly.evaluate_batch(asm.G, asm.placed, f.pose, f.rest, asm.root, asm.edges, asm.n_edges, f.mates), asm, f.ok)]
         extra = torch.zeros(3, dtype=torch.float64, device=dev)
         if args.joint:
-            jr = assembly.refine_assembly_batch(f.pieces, table, asm, sweeps=args.joint)
+            jr = assembly.refine_assembly_batch(f.pieces, table, asm, sweeps=args.joint, kept="frozen" if args.keep == "auto" else None)
             rows.append(metrics(assembly.evaluate_batch(jr.G, asm.placed, f.pose, f.rest, asm.root, asm.edges, asm.n_edges, f.mates),
                                 asm, f.ok))
             extra = torch.stack((jr.score0.double().mean(), jr.score.double().mean(), jr.sweeps_used.double().mean()))
@@ -204,7 +201,7 @@ def main():
                                               max_score=args.max_score)
             rows.append(metrics(assembly.evaluate_batch(bm.G, bm.placed, f.pose, f.rest, bm.root, bm.edges, bm.n_edges, f.mates), bm, f.ok))
             if args.joint:
-                bj = assembly.refine_assembly_batch(f.pieces, table, bm, sweeps=args.joint)
+                bj = assembly.refine_assembly_batch(f.pieces, table, bm, sweeps=args.joint, kept="frozen" if args.keep == "auto" else None)
                 rows.append(metrics(assembly.evaluate_batch(bj.G, bm.placed, f.pose, f.rest, bm.root, bm.edges, bm.n_edges, f.mates),
                                     bm, f.ok))
             same = (bm.edges == asm.edges).all(dim=2).all(dim=1).double().mean()
