@@ -133,6 +133,16 @@ class AutoKeep(collections.namedtuple("AutoKeep", "least power", defaults=(0.25,
 
 _AutoCounts = collections.namedtuple("_AutoCounts", "lo_f lo_m power")      # what _keep_counts makes of an AutoKeep
 
+# The three kinds of a refined pair, by what _keep_counts gives: None - no kept sets; counts (m_f, m_m) - kept sets; _AutoCounts -
+# kept sets with counts.  The types of a kind share their extra fields, in one order, behind the base fields.
+_Kind = collections.namedtuple("_Kind", "Refined PairBlock PairTable")
+_KINDS = (_Kind(Refined, PairBlock, PairTable), _Kind(TrimmedRefined, TrimmedPairBlock, TrimmedPairTable),
+          _Kind(AutoRefined, AutoPairBlock, AutoPairTable))
+
+
+def _kind_of(counts):
+    return _KINDS[0 if counts is None else 2 if isinstance(counts, _AutoCounts) else 1]
+
 ENCODER_ROWS = 64      # pieces per encoder call (the fused per-point stem takes up to 64 clouds)
 
 
@@ -277,19 +287,11 @@ def _refine_gathered(Bf, Bm, T, iters, keep=None):
     Z = T.numel() // (Kf * Km * 16)
     b_of = torch.arange(Z * Km, dtype=torch.long, device=T.device).view(Z, 1, Km).expand(Z, Kf, Km).reshape(-1)
     lead = T.shape[:-2]
-    if keep is None:
-        Tr, score, score0, used = ops.icp_refine(Bf, Bm, T.reshape(Z * Kf * Km, 4, 4), iters, b_of=b_of)
-        return Refined(Tr.view(*lead, 4, 4), score.view(lead), score0.view(lead), used.view(lead))
-    if isinstance(keep, _AutoCounts):
-        Tr, score, score0, used, count_f, count_m, objective, kept_f, kept_m = ops.icp_refine(
-            Bf, Bm, T.reshape(Z * Kf * Km, 4, 4), iters, b_of=b_of, auto=tuple(keep), return_kept=True)
-        return AutoRefined(Tr.view(*lead, 4, 4), score.view(lead), score0.view(lead), used.view(lead),
-                           kept_f.view(*lead, Bf.shape[1]), kept_m.view(*lead, Bm.shape[1]), count_f.view(lead), count_m.view(lead),
-                           objective.view(lead))
-    Tr, score, score0, used, kept_f, kept_m = ops.icp_refine(Bf, Bm, T.reshape(Z * Kf * Km, 4, 4), iters, b_of=b_of, keep=keep,
-                                                             return_kept=True)
-    return TrimmedRefined(Tr.view(*lead, 4, 4), score.view(lead), score0.view(lead), used.view(lead), kept_f.view(*lead, keep[0]),
-                          kept_m.view(*lead, keep[1]))
+    form = {} if keep is None else {"auto": tuple(keep)} if isinstance(keep, _AutoCounts) else {"keep": keep}
+    out = ops.icp_refine(Bf, Bm, T.reshape(Z * Kf * Km, 4, 4), iters, b_of=b_of, return_kept=keep is not None, **form)
+    # ops returns the counts and the objective before the kept sets, the tuples hold the kept sets first
+    out = out[:4] + out[-2:] + out[4:-2] if keep is not None else out
+    return _kind_of(keep).Refined(*(t.view(*lead, *t.shape[1:]) for t in out))
 
 
 def refine_pairs(pieces_f, top_f, pieces_m, top_m, T, iters=30, keep=1.0):
@@ -354,9 +356,8 @@ def _table(codes, blk, mask=None):
     score is masked already)."""
     score = blk.score if mask is None else blk.score.masked_fill(mask, float("inf"))
     fields = (blk.twist, blk.T, blk.de_fpcb, codes.de_mrpcb, blk.top_f, codes.top_m, score, codes.x2)
-    if isinstance(blk, AutoPairBlock):
-        return AutoPairTable(*fields, blk.kept_f, blk.kept_m, blk.count_f, blk.count_m, blk.objective)
-    return PairTable(*fields) if blk.kept_f is None else TrimmedPairTable(*fields, blk.kept_f, blk.kept_m)
+    kind = next(kind for kind in _KINDS if type(blk) is kind.PairBlock)
+    return kind.PairTable(*fields, *blk[len(PairBlock._fields):])
 
 
 def match_pairs(model, pieces, k=128, start=None, refine=0, keep=1.0):
@@ -478,6 +479,37 @@ def _kept_mode(kept, table, who):
         raise _lib.PznUnsupported(f"{who}: {AUTO_JOINT_MESSAGE}")
 
 
+def _joint_sets(pieces, table, z, i, j):
+    """The point sets of the ordered pairs (z[q], i[q], j[q]) (int64 [n], on the GPU; z may be one int for all of them) of
+    pieces [Z,P,N,3] and their table (leading Z), by ONE gather over the Z P N rows of all pieces -> (a [n,ka,3], b [.,kb,3],
+    b_of, na, nb) as ops.joint_refine takes them for rows that are those pairs in that order; b_of [n] (or None: b[q]) is
+    where pair q finds its moved-side set.
+      * no kept sets: a[q] = pieces[z,i][top_f[z,i,j]]; b holds one set per piece, top_m's, shared through b_of = z P + j;
+      * kept sets: the kept rows of the pair on both sides, one set per ordered pair, b_of None;
+      * an AutoPairTable: the same with stride k, the -1 padding clamped to 0 (it gathers row 0 of the set, never read) and
+        count_f / count_m of the pairs as na / nb (None otherwise)."""
+    Z, P, N, _ = pieces.shape
+    n, k = i.numel(), table.top_m.shape[-1]
+    fixed, moved = z * P + i, z * P + j      # the pieces of a pair among all Z P; piece p's rows begin at p N
+    top_f = table.top_f[z, i, j]
+    b_of = na = nb = None
+    if table.kept_f is None:
+        rows_a = (fixed * N)[:, None] + top_f
+        rows_b = torch.arange(Z * P, dtype=torch.long, device=pieces.device)[:, None] * N + table.top_m.reshape(Z * P, k)
+        b_of = moved
+    else:
+        kept_f, kept_m = table.kept_f[z, i, j].long(), table.kept_m[z, i, j].long()
+        if isinstance(table, AutoPairTable):
+            kept_f, kept_m = kept_f.clamp(min=0), kept_m.clamp(min=0)
+            na, nb = table.count_f[z, i, j].to(torch.int32), table.count_m[z, i, j].to(torch.int32)
+        rows_a = (fixed * N)[:, None] + top_f.gather(1, kept_f)
+        rows_b = (moved * N)[:, None] + table.top_m[z, j].gather(1, kept_m)
+    rows = torch.cat((rows_a.reshape(-1), rows_b.reshape(-1)))
+    picked = ops.index_points(pieces.contiguous().view(1, Z * P * N, 3), rows.reshape(1, -1))[0]
+    ka, kb = rows_a.shape[1], rows_b.shape[1]
+    return picked[:n * ka].view(n, ka, 3), picked[n * ka:].view(-1, kb, 3), b_of, na, nb
+
+
 def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None, kept=None):
     """Refine all placed poses of a greedy assembly jointly over every joint: pieces [K,N,3] (float32, on the GPU), table =
     match_pairs' PairTable of them, asm = assemble's Assembly of that table -> JointRefined:
@@ -528,29 +560,15 @@ def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None, kept=None):
         movable[int(asm.root)] = False
         mv = torch.from_numpy(movable.astype(np.uint8)).to(dev).reshape(1, K)
         jl = torch.tensor(joints, dtype=torch.int32).reshape(1, J, 2)
-        k = table.top_m.shape[1]
-        cnt_a = cnt_b = None
-        if J > 0:
+        if J > 0:      # exactly the J joints' sets, at Z = 1
             ji = torch.tensor([i for i, _ in joints], dtype=torch.long, device=dev)
             jj = torch.tensor([j for _, j in joints], dtype=torch.long, device=dev)
-            # one gather over the K N rows of all pieces: the J fixed-side sets, then one moved-side set per piece
-            if table.kept_f is None:
-                rows_a = (ji[:, None] * N + table.top_f[ji, jj]).reshape(-1)
-                rows_b = (torch.arange(K, device=dev)[:, None] * N + table.top_m).reshape(-1)
-                ka, nb, b_of = k, K, jj.reshape(1, J)
-            else:      # the kept rows of every joint: a moved-side set per ordered pair
-                kept_f, kept_m = table.kept_f[ji, jj].long(), table.kept_m[ji, jj].long()
-                if isinstance(table, AutoPairTable):      # count rows, then -1: a count per set, the padding never read
-                    kept_f, kept_m = kept_f.clamp(min=0), kept_m.clamp(min=0)
-                    cnt_a, cnt_b = table.count_f[ji, jj].to(torch.int32), table.count_m[ji, jj].to(torch.int32)
-                rows_a = (ji[:, None] * N + table.top_f[ji, jj].gather(1, kept_f)).reshape(-1)
-                rows_b = (jj[:, None] * N + table.top_m[jj].gather(1, kept_m)).reshape(-1)
-                ka, nb, b_of = table.kept_f.shape[-1], J, None
-            picked = ops.index_points(pieces.contiguous().view(1, K * N, 3), torch.cat((rows_a, rows_b)).reshape(1, -1))[0]
-            a, b = picked[:J * ka].view(J, ka, 3), picked[J * ka:].view(nb, -1, 3)
+            one = type(table)(*(None if f is None else f[None] for f in table))      # (a caller's table may leave fields out)
+            a, b, b_of, cnt_a, cnt_b = _joint_sets(pieces[None], one, 0, ji, jj)
+            b_of = None if b_of is None else b_of.reshape(1, J)
         else:
-            a = b = pieces[:0, :k]
-            b_of = None
+            a = b = pieces[:0, :table.top_m.shape[1]]
+            b_of = cnt_a = cnt_b = None
         G, score, score0, _, used, accepted = ops.joint_refine(a, b, jl, g0, mv, sweeps, b_of=b_of, na=cnt_a, nb=cnt_b)
     return JointRefined(G[0], score[0], score0[0], used[0], accepted[0], joints)
 
@@ -1272,15 +1290,9 @@ def pair_block_batch(model, pieces_f, codes_f, pieces_m, codes_m, k=128, refine=
         # pieces_f[z,i][top_f[z,i,j]] per pair, pieces_m[z,j][top_m[z,j]] per moved piece
         Bf = ops.index_points(pieces_f.reshape(Z * Kf, N, 3), top_f.reshape(Z * Kf, Km * k)).view(Z * Kf * Km, k, 3)
         Bm = ops.index_points(pieces_m.reshape(Z * Km, N, 3), codes_m.top_m.reshape(Z * Km, -1))
-        if isinstance(counts, _AutoCounts):      # the share found per pair: the auto launch, with no step at refine = 0
-            r = _refine_gathered(Bf, Bm, T.contiguous(), refine, counts)
-            return AutoPairBlock(twist, r.T, de_fpcb, top_f, r.score, r.kept_f, r.kept_m, r.count_f, r.count_m, r.objective)
-        if counts is not None:      # partial contact: the trimmed launch, with no step at refine = 0
-            r = _refine_gathered(Bf, Bm, T.contiguous(), refine, counts)
-            return TrimmedPairBlock(twist, r.T, de_fpcb, top_f, r.score, r.kept_f, r.kept_m)
-        if refine > 0:
-            r = _refine_gathered(Bf, Bm, T, refine)
-            return PairBlock(twist, r.T, de_fpcb, top_f, r.score)
+        if counts is not None or refine > 0:      # one refinement launch of counts' kind (trimmed and auto: no step at refine = 0)
+            r = _refine_gathered(Bf, Bm, T, refine, counts)
+            return _kind_of(counts).PairBlock(twist, r.T, de_fpcb, top_f, r.score, *r[len(Refined._fields):])
         Bm = Bm.view(Z, 1, Km, -1, 3).expand(Z, Kf, Km, -1, 3).reshape(Z * Kf * Km, -1, 3)
         d1, d2 = ops.chamfer(Bf, se3.transform_points(T.reshape(Z * Kf * Km, 4, 4), Bm))
         score = (d1.mean(dim=1) + d2.mean(dim=1)).view(Z, Kf, Km)
@@ -1352,30 +1364,14 @@ def refine_assembly_batch(pieces, table, asm, sweeps=30, kept=None):
                             f"joints {tuple(asm.joints.shape)}")
     dev = pieces.device
     with torch.no_grad():
-        k = table.top_m.shape[2]
-        cnt_a = cnt_b = None
-        piece_row = torch.arange(Z * P, dtype=torch.long, device=dev).view(Z, P) * N                     # first row of piece (z, p)
         ji, jj = asm.joints[..., 0].long(), asm.joints[..., 1].long()
-        used = ji >= 0
         first = torch.arange(Z, dtype=torch.long, device=dev)[:, None]
-        a_of = torch.where(used, (first * P + ji) * P + jj, torch.zeros_like(ji))
-        if table.kept_f is None:
-            rows_a = (piece_row[:, :, None, None] + table.top_f).reshape(-1)                            # [Z,P,P,k]
-            rows_b = (piece_row[:, :, None] + table.top_m).reshape(-1)                                  # [Z,P,k]
-            ka, nb = k, Z * P
-            b_of = torch.where(used, first * P + jj, torch.zeros_like(jj))
-        else:      # the kept rows of every ordered pair, on both sides
-            kept_f, kept_m = table.kept_f.long(), table.kept_m.long()
-            if isinstance(table, AutoPairTable):      # count rows, then -1: a count per set, the padding never read
-                kept_f, kept_m = kept_f.clamp(min=0), kept_m.clamp(min=0)
-                cnt_a, cnt_b = table.count_f.reshape(-1).to(torch.int32), table.count_m.reshape(-1).to(torch.int32)
-            rows_a = (piece_row[:, :, None, None] + table.top_f.gather(3, kept_f)).reshape(-1)                    # [Z,P,P,m_f]
-            top_m = table.top_m[:, None].expand(Z, P, P, k)
-            rows_b = (piece_row[:, None, :, None] + top_m.gather(3, kept_m)).reshape(-1)                          # [Z,P,P,m_m]
-            ka, nb = table.kept_f.shape[-1], Z * P * P
-            b_of = a_of
-        picked = ops.index_points(pieces.contiguous().view(1, Z * P * N, 3), torch.cat((rows_a, rows_b)).reshape(1, -1))[0]
-        a, b = picked[:Z * P * P * ka].view(Z * P * P, ka, 3), picked[Z * P * P * ka:].view(nb, -1, 3)
+        a_of = torch.where(ji >= 0, (first * P + ji) * P + jj, torch.zeros_like(ji))
+        # the sets of all Z P^2 ordered pairs in row-major order: a joint row finds its pair, and through it its sets, by a_of
+        z, i, j = (t.reshape(-1) for t in torch.meshgrid(*(torch.arange(n, dtype=torch.long, device=dev) for n in (Z, P, P)),
+                                                         indexing="ij"))
+        a, b, b_of, cnt_a, cnt_b = _joint_sets(pieces, table, z, i, j)
+        b_of = a_of if b_of is None else b_of[a_of]
         G, score, score0, _, used_sweeps, accepted = ops.joint_refine(a, b, asm.joints, asm.G.to(torch.float32), asm.movable, sweeps,
                                                                       a_of=a_of, b_of=b_of, na=cnt_a, nb=cnt_b)
     return JointRefined(G, score, score0, used_sweeps, accepted, asm.joints)

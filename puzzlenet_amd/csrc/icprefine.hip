@@ -19,9 +19,7 @@
 //     to fp32.  E(T') < E(T) takes the candidate, anything else (NaN included) stops and keeps T: the only stop rule besides
 //     iters;
 //   * DEGENERATE correspondences (a single point, all moved-side points q coincident or collinear) keep the current R and
-//     update t only.  The rule, stated once: with C's trace tr and the sum of its three principal 2x2 minors m2
-//     (= l1 l2 + l1 l3 + l2 l3 for eigenvalues l), degenerate iff m2 <= ICP_DEGENERATE * tr * tr, ICP_DEGENERATE = 1e-10
-//     (m2 / tr^2 is about l2 / l1 for a thin set; points exactly on a line, rounded to fp32, sit near 1e-14).
+//     update t only: the rule is stated, with the solve, at solve_pose in pzn_rigid.h.
 // Latency-bound: per iteration a serial chain of six barriers, a (ka | kb)-step scan and one lane's float64 solve; the
 // launch is parallel over problems only, and the grid walks when P exceeds ICP_MAX_GRID.
 //
@@ -46,7 +44,7 @@
 // masks are written from the ranks in registers and the kept minima summed exactly as the trimmed form sums them.  The loop
 // compares F = e_a (ka / m_a)^p + e_b (kb / m_b)^p where the other two compare E; counts, like masks, belong to a pose.
 // The other two instantiations compile to the instructions they had (every addition stands under if constexpr (AUTO)).
-#include "pzn_rigid.h"      // the wave sums, horn_rotation, Pose / pose_move: shared with jointrefine.hip
+#include "pzn_rigid.h"      // the wave and workgroup sums, solve_pose, Pose / pose_move: shared with jointrefine.hip
 
 namespace {
 
@@ -256,13 +254,8 @@ __device__ float evaluate(const Lds& L, const Pose& g, int ka, int kb, int ma, i
       }
     }
   }
-  s1 = wave_sum_f32_dpp(s1);
-  s2 = wave_sum_f32_dpp(s2);
-  if ((tid & (PZN_WAVE - 1)) == 0) L.rede[2 * (tid / PZN_WAVE)] = s1, L.rede[2 * (tid / PZN_WAVE) + 1] = s2;
-  __syncthreads();
-  float e1 = L.rede[0], e2 = L.rede[1];
-#pragma unroll
-  for (int w = 1; w < ICP_W; ++w) e1 = __fadd_rn(e1, L.rede[2 * w]), e2 = __fadd_rn(e2, L.rede[2 * w + 1]);
+  float e1, e2;
+  block_sum2_f32<ICP_W>(L.rede, tid, s1, s2, e1, e2);
   const float ea = __fdiv_rn(e1, (float)(TRIM ? ma : ka)), eb = __fdiv_rn(e2, (float)(TRIM ? mb : kb));
   const float e = __fadd_rn(ea, eb);
   if constexpr (AUTO) {
@@ -336,21 +329,10 @@ __device__ Pose candidate(const Lds& L, const Pose& cur, int ka, int kb, int npa
       for (int w = 1; w < ICP_W; ++w) v += L.redd[15 * w + k];
       m[k] = v;
     }
-    const double tr = m[9] + m[10] + m[11];
-    const double m2 = (m[9] * m[10] - m[12] * m[12]) + (m[9] * m[11] - m[13] * m[13]) + (m[10] * m[11] - m[14] * m[14]);
-    double R[9];
-    if (m2 <= ICP_DEGENERATE * tr * tr) {
-#pragma unroll
-      for (int k = 0; k < 9; ++k) R[k] = (double)cur.r[k];
-    } else {
-      const double S[3][3] = {{m[0], m[1], m[2]}, {m[3], m[4], m[5]}, {m[6], m[7], m[8]}};
-      horn_rotation(S, R);
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) L.cand[k] = (float)R[k];
-#pragma unroll
-    for (int u = 0; u < 3; ++u)
-      L.cand[9 + u] = (float)(cen[u] - ((R[3 * u] * cen[3] + R[3 * u + 1] * cen[4]) + R[3 * u + 2] * cen[5]));
+    const double S[3][3] = {{m[0], m[1], m[2]}, {m[3], m[4], m[5]}, {m[6], m[7], m[8]}};
+    const double C[6] = {m[9], m[10], m[11], m[12], m[13], m[14]};
+    const double pc[3] = {cen[0], cen[1], cen[2]}, qc[3] = {cen[3], cen[4], cen[5]};
+    solve_pose(S, C, cur, pc, qc, L.cand);
   }
   __syncthreads();
   Pose out;
@@ -512,10 +494,27 @@ __global__ __launch_bounds__(ICP_T) void icp_kernel(ICP_PARAMS, Args trim) {
 
 // Bytes of LDS of a launch: reduction slots, the three point images, the arg-mins; trimmed: the row minima and two masks;
 // automatic: the sorted minima too.
-size_t icp_lds_bytes(int ka, int kb, bool trim, bool automatic = false) {
+size_t icp_lds_bytes(int ka, int kb, bool trim, bool automatic) {
   const size_t rows = (size_t)ka + (size_t)kb;
   return ICP_W * 15 * sizeof(double) + (ICP_W * 2 + 12) * sizeof(float) + 3 * ((size_t)ka + 2 * (size_t)kb) * sizeof(float) +
          rows * sizeof(unsigned short) + (trim ? rows * sizeof(float) + 2 * rows : 0) + (automatic ? rows * sizeof(float) : 0);
+}
+
+// The one launch of the three forms: `supported` is the form's own pzn_*_supported answer, `extra` what the form must have
+// beside the common outputs.
+template <typename Args>
+int icp_launch(bool supported, bool extra, const float* a, const int64_t* a_of, const float* b, const int64_t* b_of,
+               const float* T0, int P, int ka, int kb, int iters, float* T, float* score, float* score0, int32_t* iters_used,
+               int32_t* corr_a, int32_t* corr_b, const Args& args, pzn_stream_t stream) {
+  if (!supported || iters < 0) return PZN_EUNSUPPORTED;
+  PZN_CHECK_ARG(P >= 0);
+  if (P == 0) return PZN_OK;
+  PZN_CHECK_ARG(a && b && T0 && T && score && score0 && iters_used && extra);
+  hipStream_t st = pzn_hip_stream(stream);
+  const int grid = P < ICP_MAX_GRID ? P : ICP_MAX_GRID;
+  PZN_LAUNCH(icp_kernel<Args>, dim3(grid), dim3(ICP_T), icp_lds_bytes(ka, kb, Args::TRIM, Args::AUTO), st, a, a_of, b, b_of, T0,
+             P, ka, kb, iters, T, score, score0, iters_used, corr_a, corr_b, args);
+  PZN_RETURN_LAUNCH_STATUS();
 }
 
 }  // namespace
@@ -525,15 +524,8 @@ PZN_EXPORT int pzn_icp_refine_supported(int ka, int kb) { return ka >= 1 && kb >
 PZN_EXPORT int pzn_icp_refine_f32(const float* a, const int64_t* a_of, const float* b, const int64_t* b_of, const float* T0,
                                   int P, int ka, int kb, int iters, float* T, float* score, float* score0,
                                   int32_t* iters_used, int32_t* corr_a, int32_t* corr_b, pzn_stream_t stream) {
-  if (!pzn_icp_refine_supported(ka, kb) || iters < 0) return PZN_EUNSUPPORTED;
-  PZN_CHECK_ARG(P >= 0);
-  if (P == 0) return PZN_OK;
-  PZN_CHECK_ARG(a && b && T0 && T && score && score0 && iters_used);
-  hipStream_t st = pzn_hip_stream(stream);
-  const int grid = P < ICP_MAX_GRID ? P : ICP_MAX_GRID;
-  PZN_LAUNCH(icp_kernel<icp_refine_kernel_args>, dim3(grid), dim3(ICP_T), icp_lds_bytes(ka, kb, false), st, a, a_of, b, b_of, T0, P, ka, kb, iters,
-             T, score, score0, iters_used, corr_a, corr_b, icp_refine_kernel_args{});
-  PZN_RETURN_LAUNCH_STATUS();
+  return icp_launch(pzn_icp_refine_supported(ka, kb), true, a, a_of, b, b_of, T0, P, ka, kb, iters, T, score, score0, iters_used,
+                    corr_a, corr_b, icp_refine_kernel_args{}, stream);
 }
 
 PZN_EXPORT int pzn_icp_refine_trim_supported(int ka, int kb, int keep_a, int keep_b) {
@@ -544,15 +536,8 @@ PZN_EXPORT int pzn_icp_refine_trim_f32(const float* a, const int64_t* a_of, cons
                                        int P, int ka, int kb, int keep_a, int keep_b, int iters, float* T, float* score,
                                        float* score0, int32_t* iters_used, int32_t* corr_a, int32_t* corr_b, int32_t* kept_a,
                                        int32_t* kept_b, pzn_stream_t stream) {
-  if (!pzn_icp_refine_trim_supported(ka, kb, keep_a, keep_b) || iters < 0) return PZN_EUNSUPPORTED;
-  PZN_CHECK_ARG(P >= 0);
-  if (P == 0) return PZN_OK;
-  PZN_CHECK_ARG(a && b && T0 && T && score && score0 && iters_used);
-  hipStream_t st = pzn_hip_stream(stream);
-  const int grid = P < ICP_MAX_GRID ? P : ICP_MAX_GRID;
-  PZN_LAUNCH(icp_kernel<icp_trim_kernel_args>, dim3(grid), dim3(ICP_T), icp_lds_bytes(ka, kb, true), st, a, a_of, b, b_of, T0, P, ka, kb, iters, T,
-             score, score0, iters_used, corr_a, corr_b, icp_trim_kernel_args{keep_a, keep_b, kept_a, kept_b});
-  PZN_RETURN_LAUNCH_STATUS();
+  return icp_launch(pzn_icp_refine_trim_supported(ka, kb, keep_a, keep_b), true, a, a_of, b, b_of, T0, P, ka, kb, iters, T, score,
+                    score0, iters_used, corr_a, corr_b, icp_trim_kernel_args{keep_a, keep_b, kept_a, kept_b}, stream);
 }
 
 PZN_EXPORT int pzn_icp_refine_auto_supported(int ka, int kb, int lo_a, int lo_b, int power) {
@@ -563,14 +548,7 @@ PZN_EXPORT int pzn_icp_refine_auto_f32(const float* a, const int64_t* a_of, cons
                                        int P, int ka, int kb, int lo_a, int lo_b, int power, int iters, float* T, float* score,
                                        float* score0, int32_t* iters_used, int32_t* corr_a, int32_t* corr_b, int32_t* count_a,
                                        int32_t* count_b, float* objective, int32_t* kept_a, int32_t* kept_b, pzn_stream_t stream) {
-  if (!pzn_icp_refine_auto_supported(ka, kb, lo_a, lo_b, power) || iters < 0) return PZN_EUNSUPPORTED;
-  PZN_CHECK_ARG(P >= 0);
-  if (P == 0) return PZN_OK;
-  PZN_CHECK_ARG(a && b && T0 && T && score && score0 && iters_used && count_a && count_b && objective);
-  hipStream_t st = pzn_hip_stream(stream);
-  const int grid = P < ICP_MAX_GRID ? P : ICP_MAX_GRID;
-  PZN_LAUNCH(icp_kernel<icp_auto_kernel_args>, dim3(grid), dim3(ICP_T), icp_lds_bytes(ka, kb, true, true), st, a, a_of, b, b_of, T0, P, ka, kb,
-             iters, T, score, score0, iters_used, corr_a, corr_b,
-             icp_auto_kernel_args{lo_a, lo_b, kept_a, kept_b, power, count_a, count_b, objective});
-  PZN_RETURN_LAUNCH_STATUS();
+  return icp_launch(pzn_icp_refine_auto_supported(ka, kb, lo_a, lo_b, power), count_a && count_b && objective, a, a_of, b, b_of,
+                    T0, P, ka, kb, iters, T, score, score0, iters_used, corr_a, corr_b,
+                    icp_auto_kernel_args{lo_a, lo_b, kept_a, kept_b, power, count_a, count_b, objective}, stream);
 }

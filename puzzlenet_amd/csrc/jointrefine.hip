@@ -14,7 +14,7 @@
 //     of w x x^T, of x - x0 and y - y0 (x0 = point 0 of p's side of its first joint, y0 = its image: a shift the centred
 //     sums do not depend on, which keeps them well conditioned far from the origin); thread, butterfly, wave order.  Thread 0
 //     centres them and solves in float64: Horn's quaternion on S = sum w (x - xc)(y - yc)^T, t = yc - R xc, rounded to fp32;
-//     a degenerate scatter of x (icprefine.hip's rule) keeps R_p.  The candidate is evaluated on the same joints and taken
+//     a degenerate scatter of x keeps R_p (solve_pose in pzn_rigid.h).  The candidate is evaluated on the same joints and taken
 //     iff E_p' < E_p (NaN rejects); only p's joints depend on G_p, so no visit raises the total - and the fp32 total, the
 //     sum over all rows in list order of the current E_e (kept in LDS), is held to that as well: a candidate under which it
 //     would round above the current total is left.  score and joint_score are that total and those E_e;
@@ -165,13 +165,8 @@ __device__ float eval_joint(const Lds& L, const Sets& S, size_t row, int ka, int
       acc[19] += wx0 * x1, acc[20] += wx0 * x2, acc[21] += wx1 * x2;
     }
   }
-  s1 = wave_sum_f32_dpp(s1);
-  s2 = wave_sum_f32_dpp(s2);
-  if ((tid & (PZN_WAVE - 1)) == 0) L.rede[2 * (tid / PZN_WAVE)] = s1, L.rede[2 * (tid / PZN_WAVE) + 1] = s2;
-  __syncthreads();
-  float e1 = L.rede[0], e2 = L.rede[1];
-#pragma unroll
-  for (int w = 1; w < JR_W; ++w) e1 = __fadd_rn(e1, L.rede[2 * w]), e2 = __fadd_rn(e2, L.rede[2 * w + 1]);
+  float e1, e2;
+  block_sum2_f32<JR_W>(L.rede, tid, s1, s2, e1, e2);
   const float e = __fadd_rn(__fdiv_rn(e1, (float)ka), __fdiv_rn(e2, (float)kb));
   __syncthreads();      // rede and the images are free again
   return e;
@@ -202,23 +197,11 @@ __device__ Pose candidate(const Lds& L, const Pose& cur, double (&acc)[JR_SUMS],
     const double S[3][3] = {{m[7] - m[1] * yc[0], m[8] - m[1] * yc[1], m[9] - m[1] * yc[2]},
                             {m[10] - m[2] * yc[0], m[11] - m[2] * yc[1], m[12] - m[2] * yc[2]},
                             {m[13] - m[3] * yc[0], m[14] - m[3] * yc[1], m[15] - m[3] * yc[2]}};
-    const double c00 = m[16] - m[1] * xc[0], c11 = m[17] - m[2] * xc[1], c22 = m[18] - m[3] * xc[2];
-    const double c01 = m[19] - m[1] * xc[1], c02 = m[20] - m[1] * xc[2], c12 = m[21] - m[2] * xc[2];
-    const double tr = c00 + c11 + c22;
-    const double m2 = (c00 * c11 - c01 * c01) + (c00 * c22 - c02 * c02) + (c11 * c22 - c12 * c12);
-    double R[9];
-    if (m2 <= ICP_DEGENERATE * tr * tr) {
-#pragma unroll
-      for (int k = 0; k < 9; ++k) R[k] = (double)cur.r[k];
-    } else {
-      horn_rotation(S, R);
-    }
+    const double C[6] = {m[16] - m[1] * xc[0], m[17] - m[2] * xc[1], m[18] - m[3] * xc[2],
+                         m[19] - m[1] * xc[1], m[20] - m[1] * xc[2], m[21] - m[2] * xc[2]};
     const double px[3] = {(double)ref[0] + xc[0], (double)ref[1] + xc[1], (double)ref[2] + xc[2]};
     const double py[3] = {(double)ref[3] + yc[0], (double)ref[4] + yc[1], (double)ref[5] + yc[2]};
-#pragma unroll
-    for (int k = 0; k < 9; ++k) L.cand[k] = (float)R[k];
-#pragma unroll
-    for (int u = 0; u < 3; ++u) L.cand[9 + u] = (float)(py[u] - ((R[3 * u] * px[0] + R[3 * u + 1] * px[1]) + R[3 * u + 2] * px[2]));
+    solve_pose(S, C, cur, py, px, L.cand);
   }
   __syncthreads();
   return load_pose(L.cand);      // (cand is written next after the barriers of the evaluations that follow)

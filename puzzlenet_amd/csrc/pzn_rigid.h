@@ -1,6 +1,7 @@
 // pzn_rigid.h — the arithmetic the pose refinement kernels share (icprefine.hip, jointrefine.hip): a pose as fp32 values
-// and how it moves a point, the two order-fixed wave sums, and Horn's closed-form rotation in float64.  One statement of
-// each, so a pose refined by one kernel moves points to the same bits in the other (and in mergefps.hip).
+// and how it moves a point, the two order-fixed wave sums, the workgroup sum of the two objective halves, Horn's closed-form
+// rotation in float64 and the one lane's solve with its degenerate rule.  One statement of each, so a pose refined by one
+// kernel moves points to the same bits in the other (and in mergefps.hip).
 #ifndef PZN_RIGID_H_
 #define PZN_RIGID_H_
 
@@ -9,7 +10,7 @@
 namespace {
 
 constexpr int ICP_SWEEPS = 12;             // cyclic Jacobi sweeps at most (a 4x4 converges in 5 to 7)
-constexpr double ICP_DEGENERATE = 1e-10;   // degenerate iff m2 <= ICP_DEGENERATE * tr * tr (icprefine.hip states the rule)
+constexpr double ICP_DEGENERATE = 1e-10;   // degenerate iff m2 <= ICP_DEGENERATE * tr * tr (solve_pose states the rule)
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
   uint64_t u;
@@ -30,6 +31,20 @@ __device__ __forceinline__ float wave_sum_f32_dpp(float v) {
   v = __fadd_rn(v, __uint_as_float(pzn::xor_lane<16>(__float_as_uint(v))));
   v = __fadd_rn(v, __uint_as_float(pzn::xor_lane<32>(__float_as_uint(v))));
   return v;
+}
+
+// The workgroup sum of the two objective halves, the same bits in every thread: the wave adds its lanes by the xor butterfly
+// (both partners form the same sum), lane 0 leaves the wave's two sums in rede [W][2], a barrier, the W wave sums are added
+// in wave order -> e1, e2.  The caller's next barrier frees rede.
+template <int W>
+__device__ __forceinline__ void block_sum2_f32(float* rede, int tid, float s1, float s2, float& e1, float& e2) {
+  s1 = wave_sum_f32_dpp(s1);
+  s2 = wave_sum_f32_dpp(s2);
+  if ((tid & (PZN_WAVE - 1)) == 0) rede[2 * (tid / PZN_WAVE)] = s1, rede[2 * (tid / PZN_WAVE) + 1] = s2;
+  __syncthreads();
+  e1 = rede[0], e2 = rede[1];
+#pragma unroll
+  for (int w = 1; w < W; ++w) e1 = __fadd_rn(e1, rede[2 * w]), e2 = __fadd_rn(e2, rede[2 * w + 1]);
 }
 
 // One Jacobi rotation of the symmetric 4x4 A in the (P, Q) plane, accumulated into V (columns = eigenvectors).
@@ -114,6 +129,30 @@ __device__ __forceinline__ void pose_move(const Pose& g, float x, float y, float
   ox = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(g.r[0], x), __fmul_rn(g.r[1], y)), __fmul_rn(g.r[2], z)), g.t[0]);
   oy = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(g.r[3], x), __fmul_rn(g.r[4], y)), __fmul_rn(g.r[5], z)), g.t[1]);
   oz = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(g.r[6], x), __fmul_rn(g.r[7], y)), __fmul_rn(g.r[8], z)), g.t[2]);
+}
+
+// One lane's solve in float64, from the centred cross-covariance S[u][v] = sum q_u p_v (fixed p, moved q), the scatter
+// sum q q^T of the moved side as c = its entries 00 11 22 01 02 12, the centroids pc, qc and the current pose -> the
+// candidate in cand [12]: R (Horn) and t = pc - R qc, each rounded to fp32.
+// DEGENERATE pairs (a single point, all moved-side points q coincident or collinear) keep the current R and update t only.
+// The rule, stated once: with the scatter's trace tr and the sum of its three principal 2x2 minors m2 (= l1 l2 + l1 l3 +
+// l2 l3 for eigenvalues l), degenerate iff m2 <= ICP_DEGENERATE * tr * tr, ICP_DEGENERATE = 1e-10 (m2 / tr^2 is about
+// l2 / l1 for a thin set; points exactly on a line, rounded to fp32, sit near 1e-14).
+__device__ __forceinline__ void solve_pose(const double (&S)[3][3], const double (&c)[6], const Pose& cur, const double (&pc)[3],
+                                           const double (&qc)[3], float* cand) {
+  const double tr = c[0] + c[1] + c[2];
+  const double m2 = (c[0] * c[1] - c[3] * c[3]) + (c[0] * c[2] - c[4] * c[4]) + (c[1] * c[2] - c[5] * c[5]);
+  double R[9];
+  if (m2 <= ICP_DEGENERATE * tr * tr) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = (double)cur.r[k];
+  } else {
+    horn_rotation(S, R);
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) cand[k] = (float)R[k];
+#pragma unroll
+  for (int u = 0; u < 3; ++u) cand[9 + u] = (float)(pc[u] - ((R[3 * u] * qc[0] + R[3 * u + 1] * qc[1]) + R[3 * u + 2] * qc[2]));
 }
 
 }  // namespace

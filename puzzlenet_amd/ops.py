@@ -228,6 +228,33 @@ def merge_resample(a, b, T, start, n_out=None, drop_a=None, drop_b=None):
     return out, src
 
 
+def _no_conversion(who, specs):
+    """specs: (name, value, accepted dtypes).  A tensor of another dtype is refused, not converted: a pose refined in another
+    precision, or an index read as another width, is not what the caller asked for."""
+    for name, t, dts in specs:
+        if isinstance(t, torch.Tensor) and t.dtype not in dts:
+            raise _lib.PznError(f"{who}: {name} must be {' or '.join(str(d) for d in dts)}; got {t.dtype}")
+
+
+def _set_maps(who, n_rows, shape, a_of, a, b_of, b):
+    """The set maps of a refinement launch of n_rows rows (poses [P], or joint rows [Z,J]: `shape`): a map is int64 of that
+    shape into a non-empty a / b; without one, a / b hold n_rows sets.  -> (a_of, b_of), contiguous or None."""
+    what = f"P = {n_rows} poses" if len(shape) == 1 else f"Z J = {n_rows} joint rows"
+    maps = []
+    for name, m, x in (("a_of", a_of, a), ("b_of", b_of, b)):
+        if m is None:
+            if x.shape[0] != n_rows:
+                raise _lib.PznError(f"{who}: {name[0]} holds {x.shape[0]} sets for {what} and no {name} is given")
+        else:
+            m = _i64(m, name)
+            if m.shape != tuple(shape):
+                raise _lib.PznError(f"{who}: expected {name}[{','.join(str(n) for n in shape)}]; got {tuple(m.shape)}")
+            if x.shape[0] == 0 and n_rows > 0:
+                raise _lib.PznError(f"{who}: {name} indexes an empty {name[0]}")
+        maps.append(m)
+    return maps
+
+
 def icp_refine_supported(ka, kb):
     return bool(_lib.load().pzn_icp_refine_supported(int(ka), int(kb)))
 
@@ -260,28 +287,15 @@ def icp_refine(a, b, T0, iters, a_of=None, b_of=None, return_corr=False, keep=No
     iters_used[, corr_a, corr_b], count_a [P] int32, count_b [P] int32, objective [P]) and with return_kept kept_a [P,ka],
     kept_b [P,kb] (int32): the kept rows ascending, then -1.  score is the trimmed E at the returned pose's counts and may
     exceed score0; objective never exceeds the F of T0.  auto = (ka, kb, p) is keep = (ka, kb) bit for bit."""
-    for name, t, dt in (("a", a, torch.float32), ("b", b, torch.float32), ("T0", T0, torch.float32), ("a_of", a_of, torch.int64),
-                        ("b_of", b_of, torch.int64)):
-        if isinstance(t, torch.Tensor) and t.dtype != dt:      # (no silent conversion: a pose refined in another precision)
-            raise _lib.PznError(f"icp_refine: {name} must be {dt}; got {t.dtype}")
+    f32, i64 = (torch.float32,), (torch.int64,)
+    _no_conversion("icp_refine", (("a", a, f32), ("b", b, f32), ("T0", T0, f32), ("a_of", a_of, i64), ("b_of", b_of, i64)))
     a, b, T0 = _f32(a, "a"), _f32(b, "b"), _f32(T0, "T0")
     if a.dim() != 3 or b.dim() != 3 or a.shape[2] != 3 or b.shape[2] != 3:
         raise _lib.PznError(f"icp_refine: expected a[.,ka,3], b[.,kb,3]; got {tuple(a.shape)}, {tuple(b.shape)}")
     if T0.dim() != 3 or T0.shape[1:] != (4, 4):
         raise _lib.PznError(f"icp_refine: expected T0[P,4,4]; got {tuple(T0.shape)}")
     P, ka, kb = T0.shape[0], a.shape[1], b.shape[1]
-    maps = []
-    for name, m, x in (("a_of", a_of, a), ("b_of", b_of, b)):
-        if m is None:
-            if x.shape[0] != P:
-                raise _lib.PznError(f"icp_refine: {name[0]} holds {x.shape[0]} sets for P = {P} poses and no {name} is given")
-        else:
-            m = _i64(m, name)
-            if m.shape != (P,):
-                raise _lib.PznError(f"icp_refine: expected {name}[{P}]; got {tuple(m.shape)}")
-            if x.shape[0] == 0 and P > 0:
-                raise _lib.PznError(f"icp_refine: {name} indexes an empty {name[0]}")
-        maps.append(m)
+    maps = _set_maps("icp_refine", P, (P,), a_of, a, b_of, b)
     iters = int(iters)
     if iters < 0 or not icp_refine_supported(ka, kb):
         raise _lib.PznUnsupported(f"icp_refine: ka = {ka}, kb = {kb}, iters = {iters} (1 <= ka, kb <= 1024, iters >= 0)")
@@ -298,36 +312,30 @@ def icp_refine(a, b, T0, iters, a_of=None, b_of=None, return_corr=False, keep=No
         if not icp_refine_auto_supported(ka, kb, *auto):
             raise _lib.PznUnsupported(f"icp_refine: auto = {tuple(auto)} of ka = {ka}, kb = {kb} rows (1 <= lo_a <= ka, 1 <= lo_b <= kb, "
                                       "1 <= power <= 4)")
-    dev = a.device
-    T = torch.empty((P, 4, 4), dtype=torch.float32, device=dev)
-    score = torch.empty((P,), dtype=torch.float32, device=dev)
-    score0 = torch.empty_like(score)
-    used = torch.empty((P,), dtype=torch.int32, device=dev)
-    ca = torch.empty((P, ka), dtype=torch.int32, device=dev) if return_corr else None
-    cb = torch.empty((P, kb), dtype=torch.int32, device=dev) if return_corr else None
-    kept = found = ()
+    # the form, resolved once: the entry point, its integer arguments before iters and the widths of the kept sets it can
+    # write (None: it writes none, and return_kept answers 0 .. k-1); the auto form alone finds counts and an objective
     if auto is not None:
-        found = (torch.empty((P,), dtype=torch.int32, device=dev), torch.empty((P,), dtype=torch.int32, device=dev),
-                 torch.empty((P,), dtype=torch.float32, device=dev))
-        if return_kept:
-            kept = tuple(torch.empty((P, k), dtype=torch.int32, device=dev) for k in (ka, kb))
-    elif return_kept and keep is None:
-        kept = tuple(torch.arange(k, dtype=torch.int32, device=dev).expand(P, k).contiguous() for k in (ka, kb))
-    elif return_kept:
-        kept = tuple(torch.empty((P, m), dtype=torch.int32, device=dev) for m in keep)
+        sym, ints, widths = "pzn_icp_refine_auto_f32", tuple(auto), (ka, kb)
+    elif keep is not None:
+        sym, ints, widths = "pzn_icp_refine_trim_f32", tuple(keep), tuple(keep)
+    else:
+        sym, ints, widths = "pzn_icp_refine_f32", (), None
+    dev = a.device
+
+    def out(shape, dtype=torch.int32):
+        return torch.empty(shape, dtype=dtype, device=dev)
+
+    T, score, score0, used = out((P, 4, 4), torch.float32), out((P,), torch.float32), out((P,), torch.float32), out((P,))
+    ca, cb = (out((P, ka)), out((P, kb))) if return_corr else (None, None)
+    found = (out((P,)), out((P,)), out((P,), torch.float32)) if auto is not None else ()
+    kept = tuple(out((P, m)) for m in widths) if return_kept and widths else ()
+    tail = () if widths is None else tuple(_p(t) for t in kept) or (None, None)
     if P > 0:
         with _on(dev):
-            if auto is not None:
-                _call("pzn_icp_refine_auto_f32", _p(a), _p(maps[0]), _p(b), _p(maps[1]), _p(T0), P, ka, kb, auto[0], auto[1], auto[2],
-                      iters, _p(T), _p(score), _p(score0), _p(used), _p(ca), _p(cb), _p(found[0]), _p(found[1]), _p(found[2]),
-                      _p(kept[0]) if kept else None, _p(kept[1]) if kept else None, _stream())
-            elif keep is None:
-                _call("pzn_icp_refine_f32", _p(a), _p(maps[0]), _p(b), _p(maps[1]), _p(T0), P, ka, kb, iters, _p(T), _p(score),
-                      _p(score0), _p(used), _p(ca), _p(cb), _stream())
-            else:
-                _call("pzn_icp_refine_trim_f32", _p(a), _p(maps[0]), _p(b), _p(maps[1]), _p(T0), P, ka, kb, keep[0], keep[1], iters,
-                      _p(T), _p(score), _p(score0), _p(used), _p(ca), _p(cb), _p(kept[0]) if kept else None,
-                      _p(kept[1]) if kept else None, _stream())
+            _call(sym, _p(a), _p(maps[0]), _p(b), _p(maps[1]), _p(T0), P, ka, kb, *ints, iters, _p(T), _p(score), _p(score0),
+                  _p(used), _p(ca), _p(cb), *(_p(t) for t in found), *tail, _stream())
+    if return_kept and widths is None:
+        kept = tuple(torch.arange(k, dtype=torch.int32, device=dev).expand(P, k).contiguous() for k in (ka, kb))
     return ((T, score, score0, used, ca, cb) if return_corr else (T, score, score0, used)) + found + kept
 
 
@@ -351,12 +359,10 @@ def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None, na=Non
     the launch is pzn_joint_refine_f32; one of them alone leaves the other side at its full size.
     1 <= K <= 64, J <= K (K - 1), 1 <= ka, kb <= 1024 and sweeps >= 0 (PznUnsupported beyond).  Z = 0 or J = 0 launches
     nothing and returns G0 with scores of 0.  No autograd, nothing waits for the device."""
-    for name, t, dts in (("a", a, (torch.float32,)), ("b", b, (torch.float32,)), ("G0", G0, (torch.float32,)),
-                         ("joints", joints, (torch.int32,)), ("movable", movable, (torch.uint8, torch.bool)),
-                         ("a_of", a_of, (torch.int64,)), ("b_of", b_of, (torch.int64,)), ("na", na, (torch.int32,)),
-                         ("nb", nb, (torch.int32,))):
-        if isinstance(t, torch.Tensor) and t.dtype not in dts:      # (no silent conversion)
-            raise _lib.PznError(f"joint_refine: {name} must be {' or '.join(str(d) for d in dts)}; got {t.dtype}")
+    f32, i32, i64 = (torch.float32,), (torch.int32,), (torch.int64,)
+    _no_conversion("joint_refine", (("a", a, f32), ("b", b, f32), ("G0", G0, f32), ("joints", joints, i32),
+                                    ("movable", movable, (torch.uint8, torch.bool)), ("a_of", a_of, i64), ("b_of", b_of, i64),
+                                    ("na", na, i32), ("nb", nb, i32)))
     a, b, G0 = _f32(a, "a"), _f32(b, "b"), _f32(G0, "G0")
     if a.dim() != 3 or b.dim() != 3 or a.shape[2] != 3 or b.shape[2] != 3:
         raise _lib.PznError(f"joint_refine: expected a[.,ka,3], b[.,kb,3]; got {tuple(a.shape)}, {tuple(b.shape)}")
@@ -382,18 +388,7 @@ def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None, na=Non
     if movable.shape != (Z, K):
         raise _lib.PznError(f"joint_refine: expected movable[{Z},{K}]; got {tuple(movable.shape)}")
     movable = movable.view(torch.uint8)
-    maps = []
-    for name, m, x in (("a_of", a_of, a), ("b_of", b_of, b)):
-        if m is None:
-            if x.shape[0] != Z * J:
-                raise _lib.PznError(f"joint_refine: {name[0]} holds {x.shape[0]} sets for Z J = {Z * J} joint rows and no {name} is given")
-        else:
-            m = _i64(m, name)
-            if m.shape != (Z, J):
-                raise _lib.PznError(f"joint_refine: expected {name}[{Z},{J}]; got {tuple(m.shape)}")
-            if x.shape[0] == 0 and Z * J > 0:
-                raise _lib.PznError(f"joint_refine: {name} indexes an empty {name[0]}")
-        maps.append(m)
+    maps = _set_maps("joint_refine", Z * J, (Z, J), a_of, a, b_of, b)
     counts = []
     for name, n, x, cap in (("na", na, a, ka), ("nb", nb, b, kb)):
         if n is not None:

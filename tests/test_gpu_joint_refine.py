@@ -279,6 +279,66 @@ def test_pieces_without_a_joint_and_fixed_pieces_keep_their_bits(dev):
     assert (acc[:, 1] > 0).all() and (acc[:, 3] > 0).all() and (score < score0).all()
 
 
+def degenerate_pair(rng, collinear, k=8, noise=0.003, angle=np.deg2rad(4.0), shift=0.01):
+    """Two pieces, the joint (0, 1), piece 1 movable: set B is k fp32 points in piece 1's frame - on one line (collinear) or on
+    _icp_ref.curve -, set A their image under a known pose plus `noise`, piece 0 at the identity; G0[1] is that pose turned by
+    `angle` about a random axis through the image's centre and shifted by `shift` in a random direction."""
+    truth = ref.rigid(ref.rot(rng.normal(size=3), rng.uniform(0.3, 2.5)), rng.uniform(-0.3, 0.3, 3))
+    if collinear:
+        b = (rng.uniform(-0.3, 0.3, (1, 3)) + np.linspace(-0.5, 0.5, k)[:, None] * rng.normal(size=(1, 3))).astype(np.float32)
+    else:
+        b = ref.curve(rng.uniform(0, 1, k), False).astype(np.float32)
+    image = ref.transform(truth, b)
+    a = (image + rng.normal(scale=noise, size=(k, 3))).astype(np.float32)
+    c, d = image.mean(axis=0), rng.normal(size=3)
+    Rp = ref.rot(rng.normal(size=3), angle)
+    G1 = ref.rigid(Rp, c - Rp @ c + shift * d / np.linalg.norm(d)) @ truth
+    G0 = np.stack([np.eye(4), G1]).astype(np.float32)
+    return jr.Puzzle(2, [(0, 1)], [a], [b], G0, np.stack([np.eye(4), truth]), np.array([False, True]))
+
+
+DEGENERATE_SEED = 4242
+
+
+def degenerate_cases(k):
+    """[the collinear puzzle, the regular one beside it]; k = 1 keeps the first point of every set of the k = 8 layout."""
+    rng = np.random.default_rng(DEGENERATE_SEED)
+    cases = [degenerate_pair(rng, True), degenerate_pair(rng, False)]
+    return [P._replace(A=[P.A[0][:k]], B=[P.B[0][:k]]) for P in cases]
+
+
+@pytest.mark.parametrize("k", [8, 1])
+def test_degenerate_scatter_keeps_the_rotation(dev, k):
+    """The degenerate rule (solve_pose in csrc/pzn_rigid.h) in the joint kernel: a moved piece whose points x lie on one line
+    (or are one point) keeps its rotation bit for bit and moves by translation only, and that lowers the score; the regular
+    puzzle beside it in the same launch turns.  The float64 visit says the same of these inputs (kept rotation; E_p falls
+    beyond the rounding intervals of both sums, so the seed makes the fall no last-place matter)."""
+    from puzzlenet_amd import ops
+    cases = degenerate_cases(k)
+    flat = [0, 1] if k == 1 else [0]      # one point is degenerate whatever the set was
+    for P in (cases[z] for z in flat):
+        g0 = jr.f32(P.G0)
+        x = P.B[0].astype(np.float64)
+        assert ref.is_degenerate((x - x.mean(axis=0)).T @ (x - x.mean(axis=0)))
+        gn = g0.copy()
+        gn[1] = jr.visit(P, g0, 1)
+        assert np.array_equal(gn[1][:3, :3], g0[1][:3, :3])
+        assert jr.objective_interval2(P.A[0], P.B[0], gn[0], gn[1])[1] < jr.objective_interval2(P.A[0], P.B[0], g0[0], g0[1])[0]
+    if k > 1:
+        x = cases[1].B[0].astype(np.float64)
+        assert not ref.is_degenerate((x - x.mean(axis=0)).T @ (x - x.mean(axis=0)))
+    G, score, score0, js, used, acc = _host(ops.joint_refine(*_stack(cases, dev), SWEEPS))
+    for z, P in enumerate(cases):
+        print(f"k = {k}, puzzle {z}: score0 {score0[z]:.6e} score {score[z]:.6e} accepted {acc[z].tolist()} sweeps {used[z]}")
+        assert np.array_equal(G[z, 0], P.G0[0]) and acc[z, 0] == 0
+        assert acc[z, 1] >= 1 and score[z] <= score0[z]
+        if z in flat:
+            assert np.array_equal(G[z, 1, :3, :3], P.G0[1, :3, :3]), z
+            assert not np.array_equal(G[z, 1, :3, 3], P.G0[1, :3, 3])
+        else:
+            assert not np.array_equal(G[z, 1, :3, :3], P.G0[1, :3, :3])      # the rule did not fire everywhere
+
+
 @pytest.mark.parametrize("graph", list(TRAJECTORY))
 def test_short_trajectory_follows_the_float64_loop(visit_errors, dev, graph):
     from puzzlenet_amd import ops

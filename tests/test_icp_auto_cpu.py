@@ -138,6 +138,29 @@ def test_autokeep_to_counts_and_rejections():
             fn(None, table, None)
 
 
+def test_the_three_kinds_share_their_extra_fields():
+    """assembly._KINDS: no kept sets, kept sets, kept sets with counts.  The Refined, block and table types of a kind are the
+    base fields followed by the same extra fields in the same order, and each is rebuilt from a flat list by type(t)(*t)."""
+    from puzzlenet_amd import assembly
+    extras = [(), ("kept_f", "kept_m"), ("kept_f", "kept_m", "count_f", "count_m", "objective")]
+    assert len(assembly._KINDS) == 3
+    assert assembly._KINDS[0] == (assembly.Refined, assembly.PairBlock, assembly.PairTable)
+    assert assembly._KINDS[1] == (assembly.TrimmedRefined, assembly.TrimmedPairBlock, assembly.TrimmedPairTable)
+    assert assembly._KINDS[2] == (assembly.AutoRefined, assembly.AutoPairBlock, assembly.AutoPairTable)
+    for counts, kind, extra in zip((None, (3, 2), assembly._AutoCounts(3, 2, 3)), assembly._KINDS, extras):
+        assert assembly._kind_of(counts) is kind
+        for typ, base in zip(kind, assembly._KINDS[0]):
+            assert typ._fields == base._fields + extra, typ
+            flat = [object() for _ in typ._fields]
+            t = typ(*flat)
+            again = type(t)(*t)
+            assert type(again) is typ and all(x is y for x, y in zip(again, flat))
+            if not extra:
+                assert t.kept_f is None and t.kept_m is None
+            else:
+                assert t.kept_f is flat[len(base._fields)] and t.kept_m is flat[len(base._fields) + 1]
+
+
 def test_the_margin_rule_leaves_out_at_most_a_quarter():
     """Of the float64 comparisons tests/test_gpu_icp_auto.py makes, how many the margin rule leaves out - from the statement
     and the bounds alone, so it is known here and not on the kernel."""
