@@ -228,6 +228,39 @@ int pzn_joint_refine_counts_f32(const float* a, const int64_t* a_of, const int32
                                 int Z, int K, int J, int ka, int kb, int sweeps,
                                 float* G, float* score, float* score0, float* joint_score,
                                 int32_t* sweeps_used, int32_t* accepted, pzn_stream_t stream);
+/* pzn_joint_refine_f32 for partial contact: of each joint's rows only a given number counts, and WHICH rows is decided again
+ * at every evaluation, under the poses at hand (pzn_icp_refine_trim_f32's rule carried to the pose graph; a kernel of its own,
+ * joint_trim_kernel).  Everything of pzn_joint_refine_f32 stands: the joint list, movable, the sets a[a_of] with ka rows and
+ * b[b_of] with kb rows, the fp32 images, the distances, the row minima and their lowest-index arg-mins, the visit order, the
+ * two acceptance guards, the outputs, and a skipped row scoring 0.  New are two counts per joint ROW, ma[z,e] in [1, ka] and
+ * mb[z,e] in [1, kb] (int32 [Z,J]; per row and not per set, because a set is shared by all joints of its piece while a count
+ * belongs to an ordered pair; NULL means ka / kb for every row).
+ * Kept set: of the ka rows of A under the poses at hand the ma rows with the smallest (row minimum, row index) in
+ * lexicographic order are kept, of the kb rows of B the mb - ranked by counting, exactly m rows whatever the ties.
+ * Energy: E_e = (sum of the kept A-row minima) / ma + (sum of the kept B-row minima) / mb, the kept minima added in
+ * pzn_joint_refine_f32's order with the other rows left out (a thread's rows in order, the butterfly, the wave order), the
+ * divisors (float)ma and (float)mb.
+ * Visit of piece p: only the pairs of the kept rows of p's joints enter the 22 float64 sums, with weights 1 / ma and 1 / mb; the
+ * reference point, Horn's solve and the degenerate rule are unchanged.
+ * Acceptance: the candidate is evaluated with ITS OWN kept sets and taken iff E_p' < E_p and the fp32 total does not round
+ * above the current one; score <= score0 holds to the bit.
+ * Out beside pzn_joint_refine_f32's: when non-NULL, kept_a[Z,J,ka] / kept_b[Z,J,kb] (int32): the rows kept under the RETURNED
+ * poses, positions ascending, -1 behind the count, all -1 for a skipped row.  The same bits on every run.
+ * A row whose ma is outside [1, ka] or whose mb is outside [1, kb] is skipped like a row with a bad (i, j); the counts of a row
+ * with a bad (i, j) are not read.  ma = ka and mb = kb on every row (or both NULL) is pzn_joint_refine_f32 bit for bit on all
+ * six shared outputs, with kept_* = 0 .. k-1.
+ * The range is pzn_joint_refine_f32's (pzn_joint_refine_trim_supported: 1 / 0): the row minima and arg-mins take the LDS image
+ * from 56.3 KB to 68.3 KB at K = 64, J = 4032, ka = kb = 1024, and the launch RAISES the kernel's dynamic LDS limit for such
+ * shapes rather than narrowing the range.  sweeps < 0 or a shape outside it: PZN_EUNSUPPORTED before any launch; Z = 0 or
+ * J = 0 is a success that launches nothing and writes nothing. */
+int pzn_joint_refine_trim_supported(int K, int J, int ka, int kb);
+int pzn_joint_refine_trim_f32(const float* a, const int64_t* a_of, const int32_t* ma,
+                              const float* b, const int64_t* b_of, const int32_t* mb,
+                              const int32_t* joints, const float* G0, const uint8_t* movable,
+                              int Z, int K, int J, int ka, int kb, int sweeps,
+                              float* G, float* score, float* score0, float* joint_score,
+                              int32_t* sweeps_used, int32_t* accepted, int32_t* kept_a, int32_t* kept_b,
+                              pzn_stream_t stream);
 
 /* The greedy walk over Z pair tables and the joint list of every walk (no counterpart in the reference; assembly.assemble and
  * the joint selection of assembly.refine_assembly for Z puzzles): one launch, one wavefront per puzzle, no workspace, no

@@ -105,6 +105,11 @@ class Refined(collections.namedtuple("Refined", "T score score0 iters_used")):
 
 JointRefined = collections.namedtuple("JointRefined", "G score score0 sweeps_used accepted joints")
 Progressive = collections.namedtuple("Progressive", "G edges placed cloud piece_id row_id parts")
+# refine_assembly(..., keep=) / refine_assembly_batch(..., keep=): JointRefined's fields, then per joint row kept_f [...,J,k] and
+# kept_m [...,J,k] (int32: positions into top_f[i,j] / top_m[j] of the rows kept under the returned poses, ascending, -1 behind
+# the count and throughout an unused row) and count_f, count_m [...,J] (int32: the counts the rows were given; an unused row's
+# mean nothing)
+TrimmedJointRefined = collections.namedtuple("TrimmedJointRefined", JointRefined._fields + ("kept_f", "kept_m", "count_f", "count_m"))
 
 # keep < 1 (partial contact): the same tuples with the trailing fields kept_f [...,Kf,Km,m_f] and kept_m [...,Kf,Km,m_m].  The
 # untrimmed types answer kept_f / kept_m with None and keep their fields, so whatever walks over the fields of today's table
@@ -469,17 +474,73 @@ AUTO_JOINT_MESSAGE = ("a table made with keep='auto' carries a kept count per pa
                       "under its own poses), or make the table with a keep fraction")
 
 
-def _kept_mode(kept, table, who):
-    """The `kept` keyword of the joint refinements: None or "frozen" (PznError for anything else, before any tensor is
-    touched).  Both refine over the kept sets the table carries, as they are; an AutoPairTable's were chosen per pair under
-    the pair pose, and freezing them is a choice the caller has to name: None refuses such a table."""
+def _kept_mode(kept, table, who, keep=None):
+    """The `kept` and `keep` keywords of the joint refinements, decided before any tensor is touched.
+    kept: None or "frozen" (PznError for anything else).  Both refine over the kept sets the table carries, as they are; an
+    AutoPairTable's were chosen per pair under the pair pose, and freezing them is a choice the caller has to name: None
+    refuses such a table - unless keep is given, which names another choice.
+    keep: None; a fraction in (0, 1] or a pair (fixed side, moved side) of such; or "table" (the table's own counts: a
+    TrimmedPairTable's kept widths or an AutoPairTable's count per pair; a table without counts is a PznError).  keep together
+    with kept="frozen" is a PznError: the kept rows are either frozen or chosen again.
+    -> None (today's paths), the shares as keep gave them, or "table"."""
     if kept is not None and not (isinstance(kept, str) and kept == "frozen"):
         raise _lib.PznError(f"{who}: kept must be None or 'frozen'; got {kept!r}")
-    if kept is None and isinstance(table, AutoPairTable):
-        raise _lib.PznUnsupported(f"{who}: {AUTO_JOINT_MESSAGE}")
+    if keep is None:
+        if kept is None and isinstance(table, AutoPairTable):
+            raise _lib.PznUnsupported(f"{who}: {AUTO_JOINT_MESSAGE}")
+        return None
+    if kept is not None:
+        raise _lib.PznError(f"{who}: keep = {keep!r} chooses the kept rows again under the joint poses and kept = {kept!r} freezes "
+                            "the table's: pass one of them")
+    if isinstance(keep, str):
+        if keep != "table":
+            raise _lib.PznError(f"{who}: keep = {keep!r} (a fraction in (0, 1], a pair (fixed, moved) of such, or 'table')")
+        if not isinstance(table, (TrimmedPairTable, AutoPairTable)):
+            raise _lib.PznError(f"{who}: keep = 'table' needs a table that carries counts (match_pairs / match_puzzles with "
+                                f"keep < 1 or keep = 'auto'); got a {type(table).__name__}")
+        return "table"
+    if isinstance(keep, AutoKeep):
+        raise _lib.PznError(f"{who}: keep = {keep!r}: the joint refinement takes its counts, it does not find them (a fraction, "
+                            "a pair of fractions, or 'table')")
+    _keep_counts(keep, 1, 1, who)      # (the shares are checked here; the counts wait for k)
+    return keep
 
 
-def _joint_sets(pieces, table, z, i, j):
+def _joint_keep_counts(mode, table, pick, shape, who):
+    """The kept counts of the joint rows for a `keep` that _kept_mode let through -> (ma, mb, m_f, m_m): int32 tensors of `shape`
+    on the GPU, or (None, None) where every row is kept (the untrimmed launch), and the two counts as ints where they are one
+    for all rows (None for an AutoPairTable's).  pick(t) takes a per-pair tensor t [...,P,P] to the joint rows."""
+    k = table.top_m.shape[-1]
+    dev = table.top_m.device
+    if mode == "table" and isinstance(table, AutoPairTable):
+        return pick(table.count_f).to(torch.int32).reshape(shape), pick(table.count_m).to(torch.int32).reshape(shape), None, None
+    if mode == "table":
+        m_f, m_m = int(table.kept_f.shape[-1]), int(table.kept_m.shape[-1])
+    else:
+        m_f, m_m = _keep_counts(mode, k, k, who) or (k, k)
+    if m_f == k and m_m == k:
+        return None, None, k, k
+    return (torch.full(shape, m_f, dtype=torch.int32, device=dev), torch.full(shape, m_m, dtype=torch.int32, device=dev), m_f, m_m)
+
+
+def _trimmed_joint_refined(out, joints, rows, ma, mb, m_f, m_m, k):
+    """TrimmedJointRefined from ops.joint_refine's tuple `out` (with its kept sets, or without them where every row was kept:
+    then 0 .. k-1 on the used rows), the JointRefined `joints` field, the joint rows on the device `rows` [...,J,2] and
+    _joint_keep_counts' answer; every tensor keeps its leading Z."""
+    G, score, score0, _, used, accepted = out[:6]
+    dev = G.device
+    if len(out) > 6:
+        kept_f, kept_m = out[6], out[7]
+    else:
+        live = (rows[..., 0] >= 0)[..., None]
+        full = torch.arange(k, dtype=torch.int32, device=dev).expand(*rows.shape[:-1], k)
+        kept_f = kept_m = torch.where(live, full, torch.full_like(full, -1))
+    if ma is None:
+        ma, mb = (torch.full(rows.shape[:-1], m, dtype=torch.int32, device=dev) for m in (m_f, m_m))
+    return TrimmedJointRefined(G, score, score0, used, accepted, joints, kept_f, kept_m, ma, mb)
+
+
+def _joint_sets(pieces, table, z, i, j, full=False):
     """The point sets of the ordered pairs (z[q], i[q], j[q]) (int64 [n], on the GPU; z may be one int for all of them) of
     pieces [Z,P,N,3] and their table (leading Z), by ONE gather over the Z P N rows of all pieces -> (a [n,ka,3], b [.,kb,3],
     b_of, na, nb) as ops.joint_refine takes them for rows that are those pairs in that order; b_of [n] (or None: b[q]) is
@@ -487,13 +548,14 @@ def _joint_sets(pieces, table, z, i, j):
       * no kept sets: a[q] = pieces[z,i][top_f[z,i,j]]; b holds one set per piece, top_m's, shared through b_of = z P + j;
       * kept sets: the kept rows of the pair on both sides, one set per ordered pair, b_of None;
       * an AutoPairTable: the same with stride k, the -1 padding clamped to 0 (it gathers row 0 of the set, never read) and
-        count_f / count_m of the pairs as na / nb (None otherwise)."""
+        count_f / count_m of the pairs as na / nb (None otherwise).
+    full: the first form whatever the table carries (its kept fields are not read)."""
     Z, P, N, _ = pieces.shape
     n, k = i.numel(), table.top_m.shape[-1]
     fixed, moved = z * P + i, z * P + j      # the pieces of a pair among all Z P; piece p's rows begin at p N
     top_f = table.top_f[z, i, j]
     b_of = na = nb = None
-    if table.kept_f is None:
+    if full or table.kept_f is None:
         rows_a = (fixed * N)[:, None] + top_f
         rows_b = torch.arange(Z * P, dtype=torch.long, device=pieces.device)[:, None] * N + table.top_m.reshape(Z * P, k)
         b_of = moved
@@ -510,7 +572,7 @@ def _joint_sets(pieces, table, z, i, j):
     return picked[:n * ka].view(n, ka, 3), picked[n * ka:].view(-1, kb, 3), b_of, na, nb
 
 
-def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None, kept=None):
+def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None, kept=None, keep=None):
     """Refine all placed poses of a greedy assembly jointly over every joint: pieces [K,N,3] (float32, on the GPU), table =
     match_pairs' PairTable of them, asm = assemble's Assembly of that table -> JointRefined:
 
@@ -537,8 +599,19 @@ def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None, kept=None):
     (PznUnsupported, AUTO_JOINT_MESSAGE) and refined with kept="frozen": joint (i, j) pairs the count_f[i,j] rows
     pieces[i][top_f[i,j][kept_f[i,j][:count_f[i,j]]]] with the count_m[i,j] rows of pieces[j] likewise, J sets of stride k
     a side (the -1 padding gathers row 0 of the set, which the kernel never reads) and the counts as ops.joint_refine's
-    na / nb: still one gather and one launch, with every 1 / ka and 1 / kb of the energy that joint's own count."""
-    _kept_mode(kept, table, "refine_assembly")
+    na / nb: still one gather and one launch, with every 1 / ka and 1 / kb of the energy that joint's own count.
+
+    keep (None: everything above, bit for bit): the kept rows of every joint are chosen AGAIN under the joint poses, at every
+    evaluation (ops.joint_refine's ma / mb, pzn_joint_refine_trim_f32; include/pzn.h states the rule), so the picked rows on
+    faces towards other neighbours neither score nor pull, and the rows that do are not tied to the pair's own pose.  The sets
+    are the FULL ones of any table - pieces[i][top_f[i,j]] and pieces[j][top_m[j]], shared through b_of - and the table's kept
+    fields are not read.  A fraction in (0, 1] or a pair (fixed side, moved side): ceil(f k) rows of each side, the pair
+    functions' rule (1.0: the untrimmed launch over the full sets).  "table": the table's own counts - a TrimmedPairTable's kept
+    widths for every joint, an AutoPairTable's count_f[i,j] and count_m[i,j] per joint; a table without counts is a PznError.
+    keep together with kept="frozen" is a PznError; an AutoPairTable with keep is not refused.  -> TrimmedJointRefined:
+    JointRefined's fields, then kept_f [J,k], kept_m [J,k] (int32: the positions into top_f[i,j] / top_m[j] kept under the
+    returned poses, ascending, -1 behind the count) and count_f, count_m [J] (int32).  Still one gather and one launch."""
+    mode = _kept_mode(kept, table, "refine_assembly", keep)
     _clouds("refine_assembly", "K", pieces=pieces)
     K, N, _ = pieces.shape
     G0 = np.asarray(asm.G, dtype=np.float64)
@@ -564,11 +637,16 @@ def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None, kept=None):
             ji = torch.tensor([i for i, _ in joints], dtype=torch.long, device=dev)
             jj = torch.tensor([j for _, j in joints], dtype=torch.long, device=dev)
             one = type(table)(*(None if f is None else f[None] for f in table))      # (a caller's table may leave fields out)
-            a, b, b_of, cnt_a, cnt_b = _joint_sets(pieces[None], one, 0, ji, jj)
+            a, b, b_of, cnt_a, cnt_b = _joint_sets(pieces[None], one, 0, ji, jj, full=mode is not None)
             b_of = None if b_of is None else b_of.reshape(1, J)
         else:
             a = b = pieces[:0, :table.top_m.shape[1]]
             b_of = cnt_a = cnt_b = None
+        if mode is not None:
+            ma, mb, m_f, m_m = _joint_keep_counts(mode, table, lambda t: t[ji, jj] if J > 0 else t[:0, 0], (1, J), "refine_assembly")
+            out = ops.joint_refine(a, b, jl, g0, mv, sweeps, b_of=b_of, ma=ma, mb=mb, return_kept=ma is not None)
+            out = _trimmed_joint_refined(out, joints, jl.to(dev) if ma is None else None, ma, mb, m_f, m_m, table.top_m.shape[1])
+            return TrimmedJointRefined(*(f[0] if isinstance(f, torch.Tensor) else f for f in out))
         G, score, score0, _, used, accepted = ops.joint_refine(a, b, jl, g0, mv, sweeps, b_of=b_of, na=cnt_a, nb=cnt_b)
     return JointRefined(G[0], score[0], score0[0], used[0], accepted[0], joints)
 
@@ -1331,7 +1409,7 @@ def match_puzzles(model, pieces, k=128, start=None, refine=0, keep=1.0):
     return _table(codes, blk, _diagonal(pieces))
 
 
-def refine_assembly_batch(pieces, table, asm, sweeps=30, kept=None):
+def refine_assembly_batch(pieces, table, asm, sweeps=30, kept=None, keep=None):
     """refine_assembly for Z puzzles with no download: pieces [Z,P,N,3] (float32, on the GPU), table = match_puzzles' PairTable
     of them, asm = assemble_batch's AssemblyBatch of that table -> JointRefined whose fields carry a leading Z: G [Z,P,4,4]
     float32, score, score0, sweeps_used [Z], accepted [Z,P], joints = asm.joints (the device tensor, unused rows (-1, -1)).
@@ -1352,8 +1430,14 @@ def refine_assembly_batch(pieces, table, asm, sweeps=30, kept=None):
     kept: refine_assembly's keyword.  An AutoPairTable is refused by default (PznUnsupported, AUTO_JOINT_MESSAGE); with
     kept="frozen" its 2 Z P^2 sets have stride k, the -1 padding of kept_* gathers row 0 of the set, and the counts travel as
     ops.joint_refine's na = count_f and nb = count_m, one per ordered pair and found by the kernel through the same a_of:
-    one gather, one launch, nothing waits for the device."""
-    _kept_mode(kept, table, "refine_assembly_batch")
+    one gather, one launch, nothing waits for the device.
+
+    keep: refine_assembly's keyword (None: everything above, bit for bit, with no new launch).  The sets are then the full
+    Z P^2 + Z P ones of the first form whatever the table carries, a fraction gives every row the counts ceil(f k), and "table"
+    a TrimmedPairTable's kept widths or, for an AutoPairTable, count_f[z,i,j] and count_m[z,i,j] gathered on the device through
+    the same a_of (an unused row gets pair (0, 0, 0)'s and is skipped).  -> TrimmedJointRefined with a leading Z: kept_f, kept_m
+    [Z,J,k] (all -1 on an unused row), count_f, count_m [Z,J].  One gather, one launch, nothing waits for the device."""
+    mode = _kept_mode(kept, table, "refine_assembly_batch", keep)
     _clouds("refine_assembly_batch", "Z,P", pieces=pieces)
     Z, P, N, _ = pieces.shape
     J = P * (P - 1)
@@ -1370,8 +1454,13 @@ def refine_assembly_batch(pieces, table, asm, sweeps=30, kept=None):
         # the sets of all Z P^2 ordered pairs in row-major order: a joint row finds its pair, and through it its sets, by a_of
         z, i, j = (t.reshape(-1) for t in torch.meshgrid(*(torch.arange(n, dtype=torch.long, device=dev) for n in (Z, P, P)),
                                                          indexing="ij"))
-        a, b, b_of, cnt_a, cnt_b = _joint_sets(pieces, table, z, i, j)
+        a, b, b_of, cnt_a, cnt_b = _joint_sets(pieces, table, z, i, j, full=mode is not None)
         b_of = a_of if b_of is None else b_of[a_of]
+        if mode is not None:
+            ma, mb, m_f, m_m = _joint_keep_counts(mode, table, lambda t: t.reshape(-1)[a_of], (Z, J), "refine_assembly_batch")
+            out = ops.joint_refine(a, b, asm.joints, asm.G.to(torch.float32), asm.movable, sweeps, a_of=a_of, b_of=b_of, ma=ma, mb=mb,
+                                   return_kept=ma is not None)
+            return _trimmed_joint_refined(out, asm.joints, asm.joints, ma, mb, m_f, m_m, table.top_m.shape[-1])
         G, score, score0, _, used_sweeps, accepted = ops.joint_refine(a, b, asm.joints, asm.G.to(torch.float32), asm.movable, sweeps,
                                                                       a_of=a_of, b_of=b_of, na=cnt_a, nb=cnt_b)
     return JointRefined(G, score, score0, used_sweeps, accepted, asm.joints)

@@ -32,6 +32,7 @@ SOURCES = [
     ("mergefps.hip", ["-ffp-contract=off"] + NOSLP),
     ("icprefine.hip", ["-ffp-contract=off"] + NOSLP),
     ("jointrefine.hip", ["-ffp-contract=off"] + NOSLP),
+    ("jointtrim.hip", ["-ffp-contract=off"] + NOSLP),
     ("assemblewalk.hip", ["-ffp-contract=off"] + NOSLP),
     ("assemblebeam.hip", ["-ffp-contract=off"] + NOSLP),
     ("progressive.hip", ["-ffp-contract=off"] + NOSLP),

@@ -343,7 +343,11 @@ def joint_refine_supported(K, J, ka, kb):
     return bool(_lib.load().pzn_joint_refine_supported(int(K), int(J), int(ka), int(kb)))
 
 
-def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None, na=None, nb=None):
+def joint_refine_trim_supported(K, J, ka, kb):
+    return bool(_lib.load().pzn_joint_refine_trim_supported(int(K), int(J), int(ka), int(kb)))
+
+
+def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None, na=None, nb=None, ma=None, mb=None, return_kept=False):
     """Z pose graphs refined in one launch (pzn_joint_refine_f32): puzzle z has the poses G0[z] [K,4,4], the mask movable[z]
     [K] (uint8 or bool) and the joint rows joints[z] [J,2] (int32 ordered pairs (i, j); a row with i < 0 is unused); row e has
     the set a[a_of[z,e]] [ka,3] in piece i's frame and b[b_of[z,e]] [kb,3] in piece j's (int64 [Z,J]; the caller keeps them
@@ -357,12 +361,25 @@ def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None, na=Non
     (pzn_joint_refine_counts_f32; ka, kb stay the strides).  Like joints: a host tensor is checked (1 <= n <= ka; PznError) and
     uploaded, a device tensor is not, and the kernel skips a row with a count out of range (joint_score 0).  With both None
     the launch is pzn_joint_refine_f32; one of them alone leaves the other side at its full size.
+    ma / mb (int32 [Z,J]): partial contact - a kept count per joint ROW (pzn_joint_refine_trim_f32, one launch of its own
+    kernel; include/pzn.h states the rule): of row e's ka rows of A only the ma[z,e] with the smallest (row minimum, row index)
+    under the poses at hand count, in E_e and as pairs of a visit, of its kb rows of B the mb[z,e]; which rows those are is
+    decided again at every evaluation.  A host tensor is checked (1 <= m <= k on the used rows - those with i >= 0 where
+    joints is a host tensor too, every row otherwise; PznError) and uploaded; a device tensor is not, and the kernel skips a
+    row with a count out of range.  One of them alone leaves the other side at its full size; counts together with na / nb
+    are a PznError.  return_kept appends kept_a [Z,J,ka] and kept_b [Z,J,kb] (int32): the rows kept under the returned poses,
+    ascending, -1 behind the count and throughout a skipped row (without counts: that launch with every row kept).  With ma,
+    mb None and return_kept False nothing changes: the same launch and the same tuple.
     1 <= K <= 64, J <= K (K - 1), 1 <= ka, kb <= 1024 and sweeps >= 0 (PznUnsupported beyond).  Z = 0 or J = 0 launches
     nothing and returns G0 with scores of 0.  No autograd, nothing waits for the device."""
     f32, i32, i64 = (torch.float32,), (torch.int32,), (torch.int64,)
     _no_conversion("joint_refine", (("a", a, f32), ("b", b, f32), ("G0", G0, f32), ("joints", joints, i32),
                                     ("movable", movable, (torch.uint8, torch.bool)), ("a_of", a_of, i64), ("b_of", b_of, i64),
-                                    ("na", na, i32), ("nb", nb, i32)))
+                                    ("na", na, i32), ("nb", nb, i32), ("ma", ma, i32), ("mb", mb, i32)))
+    trim = ma is not None or mb is not None or bool(return_kept)
+    if trim and (na is not None or nb is not None):
+        raise _lib.PznError("joint_refine: kept counts per row (ma / mb, return_kept) and point counts per set (na / nb) exclude "
+                            "each other")
     a, b, G0 = _f32(a, "a"), _f32(b, "b"), _f32(G0, "G0")
     if a.dim() != 3 or b.dim() != 3 or a.shape[2] != 3 or b.shape[2] != 3:
         raise _lib.PznError(f"joint_refine: expected a[.,ka,3], b[.,kb,3]; got {tuple(a.shape)}, {tuple(b.shape)}")
@@ -373,8 +390,10 @@ def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None, na=Non
         raise _lib.PznError(f"joint_refine: expected joints[{Z},J,2]; got "
                             f"{tuple(joints.shape) if isinstance(joints, torch.Tensor) else type(joints).__name__}")
     J = joints.shape[1]
+    used_rows = None      # the used rows as the caller's host copy of the list shows them
     if not joints.is_cuda:      # the caller's host copy: a check that waits for nothing
         i, j = joints[..., 0], joints[..., 1]
+        used_rows = i >= 0
         bad = (i >= 0) & ((i >= K) | (j < 0) | (j >= K) | (i == j))
         if bool(bad.any()):
             z, e = (int(v) for v in bad.nonzero()[0])
@@ -405,30 +424,54 @@ def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None, na=Non
                 n = n.to(a.device)
             n = _req(n, torch.int32, name)
         counts.append(n)
+    kept_counts = []
+    for name, m, cap in (("ma", ma, ka), ("mb", mb, kb)):
+        if m is not None:
+            if not isinstance(m, torch.Tensor) or m.shape != (Z, J):
+                raise _lib.PznError(f"joint_refine: expected {name}[{Z},{J}] (one kept count per joint row); got "
+                                    f"{tuple(m.shape) if isinstance(m, torch.Tensor) else type(m).__name__}")
+            if m.device.type not in ("cpu", "cuda"):
+                raise _lib.PznError(f"joint_refine: {name} must be on the GPU or a host tensor; got one on {m.device}")
+            if not m.is_cuda:      # the caller's host copy, as for joints
+                bad = (m < 1) | (m > cap)
+                if used_rows is not None:
+                    bad = bad & used_rows
+                if bool(bad.any()):
+                    z, e = (int(v) for v in bad.nonzero()[0])
+                    raise _lib.PznError(f"joint_refine: {name}[{z},{e}] = {int(m[z, e])} is no kept count of a set of {cap} rows")
+                m = m.to(a.device)
+            m = _req(m, torch.int32, name)
+        kept_counts.append(m)
     sweeps = int(sweeps)
-    if sweeps < 0 or not joint_refine_supported(K, J, ka, kb):
+    if sweeps < 0 or not (joint_refine_trim_supported if trim else joint_refine_supported)(K, J, ka, kb):
         raise _lib.PznUnsupported(f"joint_refine: K = {K}, J = {J}, ka = {ka}, kb = {kb}, sweeps = {sweeps} "
                                   "(1 <= K <= 64, J <= K (K - 1), 1 <= ka, kb <= 1024, sweeps >= 0)")
     dev = a.device
+    kept = tuple(torch.empty((Z, J, k), dtype=torch.int32, device=dev) for k in (ka, kb)) if return_kept else ()      # (empty if Z J = 0)
     if Z == 0 or J == 0:
         return (G0.clone(), torch.zeros((Z,), dtype=torch.float32, device=dev), torch.zeros((Z,), dtype=torch.float32, device=dev),
                 torch.zeros((Z, J), dtype=torch.float32, device=dev), torch.zeros((Z,), dtype=torch.int32, device=dev),
-                torch.zeros((Z, K), dtype=torch.int32, device=dev))
+                torch.zeros((Z, K), dtype=torch.int32, device=dev)) + kept
     G = torch.empty((Z, K, 4, 4), dtype=torch.float32, device=dev)
     score = torch.empty((Z,), dtype=torch.float32, device=dev)
     score0 = torch.empty_like(score)
     joint_score = torch.empty((Z, J), dtype=torch.float32, device=dev)
     used = torch.empty((Z,), dtype=torch.int32, device=dev)
     accepted = torch.empty((Z, K), dtype=torch.int32, device=dev)
+    kept_a, kept_b = kept or (None, None)
     with _on(dev):
-        if counts[0] is None and counts[1] is None:
+        if trim:
+            _call("pzn_joint_refine_trim_f32", _p(a), _p(maps[0]), _p(kept_counts[0]), _p(b), _p(maps[1]), _p(kept_counts[1]),
+                  _p(joints), _p(G0), _p(movable), Z, K, J, ka, kb, sweeps, _p(G), _p(score), _p(score0), _p(joint_score), _p(used),
+                  _p(accepted), _p(kept_a), _p(kept_b), _stream())
+        elif counts[0] is None and counts[1] is None:
             _call("pzn_joint_refine_f32", _p(a), _p(maps[0]), _p(b), _p(maps[1]), _p(joints), _p(G0), _p(movable), Z, K, J, ka, kb,
                   sweeps, _p(G), _p(score), _p(score0), _p(joint_score), _p(used), _p(accepted), _stream())
         else:
             _call("pzn_joint_refine_counts_f32", _p(a), _p(maps[0]), _p(counts[0]), _p(b), _p(maps[1]), _p(counts[1]), _p(joints),
                   _p(G0), _p(movable), Z, K, J, ka, kb, sweeps, _p(G), _p(score), _p(score0), _p(joint_score), _p(used),
                   _p(accepted), _stream())
-    return G, score, score0, joint_score, used, accepted
+    return (G, score, score0, joint_score, used, accepted) + kept
 
 
 def assemble_walk_supported(K):

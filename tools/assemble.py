@@ -2,7 +2,7 @@
 assembled cloud.
 
     python tools/assemble.py --pieces pieces.npy [--ckpt model.ckpt] [--k 128] [--max-score S] [--out PREFIX] [--progressive]
-                             [--refine N] [--keep F|auto] [--joint N] [--gt PREFIX_gt.npz] [--beam B] [--branch C] [--vote-weight W] [--forest]
+                             [--refine N] [--keep F|auto] [--joint N] [--joint-keep F|table] [--gt PREFIX_gt.npz] [--beam B] [--branch C] [--vote-weight W] [--forest]
 
 pieces.npy holds [K, N, 3] float32 (N = the model's points per piece).  Prints the score table and the edges in
 placement order, writes PREFIX_G.npy ([K,4,4], each piece into the root's frame) and PREFIX_cloud.npy ([K,N,3]).
@@ -15,6 +15,8 @@ point-to-point ICP, at most N accepted steps, one launch per table or per round)
 placed pieces that scores no worse than the walk's worst edge - by at most N sweeps of assembly.refine_assembly (one launch);
 PREFIX_G.npy and PREFIX_cloud.npy are then the refined ones, and with --gt the assembly is scored before and after.  With
 --keep auto every joint is refined over the rows its own pair kept (refine_assembly(..., kept="frozen"): a count per joint).
+--joint-keep F|table (with --joint): the kept rows of every joint are chosen again under the joint poses, at every evaluation
+(refine_assembly(..., keep=)): the share F of the full picked sets, or the counts the table carries (--keep F < 1 or auto).
 --beam B (the table walk only, with --branch C and --vote-weight W): the beam walk of assembly.assemble_beam_batch in place of the
 greedy one - B hypotheses, each extended by its C smallest entries, a child charged W times what the other placed pieces'
 entries say against its pose -; everything after the walk is the same.
@@ -67,7 +69,7 @@ def forest(args, x, table):
     for q, r in enumerate(fb.roots[0, :nc].tolist()):
         print(f"component {q}: root piece {r}, pieces {[p for p, c in enumerate(comp) if c == q]}")
     if args.joint:
-        jr = assembly.refine_assembly_batch(x[None], one, fb, sweeps=args.joint, kept="frozen" if args.keep == "auto" else None)
+        jr = assembly.refine_assembly_batch(x[None], one, fb, sweeps=args.joint, **joint_kw(args))
         G = jr.G[0].double()
         print(f"joint refinement over {int(fb.n_joints[0])} joints: summed score {float(jr.score0[0]):.6f} -> {float(jr.score[0]):.6f}, "
               f"{int(jr.sweeps_used[0])} sweeps, candidates taken per piece {jr.accepted[0].tolist()}")
@@ -75,6 +77,19 @@ def forest(args, x, table):
     np.save(args.out + "_component.npy", np.asarray(comp, dtype=np.int32))
     np.save(args.out + "_cloud.npy", assembly.apply(x, G).cpu().numpy())
     print(f"wrote {args.out}_G.npy, {args.out}_component.npy, {args.out}_cloud.npy (every component in its own root's frame)")
+
+
+def joint_keep_arg(text):
+    """--joint-keep: a share in (0, 1], or the word table (the counts the table carries)."""
+    return "table" if text == "table" else float(text)
+
+
+def joint_kw(args):
+    """The keywords of the joint refinement: --joint-keep chooses the kept rows again under the joint poses (keep=); without it a
+    table made with --keep auto is refined over the rows its pairs kept (kept="frozen")."""
+    if args.joint_keep is not None:
+        return {"keep": args.joint_keep}
+    return {"kept": "frozen" if args.keep == "auto" else None}
 
 
 def keep_arg(text):
@@ -97,6 +112,9 @@ def main():
                     "that counts in a pair's score and refinement, those closest to the other side (1.0: all; not with --progressive), "
                     "or the word auto: the share is found per pair on the device (with --joint the kept sets are refined as the pair refinement left them: kept='frozen')")
     ap.add_argument("--joint", type=int, default=0, help="sweeps at most of the joint refinement after the greedy walk (0: none)")
+    ap.add_argument("--joint-keep", type=joint_keep_arg, default=None, help="with --joint: the kept rows of every joint are chosen again "
+                    "under the joint poses - F: the share in (0, 1] of the picked boundary points of each side that counts, or the "
+                    "word table: the counts the table carries (--keep F < 1 or auto); the full picked sets are read, not the table's kept rows")
     ap.add_argument("--gt", default=None, help="PREFIX_gt.npz of tools/fracture.py: score the assembly against the truth")
     ap.add_argument("--beam", type=int, default=0, help="B: the beam walk with B hypotheses in place of the greedy walk (1 .. 8; 0: greedy)")
     ap.add_argument("--branch", type=int, default=4, help="C: with --beam, the candidates every hypothesis is extended by (1 .. 8)")
@@ -113,6 +131,9 @@ def main():
         sys.exit("--keep: a share in (0, 1] or the word auto, and 1.0 with --progressive (the progressive walk does not trim)")
     if args.joint < 0 or (args.joint and args.progressive):
         sys.exit("--joint: 0 or a number of sweeps, and for the greedy walk only (not with --progressive)")
+    if args.joint_keep is not None and (not args.joint or (args.joint_keep != "table" and not 0.0 < args.joint_keep <= 1.0)
+                                        or (args.joint_keep == "table" and args.keep == 1.0)):
+        sys.exit("--joint-keep: with --joint N, a share in (0, 1] or the word table (which needs --keep F < 1 or auto)")
 
     if not torch.cuda.is_available():
         sys.exit("tools/assemble.py needs a GPU: puzzlenet_amd has no CPU path")
@@ -185,7 +206,7 @@ def main():
         if gt is not None:
             print(f"against {args.gt} (in the root's frame), before the joint refinement:")
             report(assembly.evaluate(G, result.placed, gt["pose"], gt["rest"], result.root, result.edges, gt["mates"]))
-        jr = assembly.refine_assembly(x, table, result, sweeps=args.joint, kept="frozen" if args.keep == "auto" else None)
+        jr = assembly.refine_assembly(x, table, result, sweeps=args.joint, **joint_kw(args))
         G = jr.G.double().cpu().numpy()
         print(f"joint refinement over {len(jr.joints)} joints: summed score {float(jr.score0):.6f} -> {float(jr.score):.6f}, "
               f"{int(jr.sweeps_used)} sweeps, candidates taken per piece {jr.accepted.tolist()}")

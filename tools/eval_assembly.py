@@ -1,7 +1,7 @@
 """The assembly score of a model as a mean over a batch of fractured puzzles, with one download at the end:
 
     python tools/eval_assembly.py [--batch 64] [--pieces 8] [--m 20000] [--k 128] [--candidates 16] [--mag 0.8] [--seed 0]
-                                  [--curvature 2.0] [--ckpt model.ckpt] [--refine N] [--keep F|auto] [--joint N] [--max-score S]
+                                  [--curvature 2.0] [--ckpt model.ckpt] [--refine N] [--keep F|auto] [--joint N] [--joint-keep F|table] [--max-score S]
                                   [--progressive] [--time R] [--json out.json] [--beam B] [--branch C] [--vote-weight W]
                                   [--objects Q]
 
@@ -16,7 +16,8 @@ downloaded once.  --beam B (with --branch C, --vote-weight W) also runs the beam
 (boundary_moments and assemble_beam_batch, one launch) on the same table and prints its means beside the greedy walk's, with
 --joint both before and after the joint refinement of its own result.  Prints the means over the valid fractures: part accuracy, edge precision, and over the placed pieces other
 than the root the rotation error in degrees, the translation error and the mean squared distance; with --joint both before and
-after the joint refinement.  --progressive reports the same means for the progressive walk (assemble_progressive_batch: all
+after the joint refinement; --joint-keep F|table has that refinement choose the kept rows of every joint again under the joint
+poses (refine_assembly_batch(..., keep=): the share F of the full picked sets, or the counts the table carries).  --progressive reports the same means for the progressive walk (assemble_progressive_batch: all
 puzzles in lockstep, P - 1 rounds, every round one choice launch, one merge launch, one encoder batch and two blocked pair blocks)
 beside the greedy one, on the same fractures and table starts, still with the one download.  --time R (with --progressive) then
 times the batched progressive walk and, beside it, a loop of assemble_progressive over the same puzzles - the per-puzzle path, which
@@ -86,7 +87,7 @@ def sort_piles(args, model, f, dev):
         rows.append(row(asm.G, asm))
         extra = torch.zeros(3, dtype=torch.float64, device=dev)
         if args.joint:
-            jr = assembly.refine_assembly_batch(pile.pieces, table, asm, sweeps=args.joint, kept="frozen" if args.keep == "auto" else None)
+            jr = assembly.refine_assembly_batch(pile.pieces, table, asm, sweeps=args.joint, **joint_kw(args))
             labels.append(f"{label.split(' (')[0]} after the joint refinement")
             rows.append(row(jr.G, asm))
             extra = torch.stack((jr.score0.double().mean(), jr.score.double().mean(), jr.sweeps_used.double().mean()))
@@ -105,6 +106,19 @@ def sort_piles(args, model, f, dev):
               + (f"; joint refinement: mean summed score {h[2]:.6f} -> {h[3]:.6f}, {h[4]:.1f} sweeps" if args.joint else ""))
     if args.beam:
         print(f"forest beam: the forest walk's edges in {100 * host[at - 1]:.1f} % of the piles")
+
+
+def joint_keep_arg(text):
+    """--joint-keep: a share in (0, 1], or the word table (the counts the table carries)."""
+    return "table" if text == "table" else float(text)
+
+
+def joint_kw(args):
+    """The keywords of the joint refinement: --joint-keep chooses the kept rows again under the joint poses (keep=); without it a
+    table made with --keep auto is refined over the rows its pairs kept (kept="frozen")."""
+    if args.joint_keep is not None:
+        return {"keep": args.joint_keep}
+    return {"kept": "frozen" if args.keep == "auto" else None}
 
 
 def keep_arg(text):
@@ -130,6 +144,9 @@ def main():
                     "that counts in a pair's score and refinement, those closest to the other side (1.0: all; the progressive "
                     "walks do not trim), or the word auto: the share is found per pair on the device (with --joint the kept sets are refined as the pair refinement left them: kept='frozen')")
     ap.add_argument("--joint", type=int, default=0, help="sweeps at most of the joint refinement after the walk (0: none)")
+    ap.add_argument("--joint-keep", type=joint_keep_arg, default=None, help="with --joint: the kept rows of every joint are chosen again "
+                    "under the joint poses - F: the share in (0, 1] of the picked boundary points of each side that counts, or the "
+                    "word table: the counts the table carries (--keep F < 1 or auto); the full picked sets are read, not the table's kept rows")
     ap.add_argument("--max-score", type=float, default=None, help="stop placing pieces above this boundary distance")
     ap.add_argument("--progressive", action="store_true", help="also the progressive walk of the whole batch, in lockstep")
     ap.add_argument("--time", type=int, default=0, help="with --progressive: repeats of the timed batched walk and per-puzzle loop")
@@ -146,6 +163,9 @@ def main():
         sys.exit("--objects goes with the forest walk alone: no --progressive")
     if args.refine < 0 or args.joint < 0:
         sys.exit("--refine, --joint: 0 or a number of steps / sweeps")
+    if args.joint_keep is not None and (not args.joint or (args.joint_keep != "table" and not 0.0 < args.joint_keep <= 1.0)
+                                        or (args.joint_keep == "table" and args.keep == 1.0)):
+        sys.exit("--joint-keep: with --joint N, a share in (0, 1] or the word table (which needs --keep F < 1 or auto)")
     if args.keep != "auto" and not 0.0 < args.keep <= 1.0:
         sys.exit("--keep: a share in (0, 1] or the word auto")
     if args.time < 0 or (args.time and not args.progressive) or (args.json and not args.time):
@@ -185,7 +205,7 @@ def main():
         rows = [metrics(assembly.evaluate_batch(asm.G, asm.placed, f.pose, f.rest, asm.root, asm.edges, asm.n_edges, f.mates), asm, f.ok)]
         extra = torch.zeros(3, dtype=torch.float64, device=dev)
         if args.joint:
-            jr = assembly.refine_assembly_batch(f.pieces, table, asm, sweeps=args.joint, kept="frozen" if args.keep == "auto" else None)
+            jr = assembly.refine_assembly_batch(f.pieces, table, asm, sweeps=args.joint, **joint_kw(args))
             rows.append(metrics(assembly.evaluate_batch(jr.G, asm.placed, f.pose, f.rest, asm.root, asm.edges, asm.n_edges, f.mates),
                                 asm, f.ok))
             extra = torch.stack((jr.score0.double().mean(), jr.score.double().mean(), jr.sweeps_used.double().mean()))
@@ -201,7 +221,7 @@ def main():
                                               max_score=args.max_score)
             rows.append(metrics(assembly.evaluate_batch(bm.G, bm.placed, f.pose, f.rest, bm.root, bm.edges, bm.n_edges, f.mates), bm, f.ok))
             if args.joint:
-                bj = assembly.refine_assembly_batch(f.pieces, table, bm, sweeps=args.joint, kept="frozen" if args.keep == "auto" else None)
+                bj = assembly.refine_assembly_batch(f.pieces, table, bm, sweeps=args.joint, **joint_kw(args))
                 rows.append(metrics(assembly.evaluate_batch(bj.G, bm.placed, f.pose, f.rest, bm.root, bm.edges, bm.n_edges, f.mates),
                                     bm, f.ok))
             same = (bm.edges == asm.edges).all(dim=2).all(dim=1).double().mean()
