@@ -261,6 +261,46 @@ int pzn_joint_refine_trim_f32(const float* a, const int64_t* a_of, const int32_t
                               float* G, float* score, float* score0, float* joint_score,
                               int32_t* sweeps_used, int32_t* accepted, int32_t* kept_a, int32_t* kept_b,
                               pzn_stream_t stream);
+/* pzn_joint_refine_trim_f32 with the two counts of every joint FOUND at every evaluation of the joint, under whatever poses
+ * are being tried, instead of given per row (pzn_icp_refine_auto_f32's count search carried to the pose graph; a kernel of its
+ * own, joint_auto_kernel, one launch for Z puzzles).  Inputs: everything of pzn_joint_refine_trim_f32 except ma and mb; in
+ * their place, per launch, the least counts 1 <= lo_a <= ka, 1 <= lo_b <= kb and the integer power p in [1, 4], with
+ * pzn_icp_refine_auto_f32's meaning.
+ * Evaluation of joint row e under poses G: the images, distances, row minima and lowest-index arg-mins are
+ * pzn_joint_refine_trim_f32's.  Steps 1 to 7 of the rule above pzn_icp_refine_auto_f32 then apply to the ka row minima of A and
+ * the kb row minima of B, the order of the float32 prefix sums (thread by thread, as stated there) and the tie rules (the larger
+ * m among equal phi, the lower row index among equal minima) included.  It yields m_a, m_b, the kept rows, E_e = e_a + e_b (the
+ * trimmed energy at these counts, summed as pzn_joint_refine_trim_f32 sums it) and F_e = e_a r_a + e_b r_b, each product and
+ * the sum rounded to float32, r = (float)(q^p), q = (double)k / (double)m, the power by repeated multiplication in float64.
+ * F_p = the fp32 sum in row order of F_e over the rows with i = p or j = p; F = that sum over all rows (formed exactly as E_p
+ * and E are formed by pzn_joint_refine_f32).
+ * Visit of piece p: only the kept pairs of p's joints enter the 22 float64 sums, with weights r_a / m_a and r_b / m_b in
+ * float64 (r = q^p as above, before its cast to float, then one division by (double)m): the candidate then minimises F_p for the
+ * sets and counts at hand; the joints of one piece are summed, so their relative weight matters.  At lo = k the weight is
+ * 1 / k, pzn_joint_refine_trim_f32's.  The reference point, Horn's solve and the degenerate rule are unchanged.
+ * Acceptance: the candidate is evaluated with ITS OWN counts and kept sets and taken iff F_p' < F_p and the fp32 total F does
+ * not round above its current value; anything else (NaN included) keeps G_p.  So objective <= objective0 holds to the bit.
+ * F falls along a run; score, the sum of E_e at counts that move with the poses, need not.
+ * Out: the six of pzn_joint_refine_f32, in the units a trimmed table compares - score[Z] and score0[Z] are the sums of E_e under
+ * G and under G0, joint_score[Z,J] is E_e(G) (0 for a skipped row) - and objective[Z], objective0[Z]: the sums of F_e under G
+ * and under G0; count_a[Z,J], count_b[Z,J] (int32; 0 for a skipped row); and, when non-NULL, kept_a[Z,J,ka] / kept_b[Z,J,kb]
+ * (int32): the kept rows ascending, -1 behind the count, all -1 for a skipped row.  Every output is that of the RETURNED poses:
+ * joint_score, the counts and the kept rows are written in one last evaluation of every joint after the loop.  The same bits
+ * on every run.
+ * lo_a = ka and lo_b = kb is pzn_joint_refine_f32 bit for bit on the six shared outputs, with objective == score, every count
+ * k and kept_* = 0 .. k-1.
+ * The range is pzn_joint_refine_trim_supported's plus the three new arguments (pzn_joint_refine_auto_supported: 1 / 0).  The
+ * sorted minima add 4 (ka + kb) bytes of LDS, 76.3 KB at K = 64, J = 4032, ka = kb = 1024; the launch raises the kernel's
+ * dynamic LDS limit for such shapes.  sweeps < 0 or anything outside the range: PZN_EUNSUPPORTED before any launch; Z = 0 or
+ * J = 0 is a success that launches nothing and writes nothing. */
+int pzn_joint_refine_auto_supported(int K, int J, int ka, int kb, int lo_a, int lo_b, int power);
+int pzn_joint_refine_auto_f32(const float* a, const int64_t* a_of, const float* b, const int64_t* b_of,
+                              const int32_t* joints, const float* G0, const uint8_t* movable,
+                              int Z, int K, int J, int ka, int kb, int lo_a, int lo_b, int power, int sweeps,
+                              float* G, float* score, float* score0, float* joint_score,
+                              int32_t* sweeps_used, int32_t* accepted, float* objective, float* objective0,
+                              int32_t* count_a, int32_t* count_b, int32_t* kept_a, int32_t* kept_b,
+                              pzn_stream_t stream);
 
 /* The greedy walk over Z pair tables and the joint list of every walk (no counterpart in the reference; assembly.assemble and
  * the joint selection of assembly.refine_assembly for Z puzzles): one launch, one wavefront per puzzle, no workspace, no

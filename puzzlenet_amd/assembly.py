@@ -110,6 +110,10 @@ Progressive = collections.namedtuple("Progressive", "G edges placed cloud piece_
 # the count and throughout an unused row) and count_f, count_m [...,J] (int32: the counts the rows were given; an unused row's
 # mean nothing)
 TrimmedJointRefined = collections.namedtuple("TrimmedJointRefined", JointRefined._fields + ("kept_f", "kept_m", "count_f", "count_m"))
+# refine_assembly(..., auto=) / refine_assembly_batch(..., auto=): TrimmedJointRefined's fields - count_f, count_m are the counts
+# FOUND under the returned poses (0 on an unused row), score and score0 the trimmed energy at the counts found - then objective
+# and objective0, the F the refinement lowered under G and under asm.G (objective <= objective0; score need not fall)
+AutoJointRefined = collections.namedtuple("AutoJointRefined", TrimmedJointRefined._fields + ("objective", "objective0"))
 
 # keep < 1 (partial contact): the same tuples with the trailing fields kept_f [...,Kf,Km,m_f] and kept_m [...,Kf,Km,m_m].  The
 # untrimmed types answer kept_f / kept_m with None and keep their fields, so whatever walks over the fields of today's table
@@ -506,6 +510,30 @@ def _kept_mode(kept, table, who, keep=None):
     return keep
 
 
+def _auto_mode(auto, kept, keep, who):
+    """The `auto` keyword of the joint refinements, decided before any tensor is touched: None, True (AutoKeep()) or an AutoKeep
+    (PznError for anything else, a share or power out of range included).  It names a choice of its own - the counts of every
+    joint are found under the joint poses - so together with keep or with kept it is a PznError, and an AutoPairTable is not
+    refused.  -> None or the AutoKeep."""
+    if auto is None:
+        return None
+    if auto is True:
+        auto = AutoKeep()
+    if not isinstance(auto, AutoKeep):
+        raise _lib.PznError(f"{who}: auto must be None, True or an AutoKeep(least, power); got {auto!r}")
+    if keep is not None or kept is not None:
+        raise _lib.PznError(f"{who}: auto finds the counts of every joint under the joint poses; keep = {keep!r} gives them and "
+                            f"kept = {kept!r} freezes the table's rows: pass one of the three")
+    _keep_counts(auto, 1, 1, who)      # (least and power are checked here; the counts wait for k)
+    return auto
+
+
+def _auto_joint_refined(out, joints):
+    """AutoJointRefined from ops.joint_refine(..., auto=, return_kept=True)'s tuple and the JointRefined `joints` field."""
+    G, score, score0, _, used, accepted, kept_f, kept_m, count_f, count_m, objective, objective0 = out
+    return AutoJointRefined(G, score, score0, used, accepted, joints, kept_f, kept_m, count_f, count_m, objective, objective0)
+
+
 def _joint_keep_counts(mode, table, pick, shape, who):
     """The kept counts of the joint rows for a `keep` that _kept_mode let through -> (ma, mb, m_f, m_m): int32 tensors of `shape`
     on the GPU, or (None, None) where every row is kept (the untrimmed launch), and the two counts as ints where they are one
@@ -572,7 +600,7 @@ def _joint_sets(pieces, table, z, i, j, full=False):
     return picked[:n * ka].view(n, ka, 3), picked[n * ka:].view(-1, kb, 3), b_of, na, nb
 
 
-def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None, kept=None, keep=None):
+def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None, kept=None, keep=None, auto=None):
     """Refine all placed poses of a greedy assembly jointly over every joint: pieces [K,N,3] (float32, on the GPU), table =
     match_pairs' PairTable of them, asm = assemble's Assembly of that table -> JointRefined:
 
@@ -610,8 +638,17 @@ def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None, kept=None, 
     widths for every joint, an AutoPairTable's count_f[i,j] and count_m[i,j] per joint; a table without counts is a PznError.
     keep together with kept="frozen" is a PznError; an AutoPairTable with keep is not refused.  -> TrimmedJointRefined:
     JointRefined's fields, then kept_f [J,k], kept_m [J,k] (int32: the positions into top_f[i,j] / top_m[j] kept under the
-    returned poses, ascending, -1 behind the count) and count_f, count_m [J] (int32).  Still one gather and one launch."""
-    mode = _kept_mode(kept, table, "refine_assembly", keep)
+    returned poses, ascending, -1 behind the count) and count_f, count_m [J] (int32).  Still one gather and one launch.
+
+    auto (None: everything above, bit for bit): True (AutoKeep()) or an AutoKeep(least, power) - the two counts of every joint
+    are FOUND, at every evaluation of the joint under the poses being tried (ops.joint_refine's auto,
+    pzn_joint_refine_auto_f32; include/pzn.h states the rule), no fewer than ceil(least k) rows a side by the rule of a keep
+    fraction.  The sets are the full ones of any table, as for keep; an AutoPairTable is accepted.  auto together with keep or
+    with kept is a PznError, raised before any tensor is touched.  -> AutoJointRefined: TrimmedJointRefined's fields with the
+    counts found under the returned poses in count_f, count_m, then objective and objective0 (0-d: the F that fell; score is
+    the trimmed energy at the counts found and need not fall).  Still one gather and one launch."""
+    auto = _auto_mode(auto, kept, keep, "refine_assembly")
+    mode = "auto" if auto is not None else _kept_mode(kept, table, "refine_assembly", keep)
     _clouds("refine_assembly", "K", pieces=pieces)
     K, N, _ = pieces.shape
     G0 = np.asarray(asm.G, dtype=np.float64)
@@ -642,6 +679,11 @@ def refine_assembly(pieces, table, asm, sweeps=30, joint_score=None, kept=None, 
         else:
             a = b = pieces[:0, :table.top_m.shape[1]]
             b_of = cnt_a = cnt_b = None
+        if auto is not None:
+            k = table.top_m.shape[1]
+            out = ops.joint_refine(a, b, jl, g0, mv, sweeps, b_of=b_of, auto=tuple(_keep_counts(auto, k, k, "refine_assembly")),
+                                   return_kept=True)
+            return AutoJointRefined(*(f[0] if isinstance(f, torch.Tensor) else f for f in _auto_joint_refined(out, joints)))
         if mode is not None:
             ma, mb, m_f, m_m = _joint_keep_counts(mode, table, lambda t: t[ji, jj] if J > 0 else t[:0, 0], (1, J), "refine_assembly")
             out = ops.joint_refine(a, b, jl, g0, mv, sweeps, b_of=b_of, ma=ma, mb=mb, return_kept=ma is not None)
@@ -1409,7 +1451,7 @@ def match_puzzles(model, pieces, k=128, start=None, refine=0, keep=1.0):
     return _table(codes, blk, _diagonal(pieces))
 
 
-def refine_assembly_batch(pieces, table, asm, sweeps=30, kept=None, keep=None):
+def refine_assembly_batch(pieces, table, asm, sweeps=30, kept=None, keep=None, auto=None):
     """refine_assembly for Z puzzles with no download: pieces [Z,P,N,3] (float32, on the GPU), table = match_puzzles' PairTable
     of them, asm = assemble_batch's AssemblyBatch of that table -> JointRefined whose fields carry a leading Z: G [Z,P,4,4]
     float32, score, score0, sweeps_used [Z], accepted [Z,P], joints = asm.joints (the device tensor, unused rows (-1, -1)).
@@ -1436,8 +1478,14 @@ def refine_assembly_batch(pieces, table, asm, sweeps=30, kept=None, keep=None):
     Z P^2 + Z P ones of the first form whatever the table carries, a fraction gives every row the counts ceil(f k), and "table"
     a TrimmedPairTable's kept widths or, for an AutoPairTable, count_f[z,i,j] and count_m[z,i,j] gathered on the device through
     the same a_of (an unused row gets pair (0, 0, 0)'s and is skipped).  -> TrimmedJointRefined with a leading Z: kept_f, kept_m
-    [Z,J,k] (all -1 on an unused row), count_f, count_m [Z,J].  One gather, one launch, nothing waits for the device."""
-    mode = _kept_mode(kept, table, "refine_assembly_batch", keep)
+    [Z,J,k] (all -1 on an unused row), count_f, count_m [Z,J].  One gather, one launch, nothing waits for the device.
+
+    auto: refine_assembly's keyword (None: everything above, bit for bit, with no new launch).  The full Z P^2 + Z P sets, the
+    least counts ceil(least k) known on the host, the counts of every joint found by the kernel -> AutoJointRefined with a
+    leading Z (count_f, count_m [Z,J]: 0 on an unused row; objective, objective0 [Z]).  One gather, one launch, nothing waits
+    for the device."""
+    auto = _auto_mode(auto, kept, keep, "refine_assembly_batch")
+    mode = "auto" if auto is not None else _kept_mode(kept, table, "refine_assembly_batch", keep)
     _clouds("refine_assembly_batch", "Z,P", pieces=pieces)
     Z, P, N, _ = pieces.shape
     J = P * (P - 1)
@@ -1456,6 +1504,11 @@ def refine_assembly_batch(pieces, table, asm, sweeps=30, kept=None, keep=None):
                                                          indexing="ij"))
         a, b, b_of, cnt_a, cnt_b = _joint_sets(pieces, table, z, i, j, full=mode is not None)
         b_of = a_of if b_of is None else b_of[a_of]
+        if auto is not None:
+            k = table.top_m.shape[-1]
+            out = ops.joint_refine(a, b, asm.joints, asm.G.to(torch.float32), asm.movable, sweeps, a_of=a_of, b_of=b_of,
+                                   auto=tuple(_keep_counts(auto, k, k, "refine_assembly_batch")), return_kept=True)
+            return _auto_joint_refined(out, asm.joints)
         if mode is not None:
             ma, mb, m_f, m_m = _joint_keep_counts(mode, table, lambda t: t.reshape(-1)[a_of], (Z, J), "refine_assembly_batch")
             out = ops.joint_refine(a, b, asm.joints, asm.G.to(torch.float32), asm.movable, sweeps, a_of=a_of, b_of=b_of, ma=ma, mb=mb,

@@ -33,6 +33,7 @@ SOURCES = [
     ("icprefine.hip", ["-ffp-contract=off"] + NOSLP),
     ("jointrefine.hip", ["-ffp-contract=off"] + NOSLP),
     ("jointtrim.hip", ["-ffp-contract=off"] + NOSLP),
+    ("jointauto.hip", ["-ffp-contract=off"] + NOSLP),
     ("assemblewalk.hip", ["-ffp-contract=off"] + NOSLP),
     ("assemblebeam.hip", ["-ffp-contract=off"] + NOSLP),
     ("progressive.hip", ["-ffp-contract=off"] + NOSLP),

@@ -347,7 +347,12 @@ def joint_refine_trim_supported(K, J, ka, kb):
     return bool(_lib.load().pzn_joint_refine_trim_supported(int(K), int(J), int(ka), int(kb)))
 
 
-def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None, na=None, nb=None, ma=None, mb=None, return_kept=False):
+def joint_refine_auto_supported(K, J, ka, kb, lo_a, lo_b, power):
+    return bool(_lib.load().pzn_joint_refine_auto_supported(int(K), int(J), int(ka), int(kb), int(lo_a), int(lo_b), int(power)))
+
+
+def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None, na=None, nb=None, ma=None, mb=None, return_kept=False,
+                 auto=None):
     """Z pose graphs refined in one launch (pzn_joint_refine_f32): puzzle z has the poses G0[z] [K,4,4], the mask movable[z]
     [K] (uint8 or bool) and the joint rows joints[z] [J,2] (int32 ordered pairs (i, j); a row with i < 0 is unused); row e has
     the set a[a_of[z,e]] [ka,3] in piece i's frame and b[b_of[z,e]] [kb,3] in piece j's (int64 [Z,J]; the caller keeps them
@@ -370,13 +375,26 @@ def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None, na=Non
     are a PznError.  return_kept appends kept_a [Z,J,ka] and kept_b [Z,J,kb] (int32): the rows kept under the returned poses,
     ascending, -1 behind the count and throughout a skipped row (without counts: that launch with every row kept).  With ma,
     mb None and return_kept False nothing changes: the same launch and the same tuple.
+    auto = (lo_a, lo_b, power), ints: the two counts of every joint are FOUND at every evaluation of the joint, under the poses
+    being tried (pzn_joint_refine_auto_f32, one launch of its own kernel; include/pzn.h states the rule): per direction the m in
+    [lo, k] with the smallest (prefix sum of the sorted row minima) / m^(power + 1); the joint is scored by the objective F of
+    that rule and a candidate is taken iff F falls.  auto together with any of na, nb, ma, mb is a PznError; 1 <= lo_a <= ka,
+    1 <= lo_b <= kb, 1 <= power <= 4 (PznUnsupported beyond, before any launch).  The result is then the six outputs above
+    (score, score0 and joint_score in the trimmed E at the counts found: score may exceed score0), with return_kept kept_a
+    [Z,J,ka], kept_b [Z,J,kb], and then count_a [Z,J], count_b [Z,J] (int32, 0 for a skipped row), objective [Z], objective0
+    [Z] (the sums of F under G and G0; objective <= objective0 to the bit).  auto = (ka, kb, p) is the plain launch bit for bit.
     1 <= K <= 64, J <= K (K - 1), 1 <= ka, kb <= 1024 and sweeps >= 0 (PznUnsupported beyond).  Z = 0 or J = 0 launches
     nothing and returns G0 with scores of 0.  No autograd, nothing waits for the device."""
     f32, i32, i64 = (torch.float32,), (torch.int32,), (torch.int64,)
     _no_conversion("joint_refine", (("a", a, f32), ("b", b, f32), ("G0", G0, f32), ("joints", joints, i32),
                                     ("movable", movable, (torch.uint8, torch.bool)), ("a_of", a_of, i64), ("b_of", b_of, i64),
                                     ("na", na, i32), ("nb", nb, i32), ("ma", ma, i32), ("mb", mb, i32)))
-    trim = ma is not None or mb is not None or bool(return_kept)
+    if auto is not None:
+        if any(x is not None for x in (na, nb, ma, mb)):
+            raise _lib.PznError("joint_refine: auto (counts found per joint) excludes na / nb / ma / mb (counts given)")
+        if not isinstance(auto, (tuple, list)) or len(auto) != 3 or not all(isinstance(m, int) and not isinstance(m, bool) for m in auto):
+            raise _lib.PznError(f"joint_refine: auto = (lo_a, lo_b, power) as ints; got {auto!r}")
+    trim = auto is None and (ma is not None or mb is not None or bool(return_kept))
     if trim and (na is not None or nb is not None):
         raise _lib.PznError("joint_refine: kept counts per row (ma / mb, return_kept) and point counts per set (na / nb) exclude "
                             "each other")
@@ -446,12 +464,19 @@ def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None, na=Non
     if sweeps < 0 or not (joint_refine_trim_supported if trim else joint_refine_supported)(K, J, ka, kb):
         raise _lib.PznUnsupported(f"joint_refine: K = {K}, J = {J}, ka = {ka}, kb = {kb}, sweeps = {sweeps} "
                                   "(1 <= K <= 64, J <= K (K - 1), 1 <= ka, kb <= 1024, sweeps >= 0)")
+    if auto is not None and not joint_refine_auto_supported(K, J, ka, kb, *auto):
+        raise _lib.PznUnsupported(f"joint_refine: auto = {tuple(auto)} of ka = {ka}, kb = {kb} rows (1 <= lo_a <= ka, 1 <= lo_b <= kb, "
+                                  "1 <= power <= 4)")
     dev = a.device
     kept = tuple(torch.empty((Z, J, k), dtype=torch.int32, device=dev) for k in (ka, kb)) if return_kept else ()      # (empty if Z J = 0)
+    # what the auto form alone gives: count_a, count_b, objective, objective0 (zeros where nothing is launched)
+    new = torch.zeros if Z == 0 or J == 0 else torch.empty
+    found = () if auto is None else (new((Z, J), dtype=torch.int32, device=dev), new((Z, J), dtype=torch.int32, device=dev),
+                                     new((Z,), dtype=torch.float32, device=dev), new((Z,), dtype=torch.float32, device=dev))
     if Z == 0 or J == 0:
         return (G0.clone(), torch.zeros((Z,), dtype=torch.float32, device=dev), torch.zeros((Z,), dtype=torch.float32, device=dev),
                 torch.zeros((Z, J), dtype=torch.float32, device=dev), torch.zeros((Z,), dtype=torch.int32, device=dev),
-                torch.zeros((Z, K), dtype=torch.int32, device=dev)) + kept
+                torch.zeros((Z, K), dtype=torch.int32, device=dev)) + kept + found
     G = torch.empty((Z, K, 4, 4), dtype=torch.float32, device=dev)
     score = torch.empty((Z,), dtype=torch.float32, device=dev)
     score0 = torch.empty_like(score)
@@ -460,7 +485,11 @@ def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None, na=Non
     accepted = torch.empty((Z, K), dtype=torch.int32, device=dev)
     kept_a, kept_b = kept or (None, None)
     with _on(dev):
-        if trim:
+        if auto is not None:
+            _call("pzn_joint_refine_auto_f32", _p(a), _p(maps[0]), _p(b), _p(maps[1]), _p(joints), _p(G0), _p(movable), Z, K, J, ka, kb,
+                  auto[0], auto[1], auto[2], sweeps, _p(G), _p(score), _p(score0), _p(joint_score), _p(used), _p(accepted),
+                  _p(found[2]), _p(found[3]), _p(found[0]), _p(found[1]), _p(kept_a), _p(kept_b), _stream())
+        elif trim:
             _call("pzn_joint_refine_trim_f32", _p(a), _p(maps[0]), _p(kept_counts[0]), _p(b), _p(maps[1]), _p(kept_counts[1]),
                   _p(joints), _p(G0), _p(movable), Z, K, J, ka, kb, sweeps, _p(G), _p(score), _p(score0), _p(joint_score), _p(used),
                   _p(accepted), _p(kept_a), _p(kept_b), _stream())
@@ -471,7 +500,7 @@ def joint_refine(a, b, joints, G0, movable, sweeps, a_of=None, b_of=None, na=Non
             _call("pzn_joint_refine_counts_f32", _p(a), _p(maps[0]), _p(counts[0]), _p(b), _p(maps[1]), _p(counts[1]), _p(joints),
                   _p(G0), _p(movable), Z, K, J, ka, kb, sweeps, _p(G), _p(score), _p(score0), _p(joint_score), _p(used),
                   _p(accepted), _stream())
-    return (G, score, score0, joint_score, used, accepted) + kept
+    return (G, score, score0, joint_score, used, accepted) + kept + found
 
 
 def assemble_walk_supported(K):

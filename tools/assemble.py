@@ -2,7 +2,7 @@
 assembled cloud.
 
     python tools/assemble.py --pieces pieces.npy [--ckpt model.ckpt] [--k 128] [--max-score S] [--out PREFIX] [--progressive]
-                             [--refine N] [--keep F|auto] [--joint N] [--joint-keep F|table] [--gt PREFIX_gt.npz] [--beam B] [--branch C] [--vote-weight W] [--forest]
+                             [--refine N] [--keep F|auto] [--joint N] [--joint-keep F|table] [--joint-auto [LEAST]] [--gt PREFIX_gt.npz] [--beam B] [--branch C] [--vote-weight W] [--forest]
 
 pieces.npy holds [K, N, 3] float32 (N = the model's points per piece).  Prints the score table and the edges in
 placement order, writes PREFIX_G.npy ([K,4,4], each piece into the root's frame) and PREFIX_cloud.npy ([K,N,3]).
@@ -17,6 +17,8 @@ PREFIX_G.npy and PREFIX_cloud.npy are then the refined ones, and with --gt the a
 --keep auto every joint is refined over the rows its own pair kept (refine_assembly(..., kept="frozen"): a count per joint).
 --joint-keep F|table (with --joint): the kept rows of every joint are chosen again under the joint poses, at every evaluation
 (refine_assembly(..., keep=)): the share F of the full picked sets, or the counts the table carries (--keep F < 1 or auto).
+--joint-auto [LEAST] (with --joint, exclusive with --joint-keep): the two counts of every joint are FOUND at every evaluation, under
+the joint poses (refine_assembly(..., auto=AutoKeep(least=LEAST)), LEAST = 0.25 when left out); prints the mean count per joint.
 --beam B (the table walk only, with --branch C and --vote-weight W): the beam walk of assembly.assemble_beam_batch in place of the
 greedy one - B hypotheses, each extended by its C smallest entries, a child charged W times what the other placed pieces'
 entries say against its pose -; everything after the walk is the same.
@@ -72,7 +74,8 @@ def forest(args, x, table):
         jr = assembly.refine_assembly_batch(x[None], one, fb, sweeps=args.joint, **joint_kw(args))
         G = jr.G[0].double()
         print(f"joint refinement over {int(fb.n_joints[0])} joints: summed score {float(jr.score0[0]):.6f} -> {float(jr.score[0]):.6f}, "
-              f"{int(jr.sweeps_used[0])} sweeps, candidates taken per piece {jr.accepted[0].tolist()}")
+              f"{int(jr.sweeps_used[0])} sweeps, candidates taken per piece {jr.accepted[0].tolist()}"
+              + (mean_counts(jr) if args.joint_auto is not None else ""))
     np.save(args.out + "_G.npy", G.cpu().numpy())
     np.save(args.out + "_component.npy", np.asarray(comp, dtype=np.int32))
     np.save(args.out + "_cloud.npy", assembly.apply(x, G).cpu().numpy())
@@ -87,9 +90,19 @@ def joint_keep_arg(text):
 def joint_kw(args):
     """The keywords of the joint refinement: --joint-keep chooses the kept rows again under the joint poses (keep=); without it a
     table made with --keep auto is refined over the rows its pairs kept (kept="frozen")."""
+    if args.joint_auto is not None:
+        from puzzlenet_amd import assembly
+        return {"auto": assembly.AutoKeep(least=args.joint_auto)}
     if args.joint_keep is not None:
         return {"keep": args.joint_keep}
     return {"kept": "frozen" if args.keep == "auto" else None}
+
+
+def mean_counts(jr):
+    """--joint-auto: the mean counts found per joint, over the used joint rows (an unused row holds 0) -> text."""
+    live = jr.count_f > 0
+    n = max(int(live.sum()), 1)
+    return f", mean count per joint {float(jr.count_f[live].sum()) / n:.1f} fixed / {float(jr.count_m[live].sum()) / n:.1f} moved of {jr.kept_f.shape[-1]}"
 
 
 def keep_arg(text):
@@ -115,6 +128,10 @@ def main():
     ap.add_argument("--joint-keep", type=joint_keep_arg, default=None, help="with --joint: the kept rows of every joint are chosen again "
                     "under the joint poses - F: the share in (0, 1] of the picked boundary points of each side that counts, or the "
                     "word table: the counts the table carries (--keep F < 1 or auto); the full picked sets are read, not the table's kept rows")
+    ap.add_argument("--joint-auto", type=float, nargs="?", const=0.25, default=None, metavar="LEAST", help="with --joint, exclusive with "
+                    "--joint-keep: the two counts of every joint are found at every evaluation, under the joint poses (refine_assembly's "
+                    "auto=AutoKeep(least=LEAST); LEAST: the least share in (0, 1] kept of each side, 0.25 when left out); prints the mean "
+                    "count per joint beside the scores")
     ap.add_argument("--gt", default=None, help="PREFIX_gt.npz of tools/fracture.py: score the assembly against the truth")
     ap.add_argument("--beam", type=int, default=0, help="B: the beam walk with B hypotheses in place of the greedy walk (1 .. 8; 0: greedy)")
     ap.add_argument("--branch", type=int, default=4, help="C: with --beam, the candidates every hypothesis is extended by (1 .. 8)")
@@ -134,6 +151,8 @@ def main():
     if args.joint_keep is not None and (not args.joint or (args.joint_keep != "table" and not 0.0 < args.joint_keep <= 1.0)
                                         or (args.joint_keep == "table" and args.keep == 1.0)):
         sys.exit("--joint-keep: with --joint N, a share in (0, 1] or the word table (which needs --keep F < 1 or auto)")
+    if args.joint_auto is not None and (not args.joint or args.joint_keep is not None or not 0.0 < args.joint_auto <= 1.0):
+        sys.exit("--joint-auto: with --joint N and without --joint-keep, a least share in (0, 1]")
 
     if not torch.cuda.is_available():
         sys.exit("tools/assemble.py needs a GPU: puzzlenet_amd has no CPU path")
@@ -209,7 +228,8 @@ def main():
         jr = assembly.refine_assembly(x, table, result, sweeps=args.joint, **joint_kw(args))
         G = jr.G.double().cpu().numpy()
         print(f"joint refinement over {len(jr.joints)} joints: summed score {float(jr.score0):.6f} -> {float(jr.score):.6f}, "
-              f"{int(jr.sweeps_used)} sweeps, candidates taken per piece {jr.accepted.tolist()}")
+              f"{int(jr.sweeps_used)} sweeps, candidates taken per piece {jr.accepted.tolist()}"
+              + (mean_counts(jr) if args.joint_auto is not None else ""))
     np.save(args.out + "_G.npy", G)
     np.save(args.out + "_cloud.npy", assembly.apply(x, G).cpu().numpy())
     print(f"wrote {args.out}_G.npy, {args.out}_cloud.npy")

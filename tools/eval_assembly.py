@@ -1,7 +1,7 @@
 """The assembly score of a model as a mean over a batch of fractured puzzles, with one download at the end:
 
     python tools/eval_assembly.py [--batch 64] [--pieces 8] [--m 20000] [--k 128] [--candidates 16] [--mag 0.8] [--seed 0]
-                                  [--curvature 2.0] [--ckpt model.ckpt] [--refine N] [--keep F|auto] [--joint N] [--joint-keep F|table] [--max-score S]
+                                  [--curvature 2.0] [--ckpt model.ckpt] [--refine N] [--keep F|auto] [--joint N] [--joint-keep F|table] [--joint-auto [LEAST]] [--max-score S]
                                   [--progressive] [--time R] [--json out.json] [--beam B] [--branch C] [--vote-weight W]
                                   [--objects Q]
 
@@ -17,7 +17,9 @@ downloaded once.  --beam B (with --branch C, --vote-weight W) also runs the beam
 --joint both before and after the joint refinement of its own result.  Prints the means over the valid fractures: part accuracy, edge precision, and over the placed pieces other
 than the root the rotation error in degrees, the translation error and the mean squared distance; with --joint both before and
 after the joint refinement; --joint-keep F|table has that refinement choose the kept rows of every joint again under the joint
-poses (refine_assembly_batch(..., keep=): the share F of the full picked sets, or the counts the table carries).  --progressive reports the same means for the progressive walk (assemble_progressive_batch: all
+poses (refine_assembly_batch(..., keep=): the share F of the full picked sets, or the counts the table carries); --joint-auto
+[LEAST] (exclusive with --joint-keep) has it FIND the two counts of every joint at every evaluation, under the joint poses
+(refine_assembly_batch(..., auto=AutoKeep(least=LEAST)), LEAST = 0.25 when left out) and prints the mean count per joint.  --progressive reports the same means for the progressive walk (assemble_progressive_batch: all
 puzzles in lockstep, P - 1 rounds, every round one choice launch, one merge launch, one encoder batch and two blocked pair blocks)
 beside the greedy one, on the same fractures and table starts, still with the one download.  --time R (with --progressive) then
 times the batched progressive walk and, beside it, a loop of assemble_progressive over the same puzzles - the per-puzzle path, which
@@ -81,7 +83,7 @@ def sort_piles(args, model, f, dev):
         mean = lambda x: torch.nansum(x.double() * valid) / (valid * ~torch.isnan(x.double())).sum()
         return torch.stack([mean(x) for x in (ev.pair_precision, ev.pair_recall, ev.pair_pose_recall, ev.n_components, ev.exact)])
 
-    labels, rows, heads = [], [], [valid.sum()[None]]
+    labels, rows, heads, counts = [], [], [valid.sum()[None]], []
     for label, asm in walks:
         labels.append(label)
         rows.append(row(asm.G, asm))
@@ -91,10 +93,12 @@ def sort_piles(args, model, f, dev):
             labels.append(f"{label.split(' (')[0]} after the joint refinement")
             rows.append(row(jr.G, asm))
             extra = torch.stack((jr.score0.double().mean(), jr.score.double().mean(), jr.sweeps_used.double().mean()))
+            if args.joint_auto is not None:
+                counts.append(mean_counts(jr))
         heads.append(torch.cat((torch.stack((asm.n_joints.double().mean(), asm.n_edges.double().mean())), extra)))
     if args.beam:
         heads.append((walks[1][1].edges == forest.edges).all(dim=2).all(dim=1).double().mean()[None])
-    host = torch.cat(heads + rows).cpu().tolist()                                   # the one download
+    host = torch.cat(heads + rows + counts).cpu().tolist()                          # the one download (the mean counts at its end)
     print(f"{Z} piles of {Q} objects, {K} pieces of {f.pieces.shape[2]} points each: {int(host[0])} valid piles")
     at = 1 + 5 * len(walks) + (1 if args.beam else 0)
     names = ("pair precision", "pair recall", "pair pose recall", "components", "share sorted exactly")
@@ -103,7 +107,9 @@ def sort_piles(args, model, f, dev):
     for n, (label, _) in enumerate(walks):
         h = host[1 + 5 * n:6 + 5 * n]
         print(f"{label.split(' (')[0]}: per pile {h[1]:.2f} edges, {h[0]:.1f} joints"
-              + (f"; joint refinement: mean summed score {h[2]:.6f} -> {h[3]:.6f}, {h[4]:.1f} sweeps" if args.joint else ""))
+              + (f"; joint refinement: mean summed score {h[2]:.6f} -> {h[3]:.6f}, {h[4]:.1f} sweeps" if args.joint else "")
+              + (f", mean count per joint {host[len(host) - 2 * len(walks) + 2 * n]:.1f} fixed / "
+                 f"{host[len(host) - 2 * len(walks) + 2 * n + 1]:.1f} moved of {args.k}" if counts else ""))
     if args.beam:
         print(f"forest beam: the forest walk's edges in {100 * host[at - 1]:.1f} % of the piles")
 
@@ -116,9 +122,18 @@ def joint_keep_arg(text):
 def joint_kw(args):
     """The keywords of the joint refinement: --joint-keep chooses the kept rows again under the joint poses (keep=); without it a
     table made with --keep auto is refined over the rows its pairs kept (kept="frozen")."""
+    if args.joint_auto is not None:
+        from puzzlenet_amd import assembly
+        return {"auto": assembly.AutoKeep(least=args.joint_auto)}
     if args.joint_keep is not None:
         return {"keep": args.joint_keep}
     return {"kept": "frozen" if args.keep == "auto" else None}
+
+
+def mean_counts(jr):
+    """--joint-auto: the mean counts found per joint over the used joint rows (an unused row holds 0), on the device -> [2]."""
+    live = (jr.count_f > 0).double()
+    return torch.stack(((jr.count_f.double() * live).sum(), (jr.count_m.double() * live).sum())) / live.sum().clamp(min=1.0)
 
 
 def keep_arg(text):
@@ -147,6 +162,10 @@ def main():
     ap.add_argument("--joint-keep", type=joint_keep_arg, default=None, help="with --joint: the kept rows of every joint are chosen again "
                     "under the joint poses - F: the share in (0, 1] of the picked boundary points of each side that counts, or the "
                     "word table: the counts the table carries (--keep F < 1 or auto); the full picked sets are read, not the table's kept rows")
+    ap.add_argument("--joint-auto", type=float, nargs="?", const=0.25, default=None, metavar="LEAST", help="with --joint, exclusive with "
+                    "--joint-keep: the two counts of every joint are found at every evaluation, under the joint poses "
+                    "(refine_assembly_batch's auto=AutoKeep(least=LEAST); LEAST: the least share in (0, 1] kept of each side, 0.25 when "
+                    "left out); prints the mean count per joint beside the scores")
     ap.add_argument("--max-score", type=float, default=None, help="stop placing pieces above this boundary distance")
     ap.add_argument("--progressive", action="store_true", help="also the progressive walk of the whole batch, in lockstep")
     ap.add_argument("--time", type=int, default=0, help="with --progressive: repeats of the timed batched walk and per-puzzle loop")
@@ -166,6 +185,8 @@ def main():
     if args.joint_keep is not None and (not args.joint or (args.joint_keep != "table" and not 0.0 < args.joint_keep <= 1.0)
                                         or (args.joint_keep == "table" and args.keep == 1.0)):
         sys.exit("--joint-keep: with --joint N, a share in (0, 1] or the word table (which needs --keep F < 1 or auto)")
+    if args.joint_auto is not None and (not args.joint or args.joint_keep is not None or not 0.0 < args.joint_auto <= 1.0):
+        sys.exit("--joint-auto: with --joint N and without --joint-keep, a least share in (0, 1]")
     if args.keep != "auto" and not 0.0 < args.keep <= 1.0:
         sys.exit("--keep: a share in (0, 1] or the word auto")
     if args.time < 0 or (args.time and not args.progressive) or (args.json and not args.time):
@@ -204,8 +225,11 @@ def main():
         asm = assembly.assemble_batch(table.score, table.T, max_score=args.max_score)
         rows = [metrics(assembly.evaluate_batch(asm.G, asm.placed, f.pose, f.rest, asm.root, asm.edges, asm.n_edges, f.mates), asm, f.ok)]
         extra = torch.zeros(3, dtype=torch.float64, device=dev)
+        counts = []
         if args.joint:
             jr = assembly.refine_assembly_batch(f.pieces, table, asm, sweeps=args.joint, **joint_kw(args))
+            if args.joint_auto is not None:
+                counts.append(mean_counts(jr))
             rows.append(metrics(assembly.evaluate_batch(jr.G, asm.placed, f.pose, f.rest, asm.root, asm.edges, asm.n_edges, f.mates),
                                 asm, f.ok))
             extra = torch.stack((jr.score0.double().mean(), jr.score.double().mean(), jr.sweeps_used.double().mean()))
@@ -227,7 +251,7 @@ def main():
             same = (bm.edges == asm.edges).all(dim=2).all(dim=1).double().mean()
             rows.append(torch.stack((bm.n_edges.double().mean(), same)))
         head = torch.stack((f.ok.double().sum(), asm.n_joints.double().mean(), asm.n_edges.double().mean()))
-        host = torch.cat([head, extra] + rows).cpu().tolist()                       # the one download
+        host = torch.cat([head, extra] + rows + counts).cpu().tolist()              # the one download (the mean counts at its end)
     print(f"{B} clouds of {M} points into {P} pieces of {N}: {int(host[0])} valid fractures; per puzzle {host[2]:.2f} edges, "
           f"{host[1]:.1f} joints")
     names = ("part accuracy", "edge precision", "rotation (deg)", "translation", "msd", "share placed")
@@ -239,7 +263,8 @@ def main():
             + ((("beam walk after the joint refinement", at_b + 6),) if args.beam and args.joint else ()):
         print(f"{label}: " + ", ".join(f"{n} {v:.6g}" for n, v in zip(names, host[at:at + 6])))
     if args.joint:
-        print(f"joint refinement: mean summed score {host[3]:.6f} -> {host[4]:.6f}, {host[5]:.1f} sweeps")
+        print(f"joint refinement: mean summed score {host[3]:.6f} -> {host[4]:.6f}, {host[5]:.1f} sweeps"
+              + (f", mean count per joint {host[-2]:.1f} fixed / {host[-1]:.1f} moved of {args.k}" if counts else ""))
     if args.progressive:
         print(f"progressive walk: per puzzle {host[at_p + 6]:.2f} edges in {P - 1} lockstep rounds")
     if args.beam:
