@@ -474,6 +474,40 @@ int pzn_progressive_round_f32(const float* score, const float* T, double max_sco
                               int32_t* edges, float* edge_score, uint8_t* took, int64_t* pick,
                               pzn_stream_t stream);
 
+/* The pose graph of Z progressive walks, read off their ledgers (no counterpart in the reference; the step between
+ * assembly.ProgressiveBatch and pzn_joint_refine_counts_f32; assembly.progressive_joints_rule is the numpy statement): one launch,
+ * one workgroup per (round, puzzle), no workspace, no atomics, nothing waits for the device.
+ * pieces[Z,P,N,3] fp32: the original pieces, each in its own frame.  G[Z,P,4,4] float64: the ledger's poses, piece p into the
+ * frame of its part.  dropped[R,Z,2,k,2] int64: per round and puzzle the two lists of a merge, side 0 the fixed side and side 1
+ * the moved side, k entries (piece, row) each in original pieces and rows.  least >= 1.
+ * Per round r and puzzle z:
+ * 1. An entry is valid iff 0 <= piece < P and 0 <= row < N; every other entry is skipped (the -1 rows of a puzzle that made no
+ *    merge, -1 padding inside a list).  A round with a side that holds no valid entry yields nothing.
+ * 2. The root-frame point of a valid entry, float64: the fp32 point widened, x' = ((g00 x + g01 y) + g02 z) + g03 with every
+ *    product and sum rounded on its own, rows 1 and 2 likewise, g = G[z,piece].
+ * 3. Every valid fixed entry takes its nearest valid moved entry and every valid moved entry its nearest valid fixed entry, by
+ *    d2 = (dx dx + dy dy) + dz dz in float64, every operation rounded on its own; of equal distances the lowest position in the
+ *    list.  (Coordinates are finite: a NaN distance is never the smaller one.)
+ * 4. For a fixed piece p and a moved piece q != p: A(p,q) = the fixed entries on piece p whose nearest moved entry lies on q,
+ *    B(p,q) = the moved entries on piece q whose nearest fixed entry lies on p, both in ascending list position.  Every valid
+ *    entry is in at most one set, and the two sets of a joint face each other; they are chosen once, under G, and not trimmed.
+ * 5. The joint (p, q) is emitted iff |A| >= least and |B| >= least, into row e = hi (hi - 1) / 2 + lo of the unordered pair
+ *    (lo = min(p,q), hi = max(p,q)): J = P (P - 1) / 2 rows a puzzle.
+ * A walk's own ledger puts every unordered pair of pieces on opposite sides in exactly one round, the one that merges their two
+ * parts, so no row is written twice.  A caller's own `dropped` that breaks this is NOT checked: the numpy statement keeps the
+ * later round, here the row's contents are then those of either round, element by element.
+ * Out, all initialised by the caller (joints and rows_* to -1, the others to 0) and written only where a joint is emitted:
+ * joints[Z,J,2] int32 rows (p, q), p the fixed piece; a[Z,J,k,3], b[Z,J,k,3] fp32, the points of A and B as read from pieces, in
+ * their own piece's frame; rows_a[Z,J,k], rows_b[Z,J,k] int64, the row in the piece; na[Z,J], nb[Z,J] int32, |A| and |B|.  With
+ * the sets of stride k and the counts na / nb this is the input of pzn_joint_refine_counts_f32.  The same bits on every run.
+ * 2 <= P <= 64, 1 <= k <= 1024 (pzn_progressive_joints_supported: 1 / 0; 64 k bytes of LDS), R >= 1: PZN_EUNSUPPORTED otherwise,
+ * before any launch; Z = 0 is a success that launches nothing. */
+int pzn_progressive_joints_supported(int P, int k);
+int pzn_progressive_joints_f32(const float* pieces, const double* G, const int64_t* dropped,
+                               int R, int Z, int P, int N, int k, int least,
+                               int32_t* joints, float* a, float* b, int32_t* na, int32_t* nb,
+                               int64_t* rows_a, int64_t* rows_b, pzn_stream_t stream);
+
 /* pointnet_util.py:118-119  dists.argsort()[:, :, :K] fused with the distance:
  * idx[B,S,K] = the K nearest points of xyz[B,N,3] to each new_xyz[B,S,3],
  * ascending by (distance, index) == a stable ascending sort.  K <= N. */

@@ -69,7 +69,10 @@ computed again (two pair_block calls).  ProgressiveAssembler walks one puzzle wi
 device: one ops.progressive_round launch chooses all Z merges and books them in a float64 ledger on the device
 (csrc/progressive.hip; progressive_round_rule is its numpy statement; slots die instead of being compacted, so shapes never
 change), one ops.merge_resample launch, one encode_pieces call and two pair_block_batch calls.  Not done there: dead slots
-are still paired, stopped puzzles are still encoded, and a progressive part is not refined jointly.
+are still paired and stopped puzzles are still encoded.  refine_progressive / refine_progressive_batch are the step after
+such a walk: the rows every merge left out say which pieces meet across it, one launch reads the pose graph off them
+(ops.progressive_joints, csrc/progjoints.hip; progressive_joints_rule is its numpy statement) and one ops.joint_refine
+launch closes it, every piece but its part's frame piece moving.
 
 Inference only: eval mode, torch.no_grad(), fp32, one GPU.  Out of scope: any training on merged parts or on more than two
 pieces, a beam or several merges per round of the progressive walk, undoing a merge, and more than one GPU.
@@ -1866,8 +1869,9 @@ class ProgressiveBatch:
     of its state: what a round computed for it is discarded through torch.where(took, new, old).  Every table entry outside row i,
     column i and the dead slots is kept bit for bit.
 
-    Not done here: dead slots are still paired every round (up to half of the block work is wasted), stopped puzzles are still
-    encoded, and a progressive part is not refined jointly.  Inference only: eval mode, no_grad, fp32, one GPU."""
+    Not done here: dead slots are still paired every round (up to half of the block work is wasted) and stopped puzzles are
+    still encoded.  The finished parts are refined jointly by refine_progressive_batch(pieces, result), from the dropped rows
+    the result carries (drop_matched=True).  Inference only: eval mode, no_grad, fp32, one GPU."""
 
     def __init__(self, model, pieces, k=128, start=None, max_score=None, drop_matched=True, generator=None, merge_starts=None,
                  refine=0, count=None):
@@ -2007,3 +2011,160 @@ def assemble_progressive_batch(model, pieces, k=128, start=None, max_score=None,
                                merge_starts=None, refine=0, count=None):
     """ProgressiveBatch(...).run(): the P - 1 lockstep rounds of Z puzzles -> ProgressiveBatchResult."""
     return ProgressiveBatch(model, pieces, k, start, max_score, drop_matched, generator, merge_starts, refine, count).run()
+
+
+# --------------------------------------------------------------------------- progressive assembly, the joint refinement of a finished part
+
+# refine_progressive / refine_progressive_batch: JointRefined's fields (G [...,P,4,4] float32, score, score0, sweeps_used [...],
+# accepted [...,P], joints [...,J,2] int32 rows (fixed piece, moved piece), unused rows (-1, -1)), then joint_score [...,J], count_f,
+# count_m [...,J] (int32: the points of either side of a joint, 0 on an unused row) and rows_f, rows_m [...,J,k] (int64: the rows
+# of pieces[p] and pieces[q] they are, -1 behind the count); J = P (P - 1) / 2
+ProgressiveJointRefined = collections.namedtuple(
+    "ProgressiveJointRefined", JointRefined._fields + ("joint_score", "count_f", "count_m", "rows_f", "rows_m"))
+
+
+def progressive_joints_rule(pieces, G, dropped, least=3):
+    """The numpy statement of ops.progressive_joints (csrc/progjoints.hip, the rule in include/pzn.h), which is held to it bit for
+    bit: the pose graph of Z progressive walks read off their ledgers.  pieces [Z,P,N,3] (read as float32), G [Z,P,4,4] (float64),
+    dropped [R,Z,2,k,2] (int64: per round and side - fixed, moved - the (piece, row) pairs of a merge), least >= 1 -> (joints
+    [Z,J,2] int32, a, b [Z,J,k,3] float32, na, nb [Z,J] int32, rows_a, rows_b [Z,J,k] int64), J = P (P - 1) / 2.
+
+    Per round and puzzle: an entry with 0 <= piece < P and 0 <= row < N is valid, every other one is skipped, and a round with a
+    side without a valid entry yields nothing.  A valid entry's point goes to its part's frame in float64, x' = ((g00 x + g01 y) +
+    g02 z) + g03 with every operation rounded on its own; every valid entry takes the nearest valid entry of the other side by
+    d2 = (dx dx + dy dy) + dz dz, ties to the lowest list position.  For a fixed piece p and a moved piece q != p, A = the fixed
+    entries on p whose nearest lies on q, B = the moved entries on q whose nearest lies on p, both in list order; with |A| >= least
+    and |B| >= least the joint (p, q) fills row hi (hi - 1) / 2 + lo of the pair {lo, hi}.  Unused rows: joints -1, points 0,
+    rows -1, counts 0.  A row that two rounds emit keeps the later round's."""
+    X, Gd, D = _as_np(pieces, np.float32), _as_np(G, np.float64), _as_np(dropped, np.int64)
+    if X.ndim != 4 or X.shape[3] != 3 or X.shape[1] < 2 or Gd.shape != X.shape[:2] + (4, 4) or D.ndim != 5 \
+            or (D.shape[1], D.shape[2], D.shape[4]) != (X.shape[0], 2, 2) or int(least) < 1:
+        raise ValueError(f"progressive_joints_rule expects pieces[Z,P,N,3] with P >= 2, G[Z,P,4,4], dropped[R,Z,2,k,2] and "
+                         f"least >= 1; got {X.shape}, {Gd.shape}, {D.shape}, {least}")
+    Z, P, N = X.shape[:3]
+    R, k = D.shape[0], D.shape[3]
+    J = P * (P - 1) // 2
+    joints = np.full((Z, J, 2), -1, dtype=np.int32)
+    pts = [np.zeros((Z, J, k, 3), dtype=np.float32) for _ in range(2)]
+    cnt = [np.zeros((Z, J), dtype=np.int32) for _ in range(2)]
+    rows = [np.full((Z, J, k), -1, dtype=np.int64) for _ in range(2)]
+    for r in range(R):
+        for z in range(Z):
+            ok, own, row, moved = [], [], [], []
+            for s in range(2):
+                pi, ro = D[r, z, s, :, 0], D[r, z, s, :, 1]
+                v = (pi >= 0) & (pi < P) & (ro >= 0) & (ro < N)
+                x = X[z, np.where(v, pi, 0), np.where(v, ro, 0)].astype(np.float64)      # [k,3]
+                g = Gd[z, np.where(v, pi, 0)]                                                # [k,4,4]
+                moved.append(np.stack([((g[:, u, 0] * x[:, 0] + g[:, u, 1] * x[:, 1]) + g[:, u, 2] * x[:, 2]) + g[:, u, 3]
+                                       for u in range(3)], axis=1))
+                ok.append(v), own.append(pi), row.append(ro)
+            if not ok[0].any() or not ok[1].any():
+                continue
+            facing = []
+            for s in range(2):
+                there = np.flatnonzero(ok[1 - s])
+                d = moved[s][:, None, :] - moved[1 - s][None, there, :]
+                d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+                facing.append(own[1 - s][there[np.argmin(d2, axis=1)]])                      # (argmin: the first of equal minima)
+            sets = [{}, {}]                                                                  # (p, q) -> list positions, ascending
+            for s in range(2):
+                for e in np.flatnonzero(ok[s] & (own[s] != facing[s])):
+                    pq = (int(own[s][e]), int(facing[s][e])) if s == 0 else (int(facing[s][e]), int(own[s][e]))
+                    sets[s].setdefault(pq, []).append(int(e))
+            for (p, q), A in sets[0].items():
+                B = sets[1].get((p, q), [])
+                if len(A) < least or len(B) < least:
+                    continue
+                lo, hi = min(p, q), max(p, q)
+                e = hi * (hi - 1) // 2 + lo
+                joints[z, e] = (p, q)
+                for s, piece, members in ((0, p, A), (1, q, B)):
+                    pts[s][z, e], rows[s][z, e] = 0, -1
+                    pts[s][z, e, :len(members)] = X[z, piece, row[s][members]]
+                    rows[s][z, e, :len(members)] = row[s][members]
+                    cnt[s][z, e] = len(members)
+    return joints, pts[0], pts[1], cnt[0], cnt[1], rows[0], rows[1]
+
+
+def _check_progressive_refine(who, P, k, least):
+    """What both refine_progressive forms ask before they touch a tensor."""
+    if isinstance(least, bool) or not isinstance(least, numbers.Integral) or least < 1:
+        raise _lib.PznError(f"{who}: least must be an integer >= 1; got {least!r}")
+    if not ops.progressive_joints_supported(P, k):
+        raise _lib.PznUnsupported(f"{who}: P = {P} pieces, k = {k} dropped rows a side (2 <= P <= 64, 1 <= k <= 1024)")
+    if not ops.joint_refine_supported(P, P * (P - 1) // 2, k, k):
+        raise _lib.PznUnsupported(f"{who}: a pose graph of P = {P} pieces, {P * (P - 1) // 2} joints and sets of k = {k} points is "
+                                  "not one ops.joint_refine takes")
+
+
+_NO_DROPPED = ("{who}: the walk recorded no dropped rows (drop_matched=False): the joints of a progressive part are read off the "
+               "(piece, row) pairs its merges left out, and there is nothing else to read them from")
+
+
+def refine_progressive_batch(pieces, result, sweeps=30, least=3):
+    """The joint refinement of what assemble_progressive_batch built, with no download: pieces [Z,P,N,3] (float32, on the GPU,
+    the ORIGINAL pieces), result = the walk's ProgressiveBatchResult -> ProgressiveJointRefined with a leading Z.
+
+    The ledger composes one pose per merge, so G[p] carries the summed error of every merge between piece p and its part's frame
+    piece, and a merge of two parts knows every pair of pieces that meet across it at once: result.dropped holds the rows.  One
+    ops.progressive_joints launch turns them into a pose graph (its rule: progressive_joints_rule; a joint needs `least` points
+    on either side; the sets are chosen once, under result.G, and not trimmed again - the choice of kept="frozen"), one
+    ops.joint_refine launch with a count per set closes it: G0 = result.G rounded to float32, movable[z,p] = part[z,p] != p - a
+    part lives in its slot piece's frame, so frame pieces stay, as do dead slots and single pieces.  Every part of a puzzle is
+    refined in its own frame in the same launch.  The result feeds evaluate_batch(r.G, result.placed, pose, rest, result.root,
+    ...) as refine_assembly_batch's does.  Nothing waits for the device.
+
+    A result without dropped rows (drop_matched=False) is a PznError; P or k outside 2 <= P <= 64, 1 <= k <= 1024 is
+    PznUnsupported; both before any tensor is touched."""
+    who = "refine_progressive_batch"
+    if result.dropped is None:
+        raise _lib.PznError(_NO_DROPPED.format(who=who))
+    _clouds(who, "Z,P", pieces=pieces)
+    Z, P, N, _ = pieces.shape
+    if result.dropped.dim() != 5 or tuple(result.G.shape) != (Z, P, 4, 4) or tuple(result.part.shape) != (Z, P) \
+            or result.dropped.shape[1] != Z:
+        raise _lib.PznError(f"{who}: the result is not that of Z = {Z} puzzles of P = {P} pieces: G {tuple(result.G.shape)}, part "
+                            f"{tuple(result.part.shape)}, dropped {tuple(result.dropped.shape)}")
+    k = result.dropped.shape[3]
+    _check_progressive_refine(who, P, k, least)
+    J = P * (P - 1) // 2
+    with torch.no_grad():
+        slot = torch.arange(P, dtype=result.part.dtype, device=result.part.device)
+        movable = result.part != slot[None, :]
+        joints, a, b, na, nb, rows_a, rows_b = ops.progressive_joints(pieces, result.G, result.dropped, least)
+        G, score, score0, joint_score, used, accepted = ops.joint_refine(
+            a.view(Z * J, k, 3), b.view(Z * J, k, 3), joints, result.G.float(), movable, sweeps, na=na.view(Z * J), nb=nb.view(Z * J))
+    return ProgressiveJointRefined(G, score, score0, used, accepted, joints, joint_score, na, nb, rows_a, rows_b)
+
+
+def progressive_frames(K, edges):
+    """The frame piece of every piece's part from a walk's edges (rows that start with (label_i, label_j): the labels of the fixed
+    and of the moved part, a label being a member piece) -> [K] int64: a merged part stays in the fixed part's frame."""
+    frame = list(range(K))
+    for edge in edges:
+        fi, fj = frame[int(edge[0])], frame[int(edge[1])]
+        frame = [fi if f == fj else f for f in frame]
+    return np.array(frame, dtype=np.int64)
+
+
+def refine_progressive(pieces, prog, sweeps=30, least=3):
+    """refine_progressive_batch for one puzzle: pieces [K,N,3] (float32, on the GPU), prog = assemble_progressive's Progressive ->
+    ProgressiveJointRefined without the leading axis.  It IS the batched function at Z = 1, so it gives its bits: dropped is
+    stacked from prog.edges, and the frame piece of every part is rebuilt on the host from the edge labels (progressive_frames)."""
+    who = "refine_progressive"
+    if any(e[3] is None or e[4] is None for e in prog.edges):
+        raise _lib.PznError(_NO_DROPPED.format(who=who))
+    _clouds(who, "K", pieces=pieces)
+    K = pieces.shape[0]
+    if not prog.edges:
+        raise _lib.PznError(f"{who}: the walk made no merge, so there is no part to refine")
+    _check_progressive_refine(who, K, prog.edges[0][3].shape[0], least)
+    dev = pieces.device
+    with torch.no_grad():
+        dropped = torch.stack([torch.stack((e[3], e[4]), dim=0) for e in prog.edges], dim=0)[:, None].to(dev)      # [R,1,2,k,2]
+        part = torch.from_numpy(progressive_frames(K, prog.edges)).to(torch.int32)[None].to(dev)
+        result = ProgressiveBatchResult(torch.as_tensor(np.asarray(prog.G, dtype=np.float64))[None].to(dev), None, None, None,
+                                        None, None, part, None, None, None, None, dropped)
+    out = refine_progressive_batch(pieces[None], result, sweeps, least)
+    return ProgressiveJointRefined(*(f[0] for f in out))

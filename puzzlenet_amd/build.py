@@ -37,6 +37,7 @@ SOURCES = [
     ("assemblewalk.hip", ["-ffp-contract=off"] + NOSLP),
     ("assemblebeam.hip", ["-ffp-contract=off"] + NOSLP),
     ("progressive.hip", ["-ffp-contract=off"] + NOSLP),
+    ("progjoints.hip", ["-ffp-contract=off"] + NOSLP),
     ("knn.hip", ["-ffp-contract=off"]),
     ("group.hip", ["-ffp-contract=off"] + NOSLP),
     ("emd.hip", NOSLP),

@@ -6,6 +6,7 @@ pointers.  Inputs must live on a HIP device; there is no CPU path.
 """
 import collections
 import ctypes
+import numbers
 import os
 import weakref
 
@@ -729,6 +730,53 @@ def progressive_round(score, T, state, max_score=None):
             _call("pzn_progressive_round_f32", _p(score), _p(T), max_score, Z, P, _p(s.alive), _p(s.part), _p(s.G), _p(s.done),
                   _p(s.n_edges), _p(s.edges), _p(s.edge_score), _p(took), _p(pick), _stream())
     return took, pick
+
+
+def progressive_joints_supported(P, k):
+    return bool(_lib.load().pzn_progressive_joints_supported(int(P), int(k)))
+
+
+def progressive_joints(pieces, G, dropped, least=3):
+    """The pose graph of Z progressive walks read off their ledgers, one launch (pzn_progressive_joints_f32; include/pzn.h states
+    the rule, assembly.progressive_joints_rule is its numpy statement): pieces [Z,P,N,3] float32 (the original pieces), G [Z,P,4,4]
+    float64 (the ledger's poses), dropped [R,Z,2,k,2] int64 (per round and side - fixed, moved - the (piece, row) pairs a merge
+    left out; entries outside the pieces and rows, such as -1, are skipped), least >= 1 (a joint needs that many points on either
+    side) -> (joints [Z,J,2] int32 rows (p, q) with p the fixed piece, unused rows (-1, -1); a, b [Z,J,k,3] float32, the sets of a
+    joint in their own piece's frame, zero behind the count; na, nb [Z,J] int32, 0 on an unused row; rows_a, rows_b [Z,J,k] int64,
+    the rows in the piece, -1 behind the count), J = P (P - 1) / 2, row e of the pair {lo, hi} = hi (hi - 1) / 2 + lo.  With the
+    sets viewed as [Z J,k,3] this is what joint_refine(..., na=, nb=) takes.  A tensor of another dtype is refused, not converted.
+    2 <= P <= 64, 1 <= k <= 1024, R >= 1 (PznUnsupported beyond).  Z = 0 launches nothing.  No autograd, nothing waits for the
+    device."""
+    _no_conversion("progressive_joints", (("pieces", pieces, (torch.float32,)), ("G", G, (torch.float64,)),
+                                          ("dropped", dropped, (torch.int64,))))
+    pieces, G, dropped = _f32(pieces, "pieces"), _req(G, torch.float64, "G"), _i64(dropped, "dropped")
+    if pieces.dim() != 4 or pieces.shape[3] != 3:
+        raise _lib.PznError(f"progressive_joints: expected pieces[Z,P,N,3]; got {tuple(pieces.shape)}")
+    Z, P, N, _ = pieces.shape
+    if tuple(G.shape) != (Z, P, 4, 4):
+        raise _lib.PznError(f"progressive_joints: expected G[{Z},{P},4,4]; got {tuple(G.shape)}")
+    if dropped.dim() != 5 or dropped.shape[1] != Z or dropped.shape[2] != 2 or dropped.shape[4] != 2:
+        raise _lib.PznError(f"progressive_joints: expected dropped[R,{Z},2,k,2]; got {tuple(dropped.shape)}")
+    if isinstance(least, bool) or not isinstance(least, numbers.Integral) or least < 1:
+        raise _lib.PznError(f"progressive_joints: least must be an integer >= 1; got {least!r}")
+    R, k = dropped.shape[0], dropped.shape[3]
+    if not progressive_joints_supported(P, k) or R < 1 or N < 1:
+        raise _lib.PznUnsupported(f"progressive_joints: R = {R} rounds of P = {P} pieces of N = {N} rows, k = {k} entries a side "
+                                  "(2 <= P <= 64, 1 <= k <= 1024, R >= 1, N >= 1)")
+    dev = pieces.device
+    J = P * (P - 1) // 2
+    joints = torch.full((Z, J, 2), -1, dtype=torch.int32, device=dev)
+    a = torch.zeros((Z, J, k, 3), dtype=torch.float32, device=dev)
+    b = torch.zeros_like(a)
+    na = torch.zeros((Z, J), dtype=torch.int32, device=dev)
+    nb = torch.zeros_like(na)
+    rows_a = torch.full((Z, J, k), -1, dtype=torch.int64, device=dev)
+    rows_b = torch.full_like(rows_a, -1)
+    if Z > 0:
+        with _on(dev):
+            _call("pzn_progressive_joints_f32", _p(pieces), _p(G), _p(dropped), R, Z, P, N, k, min(int(least), 1 << 30), _p(joints),
+                  _p(a), _p(b), _p(na), _p(nb), _p(rows_a), _p(rows_b), _stream())
+    return joints, a, b, na, nb, rows_a, rows_b
 
 
 def knn(xyz, new_xyz, K):

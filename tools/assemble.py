@@ -11,9 +11,12 @@ points and matched again -; PREFIX_G.npy then maps each piece into the frame of 
 is the [N,3] part around the first pair, PREFIX_piece_id.npy / PREFIX_row_id.npy say where each of its points came from.
 --refine N: every pair pose is refined on its picked boundary points before it is used (assembly.refine_pairs: symmetric
 point-to-point ICP, at most N accepted steps, one launch per table or per round); 0, the default, uses the network's poses.
---joint N (the greedy walk only): after the walk all placed poses are refined together over every joint - every pair of
+--joint N: after the walk all placed poses are refined together over every joint - every pair of
 placed pieces that scores no worse than the walk's worst edge - by at most N sweeps of assembly.refine_assembly (one launch);
 PREFIX_G.npy and PREFIX_cloud.npy are then the refined ones, and with --gt the assembly is scored before and after.  With
+--progressive the joints are read off the rows the merges left out (assembly.refine_progressive: two launches; every piece but
+its part's frame piece moves; PREFIX_G.npy holds the refined poses, the merged cloud stays the walk's; not with --keep-matched,
+--joint-keep or --joint-auto).  With
 --keep auto every joint is refined over the rows its own pair kept (refine_assembly(..., kept="frozen"): a count per joint).
 --joint-keep F|table (with --joint): the kept rows of every joint are chosen again under the joint poses, at every evaluation
 (refine_assembly(..., keep=)): the share F of the full picked sets, or the counts the table carries (--keep F < 1 or auto).
@@ -124,7 +127,7 @@ def main():
     ap.add_argument("--keep", type=keep_arg, default=1.0, help="partial contact: the share of the picked boundary points of each side "
                     "that counts in a pair's score and refinement, those closest to the other side (1.0: all; not with --progressive), "
                     "or the word auto: the share is found per pair on the device (with --joint the kept sets are refined as the pair refinement left them: kept='frozen')")
-    ap.add_argument("--joint", type=int, default=0, help="sweeps at most of the joint refinement after the greedy walk (0: none)")
+    ap.add_argument("--joint", type=int, default=0, help="sweeps at most of the joint refinement after the walk (0: none)")
     ap.add_argument("--joint-keep", type=joint_keep_arg, default=None, help="with --joint: the kept rows of every joint are chosen again "
                     "under the joint poses - F: the share in (0, 1] of the picked boundary points of each side that counts, or the "
                     "word table: the counts the table carries (--keep F < 1 or auto); the full picked sets are read, not the table's kept rows")
@@ -146,8 +149,13 @@ def main():
         sys.exit("--refine: 0 or a number of steps")
     if (args.keep != "auto" and not 0.0 < args.keep <= 1.0) or (args.keep != 1.0 and args.progressive):
         sys.exit("--keep: a share in (0, 1] or the word auto, and 1.0 with --progressive (the progressive walk does not trim)")
-    if args.joint < 0 or (args.joint and args.progressive):
-        sys.exit("--joint: 0 or a number of sweeps, and for the greedy walk only (not with --progressive)")
+    if args.joint < 0:
+        sys.exit("--joint: 0 or a number of sweeps")
+    if args.progressive and (args.joint_keep is not None or args.joint_auto is not None):
+        sys.exit("--joint-keep, --joint-auto: options of the table walks; --progressive --joint N refines over the rows the merges "
+                 "left out, chosen once (assembly.refine_progressive)")
+    if args.progressive and args.joint and args.keep_matched:
+        sys.exit("--progressive --joint N reads the joints off the rows the merges left out: not with --keep-matched")
     if args.joint_keep is not None and (not args.joint or (args.joint_keep != "table" and not 0.0 < args.joint_keep <= 1.0)
                                         or (args.joint_keep == "table" and args.keep == 1.0)):
         sys.exit("--joint-keep: with --joint N, a share in (0, 1] or the word table (which needs --keep F < 1 or auto)")
@@ -186,15 +194,24 @@ def main():
         left = [k for k in range(K) if not res.placed[k]]
         if left:
             print(f"not in the part around the first pair: {left} ({res.parts.shape[0]} parts left)")
-        np.save(args.out + "_G.npy", res.G)
+        def score_against_gt(G, when):
+            if gt is not None and res.placed.any():
+                part = next(q for q, mem in enumerate(pa.members) if int(np.flatnonzero(res.placed)[0]) in mem)
+                root = pa.ledger.frame[part]
+                print(f"against {args.gt} (the part around the first pair, in piece {root}'s frame){when}:")
+                report(assembly.evaluate(G, res.placed, gt["pose"], gt["rest"], root))
+        G = res.G
+        if args.joint and res.edges:
+            score_against_gt(G, ", before the joint refinement")
+            jr = assembly.refine_progressive(x, res, sweeps=args.joint)
+            G = jr.G.double().cpu().numpy()
+            print(f"joint refinement over {int((jr.joints[:, 0] >= 0).sum())} joints: summed score {float(jr.score0):.6f} -> "
+                  f"{float(jr.score):.6f}, {int(jr.sweeps_used)} sweeps, candidates taken per piece {jr.accepted.tolist()}")
+        np.save(args.out + "_G.npy", G)
         for name, t in (("cloud", res.cloud), ("piece_id", res.piece_id), ("row_id", res.row_id)):
             np.save(f"{args.out}_{name}.npy", t.cpu().numpy())
         print(f"wrote {args.out}_G.npy, {args.out}_cloud.npy, {args.out}_piece_id.npy, {args.out}_row_id.npy")
-        if gt is not None and res.placed.any():
-            part = next(q for q, mem in enumerate(pa.members) if int(np.flatnonzero(res.placed)[0]) in mem)
-            root = pa.ledger.frame[part]
-            print(f"against {args.gt} (the part around the first pair, in piece {root}'s frame):")
-            report(assembly.evaluate(res.G, res.placed, gt["pose"], gt["rest"], root))
+        score_against_gt(G, ", after the joint refinement" if args.joint and res.edges else "")
         return
     table = assembly.match_pairs(model, x, k=args.k, refine=args.refine, keep=args.keep)
     if args.forest:

@@ -21,7 +21,9 @@ poses (refine_assembly_batch(..., keep=): the share F of the full picked sets, o
 [LEAST] (exclusive with --joint-keep) has it FIND the two counts of every joint at every evaluation, under the joint poses
 (refine_assembly_batch(..., auto=AutoKeep(least=LEAST)), LEAST = 0.25 when left out) and prints the mean count per joint.  --progressive reports the same means for the progressive walk (assemble_progressive_batch: all
 puzzles in lockstep, P - 1 rounds, every round one choice launch, one merge launch, one encoder batch and two blocked pair blocks)
-beside the greedy one, on the same fractures and table starts, still with the one download.  --time R (with --progressive) then
+beside the greedy one, on the same fractures and table starts, still with the one download; with --joint N a second progressive
+row follows, after refine_progressive_batch (the joints read off the rows the merges left out, two launches; --joint-keep and
+--joint-auto stay options of the table walks and do not reach it).  --time R (with --progressive) then
 times the batched progressive walk and, beside it, a loop of assemble_progressive over the same puzzles - the per-puzzle path, which
 downloads its table every round - R times each in turn after one warm-up of each, a host clock around work that ends in a device
 synchronise, and counts the library launches of one round; --json writes those numbers to a file.  Without --ckpt the weights are the closed-form pseudo-random ones and the poses mean nothing.
@@ -239,6 +241,11 @@ def main():
             pr = walk()
             rows.append(metrics(assembly.evaluate_batch(pr.G, pr.placed, f.pose, f.rest, pr.root, pr.edges, pr.n_edges, f.mates), pr, f.ok))
             rows.append(torch.stack((pr.n_edges.double().mean(),)))
+            if args.joint:
+                pj = assembly.refine_progressive_batch(f.pieces, pr, sweeps=args.joint)
+                rows.append(metrics(assembly.evaluate_batch(pj.G, pr.placed, f.pose, f.rest, pr.root, pr.edges, pr.n_edges, f.mates),
+                                    pr, f.ok))
+                rows.append(torch.stack((pj.score0.double().mean(), pj.score.double().mean(), pj.sweeps_used.double().mean())))
         if args.beam:
             moment = assembly.boundary_moments(f.pieces, table.top_m)
             bm = assembly.assemble_beam_batch(table.score, table.T, moment, beam=args.beam, branch=args.branch, weight=args.vote_weight,
@@ -256,10 +263,12 @@ def main():
           f"{host[1]:.1f} joints")
     names = ("part accuracy", "edge precision", "rotation (deg)", "translation", "msd", "share placed")
     at_p = 18 if args.joint else 12
-    at_b = at_p + (7 if args.progressive else 0)
+    at_b = at_p + ((16 if args.joint else 7) if args.progressive else 0)
     beam_label = f"beam walk (beam {args.beam}, branch {args.branch}, vote weight {args.vote_weight:g})"
     for label, at in (("greedy walk", 6),) + ((("after the joint refinement", 12),) if args.joint else ()) \
-            + ((("progressive walk", at_p),) if args.progressive else ()) + (((beam_label, at_b),) if args.beam else ()) \
+            + ((("progressive walk", at_p),) if args.progressive else ()) \
+            + ((("progressive walk after the joint refinement", at_p + 7),) if args.progressive and args.joint else ()) \
+            + (((beam_label, at_b),) if args.beam else ()) \
             + ((("beam walk after the joint refinement", at_b + 6),) if args.beam and args.joint else ()):
         print(f"{label}: " + ", ".join(f"{n} {v:.6g}" for n, v in zip(names, host[at:at + 6])))
     if args.joint:
@@ -267,6 +276,11 @@ def main():
               + (f", mean count per joint {host[-2]:.1f} fixed / {host[-1]:.1f} moved of {args.k}" if counts else ""))
     if args.progressive:
         print(f"progressive walk: per puzzle {host[at_p + 6]:.2f} edges in {P - 1} lockstep rounds")
+        if args.joint:
+            print(f"progressive walk, joint refinement over the rows the merges left out: mean summed score {host[at_p + 13]:.6f} -> "
+                  f"{host[at_p + 14]:.6f}, {host[at_p + 15]:.1f} sweeps"
+                  + (" (--joint-keep / --joint-auto are options of the table walks: the progressive sets are chosen once)"
+                     if args.joint_keep is not None or args.joint_auto is not None else ""))
     if args.beam:
         at = at_b + (12 if args.joint else 6)
         print(f"beam walk: per puzzle {host[at]:.2f} edges; the greedy walk's tree in {100 * host[at + 1]:.1f} % of the puzzles")
