@@ -1219,6 +1219,44 @@ int pzn_fracture_pair_curved_f32(const float* raw, const double* frames, const d
                                  int n_min, int cap, float* pieces, int64_t* counts, int64_t* start, int32_t* kind,
                                  int32_t* pair, uint8_t* label, double* planes, int32_t* target, int32_t* cand, int32_t* anchor,
                                  uint8_t* ok, pzn_stream_t stream);
+/* pzn_fracture_f32 / pzn_fracture_curved_f32 with EROSION, one launch: at every cut the target's points close to the taken
+ * surface are lost and belong to no piece; datapipe.fracture_eroded_rule is the statement of this entry point.  The cuts are
+ * planes (normals, with frames = half_curv = NULL) or surfaces (frames and half_curv, with normals = NULL); anything else is
+ * PZN_EINVAL, before any launch.  erode float64 [B,P-1,4] = (w_up, w_dn, depth, rho) per step, taken as given: neither clamped
+ * nor checked.  For candidate k of step s through the anchor a let f(x) be the value whose sign the side test takes - the plane's
+ * ((x n0 + y n1) + z n2) + off, the surface's f of pzn_fracture_curved_f32 - in float64, every operation rounded on its own.  A
+ * member x of the target is LOST under that candidate iff -w_dn < f < w_up (the band), or -depth < f < depth and r2 < rho rho
+ * (the chip) with d = x - a (the float32 coordinates widened, three subtractions) and r2 = (d0 d0 + d1 d1) + d2 d2.  All
+ * comparisons are strict: zeros lose nothing, and neither does a NaN; with w_up > 0 and w_dn > 0 the anchor itself (f = 0) is lost.  Up is the members
+ * with f >= 0 that are not lost, down those with f < 0 that are not lost; a candidate is valid iff both hold >= n_min points and
+ * its balance is the smaller of the two; the first valid candidate is taken, else the first most balanced one; up keeps t, down
+ * becomes s, and the lost points get label 255: they are never counted or targeted again.  A step whose target holds no point
+ * (everything has been lost) is not made: its rows of planes, cand, anchor and lost are zero, target is t, and ok = 0.  f is the
+ * offset along n to the surface, so across a cut the kept points of the two sides are >= w_up + w_dn apart along n.
+ * Outputs as in pzn_fracture_f32 (planes: the tangent planes for surfaces), except: counts exclude the lost points; order is
+ * still the stable argsort of label, so the lost rows stand behind the last piece, in the cloud's order; anchor int32 [B,P-1] is
+ * the cloud row of the anchor taken (the chip's centre), for planes too; lost int32 [B,P-1] is the number of points lost at
+ * every step, so the counts of a sample and its lost sum to M.
+ * Limits: those of pzn_fracture_f32 (pzn_fracture_eroded_supported: 1 / 0), PZN_EUNSUPPORTED otherwise, before any launch. */
+int pzn_fracture_eroded_supported(int M, int P, int K);
+int pzn_fracture_eroded_f32(const float* raw, const double* normals, const double* frames, const double* half_curv,
+                            const double* u_anchor, const double* u_start, const double* erode, int B, int M, int P, int K,
+                            int n_min, int cap, float* pieces, int64_t* counts, int64_t* start, uint8_t* label, int32_t* order,
+                            double* planes, int32_t* target, int32_t* cand, int32_t* anchor, int32_t* lost, uint8_t* ok,
+                            pzn_stream_t stream);
+/* pzn_fracture_pair_f32 / pzn_fracture_pair_curved_f32 with the erosion of pzn_fracture_eroded_f32 (normals, or frames and
+ * half_curv, as there; erode float64 [B,P-1,4], rows from P_b - 1 on are not read), one launch;
+ * datapipe.fracture_pair_eroded_rule is the statement of this entry point.  The pair and every output are as in
+ * pzn_fracture_pair_f32, on the eroded pieces: a lost point (label 255) is in no piece; anchor and lost int32 [B,P-1] as in
+ * pzn_fracture_eroded_f32, their rows from P_b - 1 on zero like those of target and cand.
+ * Limits: those of pzn_fracture_f32 (pzn_fracture_pair_eroded_supported: 1 / 0), PZN_EUNSUPPORTED otherwise, before any launch. */
+int pzn_fracture_pair_eroded_supported(int M, int P, int K);
+int pzn_fracture_pair_eroded_f32(const float* raw, const double* normals, const double* frames, const double* half_curv,
+                                 const double* u_anchor, const int32_t* n_pieces, const double* u, const double* erode,
+                                 double neighbours, int B, int M, int P, int K, int n_min, int cap, float* pieces,
+                                 int64_t* counts, int64_t* start, int32_t* kind, int32_t* pair, uint8_t* label, double* planes,
+                                 int32_t* target, int32_t* cand, int32_t* anchor, int32_t* lost, uint8_t* ok,
+                                 pzn_stream_t stream);
 /* dataset.py:1363-1366: 0/1 masks [R,N] with ones at the k picked rows idx int64 [R,k] of each cloud. */
 int pzn_pick_mask_f32(const int64_t* idx, int R, int k, int N, float* mask, pzn_stream_t stream);
 

@@ -30,6 +30,14 @@
 // (PlaneCuts, QuadricCuts).  Frame and curvatures are uniform reads per candidate, as the normal is; the anchor table's fourth
 // column, which the planes leave unused, carries the anchor's cloud row; the LDS layout and the launch geometry are those of
 // the plane kernels.
+//
+// The four *_eroded kernels (datapipe.fracture_eroded_rule / fracture_pair_eroded_rule) are the same two bodies again, with cuts
+// along which material is lost (Eroded<PlaneRowCuts>, Eroded<QuadricCuts>): per candidate a member of the target is up, down or
+// lost - a band around the surface and a chip around the anchor, from the value whose sign the side test takes - and a candidate
+// is judged by what it leaves on both sides, two counts that one workgroup sum carries in the halves of a 64-bit word.  The lost
+// points get label 255, are counted for no piece and are never targeted again; a step that finds its target empty is not made.
+// `order` takes one more scan, for the lost rows behind the last piece.  Every erosion branch is an `if constexpr` on the cuts'
+// type, so the kernels without erosion are the code they were.
 #include "pzn_common.h"
 
 namespace {
@@ -39,6 +47,7 @@ namespace {
 constexpr int FR_MAX_P = 16;         // pieces per sample
 constexpr int FR_MAX_M = 65536;      // points per sample: runs of <= 64 points, one membership mask per thread
 constexpr int FR_KC = 16;            // anchors held in LDS at a time
+constexpr int FR_LOST = 255;         // the label of a point lost along a cut (P <= 16 leaves it free)
 // the dynamic LDS region: every table at a multiple of 16 bytes, the labels last
 constexpr int FR_SLOTS = 0, FR_WBASE = FR_SLOTS + CUT_W * 4, FR_ANCHOR = FR_WBASE + CUT_W * 4, FR_LABELS = FR_ANCHOR + FR_KC * 4 * 4;
 
@@ -50,9 +59,11 @@ constexpr int FR_SLOTS = 0, FR_WBASE = FR_SLOTS + CUT_W * 4, FR_ANCHOR = FR_WBAS
 //   keep(surface)              what is held of a candidate that may be the one taken (uniform)
 //   record(taken, k, g, pl)    thread 0 only, on the step's tables: the step's row of `planes` (and of `anchor`)
 //   zero_from(i, n)            the whole workgroup, on the sample's tables: rows i .. n-1 of what record writes beside `planes`
+//   ERODED                     material is lost along the cut (Eroded<...> below)
 struct PlaneCuts {
   const double* normals;     // [B, P-1, K, 3]
   static constexpr bool ROWS = false;
+  static constexpr bool ERODED = false;
   using Taken = Plane;
   __device__ __forceinline__ PlaneCuts at(size_t, size_t c) const { return PlaneCuts{normals + c * 3}; }
   // the plane through the anchor: the anchor itself evaluates to d + (-d) = 0
@@ -74,10 +85,12 @@ struct QuadricCuts {
   const double* half_curv;   // [B, P-1, K, 2]
   int32_t* anchor;           // [B, P-1]: the cloud row of the anchor taken
   static constexpr bool ROWS = true;
+  static constexpr bool ERODED = false;
   struct Through {
     Quadric q;
     int row;                 // the anchor's cloud row
   };
+  static __device__ __forceinline__ void centre(const Through& t, double (&a)[3]) { a[0] = t.q.a0, a[1] = t.q.a1, a[2] = t.q.a2; }
   using Taken = int;         // the anchor's row is all that is held: thread 0 makes the tangent plane from it once per step
   __device__ __forceinline__ QuadricCuts at(size_t step, size_t c) const {
     return QuadricCuts{frames + c * 9, half_curv + c * 2, anchor + step};
@@ -99,6 +112,66 @@ struct QuadricCuts {
   }
   __device__ __forceinline__ void zero_from(int i, int n) const {
     for (i += threadIdx.x; i < n; i += CUT_T) anchor[i] = 0;
+  }
+};
+
+// PlaneCuts that hold on to the anchor, as an eroded cut needs it: its coordinates are the chip's centre, its cloud row is reported.
+struct PlaneRowCuts {
+  const double* normals;     // [B, P-1, K, 3]
+  int32_t* anchor;           // [B, P-1]: the cloud row of the anchor taken
+  static constexpr bool ROWS = true;
+  struct Through {
+    Plane p;
+    double a0, a1, a2;       // the anchor
+    int row;                 // its cloud row
+  };
+  struct Taken {
+    Plane p;
+    int row;
+  };
+  __device__ __forceinline__ PlaneRowCuts at(size_t step, size_t c) const { return PlaneRowCuts{normals + c * 3, anchor + step}; }
+  __device__ __forceinline__ Through through(int k, const float* anchor_row) const {
+    const double n0 = normals[3 * k], n1 = normals[3 * k + 1], n2 = normals[3 * k + 2];
+    const double ax = (double)anchor_row[0], ay = (double)anchor_row[1], az = (double)anchor_row[2];
+    return Through{Plane{n0, n1, n2, -__dadd_rn(__dadd_rn(__dmul_rn(ax, n0), __dmul_rn(ay, n1)), __dmul_rn(az, n2))}, ax, ay, az,
+                   __float_as_int(anchor_row[3])};
+  }
+  static __device__ __forceinline__ const Plane& side(const Through& t) { return t.p; }
+  static __device__ __forceinline__ void centre(const Through& t, double (&a)[3]) { a[0] = t.a0, a[1] = t.a1, a[2] = t.a2; }
+  static __device__ __forceinline__ Taken keep(const Through& t) { return Taken{t.p, t.row}; }
+  __device__ __forceinline__ void record(const Taken& taken, int, const float*, double* pl) const {
+    pl[0] = taken.p.n0, pl[1] = taken.p.n1, pl[2] = taken.p.n2, pl[3] = taken.p.off;
+    anchor[0] = taken.row;
+  }
+  __device__ __forceinline__ void zero_from(int i, int n) const {
+    for (i += threadIdx.x; i < n; i += CUT_T) anchor[i] = 0;
+  }
+};
+
+// Cuts along which material is lost (datapipe.fracture_eroded_rule): Base's candidates, and per step (w_up, w_dn, depth, rho).  With
+// f the value whose sign the side test takes, a member of the target is LOST under a candidate iff -w_dn < f < w_up (the band) or
+// -depth < f < depth and |x - anchor|^2 < rho rho (the chip), all comparisons strict, so zeros and NaNs lose nothing.  Base holds
+// the anchor (ROWS, centre, `anchor`): PlaneRowCuts or QuadricCuts.
+//   lost_to(q, f, x, y, z)     the member with value f is lost under the surface q
+//   skip()                     thread 0 only, on the step's tables: a step that is not made (zero rows)
+template <class Base>
+struct Eroded : Base {
+  const double* erode;       // [B, P-1, 4]
+  int32_t* lost;             // [B, P-1]: the points lost at every step
+  static constexpr bool ERODED = true;
+  __device__ __forceinline__ Eroded at(size_t step, size_t c) const { return Eroded{Base::at(step, c), erode + step * 4, lost + step}; }
+  __device__ __forceinline__ bool lost_to(const typename Base::Through& q, double f, float x, float y, float z) const {
+    const double w_up = erode[0], w_dn = erode[1], depth = erode[2], rho = erode[3];
+    double a[3];
+    Base::centre(q, a);
+    const double d0 = __dsub_rn((double)x, a[0]), d1 = __dsub_rn((double)y, a[1]), d2 = __dsub_rn((double)z, a[2]);
+    const double r2 = __dadd_rn(__dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1)), __dmul_rn(d2, d2));
+    return (f < w_up && f > -w_dn) || (f < depth && f > -depth && r2 < __dmul_rn(rho, rho));
+  }
+  __device__ __forceinline__ void skip() const { this->anchor[0] = 0, lost[0] = 0; }
+  __device__ __forceinline__ void zero_from(int i, int n) const {
+    Base::zero_from(i, n);
+    for (i += threadIdx.x; i < n; i += CUT_T) lost[i] = 0;
   }
 };
 
@@ -167,6 +240,20 @@ __device__ __forceinline__ bool fracture_cuts(const FractureBlock& w, const Cuts
 #pragma unroll
     for (int p = 1; p < FR_MAX_P; ++p)
       if (p < s && cnt[p] > n_t) t = p, n_t = cnt[p];
+    if constexpr (Cuts::ERODED) {
+      // everything has been lost: the step is not made (uniform: every thread holds the same counts)
+      if (n_t == 0) {
+        if (tid == 0) {
+          double* pl = planes + (size_t)(s - 1) * 4;
+          pl[0] = pl[1] = pl[2] = pl[3] = 0.0;
+          target[s - 1] = t, cand[s - 1] = 0;
+          cuts0.at((size_t)(s - 1), (size_t)(s - 1) * K).skip();
+        }
+        all_valid = false;
+        last_t = t;
+        continue;
+      }
+    }
     uint64_t tbits = 0;      // the run's members of the target
     for (int j = lo; j < hi; ++j) tbits |= (uint64_t)(lab[j] == t ? 1 : 0) << (j - lo);
     const int c_t = __popcll(tbits);
@@ -176,6 +263,8 @@ __device__ __forceinline__ bool fracture_cuts(const FractureBlock& w, const Cuts
     const double* ua = ua0 + (size_t)(s - 1) * K;
     int chosen = -1, best_k = 0, best_bal = -1, best_up = 0;
     uint64_t sel = 0;        // the run's target members on the DOWN side of the candidate that is taken
+    [[maybe_unused]] int best_dn = 0;              // eroded cuts: what is kept of the down side is no longer n_t - best_up,
+    [[maybe_unused]] uint64_t sel_lost = 0;        // and the run's target members that are lost to the candidate taken
     typename Cuts::Taken taken{};
     for (int k0 = 0; k0 < K && chosen < 0; k0 += FR_KC) {
       // 2. the anchors of candidates k0 .. k0 + FR_KC - 1 (the table's readers of the chunk before are behind block_sum's barriers)
@@ -195,19 +284,43 @@ __device__ __forceinline__ bool fracture_cuts(const FractureBlock& w, const Cuts
         const int k = k0 + kk;
         // 3. the surface through the anchor (the table is read here, in front of block_sum's barriers)
         const auto q = cuts.through(k, anchor + 4 * kk);
-        int c = 0;
-        uint64_t down = 0;
-        for (uint64_t m = tbits; m != 0; m &= m - 1) {
-          const int i = __ffsll((unsigned long long)m) - 1, j = lo + i;
-          const bool up = is_up(g[3 * j], g[3 * j + 1], g[3 * j + 2], Cuts::side(q));
-          c += up ? 1 : 0;
-          down |= (uint64_t)(up ? 0 : 1) << i;
+        int bal;
+        bool valid;
+        if constexpr (Cuts::ERODED) {
+          // every member is up, down or lost; the kept members of both sides in one sum, one count per 32-bit half (<= 65536
+          // each): slots and wave_base are adjacent and together hold CUT_W such words
+          long long c = 0;
+          uint64_t down = 0, gone = 0;
+          for (uint64_t m = tbits; m != 0; m &= m - 1) {
+            const int i = __ffsll((unsigned long long)m) - 1, j = lo + i;
+            const float x = g[3 * j], y = g[3 * j + 1], z = g[3 * j + 2];
+            const double f = value(x, y, z, Cuts::side(q));
+            const bool lost = cuts.lost_to(q, f, x, y, z), above = f >= 0.0;
+            c += lost ? 0ll : (above ? 1ll : 1ll << 32);
+            down |= (uint64_t)(!lost && !above ? 1 : 0) << i;
+            gone |= (uint64_t)(lost ? 1 : 0) << i;
+          }
+          // 4. as below, on what the candidate leaves on its two sides
+          const long long both = block_sum(c, reinterpret_cast<long long*>(slots));
+          const int up = (int)(both & 0xffffffffll), dn = (int)(both >> 32);
+          bal = up < dn ? up : dn;
+          valid = up >= n_min && dn >= n_min;
+          if (bal > best_bal || valid) sel = down, sel_lost = gone, taken = Cuts::keep(q), best_up = up, best_dn = dn;
+        } else {
+          int c = 0;
+          uint64_t down = 0;
+          for (uint64_t m = tbits; m != 0; m &= m - 1) {
+            const int i = __ffsll((unsigned long long)m) - 1, j = lo + i;
+            const bool up = is_up(g[3 * j], g[3 * j + 1], g[3 * j + 2], Cuts::side(q));
+            c += up ? 1 : 0;
+            down |= (uint64_t)(up ? 0 : 1) << i;
+          }
+          // 4. the first valid candidate, else the most balanced one (uniform: every thread holds the same sum)
+          const int up = block_sum(c, slots);
+          bal = up < n_t - up ? up : n_t - up;
+          valid = up >= n_min && n_t - up >= n_min;
+          if (bal > best_bal || valid) sel = down, taken = Cuts::keep(q), best_up = up;
         }
-        // 4. the first valid candidate, else the most balanced one (uniform: every thread holds the same sum)
-        const int up = block_sum(c, slots);
-        const int bal = up < n_t - up ? up : n_t - up;
-        const bool valid = up >= n_min && n_t - up >= n_min;
-        if (bal > best_bal || valid) sel = down, taken = Cuts::keep(q), best_up = up;
         if (bal > best_bal) best_bal = bal, best_k = k;
         if (valid) {
           chosen = k;
@@ -217,15 +330,22 @@ __device__ __forceinline__ bool fracture_cuts(const FractureBlock& w, const Cuts
     }
     all_valid = all_valid && chosen >= 0;
     if (chosen < 0) chosen = best_k;
-    // 5. the down side becomes label s
+    // 5. the down side becomes label s; what is lost belongs to no piece and is never counted or targeted again
     for (uint64_t m = sel; m != 0; m &= m - 1) lab[lo + __ffsll((unsigned long long)m) - 1] = (uint8_t)s;
+    if constexpr (Cuts::ERODED)
+      for (uint64_t m = sel_lost; m != 0; m &= m - 1) lab[lo + __ffsll((unsigned long long)m) - 1] = (uint8_t)FR_LOST;
 #pragma unroll
     for (int p = 0; p < FR_MAX_P; ++p) {
       if (p == t) cnt[p] = best_up;
-      if (p == s) cnt[p] = n_t - best_up;
+      if constexpr (Cuts::ERODED) {
+        if (p == s) cnt[p] = best_dn;
+      } else {
+        if (p == s) cnt[p] = n_t - best_up;
+      }
     }
     if (tid == 0) {
       cuts.record(taken, chosen, g, planes + (size_t)(s - 1) * 4);
+      if constexpr (Cuts::ERODED) cuts.lost[0] = n_t - best_up - best_dn;
       target[s - 1] = t;
       cand[s - 1] = chosen;
     }
@@ -280,6 +400,14 @@ __device__ __forceinline__ void fracture_body(const FractureArgs<Cuts>& a, unsig
       a.start[(size_t)p * a.B + b] = start_index(us[p], n_p);
     }
     off += n_p;
+  }
+  if constexpr (Cuts::ERODED) {
+    // `order` stays the stable argsort of the labels: the lost rows behind the last piece, in the cloud's order
+    int c = 0;
+    for (int j = lo; j < hi; ++j) c += lab[j] == FR_LOST ? 1 : 0;
+    int at = block_excl_scan(c, slots, wave_base);
+    for (int j = lo; j < hi; ++j)
+      if (lab[j] == FR_LOST) ord[off + at++] = j;
   }
   if (tid == 0) a.ok[b] = (all_valid && fits) ? 1 : 0;
 }
@@ -413,6 +541,26 @@ __global__ __launch_bounds__(CUT_T) void fracture_pair_curved_kernel(FracturePai
   fracture_pair_body(a, smem);
 }
 
+__global__ __launch_bounds__(CUT_T) void fracture_eroded_kernel(FractureArgs<Eroded<PlaneRowCuts>> a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  fracture_body(a, smem);
+}
+
+__global__ __launch_bounds__(CUT_T) void fracture_curved_eroded_kernel(FractureArgs<Eroded<QuadricCuts>> a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  fracture_body(a, smem);
+}
+
+__global__ __launch_bounds__(CUT_T) void fracture_pair_eroded_kernel(FracturePairArgs<Eroded<PlaneRowCuts>> a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  fracture_pair_body(a, smem);
+}
+
+__global__ __launch_bounds__(CUT_T) void fracture_pair_curved_eroded_kernel(FracturePairArgs<Eroded<QuadricCuts>> a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  fracture_pair_body(a, smem);
+}
+
 // the dynamic LDS of every kernel here: <= 64.4 KiB
 int fracture_lds(const void* kernel, int M, size_t* lds) {
   *lds = (size_t)FR_LABELS + ((size_t)M + 15) / 16 * 16;
@@ -494,5 +642,61 @@ PZN_EXPORT int pzn_fracture_pair_curved_f32(const float* raw, const double* fram
   size_t lds;
   if (fracture_lds(reinterpret_cast<const void*>(fracture_pair_curved_kernel), M, &lds) != PZN_OK) return PZN_ELAUNCH;
   PZN_LAUNCH(fracture_pair_curved_kernel, dim3(B), dim3(CUT_T), lds, pzn_hip_stream(stream), a);
+  PZN_RETURN_LAUNCH_STATUS();
+}
+
+PZN_EXPORT int pzn_fracture_eroded_supported(int M, int P, int K) { return pzn_fracture_supported(M, P, K); }
+
+PZN_EXPORT int pzn_fracture_eroded_f32(const float* raw, const double* normals, const double* frames, const double* half_curv,
+                                       const double* u_anchor, const double* u_start, const double* erode, int B, int M, int P,
+                                       int K, int n_min, int cap, float* pieces, int64_t* counts, int64_t* start, uint8_t* label,
+                                       int32_t* order, double* planes, int32_t* target, int32_t* cand, int32_t* anchor,
+                                       int32_t* lost, uint8_t* ok, pzn_stream_t stream) {
+  PZN_CHECK_ARG(raw && u_anchor && u_start && erode && pieces && counts && start && label && order && planes && target && cand &&
+                anchor && lost && ok);
+  // planes (normals) or surfaces (frames and half_curv), never both and never half of one
+  PZN_CHECK_ARG(normals ? (!frames && !half_curv) : (frames && half_curv));
+  PZN_CHECK_ARG(B > 0 && cap > 0 && n_min >= 0);
+  if (!pzn_fracture_eroded_supported(M, P, K)) return PZN_EUNSUPPORTED;
+  size_t lds;
+  if (normals) {
+    FractureArgs<Eroded<PlaneRowCuts>> a{raw, {{normals, anchor}, erode, lost}, u_anchor, u_start, B, M, P, K, n_min, cap, pieces,
+                                         counts, start, label, order, planes, target, cand, ok};
+    if (fracture_lds(reinterpret_cast<const void*>(fracture_eroded_kernel), M, &lds) != PZN_OK) return PZN_ELAUNCH;
+    PZN_LAUNCH(fracture_eroded_kernel, dim3(B), dim3(CUT_T), lds, pzn_hip_stream(stream), a);
+  } else {
+    FractureArgs<Eroded<QuadricCuts>> a{raw, {{frames, half_curv, anchor}, erode, lost}, u_anchor, u_start, B, M, P, K, n_min, cap,
+                                        pieces, counts, start, label, order, planes, target, cand, ok};
+    if (fracture_lds(reinterpret_cast<const void*>(fracture_curved_eroded_kernel), M, &lds) != PZN_OK) return PZN_ELAUNCH;
+    PZN_LAUNCH(fracture_curved_eroded_kernel, dim3(B), dim3(CUT_T), lds, pzn_hip_stream(stream), a);
+  }
+  PZN_RETURN_LAUNCH_STATUS();
+}
+
+PZN_EXPORT int pzn_fracture_pair_eroded_supported(int M, int P, int K) { return pzn_fracture_supported(M, P, K); }
+
+PZN_EXPORT int pzn_fracture_pair_eroded_f32(const float* raw, const double* normals, const double* frames, const double* half_curv,
+                                            const double* u_anchor, const int32_t* n_pieces, const double* u, const double* erode,
+                                            double neighbours, int B, int M, int P, int K, int n_min, int cap, float* pieces,
+                                            int64_t* counts, int64_t* start, int32_t* kind, int32_t* pair, uint8_t* label,
+                                            double* planes, int32_t* target, int32_t* cand, int32_t* anchor, int32_t* lost,
+                                            uint8_t* ok, pzn_stream_t stream) {
+  PZN_CHECK_ARG(raw && u_anchor && n_pieces && u && erode && pieces && counts && start && kind && pair && label && planes && target &&
+                cand && anchor && lost && ok);
+  PZN_CHECK_ARG(normals ? (!frames && !half_curv) : (frames && half_curv));
+  PZN_CHECK_ARG(B > 0 && cap > 0 && n_min >= 0 && neighbours >= 0.0 && neighbours <= 1.0);
+  if (!pzn_fracture_pair_eroded_supported(M, P, K)) return PZN_EUNSUPPORTED;
+  size_t lds;
+  if (normals) {
+    FracturePairArgs<Eroded<PlaneRowCuts>> a{raw, {{normals, anchor}, erode, lost}, u_anchor, n_pieces, u, neighbours, B, M, P, K,
+                                             n_min, cap, pieces, counts, start, kind, pair, label, planes, target, cand, ok};
+    if (fracture_lds(reinterpret_cast<const void*>(fracture_pair_eroded_kernel), M, &lds) != PZN_OK) return PZN_ELAUNCH;
+    PZN_LAUNCH(fracture_pair_eroded_kernel, dim3(B), dim3(CUT_T), lds, pzn_hip_stream(stream), a);
+  } else {
+    FracturePairArgs<Eroded<QuadricCuts>> a{raw, {{frames, half_curv, anchor}, erode, lost}, u_anchor, n_pieces, u, neighbours, B, M,
+                                            P, K, n_min, cap, pieces, counts, start, kind, pair, label, planes, target, cand, ok};
+    if (fracture_lds(reinterpret_cast<const void*>(fracture_pair_curved_eroded_kernel), M, &lds) != PZN_OK) return PZN_ELAUNCH;
+    PZN_LAUNCH(fracture_pair_curved_eroded_kernel, dim3(B), dim3(CUT_T), lds, pzn_hip_stream(stream), a);
+  }
   PZN_RETURN_LAUNCH_STATUS();
 }

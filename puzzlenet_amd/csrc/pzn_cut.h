@@ -14,10 +14,10 @@ struct Plane {
   double n0, n1, n2, off;
 };
 
-// points . normal + z >= 0 as numpy evaluates it for float32 points times float64 draws: ((x n0 + y n1) + z n2) + offset
-__device__ __forceinline__ bool is_up(float x, float y, float z, const Plane& p) {
-  const double d = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn((double)x, p.n0), __dmul_rn((double)y, p.n1)), __dmul_rn((double)z, p.n2)), p.off);
-  return d >= 0.0;
+// points . normal + z as numpy evaluates it for float32 points times float64 draws: ((x n0 + y n1) + z n2) + offset - the signed
+// offset of the point along the normal to the plane
+__device__ __forceinline__ double value(float x, float y, float z, const Plane& p) {
+  return __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn((double)x, p.n0), __dmul_rn((double)y, p.n1)), __dmul_rn((double)z, p.n2)), p.off);
 }
 
 // A second-order surface patch through the point a: the paraboloid h + c1 s1^2 + c2 s2^2 = 0 in the frame (e1, e2, n) at a,
@@ -29,25 +29,32 @@ struct Quadric {
   double c1, c2;
 };
 
-// f(x) >= 0 with d = x - a (the float32 coordinates widened, three subtractions), s1 = (d0 e1[0] + d1 e1[1]) + d2 e1[2], s2 and
+// f(x) with d = x - a (the float32 coordinates widened, three subtractions), s1 = (d0 e1[0] + d1 e1[1]) + d2 e1[2], s2 and
 // h likewise with e2 and n, f = (h + (c1 s1) s1) + (c2 s2) s2: float64, every operation individually rounded, as numpy
-// evaluates it.  d = 0 at a, so a itself evaluates to exactly 0 and is on the up side.
-__device__ __forceinline__ bool is_up(float x, float y, float z, const Quadric& q) {
+// evaluates it.  d = 0 at a, so a itself evaluates to exactly 0.
+__device__ __forceinline__ double value(float x, float y, float z, const Quadric& q) {
   const double d0 = __dsub_rn((double)x, q.a0), d1 = __dsub_rn((double)y, q.a1), d2 = __dsub_rn((double)z, q.a2);
   const double s1 = __dadd_rn(__dadd_rn(__dmul_rn(d0, q.e1[0]), __dmul_rn(d1, q.e1[1])), __dmul_rn(d2, q.e1[2]));
   const double s2 = __dadd_rn(__dadd_rn(__dmul_rn(d0, q.e2[0]), __dmul_rn(d1, q.e2[1])), __dmul_rn(d2, q.e2[2]));
   const double h = __dadd_rn(__dadd_rn(__dmul_rn(d0, q.n[0]), __dmul_rn(d1, q.n[1])), __dmul_rn(d2, q.n[2]));
-  const double f = __dadd_rn(__dadd_rn(h, __dmul_rn(__dmul_rn(q.c1, s1), s1)), __dmul_rn(__dmul_rn(q.c2, s2), s2));
-  return f >= 0.0;
+  return __dadd_rn(__dadd_rn(h, __dmul_rn(__dmul_rn(q.c1, s1), s1)), __dmul_rn(__dmul_rn(q.c2, s2), s2));
 }
 
-// sum of one int per thread over the workgroup, the same value returned to every thread (two barriers); slots: CUT_W ints of LDS
-__device__ __forceinline__ int block_sum(int v, int* slots) {
+// the side test of either surface: value >= 0, so a point at exactly 0 (the anchor of a fracture's cut) is on the up side
+template <class Surface>
+__device__ __forceinline__ bool is_up(float x, float y, float z, const Surface& s) {
+  return value(x, y, z, s) >= 0.0;
+}
+
+// sum of one count per thread over the workgroup, the same value returned to every thread (two barriers); slots: CUT_W counts of
+// LDS.  Count: int, or long long holding two counts, one per 32-bit half, as block_excl_scan takes them.
+template <class Count>
+__device__ __forceinline__ Count block_sum(Count v, Count* slots) {
   for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, PZN_WAVE);
   __syncthreads();          // (slots may still be read from the previous call)
   if ((threadIdx.x & (PZN_WAVE - 1)) == 0) slots[threadIdx.x / PZN_WAVE] = v;
   __syncthreads();
-  int t = 0;
+  Count t = 0;
 #pragma unroll
   for (int w = 0; w < CUT_W; ++w) t += slots[w];
   return t;

@@ -383,8 +383,17 @@ CurvedFracturePair.__doc__ = """FracturePair of a curved cut (cut_pairs_fracture
 anchors, and anchor [B,P-1] int32 the cloud row of the anchor taken at every step (zero for the cuts a sample did not make)."""
 
 
+ErodedFracturePair = collections.namedtuple("ErodedFracturePair", FracturePair._fields + ("anchor", "erode", "lost"))
+ErodedFracturePair.__doc__ = """FracturePair of an eroded cut (cut_pairs_fracture(..., erode=)): anchor [B,P-1] int32 the cloud row of the
+anchor taken at every step (the chip's centre), erode [B,P-1,4] float64 the (w_up, w_dn, depth, rho) the cuts were made with, and
+lost [B,P-1] int32 the points lost at every step (label ops.FRACTURE_LOST; zero for the cuts a sample did not make)."""
+
+ErodedCurvedFracturePair = collections.namedtuple("ErodedCurvedFracturePair", CurvedFracturePair._fields + ("erode", "lost"))
+ErodedCurvedFracturePair.__doc__ = """CurvedFracturePair of an eroded cut: then erode and lost, as ErodedFracturePair holds them."""
+
+
 def cut_pairs_fracture(raw, normals, u_anchor, pieces, u, twist, n=1024, k=128, neighbours=0.5, cap=None, frames=None,
-                       half_curv=None):
+                       half_curv=None, erode=None):
     """cut_pairs for pairs cut out of a fracture (the rule: fracture_pair_rule): every cloud cut into pieces[b] pieces, the pair
     chosen and only its pieces - and the fallback's - compacted in one launch (csrc/fracture.hip, ops.fracture_pair; the cuts
     leave >= n points on both sides, n_min = n); then, as cut_pairs_double does, the sampling of the primary and of the fallback
@@ -394,11 +403,20 @@ def cut_pairs_fracture(raw, normals, u_anchor, pieces, u, twist, n=1024, k=128, 
     u_anchor [B,P-1,K], u [B,7] float64 draws; pieces: ops.fracture_pair's; twist [B,6].
     -> ((D, moved U, igt, U, D boundary, U boundary, D mask, U mask), ok [B], FracturePair)
     frames [B,P-1,K,3,3] and half_curv [B,P-1,K,2] float64, with normals=None: the cuts are curved (ops.fracture_pair_curved; the
-    rule: fracture_pair_curved_rule) and the record is a CurvedFracturePair, which adds `anchor`."""
+    rule: fracture_pair_curved_rule) and the record is a CurvedFracturePair, which adds `anchor`.
+    erode [B,P-1,4] float64 = (w_up, w_dn, depth, rho) per step (draw_erosion): material is lost along every cut, in the same one
+    launch (ops.fracture_pair_eroded; the rule: fracture_pair_eroded_rule), and the record is the one of its form extended by
+    `anchor` (where it lacks one), `erode` and `lost`: an ErodedFracturePair or ErodedCurvedFracturePair.  None is the call
+    without erosion.  `cd` and the acceptance test of step 8 are taken on the ERODED pieces: a gap g between two boundaries adds
+    about 2 g^2 to cd, which is held against the unchanged CD_ACCEPT = 0.015."""
     cap = _feeder_cap("cut_pairs_fracture", raw, cap)
     B, M, _ = raw.shape
-    anchor = None
-    if _curved("cut_pairs_fracture", normals, frames, half_curv):
+    anchor = lost = None
+    curved = _curved("cut_pairs_fracture", normals, frames, half_curv)
+    if erode is not None:
+        packed, counts, start, kind, pair, label, planes, target, cand, anchor, lost, ok = ops.fracture_pair_eroded(
+            raw, normals, u_anchor, pieces, u, erode, n, neighbours, cap, frames=frames, half_curv=half_curv)
+    elif curved:
         packed, counts, start, kind, pair, label, planes, target, cand, anchor, ok = ops.fracture_pair_curved(
             raw, frames, half_curv, u_anchor, pieces, u, n, neighbours, cap)
     else:
@@ -417,7 +435,9 @@ def cut_pairs_fracture(raw, normals, u_anchor, pieces, u, twist, n=1024, k=128, 
     both = torch.where(rejected.repeat(2).view(2 * B, 1, 1), fallback, primary)
     top, fbnd = _picks(both, k)
     record = FracturePair(kind, pair, rejected, cd, label, planes, target, cand, primary[:B], primary[B:], bnd[:B], bnd[B:])
-    if anchor is not None:
+    if erode is not None:
+        record = (ErodedCurvedFracturePair if curved else ErodedFracturePair)(*record, anchor, erode, lost)
+    elif anchor is not None:
         record = CurvedFracturePair(*record, anchor)
     return _finish(both, top, fbnd, twist), ok & (counts[:B] >= n) & (counts[B:2 * B] >= n), record
 
@@ -530,10 +550,15 @@ class PairFeeder:
     (fracture_pair_rule, cut_pairs_fracture); batch.fracture says what was cut and batch.plane stays None.
     curvature=c (with pieces only; c >= 0, finite): c > 0 breaks along curved surfaces, paraboloids through the anchor with
     principal curvatures drawn in [-c, c] (fracture_pair_curved_rule; 2.0 is the curvature of the reference's radius-0.5 sphere);
-    batch.fracture is then a CurvedFracturePair.  0.0 is the plane mode: its staging columns, its draws, its bits."""
+    batch.fracture is then a CurvedFracturePair.  0.0 is the plane mode: its staging columns, its draws, its bits.
+    erosion=e, chip=(depth, radius) (with pieces only; finite, >= 0): material is lost along every cut - per step a band
+    w_up, w_dn ~ U[0, e) and a chip of depth ~ U[0, depth) within rho ~ U[0, radius) of the anchor (fracture_pair_eroded_rule,
+    draw_erosion) - so the pairs no longer mate perfectly; batch.fracture is then an ErodedFracturePair or
+    ErodedCurvedFracturePair.  The mode has 4 (P - 1) more staging columns, drawn from rng after the mode's other draws.  erosion
+    0 or None with no chip keeps the modes above: their staging columns, their draws, their bits."""
 
     def __init__(self, raw, device, n=1024, k=128, mag=0.8, candidates=16, seed=0, cut="plane", split_twice=False, pieces=None,
-                 neighbours=0.5, curvature=None):
+                 neighbours=0.5, curvature=None, erosion=None, chip=None):
         if cut != "plane" and cut not in ops.SOLID_KINDS:
             raise _lib.PznError(f"PairFeeder: cut={cut!r} (one of 'plane', 'sphere', 'cylinder', 'cone')")
         if split_twice and cut != "plane":
@@ -554,6 +579,9 @@ class PairFeeder:
                 raise _lib.PznUnsupported(f"PairFeeder: curvature={curvature!r} bends the cuts of a fracture (pieces=...)")
             if not isinstance(curvature, (int, float, np.integer, np.floating)) or not 0.0 <= float(curvature) < np.inf:
                 raise _lib.PznError(f"PairFeeder: curvature={curvature!r} (the largest principal curvature, finite and >= 0)")
+        if (erosion is not None or chip is not None) and pieces is None:
+            raise _lib.PznUnsupported(f"PairFeeder: erosion={erosion!r}, chip={chip!r} erode the cuts of a fracture (pieces=...)")
+        self.erosion, self.chip, eroded = _erosion_args("PairFeeder", erosion, chip)
         self.curvature = 0.0 if curvature is None else float(curvature)
         self.pieces, self.neighbours = pieces, float(neighbours)
         self.cut, self.split_twice = cut, bool(split_twice)
@@ -573,6 +601,8 @@ class PairFeeder:
         if self.pieces is not None:
             self._mode = (_fracture_pair_curved_mode(*self.pieces, self.curvature) if self.curvature > 0.0 else
                           _fracture_pair_mode(*self.pieces))
+            if eroded:
+                self._mode = _eroded_mode(self._mode, self.pieces[1], self.erosion, self.chip)
         # one pinned staging block per batch in flight (two: the upload of batch k + 1 may still be queued when k + 2 is drawn)
         self._width = self._mode.cols(self.K)[-1].stop
         self._stage = [torch.empty((B, self._width), dtype=torch.float64, pin_memory=True) for _ in range(3)]
@@ -682,12 +712,17 @@ def double_cut_rejects(kind, cd):
     return (kind == HALF_VS_OTHER) & (cd > CD_ACCEPT)
 
 
-def _side64(pts, plane):
-    """side(p, plane) = (p . normal + z >= 0) as plane_cut_mask and the kernels evaluate it: float64, every operation
-    individually rounded, ((x n0 + y n1) + z n2) + offset.  pts [M,3] float32, plane [4] float64 -> bool [M]"""
+def _value64(pts, plane):
+    """p . normal + z as plane_cut_mask and the kernels evaluate it: float64, every operation individually rounded,
+    ((x n0 + y n1) + z n2) + offset.  pts [M,3] float32, plane [4] float64 -> float64 [M]"""
     p = np.asarray(pts, dtype=np.float32).astype(np.float64)
     plane = np.asarray(plane, dtype=np.float64)
-    return ((p[:, 0] * plane[0] + p[:, 1] * plane[1]) + p[:, 2] * plane[2]) + plane[3] >= 0
+    return ((p[:, 0] * plane[0] + p[:, 1] * plane[1]) + p[:, 2] * plane[2]) + plane[3]
+
+
+def _side64(pts, plane):
+    """side(p, plane) = (_value64 >= 0).  pts [M,3] float32, plane [4] float64 -> bool [M]"""
+    return _value64(pts, plane) >= 0
 
 
 def region_rows(raw, code, tab):
@@ -819,31 +854,34 @@ def fracture_rule(raw, normals, u_anchor, u_start, P, n_min, cap=None):
     raw = np.asarray(raw, dtype=np.float32)
     normals, u_anchor, u_start = (np.asarray(t, dtype=np.float64) for t in (normals, u_anchor, u_start))
     r = _fracture_pieces(raw, _plane_side(normals), u_anchor, u_start, int(P), n_min, cap)
-    del r["anchor"]
+    del r["anchor"], r["lost"]
     return r
 
 
-def _fracture_pieces(raw, side, u_anchor, u_start, P, n_min, cap):
-    """fracture_rule / fracture_curved_rule behind their argument conversions: the steps with `side` (see _fracture_steps), then
-    the pieces.  -> the rule's dict with anchor [P-1] int32, the cloud row of the anchor taken at every step"""
+def _fracture_pieces(raw, side, u_anchor, u_start, P, n_min, cap, erode=None):
+    """fracture_rule / fracture_curved_rule / fracture_eroded_rule behind their argument conversions: the steps with `side` and
+    `erode` (see _fracture_steps), then the pieces.  -> the rule's dict with anchor [P-1] int32, the cloud row of the anchor taken
+    at every step, and lost [P-1] int32, the points lost at every step (zero without erosion)"""
     M = raw.shape[0]
     cap = M if cap is None else int(cap)
-    label, planes, target, cand, anchor, ok = _fracture_steps(raw, side, u_anchor, P, P - 1, n_min)
-    counts = np.bincount(label, minlength=P).astype(np.int64)
+    label, planes, target, cand, anchor, lost, ok = _fracture_steps(raw, side, u_anchor, P, P - 1, n_min, erode)
+    counts = np.bincount(label, minlength=P)[:P].astype(np.int64)
     order = np.argsort(label, kind="stable").astype(np.int32)
     pieces = [_pad_rows(raw[label == p], cap, raw[0]) for p in range(P)]
     start = np.array([_start_index(u_start[p], counts[p]) for p in range(P)], dtype=np.int64)
     return dict(label=label, counts=counts, pieces=pieces, order=order, start=start, planes=planes, target=target, cand=cand,
-                anchor=anchor, ok=bool(ok and counts.max() <= cap))
+                anchor=anchor, lost=lost, ok=bool(ok and counts.max() <= cap))
 
 
 def _plane_side(normals):
     """The side function of fracture_rule: normals [P-1,K,3] float64 -> side(s, k, a, pts) with a [3] float64 the anchor and pts
-    [m,3] float32 the target's points -> (the plane [4] through a with normal normals[s,k], up [m] bool)"""
+    [m,3] float32 the target's points -> (the plane [4] through a with normal normals[s,k], up [m] bool = f >= 0, f [m] float64 =
+    _value64, the value whose sign is taken)"""
     def side(s, k, a, pts):
         n = normals[s, k]
         plane = np.array([n[0], n[1], n[2], -((a[0] * n[0] + a[1] * n[1]) + a[2] * n[2])])
-        return plane, _side64(pts, plane)
+        f = _value64(pts, plane)
+        return plane, f >= 0, f
     return side
 
 
@@ -859,46 +897,61 @@ def quadric_value(pts, a, frame, half_curv):
 
 def _quadric_side(frames, half_curv):
     """The side function of fracture_curved_rule: frames [P-1,K,3,3], half_curv [P-1,K,2] float64 -> side(s, k, a, pts) as
-    _plane_side's -> (the TANGENT plane [4] at a, (n, -((ax n0 + ay n1) + az n2)), up [m] bool = quadric_value >= 0)"""
+    _plane_side's -> (the TANGENT plane [4] at a, (n, -((ax n0 + ay n1) + az n2)), up [m] bool = f >= 0, f = quadric_value)"""
     def side(s, k, a, pts):
         n = frames[s, k, 2]
         plane = np.array([n[0], n[1], n[2], -((a[0] * n[0] + a[1] * n[1]) + a[2] * n[2])])
-        return plane, quadric_value(pts, a, frames[s, k], half_curv[s, k]) >= 0
+        f = quadric_value(pts, a, frames[s, k], half_curv[s, k])
+        return plane, f >= 0, f
     return side
 
 
-def _fracture_steps(raw, side, u_anchor, P, steps, n_min):
+def _fracture_steps(raw, side, u_anchor, P, steps, n_min, erode=None):
     """Steps s = 1 .. steps (<= P - 1) of fracture_rule on raw [M,3] float32; u_anchor [P-1,K] float64; side(s - 1, k, anchor,
-    target points) -> (the plane recorded for candidate k, its up side): _plane_side or _quadric_side.
-    -> (label [M] uint8, planes [P-1,4], target [P-1], cand [P-1], anchor [P-1] (the cloud row of the anchor taken) with the rows
-    of the steps not made zero, every step made had a valid candidate)"""
+    target points) -> (the plane recorded for candidate k, its up side, the value f whose sign that is): _plane_side or
+    _quadric_side.  erode [P-1,4] float64 = (w_up, w_dn, depth, rho) per step, or None: the steps of fracture_eroded_rule, where a
+    member of the target is lost (label FRACTURE_LOST) iff -w_dn < f < w_up, or -depth < f < depth and r2 < rho rho, a candidate
+    is judged by what it leaves on both sides, and a step whose target is empty is not made.
+    -> (label [M] uint8, planes [P-1,4], target [P-1], cand [P-1], anchor [P-1] (the cloud row of the anchor taken), lost [P-1]
+    (the points lost) with the rows of the steps not made zero, every step had a valid candidate)"""
     M, K = raw.shape[0], u_anchor.shape[1]
     p64 = raw.astype(np.float64)
     label = np.zeros(M, dtype=np.uint8)
     planes = np.zeros((P - 1, 4), dtype=np.float64)
-    target, cand, anchor = (np.zeros(P - 1, dtype=np.int32) for _ in range(3))
+    target, cand, anchor, lost = (np.zeros(P - 1, dtype=np.int32) for _ in range(4))
     ok = True
     for s in range(1, steps + 1):
-        count = np.bincount(label, minlength=P)
+        count = np.bincount(label, minlength=P)[:P]                   # (the lost points are counted for no label)
         t = int(np.argmax(count[:s]))                                 # (argmax: the first among equals)
         members = np.flatnonzero(label == t)
         n_t = len(members)
+        target[s - 1] = t
+        if n_t == 0:                                                  # everything has been lost: the step is not made
+            ok = False
+            continue
         best = None
         for k in range(K):
             row = members[_start_index(u_anchor[s - 1, k], n_t)]
-            plane, up = side(s - 1, k, p64[row], raw[members])
-            n_up = int(up.sum())
-            valid = n_up >= n_min and n_t - n_up >= n_min
-            if valid or best is None or min(n_up, n_t - n_up) > best[0]:
-                best = (min(n_up, n_t - n_up), k, plane, up, row)
+            plane, up, f = side(s - 1, k, p64[row], raw[members])
+            gone = np.zeros(n_t, dtype=bool)
+            if erode is not None:
+                w_up, w_dn, depth, rho = erode[s - 1]
+                d = p64[members] - p64[row]
+                r2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+                gone = ((f < w_up) & (f > -w_dn)) | ((f < depth) & (f > -depth) & (r2 < rho * rho))
+            n_up, n_dn = int((up & ~gone).sum()), int((~up & ~gone).sum())
+            valid = n_up >= n_min and n_dn >= n_min
+            if valid or best is None or min(n_up, n_dn) > best[0]:
+                best = (min(n_up, n_dn), k, plane, up, row, gone)
             if valid:
                 break
         else:
             ok = False
-        _, cand[s - 1], planes[s - 1], up, anchor[s - 1] = best
-        target[s - 1] = t
+        _, cand[s - 1], planes[s - 1], up, anchor[s - 1], gone = best
         label[members[~up]] = s
-    return label, planes, target, cand, anchor, ok
+        label[members[gone]] = FRACTURE_LOST
+        lost[s - 1] = gone.sum()
+    return label, planes, target, cand, anchor, lost, ok
 
 
 def fracture_curved_rule(raw, frames, half_curv, u_anchor, u_start, P, n_min, cap=None):
@@ -915,7 +968,75 @@ def fracture_curved_rule(raw, frames, half_curv, u_anchor, u_start, P, n_min, ca
        anchor [P-1] int32, the cloud row of the anchor taken at every step"""
     raw = np.asarray(raw, dtype=np.float32)
     frames, half_curv, u_anchor, u_start = (np.asarray(t, dtype=np.float64) for t in (frames, half_curv, u_anchor, u_start))
-    return _fracture_pieces(raw, _quadric_side(frames, half_curv), u_anchor, u_start, int(P), n_min, cap)
+    r = _fracture_pieces(raw, _quadric_side(frames, half_curv), u_anchor, u_start, int(P), n_min, cap)
+    del r["lost"]
+    return r
+
+
+FRACTURE_LOST = ops.FRACTURE_LOST                            # the label of a point lost along a cut
+
+
+def _eroded_side(who, normals, frames, half_curv):
+    """The side function of the eroded rules: _plane_side of normals, or _quadric_side of frames and half_curv with normals=None"""
+    if _curved(who, normals, frames, half_curv):
+        return _quadric_side(np.asarray(frames, dtype=np.float64), np.asarray(half_curv, dtype=np.float64))
+    return _plane_side(np.asarray(normals, dtype=np.float64))
+
+
+def fracture_eroded_rule(raw, normals, u_anchor, u_start, erode, P, n_min, cap=None, frames=None, half_curv=None):
+    """fracture_rule (normals) or fracture_curved_rule (frames and half_curv, with normals=None) with EROSION - at every cut the
+    target's points close to the taken surface are lost and belong to no piece: the statement that pzn_fracture_eroded_f32
+    (csrc/fracture.hip) implements and the tests hold it to, bit for bit.
+      erode  [P-1,4] float64 = (w_up, w_dn, depth, rho) per step, taken as given
+    For candidate k of step s through the anchor a, f is the value whose sign the side test takes (_value64 of the plane through
+    a, quadric_value), float64, every operation rounded on its own.  A member x of the target is LOST under that candidate iff
+      band: -w_dn < f < w_up, or
+      chip: -depth < f < depth and r2 < rho rho, with d = x - a (the float32 coordinates widened, three subtractions) and
+            r2 = (d0 d0 + d1 d1) + d2 d2 - at the anchor, the one point known to lie on the surface.
+    All comparisons are strict: zeros lose nothing, and neither does a NaN; with w_up > 0 and w_dn > 0 the anchor itself (f = 0) is lost.  Up is the
+    members with f >= 0 that are not lost, down those with f < 0 that are not lost.  A candidate is valid iff BOTH hold >= n_min
+    points after the loss, and its balance is the smaller of the two; the first valid candidate is taken, else the first most
+    balanced one; up keeps t, down becomes s, the lost points get label FRACTURE_LOST (255) and are never counted or targeted
+    again.  A step whose target holds no point (everything has been lost) is not made: its rows of planes, cand, anchor and lost
+    are zero, target is t, ok is False.  f is the offset along n to the surface, so across a cut the kept points of the two sides
+    are >= w_up + w_dn apart along n.
+    -> the dict of the rule of its form with anchor [P-1] int32 (for planes too: the chip's centre) and lost [P-1] int32 (the
+       points lost at every step); counts excludes the lost points (counts.sum() + lost.sum() == M) and order, the stable argsort
+       of label, holds the lost rows behind the last piece, in the cloud's order"""
+    raw = np.asarray(raw, dtype=np.float32)
+    u_anchor, u_start, erode = (np.asarray(t, dtype=np.float64) for t in (u_anchor, u_start, erode))
+    side = _eroded_side("fracture_eroded_rule", normals, frames, half_curv)
+    return _fracture_pieces(raw, side, u_anchor, u_start, int(P), n_min, cap, erode)
+
+
+def fracture_pair_eroded_rule(raw, normals, u_anchor, u, erode, pieces, P, n_min, neighbours, cap=None, frames=None, half_curv=None):
+    """fracture_pair_rule (normals) or fracture_pair_curved_rule (frames and half_curv, with normals=None) with the erosion of
+    fracture_eroded_rule (erode [P-1,4] float64; rows from P_b - 1 on are not read): the statement that
+    pzn_fracture_pair_eroded_f32 implements.  The pair is chosen as without erosion and its pieces are the eroded ones.
+    -> fracture_pair_rule's dict with anchor and lost [P-1] int32 (rows from P_b - 1 on are zero)"""
+    raw = np.asarray(raw, dtype=np.float32)
+    u_anchor, u, erode = (np.asarray(t, dtype=np.float64) for t in (u_anchor, u, erode))
+    side = _eroded_side("fracture_pair_eroded_rule", normals, frames, half_curv)
+    return _fracture_pair(raw, side, u_anchor, u, pieces, P, n_min, neighbours, cap, erode)
+
+
+def draw_erosion(rng, B, P, erosion, chip=(0.0, 0.0)):
+    """The erosion draws of a fracture batch -> erode [B,P-1,4] float64 = (w_up, w_dn, depth, rho) per step: one rng.rand(B, P-1, 4),
+    scaled to w_up, w_dn ~ U[0, erosion), depth ~ U[0, chip[0]), rho ~ U[0, chip[1])."""
+    return rng.rand(B, P - 1, 4) * np.array([erosion, erosion, chip[0], chip[1]], dtype=np.float64)
+
+
+def _erosion_args(who, erosion, chip):
+    """erosion and chip=(depth, radius) of the feeder and the tools: finite and >= 0 -> (erosion, (depth, radius), any of them > 0)"""
+    number = (int, float, np.integer, np.floating)
+    e = 0.0 if erosion is None else erosion
+    c = (0.0, 0.0) if chip is None else tuple(chip)
+    if not isinstance(e, number) or len(c) != 2 or not all(isinstance(v, number) for v in c) or \
+            not all(0.0 <= float(v) < np.inf for v in (e,) + c):
+        raise _lib.PznError(f"{who}: erosion={erosion!r}, chip={chip!r} (the widest band and the chip's (depth, radius): finite "
+                            f"and >= 0)")
+    e, c = float(e), (float(c[0]), float(c[1]))
+    return e, c, e > 0.0 or (c[0] > 0.0 and c[1] > 0.0)
 
 
 # A training pair cut out of a fracture, as the FEEDER samples it (PairFeeder(pieces=...)).
@@ -960,7 +1081,7 @@ def fracture_pair_rule(raw, normals, u_anchor, u, pieces, P, n_min, neighbours, 
     raw = np.asarray(raw, dtype=np.float32)
     normals, u_anchor, u = (np.asarray(t, dtype=np.float64) for t in (normals, u_anchor, u))
     r = _fracture_pair(raw, _plane_side(normals), u_anchor, u, pieces, P, n_min, neighbours, cap)
-    del r["anchor"]
+    del r["anchor"], r["lost"]
     return r
 
 
@@ -970,16 +1091,19 @@ def fracture_pair_curved_rule(raw, frames, half_curv, u_anchor, u, pieces, P, n_
     tangent planes, and with anchor [P-1] int32 (rows from P_b - 1 on are zero)"""
     raw = np.asarray(raw, dtype=np.float32)
     frames, half_curv, u_anchor, u = (np.asarray(t, dtype=np.float64) for t in (frames, half_curv, u_anchor, u))
-    return _fracture_pair(raw, _quadric_side(frames, half_curv), u_anchor, u, pieces, P, n_min, neighbours, cap)
+    r = _fracture_pair(raw, _quadric_side(frames, half_curv), u_anchor, u, pieces, P, n_min, neighbours, cap)
+    del r["lost"]
+    return r
 
 
-def _fracture_pair(raw, side, u_anchor, u, pieces, P, n_min, neighbours, cap):
-    """fracture_pair_rule / fracture_pair_curved_rule behind their argument conversions -> the rule's dict with anchor [P-1]"""
+def _fracture_pair(raw, side, u_anchor, u, pieces, P, n_min, neighbours, cap, erode=None):
+    """fracture_pair_rule / fracture_pair_curved_rule / fracture_pair_eroded_rule behind their argument conversions -> the rule's
+    dict with anchor and lost [P-1]"""
     M, P, Pb = raw.shape[0], int(P), int(pieces)
     if not 2 <= Pb <= P or not 0.0 <= neighbours <= 1.0 or u.shape != (7,):
         raise _lib.PznError(f"fracture_pair_rule: pieces = {Pb} of P = {P}, neighbours = {neighbours}, u {u.shape}")
     cap = M if cap is None else int(cap)
-    label, planes, target, cand, anchor, ok = _fracture_steps(raw, side, u_anchor, P, Pb - 1, n_min)
+    label, planes, target, cand, anchor, lost, ok = _fracture_steps(raw, side, u_anchor, P, Pb - 1, n_min, erode)
     sibling = (int(target[Pb - 2]), Pb - 1)
     kind, pair = SIBLING, sibling + (-1, -1)
     if Pb >= 3 and u[0] < neighbours:
@@ -992,7 +1116,7 @@ def _fracture_pair(raw, side, u_anchor, u, pieces, P, n_min, neighbours, cap):
     counts = np.array([-1 if r is None else len(r) for r in rows], dtype=np.int64)
     start = np.array([0 if cnt < 0 else _start_index(u[3 + i], cnt) for i, cnt in enumerate(counts)], dtype=np.int64)
     return dict(kind=kind, pair=np.array(pair, dtype=np.int32), pieces=[None if r is None else _pad_rows(r, cap, raw[0]) for r in rows],
-                counts=counts, start=start, label=label, planes=planes, target=target, cand=cand, anchor=anchor,
+                counts=counts, start=start, label=label, planes=planes, target=target, cand=cand, anchor=anchor, lost=lost,
                 ok=bool(ok and counts.max() <= cap))
 
 
@@ -1022,7 +1146,18 @@ def _curved(who, normals, frames, half_curv):
     return frames is not None
 
 
-def fracture(raw, normals, u_anchor, u_start, twist, n=1024, n_min=None, k=128, cap=None, frames=None, half_curv=None):
+ErodedFracture = collections.namedtuple("ErodedFracture", Fracture._fields + ("anchor", "erode", "lost"))
+ErodedFracture.__doc__ = """Fracture with material lost along every cut (datapipe.fracture(..., erode=)): the fields of Fracture, where label
+holds ops.FRACTURE_LOST (255) for the points that belong to no piece and counts excludes them, then anchor [B,P-1] int32 (the cloud
+row of the anchor taken at every step, the chip's centre), erode [B,P-1,4] float64 (the (w_up, w_dn, depth, rho) the cuts were made
+with) and lost [B,P-1] int32 (the points lost at every step): counts.sum(1) + lost.sum(1) == M."""
+
+ErodedCurvedFracture = collections.namedtuple("ErodedCurvedFracture", CurvedFracture._fields + ("erode", "lost"))
+ErodedCurvedFracture.__doc__ = """CurvedFracture with material lost along every cut: then erode and lost, as ErodedFracture holds them."""
+
+
+def fracture(raw, normals, u_anchor, u_start, twist, n=1024, n_min=None, k=128, cap=None, frames=None, half_curv=None,
+             erode=None):
     """A batch of P-piece samples with ground truth: every cloud cut into P pieces in one launch (ops.fracture, csrc/fracture.hip;
     the rule: fracture_rule), every piece sampled to n points and moved, and which pieces touch.  raw [B,M,3] f32 on the GPU;
     normals [B,P-1,K,3], u_anchor [B,P-1,K], u_start [B,P] float64 draws (draw_fracture_batch); twist [B,P,6]; n_min: points both
@@ -1038,7 +1173,12 @@ def fracture(raw, normals, u_anchor, u_start, twist, n=1024, n_min=None, k=128, 
       ok      the kernel's ok (a valid candidate at every step, every piece within cap) and every piece holds >= n points
     frames [B,P-1,K,3,3] and half_curv [B,P-1,K,2] float64 (draw_fracture_curved_batch), with normals=None: the cuts are curved
     (ops.fracture_curved; the rule: fracture_curved_rule) and a CurvedFracture comes back - the same fields, then anchor, frames,
-    half_curv."""
+    half_curv.
+    erode [B,P-1,4] float64 = (w_up, w_dn, depth, rho) per step (draw_erosion): material is lost along every cut, in the same one
+    launch (ops.fracture_eroded; the rule: fracture_eroded_rule), and the result is the one of its form extended by anchor (where
+    it lacks one), erode and lost: an ErodedFracture or ErodedCurvedFracture.  None is the call without erosion.  The lost points
+    are in no piece, so no `src` row names one; `cd` and `mates` are taken on the ERODED pieces: a gap g between two boundaries
+    adds about 2 g^2 to cd, which is held against the unchanged CD_ACCEPT = 0.015."""
     cap = _feeder_cap("fracture", raw, cap)
     curved = _curved("fracture", normals, frames, half_curv)
     n, k = int(n), int(k)
@@ -1046,7 +1186,10 @@ def fracture(raw, normals, u_anchor, u_start, twist, n=1024, n_min=None, k=128, 
     B, M, P = raw.shape[0], raw.shape[1], u_start.shape[-1]
     if not isinstance(twist, torch.Tensor) or not twist.is_cuda or tuple(twist.shape) != (B, P, 6):
         raise _lib.PznError(f"fracture: twist as [B, P, 6] = [{B}, {P}, 6] on the GPU; got {tuple(twist.shape)}")
-    if curved:
+    if erode is not None:
+        packed, counts, start, label, order, planes, target, cand, anchor, lost, ok = ops.fracture_eroded(
+            raw, normals, u_anchor, u_start, erode, n_min, cap, frames=frames, half_curv=half_curv)
+    elif curved:
         packed, counts, start, label, order, planes, target, cand, anchor, ok = ops.fracture_curved(raw, frames, half_curv, u_anchor,
                                                                                                      u_start, n_min, cap)
     else:
@@ -1069,6 +1212,8 @@ def fracture(raw, normals, u_anchor, u_start, twist, n=1024, n_min=None, k=128, 
     mates = (cd <= CD_ACCEPT) & ~torch.eye(P, dtype=torch.bool, device=raw.device)
     f = Fracture(moved, pose, rest, src, top.view(B, P, P, k), cd, mates, ok & (cnt >= n).all(0), label, planes, target, cand,
                  cnt.t().contiguous())
+    if erode is not None:
+        return ErodedCurvedFracture(*f, anchor, frames, half_curv, erode, lost) if curved else ErodedFracture(*f, anchor, erode, lost)
     return CurvedFracture(*f, anchor, frames, half_curv) if curved else f
 
 
@@ -1080,7 +1225,7 @@ cd [Z,K,K] float32 the fracture's inside an object and +inf across, ok [Z] bool 
 
 
 def pile(frac, objects, perm=None):
-    """Regroup a Fracture or CurvedFracture of B = Z Q samples into Z piles of the pieces of Q = `objects` objects each: pile z holds
+    """Regroup a Fracture of any form (curved, eroded) of B = Z Q samples into Z piles of the pieces of Q = `objects` objects each: pile z holds
     the K = Q P pieces of samples z Q .. z Q + Q - 1, piece p of object q in slot q P + p, then shuffled: position k of pile z
     holds slot perm[z,k] (perm [Z,K] int64, every row a permutation of 0 .. K-1, on the fracture's device; None: the identity),
     so the objects are no contiguous blocks.  -> Pile.  assembly.truth_table(pile.pose[z], pile.mates[z], pile.cd[z]) is the table
@@ -1179,16 +1324,22 @@ def fracture_curved_draws(rng, gen, B, P, K, mag, curvature):
             out[:, u_anchor].reshape(B, P - 1, K), out[:, u_start].copy(), out[:, tw].reshape(B, P, 6))
 
 
-def fracture_arguments(rng, gen, B, P, K, mag, curvature):
+def fracture_arguments(rng, gen, B, P, K, mag, curvature, erosion=0.0, chip=(0.0, 0.0)):
     """The host draws of a fracture batch as the keyword arguments of datapipe.fracture that follow `raw` (float64 numpy arrays):
     fracture_draws' for curvature 0 (planes), fracture_curved_draws' with normals=None above it.  What the tools' --curvature
-    does."""
+    does.  With an erosion or a chip = (depth, radius) above 0 (the tools' --erosion and --chip), `erode` as well: draw_erosion's,
+    drawn from rng after the other draws, which stay what they are without it."""
     if not 0.0 <= curvature < np.inf:
         raise _lib.PznError(f"fracture_arguments: curvature={curvature!r} (the largest principal curvature, finite and >= 0)")
+    erosion, chip, eroded = _erosion_args("fracture_arguments", erosion, chip)
     if curvature == 0:
-        return dict(zip(("normals", "u_anchor", "u_start", "twist"), fracture_draws(rng, gen, B, P, K, mag)))
-    names = ("frames", "half_curv", "u_anchor", "u_start", "twist")
-    return dict(zip(names, fracture_curved_draws(rng, gen, B, P, K, mag, curvature)), normals=None)
+        args = dict(zip(("normals", "u_anchor", "u_start", "twist"), fracture_draws(rng, gen, B, P, K, mag)))
+    else:
+        names = ("frames", "half_curv", "u_anchor", "u_start", "twist")
+        args = dict(zip(names, fracture_curved_draws(rng, gen, B, P, K, mag, curvature)), normals=None)
+    if eroded:
+        args["erode"] = draw_erosion(rng, B, P, erosion, chip)
+    return args
 
 
 def _fracture_pair_curved_cols(P, K):   # frames, half curvatures, anchor draws, the number of pieces, uniforms, twist
@@ -1206,13 +1357,13 @@ def draw_fracture_pair_curved_batch(rng, gen, B, lo, hi, K, mag, curvature, out)
     _draw_twist(gen, mag, out[:, tw])
 
 
-def _build_fracture_pair_curved(f, d):
+def _build_fracture_pair_curved(f, d, erode=None):
     B, K, P = d.shape[0], f.K, f.pieces[1]
     frames, half_curv, u_anchor, pc, u, tw = _fracture_pair_curved_cols(P, K)
     tensors, ok, record = cut_pairs_fracture(f.raw, None, d[:, u_anchor].reshape(B, P - 1, K), d[:, pc].reshape(B).to(torch.int32),
                                              d[:, u], d[:, tw], n=f.n, k=f.k, neighbours=f.neighbours,
                                              frames=d[:, frames].reshape(B, P - 1, K, 3, 3),
-                                             half_curv=d[:, half_curv].reshape(B, P - 1, K, 2))
+                                             half_curv=d[:, half_curv].reshape(B, P - 1, K, 2), erode=erode)
     return tensors, ok, dict(fracture=record)
 
 
@@ -1238,12 +1389,12 @@ def draw_fracture_pair_batch(rng, gen, B, lo, hi, K, mag, out):
     _draw_twist(gen, mag, out[:, tw])
 
 
-def _build_fracture_pair(f, d):
+def _build_fracture_pair(f, d, erode=None):
     B, K, P = d.shape[0], f.K, f.pieces[1]
     normals, u_anchor, pc, u, tw = _fracture_pair_cols(P, K)
     tensors, ok, record = cut_pairs_fracture(f.raw, d[:, normals].reshape(B, P - 1, K, 3), d[:, u_anchor].reshape(B, P - 1, K),
                                              d[:, pc].reshape(B).to(torch.int32), d[:, u], d[:, tw], n=f.n, k=f.k,
-                                             neighbours=f.neighbours)
+                                             neighbours=f.neighbours, erode=erode)
     return tensors, ok, dict(fracture=record)
 
 
@@ -1253,6 +1404,24 @@ def _fracture_pair_mode(lo, hi):
     return _FeederMode(lambda K: _fracture_pair_cols(hi, K),
                        lambda rng, gen, B, K, mag, out: draw_fracture_pair_batch(rng, gen, B, lo, hi, K, mag, out),
                        _build_fracture_pair)
+
+
+def _eroded_mode(mode, P, erosion, chip):
+    """The feeder mode of PairFeeder(pieces=(lo, P), erosion=, chip=): the fracture-pair mode `mode` (planes or surfaces) with
+    4 (P - 1) more staging columns behind its own, the erosion of every step, drawn by draw_erosion from rng after the mode's own
+    draws; its builder passes them on as `erode`."""
+    def cols(K):
+        own = mode.cols(K)
+        return own + [slice(own[-1].stop, own[-1].stop + 4 * (P - 1))]
+
+    def draw(rng, gen, B, K, mag, out):
+        mode.draw(rng, gen, B, K, mag, out)
+        out[:, cols(K)[-1]] = draw_erosion(rng, B, P, erosion, chip).reshape(B, 4 * (P - 1))
+
+    def build(f, d):
+        return mode.build(f, d, erode=d[:, cols(f.K)[-1]].reshape(d.shape[0], P - 1, 4))
+
+    return _FeederMode(cols, draw, build)
 
 
 def fracture_draws(rng, gen, B, P, K, mag):

@@ -1291,6 +1291,111 @@ def fracture_pair_curved(raw, frames, half_curv, u_anchor, pieces, u, n_min, nei
     return out, counts, start, kind, pair, label, planes, target, cand, anchor, ok.to(torch.bool)
 
 
+FRACTURE_LOST = 255                                 # the label of a point lost along an eroded cut (P <= 16 leaves it free)
+
+
+def fracture_eroded_supported(M, P, K):
+    return bool(_lib.load().pzn_fracture_eroded_supported(int(M), int(P), int(K)))
+
+
+def fracture_pair_eroded_supported(M, P, K):
+    return bool(_lib.load().pzn_fracture_pair_eroded_supported(int(M), int(P), int(K)))
+
+
+def _eroded_cut_args(who, supported, raw, normals, frames, half_curv, u_anchor, last, erode, cap, n_min):
+    """The argument checks of the two eroded fracture forms: those of their siblings without erosion - the plane forms' with
+    normals [B,P-1,K,3], _curved_cut_args' with frames and half_curv and normals=None - and erode float64 [B,P-1,4] on the GPU.
+    `last` as _curved_cut_args takes it.  -> (B, M, P, K, curved)"""
+    if (frames is None) != (half_curv is None) or (normals is None) == (frames is None):
+        raise _lib.PznError(f"{who}: normals (planes), or frames and half_curv with normals=None (surfaces)")
+    if frames is not None:
+        B, M, P, K = _curved_cut_args(who, supported, raw, frames, half_curv, u_anchor, last, cap, n_min)
+    else:
+        name, t, cols = last
+        for nm, x, dt in (("raw", raw, torch.float32), ("normals", normals, torch.float64), ("u_anchor", u_anchor, torch.float64),
+                          (name, t, torch.float64)):
+            if not isinstance(x, torch.Tensor) or not x.is_cuda:
+                raise _lib.PznError(f"{who}: {nm} must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
+            if x.dtype != dt:
+                raise _lib.PznError(f"{who}: {nm} must be {dt}; got {x.dtype}")
+        if raw.dim() != 3 or raw.shape[2] != 3 or raw.shape[0] == 0 or raw.shape[1] == 0:
+            raise _lib.PznError(f"{who}: raw as [B, M, 3]; got {tuple(raw.shape)}")
+        B, M, _ = raw.shape
+        if normals.dim() != 4 or normals.shape[0] != B or normals.shape[3] != 3:
+            raise _lib.PznError(f"{who}: normals as [B, P - 1, K, 3]; got {tuple(normals.shape)}")
+        P, K = normals.shape[1] + 1, normals.shape[2]
+        if not supported(M, P, max(K, 1)):
+            raise _lib.PznUnsupported(f"{who}: M = {M} points into P = {P} pieces (2 <= P <= 16, M <= 65536)")
+        cols = P if cols is None else cols
+        if K < 1 or tuple(u_anchor.shape) != (B, P - 1, K) or tuple(t.shape) != (B, cols):
+            raise _lib.PznError(f"{who}: u_anchor as [B, P - 1, K] with P = {P}, K >= 1, and {name} as [B, {cols}]; got "
+                                f"{tuple(u_anchor.shape)}, {tuple(t.shape)}")
+        if int(cap) < 1 or int(n_min) < 0:
+            raise _lib.PznError(f"{who}: cap = {cap}, n_min = {n_min}")
+    if not isinstance(erode, torch.Tensor) or not erode.is_cuda:
+        raise _lib.PznError(f"{who}: erode must be a tensor on the GPU; puzzlenet_amd has no CPU fallback")
+    if erode.dtype != torch.float64 or tuple(erode.shape) != (B, P - 1, 4):
+        raise _lib.PznError(f"{who}: erode as float64 [B, P - 1, 4] = (w_up, w_dn, depth, rho) per step; got {erode.dtype} "
+                            f"{tuple(erode.shape)}")
+    return B, M, P, K, frames is not None
+
+
+def fracture_eroded(raw, normals, u_anchor, u_start, erode, n_min, cap, frames=None, half_curv=None):
+    """ops.fracture (normals) or ops.fracture_curved (frames and half_curv, with normals=None) with EROSION, one launch
+    (pzn_fracture_eroded_f32; the rule: datapipe.fracture_eroded_rule): at every cut the target's points close to the taken
+    surface are lost - a band -w_dn < f < w_up and a chip -depth < f < depth within rho of the anchor, erode [B,P-1,4] float64 =
+    (w_up, w_dn, depth, rho) per step, taken as given - and get label FRACTURE_LOST, in no piece
+    -> (pieces, counts, start, label, order, planes, target, cand as the form without erosion returns them, counts without the
+        lost points and their rows behind the last piece in order; anchor [B,P-1] int32, the cloud row of the anchor taken, for
+        planes too; lost [B,P-1] int32, the points lost at every step; ok [B] bool)
+    2 <= P <= 16, K >= 1, M <= 65536 (PznUnsupported beyond).  Nothing waits for the device."""
+    B, M, P, K, curved = _eroded_cut_args("fracture_eroded", fracture_eroded_supported, raw, normals, frames, half_curv, u_anchor,
+                                          ("u_start", u_start, None), erode, cap, n_min)
+    cap, n_min = int(cap), int(n_min)
+    raw, u_anchor, u_start, erode = (t.contiguous() for t in (raw, u_anchor, u_start, erode))
+    cuts = (None, frames.contiguous(), half_curv.contiguous()) if curved else (normals.contiguous(), None, None)
+    dev = raw.device
+    pieces, counts, start, ok = _cut_outputs(raw, P, cap)
+    label = torch.empty((B, M), dtype=torch.uint8, device=dev)
+    order = torch.empty((B, M), dtype=torch.int32, device=dev)
+    planes = torch.empty((B, P - 1, 4), dtype=torch.float64, device=dev)
+    target, cand, anchor, lost = (torch.empty((B, P - 1), dtype=torch.int32, device=dev) for _ in range(4))
+    with _on(dev):
+        _call("pzn_fracture_eroded_f32", _p(raw), _p(cuts[0]), _p(cuts[1]), _p(cuts[2]), _p(u_anchor), _p(u_start), _p(erode), B, M,
+              P, K, n_min, cap, _p(pieces), _p(counts), _p(start), _p(label), _p(order), _p(planes), _p(target), _p(cand),
+              _p(anchor), _p(lost), _p(ok), _stream())
+    return pieces, counts, start, label, order, planes, target, cand, anchor, lost, ok.to(torch.bool)
+
+
+def fracture_pair_eroded(raw, normals, u_anchor, pieces, u, erode, n_min, neighbours, cap, frames=None, half_curv=None):
+    """ops.fracture_pair (normals) or ops.fracture_pair_curved (frames and half_curv, with normals=None) with the erosion of
+    ops.fracture_eroded, one launch (pzn_fracture_pair_eroded_f32; the rule: datapipe.fracture_pair_eroded_rule): erode [B,P-1,4]
+    float64; pieces, u, neighbours as ops.fracture_pair takes them
+    -> (pieces, counts, start, kind, pair, label, planes, target, cand as the form without erosion returns them, the pieces
+        without the lost points; anchor, lost [B,P-1] int32, zero where a step was not made; ok [B] bool)
+    2 <= P <= 16, K >= 1, M <= 65536 (PznUnsupported beyond)."""
+    B, M, P, K, curved = _eroded_cut_args("fracture_pair_eroded", fracture_pair_eroded_supported, raw, normals, frames, half_curv,
+                                          u_anchor, ("u", u, FRACTURE_PAIR_UNIFORMS), erode, cap, n_min)
+    cap, n_min, neighbours = int(cap), int(n_min), float(neighbours)
+    if not 0.0 <= neighbours <= 1.0:
+        raise _lib.PznError(f"fracture_pair_eroded: neighbours = {neighbours}")
+    dev = raw.device
+    pieces = _pair_pieces("fracture_pair_eroded", pieces, B, P, dev)
+    raw, u_anchor, pieces, u, erode = (t.contiguous() for t in (raw, u_anchor, pieces, u, erode))
+    cuts = (None, frames.contiguous(), half_curv.contiguous()) if curved else (normals.contiguous(), None, None)
+    out, counts, start, ok = _cut_outputs(raw, 4, cap)
+    kind = torch.empty((B,), dtype=torch.int32, device=dev)
+    pair = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    label = torch.empty((B, M), dtype=torch.uint8, device=dev)
+    planes = torch.empty((B, P - 1, 4), dtype=torch.float64, device=dev)
+    target, cand, anchor, lost = (torch.empty((B, P - 1), dtype=torch.int32, device=dev) for _ in range(4))
+    with _on(dev):
+        _call("pzn_fracture_pair_eroded_f32", _p(raw), _p(cuts[0]), _p(cuts[1]), _p(cuts[2]), _p(u_anchor), _p(pieces), _p(u),
+              _p(erode), neighbours, B, M, P, K, n_min, cap, _p(out), _p(counts), _p(start), _p(kind), _p(pair), _p(label),
+              _p(planes), _p(target), _p(cand), _p(anchor), _p(lost), _p(ok), _stream())
+    return out, counts, start, kind, pair, label, planes, target, cand, anchor, lost, ok.to(torch.bool)
+
+
 def pick_mask(idx, N):
     """0/1 float masks [R,N] with ones at idx [R,k] (dataset.py:1363-1366), one launch."""
     idx = _i64(idx, "idx")

@@ -35,7 +35,9 @@ forest walk - the beam walk inside every component, a piece charged by the votes
 charged --max-score -; everything after the walk is --forest's.
 --gt PREFIX_gt.npz (written by tools/fracture.py beside the pieces): the assembly is scored against the truth - per piece the
 rotation error in degrees, the translation error and the mean squared distance of its points from where they belong, the share
-of pieces placed right (assembly.evaluate) and, for the greedy walk, the share of its edges between pieces that touch.
+of pieces placed right (assembly.evaluate) and, for the greedy walk, the share of its edges between pieces that touch.  A truth
+cut with tools/fracture.py --erosion says so: the share of the cloud lost along the breaks is printed, and the poses are scored
+against the eroded pieces where they belong.
 Needs a GPU; there is no CPU path."""
 import argparse
 import os
@@ -185,6 +187,9 @@ def main():
     gt = np.load(args.gt) if args.gt else None
     if gt is not None and gt["pose"].shape != (K, 4, 4):
         sys.exit(f"{args.gt}: the truth of {gt['pose'].shape[0]} pieces, {args.pieces} holds {K}")
+    if gt is not None and "lost" in gt:
+        print(f"{args.gt}: an eroded fracture, {100.0 * gt['lost'].sum() / gt['label'].shape[0]:.1f} % of the cloud lost along the "
+              f"breaks, {int(gt['mates'].sum()) // 2} pairs of mates")
     if args.progressive:
         pa = assembly.ProgressiveAssembler(model, x, k=args.k, max_score=args.max_score, drop_matched=not args.keep_matched,
                                            generator=torch.Generator().manual_seed(args.seed), refine=args.refine)

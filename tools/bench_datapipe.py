@@ -3,7 +3,7 @@ to N, labelled and moved — next to the training step's consumption rate, and t
 piece on one host core (the dominant cost of the reference's per-sample CPU pipeline).
 
     python tools/bench_datapipe.py [--cut {plane,sphere,cylinder,cone}] [--random_slice] [--reps 30] [--fracture]
-                                   [--pieces P] [--curvature 2.0]
+                                   [--pieces P] [--curvature 2.0] [--erosion E [--chip DEPTH RADIUS]]
 
 Then the loader's batch as PairFeeder builds it, B = 64, M = 10000, N = 2048, 16 candidates: datapipe.cut_pairs (plane) and, with
 --cut a solid, datapipe.cut_pairs_solid of that kind next to the tensor form datapipe.make_pairs_solid on the same clouds with the
@@ -20,7 +20,13 @@ launches beside the plane batch's, each alone between two device events (profile
 --curvature C (with --fracture or --pieces; default 2.0, 0: planes only): the curved forms beside the plane forms on the same
 clouds, normals and anchors - the ops.fracture_curved launch and the whole curved datapipe.fracture call with --fracture, the
 ops.fracture_pair_curved launch and the curved cut_pairs_fracture batch with --pieces - and the ratios curved / plane
-(profiles/fracture_curved_batch.txt holds a run)."""
+(profiles/fracture_curved_batch.txt holds a run).
+--erosion E [--chip DEPTH RADIUS] (with --fracture or --pieces; default 0: off): only the eroded forms beside the forms without
+erosion, on the same clouds and draws, planes and (--curvature > 0) surfaces: with --fracture the ops.fracture_eroded launch and the
+launch of the same form without erosion, alternating, each alone between two device events, and what erosion does to the contact
+(valid samples, mates per sample, the lost share, with and without); with --pieces the ops.fracture_pair_eroded launch and the
+cut_pairs_fracture batch the same way.  Medians, ratios and contact figures go to profiles/fracture_eroded_batch.txt, one block per
+mode."""
 import argparse, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -32,6 +38,8 @@ ap.add_argument("--reps", type=int, default=30)
 ap.add_argument("--fracture", action="store_true")
 ap.add_argument("--pieces", type=int, default=0)
 ap.add_argument("--curvature", type=float, default=2.0)
+ap.add_argument("--erosion", type=float, default=0.0)
+ap.add_argument("--chip", type=float, nargs=2, default=(0.0, 0.0), metavar=("DEPTH", "RADIUS"))
 a = ap.parse_args()
 dev = torch.device('cuda:0')
 g = torch.Generator().manual_seed(0)
@@ -181,11 +189,134 @@ def bench_pieces(P, reps, curvature):
             med(times, "curved: cut_pairs_fracture (P = %d)" % P) / med(times, "fracture: cut_pairs_fracture (P = %d)" % P)), flush=True)
 
 
+def _events(launches, reps):
+    """Every launch alone between two device events, the launches alternating -> {name: sorted microseconds}"""
+    lt = {name: [] for name in launches}
+    for rep in range(reps + 3):                          # (three warm-up rounds of everything)
+        for name, fn in launches.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(); e0.record()
+            fn()
+            e1.record(); e1.synchronize()
+            if rep >= 3:
+                lt[name].append(e0.elapsed_time(e1) * 1e3)
+    return {name: np.sort(np.array(t)) for name, t in lt.items()}
+
+
+def _write_block(lines):
+    """Print a mode's block and put it into profiles/fracture_eroded_batch.txt in place of that mode's block of an earlier run"""
+    print('\n'.join(lines), flush=True)
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'fracture_eroded_batch.txt')
+    blocks = [b for b in (open(out).read().split('\n\n') if os.path.exists(out) else []) if b.strip()]
+    mode = lines[0].split(' --reps')[0]
+    blocks = [b.strip('\n') for b in blocks if not b.startswith(mode)] + ['\n'.join(lines)]
+    with open(out, 'w') as fh:
+        fh.write('\n\n'.join(sorted(blocks)) + '\n')
+
+
+def _forms(rng, twin, B, P, K, curvature):
+    """The plane draws and (curvature > 0) the curved ones on the same normals and anchors -> {form: keyword arguments of
+    datapipe.fracture behind raw, on the device}"""
+    up = lambda t: None if t is None else torch.from_numpy(np.ascontiguousarray(t)).to(dev)
+    forms = {"planes": {k: up(v) for k, v in datapipe.fracture_arguments(rng, torch.Generator().manual_seed(0), B, P, K, 0.8, 0.0).items()}}
+    if curvature > 0:
+        forms["surfaces"] = {k: up(v) for k, v in datapipe.fracture_arguments(twin, torch.Generator().manual_seed(0), B, P, K, 0.8, curvature).items()}
+    return forms
+
+
+def bench_fracture_eroded(reps, curvature, erosion, chip):
+    from puzzlenet_amd import ops
+    B, M, P, K, n, k = 64, 10000, 8, 16, 256, 64
+    rng = np.random.RandomState(0)
+    raw = torch.from_numpy((rng.rand(B, M, 3) - 0.5).astype(np.float32)).to(dev)
+    forms = _forms(rng, _again(rng), B, P, K, curvature)
+    erode = torch.from_numpy(datapipe.draw_erosion(rng, B, P, erosion, chip)).to(dev)
+    lines = ['tools/bench_datapipe.py --fracture --erosion %g --chip %g %g --reps %d: B = %d, M = %d, P = %d, K = %d, n_min = n = %d, k = %d (medians of %d)' % (
+        erosion, chip[0], chip[1], reps, B, M, P, K, n, k, reps)]
+    launches = {}
+    for name, d in forms.items():
+        for tag, kw in (("without erosion", {}), ("eroded", dict(erode=erode))):
+            f = datapipe.fracture(raw, n=n, k=k, **d, **kw)
+            lost = float(f.lost.sum()) / (B * M) if kw else 0.0
+            lines.append('contact, %-8s %-16s valid %d/%d, smallest piece %d, mates per sample %.2f, lost share %.3f' % (
+                name + ':', tag + ':', int(f.ok.sum()), B, int(f.counts.min()), float(f.mates.sum()) / 2 / B, lost))
+        cut = dict(frames=d["frames"], half_curv=d["half_curv"]) if d["normals"] is None else {}
+        if cut:
+            launches[name + ": ops.fracture_curved"] = lambda d=d: ops.fracture_curved(raw, d["frames"], d["half_curv"], d["u_anchor"], d["u_start"], n, M)
+        else:
+            launches[name + ": ops.fracture"] = lambda d=d: ops.fracture(raw, d["normals"], d["u_anchor"], d["u_start"], n, M)
+        launches[name + ": ops.fracture_eroded"] = lambda d=d, cut=cut: ops.fracture_eroded(raw, d["normals"], d["u_anchor"], d["u_start"], erode, n, M, **cut)
+    lt = _events(launches, reps)
+    for name, t in lt.items():
+        lines.append('launch: %-34s %.0f us between events (min %.0f, max %.0f)' % (name, np.median(t), t[0], t[-1]))
+    names = list(lt)
+    for plain, eroded in zip(names[0::2], names[1::2]):
+        lines.append('ratio eroded / without, %s: %.2f (one 64-bit sum in place of a 32-bit one per candidate, about ten more float64 operations per member, one more scan for `order`)' % (
+            plain.split(':')[0], np.median(lt[eroded]) / np.median(lt[plain])))
+    _write_block(lines)
+
+
+def bench_pieces_eroded(P, reps, curvature, erosion, chip):
+    from puzzlenet_amd import ops
+    B, M, N, K = 64, 10000, 2048, 16
+    rng = np.random.RandomState(0)
+    raw = torch.from_numpy((rng.rand(B, M, 3) - 0.5).astype(np.float32)).to(dev)
+    forms = _forms(rng, _again(rng), B, P, K, curvature)
+    up = lambda t: torch.from_numpy(np.ascontiguousarray(t)).to(dev)
+    pieces, u7 = torch.full((B,), P, dtype=torch.int32, device=dev), up(rng.rand(B, ops.FRACTURE_PAIR_UNIFORMS))
+    erode = up(datapipe.draw_erosion(rng, B, P, erosion, chip))
+    lines = ['tools/bench_datapipe.py --pieces %d --erosion %g --chip %g %g --reps %d: B = %d, M = %d, N = %d, K = %d, neighbours = 0.5 (medians of %d)' % (
+        P, erosion, chip[0], chip[1], reps, B, M, N, K, reps)]
+    launches, batches = {}, {}
+    for name, d in forms.items():
+        cut = dict(frames=d["frames"], half_curv=d["half_curv"]) if d["normals"] is None else {}
+        tw = d["twist"][:, 0].contiguous()
+        for tag, kw in (("without erosion", {}), ("eroded", dict(erode=erode))):
+            batch = lambda d=d, cut=cut, kw=kw, tw=tw: datapipe.cut_pairs_fracture(raw, d["normals"], d["u_anchor"], pieces, u7, tw, n=N, **cut, **kw)
+            _, ok, rec = batch()
+            lines.append('pairs, %-8s %-16s valid %d/%d, NEIGHBOUR %d, replaced by the sibling pair %d, lost share %.3f' % (
+                name + ':', tag + ':', int(ok.sum()), B, int((rec.kind == datapipe.NEIGHBOUR).sum()), int(rec.rejected.sum()),
+                float(rec.lost.sum()) / (B * M) if kw else 0.0))
+            batches['%s: cut_pairs_fracture, %s' % (name, tag)] = batch
+        if cut:
+            launches[name + ": ops.fracture_pair_curved"] = lambda d=d: ops.fracture_pair_curved(raw, d["frames"], d["half_curv"], d["u_anchor"], pieces, u7, N, 0.5, M)
+        else:
+            launches[name + ": ops.fracture_pair"] = lambda d=d: ops.fracture_pair(raw, d["normals"], d["u_anchor"], pieces, u7, N, 0.5, M)
+        launches[name + ": ops.fracture_pair_eroded"] = lambda d=d, cut=cut: ops.fracture_pair_eroded(raw, d["normals"], d["u_anchor"], pieces, u7, erode, N, 0.5, M, **cut)
+    times = {name: [] for name in batches}
+    for rep in range(reps + 3):                          # (three warm-up rounds of everything; the forms alternate)
+        for name, fn in batches.items():
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if rep >= 3:
+                times[name].append((time.perf_counter() - t0) * 1e3)
+    lt = _events(launches, reps)
+    for name, t in times.items():
+        t = np.sort(np.array(t))
+        lines.append('%-50s %.2f ms per batch on the host clock (min %.2f, max %.2f)' % (name, np.median(t), t[0], t[-1]))
+    for name, t in lt.items():
+        lines.append('launch: %-40s %.0f us between events (min %.0f, max %.0f)' % (name, np.median(t), t[0], t[-1]))
+    names, bnames = list(lt), list(times)
+    for i in range(0, len(names), 2):
+        lines.append('ratio eroded / without, %s: launch %.2f, batch %.2f' % (
+            names[i].split(':')[0], np.median(lt[names[i + 1]]) / np.median(lt[names[i]]), np.median(times[bnames[i + 1]]) / np.median(times[bnames[i]])))
+    _write_block(lines)
+
+
+if (a.erosion or any(a.chip)) and not (a.fracture or a.pieces):
+    sys.exit("--erosion / --chip: with --fracture or --pieces (only a fracture has breaks to erode)")
 if a.fracture:
-    bench_fracture(a.reps, a.curvature)
+    if a.erosion or any(a.chip):
+        bench_fracture_eroded(a.reps, a.curvature, a.erosion, tuple(a.chip))
+    else:
+        bench_fracture(a.reps, a.curvature)
     sys.exit(0)
 if a.pieces:
-    bench_pieces(a.pieces, a.reps, a.curvature)
+    if a.erosion or any(a.chip):
+        bench_pieces_eroded(a.pieces, a.reps, a.curvature, a.erosion, tuple(a.chip))
+    else:
+        bench_pieces(a.pieces, a.reps, a.curvature)
     sys.exit(0)
 for (B, M, N) in [(64, 6000, 1024), (64, 10000, 2048), (64, 12000, 2048)]:
     raw = (torch.rand(B, M, 3, generator=g) - 0.5).to(dev)

@@ -1,12 +1,14 @@
 """The assembly score of a model as a mean over a batch of fractured puzzles, with one download at the end:
 
     python tools/eval_assembly.py [--batch 64] [--pieces 8] [--m 20000] [--k 128] [--candidates 16] [--mag 0.8] [--seed 0]
-                                  [--curvature 2.0] [--ckpt model.ckpt] [--refine N] [--keep F|auto] [--joint N] [--joint-keep F|table] [--joint-auto [LEAST]] [--max-score S]
+                                  [--curvature 2.0] [--erosion E [--chip DEPTH RADIUS]] [--ckpt model.ckpt] [--refine N] [--keep F|auto] [--joint N] [--joint-keep F|table] [--joint-auto [LEAST]] [--max-score S]
                                   [--progressive] [--time R] [--json out.json] [--beam B] [--branch C] [--vote-weight W]
                                   [--objects Q]
 
 B seeded uniform clouds of M points are each cut into P pieces that belong together (datapipe.fracture, along curved surfaces
-with principal curvatures up to --curvature, along planes with --curvature 0; every piece sampled to
+with principal curvatures up to --curvature, along planes with --curvature 0; with --erosion E [--chip DEPTH RADIUS] material is
+lost along every break, a band of up to E on either side and a chip of up to DEPTH within RADIUS of the anchor
+(datapipe.fracture(..., erode=)), so the pieces no longer mate perfectly, and the lost share is printed; every piece sampled to
 the model's N points and moved by its own pose), then the chain of puzzlenet_amd.assembly runs on the whole batch on the device:
 match_puzzles (every piece encoded once, the encoders on full batches; --refine N: every pair pose refined on its picked
 boundaries by at most N ICP steps), assemble_batch (the greedy walk and the joint list of all puzzles, one launch), with --joint N
@@ -151,6 +153,9 @@ def main():
     ap.add_argument("--n", type=int, default=1024, help="points per piece (the model's)")
     ap.add_argument("--k", type=int, default=128, help="boundary points picked per piece and pair")
     ap.add_argument("--candidates", type=int, default=16, help="candidate surfaces per cut")
+    ap.add_argument("--erosion", type=float, default=0.0, help="widest band lost on either side of a break (0: nothing is lost)")
+    ap.add_argument("--chip", type=float, nargs=2, default=(0.0, 0.0), metavar=("DEPTH", "RADIUS"),
+                    help="deepest and widest chip lost around the point a break goes through")
     ap.add_argument("--curvature", type=float, default=2.0,
                     help="largest principal curvature of a break surface (2.0: a sphere of radius 0.5; 0: planes)")
     ap.add_argument("--mag", type=float, default=0.8, help="magnitude of every piece's twist")
@@ -215,10 +220,17 @@ def main():
     raw = (rng.rand(B, M, 3) - 0.5).astype(np.float32)
     if not 0.0 <= args.curvature < float("inf"):
         sys.exit(f"--curvature {args.curvature}: finite and >= 0")
-    draws = datapipe.fracture_arguments(rng, torch.Generator().manual_seed(args.seed), B, P, args.candidates, args.mag, args.curvature)
+    try:
+        draws = datapipe.fracture_arguments(rng, torch.Generator().manual_seed(args.seed), B, P, args.candidates, args.mag,
+                                            args.curvature, args.erosion, tuple(args.chip))
+    except datapipe._lib.PznError as e:
+        sys.exit(f"--erosion {args.erosion} --chip {args.chip[0]} {args.chip[1]}: {e}")
     to = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(dev)
     with torch.no_grad():
         f = datapipe.fracture(to(raw), n=N, k=args.k, cap=min(M, 32768), **{name: to(d) for name, d in draws.items()})
+        if "erode" in draws:
+            print(f"erosion {args.erosion}, chip {tuple(args.chip)}: {100.0 * float(f.lost.sum()) / (B * M):.1f} % of the points lost along "
+                  f"the breaks, {float(f.mates.sum()) / 2 / B:.1f} mates per puzzle")
         if args.objects > 1:
             return sort_piles(args, model, f, dev)
         # the FPS starts of the table, drawn as match_puzzles draws them, so that the progressive walk can start from the same ones

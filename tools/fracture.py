@@ -2,7 +2,7 @@
 --gt scores against (puzzlenet_amd.datapipe.fracture, one launch of csrc/fracture.hip for the cut).
 
     python tools/fracture.py [--cloud cloud.npy] [--pieces 8] [--n 1024] [--k 128] [--candidates 16] [--curvature 2.0] [--mag 0.8]
-                             [--seed 0] [--out PREFIX]
+                             [--erosion E [--chip DEPTH RADIUS]] [--seed 0] [--out PREFIX]
 
 cloud.npy holds [M, 3] float32 (M <= 65536; a piece may hold at most 32768 points); without it a seeded uniform cloud of --m
 points in [-0.5, 0.5)^3 is cut.  Writes PREFIX_pieces.npy ([P, n, 3] float32: every piece sampled to n points and moved by a
@@ -13,6 +13,11 @@ The break surfaces are curved: paraboloids through a point of the piece they cut
 [-C, C] for --curvature C (2.0: the curvature of a sphere of radius 0.5); planes then holds the tangent planes there, and
 PREFIX_gt.npz also anchor [P-1] (the cloud row each surface goes through), frame [P-1,3,3] (rows e1, e2, n) and half_curv [P-1,2]
 of the surface taken at every cut.  --curvature 0 cuts with planes.
+--erosion E (default 0: off): material is lost along every break - per cut a band of the piece's points within U[0, E) above
+and U[0, E) below the surface, and with --chip DEPTH RADIUS a chip of depth U[0, DEPTH) within U[0, RADIUS) of the point the
+surface goes through (datapipe.fracture_eroded_rule).  The lost points belong to no piece (label 255); the lost share and the
+mates are printed, and PREFIX_gt.npz also holds anchor [P-1], erode [P-1,4] = (w_up, w_dn, depth, rho) and lost [P-1].  cd and
+mates are taken on the eroded pieces against the unchanged 0.015.
 Needs a GPU; there is no CPU path."""
 import argparse
 import os
@@ -35,6 +40,9 @@ def main():
     ap.add_argument("--candidates", type=int, default=16, help="candidate planes per cut")
     ap.add_argument("--curvature", type=float, default=2.0,
                     help="largest principal curvature of a break surface (0: planes)")
+    ap.add_argument("--erosion", type=float, default=0.0, help="widest band lost on either side of a break (0: nothing is lost)")
+    ap.add_argument("--chip", type=float, nargs=2, default=(0.0, 0.0), metavar=("DEPTH", "RADIUS"),
+                    help="deepest and widest chip lost around the point a break goes through")
     ap.add_argument("--mag", type=float, default=0.8, help="magnitude of every piece's twist")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default="fracture", help="prefix of the two files written")
@@ -55,7 +63,11 @@ def main():
     if not 0.0 <= args.curvature < float("inf"):
         sys.exit(f"--curvature {args.curvature}: finite and >= 0")
     to = lambda x: None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-    draws = datapipe.fracture_arguments(rng, torch.Generator().manual_seed(args.seed), 1, P, args.candidates, args.mag, args.curvature)
+    try:
+        draws = datapipe.fracture_arguments(rng, torch.Generator().manual_seed(args.seed), 1, P, args.candidates, args.mag,
+                                            args.curvature, args.erosion, tuple(args.chip))
+    except datapipe._lib.PznError as e:
+        sys.exit(f"--erosion {args.erosion} --chip {args.chip[0]} {args.chip[1]}: {e}")
     f = datapipe.fracture(to(cloud[None]), n=args.n, n_min=args.n_min, k=args.k, cap=min(M, 32768),
                           **{name: to(d) for name, d in draws.items()})
     counts = f.counts[0].tolist()
@@ -68,12 +80,17 @@ def main():
         print("cd[a, b] of the boundaries:")
         print(cd)
     print("mates:", [(a, b) for a in range(P) for b in range(a + 1, P) if mates[a, b]])
+    print(f"mates per sample: {int(mates.sum()) // 2}")
     np.save(args.out + "_pieces.npy", f.pieces[0].cpu().numpy())
     surfaces = {}
     if args.curvature > 0:
         taken = f.cand[0].cpu().numpy()
         surfaces = dict(anchor=f.anchor[0].cpu().numpy(), frame=draws["frames"][0, np.arange(P - 1), taken],
                         half_curv=draws["half_curv"][0, np.arange(P - 1), taken])
+    if "erode" in draws:
+        lost = f.lost[0].cpu().numpy()
+        print(f"lost along the breaks: {int(lost.sum())} of {M} points ({100.0 * lost.sum() / M:.1f} %), per cut {lost.tolist()}")
+        surfaces.update(anchor=f.anchor[0].cpu().numpy(), erode=draws["erode"][0], lost=lost)
     np.savez(args.out + "_gt.npz", pose=f.pose[0].cpu().numpy(), rest=f.rest[0].cpu().numpy(), label=f.label[0].cpu().numpy(),
              src=f.src[0].cpu().numpy(), mates=mates, cd=cd, planes=f.planes[0].cpu().numpy(), **surfaces)
     print(f"wrote {args.out}_pieces.npy, {args.out}_gt.npz")

@@ -3,7 +3,8 @@ labels, random motion on a background stream: the reference's loader processes, 
 :98-105) -> engine.TrainStep, a fresh batch every step, nothing synchronises.
 
     python tools/train_from_raw.py [--batch 64] [--points 2048] [--raw 10000] [--steps 20] [--cut {plane,sphere,cylinder,cone}]
-                                     [--random_slice] [--pieces P [--pieces_min L] [--neighbours q] [--curvature C]]
+                                     [--random_slice] [--pieces P [--pieces_min L] [--neighbours q] [--curvature C]
+                                     [--erosion E [--chip DEPTH RADIUS]]]
 
 --cut sphere | cylinder | cone: the reference's mesh cuts (dataset.py:715-759; "bed_sphere" is its documented training
 command) in place of the plane.  The cone (apex and base one unit from the origin) holds every point within 0.447 of the
@@ -14,6 +15,9 @@ the plane only.
 them drawn among all final pieces (PairFeeder(pieces=(L, P), neighbours=q)); with the plane only, without --random_slice.
 --curvature C (with --pieces; default 2.0, the curvature of the reference's radius-0.5 sphere): the fractures break along curved
 surfaces with principal curvatures in [-C, C] (PairFeeder(..., curvature=C)); 0: along planes.
+--erosion E [--chip DEPTH RADIUS] (with --pieces; default 0: off): material is lost along every break of the fractures, a band of up
+to E on either side and a chip of up to DEPTH within RADIUS of the anchor (PairFeeder(..., erosion=E, chip=(DEPTH, RADIUS))), so
+the training pairs no longer mate perfectly.
 """
 import argparse, os, sys, time
 import numpy as np, torch
@@ -32,9 +36,12 @@ ap.add_argument("--pieces", type=int, default=0)
 ap.add_argument("--pieces_min", type=int, default=0)
 ap.add_argument("--neighbours", type=float, default=0.5)
 ap.add_argument("--curvature", type=float, default=2.0)
+ap.add_argument("--erosion", type=float, default=0.0)
+ap.add_argument("--chip", type=float, nargs=2, default=None, metavar=("DEPTH", "RADIUS"))
 a = ap.parse_args()
 pieces = None if not a.pieces else (a.pieces_min or a.pieces, a.pieces)
 curvature = a.curvature if pieces else None      # (the feeder refuses a curvature without pieces: the other cuts have none)
+erosion = dict(erosion=a.erosion, chip=a.chip) if a.erosion or a.chip else {}      # (and an erosion: only a fracture has breaks)
 dev = torch.device("cuda:0")
 B, N, M = a.batch, a.points, a.raw
 rng = np.random.RandomState(0)
@@ -47,7 +54,7 @@ cfg = Cfg(); cfg.num_points = N
 torch.manual_seed(0)
 model = model5_b.TouchedRegraster(cfg).to(dev)
 feeder = datapipe.PairFeeder(raw, dev, n=N, seed=0, cut=a.cut, split_twice=a.random_slice, pieces=pieces, neighbours=a.neighbours,
-                             curvature=curvature)
+                             curvature=curvature, **erosion)
 runner = engine.TrainStep(model, feeder.next_batch(), cfg.lr, world=1)
 nxt = feeder.next_batch()
 losses, mem, oks, doubles, fractures = [], [], [nxt.ok], [nxt.double], [nxt.fracture]
